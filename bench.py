@@ -15,7 +15,17 @@ N > 1 : weak scaling, 54^3 cells per GPU on a Cartesian partition of the box,
         local apply (common/LinearGLL.hpp:164-176) through VectorUpdater.
 value = global owned dofs / (seconds per step)  -- the reference's definition
         index_map->size_local()/t (demo/gpu_operator/main.cpp:171) summed over ranks.
-Inputs are resident in HBM before the timed region starts."""
+Inputs are resident in HBM before the timed region starts.
+
+A plain run measures only that: set-up, --settle-steps + W untimed steps, K timed steps, the
+result line.  --full adds everything else the benchmark reports: the same W + K measurement from
+idle (`from_idle`), HIP events around the stiffness apply in every timed step (`roofline`) and the
+CPU baseline (`cpu_baseline`, unless --no-cpu-baseline).
+--dump-outputs DIR writes, after the timed steps, the vectors the step hands its caller as float64
+DIR/y.npy (y, accumulated over every step run) and DIR/kv.npy (y / m); DIR/<name>_rank<r>.npy for
+N > 1.  A vector longer than its share of DUMP_BUDGET_BYTES is written as a fixed sample: the
+positions of np.random.default_rng(0).choice(len, share, replace=False), sorted.  The input x and
+the step count are fixed by the arguments, so two runs with the same arguments compare entry for entry."""
 from __future__ import annotations
 
 import argparse
@@ -29,6 +39,24 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0     # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int, world: int) -> None:
+    """Write each device vector of `arrays` as float64 out_dir/<name>.npy (see the module docstring)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (8 * len(arrays) * world)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > share:
+            idx = np.sort(np.random.default_rng(0).choice(n, share, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.cpu().numpy().astype(np.float64))
 
 
 def cpu_baseline(sample_n: int, p: int, reps: int = 5):
@@ -79,7 +107,11 @@ def main():
     ap.add_argument("--size", type=int, default=54, help="cells per edge per GPU (reference flag --size)")
     ap.add_argument("--degree", type=int, default=4, help="element degree (reference flag --degree)")
     ap.add_argument("--generic", action="store_true", help="use the arbitrary-dofmap kernel instead of the box kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure from idle, time the stiffness apply with HIP "
+                    "events (roofline) and run the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's y and kv as "
+                    "float64 DIR/<name>.npy (a fixed sample of each, 48 MiB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--variant", type=int, default=-1, help="tuning: compiled cross-section of the one-thread-per-column "
                     "marching kernel (0..2); default: the library's choice")
     ap.add_argument("--block", default="", help="tuning: column cross-section bx,by of the k-split marching kernel")
@@ -87,8 +119,8 @@ def main():
     ap.add_argument("--settle-steps", type=int, default=1000, help="untimed steps run before the W warmup steps so that the "
                     "timed region sees the GPU at its sustained operating point: the first ~60 launches after idle run "
                     "up to 25 %% slower while board power ramps from 300 W to 1.2 kW (profiles/r03_power_ramp.md); the "
-                    "reference's RK4 loop runs thousands of steps.  0 = time from idle; the from-idle figure is reported "
-                    "beside the sustained one either way")
+                    "reference's RK4 loop runs thousands of steps.  0 = time from idle; with --full the from-idle figure "
+                    "is reported beside the sustained one either way")
     ap.add_argument("--periodic", default="", help="axes (e.g. xyz) whose opposite faces are identified: every rank "
                     "then has ghost planes on those axes and exchanges them over RCCL -- with one rank, with itself "
                     "(rehearses the multi-GPU exchange + overlap path on one GPU; not the headline configuration)")
@@ -232,11 +264,13 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed_region():
-        """W untimed warmup steps, then exactly K timed steps between barrier + synchronize; max over ranks."""
+    def timed_region(timed_kernel):
+        """W untimed warmup steps, then exactly K timed steps between barrier + synchronize; max over ranks.
+        timed_kernel: also bracket the stiffness apply of every timed step with HIP events."""
         for _ in range(args.warmup):
             step()
-        events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+        events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if timed_kernel else None
+                  for _ in range(args.steps)]
         sync()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -247,22 +281,40 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if not timed_kernel:
+            return dt, None
         # average duration of the dominant kernel (stiffness) from HIP events on its stream
         return dt, float(np.mean([a.elapsed_time(b) for a, b in events]))
 
     from_idle = None
     if args.settle_steps > 0:
-        # the same W + K measurement straight after set-up (GPU idle, board power ~300 W): reported, not `value`
-        idle_elapsed, idle_kern = timed_region()
-        from_idle = {"ms_per_step": idle_elapsed / args.steps * 1e3, "kernel_ms": idle_kern,
-                     "value": owned_global / (idle_elapsed / args.steps)}
+        if args.full:
+            # the same W + K measurement straight after set-up (GPU idle, board power ~300 W): reported, not `value`
+            idle_elapsed, idle_kern = timed_region(True)
+            from_idle = {"ms_per_step": idle_elapsed / args.steps * 1e3, "kernel_ms": idle_kern,
+                         "value": owned_global / (idle_elapsed / args.steps)}
         for _ in range(args.settle_steps):
             step()
-    elapsed, kern_ms = timed_region()
+    elapsed, kern_ms = timed_region(args.full)
     assert bool(torch.isfinite(kv).all()), "non-finite result"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": y, "kv": kv}, rank, world)
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
+        out = {
+            "metric": "dofs/sec stiffness-operator apply, P4 hex box mesh",
+            "value": owned_global / (elapsed / args.steps),
+            "unit": "dofs/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+            "settle_steps": args.settle_steps,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": workload, "degree": p, "cells_per_gpu": int(mesh.ncells),
+                       "global_dofs": int(owned_global), "parallelism": parallelism,
+                       "kernel": "generic" if args.generic else "box"},
+        }
+    if rank == 0 and args.full:
         alg = K.alg_bytes()
         # N > 1: the event pair brackets the whole overlapped apply (interior + interface + both halos)
         achieved = alg / (kern_ms * 1e-3) / 1e9
@@ -288,31 +340,21 @@ def main():
                     traffic_note = f"profiles/traffic.json was measured on library build {tj.get('lib_sha16')}, this is {sha}: not quoted"
             except Exception:
                 traffic = None
-        out = {
-            "metric": "dofs/sec stiffness-operator apply, P4 hex box mesh",
-            "value": owned_global / (elapsed / args.steps),
-            "unit": "dofs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-            "settle_steps": args.settle_steps, "from_idle": from_idle,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": workload, "degree": p, "cells_per_gpu": int(mesh.ncells),
-                       "global_dofs": int(owned_global), "parallelism": parallelism,
-                       "kernel": "generic" if args.generic else "box"},
-            "roofline": {"bound": "hbm", "kernel": "stiffness apply", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_source": traffic_note,
-                         "alg_bytes_per_launch": alg, "kernel_ms": kern_ms,
-                         "must_move_bytes_per_launch": must_move,
-                         "frac_must_move": must_move / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "stiffness_only_dofs_per_s": V.ndofs / (kern_ms * 1e-3)},
-        }
+        out["from_idle"] = from_idle
+        out["roofline"] = {"bound": "hbm", "kernel": "stiffness apply", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                           "traffic_source": traffic_note,
+                           "alg_bytes_per_launch": alg, "kernel_ms": kern_ms,
+                           "must_move_bytes_per_launch": must_move,
+                           "frac_must_move": must_move / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "stiffness_only_dofs_per_s": V.ndofs / (kern_ms * 1e-3)}
         if not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_sample, p)
             except Exception as e:  # the baseline is reported, never required for the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "dofs/s", "cores": 0, "kind": "port",
                                        "sample": f"failed: {e}"}
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1:

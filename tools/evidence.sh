@@ -16,11 +16,11 @@ pmc() {    # pmc <name> "<counters>" <program args...>
   rocprofv3 --pmc $2 --kernel-trace --output-format csv -d "$OUT/$1" -- python3 "${@:3}" > "$OUT/$1.log" 2>&1 || echo "pmc $1 failed" >> "$OUT/errors.log"
 }
 say "bench line (with cpu baseline)"
-python3 "$R/bench.py" > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
-python3 "$R/bench.py" --generic --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/bench_generic.json"
-python3 "$R/bench.py" --no-cpu-baseline --periodic x 2>/dev/null | tail -1 > "$OUT/bench_periodic_x.json"
-python3 "$R/bench.py" --no-cpu-baseline --periodic xyz 2>/dev/null | tail -1 > "$OUT/bench_periodic_xyz.json"
-python3 "$R/bench.py" --no-cpu-baseline --generic --periodic xyz 2>/dev/null | tail -1 > "$OUT/bench_generic_periodic_xyz.json"
+python3 "$R/bench.py" --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
+python3 "$R/bench.py" --full --generic --no-cpu-baseline 2>/dev/null | tail -1 > "$OUT/bench_generic.json"
+python3 "$R/bench.py" --full --no-cpu-baseline --periodic x 2>/dev/null | tail -1 > "$OUT/bench_periodic_x.json"
+python3 "$R/bench.py" --full --no-cpu-baseline --periodic xyz 2>/dev/null | tail -1 > "$OUT/bench_periodic_xyz.json"
+python3 "$R/bench.py" --full --no-cpu-baseline --generic --periodic xyz 2>/dev/null | tail -1 > "$OUT/bench_generic_periodic_xyz.json"
 say "kernel trace of bench.py (box and generic)"
 prof kt_box "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline
 prof kt_generic "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --generic
