@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iomanip>
 #include <iostream>
 #include <memory>
 
@@ -103,8 +104,8 @@ int main(int argc, char* argv[])
         if (std::abs(h1[i] - h[i]) > 1e-8) ++bad;
       }
       std::cout << "Y norm: " << std::sqrt(n1) << std::endl;
-      std::cout << "check: sum(y) = " << s << "  sum(lumped) = " << s1 << "  entries differing by > 1e-8: " << bad
-                << std::endl;
+      std::cout << std::setprecision(17) << "check: sum(y) = " << s << "  sum(lumped) = " << s1
+                << std::setprecision(6) << "  entries differing by > 1e-8: " << bad << std::endl;
     }
     // warm repetitions
     wavehip::check(wf_sync(nullptr));

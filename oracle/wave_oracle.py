@@ -454,15 +454,17 @@ def tabulate_mass_tables(p: int, variant: str, quad: str, qdegree: int):
     """Tables for the GPU MassOperator demos.
       variant 'gll'        : GLL-warped Lagrange (demo/gpu_operator_monolithic/main.cpp:69-71)
       variant 'equispaced' : equispaced Lagrange (demo/gpu_operator/main.cpp:66-68)
-      quad 'gll'           : m-point GLL rule; the demo's qdegree = degree+1 (>1)
-                             selects the (p+1)-point rule (monolithic main.cpp:94-96)
+      quad 'gll'           : Basix's GLL rule of degree qdegree, max(2, (qdegree+4)//2)
+                             points (wf_quadrature_1d).  The monolithic demo's
+                             qdegree = degree+1 (main.cpp:94-96) gives P+1 points up to
+                             P3 but fewer from P4 on (4, 5, 5, 6 points at P4..P7)
       quad 'gauss_jacobi'  : Gauss-Legendre with ceil((qdegree+1)/2) points
                              (demo/gpu_operator/main.cpp:96-99, qdegree = 2*degree)
     Returns 1-D (pts, wts, phi1[nq1][n1]) and the dense 3-D phi[nq][nd], X, W."""
     n = p + 1
     nodes = gll_points_weights(n)[0] if variant == "gll" else np.linspace(0.0, 1.0, n)
     if quad == "gll":
-        m = n if p > 1 else 2
+        m = max(2, (qdegree + 4) // 2)
         pts, wts = gll_points_weights(m)
     else:
         m = (qdegree + 2) // 2

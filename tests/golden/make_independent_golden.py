@@ -24,6 +24,13 @@ digits, then rounded once to float64:
     phi_i are tensor products of the symbolic 1-D Lagrange polynomials; J comes from
     symbolic differentiation of the trilinear map.
 The -1/0/1 clamps of the reference are inactive on this mesh (asserted below).
+  * On the same meshes, y = M x for the dense mass Phi^T diag(det J w) Phi with a
+    tensor rule whose point count differs from P+1 (common/cuda/mass.hpp:18-107):
+    Gauss-Legendre with P+2 points, which integrates phi_i phi_j det J exactly (det J
+    of a trilinear map has degree <= 2 in each reference variable), so y is the true
+    mass matrix of the displaced mesh; and Basix' GLL rule of degree P+1 (fewer
+    points than nodes from P4 on), whose value depends on the rule.  Evaluated
+    entirely in mpmath, sum-factorised, det J from the trilinear map.
 
 Output: tests/golden/independent.json (floats as repr strings, exact round trip).
 Run: python tests/golden/make_independent_golden.py      (about a minute)"""
@@ -206,6 +213,70 @@ def operators_on_mesh(p, n, c0):
     return {"p": p, "n": list(n), "c0": c0, "verts": verts, "x": rng_x, "Kx": Kx, "m": m, "mG1": mG[1], "mG2": mG[2]}
 
 
+def dense_mass_on_mesh(p, n, variant, quad, nq1):
+    """y = Phi^T diag(det J w) Phi x on the displaced mesh, all in mpmath: 1-D table of the
+    Lagrange basis (GLL or equispaced nodes) at the nq1-point rule, det J of the trilinear map
+    at the rule's points, three 1-D contractions forward and three back per cell."""
+    pts, wts = gauss_rule(nq1) if quad == "gauss_jacobi" else gll_rule(nq1)
+    nodes = gll_rule(p + 1)[0] if variant == "gll_warped" else [mp.mpf(a) / p for a in range(p + 1)]
+    phi = lagrange_table(nodes, pts, 0)                 # [q][a]
+    nn, m = p + 1, nq1
+    verts = to_f(displaced_vertices(n))     # the float64 mesh the tests build, taken exactly
+    nx, ny, nz = n
+    NX, NY, NZ = p * nx + 1, p * ny + 1, p * nz + 1
+    ndofs = NX * NY * NZ
+    x = np.array([np.sin(0.41 * g + 0.23) + 0.5 * np.cos(0.9 * g) for g in range(ndofs)])
+    y = [mp.mpf(0)] * ndofs
+    R = range(m)
+    qdegree = 2 * m - 2 if quad == "gauss_jacobi" else p + 1
+    assert m == ((qdegree + 2) // 2 if quad == "gauss_jacobi" else max(2, (qdegree + 4) // 2))
+    for cz in range(nz):
+        for cy in range(ny):
+            for cx in range(nx):
+                vid = [(cx + (v & 1)) + (nx + 1) * ((cy + ((v >> 1) & 1)) + (ny + 1) * (cz + ((v >> 2) & 1)))
+                       for v in range(8)]
+                X = [[mp.mpf(float(c)) for c in verts[v]] for v in vid]
+
+                def detj(xi):
+                    # J[d][e] = d x_d / d xi_e of x = sum_v X_v prod_e (xi_e or 1 - xi_e)
+                    J = [[mp.mpf(0)] * 3 for _ in range(3)]
+                    for v in range(8):
+                        bits = (v & 1, (v >> 1) & 1, (v >> 2) & 1)
+                        f = [xi[e] if bits[e] else 1 - xi[e] for e in range(3)]
+                        for e in range(3):
+                            dN = (1 if bits[e] else -1) * f[(e + 1) % 3] * f[(e + 2) % 3]
+                            for d in range(3):
+                                J[d][e] += X[v][d] * dN
+                    return mp.det(mp.matrix(J))
+
+                dofs = [[[(p * cx + i) + NX * ((p * cy + j) + NY * (p * cz + k)) for i in range(nn)]
+                         for j in range(nn)] for k in range(nn)]
+                u = [[[mp.mpf(float(x[dofs[k][j][i]])) for i in range(nn)] for j in range(nn)] for k in range(nn)]
+                # forward: u[k][j][i] -> v[qk][qj][qi]
+                a1 = [[[mp.fsum(phi[qi][i] * u[k][j][i] for i in range(nn)) for qi in R] for j in range(nn)]
+                      for k in range(nn)]
+                a2 = [[[mp.fsum(phi[qj][j] * a1[k][j][qi] for j in range(nn)) for qi in R] for qj in R]
+                      for k in range(nn)]
+                a3 = [[[mp.fsum(phi[qk][k] * a2[k][qj][qi] for k in range(nn)) for qi in R] for qj in R] for qk in R]
+                for qk in R:
+                    for qj in R:
+                        for qi in R:
+                            dj = detj((pts[qi], pts[qj], pts[qk]))
+                            assert dj > 0
+                            a3[qk][qj][qi] *= dj * wts[qi] * wts[qj] * wts[qk]
+                # backward
+                b2 = [[[mp.fsum(phi[qk][k] * a3[qk][qj][qi] for qk in R) for qi in R] for qj in R] for k in range(nn)]
+                b1 = [[[mp.fsum(phi[qj][j] * b2[k][qj][qi] for qj in R) for qi in R] for j in range(nn)]
+                      for k in range(nn)]
+                for k in range(nn):
+                    for j in range(nn):
+                        for i in range(nn):
+                            y[dofs[k][j][i]] += mp.fsum(phi[qi][i] * b1[k][j][qi] for qi in R)
+    return {"p": p, "n": list(n), "variant": variant, "quad": quad, "nq1": nq1,
+            "qdegree": qdegree,
+            "verts": verts, "x": x, "y": to_f(y)}
+
+
 def enc(a):
     a = np.asarray(a, dtype=np.float64)
     return {"shape": list(a.shape), "data": [repr(float(v)) for v in a.reshape(-1)]}
@@ -238,6 +309,16 @@ def main():
         r = operators_on_mesh(p, n, 1500.0)
         out["mesh_cases"].append({k: (enc(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()})
         print("mesh case", p, n, flush=True)
+    # dense mass with rectangular 1-D tables: exact Gauss (P+2 points) and under-integrating GLL (qd = P+1)
+    out["dense_mass_cases"] = []
+    for p, n, variant, quad, nq1 in [(1, (2, 2, 2), "equispaced", "gauss_jacobi", 3),
+                                     (2, (2, 2, 2), "gll_warped", "gauss_jacobi", 4),
+                                     (4, (1, 2, 1), "equispaced", "gauss_jacobi", 6),
+                                     (4, (1, 2, 1), "gll_warped", "gll", 4),
+                                     (6, (1, 1, 1), "gll_warped", "gll", 5)]:
+        r = dense_mass_on_mesh(p, n, variant, quad, nq1)
+        out["dense_mass_cases"].append({k: (enc(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()})
+        print("dense mass case", p, n, quad, nq1, flush=True)
     with open(os.path.join(HERE, "independent.json"), "w") as f:
         json.dump(out, f)
 

@@ -271,7 +271,12 @@ def test_spectral_mass_x_ones(gpu, oracle):
 @pytest.mark.parametrize("p,variant,quad,qd", [(1, "gll", "gll", 1), (2, "gll", "gll", 3), (3, "gll", "gll", 4),
                                                 (2, "equispaced", "gauss_jacobi", 4),
                                                 (3, "equispaced", "gauss_jacobi", 6),
-                                                (4, "equispaced", "gauss_jacobi", 8)])
+                                                (4, "equispaced", "gauss_jacobi", 8),
+                                                # rectangular tables: Basix' GLL of degree P+1 has fewer points
+                                                # than nodes from P4 on; Gauss of degree 2P+2 has more
+                                                (4, "gll", "gll", 5), (6, "gll", "gll", 7),
+                                                (2, "equispaced", "gauss_jacobi", 6),
+                                                (4, "equispaced", "gauss_jacobi", 10)])
 def test_dense_mass_vs_oracle(gpu, oracle, p, variant, quad, qd):
     """MassOperator (common/cuda/mass.hpp) incl. the non-collocated cuBLAS-demo
     configuration (demo/gpu_operator/main.cpp:66-68,96-99)."""

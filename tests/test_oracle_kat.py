@@ -123,6 +123,49 @@ def test_dense_mass_matches_lumped_when_collocated(oracle):
     assert np.abs(y1 - y2).max() < 1e-14 * np.abs(y2).max()
 
 
+def test_mass_table_rule_sizes_match_product(oracle):
+    """The oracle's 1-D rules are the product's (wf_quadrature_1d, host code): Basix's
+    point counts, (qd+2)//2 Gauss-Jacobi and max(2, (qd+4)//2) GLL, and the same points
+    and weights, for every degree up to the product's 16-point limit."""
+    import wave_fenics_amd as w
+    from wave_fenics_amd import _lib
+    for quad in ("gll", "gauss_jacobi"):
+        for qd in range(0, 31):
+            m = max(2, (qd + 4) // 2) if quad == "gll" else (qd + 2) // 2
+            pts, wts, phi1, phi, X, W = oracle.tabulate_mass_tables(3, "gll", quad, qd)
+            assert pts.size == wts.size == phi1.shape[0] == m, (quad, qd)
+            assert phi.shape == (m ** 3, 64) and X.shape == (m ** 3, 3) and W.shape == (m ** 3,)
+            if m > _lib.WF_MAX_QUAD_POINTS:
+                with pytest.raises(w.WavehipError):
+                    w.quadrature_1d(quad, qd)
+                continue
+            pw, ww = w.quadrature_1d(quad, qd)
+            assert pw.size == m, (quad, qd)
+            assert np.abs(pw - pts).max() <= 3e-16 and np.abs(ww - wts).max() <= 1e-15, (quad, qd)
+
+
+def test_dense_mass_under_integrated_gll_is_not_lumped(oracle):
+    """P4 with the default qdegree P+1: Basix's GLL rule has 4 points, not the 5 nodes,
+    so Phi^T D Phi is a full (non-collocated) matrix and differs from the lumped mass."""
+    p = 4
+    mesh = oracle.create_box(2, p, perturb=0.2)
+    pts, wts, phi1, phi, X, W = oracle.tabulate_mass_tables(p, "gll", "gll", p + 1)
+    assert phi1.shape == (4, 5)
+    detJ = oracle.compute_detJ_generic(mesh, X, W)
+    x = np.random.default_rng(3).uniform(-1, 1, mesh.ndofs)
+    y1, y2 = np.zeros(mesh.ndofs), np.zeros(mesh.ndofs)
+    oracle.dense_mass_apply(mesh, phi, detJ, x, y1)
+    oracle.MassOperatorCPU(mesh, p)(x, y2)
+    assert np.abs(y1 - y2).max() > 1e-3 * np.abs(y2).max()
+    # the reference-cell matrix Phi^T diag(W) Phi is not diagonal
+    Me = phi.T @ (W[:, None] * phi)
+    assert np.abs(Me - np.diag(np.diag(Me))).max() > 1e-2 * np.abs(Me).max()
+    # ... and it still integrates constants: 1^T M 1 = |Omega|
+    y = np.zeros(mesh.ndofs)
+    oracle.dense_mass_apply(mesh, phi, detJ, np.ones(mesh.ndofs), y)
+    assert abs(y.sum() - 1.0) < 1e-13
+
+
 def test_dense_mass_exact_integration(oracle):
     # equispaced P2 + Gauss rule of degree 4: 1^T M 1 = |Omega| on an affine mesh
     p = 2
