@@ -180,7 +180,16 @@ typedef struct {
   int keep_cell_order; /* batch kernels: do not sort the cells by their smallest dof                */
   int orient;        /* lattice plan: 0 = normalise cell orientations (default), 1 = require the
                         cells to agree as given                                                     */
+  int geometry;      /* box stiffness, P <= 4 marching kernel: wf_geometry_mode                     */
 } wf_tuning;
+/* How a stiffness operator stores its geometry (wf_tuning.geometry, wf_op_info_t.geometry).  A box
+ * whose cells are all affine (edge vectors along each reference axis bitwise equal, det J != 0, no
+ * -1/0/1 clamp taking effect) needs one G_c = J^-1 J^-T |det J| per cell instead of one G per point. */
+typedef enum {
+  WF_GEOMETRY_AUTO = 0,       /* tuning: per cell where the mesh allows it; info: no stiffness geometry */
+  WF_GEOMETRY_PER_POINT = 1,  /* G at every quadrature point (48 B each)                                */
+  WF_GEOMETRY_PER_CELL = 2    /* one G_c per affine cell (48 B); tuning: WF_ERR_INVALID if not affine   */
+} wf_geometry_mode;
 
 typedef struct {
   int kind;                    /* wf_op_kind                                    */
@@ -285,6 +294,7 @@ typedef struct {
                             distinct index tables, layers per item; 0 otherwise          */
   int plan_reoriented;   /* cells whose local axes the plan rotated / reflected to make them agree */
   double plan_fill;      /* cells / cell slots of the plan's columns                     */
+  int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
 int wf_op_destroy(wf_op* op);

@@ -1,6 +1,7 @@
 // C ABI of libwavehip: device shims, geometry setup, operator handles.
 // See include/wavehip.h for the reference interface each entry point replaces.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -19,6 +20,7 @@ struct wf_op {
   DMat dm{};
   int32_t* d_dofmap = nullptr;
   double* d_G6blk = nullptr;
+  double* d_Gcell = nullptr;   // box of affine cells: G_c per cell, blocked like G6blk (stiffness_march.hip)
   double* d_detJ = nullptr;
   double* d_D = nullptr;
   double* d_phi1 = nullptr;
@@ -79,6 +81,7 @@ void free_op(wf_op* op)
   if (!op) return;
   (void)hipFree(op->d_dofmap);
   (void)hipFree(op->d_G6blk);
+  (void)hipFree(op->d_Gcell);
   (void)hipFree(op->d_detJ);
   (void)hipFree(op->d_D);
   (void)hipFree(op->d_phi1);
@@ -142,6 +145,101 @@ int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB)
 }
 
 constexpr int kKsVariant = 3;   // wf_tuning.variant - 1 == 3: the k-split marching kernel (stiffness_march_ks.hip)
+
+// Per-cell geometry of a box (wf_op_create_box).  The trilinear map of a cell is affine when its edge vectors
+// along each reference axis are bitwise equal; J is then [x1-x0 | x2-x0 | x4-x0] everywhere and
+// G(q) = J^-1 J^-T |det J| w_q = G_c w_i w_j w_k.  Returns false -- the operator keeps per-point geometry -- unless
+//  * every cell is affine with det J != 0 (finite);
+//  * with the reference's -1/0/1 clamp on: the clamp changes neither a cmap derivative at the rule's points nor a
+//    component of any G(q) (it maps |v| <= 1e-8 to 0 and v within 1e-5 of +-1 to +-1: per point that would
+//    be a change per-cell G_c w_i w_j w_k cannot express).  Components that are exactly 0 stay 0 either way.
+// Computing G_c from the edge vectors avoids the cancellation of the sum over vertices x_v dphi_v.
+// Gc: [ncells][6] in cell order, components G00 G01 G02 G11 G12 G22 (the blocked layout's order).
+bool box_cell_geometry(int P, int nx, int ny, int nz, const double* xv, int use_fabs, int clamp, std::vector<double>& Gc)
+{
+  const int n = P + 1;
+  std::vector<double> pts(n), wts(n);
+  gll_points_weights(n, pts.data(), wts.data());
+  auto clamp101 = [](double v) {   // as kernels.hip
+    if (std::fabs(v + 1.0) <= 1e-8 + 1e-5) v = -1.0;
+    if (std::fabs(v) <= 1e-8) v = 0.0;
+    if (std::fabs(v - 1.0) <= 1e-8 + 1e-5) v = 1.0;
+    return v;
+  };
+  std::vector<double> W;   // w_i w_j w_k as the per-point geometry forms them
+  for (int k = 0; k < n; ++k)
+    for (int j = 0; j < n; ++j)
+      for (int i = 0; i < n; ++i) W.push_back(wts[i] * wts[j] * wts[k]);
+  const double wmin = *std::min_element(W.begin(), W.end()), wmax = *std::max_element(W.begin(), W.end());
+  if (clamp) {
+    for (int k = 0; k < n; ++k)
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i) {
+          const double f0[2] = {1.0 - pts[i], pts[i]}, f1[2] = {1.0 - pts[j], pts[j]}, f2[2] = {1.0 - pts[k], pts[k]};
+          const double g[2] = {-1.0, 1.0};
+          for (int v = 0; v < 8; ++v) {
+            const int a = v & 1, b = (v >> 1) & 1, c = (v >> 2) & 1;
+            const double d[3] = {g[a] * f1[b] * f2[c], f0[a] * g[b] * f2[c], f0[a] * f1[b] * g[c]};
+            for (double dv : d)
+              if (clamp101(dv) != dv) return false;
+          }
+        }
+  }
+  // does clamp101 leave every value |v| * W alone?  (relative slack for the rounding of the per-point form)
+  constexpr double slack = 1e-6, lo1 = 1.0 - (1e-8 + 1e-5), hi1 = 1.0 + (1e-8 + 1e-5);
+  auto clamp_free = [&](double v) {
+    v = std::fabs(v);
+    if (v == 0.0) return true;
+    if (v * wmin * (1.0 - slack) <= 1e-8) return false;
+    if (v * wmax * (1.0 + slack) < lo1 || v * wmin * (1.0 - slack) > hi1) return true;
+    for (double w : W)
+      if (v * w * (1.0 + slack) >= lo1 && v * w * (1.0 - slack) <= hi1) return false;
+    return true;
+  };
+  const size_t ncells = (size_t)nx * ny * nz;
+  Gc.assign(ncells * 6, 0.0);
+  for (int cz = 0; cz < nz; ++cz)
+    for (int cy = 0; cy < ny; ++cy)
+      for (int cx = 0; cx < nx; ++cx) {
+        const double* x[8];
+        for (int v = 0; v < 8; ++v)
+          x[v] = xv + 3 * ((size_t)(cx + (v & 1)) + (size_t)(nx + 1) * ((cy + ((v >> 1) & 1)) + (size_t)(ny + 1) * (cz + ((v >> 2) & 1))));
+        double J[9];   // J[i * 3 + d]: component i of the edge along reference axis d
+        for (int i = 0; i < 3; ++i) {
+          const double e[3] = {x[1][i] - x[0][i], x[2][i] - x[0][i], x[4][i] - x[0][i]};
+          // x1-x0 == x3-x2 == x5-x4 == x7-x6, x2-x0 == x3-x1 == x6-x4 == x7-x5, x4-x0 == x5-x1 == x6-x2 == x7-x3
+          if (!(x[3][i] - x[2][i] == e[0] && x[5][i] - x[4][i] == e[0] && x[7][i] - x[6][i] == e[0] &&
+                x[3][i] - x[1][i] == e[1] && x[6][i] - x[4][i] == e[1] && x[7][i] - x[5][i] == e[1] &&
+                x[5][i] - x[1][i] == e[2] && x[6][i] - x[2][i] == e[2] && x[7][i] - x[3][i] == e[2]))
+            return false;
+          for (int d = 0; d < 3; ++d) J[i * 3 + d] = e[d];
+        }
+        double det = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
+        if (!(det != 0.0) || !std::isfinite(det)) return false;
+        const double idet = 1.0 / det;
+        double Ji[9];
+        Ji[0] = (J[4] * J[8] - J[5] * J[7]) * idet;
+        Ji[1] = (J[2] * J[7] - J[1] * J[8]) * idet;
+        Ji[2] = (J[1] * J[5] - J[2] * J[4]) * idet;
+        Ji[3] = (J[5] * J[6] - J[3] * J[8]) * idet;
+        Ji[4] = (J[0] * J[8] - J[2] * J[6]) * idet;
+        Ji[5] = (J[2] * J[3] - J[0] * J[5]) * idet;
+        Ji[6] = (J[3] * J[7] - J[4] * J[6]) * idet;
+        Ji[7] = (J[1] * J[6] - J[0] * J[7]) * idet;
+        Ji[8] = (J[0] * J[4] - J[1] * J[3]) * idet;
+        if (use_fabs) det = std::fabs(det);
+        static const int comp[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+        double* gc = &Gc[((size_t)cx + (size_t)nx * (cy + (size_t)ny * cz)) * 6];
+        for (int m = 0; m < 6; ++m) {
+          const int a = comp[m][0], b = comp[m][1];
+          double s = 0.0;
+          for (int k = 0; k < 3; ++k) s += (Ji[a * 3 + k] * det) * Ji[b * 3 + k];
+          if (!std::isfinite(s) || (clamp && !clamp_free(s))) return false;
+          gc[m] = s;
+        }
+      }
+  return true;
+}
 
 void default_box_block(int P, const wf_tuning& tun, int* bx, int* by, int* bz)
 {
@@ -840,6 +938,8 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   const int n = P + 1, nd = n * n * n;
 
   const wf_tuning tun = tuning ? *tuning : wf_tuning{};
+  std::vector<double> h_Gc;   // per-cell geometry, [ncells][6]
+  bool per_cell = false;
 
   std::unique_ptr<wf_op, void (*)(wf_op*)> op(new wf_op, free_op);
   op->kind = kind;
@@ -883,18 +983,41 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
         return WF_ERR_INVALID;
       }
       op->bz = 1;
+    }
+    // geometry: per cell when every cell is affine and the P <= 4 marching kernel runs (the k-split and the
+    // single-pass block kernels read per-point geometry only)
+    WF_REQUIRE(tun.geometry >= WF_GEOMETRY_AUTO && tun.geometry <= WF_GEOMETRY_PER_CELL,
+               "wf_op_create_box: wf_tuning.geometry out of range");
+    const bool cell_capable = op->march && op->march_variant != kKsVariant;
+    if (tun.geometry == WF_GEOMETRY_PER_CELL && !cell_capable) {
+      set_error("wf_op_create_box: per-cell geometry needs the marching kernel of degree <= 4");
+      return WF_ERR_UNSUPPORTED;
+    }
+    if (cell_capable && tun.geometry != WF_GEOMETRY_PER_POINT) {
+      if (box_cell_geometry(P, nx, ny, nz, h_xverts, (flags & WF_FLAG_NO_FABS) ? 0 : 1, (flags & WF_FLAG_NO_CLAMP) ? 0 : 1,
+                            h_Gc))
+        per_cell = true;
+      else if (tun.geometry == WF_GEOMETRY_PER_CELL) {
+        set_error("wf_op_create_box: per-cell geometry requested but the mesh is not affine (or the -1/0/1 clamp "
+                  "takes effect)");
+        return WF_ERR_INVALID;
+      }
+    }
+    if (op->march) {
       const int ncols = ((nx + op->bx - 1) / op->bx) * ((ny + op->by - 1) / op->by);
-      // z segmentation: work items = columns x segments run in rounds of the 512
-      // resident workgroups (2 per CU); each item pays ~1.5 layers of pipeline fill.
-      // Pick the segment length that minimises rounds * (lz + 1.5).
+      // z segmentation: work items = columns x segments run in rounds of the resident workgroups (occupancy
+      // query: 2 per CU for the per-point P4 kernel, 3 for the per-cell one); each item pays ~1.5 layers of
+      // pipeline fill.  Pick the segment length that minimises rounds * (lz + 1.5).
+      long resident = op->march_variant != kKsVariant
+                          ? march_resident(P, op->march_variant, per_cell)
+                          : march_ks_resident(P, op->bx, op->by);
+      if (resident <= 0) resident = 512;
       double best = 1e300;
       op->lz = nz;
       for (int nseg = 1; nseg <= nz; ++nseg) {
         const int lz = (nz + nseg - 1) / nseg;
         if (lz < 3 && nseg > 1) break;
         const long items = (long)ncols * ((nz + lz - 1) / lz);
-        // workgroups per round
-        const long resident = op->march_variant != kKsVariant ? 512 : march_ks_resident(P, op->bx, op->by);
         const double cost = (double)((items + resident - 1) / resident) * (lz + 1.5);
         if (cost < best - 1e-9) {
           best = cost;
@@ -906,12 +1029,17 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   }
   int rc;
 
-  std::vector<double> D(2 * n * n);   // D, then its transpose (scalar-loaded by the k-split kernel)
+  // D, then its transpose (scalar-loaded by the k-split kernel), then the 1-D weights (per-cell marching kernel)
+  std::vector<double> D(2 * n * n + n);
   gll_derivative_matrix(P, D.data());
   for (int q = 0; q < n; ++q)
     for (int a2 = 0; a2 < n; ++a2) D[n * n + a2 * n + q] = D[q * n + a2];
   for (int q = 0; q < n * n; ++q) op->dm.v[q] = D[q];
-  if ((rc = dev_upload(&op->d_D, D.data(), (size_t)2 * n * n, &op->device_bytes)) != WF_OK) return rc;
+  {
+    std::vector<double> pts(n);
+    gll_points_weights(n, pts.data(), D.data() + 2 * n * n);
+  }
+  if ((rc = dev_upload(&op->d_D, D.data(), D.size(), &op->device_bytes)) != WF_OK) return rc;
 
   Scratch<double> d_x, d_pts, d_wts;
   const size_t nverts = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
@@ -920,7 +1048,19 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   const int use_fabs = (flags & WF_FLAG_NO_FABS) ? 0 : 1;
   const int clamp = (flags & WF_FLAG_NO_CLAMP) ? 0 : 1;
 
-  if (kind == WF_OP_STIFFNESS) {
+  if (kind == WF_OP_STIFFNESS && per_cell) {
+    // G_c blocked like G6blk: [column-layer block][cell of the layer][6], padding cells zero
+    const int nbx = (nx + op->bx - 1) / op->bx, nby = (ny + op->by - 1) / op->by, CB = op->bx * op->by;
+    std::vector<double> blk((size_t)nbx * nby * nz * CB * 6, 0.0);
+    for (int cz = 0; cz < nz; ++cz)
+      for (int cy = 0; cy < ny; ++cy)
+        for (int cx = 0; cx < nx; ++cx) {
+          const size_t b = (size_t)(cx / op->bx) + (size_t)nbx * ((cy / op->by) + (size_t)nby * cz);
+          const int cl = cx % op->bx + op->bx * (cy % op->by);
+          std::memcpy(&blk[(b * CB + cl) * 6], &h_Gc[((size_t)cx + (size_t)nx * (cy + (size_t)ny * cz)) * 6], 6 * sizeof(double));
+        }
+    if ((rc = dev_upload(&op->d_Gcell, blk.data(), blk.size(), &op->device_bytes)) != WF_OK) return rc;
+  } else if (kind == WF_OP_STIFFNESS) {
     const size_t nblk = (size_t)((nx + op->bx - 1) / op->bx) * ((ny + op->by - 1) / op->by) * ((nz + op->bz - 1) / op->bz);
     const size_t g6 = nblk * op->bx * op->by * op->bz * nd * 6;
     if ((rc = dev_alloc(&op->d_G6blk, g6, &op->device_bytes)) != WF_OK) return rc;
@@ -979,7 +1119,7 @@ static int launch_box_march(const wf_op* op, int lz0, const double* d_x, double*
   if (op->march_variant == kKsVariant)
     return launch_stiffness_march_ks_box(op->P, op->bx, op->by, op->nx, op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_D, op->dm, op->coeff,
                                          d_x, d_y, d_items, nitems, s);
-  return launch_stiffness_march(op->P, op->march_variant, op->nx, op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_D, op->dm,
+  return launch_stiffness_march(op->P, op->march_variant, op->nx, op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_Gcell, op->d_D, op->dm,
                                 op->coeff, d_x, d_y, d_items, nitems, s);
 }
 
@@ -1175,7 +1315,9 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   if (op->dense) {
     info->flops = 12.0 * op->ncells * (double)op->nq * op->nd;                                  // dense skernel, SURVEY 8a3
     info->alg_bytes = (double)op->ncells * (48.0 + 4.0 * op->nd) + 16.0 * op->ndofs;
-  } else if (op->kind == WF_OP_STIFFNESS)
+  } else if (op->kind == WF_OP_STIFFNESS && op->d_Gcell)
+    info->alg_bytes = (double)op->ncells * (48.0 + 4.0 * op->nd) + 16.0 * op->ndofs;   // per-cell geometry, as the tet path
+  else if (op->kind == WF_OP_STIFFNESS)
     info->alg_bytes = (double)op->ncells * (48.0 * op->nq + 4.0 * op->nd) + 16.0 * op->ndofs;
   else if (op->d_mdiag)
     info->alg_bytes = 24.0 * op->ndofs;   // pre-assembled diagonal: read m, x, y + write y (SURVEY 8d counts 24)
@@ -1190,6 +1332,8 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   info->plan_lz = op->have_plan ? op->plan.lz : (op->structured && op->march ? op->lz : 0);
   info->plan_reoriented = op->plan_reoriented;
   info->plan_fill = op->plan_fill;
+  info->geometry = (op->dense || op->d_Gcell) ? WF_GEOMETRY_PER_CELL
+                   : op->kind == WF_OP_STIFFNESS ? WF_GEOMETRY_PER_POINT : WF_GEOMETRY_AUTO;
   return WF_OK;
 }
 

@@ -70,6 +70,44 @@ __device__ __forceinline__ void stiffness_phase1(const double* __restrict__ U, i
   }
 }
 
+// Phase 1 for an affine cell: G(i, j, k) = G_c w_i w_j w_k with one G_c per cell.  gcw holds
+// coeff * w_i w_j * G_c (components as in the blocked layout: G00 G01 | G02 G11 | G12 G22), wk the
+// 1-D weights.  Everything else as stiffness_phase1.
+template <int P>
+__device__ __forceinline__ void stiffness_phase1_cell(const double* __restrict__ U, int sk, int sj,
+                                                      double* __restrict__ Fr, double* __restrict__ Fs,
+                                                      const double* __restrict__ sD, const DMat& dm,
+                                                      const double2 (&gcw)[3], const double (&wk)[P + 1], int i, int j,
+                                                      bool active, double (&ft)[P + 1])
+{
+  constexpr int n = P + 1, n2 = n * n;
+  if (active) {
+    double ru[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) ru[k] = U[k * sk + j * sj + i];
+    double di[n], dj[n];
+#pragma unroll
+    for (int a = 0; a < n; ++a) {
+      di[a] = sD[i * n + a];
+      dj[a] = sD[j * n + a];
+    }
+    const double g00 = gcw[0].x, g01 = gcw[0].y, g02 = gcw[1].x, g11 = gcw[1].y, g12 = gcw[2].x, g22 = gcw[2].y;
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+      double ur = 0.0, us = 0.0, ut = 0.0;
+#pragma unroll
+      for (int a = 0; a < n; ++a) {
+        ur += di[a] * U[k * sk + j * sj + a];
+        us += dj[a] * U[k * sk + a * sj + i];
+        ut += (WF_CORE_DZ_LDS && P >= 7 ? sD[k * n + a] : dm.v[k * n + a]) * ru[a];
+      }
+      Fr[k * n2 + j * n + i] = wk[k] * (g00 * ur + g01 * us + g02 * ut);
+      Fs[k * n2 + j * n + i] = wk[k] * (g01 * ur + g11 * us + g12 * ut);
+      ft[k] = wk[k] * (g02 * ur + g12 * us + g22 * ut);
+    }
+  }
+}
+
 template <int P>
 __device__ __forceinline__ void stiffness_phase2(const double* __restrict__ Fr, const double* __restrict__ Fs,
                                                  const double* __restrict__ sD, const DMat& dm,

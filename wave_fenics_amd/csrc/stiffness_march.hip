@@ -56,13 +56,22 @@ __device__ unsigned long long g_march_trace[512 * 4 * kMarchTraceIters * kMarchT
 #define WF_MTR(slot)
 #endif
 
-template <int P, int BX, int BY>
-__global__ __launch_bounds__(256, 2) void k_stiffness_march(int nx, int ny, int nz, int lz, int lz0,
-                                                            const double2* __restrict__ G6blk,
-                                                            const double* __restrict__ dD, DMat dm,
-                                                            double coeff, const double* __restrict__ x,
-                                                            double* __restrict__ y,
-                                                            const int32_t* __restrict__ items, int ablate_arg)
+// Per-cell geometry (PC = true; affine cells, wf_op_create_box): G6blk is then the per-cell stream
+// Gc[column-layer block][cell of the layer][3] (double2: G00 G01 | G02 G11 | G12 G22, weights left out) and
+// G(i, j, k) = Gc w_i w_j w_k is formed in phase 1.  Each thread loads the 48 B of its cell one layer ahead
+// (the lanes of one cell read the same address); the x prefetch, tile add, rotate and flush are unchanged.
+// Occupancy of the per-cell form: waves per SIMD = workgroups per CU.  P <= 3 fits 128 VGPRs (four per CU) without
+// spills; P4 needs more (at four per CU: 12 VGPRs and 18 SGPRs spilled to scratch), so it runs three per CU
+// (LDS would allow four: ~36 KB per workgroup at 5x2).
+#ifndef WF_MARCH_CELL_WAVES_P4
+#define WF_MARCH_CELL_WAVES_P4 3
+#endif
+constexpr int march_cell_waves(int P) { return P >= 4 ? WF_MARCH_CELL_WAVES_P4 : 4; }
+template <int P, int BX, int BY, bool PC>
+__global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness_march(
+    int nx, int ny, int nz, int lz, int lz0, const double2* __restrict__ G6blk, const double* __restrict__ dD, DMat dm,
+    double coeff, const double* __restrict__ x, double* __restrict__ y, const int32_t* __restrict__ items,
+    int ablate_arg)
 {
   [[maybe_unused]] const int ablate = WF_ABLATE_FLAGS(ablate_arg);
   constexpr int n = P + 1, n2 = n * n, nd = n * n2;
@@ -123,7 +132,24 @@ __global__ __launch_bounds__(256, 2) void k_stiffness_march(int nx, int ny, int 
 
   const int32_t poff0 = (int32_t)((size_t)I0 + (size_t)NX * J0);   // always inside the mesh
 
+  // per-cell form: coeff * w_i w_j, the weights w_k (loaded once, held in VGPRs), and the thread's cell clamped into
+  // the column (idle threads read the last one)
+  [[maybe_unused]] const double cw = coeff * dD[2 * n2 + i] * dD[2 * n2 + j];
+  [[maybe_unused]] double wk[n];
+  if constexpr (PC)
+#pragma unroll
+    for (int k = 0; k < n; ++k) wk[k] = dD[2 * n2 + k];
+  [[maybe_unused]] const int clc = cl < CB ? cl : CB - 1;
+  using GReg = std::conditional_t<PC, double2[3], double2[n][3]>;
+
   // ---- prologue: geometry of layer z0 -> registers, x planes 0..P -> LDS ------
+  auto load_gc = [&](double2 (&g)[3], int kz) {
+    size_t blk = (size_t)Bx + (size_t)nbx * (By + (size_t)nby * kz);
+    if (ablate & 2) blk = 0;
+    const double2* gp = G6blk + (blk * CB + clc) * 3;
+#pragma unroll
+    for (int p = 0; p < 3; ++p) g[p] = gp[p];
+  };
   auto load_g = [&](double2 (&g)[n][3], int kz, int k0 = 0, int k1 = P + 1) {
     size_t blk = (size_t)Bx + (size_t)nbx * (By + (size_t)nby * kz);
     if (ablate & 2) blk = 0;   // diagnostic: geometry served from L2
@@ -146,8 +172,11 @@ __global__ __launch_bounds__(256, 2) void k_stiffness_march(int nx, int ny, int 
   // [0, G1), [G1, G2), [G2, n)) instead of one burst of 3 n loads at the top
   // (P4: 0.2209 -> 0.2182 ms; P2 has a third of the geometry per layer and was 5 % slower with it)
   constexpr int G1 = P >= 4 ? (n + 1) / 3 : n, G2 = P >= 4 ? (2 * n + 1) / 3 : n;
-  double2 gA[n][3], gB[n][3];
-  load_g(gA, z0);
+  GReg gA, gB;
+  if constexpr (PC)
+    load_gc(gA, z0);
+  else
+    load_g(gA, z0);
   if (t < n * n) sD[t] = dD[t];
 #if WF_MARCH_TILE_ADD
   for (int e = t; e < P * TP; e += 256) O[e] = 0.0;
@@ -183,7 +212,7 @@ __global__ __launch_bounds__(256, 2) void k_stiffness_march(int nx, int ny, int 
   // of the path that issued the geometry loads with the one that did not -- in which the x loads are the YOUNGEST
   // pending loads -- and the rotate then waited with vmcnt(2)/(1)/(0), i.e. for the geometry instalments issued
   // after the x loads too, instead of vmcnt(11)/(10)/(9).
-  auto layer = [&](auto hn_tag, double2 (&gcur)[n][3], double2 (&gnext)[n][3], int kz) {
+  auto layer = [&](auto hn_tag, GReg& gcur, GReg& gnext, int kz) {
     const bool has_next = hn_tag;   // a compile-time constant for the specialised copies (P >= 4)
     const size_t base = plane * (size_t)(P * kz);   // first lattice plane of this layer
     WF_MTR(0);
@@ -201,12 +230,23 @@ __global__ __launch_bounds__(256, 2) void k_stiffness_march(int nx, int ny, int 
 #pragma unroll
       for (int m = 0; m < NPOS; ++m) xn[m] = (ablate & 4) ? 1.0 + m : xb[poff[m] >= 0 ? poff[m] : poff0];
     }
-    if (has_next) load_g(gnext, kzn, 0, G1);   // uniform branch; a self-prefetch in the last layer would re-read 1/lz of the geometry
+    if constexpr (PC)
+      load_gc(gnext, kzn);   // 48 B: the last layer re-reads its own
+    else if (has_next)
+      load_g(gnext, kzn, 0, G1);   // uniform branch; a self-prefetch in the last layer would re-read 1/lz of the geometry
 
     WF_MTR(1);
     // (b) element kernels of the layer
     double out[n];
-    if (ablate & 8) {
+    if constexpr (PC) {
+      double ft[n];
+      double2 gcw[3];
+#pragma unroll
+      for (int p = 0; p < 3; ++p) gcw[p] = make_double2(cw * gcur[p].x, cw * gcur[p].y);
+      stiffness_phase1_cell<P>(Uc, TP, TX, Fr + cl * nd, Fs + cl * nd, sD, dm, gcw, wk, i, j, active, ft);
+      __syncthreads();
+      stiffness_phase2<P>(Fr + cl * nd, Fs + cl * nd, sD, dm, ft, i, j, active, out);
+    } else if (ablate & 8) {
       stiffness_column<P>(Uc, TP, TX, Fr + cl * nd, Fs + cl * nd, sD, dm, gcur, coeff, i, j, active, out, ablate);
       if (has_next) load_g(gnext, kzn, G1, G2);
     } else {
@@ -272,7 +312,8 @@ __global__ __launch_bounds__(256, 2) void k_stiffness_march(int nx, int ny, int 
 #endif
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the LDS writes (and the wait for xn) above the atomics
-    if (has_next) load_g(gnext, kzn, G2, n);
+    if constexpr (!PC)
+      if (has_next) load_g(gnext, kzn, G2, n);
     WF_MTR(4);
     // (d) combine the cells of the layer (fixed order) and add the finished planes to y
 #pragma unroll
@@ -374,16 +415,20 @@ static int march_ablate()
 }
 
 template <int P, int BX, int BY>
-static int launch_march_t(int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk, const double* d_D,
-                          const DMat& dm, double coeff, const double* d_x, double* d_y, const int32_t* d_items,
-                          int nitems, hipStream_t s)
+static int launch_march_t(int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk, const double* d_Gcell,
+                          const double* d_D, const DMat& dm, double coeff, const double* d_x,
+                          double* d_y, const int32_t* d_items, int nitems, hipStream_t s)
 {
   const int ncols = ((nx + BX - 1) / BX) * ((ny + BY - 1) / BY);
   const int nseg = 1 + (std::max(nz - lz0, 0) + lz - 1) / lz;
   const int nwg = d_items ? nitems : ncols * nseg;
   if (nwg == 0) return WF_OK;
-  hipLaunchKernelGGL((k_stiffness_march<P, BX, BY>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0,
-                     reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, d_items, march_ablate());
+  if (d_Gcell)
+    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, true>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0,
+                       reinterpret_cast<const double2*>(d_Gcell), d_D, dm, coeff, d_x, d_y, d_items, march_ablate());
+  else
+    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, false>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0,
+                       reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, d_items, march_ablate());
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error(std::string("stiffness_march launch failed: ") + hipGetErrorString(e));
@@ -412,11 +457,11 @@ bool march_variant(int P, int variant, int* bx, int* by)
 }
 
 #define WF_MARCH_CASE(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return launch_march_t<PP, BXX, BYY>(nx, ny, nz, lz, lz0, d_G6blk, d_D, dm, coeff, d_x, d_y, d_items, nitems, s);
+  if (P == PP && variant == V) return launch_march_t<PP, BXX, BYY>(nx, ny, nz, lz, lz0, d_G6blk, d_Gcell, d_D, dm, coeff, d_x, d_y, d_items, nitems, s);
 
 int launch_stiffness_march(int P, int variant, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,
-                           const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_y,
-                           const int32_t* d_items, int nitems, hipStream_t s)
+                           const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
+                           const double* d_x, double* d_y, const int32_t* d_items, int nitems, hipStream_t s)
 {
   if ((size_t)nx * ny * nz == 0) return WF_OK;
   WF_MARCH_CASE(1, 0, 8, 8) WF_MARCH_CASE(1, 1, 4, 4) WF_MARCH_CASE(1, 2, 8, 4)
@@ -425,6 +470,32 @@ int launch_stiffness_march(int P, int variant, int nx, int ny, int nz, int lz, i
   WF_MARCH_CASE(4, 0, 3, 3) WF_MARCH_CASE(4, 1, 5, 2) WF_MARCH_CASE(4, 2, 2, 2)
   set_error("stiffness_march: unsupported degree/variant");
   return WF_ERR_UNSUPPORTED;
+}
+
+// Workgroups of the (P, variant) kernel resident on the device at once (occupancy query x CUs; the z
+// segmentation of wf_op_create_box runs its work items in rounds of this many).  0 if the query fails.
+template <int P, int BX, int BY>
+static int march_resident_t(bool per_cell)
+{
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  const hipError_t e = per_cell
+                           ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, true>, 256, 0)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, false>, 256, 0);
+  return e == hipSuccess ? per_cu * cus : 0;
+}
+
+#define WF_MARCH_RES(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return march_resident_t<PP, BXX, BYY>(per_cell);
+
+int march_resident(int P, int variant, bool per_cell)
+{
+  WF_MARCH_RES(1, 0, 8, 8) WF_MARCH_RES(1, 1, 4, 4) WF_MARCH_RES(1, 2, 8, 4)
+  WF_MARCH_RES(2, 0, 5, 5) WF_MARCH_RES(2, 1, 3, 3) WF_MARCH_RES(2, 2, 7, 4)
+  WF_MARCH_RES(3, 0, 4, 4) WF_MARCH_RES(3, 1, 3, 3) WF_MARCH_RES(3, 2, 4, 2)
+  WF_MARCH_RES(4, 0, 3, 3) WF_MARCH_RES(4, 1, 5, 2) WF_MARCH_RES(4, 2, 2, 2)
+  return 0;
 }
 
 }  // namespace wf

@@ -131,8 +131,9 @@ def precompute_geometric_data(mesh, p: int, use_fabs: bool = True, clamp: bool =
 # operator handles
 # ---------------------------------------------------------------------------
 def make_tuning(tuning) -> "_lib.Tuning | None":
-    """wf_tuning from a dict (kernel=, variant=, lz=, lz0=, block=(bx, by, bz), keep_cell_order=, orient=) or None.
-    `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any", "elementwise", "march"."""
+    """wf_tuning from a dict (kernel=, variant=, lz=, lz0=, block=(bx, by, bz), keep_cell_order=, orient=, geometry=)
+    or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any", "elementwise", "march";
+    `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"."""
     if tuning is None:
         return None
     if isinstance(tuning, _lib.Tuning):
@@ -149,9 +150,12 @@ def make_tuning(tuning) -> "_lib.Tuning | None":
     t.bx, t.by, t.bz = (int(v) for v in tuning.get("block", (0, 0, 0)))
     t.keep_cell_order = int(bool(tuning.get("keep_cell_order", False)))
     t.orient = int(tuning.get("orient", 0))
+    g = tuning.get("geometry", 0)
+    t.geometry = GEOMETRY_MODES[g] if isinstance(g, str) else int(g)
     return t
 
 
+GEOMETRY_MODES = {"auto": 0, "per_point": 1, "per_cell": 2}
 KERNEL_NAMES = {0: "none", 1: "march_box", 2: "march_idx", 3: "batch_unique", 4: "box_block", 5: "diagonal",
                 6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise"}
 
@@ -183,6 +187,11 @@ class _Operator:
     def kernel(self) -> str:
         """Name of the kernel wf_op_apply launches (wf_op_info_t.kernel)."""
         return KERNEL_NAMES.get(self.info.kernel, "?")
+
+    @property
+    def geometry(self) -> str:
+        """How the stiffness geometry is stored (wf_op_info_t.geometry): "per_point", "per_cell" or "none"."""
+        return {1: "per_point", 2: "per_cell"}.get(self.info.geometry, "none")
 
     def _info(self):
         info = OpInfo()
