@@ -181,6 +181,7 @@ typedef struct {
   int orient;        /* lattice plan: 0 = normalise cell orientations (default), 1 = require the
                         cells to agree as given                                                     */
   int geometry;      /* box stiffness, P <= 4 marching kernel: wf_geometry_mode                     */
+  int metric;        /* box stiffness with per-cell geometry: wf_metric_mode                        */
 } wf_tuning;
 /* How a stiffness operator stores its geometry (wf_tuning.geometry, wf_op_info_t.geometry).  A box
  * whose cells are all affine (edge vectors along each reference axis bitwise equal, det J != 0, no
@@ -190,6 +191,16 @@ typedef enum {
   WF_GEOMETRY_PER_POINT = 1,  /* G at every quadrature point (48 B each)                                */
   WF_GEOMETRY_PER_CELL = 2    /* one G_c per affine cell (48 B); tuning: WF_ERR_INVALID if not affine   */
 } wf_geometry_mode;
+/* Which form of the per-cell box kernel runs (wf_tuning.metric, wf_op_info_t.metric).  When every G_c is
+ * diagonal (a rectilinear box: off-diagonals exactly 0) the cell operator separates into one 1-D operator
+ * A = D^T diag(w) D per axis, which takes about half the LDS reads and FMAs of the full tensor. */
+typedef enum {
+  WF_METRIC_AUTO = 0,         /* tuning: axes where every G_c is diagonal, else full                   */
+  WF_METRIC_NONE = 0,         /* info: no per-cell geometry                                            */
+  WF_METRIC_FULL = 1,         /* the full-tensor per-cell form (tuning: also on rectilinear boxes)     */
+  WF_METRIC_AXES = 2          /* the separable form; tuning: WF_ERR_INVALID if a G_c is not diagonal,
+                                 WF_ERR_UNSUPPORTED without per-cell geometry                         */
+} wf_metric_mode;
 
 typedef struct {
   int kind;                    /* wf_op_kind                                    */
@@ -295,6 +306,7 @@ typedef struct {
   int plan_reoriented;   /* cells whose local axes the plan rotated / reflected to make them agree */
   double plan_fill;      /* cells / cell slots of the plan's columns                     */
   int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
+  int metric;            /* wf_metric_mode of the per-cell box kernel (0: none)          */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
 int wf_op_destroy(wf_op* op);

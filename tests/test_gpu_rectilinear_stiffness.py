@@ -1,0 +1,228 @@
+"""Separable ("axes") form of the box stiffness operator (wf_tuning.metric, wf_op_info_t.metric).
+
+A box whose cells are affine and axis-aligned has a diagonal G_c in every cell.  With the GLL rule at the
+nodes the cell operator then separates into one 1-D operator A = D^T diag(w) D per axis.  Every such
+operator is checked against the CPU oracle (1e-12 of max|y|) and against the same box with the
+full-tensor per-cell form and with per-point geometry (1e-13: only the rounding differs)."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+TOL_ORACLE = 1e-12
+TOL_FORM = 1e-13
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import wave_fenics_amd as w
+    w.lib()
+    return torch.device("cuda", 0)
+
+
+def relerr(a, b):
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+def lattice_x(vx, vy, vz):
+    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
+    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
+
+
+def spaces(oracle, n, p, x=None, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), perturb=0.0):
+    """(oracle mesh, FunctionSpace) of the box n; x replaces the vertex coordinates when given."""
+    import wave_fenics_amd as w
+    om = oracle.create_box(n, p, lo=lo, hi=hi, perturb=perturb)
+    mesh = w.create_box(n, lo=lo, hi=hi, perturb=perturb)
+    if x is not None:
+        om.x = np.ascontiguousarray(x, dtype=np.float64)
+        mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
+    assert np.array_equal(mesh.x, om.x)
+    return om, w.create_functionspace(mesh, p)
+
+
+def rectilinear(oracle, case, n, p):
+    if case == "unit":
+        return spaces(oracle, n, p)
+    if case == "anisotropic":
+        return spaces(oracle, n, p, hi=(2.0, 1.0, 0.5))
+    if case == "far":   # coordinates ~1, h ~ 0.1 / n: the benchmark's coordinate-to-h ratio
+        return spaces(oracle, n, p, lo=(0.9,) * 3, hi=(1.0,) * 3)
+    assert case == "graded"   # uneven spacing per axis
+    rng = np.random.default_rng(11)
+    axes = [np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 2.0, m))]) for m in n]
+    return spaces(oracle, n, p, x=lattice_x(*axes))
+
+
+def stiffness(V, p, flags=0, **tuning):
+    import wave_fenics_amd as w
+    return w.StiffnessOperator(V, p, {"c0": 1500.0}, structured=True, flags=flags, tuning=tuning or None)
+
+
+def apply(op, x, gpu):
+    import torch
+    y = torch.zeros(op.info.ndofs, dtype=torch.float64, device=gpu)
+    op(torch.from_numpy(x).to(gpu), y)
+    torch.cuda.synchronize()
+    return y.cpu().numpy()
+
+
+# odd sizes: partial columns of every compiled cross-section in x and y
+@pytest.mark.parametrize("p,n", [(1, (9, 7, 5)), (2, (7, 5, 3)), (3, (5, 5, 4)), (4, (7, 5, 3))])
+@pytest.mark.parametrize("case", ["unit", "anisotropic", "far", "graded"])
+def test_rectilinear_boxes_take_the_axes_form(gpu, oracle, p, n, case):
+    om, V = rectilinear(oracle, case, n, p)
+    x = np.random.default_rng(1).uniform(-1, 1, om.ndofs)
+    yref = np.zeros(om.ndofs)
+    oracle.StiffnessOperator(om, p)(x, yref)
+    ax, full, pp = stiffness(V, p), stiffness(V, p, metric="full"), stiffness(V, p, geometry="per_point")
+    assert ax.kernel == full.kernel == pp.kernel == "march_box"
+    assert ax.geometry == full.geometry == "per_cell" and pp.geometry == "per_point"
+    assert (ax.metric, full.metric, pp.metric) == ("axes", "full", "none")
+    assert stiffness(V, p, metric="axes").metric == "axes"
+    y = apply(ax, x, gpu)
+    assert relerr(y, yref) <= TOL_ORACLE, relerr(y, yref)
+    assert relerr(y, apply(full, x, gpu)) <= TOL_FORM
+    assert relerr(y, apply(pp, x, gpu)) <= TOL_FORM
+    # storage and the byte model are those of the full per-cell form
+    nd = (p + 1) ** 3
+    assert ax.info.device_bytes == full.info.device_bytes
+    assert ax.alg_bytes() == pytest.approx(ax.info.num_cells * (48.0 + 4.0 * nd) + 16.0 * ax.info.ndofs)
+
+
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+@pytest.mark.parametrize("variant", [0, 1, 2])
+def test_every_cross_section(gpu, oracle, p, variant):
+    om, V = rectilinear(oracle, "graded", (9, 7, 4), p)
+    x = np.random.default_rng(2).uniform(-1, 1, om.ndofs)
+    yref = np.zeros(om.ndofs)
+    oracle.StiffnessOperator(om, p)(x, yref)
+    op = stiffness(V, p, variant=variant)
+    assert op.metric == "axes"
+    assert relerr(apply(op, x, gpu), yref) <= TOL_ORACLE
+
+
+def test_sheared_and_perturbed_boxes(gpu, oracle):
+    import wave_fenics_amd as w
+    n, p = (4, 3, 3), 4
+    x = lattice_x(*[np.arange(m + 1) * 0.125 for m in n])
+    x[:, 0] += 0.25 * x[:, 1]   # dyadic shear: affine cells, G01 != 0
+    om, V = spaces(oracle, n, p, x=x)
+    op = stiffness(V, p)
+    assert (op.geometry, op.metric) == ("per_cell", "full")
+    xr = np.random.default_rng(4).uniform(-1, 1, om.ndofs)
+    yref = np.zeros(om.ndofs)
+    oracle.StiffnessOperator(om, p)(xr, yref)
+    assert relerr(apply(op, xr, gpu), yref) <= TOL_ORACLE
+    with pytest.raises(w.WavehipError):
+        stiffness(V, p, metric="axes")
+    _, V = spaces(oracle, n, p, perturb=0.2)
+    op = stiffness(V, p)
+    assert (op.geometry, op.metric) == ("per_point", "none")
+    with pytest.raises(w.WavehipError):
+        stiffness(V, p, metric="axes")
+    _, V = spaces(oracle, n, p)
+    with pytest.raises(w.WavehipError):   # per-point geometry forced: no per-cell form to run
+        stiffness(V, p, geometry="per_point", metric="axes")
+
+
+@pytest.mark.parametrize("p", [2, 4])
+def test_flags_act_alike_in_both_forms(gpu, oracle, p):
+    """A box mirrored in x (det J < 0): WF_FLAG_NO_FABS negates the operator, WF_FLAG_NO_CLAMP changes nothing
+    on this mesh; the axes form follows the full one in both."""
+    from wave_fenics_amd._lib import WF_FLAG_NO_CLAMP, WF_FLAG_NO_FABS
+    n = (5, 4, 3)
+    axes = [np.linspace(0.0, 1.0, m + 1) for m in n]
+    axes[0] = axes[0][::-1].copy()
+    om, V = spaces(oracle, n, p, x=lattice_x(*axes))
+    x = np.random.default_rng(5).uniform(-1, 1, om.ndofs)
+    ys = {}
+    for flags in (0, WF_FLAG_NO_FABS, WF_FLAG_NO_CLAMP, WF_FLAG_NO_FABS | WF_FLAG_NO_CLAMP):
+        ax, full = stiffness(V, p, flags), stiffness(V, p, flags, metric="full")
+        assert (ax.metric, full.metric) == ("axes", "full"), flags
+        ys[flags] = apply(ax, x, gpu)
+        assert relerr(ys[flags], apply(full, x, gpu)) <= TOL_FORM, flags
+    yref = np.zeros(om.ndofs)
+    oracle.StiffnessOperator(om, p)(x, yref)
+    assert relerr(ys[0], yref) <= TOL_ORACLE
+    assert relerr(ys[WF_FLAG_NO_FABS], -ys[0]) <= TOL_FORM
+    assert relerr(ys[WF_FLAG_NO_CLAMP], ys[0]) <= TOL_FORM
+    assert relerr(ys[WF_FLAG_NO_FABS | WF_FLAG_NO_CLAMP], -ys[0]) <= TOL_FORM
+
+
+@pytest.mark.parametrize("p,n,lz", [(4, (6, 5, 11), 3), (2, (8, 7, 9), 2)])
+def test_parts_sum_to_the_full_apply(gpu, oracle, p, n, lz):
+    import torch
+    from wave_fenics_amd._lib import WF_PART_INTERFACE, WF_PART_INTERIOR, WF_PART_INTERIOR_A, WF_PART_INTERIOR_B
+    _, V = spaces(oracle, n, p, hi=(1.0, 0.8, 1.2))
+    K = stiffness(V, p, lz=lz)
+    assert K.metric == "axes"
+    x = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, V.ndofs)).to(gpu)
+    yfull = torch.zeros_like(x)
+    K(x, yfull)
+    assert K.set_ghost_faces(True, False, True)
+    for parts in ((WF_PART_INTERIOR, WF_PART_INTERFACE), (WF_PART_INTERIOR_A, WF_PART_INTERFACE, WF_PART_INTERIOR_B)):
+        y = torch.zeros_like(x)
+        for part in parts:
+            K.apply_part(x, y, part)
+        torch.cuda.synchronize()
+        assert relerr(y.cpu().numpy(), yfull.cpu().numpy()) <= TOL_FORM, parts
+
+
+@pytest.mark.parametrize("p,n", [(2, (7, 6, 9)), (4, (6, 5, 7))])
+def test_axes_applies_are_repeatable(gpu, oracle, p, n):
+    import torch
+    _, V = spaces(oracle, n, p, hi=(1.0, 0.7, 1.3))
+    op = stiffness(V, p)
+    assert op.metric == "axes"
+    x = torch.rand(V.ndofs, dtype=torch.float64, device=gpu)
+    ref, worst = None, 0.0
+    for _ in range(100):
+        y = torch.zeros_like(x)
+        op(x, y)
+        if ref is None:
+            ref = y.clone()
+        else:
+            worst = max(worst, float((y - ref).abs().max() / ref.abs().max()))
+    assert worst <= 1e-14, worst
+
+
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_constants_in_the_kernel_and_energy(gpu, oracle, p):
+    """K 1 = 0, and x^T K x agrees with the full-tensor form on a random x."""
+    om, V = rectilinear(oracle, "graded", (6, 5, 4), p)
+    ax, full = stiffness(V, p), stiffness(V, p, metric="full")
+    assert ax.metric == "axes"
+    x = np.random.default_rng(6).uniform(-1, 1, om.ndofs)
+    y, yf = apply(ax, x, gpu), apply(full, x, gpu)
+    one = apply(ax, np.ones(om.ndofs), gpu)
+    assert np.abs(one).max() <= 1e-12 * np.abs(y).max(), np.abs(one).max() / np.abs(y).max()
+    e, ef = float(x @ y), float(x @ yf)
+    assert e < 0.0   # -c0^2 K: negative definite on a non-constant x
+    assert abs(e - ef) <= 1e-13 * abs(ef), (e, ef)
+
+
+def test_full_size_bench_input(gpu):
+    """The benchmark's box (P4, 54^3 cells) and input sin(2 pi X): axes form against per-point geometry."""
+    import torch
+    import wave_fenics_amd as w
+    p, n = 4, 54
+    V = w.create_functionspace(w.create_box(n), p)
+    ax = w.StiffnessOperator(V, p, {"c0": 1500.0})
+    assert (ax.geometry, ax.metric, ax.kernel) == ("per_cell", "axes", "march_box")
+    pts, _, _ = w.tabulate_gll(p)   # dof x coordinates, as bench.py builds them
+    xs = np.concatenate([(np.arange(n)[:, None] + pts[None, :p]).reshape(-1), [float(n)]]) / n
+    x = torch.sin(2 * np.pi * torch.from_numpy(xs).to(gpu)).repeat((p * n + 1) ** 2).contiguous()
+    y = torch.zeros_like(x)
+    ax(x, y)
+    del ax
+    pp = w.StiffnessOperator(V, p, {"c0": 1500.0}, tuning={"geometry": "per_point"})
+    assert pp.geometry == "per_point"
+    ypp = torch.zeros_like(x)
+    pp(x, ypp)
+    torch.cuda.synchronize()
+    err = float((y - ypp).abs().max() / ypp.abs().max())
+    print(f"P4 54^3 sin(2 pi X): axes vs per point max|dy|/max|y| = {err:.3e}")
+    assert err <= 1e-11

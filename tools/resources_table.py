@@ -12,7 +12,7 @@ for l in open(raw):
     src, rest = l.split(": ", 1)
     m = re.search(r"Function Name: (\S+)", rest)
     name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
-    name = re.sub(r"\(.*", "", name).replace("void ", "")
+    name = re.sub(r"\(.*", "", name.replace("(wf::MarchGeom)", "geom ")).replace("void ", "")
     v = {k: re.search(p + r": (\d+)", rest).group(1) for k, p in K.items()}
     out.append(f"{src:26s} {name[:64]:64s} {v['sg']:>4} {v['vg']:>4} {v['ag']:>4} {v['sc']:>4} {v['oc']:>2} {v['ss']:>4} {v['vs']:>3} {v['ld']:>6}")
 open(dst, "w").write("\n".join(out) + "\n")

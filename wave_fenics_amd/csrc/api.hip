@@ -18,6 +18,8 @@ struct wf_op {
   int lz0_split = 1;                          // length of the first z segment of the interior / interface parts
   double coeff = 0.0;
   DMat dm{};
+  DMat am{};   // A = D^T diag(w) D: the 1-D operator of the separable box form (metric = WF_METRIC_AXES)
+  int metric = WF_METRIC_NONE;   // wf_metric_mode of a per-cell box stiffness operator
   int32_t* d_dofmap = nullptr;
   double* d_G6blk = nullptr;
   double* d_Gcell = nullptr;   // box of affine cells: G_c per cell, blocked like G6blk (stiffness_march.hip)
@@ -988,6 +990,7 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
     // single-pass block kernels read per-point geometry only)
     WF_REQUIRE(tun.geometry >= WF_GEOMETRY_AUTO && tun.geometry <= WF_GEOMETRY_PER_CELL,
                "wf_op_create_box: wf_tuning.geometry out of range");
+    WF_REQUIRE(tun.metric >= WF_METRIC_AUTO && tun.metric <= WF_METRIC_AXES, "wf_op_create_box: wf_tuning.metric out of range");
     const bool cell_capable = op->march && op->march_variant != kKsVariant;
     if (tun.geometry == WF_GEOMETRY_PER_CELL && !cell_capable) {
       set_error("wf_op_create_box: per-cell geometry needs the marching kernel of degree <= 4");
@@ -1003,13 +1006,31 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
         return WF_ERR_INVALID;
       }
     }
+    // metric: the separable (axes) form when every G_c is diagonal -- off-diagonals exactly 0, either sign; the
+    // clamp checks above already hold (they leave an exact 0 alone)
+    if (tun.metric == WF_METRIC_AXES && !per_cell) {
+      set_error("wf_op_create_box: the axes metric needs per-cell geometry");
+      return WF_ERR_UNSUPPORTED;
+    }
+    if (per_cell) {
+      bool diagonal = true;
+      for (size_t c = 0; c < h_Gc.size() && diagonal; c += 6)
+        diagonal = h_Gc[c + 1] == 0.0 && h_Gc[c + 2] == 0.0 && h_Gc[c + 4] == 0.0;
+      if (tun.metric == WF_METRIC_AXES && !diagonal) {
+        set_error("wf_op_create_box: axes metric requested but a cell's G_c has a non-zero off-diagonal");
+        return WF_ERR_INVALID;
+      }
+      op->metric = diagonal && tun.metric != WF_METRIC_FULL ? WF_METRIC_AXES : WF_METRIC_FULL;
+    }
+    const MarchGeom geom = !per_cell ? MarchGeom::point : op->metric == WF_METRIC_AXES ? MarchGeom::cell_axes : MarchGeom::cell;
     if (op->march) {
       const int ncols = ((nx + op->bx - 1) / op->bx) * ((ny + op->by - 1) / op->by);
       // z segmentation: work items = columns x segments run in rounds of the resident workgroups (occupancy
-      // query: 2 per CU for the per-point P4 kernel, 3 for the per-cell one); each item pays ~1.5 layers of
+      // query of the kernel that launches: 2 per CU for the per-point P4 kernel, 3 for the full per-cell one and 3 for
+      // the axes one); each item pays ~1.5 layers of
       // pipeline fill.  Pick the segment length that minimises rounds * (lz + 1.5).
       long resident = op->march_variant != kKsVariant
-                          ? march_resident(P, op->march_variant, per_cell)
+                          ? march_resident(P, op->march_variant, geom)
                           : march_ks_resident(P, op->bx, op->by);
       if (resident <= 0) resident = 512;
       double best = 1e300;
@@ -1029,15 +1050,25 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   }
   int rc;
 
-  // D, then its transpose (scalar-loaded by the k-split kernel), then the 1-D weights (per-cell marching kernel)
-  std::vector<double> D(2 * n * n + n);
+  // D, then its transpose (scalar-loaded by the k-split kernel), then the 1-D weights (per-cell marching kernel), then
+  // A = D^T diag(w) D (axes form: A[i][a] = sum_q D[q][i] w_q D[q][a], summed in long double and rounded once)
+  std::vector<double> D(3 * n * n + n);
   gll_derivative_matrix(P, D.data());
   for (int q = 0; q < n; ++q)
     for (int a2 = 0; a2 < n; ++a2) D[n * n + a2 * n + q] = D[q * n + a2];
   for (int q = 0; q < n * n; ++q) op->dm.v[q] = D[q];
   {
     std::vector<double> pts(n);
+    const double* w = D.data() + 2 * n * n;
     gll_points_weights(n, pts.data(), D.data() + 2 * n * n);
+    double* A = D.data() + 2 * n * n + n;
+    for (int i = 0; i < n; ++i)
+      for (int a2 = i; a2 < n; ++a2) {
+        long double s = 0.0L;
+        for (int q = 0; q < n; ++q) s += (long double)D[q * n + i] * (long double)w[q] * (long double)D[q * n + a2];
+        A[i * n + a2] = A[a2 * n + i] = (double)s;
+      }
+    for (int q = 0; q < n * n; ++q) op->am.v[q] = A[q];
   }
   if ((rc = dev_upload(&op->d_D, D.data(), D.size(), &op->device_bytes)) != WF_OK) return rc;
 
@@ -1119,7 +1150,10 @@ static int launch_box_march(const wf_op* op, int lz0, const double* d_x, double*
   if (op->march_variant == kKsVariant)
     return launch_stiffness_march_ks_box(op->P, op->bx, op->by, op->nx, op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_D, op->dm, op->coeff,
                                          d_x, d_y, d_items, nitems, s);
-  return launch_stiffness_march(op->P, op->march_variant, op->nx, op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_Gcell, op->d_D, op->dm,
+  const bool axes = op->metric == WF_METRIC_AXES;
+  return launch_stiffness_march(op->P, op->march_variant,
+                                !op->d_Gcell ? MarchGeom::point : axes ? MarchGeom::cell_axes : MarchGeom::cell, op->nx,
+                                op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_Gcell, op->d_D, axes ? op->am : op->dm,
                                 op->coeff, d_x, d_y, d_items, nitems, s);
 }
 
@@ -1334,6 +1368,7 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   info->plan_fill = op->plan_fill;
   info->geometry = (op->dense || op->d_Gcell) ? WF_GEOMETRY_PER_CELL
                    : op->kind == WF_OP_STIFFNESS ? WF_GEOMETRY_PER_POINT : WF_GEOMETRY_AUTO;
+  info->metric = op->d_Gcell ? op->metric : WF_METRIC_NONE;
   return WF_OK;
 }
 

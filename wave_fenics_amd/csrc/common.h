@@ -91,12 +91,15 @@ int launch_stiffness_box(int P, int nx, int ny, int nz, int bx, int by, int bz, 
                          const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_y,
                          hipStream_t s);
 bool march_variant(int P, int variant, int* bx, int* by);
-// d_Gcell != null: the per-cell geometry of affine cells (d_G6blk unused); d_D then carries the 1-D weights at
-// [2 n^2, 2 n^2 + n)
-int launch_stiffness_march(int P, int variant, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,
-                           const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
+// Geometry form of the box marching kernel (stiffness_march.hip): G at every point, one full G_c per affine cell, or
+// one diagonal G_c per rectilinear affine cell (the separable operator: one 1-D operator A = D^T diag(w) D per axis).
+enum class MarchGeom : int { point = 0, cell = 1, cell_axes = 2 };
+// geom != point: d_Gcell is the per-cell geometry of affine cells (d_G6blk unused); d_D then carries the 1-D weights
+// at [2 n^2, 2 n^2 + n) and, for cell_axes, A at [2 n^2 + n, 3 n^2 + n); dm is A instead of D for cell_axes
+int launch_stiffness_march(int P, int variant, MarchGeom geom, int nx, int ny, int nz, int lz, int lz0,
+                           const double* d_G6blk, const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
                            const double* d_x, double* d_y, const int32_t* d_items, int nitems, hipStream_t s);
-int march_resident(int P, int variant, bool per_cell);   // workgroups resident on the device (occupancy query)
+int march_resident(int P, int variant, MarchGeom geom);   // workgroups resident on the device (occupancy query)
 // indexed marching kernels for arbitrary dofmaps (generic_plan.cpp, stiffness_march_idx.hip, stiffness_march_ks.hip)
 struct MarchPlan {
   bool ok = false;                      // false: the mesh does not tile into lattice columns

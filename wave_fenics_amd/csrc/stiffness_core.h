@@ -108,6 +108,37 @@ __device__ __forceinline__ void stiffness_phase1_cell(const double* __restrict__
   }
 }
 
+// One pass for a rectilinear affine cell (G_c diagonal).  With the rule collocated at the nodes the reference
+// gradient along r at point q is D[q_i][a_i] d(q_j, a_j) d(q_k, a_k), so the cell operator separates into one 1-D
+// operator per axis, A = D^T diag(w) D:
+//   out[k] = w_k (sx sum_a A[i][a] u(a, j, k) + sy sum_a A[j][a] u(i, a, k)) + sz sum_a A[k][a] u(i, j, a)
+// with sx = coeff G00 w_j, sy = coeff G11 w_i, sz = coeff G22 w_i w_j.  ai, aj: the thread's rows of A (registers);
+// am: A by value (compile-time indices -> SGPRs).  No Fr / Fs scratch and no barrier.
+template <int P>
+__device__ __forceinline__ void stiffness_axes_cell(const double* __restrict__ U, int sk, int sj, const DMat& am,
+                                                    const double (&ai)[P + 1], const double (&aj)[P + 1],
+                                                    const double (&wk)[P + 1], double sx, double sy, double sz, int i,
+                                                    int j, bool active, double (&out)[P + 1])
+{
+  constexpr int n = P + 1;
+  if (active) {
+    double ru[n];
+#pragma unroll
+    for (int k = 0; k < n; ++k) ru[k] = U[k * sk + j * sj + i];
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+      double ux = 0.0, uy = 0.0, uz = 0.0;
+#pragma unroll
+      for (int a = 0; a < n; ++a) {
+        ux += ai[a] * U[k * sk + j * sj + a];
+        uy += aj[a] * U[k * sk + a * sj + i];
+        uz += am.v[k * n + a] * ru[a];
+      }
+      out[k] = wk[k] * (sx * ux + sy * uy) + sz * uz;
+    }
+  }
+}
+
 template <int P>
 __device__ __forceinline__ void stiffness_phase2(const double* __restrict__ Fr, const double* __restrict__ Fs,
                                                  const double* __restrict__ sD, const DMat& dm,

@@ -56,24 +56,39 @@ __device__ unsigned long long g_march_trace[512 * 4 * kMarchTraceIters * kMarchT
 #define WF_MTR(slot)
 #endif
 
-// Per-cell geometry (PC = true; affine cells, wf_op_create_box): G6blk is then the per-cell stream
+// Per-cell geometry (G != MarchGeom::point; affine cells, wf_op_create_box): G6blk is then the per-cell stream
 // Gc[column-layer block][cell of the layer][3] (double2: G00 G01 | G02 G11 | G12 G22, weights left out) and
 // G(i, j, k) = Gc w_i w_j w_k is formed in phase 1.  Each thread loads the 48 B of its cell one layer ahead
 // (the lanes of one cell read the same address); the x prefetch, tile add, rotate and flush are unchanged.
 // Occupancy of the per-cell form: waves per SIMD = workgroups per CU.  P <= 3 fits 128 VGPRs (four per CU) without
 // spills; P4 needs more (at four per CU: 12 VGPRs and 18 SGPRs spilled to scratch), so it runs three per CU
 // (LDS would allow four: ~36 KB per workgroup at 5x2).
+// Rectilinear affine cells (G = MarchGeom::cell_axes: every G_c diagonal) take the separable form instead,
+// stiffness_axes_cell: one pass over the layer's x tile per layer, no Fr / Fs and no barrier inside the element kernel;
+// dm then holds A = D^T diag(w) D and dD the thread's rows of it.  P4 at 5x2: 132 VGPRs at three per CU, 110 at four,
+// scratch at five.  Measured on cfg2 (apply alone, median of 50): three per CU 0.104 ms, four per CU 0.108 ms.
+// Measured and rejected: the x prefetch two layers ahead, with branchless atomics (out-of-tile lanes adding -0.0 to
+// the tile's first entry) so that the rotate's wait no longer covered the previous layer's atomics: 0.157 ms.  Without
+// atomics it gained little (0.062 -> 0.060 ms), and the extra same-address atomics cost far more.
 #ifndef WF_MARCH_CELL_WAVES_P4
 #define WF_MARCH_CELL_WAVES_P4 3
 #endif
+#ifndef WF_MARCH_AXES_WAVES_P4
+#define WF_MARCH_AXES_WAVES_P4 3
+#endif
 constexpr int march_cell_waves(int P) { return P >= 4 ? WF_MARCH_CELL_WAVES_P4 : 4; }
-template <int P, int BX, int BY, bool PC>
-__global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness_march(
+constexpr int march_waves(MarchGeom G, int P)
+{
+  return G == MarchGeom::point ? 2 : G == MarchGeom::cell ? march_cell_waves(P) : P >= 4 ? WF_MARCH_AXES_WAVES_P4 : 4;
+}
+template <int P, int BX, int BY, MarchGeom G>
+__global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
     int nx, int ny, int nz, int lz, int lz0, const double2* __restrict__ G6blk, const double* __restrict__ dD, DMat dm,
     double coeff, const double* __restrict__ x, double* __restrict__ y, const int32_t* __restrict__ items,
     int ablate_arg)
 {
   [[maybe_unused]] const int ablate = WF_ABLATE_FLAGS(ablate_arg);
+  constexpr bool PC = G != MarchGeom::point, AX = G == MarchGeom::cell_axes;
   constexpr int n = P + 1, n2 = n * n, nd = n * n2;
   constexpr int CB = BX * BY, NT = CB * n2;
   constexpr int TX = P * BX + 1, TY = P * BY + 1, TP = TX * TY;
@@ -93,9 +108,9 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
 #else
   __shared__ __attribute__((aligned(16))) double O[CB * P * n2];     // per-cell results, planes 0..P-1
 #endif
-  __shared__ __attribute__((aligned(16))) double Fr[CB * nd];
-  __shared__ __attribute__((aligned(16))) double Fs[CB * nd];
-  __shared__ __attribute__((aligned(16))) double sD[n * n];
+  __shared__ __attribute__((aligned(16))) double Fr[AX ? 1 : CB * nd];   // the axes form has no phase scratch
+  __shared__ __attribute__((aligned(16))) double Fs[AX ? 1 : CB * nd];
+  __shared__ __attribute__((aligned(16))) double sD[AX ? 1 : n * n];   // the axes form reads A from dm and dD
 
   const int t = threadIdx.x;
   const int nbx = (nx + BX - 1) / BX, nby = (ny + BY - 1) / BY;
@@ -140,7 +155,19 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
 #pragma unroll
     for (int k = 0; k < n; ++k) wk[k] = dD[2 * n2 + k];
   [[maybe_unused]] const int clc = cl < CB ? cl : CB - 1;
-  using GReg = std::conditional_t<PC, double2[3], double2[n][3]>;
+  // axes form: the thread's rows A[i][.], A[j][.] and the per-axis scales without G_c (coeff w_j, coeff w_i,
+  // coeff w_i w_j), held in VGPRs for the whole work item
+  [[maybe_unused]] double ai[n], aj[n];
+  [[maybe_unused]] const double sx0 = coeff * dD[2 * n2 + j], sy0 = coeff * dD[2 * n2 + i];
+  if constexpr (AX)
+#pragma unroll
+    for (int a = 0; a < n; ++a) {
+      ai[a] = dD[2 * n2 + n + i * n + a];
+      aj[a] = dD[2 * n2 + n + j * n + a];
+    }
+  // axes form: the registers carried from layer to layer are the three scales of stiffness_axes_cell, formed from
+  // the loaded G_c before the layer's atomics (see (c)); the other forms carry G_c or G itself
+  using GReg = std::conditional_t<AX, double[3], std::conditional_t<PC, double2[3], double2[n][3]>>;
 
   // ---- prologue: geometry of layer z0 -> registers, x planes 0..P -> LDS ------
   auto load_gc = [&](double2 (&g)[3], int kz) {
@@ -149,6 +176,11 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
     const double2* gp = G6blk + (blk * CB + clc) * 3;
 #pragma unroll
     for (int p = 0; p < 3; ++p) g[p] = gp[p];
+  };
+  auto axes_scales = [&](double (&sc)[3], const double2 (&g)[3]) {
+    sc[0] = sx0 * g[0].x;   // coeff G00 w_j
+    sc[1] = sy0 * g[1].y;   // coeff G11 w_i
+    sc[2] = cw * g[2].y;    // coeff G22 w_i w_j
   };
   auto load_g = [&](double2 (&g)[n][3], int kz, int k0 = 0, int k1 = P + 1) {
     size_t blk = (size_t)Bx + (size_t)nbx * (By + (size_t)nby * kz);
@@ -173,11 +205,16 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
   // (P4: 0.2209 -> 0.2182 ms; P2 has a third of the geometry per layer and was 5 % slower with it)
   constexpr int G1 = P >= 4 ? (n + 1) / 3 : n, G2 = P >= 4 ? (2 * n + 1) / 3 : n;
   GReg gA, gB;
-  if constexpr (PC)
+  if constexpr (AX) {
+    double2 g0[3];
+    load_gc(g0, z0);
+    axes_scales(gA, g0);
+  } else if constexpr (PC)
     load_gc(gA, z0);
   else
     load_g(gA, z0);
-  if (t < n * n) sD[t] = dD[t];
+  if constexpr (!AX)
+    if (t < n * n) sD[t] = dD[t];
 #if WF_MARCH_TILE_ADD
   for (int e = t; e < P * TP; e += 256) O[e] = 0.0;
 #endif
@@ -230,7 +267,10 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
 #pragma unroll
       for (int m = 0; m < NPOS; ++m) xn[m] = (ablate & 4) ? 1.0 + m : xb[poff[m] >= 0 ? poff[m] : poff0];
     }
-    if constexpr (PC)
+    [[maybe_unused]] double2 gl[3];
+    if constexpr (AX)
+      load_gc(gl, kzn);      // turned into the scales gnext in (c)
+    else if constexpr (PC)
       load_gc(gnext, kzn);   // 48 B: the last layer re-reads its own
     else if (has_next)
       load_g(gnext, kzn, 0, G1);   // uniform branch; a self-prefetch in the last layer would re-read 1/lz of the geometry
@@ -238,7 +278,9 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
     WF_MTR(1);
     // (b) element kernels of the layer
     double out[n];
-    if constexpr (PC) {
+    if constexpr (AX) {
+      stiffness_axes_cell<P>(Uc, TP, TX, dm, ai, aj, wk, gcur[0], gcur[1], gcur[2], i, j, active, out);
+    } else if constexpr (PC) {
       double ft[n];
       double2 gcw[3];
 #pragma unroll
@@ -310,6 +352,13 @@ __global__ __launch_bounds__(256, PC ? march_cell_waves(P) : 2) void k_stiffness
         if (pos < P * TP) Ux[TP + pos] = poff[m] >= 0 ? xn[m] : 0.0;
       }
 #endif
+    }
+    // axes form: consume the G_c loads here too.  Consumed in the next layer's element pass instead, their wait
+    // (vmcnt counts loads and atomics in one queue) also waited for this layer's atomics.  The empty asm pins the
+    // products here: without it they were sunk below the atomics.
+    if constexpr (AX) {
+      axes_scales(gnext, gl);
+      __asm__ volatile("" : "+v"(gnext[0]), "+v"(gnext[1]), "+v"(gnext[2]));
     }
     __builtin_amdgcn_sched_barrier(0);   // keep the LDS writes (and the wait for xn) above the atomics
     if constexpr (!PC)
@@ -415,20 +464,26 @@ static int march_ablate()
 }
 
 template <int P, int BX, int BY>
-static int launch_march_t(int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk, const double* d_Gcell,
-                          const double* d_D, const DMat& dm, double coeff, const double* d_x,
+static int launch_march_t(MarchGeom geom, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,
+                          const double* d_Gcell, const double* d_D, const DMat& dm, double coeff, const double* d_x,
                           double* d_y, const int32_t* d_items, int nitems, hipStream_t s)
 {
   const int ncols = ((nx + BX - 1) / BX) * ((ny + BY - 1) / BY);
   const int nseg = 1 + (std::max(nz - lz0, 0) + lz - 1) / lz;
   const int nwg = d_items ? nitems : ncols * nseg;
   if (nwg == 0) return WF_OK;
-  if (d_Gcell)
-    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, true>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0,
-                       reinterpret_cast<const double2*>(d_Gcell), d_D, dm, coeff, d_x, d_y, d_items, march_ablate());
+  if (geom == MarchGeom::cell_axes)
+    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, MarchGeom::cell_axes>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny,
+                       nz, lz, lz0, reinterpret_cast<const double2*>(d_Gcell), d_D, dm, coeff, d_x, d_y, d_items,
+                       march_ablate());
+  else if (geom == MarchGeom::cell)
+    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, MarchGeom::cell>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz,
+                       lz, lz0, reinterpret_cast<const double2*>(d_Gcell), d_D, dm, coeff, d_x, d_y, d_items,
+                       march_ablate());
   else
-    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, false>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0,
-                       reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, d_items, march_ablate());
+    hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, MarchGeom::point>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz,
+                       lz, lz0, reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, d_items,
+                       march_ablate());
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error(std::string("stiffness_march launch failed: ") + hipGetErrorString(e));
@@ -457,10 +512,10 @@ bool march_variant(int P, int variant, int* bx, int* by)
 }
 
 #define WF_MARCH_CASE(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return launch_march_t<PP, BXX, BYY>(nx, ny, nz, lz, lz0, d_G6blk, d_Gcell, d_D, dm, coeff, d_x, d_y, d_items, nitems, s);
+  if (P == PP && variant == V) return launch_march_t<PP, BXX, BYY>(geom, nx, ny, nz, lz, lz0, d_G6blk, d_Gcell, d_D, dm, coeff, d_x, d_y, d_items, nitems, s);
 
-int launch_stiffness_march(int P, int variant, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,
-                           const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
+int launch_stiffness_march(int P, int variant, MarchGeom geom, int nx, int ny, int nz, int lz, int lz0,
+                           const double* d_G6blk, const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
                            const double* d_x, double* d_y, const int32_t* d_items, int nitems, hipStream_t s)
 {
   if ((size_t)nx * ny * nz == 0) return WF_OK;
@@ -475,21 +530,24 @@ int launch_stiffness_march(int P, int variant, int nx, int ny, int nz, int lz, i
 // Workgroups of the (P, variant) kernel resident on the device at once (occupancy query x CUs; the z
 // segmentation of wf_op_create_box runs its work items in rounds of this many).  0 if the query fails.
 template <int P, int BX, int BY>
-static int march_resident_t(bool per_cell)
+static int march_resident_t(MarchGeom geom)
 {
   int dev = 0, cus = 0, per_cu = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
     return 0;
-  const hipError_t e = per_cell
-                           ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, true>, 256, 0)
-                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, false>, 256, 0);
+  const hipError_t e =
+      geom == MarchGeom::cell_axes
+          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, MarchGeom::cell_axes>, 256, 0)
+      : geom == MarchGeom::cell
+          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, MarchGeom::cell>, 256, 0)
+          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, MarchGeom::point>, 256, 0);
   return e == hipSuccess ? per_cu * cus : 0;
 }
 
 #define WF_MARCH_RES(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return march_resident_t<PP, BXX, BYY>(per_cell);
+  if (P == PP && variant == V) return march_resident_t<PP, BXX, BYY>(geom);
 
-int march_resident(int P, int variant, bool per_cell)
+int march_resident(int P, int variant, MarchGeom geom)
 {
   WF_MARCH_RES(1, 0, 8, 8) WF_MARCH_RES(1, 1, 4, 4) WF_MARCH_RES(1, 2, 8, 4)
   WF_MARCH_RES(2, 0, 5, 5) WF_MARCH_RES(2, 1, 3, 3) WF_MARCH_RES(2, 2, 7, 4)

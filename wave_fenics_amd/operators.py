@@ -131,9 +131,10 @@ def precompute_geometric_data(mesh, p: int, use_fabs: bool = True, clamp: bool =
 # operator handles
 # ---------------------------------------------------------------------------
 def make_tuning(tuning) -> "_lib.Tuning | None":
-    """wf_tuning from a dict (kernel=, variant=, lz=, lz0=, block=(bx, by, bz), keep_cell_order=, orient=, geometry=)
-    or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any", "elementwise", "march";
-    `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"."""
+    """wf_tuning from a dict (kernel=, variant=, lz=, lz0=, block=(bx, by, bz), keep_cell_order=, orient=, geometry=,
+    metric=) or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any", "elementwise",
+    "march"; `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"; `metric` a wf_metric_mode
+    value or one of "auto", "full", "axes"."""
     if tuning is None:
         return None
     if isinstance(tuning, _lib.Tuning):
@@ -152,10 +153,13 @@ def make_tuning(tuning) -> "_lib.Tuning | None":
     t.orient = int(tuning.get("orient", 0))
     g = tuning.get("geometry", 0)
     t.geometry = GEOMETRY_MODES[g] if isinstance(g, str) else int(g)
+    m = tuning.get("metric", 0)
+    t.metric = METRIC_MODES[m] if isinstance(m, str) else int(m)
     return t
 
 
 GEOMETRY_MODES = {"auto": 0, "per_point": 1, "per_cell": 2}
+METRIC_MODES = {"auto": 0, "full": 1, "axes": 2}
 KERNEL_NAMES = {0: "none", 1: "march_box", 2: "march_idx", 3: "batch_unique", 4: "box_block", 5: "diagonal",
                 6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise"}
 
@@ -192,6 +196,11 @@ class _Operator:
     def geometry(self) -> str:
         """How the stiffness geometry is stored (wf_op_info_t.geometry): "per_point", "per_cell" or "none"."""
         return {1: "per_point", 2: "per_cell"}.get(self.info.geometry, "none")
+
+    @property
+    def metric(self) -> str:
+        """Form of the per-cell box kernel (wf_op_info_t.metric): "full", "axes" or "none" (no per-cell geometry)."""
+        return {1: "full", 2: "axes"}.get(self.info.metric, "none")
 
     def _info(self):
         info = OpInfo()
