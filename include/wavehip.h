@@ -182,6 +182,7 @@ typedef struct {
                         cells to agree as given                                                     */
   int geometry;      /* box stiffness, P <= 4 marching kernel: wf_geometry_mode                     */
   int metric;        /* box stiffness with per-cell geometry: wf_metric_mode                        */
+  int update;        /* box stiffness, separable (axes) form: wf_update_mode                        */
 } wf_tuning;
 /* How a stiffness operator stores its geometry (wf_tuning.geometry, wf_op_info_t.geometry).  A box
  * whose cells are all affine (edge vectors along each reference axis bitwise equal, det J != 0, no
@@ -201,6 +202,16 @@ typedef enum {
   WF_METRIC_AXES = 2          /* the separable form; tuning: WF_ERR_INVALID if a G_c is not diagonal,
                                  WF_ERR_UNSUPPORTED without per-cell geometry                         */
 } wf_metric_mode;
+/* How the separable box kernel adds its result into y (wf_tuning.update, wf_op_info_t.update).  The atomic
+ * form adds each column's tile with fp64 atomics; the owner form gives every y entry to one thread, which
+ * gathers it from the cells around the node and reads and writes it once (no atomics, a fixed summation
+ * order: bitwise reproducible).  wf_tuning.variant then indexes the owner form's own cross-sections. */
+typedef enum {
+  WF_UPDATE_AUTO = 0,         /* tuning: owner where it measured faster (P4), else atomic             */
+  WF_UPDATE_NONE = 0,         /* info: not the separable box kernel                                     */
+  WF_UPDATE_ATOMIC = 1,       /* row atomics (also the only form of the full and per-point kernels)     */
+  WF_UPDATE_OWNER = 2         /* owner computes; tuning: WF_ERR_UNSUPPORTED unless the axes form runs   */
+} wf_update_mode;
 
 typedef struct {
   int kind;                    /* wf_op_kind                                    */
@@ -307,6 +318,7 @@ typedef struct {
   double plan_fill;      /* cells / cell slots of the plan's columns                     */
   int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
   int metric;            /* wf_metric_mode of the per-cell box kernel (0: none)          */
+  int update;            /* wf_update_mode of the separable box kernel (0: none)         */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
 int wf_op_destroy(wf_op* op);

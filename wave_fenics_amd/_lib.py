@@ -20,7 +20,7 @@ class Tuning(ctypes.Structure):
     """wf_tuning: explicit kernel selection / tuning (all zero = the library's choice)."""
     _fields_ = [("kernel", c_int), ("variant", c_int), ("lz", c_int), ("lz0", c_int),
                 ("bx", c_int), ("by", c_int), ("bz", c_int), ("keep_cell_order", c_int), ("orient", c_int),
-                ("geometry", c_int), ("metric", c_int)]
+                ("geometry", c_int), ("metric", c_int), ("update", c_int)]
 
 
 class OpDesc(ctypes.Structure):
@@ -53,6 +53,7 @@ class OpInfo(ctypes.Structure):
         ("items_interior", c_int), ("items_interface", c_int),
         ("kernel", c_int), ("plan_items", c_int), ("plan_patterns", c_int), ("plan_lz", c_int),
         ("plan_reoriented", c_int), ("plan_fill", c_double), ("geometry", c_int), ("metric", c_int),
+        ("update", c_int),
     ]
 
 

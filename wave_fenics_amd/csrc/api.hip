@@ -20,6 +20,8 @@ struct wf_op {
   DMat dm{};
   DMat am{};   // A = D^T diag(w) D: the 1-D operator of the separable box form (metric = WF_METRIC_AXES)
   int metric = WF_METRIC_NONE;   // wf_metric_mode of a per-cell box stiffness operator
+  int update = WF_UPDATE_NONE;   // wf_update_mode of the separable box kernel (owner: stiffness_march_owner.hip)
+  int obx = 0, oby = 0;          // owner form: its cross-section (bx, by stay the atomic one's, which blocks the geometry)
   int32_t* d_dofmap = nullptr;
   double* d_G6blk = nullptr;
   double* d_Gcell = nullptr;   // box of affine cells: G_c per cell, blocked like G6blk (stiffness_march.hip)
@@ -1023,15 +1025,32 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
       op->metric = diagonal && tun.metric != WF_METRIC_FULL ? WF_METRIC_AXES : WF_METRIC_FULL;
     }
     const MarchGeom geom = !per_cell ? MarchGeom::point : op->metric == WF_METRIC_AXES ? MarchGeom::cell_axes : MarchGeom::cell;
+    // update: the owner-computes form of the separable kernel (no atomics) where it measured faster -- P4 -- or on
+    // request; wf_tuning.variant then indexes its own cross-section table.  The per-cell geometry keeps the blocking
+    // of the atomic form's cross-section of the same index.
+    WF_REQUIRE(tun.update >= WF_UPDATE_AUTO && tun.update <= WF_UPDATE_OWNER, "wf_op_create_box: wf_tuning.update out of range");
+    if (geom == MarchGeom::cell_axes) {
+      const bool owner = tun.update == WF_UPDATE_OWNER || (tun.update == WF_UPDATE_AUTO && P == 4);
+      op->update = owner ? WF_UPDATE_OWNER : WF_UPDATE_ATOMIC;
+      if (owner && !march_owner_variant(P, op->march_variant, &op->obx, &op->oby)) {
+        set_error("wf_op_create_box: wf_tuning.variant out of range");
+        return WF_ERR_INVALID;
+      }
+    } else if (tun.update == WF_UPDATE_OWNER) {
+      set_error("wf_op_create_box: the owner update needs the separable (axes) form of the marching kernel");
+      return WF_ERR_UNSUPPORTED;
+    }
+    const bool owner = op->update == WF_UPDATE_OWNER;
     if (op->march) {
-      const int ncols = ((nx + op->bx - 1) / op->bx) * ((ny + op->by - 1) / op->by);
+      const int ncols = owner ? march_owner_columns(P, P * op->obx, P * op->oby, nx, ny)
+                              : ((nx + op->bx - 1) / op->bx) * ((ny + op->by - 1) / op->by);
       // z segmentation: work items = columns x segments run in rounds of the resident workgroups (occupancy
       // query of the kernel that launches: 2 per CU for the per-point P4 kernel, 3 for the full per-cell one and 3 for
       // the axes one); each item pays ~1.5 layers of
       // pipeline fill.  Pick the segment length that minimises rounds * (lz + 1.5).
-      long resident = op->march_variant != kKsVariant
-                          ? march_resident(P, op->march_variant, geom)
-                          : march_ks_resident(P, op->bx, op->by);
+      long resident = owner                                ? march_owner_resident(P, op->march_variant)
+                      : op->march_variant != kKsVariant ? march_resident(P, op->march_variant, geom)
+                                                         : march_ks_resident(P, op->bx, op->by);
       if (resident <= 0) resident = 512;
       double best = 1e300;
       op->lz = nz;
@@ -1150,6 +1169,9 @@ static int launch_box_march(const wf_op* op, int lz0, const double* d_x, double*
   if (op->march_variant == kKsVariant)
     return launch_stiffness_march_ks_box(op->P, op->bx, op->by, op->nx, op->ny, op->nz, op->lz, lz0, op->d_G6blk, op->d_D, op->dm, op->coeff,
                                          d_x, d_y, d_items, nitems, s);
+  if (op->update == WF_UPDATE_OWNER)
+    return launch_stiffness_march_owner(op->P, op->march_variant, op->nx, op->ny, op->nz, op->lz, lz0, op->bx, op->by,
+                                        op->d_Gcell, op->d_D, op->am, op->coeff, d_x, d_y, d_items, nitems, s);
   const bool axes = op->metric == WF_METRIC_AXES;
   return launch_stiffness_march(op->P, op->march_variant,
                                 !op->d_Gcell ? MarchGeom::point : axes ? MarchGeom::cell_axes : MarchGeom::cell, op->nx,
@@ -1229,7 +1251,11 @@ int wf_op_set_ghost_faces(wf_op* op, int ghost_x0, int ghost_y0, int ghost_z0)
               "splits any marching operator)");
     return WF_ERR_UNSUPPORTED;
   }
-  const int nbx = (op->nx + op->bx - 1) / op->bx, nby = (op->ny + op->by - 1) / op->by;
+  // the owner form's columns: lattice lines in pieces of P*obx x P*oby
+  const bool owner = op->update == WF_UPDATE_OWNER;
+  const int P = op->P, NX = P * op->nx + 1, NY = P * op->ny + 1;
+  const int nbx = owner ? (NX + P * op->obx - 1) / (P * op->obx) : (op->nx + op->bx - 1) / op->bx;
+  const int nby = owner ? (NY + P * op->oby - 1) / (P * op->oby) : (op->ny + op->by - 1) / op->by;
   // With a ghost plane below, the first z segment is kept short (wf_tuning.lz0, default 3 layers):
   // only its first layer reads the ghost plane, but the whole segment has to wait for the halo, and
   // the less interface work there is the earlier the reverse exchange can start under the interior.
@@ -1240,8 +1266,11 @@ int wf_op_set_ghost_faces(wf_op* op, int ghost_x0, int ghost_y0, int ghost_z0)
   for (int seg = 0; seg < nseg; ++seg)
     for (int col = 0; col < ncols; ++col) {
       const int Bx = col % nbx, By = col / nbx;
-      // a work item is "interface" when it reads a ghost plane of x / adds into a ghost plane of y
-      const bool iface = (ghost_x0 && Bx == 0) || (ghost_y0 && By == 0) || (ghost_z0 && seg == 0);
+      // a work item is "interface" when it reads a ghost plane of x / adds into a ghost plane of y.  The owner form
+      // reads P lattice lines / planes below what it owns: [I0 - P, ..] x [J0 - P, ..] x [P z0 - P, ..]
+      const int z0 = seg == 0 ? 0 : op->lz0_split + (seg - 1) * op->lz;
+      const bool iface = owner ? (ghost_x0 && P * op->obx * Bx <= P) || (ghost_y0 && P * op->oby * By <= P) || (ghost_z0 && z0 <= 1)
+                               : (ghost_x0 && Bx == 0) || (ghost_y0 && By == 0) || (ghost_z0 && seg == 0);
       items[iface ? 1 : 0].push_back(col + ncols * seg);
     }
   return set_item_lists(op, items);
@@ -1272,17 +1301,23 @@ int wf_op_set_ghost_dofs(wf_op* op, const int32_t* h_ghost_positions, int32_t ng
     for (size_t g = 0; g < plane && !gz; ++g) gz = ghost[g] != 0;
     op->lz0_split = op->lz;
     if (gz) op->lz0_split = std::max(1, std::min(op->tun.lz0 > 0 ? op->tun.lz0 : 3, op->lz));
-    const int nbx = (op->nx + op->bx - 1) / op->bx, nby = (op->ny + op->by - 1) / op->by;
+    // the owner form's columns are pieces of P*obx x P*oby lattice lines; its footprint reaches P lines / planes below
+    // what it owns: [I0 - P, I0 + P obx] x [J0 - P, J0 + P oby] x [P z0 - P, P z1]
+    const bool owner = op->update == WF_UPDATE_OWNER;
+    const int cbx = owner ? op->obx : op->bx, cby = owner ? op->oby : op->by;   // cells per column
+    const int LXo = P * cbx, LYo = P * cby, halo = owner ? P : 0;
+    const int nbx = owner ? (NX + LXo - 1) / LXo : (op->nx + op->bx - 1) / op->bx;
+    const int nby = owner ? (NY + LYo - 1) / LYo : (op->ny + op->by - 1) / op->by;
     const int ncols = nbx * nby, nseg = 1 + (std::max(op->nz - op->lz0_split, 0) + op->lz - 1) / op->lz;
     for (int seg = 0; seg < nseg; ++seg) {
       const int z0 = seg == 0 ? 0 : op->lz0_split + (seg - 1) * op->lz;
       const int z1 = std::min(op->nz, seg == 0 ? op->lz0_split : z0 + op->lz);
       for (int col = 0; col < ncols; ++col) {
         const int Bx = col % nbx, By = col / nbx;
-        const int I0 = P * Bx * op->bx, J0 = P * By * op->by;
-        const int I1 = std::min(NX - 1, I0 + P * op->bx), J1 = std::min(NY - 1, J0 + P * op->by);
+        const int I0 = std::max(0, P * Bx * cbx - halo), J0 = std::max(0, P * By * cby - halo);
+        const int I1 = std::min(NX - 1, P * Bx * cbx + P * cbx), J1 = std::min(NY - 1, P * By * cby + P * cby);
         bool iface = false;
-        for (int K = P * z0; K <= P * z1 && !iface; ++K)
+        for (int K = std::max(0, P * z0 - halo); K <= P * z1 && !iface; ++K)
           for (int J = J0; J <= J1 && !iface; ++J) {
             const char* row = &ghost[(size_t)I0 + (size_t)NX * J + plane * K];
             for (int I = 0; I <= I1 - I0; ++I)
@@ -1369,6 +1404,7 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   info->geometry = (op->dense || op->d_Gcell) ? WF_GEOMETRY_PER_CELL
                    : op->kind == WF_OP_STIFFNESS ? WF_GEOMETRY_PER_POINT : WF_GEOMETRY_AUTO;
   info->metric = op->d_Gcell ? op->metric : WF_METRIC_NONE;
+  info->update = op->d_Gcell ? op->update : WF_UPDATE_NONE;
   return WF_OK;
 }
 

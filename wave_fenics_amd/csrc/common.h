@@ -100,6 +100,16 @@ int launch_stiffness_march(int P, int variant, MarchGeom geom, int nx, int ny, i
                            const double* d_G6blk, const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
                            const double* d_x, double* d_y, const int32_t* d_items, int nitems, hipStream_t s);
 int march_resident(int P, int variant, MarchGeom geom);   // workgroups resident on the device (occupancy query)
+// Owner-computes form of cell_axes (stiffness_march_owner.hip): every y entry read and written once by its owning thread,
+// no atomics.  Its own cross-section table (march_owner_variant); columns = lattice lines in pieces of P*BX x P*BY.
+bool march_owner_variant(int P, int variant, int* bx, int* by);
+int march_owner_columns(int P, int lx, int ly, int nx, int ny);
+// d_Gcell blocked by the atomic form's cross-section gbx x gby
+int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int lz, int lz0, int gbx, int gby,
+                                 const double* d_Gcell,
+                                 const double* d_D, const DMat& am, double coeff, const double* d_x, double* d_y,
+                                 const int32_t* d_items, int nitems, hipStream_t s);
+int march_owner_resident(int P, int variant);   // workgroups resident on the device (occupancy query)
 // indexed marching kernels for arbitrary dofmaps (generic_plan.cpp, stiffness_march_idx.hip, stiffness_march_ks.hip)
 struct MarchPlan {
   bool ok = false;                      // false: the mesh does not tile into lattice columns

@@ -1,0 +1,396 @@
+// Box stiffness, separable (cell_axes) form, owner-computes update: y += -c0^2 K x without atomics.
+//
+// Every lattice dof of y is owned by exactly one thread, which reads it once and writes it once, with
+// plain loads and stores.  The result at node (I, J, K) is gathered from the (at most 8) cells that
+// contain it ("r06"); with the GLL rule at the nodes and a diagonal G_c per cell:
+//   y(I,J,K) += sum_{cx ∋ I} (A[i_cx] . x(cx-line along x)) coeff w_j w_k sum_{cy ∋ J, cz ∋ K} G00(cx,cy,cz)
+//             + sum_{cy ∋ J} (A[j_cy] . x(cy-line along y)) coeff w_i w_k sum_{cx ∋ I, cz ∋ K} G11(cx,cy,cz)
+//             + sum_{cz ∋ K} (A[k_cz] . x(cz-line along z)) coeff w_i w_j sum_{cx ∋ I, cy ∋ J} G22(cx,cy,cz)
+// with A = D^T diag(w) D and w_0 = w_P (symmetric rule), so the weight of a face node is the same in both cells.
+//
+// One 256-thread workgroup owns the lattice lines I in [I0, I0 + P BX), J in [J0, J0 + P BY) of a z segment
+// (a column of BX x BY cells; the lattice is cut into such pieces from I = 0, so the closing line I = NX - 1 of a
+// mesh whose nx is a multiple of BX falls into a column of its own) and marches in z, one thread per (I, J) line:
+//   * z term: the thread's own x line, in a register window of 2P + 1 planes that rotates by P per layer;
+//   * x and y terms: the layer's P + 1 x planes staged in LDS with a halo of P lattice lines on the -x / -y sides
+//     and the closing line on the +x / +y sides (a (P BX + P + 1) x (P BY + P + 1) rectangle);
+//   * scales: the G_c of the (BX + 1) x (BY + 1) cells around the column (halo cells included) staged in LDS per
+//     layer; each thread sums the ones its node touches into five scales per layer and carries the previous layer's
+//     for the shared plane k = 0;
+//   * x, y and G_c of the next layer are prefetched one layer ahead as unconditional loads on clamped addresses, and
+//     the layer body exists as two compile-time copies (has_next), as in k_stiffness_march.
+// The summation order of every y entry is fixed, so the apply is bitwise reproducible.
+#include <cstdlib>
+
+#include <type_traits>
+
+#include "stiffness_core.h"
+
+namespace wf {
+
+#ifndef WF_OWNER_WAVES
+#define WF_OWNER_WAVES 2
+#endif
+
+template <int P, int BX, int BY>
+__global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
+    int nx, int ny, int nz, int lz, int lz0, int gbx, int gby, const double* __restrict__ Gc, const double* __restrict__ dD, DMat am,
+    double coeff, const double* __restrict__ x, double* __restrict__ y, const int32_t* __restrict__ items,
+    int ablate_arg)
+{
+  [[maybe_unused]] const int ablate = WF_ABLATE_FLAGS(ablate_arg);
+  constexpr int n = P + 1;
+  constexpr int LX = P * BX, LY = P * BY, NL = LX * LY;   // owned lines
+  constexpr int RX = LX + P + 1, RY = LY + P + 1, RP = RX * RY;   // staged rectangle of one plane
+  constexpr int NPF = (P * RP + 255) / 256;          // x prefetch positions per thread (planes 1..P)
+  constexpr int NPF0 = ((P + 1) * RP + 255) / 256;   // prologue positions (planes 0..P)
+  constexpr int NCP = (RP + 255) / 256;              // positions of one plane
+  constexpr int GCX = BX + 1, GC = GCX * (BY + 1), NG = 3 * GC;   // staged G00 | G11 | G22 of the cells
+  constexpr int NGL = (NG + 255) / 256;
+  static_assert(NL <= 256, "column does not fit a 256-thread workgroup");
+
+  // x planes 0..P of the layer + a dump row for positions past the rectangle (branchless rotate, see (c))
+  __shared__ __attribute__((aligned(16))) double Ux[(P + 1) * RP + 256];
+  __shared__ __attribute__((aligned(16))) double Gs[NGL * 256];
+
+  const int t = threadIdx.x;
+  const int NX = P * nx + 1, NY = P * ny + 1;
+  const size_t plane = (size_t)NX * NY;
+  const int nbxo = (NX + LX - 1) / LX, nbyo = (NY + LY - 1) / LY, ncols = nbxo * nbyo;
+  const int item = items ? items[blockIdx.x] : (int)blockIdx.x;
+  const int col = item % ncols, seg = item / ncols;
+  const int Bx = col % nbxo, By = col / nbxo;
+  const int z0 = seg == 0 ? 0 : lz0 + (seg - 1) * lz, z1 = min(nz, seg == 0 ? lz0 : z0 + lz);
+  const int I0 = LX * Bx, J0 = LY * By, cx0 = BX * Bx, cy0 = BY * By;
+
+  // ---- the thread's line ---------------------------------------------------
+  const int tt = t < NL ? t : NL - 1;
+  const int ti = tt % LX, tj = tt / LX, i = ti % P, j = tj % P;
+  const int I = I0 + ti, J = J0 + tj;
+  const bool own = t < NL && I < NX && J < NY;
+  const int32_t yoff = own ? (int32_t)((size_t)I + (size_t)NX * J) : (int32_t)((size_t)I0 + (size_t)NX * J0);
+  // LDS: own position, first node of the +x cell in the thread's row, first node of the +y cell in its column
+  const int rown = (tj + P) * RX, cown = ti + P;
+  const int cR = P + ti - i, rA = P + tj - j;
+
+  // rows of A (the thread's i and j), 1-D weights, coefficient products
+  double ai[n], aj[n], wk[n];
+#pragma unroll
+  for (int a = 0; a < n; ++a) {
+    wk[a] = dD[2 * n * n + a];
+    ai[a] = dD[2 * n * n + n + i * n + a];
+    aj[a] = dD[2 * n * n + n + j * n + a];
+  }
+  const double cwj = coeff * wk[j], cwi = coeff * wk[i], cwij = coeff * wk[i] * wk[j];
+
+  // ---- staged positions (identical in every layer) -------------------------
+  // position m: (I0 - P + c, J0 - P + r, pl); prefetch of the next layer: plane P*(kz+1) + pl + 1 -> LDS slot pl + 1
+  int32_t poff[NPF];   // lattice offset relative to plane P*kz' + 1; -1 = outside the mesh or past the rectangle
+#pragma unroll
+  for (int m = 0; m < NPF; ++m) {
+    const int pos = t + 256 * m;
+    const int pl = pos / RP, r = pos % RP, II = I0 - P + r % RX, JJ = J0 - P + r / RX;
+    poff[m] = -1;
+    if (pos < P * RP && II >= 0 && II < NX && JJ >= 0 && JJ < NY)
+      poff[m] = (int32_t)((size_t)II + (size_t)NX * JJ + plane * pl);
+  }
+  const int32_t pclamp = (int32_t)((size_t)I0 + (size_t)NX * J0);   // first owned position: always inside the mesh
+
+  // G_c entries staged by this thread: entry e = comp * GC + cell, cell (lcx, lcy) = (cx0 - 1 + lcx, cy0 - 1 + lcy).
+  // Gc is blocked by the atomic form's cross-section gbx x gby (the operator's geometry does not depend on the update).
+  const int nbx = (nx + gbx - 1) / gbx, nby = (ny + gby - 1) / gby;
+  const size_t gstride = (size_t)nbx * nby * (gbx * gby) * 6;   // one cell layer of the blocked layout
+  size_t gbase[NGL];
+  bool gval[NGL];
+#pragma unroll
+  for (int q = 0; q < NGL; ++q) {
+    const int e = t + 256 * q, comp = e / GC, c = e % GC;
+    const int cx = cx0 - 1 + c % GCX, cy = cy0 - 1 + c / GCX;
+    gval[q] = e < NG && cx >= 0 && cx < nx && cy >= 0 && cy < ny;
+    const int cxc = gval[q] ? cx : 0, cyc = gval[q] ? cy : 0;
+    gbase[q] = (((size_t)(cxc / gbx) + (size_t)nbx * (cyc / gby)) * (gbx * gby) + cxc % gbx + gbx * (cyc % gby)) * 6 +
+               (comp == 0 ? 0 : comp == 1 ? 3 : 5);
+  }
+  auto load_g = [&](double (&g)[NGL], int kz) {
+#pragma unroll
+    for (int q = 0; q < NGL; ++q) g[q] = Gc[gbase[q] + gstride * kz];
+  };
+  auto store_g = [&](const double (&g)[NGL]) {
+#pragma unroll
+    for (int q = 0; q < NGL; ++q) Gs[t + 256 * q] = gval[q] ? g[q] : 0.0;
+  };
+  // the thread's five scales of one layer from the staged G_c: x term (+x cell, -x cell), y term (+y, -y), z term
+  const bool mi = i == 0, mj = j == 0;
+  const int lR = (ti - i) / P + 1, lA = (tj - j) / P + 1;   // staged cell of the +x / +y cell
+  auto scales = [&](double (&s)[5]) {
+    const double* g0 = Gs;
+    const double* g1 = Gs + GC;
+    const double* g2 = Gs + 2 * GC;
+    const int AR = lA * GCX + lR, AL = AR - 1, BR = AR - GCX, BL = BR - 1;
+    const double x_ar = g0[AR], x_br = g0[BR], x_al = g0[AL], x_bl = g0[BL];
+    const double y_ar = g1[AR], y_al = g1[AL], y_br = g1[BR], y_bl = g1[BL];
+    const double z_ar = g2[AR], z_al = g2[AL], z_br = g2[BR], z_bl = g2[BL];
+    s[0] = cwj * (mj ? x_ar + x_br : x_ar);
+    s[1] = mi ? cwj * (mj ? x_al + x_bl : x_al) : 0.0;
+    s[2] = cwi * (mi ? y_ar + y_al : y_ar);
+    s[3] = mj ? cwi * (mi ? y_br + y_bl : y_br) : 0.0;
+    const double za = mi ? z_ar + z_al : z_ar, zb = mi ? z_br + z_bl : z_br;
+    s[4] = cwij * (mj ? za + zb : za);
+  };
+
+  // ---- prologue: x planes 0..P of layer z0 -> LDS, the scales of layers z0 - 1 and z0, y of layer z0 ------------
+  double xz[2 * P + 1];   // x(I, J, P*kz - P + m)
+  double sc[5], sf[4], spz;   // scales of the layer; the shared plane's x / y scales (this + previous layer); previous z
+  double yA[P], yB[P];
+  {
+    double gp[NGL], gcur[NGL];
+    load_g(gp, z0 > 0 ? z0 - 1 : z0);
+    load_g(gcur, z0);
+#pragma unroll
+    for (int m = 0; m < P; ++m) {
+      const long K = (long)P * z0 - P + m;
+      const double v = x[plane * (size_t)(K >= 0 ? K : 0) + yoff];
+      xz[m] = K >= 0 ? v : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < P; ++k) yA[k] = (ablate & 1) ? 0.0 : y[plane * (size_t)(P * z0 + k) + yoff];
+    const size_t base = plane * (size_t)(P * z0);
+#pragma unroll
+    for (int m = 0; m < NPF0; ++m) {
+      const int pos = t + 256 * m;
+      if (pos < (P + 1) * RP) {
+        const int pl = pos / RP, r = pos % RP, II = I0 - P + r % RX, JJ = J0 - P + r / RX;
+        double v = 0.0;
+        if (II >= 0 && II < NX && JJ >= 0 && JJ < NY) v = x[base + (size_t)II + (size_t)NX * JJ + plane * pl];
+        Ux[pos] = v;
+      }
+    }
+    store_g(gp);
+    __syncthreads();
+    double sp[5];
+    scales(sp);
+    if (z0 == 0)
+#pragma unroll
+      for (int q = 0; q < 5; ++q) sp[q] = 0.0;
+    __syncthreads();
+    store_g(gcur);
+    __syncthreads();
+    scales(sc);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sf[q] = sc[q] + sp[q];
+    spz = sp[4];
+#pragma unroll
+    for (int m = 0; m <= P; ++m) xz[P + m] = Ux[m * RP + rown + cown];
+  }
+
+  // the x / y terms of one plane (LDS slot k): sx, sy = the scales of the +x / -x / +y / -y cells
+  auto xy_terms = [&](int k, double s0, double s1, double s2, double s3) {
+    const double* L = Ux + k * RP;
+    double xr = 0.0, xl = 0.0, ya = 0.0, yb = 0.0;
+#pragma unroll
+    for (int a = 0; a < n; ++a) {
+      xr += ai[a] * L[rown + cR + a];
+      xl += am.v[P * n + a] * L[rown + cR - P + a];
+      ya += aj[a] * L[(rA + a) * RX + cown];
+      yb += am.v[P * n + a] * L[(rA - P + a) * RX + cown];
+    }
+    return xr * s0 + xl * s1 + ya * s2 + yb * s3;
+  };
+  auto store_y = [&](size_t K, double v) {
+    double* dst = y + plane * K + yoff;
+    if (ablate & 1) {
+      if (v == 1.2345e300) *dst = v;
+    } else if (own) {
+      *dst = v;
+    }
+  };
+
+  // One layer: owned planes P*kz .. P*kz + P - 1.  ycur holds their y (prefetched), ynext receives the next layer's.
+  auto layer = [&](auto hn_tag, double (&ycur)[P], double (&ynext)[P], int kz) {
+    constexpr bool has_next = decltype(hn_tag)::value;
+    // (a) next layer's x planes, G_c and y: in flight during this layer's arithmetic.  Unconditional loads on
+    // clamped addresses; what is live is decided where the registers are consumed, in (c).
+    [[maybe_unused]] double xn[NPF], gn[NGL];
+    if constexpr (has_next) {
+      const double* xb = x + plane * (size_t)(P * (kz + 1) + 1);
+#pragma unroll
+      for (int m = 0; m < NPF; ++m) xn[m] = xb[poff[m] >= 0 ? poff[m] : pclamp];
+      load_g(gn, kz + 1);
+#pragma unroll
+      for (int k = 0; k < P; ++k) ynext[k] = (ablate & 1) ? 0.0 : y[plane * (size_t)(P * (kz + 1) + k) + yoff];
+    }
+
+    // (b) the P owned planes.  Plane 0 is shared with the layer below: x / y scales of both layers, two z terms.
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      double zc = 0.0;
+#pragma unroll
+      for (int a = 0; a < n; ++a) zc += am.v[k * n + a] * xz[P + a];
+      double v;
+      if (k == 0) {
+        double zp = 0.0;
+#pragma unroll
+        for (int a = 0; a < n; ++a) zp += am.v[P * n + a] * xz[a];
+        v = wk[0] * xy_terms(0, sf[0], sf[1], sf[2], sf[3]) + zc * sc[4] + zp * spz;
+      } else {
+        v = wk[k] * xy_terms(k, sc[0], sc[1], sc[2], sc[3]) + zc * sc[4];
+      }
+      store_y((size_t)(P * kz + k), ycur[k] + v);
+    }
+
+    if constexpr (has_next) {
+      double xcp[NCP];
+#pragma unroll
+      for (int m = 0; m < NCP; ++m) {
+        const int pos = t + 256 * m;
+        xcp[m] = pos < RP ? Ux[P * RP + pos] : 0.0;
+      }
+      __syncthreads();
+      // (c) rotate: plane P -> slot 0, the prefetched planes -> slots 1..P, G_c of the next layer.  No per-lane
+      // branch between the loads and these stores: a thread's last position past the rectangle goes to the dump row.
+#pragma unroll
+      for (int m = 0; m < NCP; ++m) {
+        const int pos = t + 256 * m;
+        Ux[(256 * (m + 1) <= RP || pos < RP) ? pos : (P + 1) * RP + t] = xcp[m];
+      }
+#pragma unroll
+      for (int m = 0; m < NPF; ++m) {
+        const int pos = t + 256 * m;
+        Ux[(256 * (m + 1) <= P * RP || pos < P * RP) ? RP + pos : (P + 1) * RP + t] = poff[m] >= 0 ? xn[m] : 0.0;
+      }
+      store_g(gn);
+      __syncthreads();
+      // the z window rotates by P; the new scales, the shared plane's sums
+#pragma unroll
+      for (int m = 0; m <= P; ++m) xz[m] = xz[m + P];
+#pragma unroll
+      for (int m = 1; m <= P; ++m) xz[P + m] = Ux[m * RP + rown + cown];
+      double sn[5];
+      scales(sn);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sf[q] = sn[q] + sc[q];
+      spz = sc[4];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) sc[q] = sn[q];
+    }
+  };
+
+  using HasNext = std::integral_constant<bool, true>;
+  using IsLast = std::integral_constant<bool, false>;
+  // unrolled by two: the y registers swap roles instead of being copied (a copy would wait for the prefetch)
+  for (int kz = z0; kz < z1; kz += 2) {
+    if (kz + 1 < z1) {
+      layer(HasNext{}, yA, yB, kz);
+      if (kz + 2 < z1)
+        layer(HasNext{}, yB, yA, kz + 1);
+      else
+        layer(IsLast{}, yB, yA, kz + 1);
+    } else {
+      layer(IsLast{}, yA, yB, kz);
+    }
+  }
+
+  // ---- epilogue: the mesh's top plane P*nz (LDS slot P), owned by the last segment: the last layer's cells only --
+  if (z1 == nz) {
+    double zp = 0.0;
+#pragma unroll
+    for (int a = 0; a < n; ++a) zp += am.v[P * n + a] * xz[P + a];
+    const double v = wk[0] * xy_terms(P, sc[0], sc[1], sc[2], sc[3]) + zp * sc[4];
+    const size_t K = (size_t)P * nz;
+    const double y0 = (ablate & 1) ? 0.0 : y[plane * K + yoff];
+    store_y(K, y0 + v);
+  }
+}
+
+static int owner_ablate()
+{
+#ifdef WF_DIAG
+  const char* e = std::getenv("WF_ABLATE");
+  return e ? std::atoi(e) : 0;
+#else
+  return 0;
+#endif
+}
+
+template <int P, int BX, int BY>
+static int launch_owner_t(int nx, int ny, int nz, int lz, int lz0, int gbx, int gby, const double* d_Gcell, const double* d_D,
+                          const DMat& am, double coeff, const double* d_x, double* d_y, const int32_t* d_items, int nitems,
+                          hipStream_t s)
+{
+  const int nseg = 1 + (std::max(nz - lz0, 0) + lz - 1) / lz;
+  const int nwg = d_items ? nitems : march_owner_columns(P, P * BX, P * BY, nx, ny) * nseg;
+  if (nwg == 0) return WF_OK;
+  hipLaunchKernelGGL((k_stiffness_owner<P, BX, BY>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0, gbx, gby, d_Gcell,
+                     d_D, am, coeff, d_x, d_y, d_items, owner_ablate());
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_error(std::string("stiffness_march (owner) launch failed: ") + hipGetErrorString(e));
+    return WF_ERR_HIP;
+  }
+  return WF_OK;
+}
+
+// Columns of the owner form: the lattice lines cut into pieces of P*BX x P*BY from (0, 0).
+int march_owner_columns(int P, int lx, int ly, int nx, int ny)
+{
+  const int NX = P * nx + 1, NY = P * ny + 1;
+  return ((NX + lx - 1) / lx) * ((NY + ly - 1) / ly);
+}
+
+// The (BX, BY) column cross-sections of the owner form, per degree (index = wf_tuning.variant - 1 when the owner
+// form runs; march_variant is the table of the atomic forms).  P*BX x P*BY owned lines, at most 256: square, wide, tall.
+bool march_owner_variant(int P, int variant, int* bx, int* by)
+{
+  static const int tab[5][3][2] = {
+      {{0, 0}, {0, 0}, {0, 0}},
+      {{16, 16}, {32, 8}, {8, 32}},   // P1: 256 lines
+      {{8, 8}, {16, 4}, {4, 16}},     // P2: 256 lines
+      {{5, 5}, {7, 3}, {3, 7}},       // P3: 225 / 189 / 189 lines
+      {{4, 4}, {8, 2}, {2, 8}},       // P4: 256 lines; default index 1 (8x2), as the atomic 5x2
+  };
+  if (P < 1 || P > 4 || variant < 0 || variant > 2) return false;
+  *bx = tab[P][variant][0];
+  *by = tab[P][variant][1];
+  return true;
+}
+
+#define WF_OWNER_CASE(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return launch_owner_t<PP, BXX, BYY>(nx, ny, nz, lz, lz0, gbx, gby, d_Gcell, d_D, am, coeff, d_x, d_y, d_items, nitems, s);
+
+int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int lz, int lz0, int gbx, int gby,
+                                 const double* d_Gcell,
+                                 const double* d_D, const DMat& am, double coeff, const double* d_x, double* d_y,
+                                 const int32_t* d_items, int nitems, hipStream_t s)
+{
+  if ((size_t)nx * ny * nz == 0) return WF_OK;
+  WF_OWNER_CASE(1, 0, 16, 16) WF_OWNER_CASE(1, 1, 32, 8) WF_OWNER_CASE(1, 2, 8, 32)
+  WF_OWNER_CASE(2, 0, 8, 8) WF_OWNER_CASE(2, 1, 16, 4) WF_OWNER_CASE(2, 2, 4, 16)
+  WF_OWNER_CASE(3, 0, 5, 5) WF_OWNER_CASE(3, 1, 7, 3) WF_OWNER_CASE(3, 2, 3, 7)
+  WF_OWNER_CASE(4, 0, 4, 4) WF_OWNER_CASE(4, 1, 8, 2) WF_OWNER_CASE(4, 2, 2, 8)
+  set_error("stiffness_march (owner): unsupported degree/variant");
+  return WF_ERR_UNSUPPORTED;
+}
+
+template <int P, int BX, int BY>
+static int owner_resident_t()
+{
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_owner<P, BX, BY>, 256, 0);
+  return e == hipSuccess ? per_cu * cus : 0;
+}
+
+#define WF_OWNER_RES(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return owner_resident_t<PP, BXX, BYY>();
+
+int march_owner_resident(int P, int variant)
+{
+  WF_OWNER_RES(1, 0, 16, 16) WF_OWNER_RES(1, 1, 32, 8) WF_OWNER_RES(1, 2, 8, 32)
+  WF_OWNER_RES(2, 0, 8, 8) WF_OWNER_RES(2, 1, 16, 4) WF_OWNER_RES(2, 2, 4, 16)
+  WF_OWNER_RES(3, 0, 5, 5) WF_OWNER_RES(3, 1, 7, 3) WF_OWNER_RES(3, 2, 3, 7)
+  WF_OWNER_RES(4, 0, 4, 4) WF_OWNER_RES(4, 1, 8, 2) WF_OWNER_RES(4, 2, 2, 8)
+  return 0;
+}
+
+}  // namespace wf

@@ -132,9 +132,10 @@ def precompute_geometric_data(mesh, p: int, use_fabs: bool = True, clamp: bool =
 # ---------------------------------------------------------------------------
 def make_tuning(tuning) -> "_lib.Tuning | None":
     """wf_tuning from a dict (kernel=, variant=, lz=, lz0=, block=(bx, by, bz), keep_cell_order=, orient=, geometry=,
-    metric=) or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any", "elementwise",
-    "march"; `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"; `metric` a wf_metric_mode
-    value or one of "auto", "full", "axes"."""
+    metric=, update=) or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any",
+    "elementwise", "march"; `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"; `metric` a
+    wf_metric_mode value or one of "auto", "full", "axes"; `update` a wf_update_mode value or one of "auto", "atomic",
+    "owner"."""
     if tuning is None:
         return None
     if isinstance(tuning, _lib.Tuning):
@@ -155,11 +156,14 @@ def make_tuning(tuning) -> "_lib.Tuning | None":
     t.geometry = GEOMETRY_MODES[g] if isinstance(g, str) else int(g)
     m = tuning.get("metric", 0)
     t.metric = METRIC_MODES[m] if isinstance(m, str) else int(m)
+    u = tuning.get("update", 0)
+    t.update = UPDATE_MODES[u] if isinstance(u, str) else int(u)
     return t
 
 
 GEOMETRY_MODES = {"auto": 0, "per_point": 1, "per_cell": 2}
 METRIC_MODES = {"auto": 0, "full": 1, "axes": 2}
+UPDATE_MODES = {"auto": 0, "atomic": 1, "owner": 2}
 KERNEL_NAMES = {0: "none", 1: "march_box", 2: "march_idx", 3: "batch_unique", 4: "box_block", 5: "diagonal",
                 6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise"}
 
@@ -201,6 +205,12 @@ class _Operator:
     def metric(self) -> str:
         """Form of the per-cell box kernel (wf_op_info_t.metric): "full", "axes" or "none" (no per-cell geometry)."""
         return {1: "full", 2: "axes"}.get(self.info.metric, "none")
+
+    @property
+    def update(self) -> str:
+        """How the separable box kernel adds into y (wf_op_info_t.update): "atomic", "owner" or "none" (another
+        kernel)."""
+        return {1: "atomic", 2: "owner"}.get(self.info.update, "none")
 
     def _info(self):
         info = OpInfo()
