@@ -501,8 +501,11 @@ int wf_op_apply_overlapped(wf_op* op, wf_updater* u, double* d_x, double* d_y, v
     WF_HIP_CHECK(hipEventRecord(u->ev_interior, u->low_stream));
     if ((rc = fwd_begin(u, d_x, main, true)) != WF_OK || (rc = fwd_end(u, d_x, main, true)) != WF_OK) return rc;
     if ((rc = wf_op_apply_part(op, d_x, d_y, WF_PART_INTERFACE, main)) != WF_OK) return rc;
-    if ((rc = rev_begin(u, d_y, main, true)) != WF_OK || (rc = rev_end(u, d_y, main, true)) != WF_OK) return rc;
+    if ((rc = rev_begin(u, d_y, main, true)) != WF_OK) return rc;
+    // the reverse unpack adds into owned entries of y that the interior part may hold between its read and its
+    // write (the owner-computes box kernel updates y with plain loads and stores): it waits for the interior
     WF_HIP_CHECK(hipStreamWaitEvent(main, u->ev_interior, 0));
+    if ((rc = rev_end(u, d_y, main, true)) != WF_OK) return rc;
     return WF_OK;
   }
   WF_HIP_CHECK(hipEventRecord(u->ev_main, main));
@@ -510,8 +513,12 @@ int wf_op_apply_overlapped(wf_op* op, wf_updater* u, double* d_x, double* d_y, v
   // the side stream IS the communication stream here: exchanges are enqueued on it directly
   if ((rc = fwd_begin(u, d_x, side, true)) != WF_OK || (rc = fwd_end(u, d_x, side, true)) != WF_OK) return rc;
   if ((rc = wf_op_apply_part(op, d_x, d_y, WF_PART_INTERFACE, side)) != WF_OK) return rc;
-  if ((rc = rev_begin(u, d_y, side, true)) != WF_OK || (rc = rev_end(u, d_y, side, true)) != WF_OK) return rc;
+  if ((rc = rev_begin(u, d_y, side, true)) != WF_OK) return rc;
   if ((rc = wf_op_apply_part(op, d_x, d_y, WF_PART_INTERIOR, main)) != WF_OK) return rc;
+  // the reverse unpack waits for the interior part, as above
+  WF_HIP_CHECK(hipEventRecord(u->ev_interior, main));
+  WF_HIP_CHECK(hipStreamWaitEvent(side, u->ev_interior, 0));
+  if ((rc = rev_end(u, d_y, side, true)) != WF_OK) return rc;
   WF_HIP_CHECK(hipEventRecord(u->ev_side, side));
   WF_HIP_CHECK(hipStreamWaitEvent(main, u->ev_side, 0));
   return WF_OK;

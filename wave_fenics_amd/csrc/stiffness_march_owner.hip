@@ -28,8 +28,9 @@
 
 namespace wf {
 
+// workgroups per CU the register allocation must allow: three at P4 (<= 168 VGPRs, no scratch); P1-P3 fit more
 #ifndef WF_OWNER_WAVES
-#define WF_OWNER_WAVES 2
+#define WF_OWNER_WAVES 3
 #endif
 
 template <int P, int BX, int BY>
@@ -57,7 +58,11 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
   const int NX = P * nx + 1, NY = P * ny + 1;
   const size_t plane = (size_t)NX * NY;
   const int nbxo = (NX + LX - 1) / LX, nbyo = (NY + LY - 1) / LY, ncols = nbxo * nbyo;
-  const int item = items ? items[blockIdx.x] : (int)blockIdx.x;
+  // XCD-aware order: consecutive workgroups go round-robin to the 8 XCDs, so each XCD is given a contiguous run of
+  // items instead; the halo lines a column reads then mostly belong to columns on the same XCD, and its L2 serves them
+  const int nwg = (int)gridDim.x, xq = nwg / 8, xr = nwg % 8, xcd = (int)blockIdx.x % 8;
+  const int b = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (int)blockIdx.x / 8;
+  const int item = items ? items[b] : b;
   const int col = item % ncols, seg = item / ncols;
   const int Bx = col % nbxo, By = col / nbxo;
   const int z0 = seg == 0 ? 0 : lz0 + (seg - 1) * lz, z1 = min(nz, seg == 0 ? lz0 : z0 + lz);
@@ -154,16 +159,22 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
     }
 #pragma unroll
     for (int k = 0; k < P; ++k) yA[k] = (ablate & 1) ? 0.0 : y[plane * (size_t)(P * z0 + k) + yoff];
+    // every plane load is in flight before the first is consumed: unconditional loads on clamped addresses, then
+    // the LDS stores (positions past the rectangle go to the dump row), as in the rotate (c)
     const size_t base = plane * (size_t)(P * z0);
+    double xp[NPF0];
+    bool xin[NPF0];
 #pragma unroll
     for (int m = 0; m < NPF0; ++m) {
       const int pos = t + 256 * m;
-      if (pos < (P + 1) * RP) {
-        const int pl = pos / RP, r = pos % RP, II = I0 - P + r % RX, JJ = J0 - P + r / RX;
-        double v = 0.0;
-        if (II >= 0 && II < NX && JJ >= 0 && JJ < NY) v = x[base + (size_t)II + (size_t)NX * JJ + plane * pl];
-        Ux[pos] = v;
-      }
+      const int pl = pos / RP, r = pos % RP, II = I0 - P + r % RX, JJ = J0 - P + r / RX;
+      xin[m] = pos < (P + 1) * RP && II >= 0 && II < NX && JJ >= 0 && JJ < NY;
+      xp[m] = x[base + (xin[m] ? (size_t)II + (size_t)NX * JJ + plane * pl : (size_t)pclamp)];
+    }
+#pragma unroll
+    for (int m = 0; m < NPF0; ++m) {
+      const int pos = t + 256 * m;
+      Ux[(256 * (m + 1) <= (P + 1) * RP || pos < (P + 1) * RP) ? pos : (P + 1) * RP + t] = xin[m] ? xp[m] : 0.0;
     }
     store_g(gp);
     __syncthreads();

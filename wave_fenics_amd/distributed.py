@@ -400,8 +400,13 @@ def overlapped_apply(op, updater: VectorUpdater, x, y):
     with torch.cuda.stream(side):
         updater.update_fwd(x)
         op.apply_part(x, y, WF_PART_INTERFACE)
-        updater.update_rev(y)
+        updater.update_rev_begin(y)
     op.apply_part(x, y, WF_PART_INTERIOR)
+    # the reverse add lands on owned entries of y that the interior part may hold between its read and its write
+    # (the owner-computes box kernel updates y with plain loads and stores), so it waits for the interior part
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        updater.update_rev_end(y)
     main.wait_stream(side)
 
 
