@@ -10,8 +10,11 @@
 // than 1e-8 -- meaningful for the collocated rule (gll/gll), where both are the same
 // diagonal; for other rules the sums over all dofs (= the volume) are compared.
 //
+// --update auto|atomic|owner (--op stiffness) asks wf_op_create_box_tuned for that form of the separable box kernel
+// (wf_tuning.update): owner = every y entry read and written once by its owning thread, on a rectilinear box at P1 to P7.
+//
 //   operator_demo [--size N] [--degree P] [--op stiffness|mass|spectral|dense] [--reps R]
-//                 [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--check]
+//                 [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--update auto|atomic|owner] [--check]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -27,7 +30,7 @@ int main(int argc, char* argv[])
 {
   int Nx = 32, degree = 1, reps = 20, qdegree = -1;
   bool check = false;
-  std::string opname = "stiffness", variant = "gll", quad = "gll";
+  std::string opname = "stiffness", variant = "gll", quad = "gll", update = "auto";
   for (int i = 1; i < argc; ++i) {
     auto is = [&](const char* f) { return std::strcmp(argv[i], f) == 0 && i + 1 < argc; };
     if (is("--size")) Nx = std::atoi(argv[++i]);
@@ -37,12 +40,17 @@ int main(int argc, char* argv[])
     else if (is("--variant")) variant = argv[++i];
     else if (is("--quad")) quad = argv[++i];
     else if (is("--qdegree")) qdegree = std::atoi(argv[++i]);
+    else if (is("--update")) update = argv[++i];
     else if (std::strcmp(argv[i], "--check") == 0) check = true;
     else {
       std::cerr << "usage: operator_demo [--size N] [--degree P] [--op stiffness|mass|spectral|dense] [--reps R]"
-                   " [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--check]\n";
+                   " [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--update auto|atomic|owner] [--check]\n";
       return 2;
     }
+  }
+  if (update != "auto" && update != "atomic" && update != "owner") {
+    std::cerr << "--update must be auto, atomic or owner\n";
+    return 2;
   }
   try {
     wavehip::set_device(0);
@@ -66,7 +74,9 @@ int main(int argc, char* argv[])
     } else {
       const int kind = opname == "stiffness" ? WF_OP_STIFFNESS : WF_OP_MASS_LUMPED;
       const int flags = opname == "spectral" ? WF_FLAG_NO_FABS : WF_FLAG_NONE;
-      wavehip::check(wf_op_create_box(kind, degree, Nx, Nx, Nx, mesh.x.data(), 1500.0, flags, &op));
+      wf_tuning tuning{};
+      if (kind == WF_OP_STIFFNESS) tuning.update = update == "owner" ? WF_UPDATE_OWNER : update == "atomic" ? WF_UPDATE_ATOMIC : WF_UPDATE_AUTO;
+      wavehip::check(wf_op_create_box_tuned(kind, degree, Nx, Nx, Nx, mesh.x.data(), 1500.0, flags, &tuning, &op));
     }
     wf_op_info_t info{};
     wavehip::check(wf_op_info(op, &info));
@@ -119,6 +129,13 @@ int main(int argc, char* argv[])
     std::cout << "Number of cells: " << info.num_cells;
     std::cout << "\nNumber of dofs: " << info.num_dofs_cell;
     std::cout << "\nNumber of quads: " << info.num_quads;
+    if (opname == "stiffness") {
+      static const char* kGeometry[] = {"none", "per_point", "per_cell"};
+      static const char* kMetric[] = {"none", "full", "axes"};
+      static const char* kUpdate[] = {"none", "atomic", "owner"};
+      std::cout << "\nKernel: " << (info.kernel == WF_KERNEL_MARCH_BOX ? "march_box" : "other") << "  geometry: " << kGeometry[info.geometry]
+                << "  metric: " << kMetric[info.metric] << "  update: " << kUpdate[info.update];
+    }
     std::cout << "\n#Elapsed Time: " << t;
     std::cout << "\nDOF/s: " << N / t;
     std::cout << "\nDOF/s (warm, " << reps << " reps): " << N / tw;

@@ -173,20 +173,25 @@ typedef enum {
 } wf_kernel_hint;
 typedef struct {
   int kernel;        /* wf_kernel_hint                                                              */
-  int variant;       /* box marching kernel: compiled column cross-section + 1 (0 = default)        */
+  int variant;       /* box marching kernel: compiled column cross-section + 1 (0 = default); with
+                        the owner update it indexes the owner form's cross-sections (3 per degree)  */
   int lz;            /* layers per z segment of the marching kernels (0 = chosen from the mesh)     */
   int lz0;           /* length of the first z segment under a z ghost plane (0 = 3)                 */
   int bx, by, bz;    /* cells per block of the single-pass box kernel (0 = default)                 */
   int keep_cell_order; /* batch kernels: do not sort the cells by their smallest dof                */
   int orient;        /* lattice plan: 0 = normalise cell orientations (default), 1 = require the
                         cells to agree as given                                                     */
-  int geometry;      /* box stiffness, P <= 4 marching kernel: wf_geometry_mode                     */
+  int geometry;      /* box stiffness, P <= 4 marching kernel (P5 to P7: with update = OWNER only):
+                        wf_geometry_mode                                                            */
   int metric;        /* box stiffness with per-cell geometry: wf_metric_mode                        */
-  int update;        /* box stiffness, separable (axes) form: wf_update_mode                        */
+  int update;        /* box stiffness, separable (axes) form: wf_update_mode; OWNER on request at
+                        P1 to P7                                                                    */
 } wf_tuning;
 /* How a stiffness operator stores its geometry (wf_tuning.geometry, wf_op_info_t.geometry).  A box
  * whose cells are all affine (edge vectors along each reference axis bitwise equal, det J != 0, no
- * -1/0/1 clamp taking effect) needs one G_c = J^-1 J^-T |det J| per cell instead of one G per point. */
+ * -1/0/1 clamp taking effect) needs one G_c = J^-1 J^-T |det J| per cell instead of one G per point.
+ * At P5 to P7 the only per-cell kernel is the owner form (wf_tuning.update = WF_UPDATE_OWNER); without that
+ * request the k-split kernel runs on per-point geometry and PER_CELL is WF_ERR_UNSUPPORTED. */
 typedef enum {
   WF_GEOMETRY_AUTO = 0,       /* tuning: per cell where the mesh allows it; info: no stiffness geometry */
   WF_GEOMETRY_PER_POINT = 1,  /* G at every quadrature point (48 B each)                                */
@@ -205,12 +210,15 @@ typedef enum {
 /* How the separable box kernel adds its result into y (wf_tuning.update, wf_op_info_t.update).  The atomic
  * form adds each column's tile with fp64 atomics; the owner form gives every y entry to one thread, which
  * gathers it from the cells around the node and reads and writes it once (no atomics, a fixed summation
- * order: bitwise reproducible).  wf_tuning.variant then indexes the owner form's own cross-sections. */
+ * order: bitwise reproducible).  wf_tuning.variant then indexes the owner form's own cross-sections.
+ * The owner form is compiled for P1 to P7; the atomic separable form for P1 to P4. */
 typedef enum {
-  WF_UPDATE_AUTO = 0,         /* tuning: owner where it measured faster (P4), else atomic             */
+  WF_UPDATE_AUTO = 0,         /* tuning: owner at P4, atomic at P1 to P3; P5 to P7: the k-split kernel
+                                 on per-point geometry (the owner form there is on request only)       */
   WF_UPDATE_NONE = 0,         /* info: not the separable box kernel                                     */
   WF_UPDATE_ATOMIC = 1,       /* row atomics (also the only form of the full and per-point kernels)     */
-  WF_UPDATE_OWNER = 2         /* owner computes; tuning: WF_ERR_UNSUPPORTED unless the axes form runs   */
+  WF_UPDATE_OWNER = 2         /* owner computes (P1 to P7); tuning: WF_ERR_UNSUPPORTED unless the axes
+                                 form runs (a rectilinear box)                                          */
 } wf_update_mode;
 
 typedef struct {

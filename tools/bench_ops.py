@@ -124,10 +124,13 @@ def main():
             cases = [(True, None), (False, None), (False, {"kernel": "batch"})]
             if "KS" in os.environ and p <= 4:
                 cases = [(True, None), (True, {"variant": 3})]
+            if p >= 5:   # the owner form on request next to the default k-split kernel (OWNER_VARIANTS=1: every cross-section)
+                own = [{"update": "owner", "variant": v} for v in (0, 1, 2)] if "OWNER_VARIANTS" in os.environ else [{"update": "owner"}]
+                cases[1:1] = [(True, t) for t in own]
             for structured, tuning in cases:
                 op = w.StiffnessOperator(V, p, structured=structured, tuning=tuning)
                 report(f"stiffness P{p} " + ("box" if structured else "any dofmap") + f" [{op.kernel}]", timeit(lambda: op(x, y)),
-                       op.alg_bytes(), N, dict(tag, kernel=op.kernel, lz=op.info.plan_lz, tuning=str(tuning)))
+                       op.alg_bytes(), N, dict(tag, kernel=op.kernel, update=op.update, lz=op.info.plan_lz, tuning=str(tuning)))
                 del op
         if "mass" in only:
             op = w.SpectralMassOperator(V, p, structured=False)

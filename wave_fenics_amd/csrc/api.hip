@@ -944,6 +944,7 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   const wf_tuning tun = tuning ? *tuning : wf_tuning{};
   std::vector<double> h_Gc;   // per-cell geometry, [ncells][6]
   bool per_cell = false;
+  bool owner_hi = false;   // P >= 5 and the owner form requested: the only per-cell kernel of these degrees
 
   std::unique_ptr<wf_op, void (*)(wf_op*)> op(new wf_op, free_op);
   op->kind = kind;
@@ -971,11 +972,21 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
     if (op->march) {
       // P <= 4: the one-thread-per-column kernel (stiffness_march.hip), cross-section wf_tuning.variant - 1;
       // P >= 5: the k-split kernel (stiffness_march_ks.hip), cross-section wf_tuning.bx x by when compiled
-      // (wf_tuning.variant = 4 selects it at P4 as well, for comparisons)
+      // (wf_tuning.variant = 4 selects it at P4 as well, for comparisons).  P >= 5 with wf_tuning.update = OWNER: the
+      // owner form (stiffness_march_owner.hip) when the mesh allows it; wf_tuning.variant indexes its cross-sections and
+      // the per-cell geometry is blocked by that cross-section (there is no atomic per-cell kernel at these degrees).
       static const int kDefaultVariant[8] = {0, 0, 0, 0, 1, kKsVariant, kKsVariant, kKsVariant};   // P4: 5x2 columns
+      static const int kOwnerDefaultHi[8] = {0, 0, 0, 0, 0, 1, 2, 0};   // P5 5x2, P6 2x3, P7 2x2: the measured best
       op->march_variant = tun.variant > 0 ? tun.variant - 1 : kDefaultVariant[P];
       if (P >= 5) op->march_variant = kKsVariant;
-      if (op->march_variant == kKsVariant) {
+      owner_hi = P >= 5 && tun.update == WF_UPDATE_OWNER;
+      if (owner_hi) {
+        op->march_variant = tun.variant > 0 ? tun.variant - 1 : kOwnerDefaultHi[P];
+        if (op->march_variant >= kKsVariant || !march_owner_variant(P, op->march_variant, &op->bx, &op->by)) {
+          set_error("wf_op_create_box: wf_tuning.variant out of range");
+          return WF_ERR_INVALID;
+        }
+      } else if (op->march_variant == kKsVariant) {
         op->bx = tun.bx;
         op->by = tun.by;
         if (!march_ks_shape(P, &op->bx, &op->by)) {
@@ -988,12 +999,12 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
       }
       op->bz = 1;
     }
-    // geometry: per cell when every cell is affine and the P <= 4 marching kernel runs (the k-split and the
-    // single-pass block kernels read per-point geometry only)
+    // geometry: per cell when every cell is affine and the P <= 4 marching kernel or the owner form runs (the k-split
+    // and the single-pass block kernels read per-point geometry only)
     WF_REQUIRE(tun.geometry >= WF_GEOMETRY_AUTO && tun.geometry <= WF_GEOMETRY_PER_CELL,
                "wf_op_create_box: wf_tuning.geometry out of range");
     WF_REQUIRE(tun.metric >= WF_METRIC_AUTO && tun.metric <= WF_METRIC_AXES, "wf_op_create_box: wf_tuning.metric out of range");
-    const bool cell_capable = op->march && op->march_variant != kKsVariant;
+    const bool cell_capable = op->march && (op->march_variant != kKsVariant || owner_hi);
     if (tun.geometry == WF_GEOMETRY_PER_CELL && !cell_capable) {
       set_error("wf_op_create_box: per-cell geometry needs the marching kernel of degree <= 4");
       return WF_ERR_UNSUPPORTED;
@@ -1026,8 +1037,8 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
     }
     const MarchGeom geom = !per_cell ? MarchGeom::point : op->metric == WF_METRIC_AXES ? MarchGeom::cell_axes : MarchGeom::cell;
     // update: the owner-computes form of the separable kernel (no atomics) where it measured faster -- P4 -- or on
-    // request; wf_tuning.variant then indexes its own cross-section table.  The per-cell geometry keeps the blocking
-    // of the atomic form's cross-section of the same index.
+    // request (P1 to P7); wf_tuning.variant then indexes its own cross-section table.  The per-cell geometry keeps the
+    // blocking of the atomic form's cross-section of the same index (P >= 5: of the owner cross-section).
     WF_REQUIRE(tun.update >= WF_UPDATE_AUTO && tun.update <= WF_UPDATE_OWNER, "wf_op_create_box: wf_tuning.update out of range");
     if (geom == MarchGeom::cell_axes) {
       const bool owner = tun.update == WF_UPDATE_OWNER || (tun.update == WF_UPDATE_AUTO && P == 4);

@@ -18,7 +18,11 @@
 //     layer; each thread sums the ones its node touches into five scales per layer and carries the previous layer's
 //     for the shared plane k = 0;
 //   * x, y and G_c of the next layer are prefetched one layer ahead as unconditional loads on clamped addresses, and
-//     the layer body exists as two compile-time copies (has_next), as in k_stiffness_march.
+//     the layer body exists as two compile-time copies (has_next), as in k_stiffness_march;
+//   * the rows of A indexed by the plane (row k of the z term, row P of the -x / -y / -z cells) are scalar operands from
+//     the by-value DMat at P <= 4; at P >= 5 they would be up to 128 SGPRs, so only row P stays a scalar operand there
+//     and the rows k < P are broadcast reads from LDS (as the z rows of D in k_march_ks), and the kernel is built for
+//     two workgroups per CU instead of three (-DWF_OWNER_A_CONST: every such row a constant load from d_D instead).
 // The summation order of every y entry is fixed, so the apply is bitwise reproducible.
 #include <cstdlib>
 
@@ -32,9 +36,16 @@ namespace wf {
 #ifndef WF_OWNER_WAVES
 #define WF_OWNER_WAVES 3
 #endif
+// P >= 5: at three per CU every cross-section spills to scratch (36 to 280 B/lane); two (<= 256 VGPRs) do not
+#ifndef WF_OWNER_WAVES_HI
+#define WF_OWNER_WAVES_HI 2
+#endif
+
+template <int P>
+constexpr int owner_waves() { return P >= 5 ? WF_OWNER_WAVES_HI : WF_OWNER_WAVES; }
 
 template <int P, int BX, int BY>
-__global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
+__global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     int nx, int ny, int nz, int lz, int lz0, int gbx, int gby, const double* __restrict__ Gc, const double* __restrict__ dD, DMat am,
     double coeff, const double* __restrict__ x, double* __restrict__ y, const int32_t* __restrict__ items,
     int ablate_arg)
@@ -53,6 +64,19 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
   // x planes 0..P of the layer + a dump row for positions past the rectangle (branchless rotate, see (c))
   __shared__ __attribute__((aligned(16))) double Ux[(P + 1) * RP + 256];
   __shared__ __attribute__((aligned(16))) double Gs[NGL * 256];
+  // A[k][a] for the rows indexed by the plane (k, a compile-time after unrolling).  P >= 5: rows k < P from LDS (filled
+  // before the prologue's first barrier), row P from am.v; P <= 4: am.v
+#ifdef WF_OWNER_A_CONST
+  constexpr bool a_lds = false, a_const = P >= 5;
+#else
+  constexpr bool a_lds = P >= 5, a_const = false;
+#endif
+  __shared__ __attribute__((aligned(16))) double As[a_lds ? P * n : 1];
+  auto arow = [&](int k, int a) {
+    if (a_const) return dD[2 * n * n + n + k * n + a];
+    if (a_lds && k < P) return As[k * n + a];
+    return am.v[k * n + a];
+  };
 
   const int t = threadIdx.x;
   const int NX = P * nx + 1, NY = P * ny + 1;
@@ -87,6 +111,8 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
     aj[a] = dD[2 * n * n + n + j * n + a];
   }
   const double cwj = coeff * wk[j], cwi = coeff * wk[i], cwij = coeff * wk[i] * wk[j];
+  if constexpr (a_lds)
+    if (t < P * n) As[t] = dD[2 * n * n + n + t];
 
   // ---- staged positions (identical in every layer) -------------------------
   // position m: (I0 - P + c, J0 - P + r, pl); prefetch of the next layer: plane P*(kz+1) + pl + 1 -> LDS slot pl + 1
@@ -102,7 +128,8 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
   const int32_t pclamp = (int32_t)((size_t)I0 + (size_t)NX * J0);   // first owned position: always inside the mesh
 
   // G_c entries staged by this thread: entry e = comp * GC + cell, cell (lcx, lcy) = (cx0 - 1 + lcx, cy0 - 1 + lcy).
-  // Gc is blocked by the atomic form's cross-section gbx x gby (the operator's geometry does not depend on the update).
+  // Gc is blocked by gbx x gby: the atomic form's cross-section at P <= 4 (the operator's geometry does not depend on the
+  // update there), the owner cross-section at P >= 5 (no atomic per-cell kernel).
   const int nbx = (nx + gbx - 1) / gbx, nby = (ny + gby - 1) / gby;
   const size_t gstride = (size_t)nbx * nby * (gbx * gby) * 6;   // one cell layer of the blocked layout
   size_t gbase[NGL];
@@ -201,9 +228,9 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
 #pragma unroll
     for (int a = 0; a < n; ++a) {
       xr += ai[a] * L[rown + cR + a];
-      xl += am.v[P * n + a] * L[rown + cR - P + a];
+      xl += arow(P, a) * L[rown + cR - P + a];
       ya += aj[a] * L[(rA + a) * RX + cown];
-      yb += am.v[P * n + a] * L[(rA - P + a) * RX + cown];
+      yb += arow(P, a) * L[(rA - P + a) * RX + cown];
     }
     return xr * s0 + xl * s1 + ya * s2 + yb * s3;
   };
@@ -236,12 +263,12 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
     for (int k = 0; k < P; ++k) {
       double zc = 0.0;
 #pragma unroll
-      for (int a = 0; a < n; ++a) zc += am.v[k * n + a] * xz[P + a];
+      for (int a = 0; a < n; ++a) zc += arow(k, a) * xz[P + a];
       double v;
       if (k == 0) {
         double zp = 0.0;
 #pragma unroll
-        for (int a = 0; a < n; ++a) zp += am.v[P * n + a] * xz[a];
+        for (int a = 0; a < n; ++a) zp += arow(P, a) * xz[a];
         v = wk[0] * xy_terms(0, sf[0], sf[1], sf[2], sf[3]) + zc * sc[4] + zp * spz;
       } else {
         v = wk[k] * xy_terms(k, sc[0], sc[1], sc[2], sc[3]) + zc * sc[4];
@@ -305,7 +332,7 @@ __global__ __launch_bounds__(256, WF_OWNER_WAVES) void k_stiffness_owner(
   if (z1 == nz) {
     double zp = 0.0;
 #pragma unroll
-    for (int a = 0; a < n; ++a) zp += am.v[P * n + a] * xz[P + a];
+    for (int a = 0; a < n; ++a) zp += arow(P, a) * xz[P + a];
     const double v = wk[0] * xy_terms(P, sc[0], sc[1], sc[2], sc[3]) + zp * sc[4];
     const size_t K = (size_t)P * nz;
     const double y0 = (ablate & 1) ? 0.0 : y[plane * K + yoff];
@@ -352,14 +379,17 @@ int march_owner_columns(int P, int lx, int ly, int nx, int ny)
 // form runs; march_variant is the table of the atomic forms).  P*BX x P*BY owned lines, at most 256: square, wide, tall.
 bool march_owner_variant(int P, int variant, int* bx, int* by)
 {
-  static const int tab[5][3][2] = {
+  static const int tab[8][3][2] = {
       {{0, 0}, {0, 0}, {0, 0}},
       {{16, 16}, {32, 8}, {8, 32}},   // P1: 256 lines
       {{8, 8}, {16, 4}, {4, 16}},     // P2: 256 lines
       {{5, 5}, {7, 3}, {3, 7}},       // P3: 225 / 189 / 189 lines
       {{4, 4}, {8, 2}, {2, 8}},       // P4: 256 lines; default index 1 (8x2), as the atomic 5x2
+      {{3, 3}, {5, 2}, {2, 5}},       // P5: 225 / 250 / 250 lines; default index 1 (5x2)
+      {{3, 2}, {7, 1}, {2, 3}},       // P6: 216 / 252 / 216 lines; default index 2 (2x3)
+      {{2, 2}, {5, 1}, {1, 5}},       // P7: 196 / 245 / 245 lines; default index 0 (2x2)
   };
-  if (P < 1 || P > 4 || variant < 0 || variant > 2) return false;
+  if (P < 1 || P > 7 || variant < 0 || variant > 2) return false;
   *bx = tab[P][variant][0];
   *by = tab[P][variant][1];
   return true;
@@ -378,6 +408,9 @@ int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int
   WF_OWNER_CASE(2, 0, 8, 8) WF_OWNER_CASE(2, 1, 16, 4) WF_OWNER_CASE(2, 2, 4, 16)
   WF_OWNER_CASE(3, 0, 5, 5) WF_OWNER_CASE(3, 1, 7, 3) WF_OWNER_CASE(3, 2, 3, 7)
   WF_OWNER_CASE(4, 0, 4, 4) WF_OWNER_CASE(4, 1, 8, 2) WF_OWNER_CASE(4, 2, 2, 8)
+  WF_OWNER_CASE(5, 0, 3, 3) WF_OWNER_CASE(5, 1, 5, 2) WF_OWNER_CASE(5, 2, 2, 5)
+  WF_OWNER_CASE(6, 0, 3, 2) WF_OWNER_CASE(6, 1, 7, 1) WF_OWNER_CASE(6, 2, 2, 3)
+  WF_OWNER_CASE(7, 0, 2, 2) WF_OWNER_CASE(7, 1, 5, 1) WF_OWNER_CASE(7, 2, 1, 5)
   set_error("stiffness_march (owner): unsupported degree/variant");
   return WF_ERR_UNSUPPORTED;
 }
@@ -401,6 +434,9 @@ int march_owner_resident(int P, int variant)
   WF_OWNER_RES(2, 0, 8, 8) WF_OWNER_RES(2, 1, 16, 4) WF_OWNER_RES(2, 2, 4, 16)
   WF_OWNER_RES(3, 0, 5, 5) WF_OWNER_RES(3, 1, 7, 3) WF_OWNER_RES(3, 2, 3, 7)
   WF_OWNER_RES(4, 0, 4, 4) WF_OWNER_RES(4, 1, 8, 2) WF_OWNER_RES(4, 2, 2, 8)
+  WF_OWNER_RES(5, 0, 3, 3) WF_OWNER_RES(5, 1, 5, 2) WF_OWNER_RES(5, 2, 2, 5)
+  WF_OWNER_RES(6, 0, 3, 2) WF_OWNER_RES(6, 1, 7, 1) WF_OWNER_RES(6, 2, 2, 3)
+  WF_OWNER_RES(7, 0, 2, 2) WF_OWNER_RES(7, 1, 5, 1) WF_OWNER_RES(7, 2, 1, 5)
   return 0;
 }
 

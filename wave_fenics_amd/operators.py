@@ -135,7 +135,10 @@ def make_tuning(tuning) -> "_lib.Tuning | None":
     metric=, update=) or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any",
     "elementwise", "march"; `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"; `metric` a
     wf_metric_mode value or one of "auto", "full", "axes"; `update` a wf_update_mode value or one of "auto", "atomic",
-    "owner"."""
+    "owner".  {"update": "owner"} gives the owner-computes separable box stiffness kernel (per-cell geometry, no atomics,
+    bitwise reproducible) on a rectilinear box at degrees 1 to 7 and raises WavehipError on any other mesh; `variant`
+    then indexes its three cross-sections.  "auto" picks it at degree 4 only; at degrees 5 to 7 "auto" keeps the k-split
+    kernel with per-point geometry."""
     if tuning is None:
         return None
     if isinstance(tuning, _lib.Tuning):
