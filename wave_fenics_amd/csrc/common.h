@@ -2,9 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -53,6 +55,42 @@ struct MarkerScope {
       return WF_ERR_INVALID;                     \
     }                                            \
   } while (0)
+
+// After a kernel launch: WF_ERR_HIP with "<what> launch failed: ..." if it did not go out.
+inline int launch_status(const char* what)
+{
+  const hipError_t e = hipGetLastError();
+  if (e == hipSuccess) return WF_OK;
+  set_error(std::string(what) + " launch failed: " + hipGetErrorString(e));
+  return WF_ERR_HIP;
+}
+#define WF_LAUNCH_CHECK()                                       \
+  do {                                                          \
+    if (int _rc = ::wf::launch_status("kernel")) return _rc;    \
+  } while (0)
+
+// Diagnostic ablation mask (profiling only; WF_ABLATE unset or 0 in production):
+// 1 = no scatter, 2 = geometry served from L2, 4 = no x gather, 8 = no contractions.
+inline int ablate_flags()
+{
+#ifdef WF_DIAG
+  const char* e = std::getenv("WF_ABLATE");
+  return e ? std::atoi(e) : 0;
+#else
+  return 0;
+#endif
+}
+
+// Workgroups of a 256-thread kernel without dynamic LDS resident on the device at once (occupancy query x CUs; the z
+// segmentation of wf_op_create_box runs its work items in rounds of this many).  0 if the query fails.
+template <class Kernel>
+int resident_workgroups(Kernel kernel)
+{
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) == hipSuccess ? per_cu * cus : 0;
+}
 
 // 1-D collocation derivative matrix, passed by value as a kernel argument so
 // that compile-time-indexed entries become scalar (SGPR) operands.
@@ -103,13 +141,27 @@ int march_resident(int P, int variant, MarchGeom geom);   // workgroups resident
 // Owner-computes form of cell_axes (stiffness_march_owner.hip): every y entry read and written once by its owning thread,
 // no atomics.  Its own cross-section table (march_owner_variant); columns = lattice lines in pieces of P*BX x P*BY.
 bool march_owner_variant(int P, int variant, int* bx, int* by);
-int march_owner_columns(int P, int lx, int ly, int nx, int ny);
 // d_Gcell blocked by gbx x gby: the atomic form's cross-section at P <= 4, the owner cross-section itself at P >= 5
 int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int lz, int lz0, int gbx, int gby,
                                  const double* d_Gcell,
                                  const double* d_D, const DMat& am, double coeff, const double* d_x, double* d_y,
                                  const int32_t* d_items, int nitems, hipStream_t s);
 int march_owner_resident(int P, int variant);   // workgroups resident on the device (occupancy query)
+// Work items of the box marching kernels, host side (the kernels carry the same arithmetic): item = column + columns *
+// z segment.  Columns of the atomic forms are pieces of bx x by cells; the owner form cuts the lattice lines 0 .. P nx
+// into pieces of P*bx x P*by from (0, 0).  Segment 0 has lz0 layers, every later one lz (the last one what is left).
+struct BoxColumns {
+  int nbx, nby;
+  int count() const { return nbx * nby; }
+};
+inline BoxColumns box_columns(int nx, int ny, int bx, int by) { return {(nx + bx - 1) / bx, (ny + by - 1) / by}; }
+inline BoxColumns box_owner_columns(int P, int nx, int ny, int bx, int by)
+{
+  return box_columns(P * nx + 1, P * ny + 1, P * bx, P * by);
+}
+inline int box_segments(int nz, int lz, int lz0) { return 1 + (std::max(nz - lz0, 0) + lz - 1) / lz; }
+inline int box_segment_begin(int seg, int lz, int lz0) { return seg == 0 ? 0 : lz0 + (seg - 1) * lz; }
+inline int box_segment_end(int seg, int nz, int lz, int lz0) { return std::min(nz, seg == 0 ? lz0 : lz0 + seg * lz); }
 // indexed marching kernels for arbitrary dofmaps (generic_plan.cpp, stiffness_march_idx.hip, stiffness_march_ks.hip)
 struct MarchPlan {
   bool ok = false;                      // false: the mesh does not tile into lattice columns

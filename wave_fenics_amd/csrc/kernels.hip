@@ -1056,60 +1056,30 @@ static int launch_mass_dense_col_t(int ncells, const int32_t* d_uoff, const int3
   const size_t lds = (size_t)(2 * CB * nd + n * n) * sizeof(double);
   hipLaunchKernelGGL(k_mass_dense_col<P>, dim3(nb), dim3(256), lds, s, ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ,
                      d_x, d_y);
-  return WF_OK;
+  return launch_status("mass_dense_col");
 }
 
 int launch_mass_dense_col(int P, int ncells, const int32_t* d_uoff, const int32_t* d_uniq, const uint16_t* d_loc,
                           const double* d_phi1, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s)
 {
   if (ncells == 0) return WF_OK;
-  int rc = WF_ERR_UNSUPPORTED;
   switch (P) {
-    case 1: rc = launch_mass_dense_col_t<1>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
-    case 2: rc = launch_mass_dense_col_t<2>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
-    case 3: rc = launch_mass_dense_col_t<3>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
-    case 4: rc = launch_mass_dense_col_t<4>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
-    case 5: rc = launch_mass_dense_col_t<5>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
-    case 6: rc = launch_mass_dense_col_t<6>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
-    case 7: rc = launch_mass_dense_col_t<7>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s); break;
+    case 1: return launch_mass_dense_col_t<1>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+    case 2: return launch_mass_dense_col_t<2>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+    case 3: return launch_mass_dense_col_t<3>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+    case 4: return launch_mass_dense_col_t<4>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+    case 5: return launch_mass_dense_col_t<5>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+    case 6: return launch_mass_dense_col_t<6>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+    case 7: return launch_mass_dense_col_t<7>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
   }
-  if (rc != WF_OK) {
-    set_error("mass_dense_col: degree must be 1..7");
-    return rc;
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("mass_dense_col launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+  set_error("mass_dense_col: degree must be 1..7");
+  return WF_ERR_UNSUPPORTED;
 }
 
 // --------------------------------------------------------------------------
 // launchers
 // --------------------------------------------------------------------------
-// Diagnostic ablation mask (profiling only; WF_ABLATE unset or 0 in production):
-// 1 = no scatter, 2 = geometry served from L2, 4 = no x gather, 8 = no contractions.
-static int ablate_flags()
-{
-#ifdef WF_DIAG
-  const char* e = std::getenv("WF_ABLATE");
-  return e ? std::atoi(e) : 0;
-#else
-  return 0;
-#endif
-}
-
 static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
-#define WF_LAUNCH_CHECK()                                                       \
-  do {                                                                          \
-    hipError_t _e = hipGetLastError();                                          \
-    if (_e != hipSuccess) {                                                     \
-      set_error(std::string("kernel launch failed: ") + hipGetErrorString(_e)); \
-      return WF_ERR_HIP;                                                        \
-    }                                                                           \
-  } while (0)
 
 int launch_geometry_hex(int P, int ncells, const double* d_xverts, const int32_t* d_geom_dofmap,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp, double* d_G9,

@@ -423,12 +423,7 @@ static int launch_mass_t(const MassArgs& a, int nitems, size_t lds, hipStream_t 
   WF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mass_march<P, BX, BY>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((k_mass_march<P, BX, BY>), dim3((unsigned)nitems), dim3(MassLayout<P, BX, BY>::WG), lds, s, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("mass_march launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+  return launch_status("mass_march");
 }
 
 // column cross-sections (the first of a degree is its default): whole cells per wave (floor(64 / n^2))

@@ -542,12 +542,7 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
   hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * NW), lds, s, d->nd, d->nq, d->nbatch, d->numax, d->d_T, d->d_w, d->d_C,
                      d->d_locP, d->d_uoff, d->d_uniq, d->d_clampb, coeff, do_clamp, d_x, d_y,
                      ablate, stagger);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("stiffness_dense launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+  return launch_status("stiffness_dense");
 }
 
 // NU = 5 covers the unique dofs of 64 well-numbered P4 cells (1154 on the Kuhn box); 9 is the worst case 64 * 35

@@ -453,106 +453,73 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
   }
 }
 
-static int march_ablate()
-{
-#ifdef WF_DIAG
-  const char* e = std::getenv("WF_ABLATE");
-  return e ? std::atoi(e) : 0;
-#else
-  return 0;
-#endif
-}
-
 template <int P, int BX, int BY>
 static int launch_march_t(MarchGeom geom, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,
                           const double* d_Gcell, const double* d_D, const DMat& dm, double coeff, const double* d_x,
                           double* d_y, const int32_t* d_items, int nitems, hipStream_t s)
 {
-  const int ncols = ((nx + BX - 1) / BX) * ((ny + BY - 1) / BY);
-  const int nseg = 1 + (std::max(nz - lz0, 0) + lz - 1) / lz;
-  const int nwg = d_items ? nitems : ncols * nseg;
+  const int nwg = d_items ? nitems : box_columns(nx, ny, BX, BY).count() * box_segments(nz, lz, lz0);
   if (nwg == 0) return WF_OK;
   if (geom == MarchGeom::cell_axes)
     hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, MarchGeom::cell_axes>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny,
                        nz, lz, lz0, reinterpret_cast<const double2*>(d_Gcell), d_D, dm, coeff, d_x, d_y, d_items,
-                       march_ablate());
+                       ablate_flags());
   else if (geom == MarchGeom::cell)
     hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, MarchGeom::cell>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz,
                        lz, lz0, reinterpret_cast<const double2*>(d_Gcell), d_D, dm, coeff, d_x, d_y, d_items,
-                       march_ablate());
+                       ablate_flags());
   else
     hipLaunchKernelGGL((k_stiffness_march<P, BX, BY, MarchGeom::point>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz,
                        lz, lz0, reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, d_items,
-                       march_ablate());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("stiffness_march launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+                       ablate_flags());
+  return launch_status("stiffness_march");
 }
 
-// The (BX, BY) column cross-sections compiled per degree.  index = variant.
+// The (P, variant, BX, BY) column cross-sections compiled per degree: P1 64 / 16 / 32 cells, P2 25 / 9 / 28, P3 16 / 9 / 8,
+// P4 9 / 10 / 4.  P5..P7: the k-split kernel (stiffness_march_ks.hip); this one ran at one wave per SIMD there (two
+// geometry register sets per column do not fit 256 VGPRs) and measured 0.26-0.51 ms at 10 M dofs against 0.17-0.22 ms.
+#define WF_MARCH_SHAPES(X)                \
+  X(1, 0, 8, 8) X(1, 1, 4, 4) X(1, 2, 8, 4) \
+  X(2, 0, 5, 5) X(2, 1, 3, 3) X(2, 2, 7, 4) \
+  X(3, 0, 4, 4) X(3, 1, 3, 3) X(3, 2, 4, 2) \
+  X(4, 0, 3, 3) X(4, 1, 5, 2) X(4, 2, 2, 2)
+
 bool march_variant(int P, int variant, int* bx, int* by)
 {
-  static const int tab[8][3][2] = {
-      {{0, 0}, {0, 0}, {0, 0}},
-      {{8, 8}, {4, 4}, {8, 4}},   // P1: 64 / 16 / 32 cells
-      {{5, 5}, {3, 3}, {7, 4}},   // P2: 25 / 9 / 28 cells
-      {{4, 4}, {3, 3}, {4, 2}},   // P3: 16 / 9 / 8 cells
-      {{3, 3}, {5, 2}, {2, 2}},   // P4: 9 / 10 / 4 cells
-      {{0, 0}, {0, 0}, {0, 0}},   // P5..P7: the k-split kernel (stiffness_march_ks.hip); this one ran at one wave per
-      {{0, 0}, {0, 0}, {0, 0}},   // SIMD there (two geometry register sets per column do not fit 256 VGPRs) and
-      {{0, 0}, {0, 0}, {0, 0}},   // measured 0.26-0.51 ms at 10 M dofs against 0.17-0.22 ms
-  };
-  if (P < 1 || P > 4 || variant < 0 || variant > 2) return false;
-  *bx = tab[P][variant][0];
-  *by = tab[P][variant][1];
-  return true;
+#define X(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return *bx = BXX, *by = BYY, true;
+  WF_MARCH_SHAPES(X)
+#undef X
+  return false;
 }
-
-#define WF_MARCH_CASE(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return launch_march_t<PP, BXX, BYY>(geom, nx, ny, nz, lz, lz0, d_G6blk, d_Gcell, d_D, dm, coeff, d_x, d_y, d_items, nitems, s);
 
 int launch_stiffness_march(int P, int variant, MarchGeom geom, int nx, int ny, int nz, int lz, int lz0,
                            const double* d_G6blk, const double* d_Gcell, const double* d_D, const DMat& dm, double coeff,
                            const double* d_x, double* d_y, const int32_t* d_items, int nitems, hipStream_t s)
 {
   if ((size_t)nx * ny * nz == 0) return WF_OK;
-  WF_MARCH_CASE(1, 0, 8, 8) WF_MARCH_CASE(1, 1, 4, 4) WF_MARCH_CASE(1, 2, 8, 4)
-  WF_MARCH_CASE(2, 0, 5, 5) WF_MARCH_CASE(2, 1, 3, 3) WF_MARCH_CASE(2, 2, 7, 4)
-  WF_MARCH_CASE(3, 0, 4, 4) WF_MARCH_CASE(3, 1, 3, 3) WF_MARCH_CASE(3, 2, 4, 2)
-  WF_MARCH_CASE(4, 0, 3, 3) WF_MARCH_CASE(4, 1, 5, 2) WF_MARCH_CASE(4, 2, 2, 2)
+#define X(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return launch_march_t<PP, BXX, BYY>(geom, nx, ny, nz, lz, lz0, d_G6blk, d_Gcell, d_D, dm, coeff, d_x, d_y, d_items, nitems, s);
+  WF_MARCH_SHAPES(X)
+#undef X
   set_error("stiffness_march: unsupported degree/variant");
   return WF_ERR_UNSUPPORTED;
 }
 
-// Workgroups of the (P, variant) kernel resident on the device at once (occupancy query x CUs; the z
-// segmentation of wf_op_create_box runs its work items in rounds of this many).  0 if the query fails.
 template <int P, int BX, int BY>
 static int march_resident_t(MarchGeom geom)
 {
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  const hipError_t e =
-      geom == MarchGeom::cell_axes
-          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, MarchGeom::cell_axes>, 256, 0)
-      : geom == MarchGeom::cell
-          ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, MarchGeom::cell>, 256, 0)
-          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_march<P, BX, BY, MarchGeom::point>, 256, 0);
-  return e == hipSuccess ? per_cu * cus : 0;
+  return geom == MarchGeom::cell_axes ? resident_workgroups(k_stiffness_march<P, BX, BY, MarchGeom::cell_axes>)
+         : geom == MarchGeom::cell    ? resident_workgroups(k_stiffness_march<P, BX, BY, MarchGeom::cell>)
+                                      : resident_workgroups(k_stiffness_march<P, BX, BY, MarchGeom::point>);
 }
-
-#define WF_MARCH_RES(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return march_resident_t<PP, BXX, BYY>(geom);
 
 int march_resident(int P, int variant, MarchGeom geom)
 {
-  WF_MARCH_RES(1, 0, 8, 8) WF_MARCH_RES(1, 1, 4, 4) WF_MARCH_RES(1, 2, 8, 4)
-  WF_MARCH_RES(2, 0, 5, 5) WF_MARCH_RES(2, 1, 3, 3) WF_MARCH_RES(2, 2, 7, 4)
-  WF_MARCH_RES(3, 0, 4, 4) WF_MARCH_RES(3, 1, 3, 3) WF_MARCH_RES(3, 2, 4, 2)
-  WF_MARCH_RES(4, 0, 3, 3) WF_MARCH_RES(4, 1, 5, 2) WF_MARCH_RES(4, 2, 2, 2)
+#define X(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return march_resident_t<PP, BXX, BYY>(geom);
+  WF_MARCH_SHAPES(X)
+#undef X
   return 0;
 }
 

@@ -273,12 +273,7 @@ static int launch_t(const MarchPlanDev& pd, const double* d_G6blk, const double*
   hipLaunchKernelGGL((k_march_idx<OP, P, BX, BY>), dim3((unsigned)nwg), dim3(256), dyn, s, pd.lz, pd.tile_size,
                      pd.d_item_base, pd.d_item_pattern, pd.d_item_layers, pd.d_pat_off,
                      static_cast<const void*>(d_G6blk), d_D, dm, coeff, d_x, d_y, d_items);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("stiffness_march_idx launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+  return launch_status("stiffness_march_idx");
 }
 
 // the stiffness operator runs the k-split kernel (stiffness_march_ks.hip) at P >= 5

@@ -468,12 +468,7 @@ static int launch_ks_t(const KSArgs& a, const DMat& dm, int nwg, size_t lds, hip
   WF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_march_ks<P, BX, BY, IDX>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((k_march_ks<P, BX, BY, IDX>), dim3((unsigned)nwg), dim3(KSLayout<P, BX, BY>::WG), lds, s, a, dm);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("march_ks launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+  return launch_status("march_ks");
 }
 
 // Compiled column cross-sections (BX * BY * n^2 <= 256 threads per half); the first entry of a degree is
@@ -528,9 +523,7 @@ int launch_stiffness_march_ks_box(int P, int bx, int by, int nx, int ny, int nz,
   a.items = d_items;
   a.G6blk = reinterpret_cast<const double2*>(d_G6blk);
   a.dD = d_D; a.coeff = coeff; a.x = d_x; a.y = d_y;
-  const int ncols = ((nx + bx - 1) / bx) * ((ny + by - 1) / by);
-  const int nseg = 1 + (std::max(nz - lz0, 0) + lz - 1) / lz;
-  const int nwg = d_items ? nitems : ncols * nseg;
+  const int nwg = d_items ? nitems : box_columns(nx, ny, bx, by).count() * box_segments(nz, lz, lz0);
   const size_t lds = march_ks_lds_bytes(P, bx, by, 0, false);
 #define X(PP, BXX, BYY) \
   if (P == PP && bx == BXX && by == BYY) return launch_ks_t<PP, BXX, BYY, false>(a, dm, nwg, lds, s);

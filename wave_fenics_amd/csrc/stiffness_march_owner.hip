@@ -340,63 +340,37 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   }
 }
 
-static int owner_ablate()
-{
-#ifdef WF_DIAG
-  const char* e = std::getenv("WF_ABLATE");
-  return e ? std::atoi(e) : 0;
-#else
-  return 0;
-#endif
-}
-
 template <int P, int BX, int BY>
 static int launch_owner_t(int nx, int ny, int nz, int lz, int lz0, int gbx, int gby, const double* d_Gcell, const double* d_D,
                           const DMat& am, double coeff, const double* d_x, double* d_y, const int32_t* d_items, int nitems,
                           hipStream_t s)
 {
-  const int nseg = 1 + (std::max(nz - lz0, 0) + lz - 1) / lz;
-  const int nwg = d_items ? nitems : march_owner_columns(P, P * BX, P * BY, nx, ny) * nseg;
+  const int nwg = d_items ? nitems : box_owner_columns(P, nx, ny, BX, BY).count() * box_segments(nz, lz, lz0);
   if (nwg == 0) return WF_OK;
   hipLaunchKernelGGL((k_stiffness_owner<P, BX, BY>), dim3((unsigned)nwg), dim3(256), 0, s, nx, ny, nz, lz, lz0, gbx, gby, d_Gcell,
-                     d_D, am, coeff, d_x, d_y, d_items, owner_ablate());
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("stiffness_march (owner) launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+                     d_D, am, coeff, d_x, d_y, d_items, ablate_flags());
+  return launch_status("stiffness_march (owner)");
 }
 
-// Columns of the owner form: the lattice lines cut into pieces of P*BX x P*BY from (0, 0).
-int march_owner_columns(int P, int lx, int ly, int nx, int ny)
-{
-  const int NX = P * nx + 1, NY = P * ny + 1;
-  return ((NX + lx - 1) / lx) * ((NY + ly - 1) / ly);
-}
+// The (P, variant, BX, BY) column cross-sections of the owner form (variant = wf_tuning.variant - 1 when the owner
+// form runs; WF_MARCH_SHAPES is the table of the atomic forms).  P*BX x P*BY owned lines, at most 256: square, wide, tall.
+#define WF_OWNER_SHAPES(X)                                                                                \
+  X(1, 0, 16, 16) X(1, 1, 32, 8) X(1, 2, 8, 32) /* P1: 256 lines */                                         \
+  X(2, 0, 8, 8) X(2, 1, 16, 4) X(2, 2, 4, 16)   /* P2: 256 lines */                                         \
+  X(3, 0, 5, 5) X(3, 1, 7, 3) X(3, 2, 3, 7)     /* P3: 225 / 189 / 189 lines */                             \
+  X(4, 0, 4, 4) X(4, 1, 8, 2) X(4, 2, 2, 8)     /* P4: 256 lines; default index 1 (8x2), as the atomic 5x2 */ \
+  X(5, 0, 3, 3) X(5, 1, 5, 2) X(5, 2, 2, 5)     /* P5: 225 / 250 / 250 lines; default index 1 (5x2) */      \
+  X(6, 0, 3, 2) X(6, 1, 7, 1) X(6, 2, 2, 3)     /* P6: 216 / 252 / 216 lines; default index 2 (2x3) */      \
+  X(7, 0, 2, 2) X(7, 1, 5, 1) X(7, 2, 1, 5)     /* P7: 196 / 245 / 245 lines; default index 0 (2x2) */
 
-// The (BX, BY) column cross-sections of the owner form, per degree (index = wf_tuning.variant - 1 when the owner
-// form runs; march_variant is the table of the atomic forms).  P*BX x P*BY owned lines, at most 256: square, wide, tall.
 bool march_owner_variant(int P, int variant, int* bx, int* by)
 {
-  static const int tab[8][3][2] = {
-      {{0, 0}, {0, 0}, {0, 0}},
-      {{16, 16}, {32, 8}, {8, 32}},   // P1: 256 lines
-      {{8, 8}, {16, 4}, {4, 16}},     // P2: 256 lines
-      {{5, 5}, {7, 3}, {3, 7}},       // P3: 225 / 189 / 189 lines
-      {{4, 4}, {8, 2}, {2, 8}},       // P4: 256 lines; default index 1 (8x2), as the atomic 5x2
-      {{3, 3}, {5, 2}, {2, 5}},       // P5: 225 / 250 / 250 lines; default index 1 (5x2)
-      {{3, 2}, {7, 1}, {2, 3}},       // P6: 216 / 252 / 216 lines; default index 2 (2x3)
-      {{2, 2}, {5, 1}, {1, 5}},       // P7: 196 / 245 / 245 lines; default index 0 (2x2)
-  };
-  if (P < 1 || P > 7 || variant < 0 || variant > 2) return false;
-  *bx = tab[P][variant][0];
-  *by = tab[P][variant][1];
-  return true;
+#define X(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return *bx = BXX, *by = BYY, true;
+  WF_OWNER_SHAPES(X)
+#undef X
+  return false;
 }
-
-#define WF_OWNER_CASE(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return launch_owner_t<PP, BXX, BYY>(nx, ny, nz, lz, lz0, gbx, gby, d_Gcell, d_D, am, coeff, d_x, d_y, d_items, nitems, s);
 
 int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int lz, int lz0, int gbx, int gby,
                                  const double* d_Gcell,
@@ -404,39 +378,20 @@ int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int
                                  const int32_t* d_items, int nitems, hipStream_t s)
 {
   if ((size_t)nx * ny * nz == 0) return WF_OK;
-  WF_OWNER_CASE(1, 0, 16, 16) WF_OWNER_CASE(1, 1, 32, 8) WF_OWNER_CASE(1, 2, 8, 32)
-  WF_OWNER_CASE(2, 0, 8, 8) WF_OWNER_CASE(2, 1, 16, 4) WF_OWNER_CASE(2, 2, 4, 16)
-  WF_OWNER_CASE(3, 0, 5, 5) WF_OWNER_CASE(3, 1, 7, 3) WF_OWNER_CASE(3, 2, 3, 7)
-  WF_OWNER_CASE(4, 0, 4, 4) WF_OWNER_CASE(4, 1, 8, 2) WF_OWNER_CASE(4, 2, 2, 8)
-  WF_OWNER_CASE(5, 0, 3, 3) WF_OWNER_CASE(5, 1, 5, 2) WF_OWNER_CASE(5, 2, 2, 5)
-  WF_OWNER_CASE(6, 0, 3, 2) WF_OWNER_CASE(6, 1, 7, 1) WF_OWNER_CASE(6, 2, 2, 3)
-  WF_OWNER_CASE(7, 0, 2, 2) WF_OWNER_CASE(7, 1, 5, 1) WF_OWNER_CASE(7, 2, 1, 5)
+#define X(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return launch_owner_t<PP, BXX, BYY>(nx, ny, nz, lz, lz0, gbx, gby, d_Gcell, d_D, am, coeff, d_x, d_y, d_items, nitems, s);
+  WF_OWNER_SHAPES(X)
+#undef X
   set_error("stiffness_march (owner): unsupported degree/variant");
   return WF_ERR_UNSUPPORTED;
 }
 
-template <int P, int BX, int BY>
-static int owner_resident_t()
-{
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_owner<P, BX, BY>, 256, 0);
-  return e == hipSuccess ? per_cu * cus : 0;
-}
-
-#define WF_OWNER_RES(PP, V, BXX, BYY) \
-  if (P == PP && variant == V) return owner_resident_t<PP, BXX, BYY>();
-
 int march_owner_resident(int P, int variant)
 {
-  WF_OWNER_RES(1, 0, 16, 16) WF_OWNER_RES(1, 1, 32, 8) WF_OWNER_RES(1, 2, 8, 32)
-  WF_OWNER_RES(2, 0, 8, 8) WF_OWNER_RES(2, 1, 16, 4) WF_OWNER_RES(2, 2, 4, 16)
-  WF_OWNER_RES(3, 0, 5, 5) WF_OWNER_RES(3, 1, 7, 3) WF_OWNER_RES(3, 2, 3, 7)
-  WF_OWNER_RES(4, 0, 4, 4) WF_OWNER_RES(4, 1, 8, 2) WF_OWNER_RES(4, 2, 2, 8)
-  WF_OWNER_RES(5, 0, 3, 3) WF_OWNER_RES(5, 1, 5, 2) WF_OWNER_RES(5, 2, 2, 5)
-  WF_OWNER_RES(6, 0, 3, 2) WF_OWNER_RES(6, 1, 7, 1) WF_OWNER_RES(6, 2, 2, 3)
-  WF_OWNER_RES(7, 0, 2, 2) WF_OWNER_RES(7, 1, 5, 1) WF_OWNER_RES(7, 2, 1, 5)
+#define X(PP, V, BXX, BYY) \
+  if (P == PP && variant == V) return resident_workgroups(k_stiffness_owner<PP, BXX, BYY>);
+  WF_OWNER_SHAPES(X)
+#undef X
   return 0;
 }
 

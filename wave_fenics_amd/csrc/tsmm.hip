@@ -406,12 +406,7 @@ static int launch_tsmm_t(int layout, int64_t ncells, int Kfull, int N, int n0, i
   if (layout == 0) rc = k0 > 0 ? go(k_tsmm<NT, 0, true>) : go(k_tsmm<NT, 0, false>);
   else rc = k0 > 0 ? go(k_tsmm<NT, 1, true>) : go(k_tsmm<NT, 1, false>);
   if (rc != WF_OK) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error(std::string("wf_tsmm launch failed: ") + hipGetErrorString(e));
-    return WF_ERR_HIP;
-  }
-  return WF_OK;
+  return launch_status("wf_tsmm");
 }
 
 }  // namespace wf

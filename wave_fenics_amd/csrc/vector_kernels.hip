@@ -30,15 +30,6 @@ static inline unsigned reduction_grid(size_t n, unsigned block)
   return (unsigned)(g < cap ? (g ? g : 1) : cap);
 }
 
-#define WF_LAUNCH_CHECK()                                                       \
-  do {                                                                          \
-    hipError_t _e = hipGetLastError();                                          \
-    if (_e != hipSuccess) {                                                     \
-      set_error(std::string("kernel launch failed: ") + hipGetErrorString(_e)); \
-      return WF_ERR_HIP;                                                        \
-    }                                                                           \
-  } while (0)
-
 // common/cuda/scatter.cu:5-11
 __global__ void k_gather(int32_t N, const int32_t* __restrict__ idx, const double* __restrict__ in,
                          double* __restrict__ out)
