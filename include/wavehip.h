@@ -271,7 +271,10 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
  * [3][nq][nd], already clamped by the caller like operators.hpp:27-29;
  * h_weights [nq]; cells are affine tetrahedra given by h_geom_dofmap [ncells][4].
  * G = (J^-1 |det J| w_q) J^-T with the -1/0/1 clamp is formed on the fly
- * (precomputation.hpp:95-107).  Compiled shapes: Lagrange P1..P4. */
+ * (precomputation.hpp:95-107).  Compiled shapes: Lagrange P1..P4; any other (nd, nq) with
+ * the same tile counts ceil(nq/16), ceil(nd/4), ceil(nd/16) runs too, the rest is
+ * WF_ERR_UNSUPPORTED at creation.
+ * A degenerate cell (det J zero or not finite) is WF_ERR_INVALID at creation. */
 typedef struct {
   int nd, nq;                   /* dofs and quadrature points per cell            */
   int ncells, ndofs;

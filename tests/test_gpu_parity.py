@@ -890,6 +890,61 @@ def test_tsmm_vs_numpy(gpu, ncells, K, N):
     assert np.abs(out.cpu().numpy().reshape(N, ncells).T - C).max() <= 1e-13 * scale
 
 
+def tsmm_check(gpu, ncells, K, N, layout, shift):
+    """wf_tsmm on operands inside padded buffers (16 sentinels on either side, `shift` entries off 16-byte alignment),
+    out full of NaN on entry: out = in . phi overwrites, and nothing outside out is written"""
+    import torch
+    import wave_fenics_amd as w
+    PAD = 16
+    rng = np.random.default_rng(1000 * ncells + 10 * K + N)
+    A, Bm = rng.uniform(-1, 1, (ncells, K)), rng.uniform(-1, 1, (K, N))
+    C = A @ Bm
+    scale = (np.abs(A) @ np.abs(Bm)).max()
+    hin = (A if layout == 0 else np.ascontiguousarray(A.T)).reshape(-1)
+
+    def padded(v, fill=None):
+        h = np.full(PAD + v.size + PAD + 1, -7.0e77)
+        h[PAD + shift:PAD + shift + v.size] = v if fill is None else fill
+        buf = torch.from_numpy(h).to(gpu)
+        view = buf[PAD + shift:PAD + shift + v.size]
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 8 * shift
+        return h, buf, view
+
+    h_in, b_in, d_in = padded(hin)
+    h_phi, b_phi, d_phi = padded(Bm.reshape(-1))
+    h_out, b_out, d_out = padded(np.zeros(ncells * N), fill=np.nan)      # out = in . phi: whatever out held is gone
+    w.tsmm(ncells, d_in, d_phi.view(K, N), d_out, layout=layout)
+    torch.cuda.synchronize()
+    assert np.array_equal(b_in.cpu().numpy().view(np.uint64), h_in.view(np.uint64))
+    assert np.array_equal(b_phi.cpu().numpy().view(np.uint64), h_phi.view(np.uint64))
+    g = b_out.cpu().numpy()
+    pad = np.ones(g.size, dtype=bool)
+    pad[PAD + shift:PAD + shift + ncells * N] = False
+    assert np.array_equal(g.view(np.uint64)[pad], h_out.view(np.uint64)[pad]), "an entry outside out was written"
+    got = g[PAD + shift:PAD + shift + ncells * N]
+    got = got.reshape(ncells, N) if layout == 0 else got.reshape(N, ncells).T
+    assert np.isfinite(got).all(), "out was accumulated onto, not overwritten"
+    err = np.abs(got - C).max()
+    print(f"tsmm {ncells} x {K} x {N} layout {layout} shift {shift}: {err / scale:.3e} of the row magnitude")
+    assert err <= 1e-13 * scale
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+@pytest.mark.parametrize("ncells,K,N", [(77, 27, 27), (100, 128, 40), (100, 129, 129), (130, 343, 343),     # out pre-filled with NaN
+                                        (1, 27, 27), (1, 129, 216), (50, 35, 1), (33, 343, 1), (1, 1, 1)])  # one cell, one column
+def test_tsmm_overwrites_out(gpu, ncells, K, N, layout):
+    """`out = in . phi` with out full of NaN on entry: K <= 128 is one row range, K > 128 several that accumulate onto
+    the first, which must overwrite; 1e-13 of the row magnitude as test_tsmm_vs_numpy"""
+    tsmm_check(gpu, ncells, K, N, layout, 0)
+
+
+@pytest.mark.parametrize("layout", [0, 1])
+@pytest.mark.parametrize("ncells,K,N", [(77, 27, 27), (100, 129, 125), (1, 27, 27), (50, 35, 1), (4099, 125, 125)])
+def test_tsmm_8_byte_aligned_operands(gpu, ncells, K, N, layout):
+    """in, phi and out one entry off 16-byte alignment inside padded buffers"""
+    tsmm_check(gpu, ncells, K, N, layout, 1)
+
+
 def test_edge_cases_single_cell_and_empty(gpu, oracle):
     """Smallest inputs: one cell (every kernel's partial-batch path), an operator
     with zero local cells (a rank that owns no cell), zero-length vector kernels."""

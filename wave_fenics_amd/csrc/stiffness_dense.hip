@@ -413,6 +413,28 @@ static int up(Tp** p, const std::vector<Tp>& h, size_t* total)
   return WF_OK;
 }
 
+// Compiled shapes (QT, KT, DT, XR): Lagrange P1..P4 on the tetrahedron with the m = p Gauss-Jacobi
+// rule, (nd, nq) = (4,1) (10,8) (20,27) (35,64), plus P4 with the m = 3 rule.  The XR = 0 form of a
+// shape serves every other (nd, nq) with the same tile counts.
+#define WF_DENSE_SHAPES(F) \
+  F(1, 1, 1, 0)            \
+  F(1, 3, 1, 0)            \
+  F(2, 5, 2, 4) /* P3: nd = 20 = 16 + 4 */ \
+  F(2, 5, 2, 0)            \
+  F(4, 9, 3, 3) /* P4: nd = 35 = 32 + 3 */ \
+  F(4, 9, 3, 0)            \
+  F(2, 9, 3, 3)            \
+  F(2, 9, 3, 0)
+
+static bool dense_shape_compiled(int QT, int KT, int DT)
+{
+#define WF_DENSE_HAS(Q, K, D, X) \
+  if (QT == Q && KT == K && DT == D) return true;
+  WF_DENSE_SHAPES(WF_DENSE_HAS)
+#undef WF_DENSE_HAS
+  return false;
+}
+
 // Host setup: padded table, per-cell affine geometry C = |det J| K K^T, per-batch
 // unique-dof lists and local indices.
 int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, const double* dphi,
@@ -425,6 +447,10 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
   d->KT = (nd + 3) / 4;
   d->DT = (nd + 15) / 16;
   d->nw = 4;
+  if (!dense_shape_compiled(d->QT, d->KT, d->DT)) {
+    set_error("stiffness_dense: (nd, nq) shape not compiled (supported: tetrahedron P1..P4)");
+    return WF_ERR_UNSUPPORTED;
+  }
 
   const int NCB = 16 * d->nw;
   const int NQP = 16 * d->QT, KP = dense_pitch(d->KT);
@@ -462,6 +488,12 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
     };
     double* cc = &C[(size_t)c * 6];
     cc[0] = kk(0, 0); cc[1] = kk(0, 1); cc[2] = kk(0, 2); cc[3] = kk(1, 1); cc[4] = kk(1, 2); cc[5] = kk(2, 2);
+    bool finite = ad > 0.0;   // false for det J = 0 and for NaN
+    for (int e = 0; e < 6; ++e) finite = finite && std::isfinite(cc[e]);
+    if (!finite) {
+      set_error("wf_op_create_dense_simplex: cell " + std::to_string(c) + " is degenerate (det J is zero or not finite)");
+      return WF_ERR_INVALID;
+    }
   }
   const int KT2 = (d->KT + 1) / 2;
   std::vector<uint32_t> locP((size_t)nbatch * KT2 * 4 * NCB, 0);
@@ -551,20 +583,12 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
     return d->numax <= 5 * 256 ? launch_dense_t<Q, K, D, 4, 5, X>(d, coeff, do_clamp, d_x, d_y, s)                \
                                : launch_dense_t<Q, K, D, 4, 9, X>(d, coeff, do_clamp, d_x, d_y, s);
 
-// Compiled shapes: Lagrange P1..P4 on the tetrahedron with the m = p Gauss-Jacobi
-// rule (nd, nq) = (4,1) (10,8) (20,27) (35,64), plus P4 with the m = 3 rule.
+// (dense_setup has refused every shape that is not in WF_DENSE_SHAPES)
 int launch_stiffness_dense(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,
                            hipStream_t s)
 {
   if (d->nbatch == 0) return WF_OK;
-  WF_DENSE_CASE(1, 1, 1, 0)
-  WF_DENSE_CASE(1, 3, 1, 0)
-  WF_DENSE_CASE(2, 5, 2, 4)   // P3: nd = 20 = 16 + 4
-  WF_DENSE_CASE(2, 5, 2, 0)
-  WF_DENSE_CASE(4, 9, 3, 3)   // P4: nd = 35 = 32 + 3
-  WF_DENSE_CASE(4, 9, 3, 0)
-  WF_DENSE_CASE(2, 9, 3, 3)
-  WF_DENSE_CASE(2, 9, 3, 0)
+  WF_DENSE_SHAPES(WF_DENSE_CASE)
   set_error("stiffness_dense: (nd, nq) shape not compiled (supported: tetrahedron P1..P4)");
   return WF_ERR_UNSUPPORTED;
 }
