@@ -16,6 +16,7 @@ SOURCES = [
     "mass_march.hip", "stiffness_dense.hip", "tsmm.hip", "vector_kernels.hip", "comm.hip", "cg.hip", "api.hip",
 ]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "stiffness_core.h"),
+           os.path.join(CSRC, "march_column.h"),
            os.path.join(ROOT, "include", "wavehip.h")]
 
 
@@ -41,7 +42,8 @@ def _compile(src: str, force: bool, verbose: bool) -> str:
     if not force and os.path.exists(obj) and all(os.path.getmtime(d) <= os.path.getmtime(obj) for d in deps):
         return obj
     cmd = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
-           "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-c", path, "-o", obj]
+           "-I",
+           os.path.join(ROOT, "include"), "-I", CSRC, "-c", path, "-o", obj]
     if verbose:
         cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
     subprocess.check_call(cmd)

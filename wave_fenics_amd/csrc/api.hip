@@ -6,7 +6,7 @@
 #include <cstring>
 #include <memory>
 
-#include "common.h"
+#include "march_column.h"
 
 using namespace wf;
 
@@ -1245,9 +1245,9 @@ int split_box_items(wf_op* op, bool ghost_below, Interface&& interface)
   const int ncols = cols.count(), nseg = box_segments(op->nz, lz, op->lz0_split);
   std::vector<int32_t> items[4];
   for (int seg = 0; seg < nseg; ++seg) {
-    const int z0 = box_segment_begin(seg, lz, op->lz0_split), z1 = box_segment_end(seg, op->nz, lz, op->lz0_split);
+    const BoxSegment zs = box_segment(seg, op->nz, lz, op->lz0_split);
     for (int col = 0; col < ncols; ++col)
-      items[interface(col % cols.nbx, col / cols.nbx, seg, z0, z1) ? 1 : 0].push_back(col + ncols * seg);
+      items[interface(col % cols.nbx, col / cols.nbx, seg, zs.z0, zs.z1) ? 1 : 0].push_back(col + ncols * seg);
   }
   return set_item_lists(op, items);
 }

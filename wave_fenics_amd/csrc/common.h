@@ -147,9 +147,9 @@ int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int
                                  const double* d_D, const DMat& am, double coeff, const double* d_x, double* d_y,
                                  const int32_t* d_items, int nitems, hipStream_t s);
 int march_owner_resident(int P, int variant);   // workgroups resident on the device (occupancy query)
-// Work items of the box marching kernels, host side (the kernels carry the same arithmetic): item = column + columns *
-// z segment.  Columns of the atomic forms are pieces of bx x by cells; the owner form cuts the lattice lines 0 .. P nx
-// into pieces of P*bx x P*by from (0, 0).  Segment 0 has lz0 layers, every later one lz (the last one what is left).
+// Work items of the box marching kernels: item = column + columns * z segment.  Columns of the atomic forms are pieces of bx x by cells; the owner form cuts the lattice lines 0 .. P nx
+// into pieces of P*bx x P*by from (0, 0).  Segment 0 has lz0 layers, every later one lz (the last one what is left):
+// box_segment (march_column.h), for host and kernels alike.
 struct BoxColumns {
   int nbx, nby;
   int count() const { return nbx * nby; }
@@ -160,8 +160,6 @@ inline BoxColumns box_owner_columns(int P, int nx, int ny, int bx, int by)
   return box_columns(P * nx + 1, P * ny + 1, P * bx, P * by);
 }
 inline int box_segments(int nz, int lz, int lz0) { return 1 + (std::max(nz - lz0, 0) + lz - 1) / lz; }
-inline int box_segment_begin(int seg, int lz, int lz0) { return seg == 0 ? 0 : lz0 + (seg - 1) * lz; }
-inline int box_segment_end(int seg, int nz, int lz, int lz0) { return std::min(nz, seg == 0 ? lz0 : lz0 + seg * lz); }
 // indexed marching kernels for arbitrary dofmaps (generic_plan.cpp, stiffness_march_idx.hip, stiffness_march_ks.hip)
 struct MarchPlan {
   bool ok = false;                      // false: the mesh does not tile into lattice columns
@@ -187,13 +185,13 @@ int orient_sign(int code);                                       // +1 rotation,
 int build_march_plan(int P, size_t ncells, const int32_t* tdm, int BX, int BY, int lz_max, int lz_fixed, bool normalise,
                      MarchPlan* plan);
 constexpr int OP_KIND_STIFFNESS = 0, OP_KIND_MASS = 1;
-// column cross-section, LDS need and LDS budget (per workgroup) of the indexed marching kernel of (kind, P)
+// column cross-section, LDS need and LDS budget (per workgroup) of the indexed marching kernel of (kind, P); the
+// needs of the k-split and the dense-mass kernel themselves: march_ks_lds_bytes, mass_march_lds_bytes (march_column.h)
 void march_idx_shape(int kind, int P, int* bx, int* by);   // stiffness: keeps a compiled (*bx, *by) of the k-split kernel
 size_t march_idx_lds_bytes(int kind, int P, int BX, int BY, int lz);
 size_t march_idx_lds_budget(int kind, int P, int BX, int BY);
 // dense mass on the lattice columns (mass_march.hip)
 void mass_march_shape(int P, int* bx, int* by);
-size_t mass_march_lds_bytes(int P, int BX, int BY, int lz);
 int launch_mass_march(int P, const MarchPlanDev& pd, const double* d_detJblk, const double* d_phi1, const double* d_x,
                       double* d_y, hipStream_t s);
 int launch_stiffness_march_idx(int P, const MarchPlanDev& pd, const double* d_G6blk, const double* d_D,
@@ -202,7 +200,6 @@ int launch_stiffness_march_idx(int P, const MarchPlanDev& pd, const double* d_G6
 // k-split marching kernel (stiffness_march_ks.hip): the stiffness kernel of every degree
 bool march_ks_shape(int P, int* bx, int* by);   // keeps a compiled (*bx, *by), else sets the degree's default
 int march_ks_resident(int P, int bx, int by);   // workgroups resident on the chip
-size_t march_ks_lds_bytes(int P, int BX, int BY, int lz, bool idx);
 int launch_stiffness_march_ks_box(int P, int bx, int by, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,
                                   const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_y,
                                   const int32_t* d_items, int nitems, hipStream_t s);

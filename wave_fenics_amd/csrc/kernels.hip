@@ -15,6 +15,7 @@
 // 16-byte loads that are contiguous across the wave, and all loads of a batch
 // are issued before any arithmetic.
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 
@@ -23,6 +24,23 @@ namespace wf {
 // --------------------------------------------------------------------------
 // small helpers
 // --------------------------------------------------------------------------
+// f(std::integral_constant<int, P>) for the degree P = 1..7; any other degree is the error `what`
+template <class F>
+static int dispatch_degree(int P, const char* what, F&& f)
+{
+  switch (P) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+  }
+  set_error(what);
+  return WF_ERR_UNSUPPORTED;
+}
+
 __device__ __forceinline__ double clamp101(double v)
 {
   // xt::isclose(v, b) with rtol 1e-5, atol 1e-8, applied for b = -1, 0, 1
@@ -239,8 +257,19 @@ __global__ void k_geometry_box(int n, int nx, int ny, int nz, int bx, int by, in
 }
 
 }  // namespace wf
-#include "stiffness_core.h"  // stiffness_column<P>
+#include "stiffness_core.h"  // stiffness_column<P>, load_stream
 namespace wf {
+
+// the whole geometry of one thread's column (i, j, *) of a batch, from its first entry gp = G6blk[batch][0][0][t]:
+// 3 n non-temporal 16-byte loads, contiguous across the wave, issued together (NT: threads of the batch)
+template <int P>
+__device__ __forceinline__ void batch_load_geometry(double2 (&g)[P + 1][3], const double2* gp, int NT)
+{
+#pragma unroll
+  for (int k = 0; k < P + 1; ++k)
+#pragma unroll
+    for (int p = 0; p < 3; ++p) g[k][p] = load_stream(gp + (size_t)(k * 3 + p) * NT);
+}
 
 // --------------------------------------------------------------------------
 // generic stiffness: arbitrary tensor-ordered dofmap, atomic scatter
@@ -274,6 +303,7 @@ __global__ __launch_bounds__(256) void k_stiffness_generic(int ncells, const int
   if (active) {
     const double2* gp = G6blk + (batch * n * 3) * (size_t)NT + t;
     if (ablate & 2) gp = G6blk + t;   // diagnostic: every workgroup re-reads batch 0 (L2-resident)
+    // batch_load_geometry, written out: the call compiles to other code in this kernel
 #pragma unroll
     for (int k = 0; k < n; ++k)
 #pragma unroll
@@ -322,10 +352,6 @@ __global__ __launch_bounds__(256) void k_stiffness_generic(int ncells, const int
 }
 
 // --------------------------------------------------------------------------
-// structured box stiffness: implicit dofmap, block dof tile in LDS, atomics only
-// on dofs shared with a neighbouring block
-// --------------------------------------------------------------------------
-// --------------------------------------------------------------------------
 // generic stiffness, batch-unique form (default for arbitrary dofmaps): the host
 // lists the unique dofs of every batch of CB cells once (uniq, sorted) and the
 // position of every element-local dof in that list (loc, uint16).  x is read once
@@ -334,7 +360,15 @@ __global__ __launch_bounds__(256) void k_stiffness_generic(int ncells, const int
 // order -- fewer and better-shaped atomic requests than the element-wise scatter
 // (P4, lexicographic numbering: 1025 instead of 1250 per batch, runs of 41
 // contiguous doubles instead of 5).
+// The product library launches the pipelined forms below (k_stiffness_generic_up2 / _up).  This plain one-batch-per-
+// workgroup form carries the ablation masks, so it is compiled for the diagnostic build only (-DWF_DIAG, where a
+// non-zero WF_ABLATE selects it) or as the only form with -DWF_GENERIC_PIPELINED=0.
 // --------------------------------------------------------------------------
+#ifndef WF_GENERIC_PIPELINED
+#define WF_GENERIC_PIPELINED 1
+#endif
+#if defined(WF_DIAG) || !WF_GENERIC_PIPELINED
+#define WF_GENERIC_U_PLAIN 1
 template <int P>
 __global__ __launch_bounds__(256) void k_stiffness_generic_u(int ncells, const int32_t* __restrict__ uoff,
                                                              const int32_t* __restrict__ uniq,
@@ -364,10 +398,7 @@ __global__ __launch_bounds__(256) void k_stiffness_generic_u(int ncells, const i
   if (active) {
     const double2* gp = G6blk + (batch * n * 3) * (size_t)NT + t;
     if (ablate & 2) gp = G6blk + t;
-#pragma unroll
-    for (int k = 0; k < n; ++k)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) g[k][p] = load_stream(gp + (size_t)(k * 3 + p) * NT);
+    batch_load_geometry<P>(g, gp, NT);
   }
   if (t < n * n) sD[t] = dD[t];
 
@@ -412,6 +443,7 @@ __global__ __launch_bounds__(256) void k_stiffness_generic_u(int ncells, const i
     }
   }
 }
+#endif
 
 // The same kernel as a persistent workgroup that walks batches and carries the NEXT batch's unique-dof indices in
 // registers: the x gather of a batch is a chain of three dependent loads (uoff -> uniq -> x), and the ablation masks
@@ -463,13 +495,7 @@ __global__ __launch_bounds__(256) void k_stiffness_generic_up(int ncells, int nb
 #pragma unroll
     for (int m = 0; m < NFLAT; ++m) xr[m] = x[uq[m]];
     double2 g[n][3];
-    {
-      const double2* gp = G6blk + ((size_t)b * n * 3) * (size_t)NT + (active ? t : NT - 1);
-#pragma unroll
-      for (int k = 0; k < n; ++k)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) g[k][p] = load_stream(gp + (size_t)(k * 3 + p) * NT);
-    }
+    batch_load_geometry<P>(g, G6blk + ((size_t)b * n * 3) * (size_t)NT + (active ? t : NT - 1), NT);
     uint16_t lc[NFLAT];
     const int nvalid = min(CB, ncells - cell0) * nd;
 #pragma unroll
@@ -567,11 +593,7 @@ __global__ __launch_bounds__(256) void k_stiffness_generic_up2(int ncells, int n
   auto load_batch = [&](double (&xr)[NFLAT], double2 (&g)[n][3], uint16_t (&lc)[NFLAT], const int32_t (&uq)[NFLAT], int b) {
 #pragma unroll
     for (int m = 0; m < NFLAT; ++m) xr[m] = x[uq[m]];
-    const double2* gp = G6blk + ((size_t)b * n * 3) * (size_t)NT + (active ? t : NT - 1);
-#pragma unroll
-    for (int k = 0; k < n; ++k)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) g[k][p] = load_stream(gp + (size_t)(k * 3 + p) * NT);
+    batch_load_geometry<P>(g, G6blk + ((size_t)b * n * 3) * (size_t)NT + (active ? t : NT - 1), NT);
     const int cell0 = b * CB, nvalid = min(CB, ncells - cell0) * nd;
 #pragma unroll
     for (int m = 0; m < NFLAT; ++m) {
@@ -665,6 +687,10 @@ __global__ __launch_bounds__(256) void k_stiffness_generic_up2(int ncells, int n
   }
 }
 
+// --------------------------------------------------------------------------
+// structured box stiffness: implicit dofmap, block dof tile in LDS, atomics only
+// on dofs shared with a neighbouring block
+// --------------------------------------------------------------------------
 template <int P>
 __global__ __launch_bounds__(256) void k_stiffness_box(int nx, int ny, int nz, int bx, int by, int bz,
                                                        const double2* __restrict__ G6blk,
@@ -696,6 +722,7 @@ __global__ __launch_bounds__(256) void k_stiffness_box(int nx, int ny, int nz, i
   if (inrange) {
     const double2* gp = G6blk + ((size_t)blockIdx.x * n * 3) * (size_t)NT + t;
     if (ablate & 2) gp = G6blk + t;
+    // batch_load_geometry, written out: the call compiles to other code in this kernel
 #pragma unroll
     for (int k = 0; k < n; ++k)
 #pragma unroll
@@ -1063,17 +1090,9 @@ int launch_mass_dense_col(int P, int ncells, const int32_t* d_uoff, const int32_
                           const double* d_phi1, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s)
 {
   if (ncells == 0) return WF_OK;
-  switch (P) {
-    case 1: return launch_mass_dense_col_t<1>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-    case 2: return launch_mass_dense_col_t<2>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-    case 3: return launch_mass_dense_col_t<3>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-    case 4: return launch_mass_dense_col_t<4>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-    case 5: return launch_mass_dense_col_t<5>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-    case 6: return launch_mass_dense_col_t<6>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-    case 7: return launch_mass_dense_col_t<7>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
-  }
-  set_error("mass_dense_col: degree must be 1..7");
-  return WF_ERR_UNSUPPORTED;
+  return dispatch_degree(P, "mass_dense_col: degree must be 1..7", [&](auto p) {
+    return launch_mass_dense_col_t<decltype(p)::value>(ncells, d_uoff, d_uniq, d_loc, d_phi1, d_detJ, d_x, d_y, s);
+  });
 }
 
 // --------------------------------------------------------------------------
@@ -1146,9 +1165,6 @@ static int launch_stiffness_generic_t(int ncells, const int32_t* d_dofmap, const
   return WF_OK;
 }
 
-#ifndef WF_GENERIC_PIPELINED
-#define WF_GENERIC_PIPELINED 1
-#endif
 #ifndef WF_GENERIC_UP2_MAXP
 #define WF_GENERIC_UP2_MAXP 4   // degrees that use the fully pipelined kernel (two geometry register sets; P5, P6 need 256 VGPRs + AGPRs: one wave per SIMD)
 #endif
@@ -1160,27 +1176,27 @@ static int launch_stiffness_generic_u_t(int ncells, const int32_t* d_uoff, const
   constexpr int n = P + 1, nd = n * n * n, CB = 256 / (n * n);
   const unsigned nb = (unsigned)((ncells + CB - 1) / CB);
   const size_t lds = (size_t)(3 * CB * nd + n * n) * sizeof(double);
-#if WF_GENERIC_PIPELINED
-  if (ablate_flags() == 0) {
-    // persistent workgroups, as many as fit the chip at this kernel's register / LDS use (4 per CU at P <= 4)
-    int per_cu = 0;
-    if constexpr (P <= WF_GENERIC_UP2_MAXP) {
-      WF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_generic_up2<P>, 256, lds));
-      const unsigned grid = std::min<unsigned>(nb, (unsigned)std::max(1, per_cu) * 256u);
-      hipLaunchKernelGGL(k_stiffness_generic_up2<P>, dim3(grid), dim3(256), lds, s, ncells, (int)nb, d_uoff, d_uniq, d_loc,
-                         reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y);
-    } else {
-      WF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_generic_up<P>, 256, lds));
-      const unsigned grid = std::min<unsigned>(nb, (unsigned)std::max(1, per_cu) * 256u);
-      hipLaunchKernelGGL(k_stiffness_generic_up<P>, dim3(grid), dim3(256), lds, s, ncells, (int)nb, d_uoff, d_uniq, d_loc,
-                         reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y);
-    }
+#ifdef WF_GENERIC_U_PLAIN
+  if (!WF_GENERIC_PIPELINED || ablate_flags() != 0) {
+    hipLaunchKernelGGL(k_stiffness_generic_u<P>, dim3(nb), dim3(256), lds, s, ncells, d_uoff, d_uniq, d_loc,
+                       reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, ablate_flags());
     WF_LAUNCH_CHECK();
     return WF_OK;
   }
 #endif
-  hipLaunchKernelGGL(k_stiffness_generic_u<P>, dim3(nb), dim3(256), lds, s, ncells, d_uoff, d_uniq, d_loc,
-                     reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y, ablate_flags());
+  // persistent workgroups, as many as fit the chip at this kernel's register / LDS use (4 per CU at P <= 4)
+  int per_cu = 0;
+  if constexpr (P <= WF_GENERIC_UP2_MAXP) {
+    WF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_generic_up2<P>, 256, lds));
+    const unsigned grid = std::min<unsigned>(nb, (unsigned)std::max(1, per_cu) * 256u);
+    hipLaunchKernelGGL(k_stiffness_generic_up2<P>, dim3(grid), dim3(256), lds, s, ncells, (int)nb, d_uoff, d_uniq, d_loc,
+                       reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y);
+  } else {
+    WF_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stiffness_generic_up<P>, 256, lds));
+    const unsigned grid = std::min<unsigned>(nb, (unsigned)std::max(1, per_cu) * 256u);
+    hipLaunchKernelGGL(k_stiffness_generic_up<P>, dim3(grid), dim3(256), lds, s, ncells, (int)nb, d_uoff, d_uniq, d_loc,
+                       reinterpret_cast<const double2*>(d_G6blk), d_D, dm, coeff, d_x, d_y);
+  }
   WF_LAUNCH_CHECK();
   return WF_OK;
 }
@@ -1190,17 +1206,9 @@ int launch_stiffness_generic_u(int P, int ncells, const int32_t* d_uoff, const i
                                const double* d_x, double* d_y, hipStream_t s)
 {
   if (ncells == 0) return WF_OK;
-  switch (P) {
-    case 1: return launch_stiffness_generic_u_t<1>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 2: return launch_stiffness_generic_u_t<2>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 3: return launch_stiffness_generic_u_t<3>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 4: return launch_stiffness_generic_u_t<4>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 5: return launch_stiffness_generic_u_t<5>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 6: return launch_stiffness_generic_u_t<6>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 7: return launch_stiffness_generic_u_t<7>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-  }
-  set_error("stiffness: degree must be 1..7");
-  return WF_ERR_UNSUPPORTED;
+  return dispatch_degree(P, "stiffness: degree must be 1..7", [&](auto p) {
+    return launch_stiffness_generic_u_t<decltype(p)::value>(ncells, d_uoff, d_uniq, d_loc, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
+  });
 }
 
 int launch_stiffness_generic(int P, int ncells, const int32_t* d_dofmap, const double* d_G6blk,
@@ -1208,17 +1216,9 @@ int launch_stiffness_generic(int P, int ncells, const int32_t* d_dofmap, const d
                              hipStream_t s)
 {
   if (ncells == 0) return WF_OK;
-  switch (P) {
-    case 1: return launch_stiffness_generic_t<1>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 2: return launch_stiffness_generic_t<2>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 3: return launch_stiffness_generic_t<3>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 4: return launch_stiffness_generic_t<4>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 5: return launch_stiffness_generic_t<5>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 6: return launch_stiffness_generic_t<6>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 7: return launch_stiffness_generic_t<7>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-  }
-  set_error("stiffness: degree must be 1..7");
-  return WF_ERR_UNSUPPORTED;
+  return dispatch_degree(P, "stiffness: degree must be 1..7", [&](auto p) {
+    return launch_stiffness_generic_t<decltype(p)::value>(ncells, d_dofmap, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
+  });
 }
 
 template <int P>
@@ -1246,17 +1246,9 @@ int launch_stiffness_box(int P, int nx, int ny, int nz, int bx, int by, int bz, 
     set_error("stiffness_box: block does not fit a 256-thread workgroup");
     return WF_ERR_INVALID;
   }
-  switch (P) {
-    case 1: return launch_stiffness_box_t<1>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 2: return launch_stiffness_box_t<2>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 3: return launch_stiffness_box_t<3>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 4: return launch_stiffness_box_t<4>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 5: return launch_stiffness_box_t<5>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 6: return launch_stiffness_box_t<6>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-    case 7: return launch_stiffness_box_t<7>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
-  }
-  set_error("stiffness_box: degree must be 1..7");
-  return WF_ERR_UNSUPPORTED;
+  return dispatch_degree(P, "stiffness_box: degree must be 1..7", [&](auto p) {
+    return launch_stiffness_box_t<decltype(p)::value>(nx, ny, nz, bx, by, bz, d_G6blk, d_D, dm, coeff, d_x, d_y, s);
+  });
 }
 
 int launch_mass_lumped(int64_t nentries, const int32_t* d_dofmap, const double* d_detJ, const double* d_x,

@@ -25,8 +25,7 @@
 // tools/mass_trace.sh/.py: per-wave phase timeline.  P6 before these four changes (private per-cell results gathered
 // by the flush, whole table staged in LDS: lz = 4): layer 5.0 us = prefetch issue 1.0 + passes 1.4 + x -> LDS 0.5 +
 // flush 1.8; now about 3.2 us.  HBM-bound by its bytes (8 B of det J w per point + x + y), latency-bound in practice.
-#include <type_traits>
-
+#include "march_column.h"
 #include "stiffness_core.h"
 
 namespace wf {
@@ -34,41 +33,31 @@ namespace wf {
 // Diagnostic build (tools/mass_trace.sh): per-wave timestamps of the phases of the first layers of the first 512
 // workgroups, 100 MHz constant clock.
 #ifdef WF_MASS_TRACE
-constexpr int kMassTraceIters = 12, kMassTraceSlots = 10;
-__device__ unsigned long long g_mass_trace[512 * 4 * kMassTraceIters * kMassTraceSlots];
-#define WF_MSTR(slot)                                                                 \
-  if ((threadIdx.x & 63) == 0 && l < kMassTraceIters && blockIdx.x < 512 && (threadIdx.x >> 6) < 4) \
-  g_mass_trace[((blockIdx.x * 4 + (threadIdx.x >> 6)) * kMassTraceIters + l) * kMassTraceSlots + (slot)] = wall_clock64()
+WF_COLUMN_TRACE(g_mass_trace, wf_debug_mass_trace, 12, 10)
+#define WF_MSTR(slot) WF_TRACE_STAMP(g_mass_trace, l, slot)
 #else
 #define WF_MSTR(slot)
 #endif
 
 template <int P, int BX, int BY>
-struct MassLayout {
-  static constexpr int n = P + 1, n2 = n * n, nd = n * n2, CB = BX * BY;
+struct MassLayout : ColumnTile<P, BX, BY> {
+  using T = ColumnTile<P, BX, BY>;
+  static constexpr int n2 = T::n2, nd = T::nd, CB = T::CB, TP = T::TP;
   static constexpr int CW = 64 / n2;                      // cells per wave
-  static constexpr int NWV = (CB + CW - 1) / CW;          // waves per workgroup
-  static constexpr int WG = 64 * NWV;
-  static constexpr int TX = P * BX + 1, TY = P * BY + 1, TP = TX * TY;
+  static constexpr int WG = mass_workgroup_size(P, BX, BY);   // whole waves: ceil(CB / CW) of them
   static constexpr int oUx = 0;                           // [2][(P + 1) TP]
   static constexpr int oO = oUx + 2 * (P + 1) * TP;       // [2][P TP] result tile of a layer, cells combined
   static constexpr int oCy = oO + 2 * P * TP;             // [2][CB n2]
   static constexpr int oA = oCy + 2 * CB * n2;            // [CB nd] wave-private scratch of a cell (the passes work in place)
   static constexpr int oDump = oA + CB * nd;               // [WG] where a thread's out-of-tile last position is stored
-  static constexpr int ndoubles = ((oDump + 64 * ((CB + CW - 1) / CW) + 1) / 2) * 2;
+  static constexpr int ndoubles = ((oDump + WG + 1) / 2) * 2;
   // ring of index-table planes behind the doubles: at the time layer l stores the planes of layer l + 2
   // (<= P l + 3 P) the flush of layer l - 1 may still read plane P (l - 1): 4 P + 1 planes are live
   static constexpr int RP = 4 * P + 1, RPT = RP * TP;
+  // the ring is followed by a dump slot per thread for the table planes' out-of-tile last positions
+  static constexpr size_t bytes = ndoubles * sizeof(double) + (size_t)(RPT + WG) * sizeof(int32_t);
   static_assert(CW >= 1, "a cell does not fit a wave");
 };
-
-size_t mass_march_lds_bytes(int P, int BX, int BY, int lz)
-{
-  const int n = P + 1, n2 = n * n, nd = n * n2, CB = BX * BY, TP = (P * BX + 1) * (P * BY + 1);
-  const size_t d = (size_t)2 * (P + 1) * TP + (size_t)2 * P * TP + (size_t)2 * CB * n2 + (size_t)CB * nd + 64 * (size_t)((CB + (64 / n2) - 1) / (64 / n2)) + 2;
-  (void)lz;   // the index table streams through a ring of 4 P + 1 planes: the footprint does not depend on the segment length
-  return d * sizeof(double) + ((size_t)(4 * P + 1) * TP + 64 * (size_t)((CB + (64 / n2) - 1) / (64 / n2))) * sizeof(int32_t);
-}
 
 struct MassArgs {
   int lz, tile_size;
@@ -374,15 +363,13 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
     __syncthreads();   // the one workgroup barrier of the layer
     WF_MSTR(8);
   };
-  using Yes = std::integral_constant<bool, true>;
-  using No = std::integral_constant<bool, false>;
   auto layer_any = [&](double (&dcur)[n], double (&dnext)[n], int l, int b) {
     if (l + 2 < nl)
-      layer(Yes{}, Yes{}, dcur, dnext, l, b);
+      layer(On{}, On{}, dcur, dnext, l, b);
     else if (l + 1 < nl)
-      layer(Yes{}, No{}, dcur, dnext, l, b);
+      layer(On{}, Off{}, dcur, dnext, l, b);
     else
-      layer(No{}, No{}, dcur, dnext, l, b);
+      layer(Off{}, Off{}, dcur, dnext, l, b);
   };
   for (int l = 0; l < nl; l += 2) {
     layer_any(dA, dB, l, 0);
@@ -401,6 +388,7 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
       const int32_t off = sIdx[ring(rb_flush, pos)];
       if (off < 0) continue;
       const int J = pos / TX, I = pos % TX;
+      // column_plane_sum (march_column.h), written out: the call compiles to other code in this kernel
       const int ca = I / P, ia = I % P, cb = J / P, jb = J % P;
       double v = 0.0;
       if (cb < BY) {
@@ -431,6 +419,12 @@ static int launch_mass_t(const MassArgs& a, int nitems, size_t lds, hipStream_t 
 // 0.155, 2x1 0.166; P6 2x2 0.126, 2x1 0.138, 1x1 0.182; P2 7x4 0.126, 7x2 0.140 (tools/bench_mass_lz.py).
 #define WF_MASS_SHAPES(X) \
   X(1, 8, 8) X(2, 7, 4) X(3, 4, 4) X(4, 4, 2) X(4, 2, 2) X(5, 2, 2) X(6, 2, 2) X(6, 2, 1) X(7, 2, 1)
+
+#define X(PP, BXX, BYY)                                                                     \
+  static_assert(mass_march_lds_bytes(PP, BXX, BYY, 0) >= MassLayout<PP, BXX, BYY>::bytes, \
+                "mass_march_lds_bytes does not cover MassLayout");
+WF_MASS_SHAPES(X)
+#undef X
 
 // keeps (*bx, *by) if that cross-section is compiled for the degree, else the degree's default
 void mass_march_shape(int P, int* bx, int* by)
@@ -473,13 +467,3 @@ int launch_mass_march(int P, const MarchPlanDev& pd, const double* d_detJblk, co
 }
 
 }  // namespace wf
-
-#ifdef WF_MASS_TRACE
-extern "C" int wf_debug_mass_trace(unsigned long long* host, size_t n)
-{
-  void* sym = nullptr;
-  if (hipGetSymbolAddress(&sym, HIP_SYMBOL(wf::g_mass_trace)) != hipSuccess) return -1;
-  if (n > sizeof(wf::g_mass_trace) / 8) n = sizeof(wf::g_mass_trace) / 8;
-  return hipMemcpy(host, sym, n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -23,8 +23,7 @@
 // y accumulated, coefficient -c0^2 (operators.hpp:114-115).
 #include <cstdlib>
 
-#include <type_traits>
-
+#include "march_column.h"
 #include "stiffness_core.h"
 
 namespace wf {
@@ -40,18 +39,9 @@ namespace wf {
 //    instead of the round-robin order: 0.247 ms.
 // Diagnostic build (tools/march_trace.sh): per-wave timestamps of the phases of the first layers of
 // the first 512 workgroups, 100 MHz constant clock.
-#ifndef WF_MARCH_BRANCHLESS_ROTATE
-#define WF_MARCH_BRANCHLESS_ROTATE 1
-#endif
-#ifndef WF_MARCH_TILE_ADD
-#define WF_MARCH_TILE_ADD 1
-#endif
 #ifdef WF_MARCH_TRACE
-constexpr int kMarchTraceIters = 12, kMarchTraceSlots = 6;
-__device__ unsigned long long g_march_trace[512 * 4 * kMarchTraceIters * kMarchTraceSlots];
-#define WF_MTR(slot)                                                                                          \
-  if ((threadIdx.x & 63) == 0 && trace_it < kMarchTraceIters && blockIdx.x < 512)                              \
-  g_march_trace[((blockIdx.x * 4 + (threadIdx.x >> 6)) * kMarchTraceIters + trace_it) * kMarchTraceSlots + (slot)] = wall_clock64()
+WF_COLUMN_TRACE(g_march_trace, wf_debug_march_trace, 12, 6)
+#define WF_MTR(slot) WF_TRACE_STAMP(g_march_trace, trace_it, slot)
 #else
 #define WF_MTR(slot)
 #endif
@@ -89,9 +79,8 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
 {
   [[maybe_unused]] const int ablate = WF_ABLATE_FLAGS(ablate_arg);
   constexpr bool PC = G != MarchGeom::point, AX = G == MarchGeom::cell_axes;
-  constexpr int n = P + 1, n2 = n * n, nd = n * n2;
-  constexpr int CB = BX * BY, NT = CB * n2;
-  constexpr int TX = P * BX + 1, TY = P * BY + 1, TP = TX * TY;
+  using T = ColumnTile<P, BX, BY>;
+  constexpr int n = T::n, n2 = T::n2, nd = T::nd, CB = T::CB, NT = CB * n2, TX = T::TX, TY = T::TY, TP = T::TP;
   constexpr int NPOS = (P * TP + 255) / 256;        // flush / x-prefetch positions per thread
   constexpr int NPOS0 = ((P + 1) * TP + 255) / 256; // prologue x positions per thread
   constexpr int NCP = (TP + 255) / 256;             // positions of one plane per thread
@@ -99,15 +88,12 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
 
   // x planes of the layer + a dump row: threads whose last position lies past the tile store there, so that the
   // stores that consume the prefetched x registers sit in straight-line code (see (c))
-  __shared__ __attribute__((aligned(16))) double Ux[(P + 1) * TP + (WF_MARCH_BRANCHLESS_ROTATE ? 256 : 0)];
-#if WF_MARCH_TILE_ADD
+  __shared__ __attribute__((aligned(16))) double Ux[(P + 1) * TP + 256];
   // results of the layer's cells, summed where they share a face (ds_add_f64): planes 0..P-1 of the tile.  The
   // flush of a position is then one LDS read (+ the zero for the next layer) and one global atomic; as a gather
   // over the (up to four) cells' private results it decoded its position and took four guarded LDS reads.
+  // (reused for the cells' carried planes in the epilogue)
   __shared__ __attribute__((aligned(16))) double O[P * TP > CB * n2 ? P * TP : CB * n2];
-#else
-  __shared__ __attribute__((aligned(16))) double O[CB * P * n2];     // per-cell results, planes 0..P-1
-#endif
   __shared__ __attribute__((aligned(16))) double Fr[AX ? 1 : CB * nd];   // the axes form has no phase scratch
   __shared__ __attribute__((aligned(16))) double Fs[AX ? 1 : CB * nd];
   __shared__ __attribute__((aligned(16))) double sD[AX ? 1 : n * n];   // the axes form reads A from dm and dD
@@ -122,7 +108,8 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
   const int Bx = col % nbx, By = col / nbx;
   // z segments: [0, lz0), then pieces of lz layers (lz0 = lz unless the operator is split for the
   // ghost exchange: a short first segment keeps the work that reads the z ghost plane small)
-  const int z0 = seg == 0 ? 0 : lz0 + (seg - 1) * lz, z1 = min(nz, seg == 0 ? lz0 : z0 + lz);
+  const BoxSegment zs = box_segment(seg, nz, lz, lz0);
+  const int z0 = zs.z0, z1 = zs.z1;
   const bool active = t < NT;
   const int cl = t / n2, ji = t % n2, j = ji / n, i = ji % n;
   const int lx = cl % BX, ly = cl / BX;
@@ -215,9 +202,7 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
     load_g(gA, z0);
   if constexpr (!AX)
     if (t < n * n) sD[t] = dD[t];
-#if WF_MARCH_TILE_ADD
   for (int e = t; e < P * TP; e += 256) O[e] = 0.0;
-#endif
   {
     const size_t base = plane * (size_t)(P * z0);
 #pragma unroll
@@ -308,14 +293,9 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
     if (active) {
       out[0] += carry;        // z-shared plane: partial sum of the layer below
       carry = out[P];
-#if WF_MARCH_TILE_ADD
       double* To = O + (P * ly + j) * TX + P * lx + i;
 #pragma unroll
       for (int k = 0; k < P; ++k) __hip_atomic_fetch_add(To + k * TP, out[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-#pragma unroll
-      for (int k = 0; k < P; ++k) O[(cl * P + k) * n2 + ji] = out[k];
-#endif
     }
     __syncthreads();
     WF_MTR(3);
@@ -325,33 +305,21 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
     // atomics share vmcnt on gfx9 and the compiler waits for vmcnt(0) once both kinds are pending:
     // placed after the flush, every layer waited for the round trip of its own atomics.
     if (has_next) {
-#if WF_MARCH_BRANCHLESS_ROTATE
       // No per-lane branches between the prefetch and its consumers: behind an exec-masked branch the compiler's
       // wait-count bookkeeping fell back to vmcnt(0), i.e. the rotate waited for the geometry instalments issued
       // AFTER the x loads as well (ISA: s_waitcnt vmcnt(1) / (2) / (0) in front of the three stores).  Only a
-      // thread's last position can lie outside the tile; it is stored to the dump row instead.
+      // thread's last position can lie outside the tile; it is stored to the dump row instead (tile_or_dump; with
+      // `if (pos < TP)` around the stores, measured and rejected, the waits above came back).
 #pragma unroll
       for (int m = 0; m < NCP; ++m) {
         const int pos = t + 256 * m;
-        Ux[(256 * (m + 1) <= TP || pos < TP) ? pos : (P + 1) * TP + t] = xcp[m];
+        Ux[tile_or_dump<TP>(m, pos, 0, (P + 1) * TP, t)] = xcp[m];
       }
 #pragma unroll
       for (int m = 0; m < NPOS; ++m) {
         const int pos = t + 256 * m;
-        Ux[(256 * (m + 1) <= P * TP || pos < P * TP) ? TP + pos : (P + 1) * TP + t] = poff[m] >= 0 ? xn[m] : 0.0;
+        Ux[tile_or_dump<P * TP>(m, pos, TP, (P + 1) * TP, t)] = poff[m] >= 0 ? xn[m] : 0.0;
       }
-#else
-#pragma unroll
-      for (int m = 0; m < NCP; ++m) {
-        const int pos = t + 256 * m;
-        if (pos < TP) Ux[pos] = xcp[m];
-      }
-#pragma unroll
-      for (int m = 0; m < NPOS; ++m) {
-        const int pos = t + 256 * m;
-        if (pos < P * TP) Ux[TP + pos] = poff[m] >= 0 ? xn[m] : 0.0;
-      }
-#endif
     }
     // axes form: consume the G_c loads here too.  Consumed in the next layer's element pass instead, their wait
     // (vmcnt counts loads and atomics in one queue) also waited for this layer's atomics.  The empty asm pins the
@@ -367,7 +335,6 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
     // (d) combine the cells of the layer (fixed order) and add the finished planes to y
 #pragma unroll
     for (int m = 0; m < NPOS; ++m) {
-#if WF_MARCH_TILE_ADD
       const int pos = t + 256 * m;
       double v = 0.0;
       if (pos < P * TP) {
@@ -375,21 +342,6 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
         O[pos] = 0.0;
       }
       if (poff[m] < 0) continue;
-#else
-      if (poff[m] < 0) continue;
-      const int pos = t + 256 * m;
-      const int pl = pos / TP, r = pos % TP, J = r / TX, I = r % TX;
-      const int ca = I / P, ia = I % P, cb = J / P, jb = J % P;
-      double v = 0.0;
-      if (cb < BY) {
-        if (ca < BX) v += O[((cb * BX + ca) * P + pl) * n2 + jb * n + ia];
-        if (ia == 0 && ca > 0) v += O[((cb * BX + ca - 1) * P + pl) * n2 + jb * n + P];
-      }
-      if (jb == 0 && cb > 0) {
-        if (ca < BX) v += O[(((cb - 1) * BX + ca) * P + pl) * n2 + P * n + ia];
-        if (ia == 0 && ca > 0) v += O[(((cb - 1) * BX + ca - 1) * P + pl) * n2 + P * n + P];
-      }
-#endif
       double* dst = y + base + poff[m];
       if (ablate & 1) {
         if (v == 1.2345e300) *dst = v;
@@ -402,8 +354,6 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
 
     __syncthreads();
   };
-  using HasNext = std::integral_constant<bool, true>;
-  using IsLast = std::integral_constant<bool, false>;
   // P <= 3 issues the whole prefetch in one burst at the top of the layer and measured 6 % SLOWER with the two
   // copies (P2 0.3125 -> 0.3325 ms; P3 unchanged; P4 0.2017 -> 0.1954 ms): one body with a run-time flag there.
   constexpr bool kTwoCopies = P >= 4;
@@ -412,13 +362,13 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
       layer(kz + 1 < z1, gA, gB, kz);   // (plain bools: a wrapper struct with operator bool compiled to 6 % slower code)
       if (kz + 1 < z1) layer(kz + 2 < z1, gB, gA, kz + 1);
     } else if (kz + 1 < z1) {
-      layer(HasNext{}, gA, gB, kz);
+      layer(On{}, gA, gB, kz);
       if (kz + 2 < z1)
-        layer(HasNext{}, gB, gA, kz + 1);
+        layer(On{}, gB, gA, kz + 1);
       else
-        layer(IsLast{}, gB, gA, kz + 1);
+        layer(Off{}, gB, gA, kz + 1);
     } else {
-      layer(IsLast{}, gA, gB, kz);
+      layer(Off{}, gA, gB, kz);
     }
   }
 
@@ -433,6 +383,7 @@ __global__ __launch_bounds__(256, march_waves(G, P)) void k_stiffness_march(
       if (pos >= TP) continue;
       const int J = pos / TX, I = pos % TX;
       if (I >= EX || J >= EY) continue;
+      // column_plane_sum (march_column.h), written out: the call compiles to other code in this kernel
       const int ca = I / P, ia = I % P, cb = J / P, jb = J % P;
       double v = 0.0;
       if (cb < BY) {
@@ -524,13 +475,3 @@ int march_resident(int P, int variant, MarchGeom geom)
 }
 
 }  // namespace wf
-
-#ifdef WF_MARCH_TRACE
-extern "C" int wf_debug_march_trace(unsigned long long* host, size_t n)
-{
-  void* sym = nullptr;
-  if (hipGetSymbolAddress(&sym, HIP_SYMBOL(wf::g_march_trace)) != hipSuccess) return -1;
-  if (n > sizeof(wf::g_march_trace) / 8) n = sizeof(wf::g_march_trace) / 8;
-  return hipMemcpy(host, sym, n * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -23,8 +23,7 @@
 // IDX = true : any dofmap, addresses from the work item's index table staged in LDS
 //              (k_march_idx's interface, plan of generic_plan.cpp).
 // HBM-bound; algorithmic bytes ncells (48 nq + 4 nd) + 16 ndofs.
-#include <type_traits>
-
+#include "march_column.h"
 #include "stiffness_core.h"
 
 namespace wf {
@@ -107,10 +106,10 @@ __device__ __forceinline__ void ks_phase2(const double* __restrict__ Fr, const d
 
 // shared-memory carve-up (doubles unless noted); dynamic LDS so that the index table can follow
 template <int P, int BX, int BY>
-struct KSLayout {
-  static constexpr int n = P + 1, n2 = n * n, nd = n * n2, CB = BX * BY, NTc = CB * n2;
-  static constexpr int TH = ((NTc + 63) / 64) * 64, WG = 2 * TH;
-  static constexpr int TX = P * BX + 1, TY = P * BY + 1, TP = TX * TY;
+struct KSLayout : ColumnTile<P, BX, BY> {
+  using T = ColumnTile<P, BX, BY>;
+  static constexpr int n = T::n, n2 = T::n2, nd = T::nd, CB = T::CB, TP = T::TP, NTc = CB * n2;
+  static constexpr int WG = ks_workgroup_size(P, BX, BY), TH = WG / 2;
   static constexpr int oUx = 0;                          // [2][(P + 1) TP]
   static constexpr int oO = oUx + 2 * (P + 1) * TP;      // [2][P TP] result tile of a layer, the cells' contributions summed (ds_add_f64)
   static constexpr int oCy = oO + 2 * P * TP;            // [2][NTc]
@@ -119,13 +118,6 @@ struct KSLayout {
   static constexpr int ndoubles = ((oD + 2 * n * n + 1) / 2) * 2;
   static_assert(NTc <= 256, "column does not fit two halves of 256 threads");
 };
-
-size_t march_ks_lds_bytes(int P, int BX, int BY, int lz, bool idx)
-{
-  const int n = P + 1, n2 = n * n, nd = n * n2, CB = BX * BY, TP = (P * BX + 1) * (P * BY + 1);
-  size_t d = (size_t)2 * (P + 1) * TP + (size_t)2 * P * TP + (size_t)2 * CB * n2 + (size_t)3 * CB * nd + 2 * n * n + 2;
-  return d * sizeof(double) + (idx ? (size_t)(P * lz + 1) * TP * sizeof(int32_t) : 0);
-}
 
 struct KSArgs {
   // box
@@ -193,9 +185,9 @@ __device__ __forceinline__ void ks_march(const KSArgs& a, const DMat& dm, double
     const int nbx = (a.nx + BX - 1) / BX, nby = (a.ny + BY - 1) / BY, ncols = nbx * nby;
     const int col = (int)(item % ncols), seg = (int)(item / ncols);
     const int Bx = col % nbx, By = col / nbx;
-    z0 = seg == 0 ? 0 : a.lz0 + (seg - 1) * a.lz;
-    const int z1 = min(a.nz, seg == 0 ? a.lz0 : z0 + a.lz);
-    nl = z1 - z0;
+    const BoxSegment zs = box_segment(seg, a.nz, a.lz, a.lz0);
+    z0 = zs.z0;
+    nl = zs.z1 - z0;
     const int NX = P * a.nx + 1, NY = P * a.ny + 1;
     plane = (size_t)NX * NY;
     const int I0 = P * Bx * BX, J0 = P * By * BY;
@@ -388,8 +380,6 @@ __device__ __forceinline__ void ks_march(const KSArgs& a, const DMat& dm, double
     // (e) flush: runs beside the next layer's phase 1 (no barrier in between)
     if (FS == 0) flush(Tb, l, 0, NPOS);
   };
-  using Yes = std::integral_constant<bool, true>;
-  using No = std::integral_constant<bool, false>;
   // Measured per cross-section (tools/bench_shapes.py, two libraries side by side): the copies help the workgroups
   // that request LATE (P5 3x1 0.205 -> 0.195 ms, P6 2x1 0.216 -> 0.194, P6 2x1 indexed 0.230 -> 0.205) and hurt the
   // 512-thread ones that request EARLY (P4 5x2 0.205 -> 0.24, P5 7x1 0.219 -> 0.233, P6 5x1 0.213 -> 0.238, P7 2x2
@@ -398,11 +388,11 @@ __device__ __forceinline__ void ks_march(const KSArgs& a, const DMat& dm, double
     if constexpr (EARLY || (P == 7 && BX * BY > 1))   // (P7 2x1: 0.165 ms with one body, 0.167 with the copies)
       layer(l + 1 < nl, l + 2 < nl, gcur, gnext, l, b);   // (plain bools: a wrapper struct with operator bool compiled to slower code)
     else if (l + 2 < nl)
-      layer(Yes{}, Yes{}, gcur, gnext, l, b);
+      layer(On{}, On{}, gcur, gnext, l, b);
     else if (l + 1 < nl)
-      layer(Yes{}, No{}, gcur, gnext, l, b);
+      layer(On{}, Off{}, gcur, gnext, l, b);
     else
-      layer(No{}, No{}, gcur, gnext, l, b);
+      layer(Off{}, Off{}, gcur, gnext, l, b);
   };
   for (int l = 0; l < nl; l += 2) {
     layer_any(gA, gB, l, 0);
@@ -427,6 +417,7 @@ __device__ __forceinline__ void ks_march(const KSArgs& a, const DMat& dm, double
         if (I >= EX || J >= EY) continue;
         dst = plane * (size_t)(P * (z0 + nl)) + gbase + (size_t)I + (size_t)(P * a.nx + 1) * J;
       }
+      // column_plane_sum (march_column.h), written out: the call compiles to other code in this kernel
       const int ca = I / P, ia = I % P, cb = J / P, jb = J % P;
       double v = 0.0;
       if (cb < BY) {
@@ -442,10 +433,10 @@ __device__ __forceinline__ void ks_march(const KSArgs& a, const DMat& dm, double
   }
 }
 
-// waves per SIMD the register allocation aims at: 512-thread workgroups (two waves per SIMD each) run one
-// per CU; 256-thread workgroups (small columns) three per CU
+// waves per SIMD the register allocation aims at, from the workgroups that share a CU (ks_workgroups_per_cu): one
+// 512-thread workgroup (two waves per SIMD), three (P4) or two 256-thread ones, four 128-thread ones
 template <int P, int BX, int BY>
-constexpr int ks_min_waves() { return KSLayout<P, BX, BY>::WG >= 512 ? 2 : (P <= 4 ? 3 : 2); }
+constexpr int ks_min_waves() { return ks_workgroups_per_cu(P, BX, BY) * KSLayout<P, BX, BY>::WG / 256; }
 
 template <int P, int BX, int BY, bool IDX>
 __global__ __launch_bounds__((KSLayout<P, BX, BY>::WG), (ks_min_waves<P, BX, BY>())) void k_march_ks(KSArgs a, DMat dm)
@@ -483,6 +474,12 @@ static int launch_ks_t(const KSArgs& a, const DMat& dm, int nwg, size_t lds, hip
   X(6, 2, 1) X(6, 1, 1) X(6, 5, 1)                                                        \
   X(7, 2, 1) X(7, 2, 2) X(7, 1, 1)
 
+#define X(PP, BXX, BYY)                                                                                                  \
+  static_assert(march_ks_lds_bytes(PP, BXX, BYY, 0, false) >= KSLayout<PP, BXX, BYY>::ndoubles * sizeof(double), \
+                "march_ks_lds_bytes does not cover KSLayout");
+WF_KS_SHAPES(X)
+#undef X
+
 bool march_ks_shape(int P, int* bx, int* by)
 {
   // keep *bx, *by when they name a compiled cross-section of this degree, else the default
@@ -506,11 +503,8 @@ bool march_ks_shape(int P, int* bx, int* by)
 // workgroups of the kernel that fit a CU (LDS and register file): the round size of the z segmentation
 int march_ks_resident(int P, int bx, int by)
 {
-  const int n = P + 1, NTc = bx * by * n * n, TH = ((NTc + 63) / 64) * 64, WG = 2 * TH;
-  const int per_cu_regs = WG >= 512 ? (P <= 3 ? 2 : 1) : (P <= 4 ? 768 / WG : 512 / WG);
-  const size_t lds = march_ks_lds_bytes(P, bx, by, 0, false);
-  const int per_cu_lds = (int)std::max<size_t>(1, (size_t)160 * 1024 / lds);
-  return 256 * std::max(1, std::min(per_cu_regs, per_cu_lds));
+  const int per_cu_lds = (int)std::max<size_t>(1, (size_t)160 * 1024 / march_ks_lds_bytes(P, bx, by, 0, false));
+  return 256 * std::max(1, std::min(ks_workgroups_per_cu(P, bx, by), per_cu_lds));
 }
 
 int launch_stiffness_march_ks_box(int P, int bx, int by, int nx, int ny, int nz, int lz, int lz0, const double* d_G6blk,

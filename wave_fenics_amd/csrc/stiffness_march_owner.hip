@@ -26,8 +26,7 @@
 // The summation order of every y entry is fixed, so the apply is bitwise reproducible.
 #include <cstdlib>
 
-#include <type_traits>
-
+#include "march_column.h"
 #include "stiffness_core.h"
 
 namespace wf {
@@ -89,7 +88,8 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   const int item = items ? items[b] : b;
   const int col = item % ncols, seg = item / ncols;
   const int Bx = col % nbxo, By = col / nbxo;
-  const int z0 = seg == 0 ? 0 : lz0 + (seg - 1) * lz, z1 = min(nz, seg == 0 ? lz0 : z0 + lz);
+  const BoxSegment zs = box_segment(seg, nz, lz, lz0);
+  const int z0 = zs.z0, z1 = zs.z1;
   const int I0 = LX * Bx, J0 = LY * By, cx0 = BX * Bx, cy0 = BY * By;
 
   // ---- the thread's line ---------------------------------------------------
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
 #pragma unroll
     for (int m = 0; m < NPF0; ++m) {
       const int pos = t + 256 * m;
-      Ux[(256 * (m + 1) <= (P + 1) * RP || pos < (P + 1) * RP) ? pos : (P + 1) * RP + t] = xin[m] ? xp[m] : 0.0;
+      Ux[tile_or_dump<(P + 1) * RP>(m, pos, 0, (P + 1) * RP, t)] = xin[m] ? xp[m] : 0.0;
     }
     store_g(gp);
     __syncthreads();
@@ -289,12 +289,12 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
 #pragma unroll
       for (int m = 0; m < NCP; ++m) {
         const int pos = t + 256 * m;
-        Ux[(256 * (m + 1) <= RP || pos < RP) ? pos : (P + 1) * RP + t] = xcp[m];
+        Ux[tile_or_dump<RP>(m, pos, 0, (P + 1) * RP, t)] = xcp[m];
       }
 #pragma unroll
       for (int m = 0; m < NPF; ++m) {
         const int pos = t + 256 * m;
-        Ux[(256 * (m + 1) <= P * RP || pos < P * RP) ? RP + pos : (P + 1) * RP + t] = poff[m] >= 0 ? xn[m] : 0.0;
+        Ux[tile_or_dump<P * RP>(m, pos, RP, (P + 1) * RP, t)] = poff[m] >= 0 ? xn[m] : 0.0;
       }
       store_g(gn);
       __syncthreads();
@@ -313,18 +313,16 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     }
   };
 
-  using HasNext = std::integral_constant<bool, true>;
-  using IsLast = std::integral_constant<bool, false>;
   // unrolled by two: the y registers swap roles instead of being copied (a copy would wait for the prefetch)
   for (int kz = z0; kz < z1; kz += 2) {
     if (kz + 1 < z1) {
-      layer(HasNext{}, yA, yB, kz);
+      layer(On{}, yA, yB, kz);
       if (kz + 2 < z1)
-        layer(HasNext{}, yB, yA, kz + 1);
+        layer(On{}, yB, yA, kz + 1);
       else
-        layer(IsLast{}, yB, yA, kz + 1);
+        layer(Off{}, yB, yA, kz + 1);
     } else {
-      layer(IsLast{}, yA, yB, kz);
+      layer(Off{}, yA, yB, kz);
     }
   }
 
