@@ -139,11 +139,35 @@ typedef enum {
                               Basix' tensor-product factorisation, instead of the engine's
                               l = i + n (j + n k).  The 3x3 axes of G are reference axes
                               0, 1, 2 = x, y, z in both conventions.                   */
-  WF_FLAG_MASS_ELEMENTWISE = 4 /* lumped mass with a dofmap: apply as the reference's
+  WF_FLAG_MASS_ELEMENTWISE = 4, /* lumped mass with a dofmap: apply as the reference's
                               gather * detJ -> scatter-add per cell
                               (spectral_mass.hpp:84-89) instead of the pre-assembled
                               diagonal y += m .* x (m = M 1 built once at create)  */
+  WF_FLAG_ORDERED = 16     /* order-fixed accumulation: y is a pure function of the inputs (bitwise
+                              reproducible on any mesh, no atomics).  See "Order-fixed accumulation"
+                              below.                                                            */
 } wf_flags;
+
+/* Order-fixed accumulation (WF_FLAG_ORDERED).  Two passes: pass 1 writes every cell's element-local
+ * result with plain stores, pass 2 gives every y entry to one thread, which sums that entry's
+ * contributions in a fixed order and reads and writes y[d] once.
+ * The order contract: the contributions of dof d are the entries of the caller's h_dofmap equal to d, in
+ * the order in which they appear when h_dofmap is read front to back (ascending cell index in the caller's
+ * numbering, then position within the cell's row); y[d] = y[d] + (((v_0 + v_1) + v_2) + ...); a dof no
+ * cell lists keeps its y.  Internal cell sorting and batch composition do not enter, nor does the dof
+ * numbering: relabelling the dofs relabels y bitwise.
+ *   wf_op_create         stiffness (P1 to P7, per-point geometry), dense mass (any tensor rule), lumped mass with
+ *                        WF_FLAG_MASS_ELEMENTWISE: kernel WF_KERNEL_CELLS_ORDERED, update WF_UPDATE_ORDERED.  Lumped mass
+ *                        without it: the kernel stays WF_KERNEL_DIAGONAL, the diagonal m = M 1 is assembled in that order
+ *                        (two creations give a bitwise equal m).
+ *   wf_op_create_box*    builds the box's lexicographic dofmap and vertex map on the host and is then that dofmap operator
+ *                        (wf_op_info_t.structured stays 1).
+ *   wf_op_create_dense_simplex   WF_ERR_UNSUPPORTED.
+ * Any non-default wf_tuning field other than keep_cell_order is WF_ERR_INVALID together with the flag (there is no kernel
+ * to choose); wf_op_set_ghost_faces / _dofs are WF_ERR_UNSUPPORTED as for the batch kernels.  The operator owns the
+ * scratch v[ncells * nd] (counted in device_bytes): ONE APPLY PER OPERATOR MAY BE IN FLIGHT AT A TIME -- applies of one
+ * handle on different streams must be ordered by the caller.  alg_bytes is the default form's formula plus
+ * 20 ncells nd + 4 (ndofs + 1).  wf_dot / wf_cg keep their own cross-workgroup atomics. */
 
 /* Which kernel an operator runs (wf_op_info_t.kernel) ... */
 typedef enum {
@@ -156,7 +180,9 @@ typedef enum {
   WF_KERNEL_DIAGONAL = 5,       /* pre-assembled lumped mass, y += m .* x                                   */
   WF_KERNEL_MASS_DENSE_ANY = 6, /* k_mass_dense: any tensor rule (nq1 != P+1 allowed)                       */
   WF_KERNEL_DENSE_SIMPLEX = 7,  /* k_stiffness_dense: MFMA fp64, affine simplices                           */
-  WF_KERNEL_ELEMENTWISE = 8     /* k_mass_lumped: one thread per element-local dof                          */
+  WF_KERNEL_ELEMENTWISE = 8,    /* k_mass_lumped: one thread per element-local dof                          */
+  WF_KERNEL_CELLS_ORDERED = 9   /* WF_FLAG_ORDERED: cell batches store element-local results, one thread per y
+                                   entry sums them in a fixed order (ordered.hip)                           */
 } wf_kernel_id;
 
 /* ... and the explicit, thread-safe way to select one (tests, tuning runs).  Every field 0 =
@@ -217,8 +243,9 @@ typedef enum {
                                  on per-point geometry (the owner form there is on request only)       */
   WF_UPDATE_NONE = 0,         /* info: not the separable box kernel                                     */
   WF_UPDATE_ATOMIC = 1,       /* row atomics (also the only form of the full and per-point kernels)     */
-  WF_UPDATE_OWNER = 2         /* owner computes (P1 to P7); tuning: WF_ERR_UNSUPPORTED unless the axes
+  WF_UPDATE_OWNER = 2,        /* owner computes (P1 to P7); tuning: WF_ERR_UNSUPPORTED unless the axes
                                  form runs (a rectilinear box)                                          */
+  WF_UPDATE_ORDERED = 3       /* info only (WF_FLAG_ORDERED operators); wf_tuning.update = 3 stays an error */
 } wf_update_mode;
 
 typedef struct {
@@ -285,7 +312,7 @@ typedef struct {
   const double* h_xverts;       /* [nverts][3]                                    */
   const int32_t* h_geom_dofmap; /* [ncells][4]                                    */
   double c0;
-  int flags;                    /* WF_FLAG_NO_CLAMP                               */
+  int flags;                    /* WF_FLAG_NO_CLAMP; WF_FLAG_ORDERED: WF_ERR_UNSUPPORTED */
 } wf_dense_desc;
 int wf_op_create_dense_simplex(const wf_dense_desc* desc, wf_op** out);
 
@@ -329,7 +356,7 @@ typedef struct {
   double plan_fill;      /* cells / cell slots of the plan's columns                     */
   int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
   int metric;            /* wf_metric_mode of the per-cell box kernel (0: none)          */
-  int update;            /* wf_update_mode of the separable box kernel (0: none)         */
+  int update;            /* wf_update_mode of the separable box kernel (0: none); WF_UPDATE_ORDERED */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
 int wf_op_destroy(wf_op* op);
@@ -341,6 +368,17 @@ int wf_gather(int32_t N, const int32_t* d_indices, const double* d_in, double* d
 int wf_scatter_add(int32_t N, const int32_t* d_indices, const double* d_in, double* d_out, void* stream); /* out[indices[i]] += in[i]  */
 int wf_scatter_set(int32_t N, const int32_t* d_indices, const double* d_in, double* d_out, void* stream); /* out[indices[i]]  = in[i]  (VectorUpdater.hpp:141 unpack) */
 int wf_transform1(int32_t N, const double* d_in, const double* d_detJ, double* d_out, void* stream);      /* out[i] = in[i]*detJ[i]    */
+
+/* The two halves of the order-fixed accumulation as free functions.
+ * wf_ordered_slots (host only): the plan of the order contract, a stable counting sort of the flattened dofmap.  The
+ *   slots of dof d are h_row_off[d] .. h_row_off[d+1]-1; h_slot[c*nd + l] is the slot of entry (c, l), ascending with the
+ *   position of the entry in h_dofmap.  WF_ERR_INVALID for an index outside [0, ndofs), WF_ERR_UNSUPPORTED if ncells*nd
+ *   does not fit int32.
+ * wf_segment_sum_add: y[d] = y[d] + (((vals[row_off[d]] + vals[row_off[d]+1]) + ...) + vals[row_off[d+1]-1]) for
+ *   d < n, one thread per row, no atomics; rows of any length, an empty row leaves y[d] untouched; n = 0 is a no-op. */
+int wf_ordered_slots(int64_t ncells, int nd, int32_t ndofs, const int32_t* h_dofmap, int32_t* h_row_off /*[ndofs+1]*/,
+                     int32_t* h_slot /*[ncells*nd]*/);
+int wf_segment_sum_add(int32_t n, const int32_t* d_row_off, const double* d_vals, double* d_y, void* stream);
 
 /* ---- a12: tall-skinny dense matmul (TSMM) ---------------------------------
  * out[cell][n] = sum_k in[cell][k] * phi[k][n], phi row-major [K][N] on the device.

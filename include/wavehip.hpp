@@ -103,6 +103,17 @@ void scatter(std::int32_t N, const std::int32_t* indices, const T* in, T* out, i
 {
   check(wf_scatter_add(N, indices, in, out, stream));
 }
+/// The plan of the order-fixed accumulation (WF_FLAG_ORDERED): stable counting sort of a flattened dofmap, host only.
+inline void ordered_slots(std::int64_t ncells, int nd, std::int32_t ndofs, const std::int32_t* dofmap, std::int32_t* row_off,
+                          std::int32_t* slot)
+{
+  check(wf_ordered_slots(ncells, nd, ndofs, dofmap, row_off, slot));
+}
+/// y[d] += vals[row_off[d]] + ... + vals[row_off[d+1]-1], summed front to back by one thread per row (no atomics).
+inline void segment_sum_add(std::int32_t n, const std::int32_t* row_off, const double* vals, double* y, void* stream = nullptr)
+{
+  check(wf_segment_sum_add(n, row_off, vals, y, stream));
+}
 template <typename T>
 void transform1(std::int32_t N, const T* in, const T* detJ, T* out, int /*block_size*/ = 512, void* stream = nullptr)
 {

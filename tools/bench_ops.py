@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import wave_fenics_amd as w  # noqa: E402
 from wave_fenics_amd import la  # noqa: E402
+from wave_fenics_amd._lib import WF_FLAG_ORDERED  # noqa: E402
 
 
 def timeit(fn, reps=20, warm=3, settle_s=0.4):
@@ -127,8 +128,11 @@ def main():
             if p >= 5:   # the owner form on request next to the default k-split kernel (OWNER_VARIANTS=1: every cross-section)
                 own = [{"update": "owner", "variant": v} for v in (0, 1, 2)] if "OWNER_VARIANTS" in os.environ else [{"update": "owner"}]
                 cases[1:1] = [(True, t) for t in own]
-            for structured, tuning in cases:
-                op = w.StiffnessOperator(V, p, structured=structured, tuning=tuning)
+            cases = [c + (0,) for c in cases]
+            if p in (4, 6):   # order-fixed accumulation next to the default dofmap operator
+                cases.append((False, None, WF_FLAG_ORDERED))
+            for structured, tuning, flags in cases:
+                op = w.StiffnessOperator(V, p, structured=structured, tuning=tuning, flags=flags)
                 report(f"stiffness P{p} " + ("box" if structured else "any dofmap") + f" [{op.kernel}]", timeit(lambda: op(x, y)),
                        op.alg_bytes(), N, dict(tag, kernel=op.kernel, update=op.update, lz=op.info.plan_lz, tuning=str(tuning)))
                 del op
@@ -154,8 +158,13 @@ def main():
                 op = w.MassOperator(V, p, phi1, detq)
                 alg = mesh.ncells * (8.0 * m ** 3 + 4.0 * (p + 1) ** 3) + 16.0 * N
                 report(f"dense mass P{p} {label} (sum-factorised Phi^T D Phi)", timeit(lambda: op.apply(x, y), reps=10),
-                       alg, N, dict(tag, flops_ref_model=op.flops()))
+                       alg, N, dict(tag, kernel=op.kernel, flops_ref_model=op.flops()))
                 del op
+                if label != "gll-collocated":   # order-fixed accumulation next to the default form
+                    op = w.MassOperator(V, p, phi1, detq, flags=WF_FLAG_ORDERED)
+                    report(f"dense mass P{p} {label} ordered [{op.kernel}]", timeit(lambda: op.apply(x, y), reps=10),
+                           op.alg_bytes(), N, dict(tag, kernel=op.kernel, flops_ref_model=op.flops()))
+                    del op
         if "vector" in only and p == 4:
             z = torch.zeros_like(x)
             report("axpy r=a*x+y", timeit(lambda: la.axpy(z, 0.5, x, y)), 24.0 * N, N)

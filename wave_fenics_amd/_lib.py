@@ -85,11 +85,13 @@ WF_COMM_ID_BYTES = 128
 WF_SUM, WF_MAX = 0, 1
 WF_UPDATER_DEFAULT, WF_UPDATER_INLINE, WF_UPDATER_CHAIN_ON_SIDE = 0, 1, 2
 (WF_KERNEL_NONE, WF_KERNEL_MARCH_BOX, WF_KERNEL_MARCH_IDX, WF_KERNEL_BATCH_UNIQUE, WF_KERNEL_BOX_BLOCK, WF_KERNEL_DIAGONAL,
- WF_KERNEL_MASS_DENSE_ANY, WF_KERNEL_DENSE_SIMPLEX, WF_KERNEL_ELEMENTWISE) = range(9)
+ WF_KERNEL_MASS_DENSE_ANY, WF_KERNEL_DENSE_SIMPLEX, WF_KERNEL_ELEMENTWISE, WF_KERNEL_CELLS_ORDERED) = range(10)
 (WF_KERNEL_AUTO, WF_KERNEL_FORCE_BATCH, WF_KERNEL_FORCE_BOX_BLOCK, WF_KERNEL_FORCE_MASS_ANY, WF_KERNEL_FORCE_ELEMENTWISE,
  WF_KERNEL_FORCE_MARCH) = range(6)
 WF_OP_STIFFNESS, WF_OP_MASS_LUMPED, WF_OP_MASS_DENSE = 0, 1, 2
 WF_FLAG_NONE, WF_FLAG_NO_FABS, WF_FLAG_NO_CLAMP, WF_FLAG_MASS_ELEMENTWISE, WF_FLAG_TENSOR_X_SLOWEST = 0, 1, 2, 4, 8
+WF_FLAG_ORDERED = 16   # order-fixed accumulation: bitwise reproducible y on any mesh (include/wavehip.h)
+WF_UPDATE_NONE, WF_UPDATE_ATOMIC, WF_UPDATE_OWNER, WF_UPDATE_ORDERED = 0, 1, 2, 3   # ORDERED: wf_op_info_t.update only
 WF_PART_ALL, WF_PART_INTERIOR, WF_PART_INTERFACE, WF_PART_INTERIOR_A, WF_PART_INTERIOR_B = 0, 1, 2, 3, 4
 
 # every symbol include/wavehip.h declares: name -> (restype, argtypes)
@@ -129,6 +131,8 @@ SIGNATURES = {
     "wf_scatter_add": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_scatter_set": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_transform1": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wf_ordered_slots": (c_int, [c_int64, c_int, c_int32, _ip, _ip, _ip]),
+    "wf_segment_sum_add": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_tsmm": (c_int, [c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_copy": (c_int, [c_int64, c_void_p, c_void_p, c_void_p]),
     "wf_fill": (c_int, [c_int64, c_double, c_void_p, c_void_p]),

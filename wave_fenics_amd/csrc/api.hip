@@ -27,6 +27,9 @@ enum class OpKernel : int {
   mass_column,           // dense mass, square table, column threads on batch-unique dof lists
   mass_any,              // dense mass, any tensor rule
   dense_simplex,         // dense simplex operator (stiffness_dense.hip)
+  ordered_stiffness,     // WF_FLAG_ORDERED (ordered.hip): cell batches store to v[slot], one thread per y entry sums its run
+  ordered_mass,          // the same for the dense mass, any tensor rule
+  ordered_lumped,        // the same for the lumped mass in the reference's sequence
 };
 
 // what wf_op_create_box_tuned decides about a box operator before it touches device memory (choose_box_stiffness)
@@ -60,6 +63,12 @@ struct wf_op {
   int32_t* d_uniq = nullptr;
   uint16_t* d_loc = nullptr;
   int unique_cb = 0;
+  // order-fixed accumulation (WF_FLAG_ORDERED): slot of every element-local entry (internal cell order, tensor order),
+  // row offsets per dof and the scratch v[ncells * nd] that pass 1 writes and pass 2 reads
+  int ordered = 0;
+  int32_t* d_slot = nullptr;
+  int32_t* d_row_off = nullptr;
+  double* d_v = nullptr;
   // work-item lists of the marching kernel: [0] interior, [1] interface, [2]/[3] the two halves of the interior
   int32_t* d_items[4] = {nullptr, nullptr, nullptr, nullptr};
   int nitems[4] = {0, 0, 0, 0};
@@ -118,6 +127,9 @@ void free_op(wf_op* op)
   (void)hipFree(op->d_uoff);
   (void)hipFree(op->d_uniq);
   (void)hipFree(op->d_loc);
+  (void)hipFree(op->d_slot);
+  (void)hipFree(op->d_row_off);
+  (void)hipFree(op->d_v);
   for (int k = 0; k < 4; ++k) (void)hipFree(op->d_items[k]);
   (void)hipFree(op->plan.d_item_base);
   (void)hipFree(op->plan.d_item_pattern);
@@ -844,15 +856,44 @@ struct BatchInputs {
   const double* h_detJ = nullptr;
 };
 
+// Order-fixed accumulation: the plan of the order contract (wf_ordered_slots on the CALLER's dofmap, so neither the
+// internal cell order nor the tensor permutation enters the summation order), the slot table carried into the internal
+// cell order and the engine's tensor order, and the scratch v.
+int build_ordered_plan(const wf_op_desc* desc, const CallerFrame& fr, const std::vector<int32_t>& cperm, wf_op* op)
+{
+  const int nd = op->nd;
+  const size_t ncells = (size_t)desc->ncells;
+  std::vector<int32_t> row_off((size_t)desc->ndofs + 1), slot(ncells * nd), tslot(ncells * nd);
+  int rc;
+  if ((rc = wf_ordered_slots((int64_t)ncells, nd, desc->ndofs, desc->h_dofmap, row_off.data(), slot.data())) != WF_OK) return rc;
+  const int32_t* perm = fr.perm();
+  for (size_t c = 0; c < ncells; ++c)
+    for (int l = 0; l < nd; ++l) tslot[c * nd + l] = slot[(size_t)cperm[c] * nd + (perm ? perm[l] : l)];
+  if ((rc = dev_upload(&op->d_slot, tslot.data(), tslot.size(), &op->device_bytes)) != WF_OK) return rc;
+  if ((rc = dev_upload(&op->d_row_off, row_off.data(), row_off.size(), &op->device_bytes)) != WF_OK) return rc;
+  return dev_alloc(&op->d_v, ncells * nd, &op->device_bytes);
+}
+
+void free_ordered_plan(wf_op* op)
+{
+  const size_t entries = (size_t)op->ncells * op->nd;
+  op->device_bytes -= entries * (sizeof(int32_t) + sizeof(double)) + ((size_t)op->ndofs + 1) * sizeof(int32_t);
+  (void)hipFree(op->d_slot);
+  (void)hipFree(op->d_row_off);
+  (void)hipFree(op->d_v);
+  op->d_slot = op->d_row_off = nullptr;
+  op->d_v = nullptr;
+}
+
 int batch_stiffness(const wf_op_desc* desc, const CallerFrame& fr, const BatchInputs& in, bool no_unique, wf_op* op)
 {
   const int P = op->P, n = op->n, nd = op->nd, CB = cells_per_batch(P);
   const size_t ncells = (size_t)desc->ncells, nbatch = (ncells + CB - 1) / CB;
   int rc;
   // batch-unique dof lists (WF_KERNEL_FORCE_ELEMENTWISE keeps the element-wise scatter for comparison)
-  const bool unique = !no_unique && ncells > 0;
+  const bool unique = !no_unique && ncells > 0 && !op->ordered;
   if (unique && (rc = build_unique_lists(op, ncells, nd, CB)) != WF_OK) return rc;
-  op->kernel = unique ? OpKernel::generic_unique : OpKernel::generic_elementwise;
+  op->kernel = op->ordered ? OpKernel::ordered_stiffness : unique ? OpKernel::generic_unique : OpKernel::generic_elementwise;
   const size_t g6 = nbatch * CB * nd * 6;
   if ((rc = dev_alloc(&op->d_G6blk, g6, &op->device_bytes)) != WF_OK) return rc;
   if (g6) WF_HIP_CHECK(hipMemset(op->d_G6blk, 0, g6 * sizeof(double)));
@@ -895,7 +936,7 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
   op->nq1 = nq1;
   op->nq = nq1 * nq1 * nq1;
   // square tables (nq1 == P+1): column-thread kernel, batches of cells_per_batch(P)
-  const bool square = dense && nq1 == n && tun.kernel != WF_KERNEL_FORCE_MASS_ANY;
+  const bool square = dense && nq1 == n && tun.kernel != WF_KERNEL_FORCE_MASS_ANY && !op->ordered;
   const int CBm = (dense && !square) ? mass_dense_cells_per_batch(std::max(n, nq1)) : cells_per_batch(P);
   // dense mass: the unique-dof tile pays off only for small elements (measured at 10 M dofs:
   // P2 0.80 -> 0.68 ms, P4 0.43 -> 0.46 ms, P6 0.34 -> 0.41 ms)
@@ -903,7 +944,7 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
   // reference's element-wise sequence
   const bool elementwise = !dense && (desc->flags & WF_FLAG_MASS_ELEMENTWISE);
   const bool want = elementwise || (dense && (P <= 3 || square));
-  const bool unique = want && !no_unique && ncells > 0;
+  const bool unique = want && !no_unique && ncells > 0 && !op->ordered;
   if (unique && (rc = build_unique_lists(op, ncells, nd, CBm)) != WF_OK) return rc;
 
   if (desc->h_detJ) {
@@ -921,11 +962,11 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
     return WF_ERR_INVALID;
   }
   if (dense) {
-    op->kernel = square && unique ? OpKernel::mass_column : OpKernel::mass_any;
+    op->kernel = op->ordered ? OpKernel::ordered_mass : square && unique ? OpKernel::mass_column : OpKernel::mass_any;
     return WF_OK;
   }
   if (elementwise) {
-    op->kernel = unique ? OpKernel::lumped_unique : OpKernel::lumped_elementwise;
+    op->kernel = op->ordered ? OpKernel::ordered_lumped : unique ? OpKernel::lumped_unique : OpKernel::lumped_elementwise;
     return WF_OK;
   }
   // A lumped mass is a diagonal: assemble m = M 1 once with the reference's own
@@ -937,10 +978,17 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
   if (op->ndofs) {
     if ((rc = wf_fill(op->ndofs, 1.0, d_ones.p, nullptr)) != WF_OK) return rc;
     WF_HIP_CHECK(hipMemset(op->d_mdiag, 0, (size_t)op->ndofs * sizeof(double)));
-    if (ncells && (rc = launch_mass_lumped((int64_t)ncells * nd, op->d_dofmap, op->d_detJ, d_ones.p, op->d_mdiag, nullptr)) != WF_OK)
+    // WF_FLAG_ORDERED: the same sequence through the two ordered passes, so that m is bitwise reproducible
+    if (ncells && op->ordered) {
+      if ((rc = launch_mass_lumped_ordered((int64_t)ncells * nd, op->d_dofmap, op->d_slot, op->d_detJ, d_ones.p, op->d_v, nullptr)) != WF_OK)
+        return rc;
+      if ((rc = wf_segment_sum_add(op->ndofs, op->d_row_off, op->d_v, op->d_mdiag, nullptr)) != WF_OK) return rc;
+    } else if (ncells && (rc = launch_mass_lumped((int64_t)ncells * nd, op->d_dofmap, op->d_detJ, d_ones.p, op->d_mdiag, nullptr)) != WF_OK) {
       return rc;
+    }
     WF_HIP_CHECK(hipDeviceSynchronize());
   }
+  if (op->ordered) free_ordered_plan(op);
   op->device_bytes -= ncells * nd * sizeof(double);
   (void)hipFree(op->d_detJ);
   op->d_detJ = nullptr;
@@ -988,6 +1036,7 @@ int create_batch(const wf_op_desc* desc, const CallerFrame& fr, const int32_t* t
     if ((rc = dev_upload(&op->d_dofmap, src, ncells * nd, &op->device_bytes)) != WF_OK) return rc;
   }
   if ((rc = upload_derivative_tables(op, false)) != WF_OK) return rc;
+  if (op->ordered && (rc = build_ordered_plan(desc, fr, in.cperm, op)) != WF_OK) return rc;
   rc = desc->kind == WF_OP_STIFFNESS ? batch_stiffness(desc, fr, in, no_unique, op) : batch_mass(desc, in, no_unique, op);
   if (rc != WF_OK) return rc;
   WF_HIP_CHECK(hipDeviceSynchronize());
@@ -1034,6 +1083,15 @@ int wf_op_create(const wf_op_desc* desc, wf_op** out)
   const CallerFrame fr(desc, n);
   OpPtr op = new_op(desc->kind, P, nd, nd, desc->ncells, desc->ndofs, desc->c0, desc->tuning);
   const wf_tuning& tun = op->tun;
+  // order-fixed accumulation: one form per operator kind, always on the cell batches -- there is no kernel to choose
+  op->ordered = (desc->flags & WF_FLAG_ORDERED) != 0;
+  if (op->ordered) {
+    wf_tuning rest = tun;
+    rest.keep_cell_order = 0;
+    const wf_tuning none{};
+    WF_REQUIRE(std::memcmp(&rest, &none, sizeof(wf_tuning)) == 0,
+               "wf_op_create: WF_FLAG_ORDERED takes no wf_tuning field other than keep_cell_order");
+  }
 
   // the lattice-column plan serves the stiffness operator and the dense mass with a square 1-D table
   const bool plan_stiffness = desc->kind == WF_OP_STIFFNESS;
@@ -1043,13 +1101,13 @@ int wf_op_create(const wf_op_desc* desc, wf_op** out)
                            || tun.kernel == WF_KERNEL_FORCE_MASS_ANY;
   int rc;
   // a collocated dense mass is a diagonal; a wf_tuning kernel hint keeps the dense kernels
-  if (plan_mass && tun.kernel == WF_KERNEL_AUTO && ncells > 0 && mass_collocated(desc, n)) {
+  if (plan_mass && tun.kernel == WF_KERNEL_AUTO && ncells > 0 && !op->ordered && mass_collocated(desc, n)) {
     rc = create_mass_diagonal(desc, fr, op.get());
   } else {
     std::vector<int32_t> tdm_store;
     const int32_t* tdm = nullptr;
     rc = tensor_dofmap(desc, fr, nd, tdm_store, &tdm);
-    if (rc == WF_OK && (plan_stiffness || plan_mass) && !force_batch && ncells > 0) {
+    if (rc == WF_OK && (plan_stiffness || plan_mass) && !force_batch && !op->ordered && ncells > 0) {
       if (plan_stiffness)
         WF_REQUIRE(desc->h_G || have_mesh, "wf_op_create: stiffness needs h_G or the mesh (h_xverts, h_geom_dofmap)");
       rc = create_on_plan(desc, fr, tdm, plan_mass, op.get());
@@ -1209,6 +1267,48 @@ int upload_box_cell_geometry(wf_op* op, const std::vector<double>& h_Gc)
   return dev_upload(&op->d_Gcell, blk.data(), blk.size(), &op->device_bytes);
 }
 
+// WF_FLAG_ORDERED on a box: the box's lexicographic dofmap (dof (I, J, K) -> I + NX (J + NY K), tensor order) and vertex
+// map (vertex (a, b, c) -> a + (nx+1)(b + (ny+1) c)) built on the host, then the dofmap operator of wf_op_create -- a box
+// operator with the flag IS that dofmap operator, bit for bit.
+int create_box_ordered(int kind, int P, int nx, int ny, int nz, const double* h_xverts, double c0, int flags,
+                       const wf_tuning* tuning, wf_op** out)
+{
+  const int n = P + 1, nd = n * n * n;
+  const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
+  const size_t ncells = (size_t)nx * ny * nz;
+  std::vector<int32_t> dm(ncells * nd), gd(ncells * 8);
+  for (int cz = 0; cz < nz; ++cz)
+    for (int cy = 0; cy < ny; ++cy)
+      for (int cx = 0; cx < nx; ++cx) {
+        const size_t c = (size_t)cx + (size_t)nx * (cy + (size_t)ny * cz);
+        const size_t base = (size_t)P * cx + NX * ((size_t)P * cy + NY * ((size_t)P * cz));
+        for (int k = 0; k < n; ++k)
+          for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) dm[c * nd + i + n * (j + n * k)] = (int32_t)(base + i + NX * (j + NY * k));
+        for (int v = 0; v < 8; ++v)
+          gd[c * 8 + v] = (int32_t)((cx + (v & 1)) + (size_t)(nx + 1) * ((cy + ((v >> 1) & 1)) + (size_t)(ny + 1) * (cz + ((v >> 2) & 1))));
+      }
+  wf_op_desc d{};
+  d.kind = kind;
+  d.degree = P;
+  d.ncells = (int)ncells;
+  d.ndofs = (int)(NX * NY * NZ);
+  d.h_dofmap = dm.data();
+  d.nverts = (nx + 1) * (ny + 1) * (nz + 1);
+  d.h_xverts = h_xverts;
+  d.h_geom_dofmap = gd.data();
+  d.c0 = c0;
+  d.flags = flags;
+  d.tuning = tuning;
+  int rc = wf_op_create(&d, out);
+  if (rc != WF_OK) return rc;
+  (*out)->structured = 1;
+  (*out)->nx = nx;
+  (*out)->ny = ny;
+  (*out)->nz = nz;
+  return WF_OK;
+}
+
 // uploads the interior / interface work-item lists (and the two interior halves)
 int set_item_lists(wf_op* op, std::vector<int32_t> (&items)[4])
 {
@@ -1271,6 +1371,7 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
   WF_REQUIRE(NX * NY * NZ < ((size_t)1 << 31), "wf_op_create_box: dof lattice exceeds int32");
   const int n = P + 1, nd = n * n * n;
+  if (flags & WF_FLAG_ORDERED) return create_box_ordered(kind, P, nx, ny, nz, h_xverts, c0, flags, tuning, out);
 
   OpPtr op = new_op(kind, P, nd, nd, nx * ny * nz, (int)(NX * NY * NZ), c0, tuning);
   op->nq1 = n;
@@ -1322,6 +1423,11 @@ int wf_op_create_dense_simplex(const wf_dense_desc* desc, wf_op** out)
   WF_REQUIRE(desc && out, "wf_op_create_dense_simplex: null argument");
   *out = nullptr;
   WF_REQUIRE(desc->nd > 0 && desc->nq > 0 && desc->ncells >= 0 && desc->ndofs >= 0, "wf_op_create_dense_simplex: bad sizes");
+  if (desc->flags & WF_FLAG_ORDERED) {
+    set_error("wf_op_create_dense_simplex: WF_FLAG_ORDERED is not implemented for the dense simplex operator (its "
+              "persistent MFMA kernel adds with atomics)");
+    return WF_ERR_UNSUPPORTED;
+  }
   WF_REQUIRE(desc->h_dofmap && desc->h_dphi && desc->h_weights && desc->h_xverts && desc->h_geom_dofmap,
              "wf_op_create_dense_simplex: null array");
   for (size_t e = 0; e < (size_t)desc->ncells * desc->nd; ++e)
@@ -1377,6 +1483,18 @@ static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitem
       return launch_mass_dense(op->P, op->nq1, op->ncells, op->d_dofmap, op->d_uoff, op->d_uniq, op->d_loc, op->unique_cb,
                                op->d_phi1, op->d_detJ, d_x, d_y, s);
     case OpKernel::dense_simplex: return launch_stiffness_dense(op->dense, op->coeff, op->dense_clamp, d_x, d_y, s);
+    case OpKernel::ordered_stiffness:
+    case OpKernel::ordered_mass:
+    case OpKernel::ordered_lumped: {
+      // pass 1 into the operator's scratch v, pass 2 behind it on the same stream
+      int rc = op->kernel == OpKernel::ordered_stiffness
+                   ? launch_stiffness_ordered(op->P, op->ncells, op->d_dofmap, op->d_slot, op->d_G6blk, op->d_D, op->dm, op->coeff, d_x, op->d_v, s)
+               : op->kernel == OpKernel::ordered_mass
+                   ? launch_mass_dense_ordered(op->P, op->nq1, op->ncells, op->d_dofmap, op->d_slot, op->d_phi1, op->d_detJ, d_x, op->d_v, s)
+                   : launch_mass_lumped_ordered((int64_t)op->ncells * op->nd, op->d_dofmap, op->d_slot, op->d_detJ, d_x, op->d_v, s);
+      if (rc != WF_OK || op->ncells == 0) return rc;
+      return wf_segment_sum_add(op->ndofs, op->d_row_off, op->d_v, d_y, s);
+    }
     case OpKernel::none: break;
   }
   set_error("wf_op_apply: corrupt handle");
@@ -1512,6 +1630,9 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
     case OpKernel::mass_column: kernel = WF_KERNEL_BATCH_UNIQUE; break;
     case OpKernel::mass_any: kernel = WF_KERNEL_MASS_DENSE_ANY; break;
     case OpKernel::dense_simplex: kernel = WF_KERNEL_DENSE_SIMPLEX, geometry = WF_GEOMETRY_PER_CELL; break;
+    case OpKernel::ordered_stiffness: kernel = WF_KERNEL_CELLS_ORDERED, geometry = WF_GEOMETRY_PER_POINT, update = WF_UPDATE_ORDERED; break;
+    case OpKernel::ordered_mass:
+    case OpKernel::ordered_lumped: kernel = WF_KERNEL_CELLS_ORDERED, update = WF_UPDATE_ORDERED; break;
     case OpKernel::none: break;
   }
   const bool dense = op->kernel == OpKernel::dense_simplex;
@@ -1532,6 +1653,8 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
     info->alg_bytes = 24.0 * op->ndofs;   // pre-assembled diagonal: read m, x, y + write y (SURVEY 8d counts 24)
   else
     info->alg_bytes = (double)op->ncells * (8.0 * op->nq + 4.0 * op->nd) + 16.0 * op->ndofs;
+  // order-fixed accumulation: per element-local entry the slot (4), the store and the load of v (8 + 8); the row offsets
+  if (kernel == WF_KERNEL_CELLS_ORDERED) info->alg_bytes += 20.0 * op->ncells * op->nd + 4.0 * (op->ndofs + 1.0);
   info->device_bytes = op->device_bytes;
   info->items_interior = op->nitems[0];
   info->items_interface = op->nitems[1];

@@ -224,5 +224,14 @@ int launch_mass_dense_col(int P, int ncells, const int32_t* d_uoff, const int32_
 int launch_mass_dense(int P, int nq1, int ncells, const int32_t* d_dofmap, const int32_t* d_uoff,
                       const int32_t* d_uniq, const uint16_t* d_loc, int CBu, const double* d_phi1,
                       const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
+// order-fixed accumulation (ordered.hip): pass 1 of the cell-batch kernels, v[slot[c][l]] = element-local value; pass 2
+// is wf_segment_sum_add.  ordered_slots: the stable counting sort of a flattened dofmap (wf_ordered_slots).
+int ordered_slots(int64_t nentries, int32_t ndofs, const int32_t* dofmap, int32_t* row_off, int32_t* slot);
+int launch_stiffness_ordered(int P, int ncells, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_G6blk,
+                             const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_v, hipStream_t s);
+int launch_mass_dense_ordered(int P, int nq1, int ncells, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_phi1,
+                              const double* d_detJ, const double* d_x, double* d_v, hipStream_t s);
+int launch_mass_lumped_ordered(int64_t nentries, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_detJ,
+                               const double* d_x, double* d_v, hipStream_t s);
 
 }  // namespace wf

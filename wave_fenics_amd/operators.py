@@ -168,7 +168,7 @@ GEOMETRY_MODES = {"auto": 0, "per_point": 1, "per_cell": 2}
 METRIC_MODES = {"auto": 0, "full": 1, "axes": 2}
 UPDATE_MODES = {"auto": 0, "atomic": 1, "owner": 2}
 KERNEL_NAMES = {0: "none", 1: "march_box", 2: "march_idx", 3: "batch_unique", 4: "box_block", 5: "diagonal",
-                6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise"}
+                6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise", 9: "cells_ordered"}
 
 
 class _Operator:
@@ -212,8 +212,9 @@ class _Operator:
     @property
     def update(self) -> str:
         """How the separable box kernel adds into y (wf_op_info_t.update): "atomic", "owner" or "none" (another
-        kernel)."""
-        return {1: "atomic", 2: "owner"}.get(self.info.update, "none")
+        kernel); "ordered" for an operator created with WF_FLAG_ORDERED (order-fixed accumulation: every y entry summed
+        by one thread in the order of the caller's dofmap, bitwise reproducible on any mesh)."""
+        return {1: "atomic", 2: "owner", 3: "ordered"}.get(self.info.update, "none")
 
     def _info(self):
         info = OpInfo()
@@ -361,7 +362,7 @@ class MassOperatorLumped(_Operator):
         if structured is None:
             structured = bool(getattr(V, "structured", False)) and detJ is None and perm is None
         if structured:
-            self._create_box(_lib.WF_OP_MASS_LUMPED, bdegree, V.mesh, 0.0, flags)
+            self._create_box(_lib.WF_OP_MASS_LUMPED, bdegree, V.mesh, 0.0, flags, tuning if flags & _lib.WF_FLAG_ORDERED else None)
             return
         d, keep = _base_desc(V, _lib.WF_OP_MASS_LUMPED, bdegree, perm)
         d.flags = flags
@@ -398,9 +399,11 @@ class MassOperator(_Operator):
     explicit tables: `phi1` [nq1][P+1] and `detJ` [ncells][nq1^3] (mass.hpp:35-39)."""
 
     def __init__(self, V: FunctionSpace, degree: int, phi1: np.ndarray | None = None, detJ: np.ndarray | None = None,
-                 perm=None, variant: str = "gll_warped", quad: str = "gll", qdegree: int | None = None, tuning=None):
+                 perm=None, variant: str = "gll_warped", quad: str = "gll", qdegree: int | None = None, tuning=None,
+                 flags: int = 0):
         super().__init__()
         d, keep = _base_desc(V, _lib.WF_OP_MASS_DENSE, degree, perm)
+        d.flags = flags
         if phi1 is None:
             if qdegree is None:
                 qdegree = degree + 1 if degree > 1 else degree      # gpu_operator_monolithic/main.cpp:95
@@ -445,6 +448,25 @@ def scatter(N: int, indices, inp, out, block_size: int = 512, stream: int | None
 
 def scatter_set(N: int, indices, inp, out, stream: int | None = None):
     check(lib().wf_scatter_set(N, _ptr(indices), _ptr(inp), _ptr(out), _stream(inp) if stream is None else stream))
+
+
+def ordered_slots(dofmap, ndofs: int):
+    """The plan of the order-fixed accumulation (wf_ordered_slots, host only): a stable counting sort of the flattened
+    dofmap [ncells][nd].  Returns (row_off[ndofs + 1], slot[ncells][nd]): the contributions of dof d occupy the slots
+    row_off[d] .. row_off[d+1]-1 in the order in which the dofmap lists d."""
+    dm = np.ascontiguousarray(dofmap, dtype=np.int32)
+    if dm.ndim != 2:
+        raise _lib.WavehipError("ordered_slots: dofmap must be [ncells][nd]")
+    row_off = np.zeros(int(ndofs) + 1, dtype=np.int32)
+    slot = np.zeros(dm.shape, dtype=np.int32)
+    check(lib().wf_ordered_slots(dm.shape[0], dm.shape[1], int(ndofs), _ip(dm), _ip(row_off), _ip(slot)))
+    return row_off, slot
+
+
+def segment_sum_add(n: int, row_off, vals, y, stream: int | None = None):
+    """y[d] += vals[row_off[d]] + vals[row_off[d]+1] + ... (summed front to back by one thread, no atomics) for d < n
+    (wf_segment_sum_add): pass 2 of the order-fixed accumulation.  row_off: int32 device tensor [n + 1]."""
+    check(lib().wf_segment_sum_add(int(n), _ptr(row_off), _ptr(vals), _ptr(y), _stream(y) if stream is None else stream))
 
 
 def transform1(N: int, inp, detJ, out, block_size: int = 512, stream: int | None = None):
