@@ -12,9 +12,13 @@
 //
 // --update auto|atomic|owner (--op stiffness) asks wf_op_create_box_tuned for that form of the separable box kernel
 // (wf_tuning.update): owner = every y entry read and written once by its owning thread, on a rectilinear box at P1 to P7.
+// --kernel auto|march (--op dense) asks for the lattice-column marching kernel also when the rule's table is rectangular
+// (wf_tuning.kernel = WF_KERNEL_FORCE_MASS_MARCH; the default rule of P4 to P7 is); the "Kernel id:" line is the
+// wf_kernel_id the operator runs.
 //
 //   operator_demo [--size N] [--degree P] [--op stiffness|mass|spectral|dense] [--reps R]
-//                 [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--update auto|atomic|owner] [--check]
+//                 [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--update auto|atomic|owner]
+//                 [--kernel auto|march] [--check]
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -30,7 +34,7 @@ int main(int argc, char* argv[])
 {
   int Nx = 32, degree = 1, reps = 20, qdegree = -1;
   bool check = false;
-  std::string opname = "stiffness", variant = "gll", quad = "gll", update = "auto";
+  std::string opname = "stiffness", variant = "gll", quad = "gll", update = "auto", kernel = "auto";
   for (int i = 1; i < argc; ++i) {
     auto is = [&](const char* f) { return std::strcmp(argv[i], f) == 0 && i + 1 < argc; };
     if (is("--size")) Nx = std::atoi(argv[++i]);
@@ -41,15 +45,21 @@ int main(int argc, char* argv[])
     else if (is("--quad")) quad = argv[++i];
     else if (is("--qdegree")) qdegree = std::atoi(argv[++i]);
     else if (is("--update")) update = argv[++i];
+    else if (is("--kernel")) kernel = argv[++i];
     else if (std::strcmp(argv[i], "--check") == 0) check = true;
     else {
       std::cerr << "usage: operator_demo [--size N] [--degree P] [--op stiffness|mass|spectral|dense] [--reps R]"
-                   " [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--update auto|atomic|owner] [--check]\n";
+                   " [--variant gll|equispaced] [--quad gll|gauss] [--qdegree Q] [--update auto|atomic|owner]"
+                   " [--kernel auto|march] [--check]\n";
       return 2;
     }
   }
   if (update != "auto" && update != "atomic" && update != "owner") {
     std::cerr << "--update must be auto, atomic or owner\n";
+    return 2;
+  }
+  if (kernel != "auto" && kernel != "march") {
+    std::cerr << "--kernel must be auto or march\n";
     return 2;
   }
   try {
@@ -67,9 +77,11 @@ int main(int argc, char* argv[])
       // MassOperator<double> op(V, e, quad, qdegree)  (gpu_operator_monolithic/main.cpp:93-96)
       if (qdegree < 0) qdegree = (degree > 1) ? degree + 1 : degree;
       auto S = V.space();
+      wf_tuning tuning{};
+      tuning.kernel = kernel == "march" ? WF_KERNEL_FORCE_MASS_MARCH : WF_KERNEL_AUTO;
       dense = std::make_unique<wavehip::MassOperator<double>>(
           S, degree, variant == "equispaced" ? WF_VARIANT_EQUISPACED : WF_VARIANT_GLL_WARPED,
-          quad == "gauss" ? WF_QUAD_GAUSS_JACOBI : WF_QUAD_GLL, qdegree);
+          quad == "gauss" ? WF_QUAD_GAUSS_JACOBI : WF_QUAD_GLL, qdegree, &tuning);
       op = dense->handle();
     } else {
       const int kind = opname == "stiffness" ? WF_OP_STIFFNESS : WF_OP_MASS_LUMPED;
@@ -136,6 +148,7 @@ int main(int argc, char* argv[])
       std::cout << "\nKernel: " << (info.kernel == WF_KERNEL_MARCH_BOX ? "march_box" : "other") << "  geometry: " << kGeometry[info.geometry]
                 << "  metric: " << kMetric[info.metric] << "  update: " << kUpdate[info.update];
     }
+    if (opname == "dense") std::cout << "\nKernel id: " << info.kernel;
     std::cout << "\n#Elapsed Time: " << t;
     std::cout << "\nDOF/s: " << N / t;
     std::cout << "\nDOF/s (warm, " << reps << " reps): " << N / tw;

@@ -194,9 +194,25 @@ typedef enum {
   WF_KERNEL_FORCE_BOX_BLOCK = 2,  /* box stiffness: the single-pass block kernel instead of marching        */
   WF_KERNEL_FORCE_MASS_ANY = 3,   /* dense mass: the any-rule kernel even for square tables                 */
   WF_KERNEL_FORCE_ELEMENTWISE = 4,/* batch kernels without the unique-dof tile (element-wise atomics)       */
-  WF_KERNEL_FORCE_MARCH = 5       /* adopt the lattice-column plan whatever its fill (default: plans whose
+  WF_KERNEL_FORCE_MARCH = 5,      /* adopt the lattice-column plan whatever its fill (default: plans whose
                                      columns are mostly empty keep the batch kernel)                        */
+  WF_KERNEL_FORCE_MASS_MARCH = 6  /* dense mass with a rectangular table (nq1 != P+1): the marching kernel
+                                     k_mass_march instead of k_mass_dense -- see below                      */
 } wf_kernel_hint;
+/* WF_KERNEL_FORCE_MASS_MARCH.  A dense mass whose 1-D table is rectangular runs k_mass_dense (WF_KERNEL_MASS_DENSE_ANY)
+ * under every other hint; the marching kernel takes it on request only.  WF_OP_MASS_DENSE with nq1 != P+1 and a
+ * compiled pair (P, nq1): the lattice-column plan is built as for WF_KERNEL_FORCE_MARCH -- adopted whatever its fill,
+ * wf_tuning.lz, bx / by (a compiled cross-section of the pair, else its default) and orient honoured; cell
+ * orientations are normalised only when the table reads the same backwards, phi1[nq1-1-q][P-a] == phi1[q][a].
+ * wf_op_info_t then reports kernel = WF_KERNEL_MARCH_IDX, the plan_* fields, num_quads = nq1^3, and flops and
+ * alg_bytes by the formulas of every dense mass.  Compiled pairs (P, nq1): Gauss rules of degree 2P+2, (1,3) (2,4)
+ * (3,5) (4,6) (5,7) (6,8); the GLL rule of degree P+1 where it is not square, (4,4) (5,5) (6,5) (7,6).  Cross-sections
+ * other than the default: 2x2 at (4,6) and (4,4), 2x1 at (6,8) and (6,5).  A cell must fit one wavefront
+ * (max(P+1, nq1) <= 8).  With nq1 == P+1 the hint is WF_KERNEL_FORCE_MARCH.
+ * Errors: a stiffness or lumped-mass operator with the hint is WF_ERR_INVALID; a pair that is not compiled, or a mesh
+ * that does not tile into lattice columns, is WF_ERR_UNSUPPORTED (wf_last_error names (P, nq1)); together with
+ * WF_FLAG_ORDERED it is WF_ERR_INVALID like every other hint.  wf_op_set_ghost_dofs stays WF_ERR_UNSUPPORTED for
+ * mass operators. */
 typedef struct {
   int kernel;        /* wf_kernel_hint                                                              */
   int variant;       /* box marching kernel: compiled column cross-section + 1 (0 = default); with

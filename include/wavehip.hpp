@@ -226,23 +226,25 @@ private:
 };
 
 /// MassOperator(V, element, quad_type, qd) -- common/cuda/mass.hpp:18-107.
-/// phi1: 1-D interpolation matrix [nq1][degree+1]; detJ: [ncells][nq1^3] (host).
+/// phi1: 1-D interpolation matrix [nq1][degree+1]; detJ: [ncells][nq1^3] (host).  tuning: the kernel selection of
+/// wf_tuning (read during construction only), e.g. kernel = WF_KERNEL_FORCE_MASS_MARCH for a rectangular table.
 template <typename T>
 class MassOperator : public detail::OpBase {
 public:
-  MassOperator(const Space& V, int degree, int nq1, const double* phi1, const double* detJ)
+  MassOperator(const Space& V, int degree, int nq1, const double* phi1, const double* detJ, const wf_tuning* tuning = nullptr)
   {
     wf_op_desc d = base_desc(V, WF_OP_MASS_DENSE, degree);
     d.nq1 = nq1;
     d.h_phi1 = phi1;
     d.h_detJ = detJ;
+    d.tuning = tuning;
     check(wf_op_create(&d, &_op));
   }
   /// The reference's argument list (mass.hpp:20-21): element = degree + Lagrange variant
   /// (WF_VARIANT_GLL_WARPED / WF_VARIANT_EQUISPACED), quad_type (WF_QUAD_GLL /
   /// WF_QUAD_GAUSS_JACOBI) and quadrature degree qd.  Builds the 1-D table (tabulate_1d,
   /// precompute.hpp:179-189) on the host and det J * w at the rule's points on the device.
-  MassOperator(const Space& V, int degree, int variant, int quad_type, int qd)
+  MassOperator(const Space& V, int degree, int variant, int quad_type, int qd, const wf_tuning* tuning = nullptr)
   {
     int nq1 = 0;
     double pts[WF_MAX_QUAD_POINTS], wts[WF_MAX_QUAD_POINTS];
@@ -255,6 +257,7 @@ public:
     d.h_qpts1 = pts;
     d.h_qwts1 = wts;
     d.flags |= WF_FLAG_NO_FABS;   // mass.hpp:35-39: det J * w keeps its sign (compute_jacobian_determinant)
+    d.tuning = tuning;
     check(wf_op_create(&d, &_op));
   }
 };

@@ -1,0 +1,244 @@
+"""The dense mass Phi^T diag(det J w) Phi with a RECTANGULAR 1-D table phi1[M][P+1], M != P+1, on the
+lattice-column marching kernel k_mass_march<P, M, BX, BY> (mass_march.hip), which runs such a table on
+request: wf_tuning.kernel = WF_KERNEL_FORCE_MASS_MARCH, {"kernel": "mass_march"}.
+
+Every parity case runs both constructors (the rule; explicit phi1 / detJ), starts from a non-zero y0 of
+the scale of M x, applies twice (y0 + M x, y0 + 2 M x) and compares with oracle.dense_mass_apply at
+TOL = 1e-12 relative to max|M x| -- the bound of the other dense-mass tests (fp64, summation order).  It
+asserts the kernel ("march_idx"), num_quads = M^3 and the plan fields.
+
+  * all ten compiled pairs (P, M) on a box with partly filled cross-sections and three layers;
+  * one, two and five layers, whole and cut into z segments; the alternative cross-sections;
+  * re-oriented meshes, a table that does not read the same backwards (no cell may be re-oriented), an
+    element-ordered dofmap with `perm`, a square table under the new hint;
+  * the errors: other operators, pairs that are not compiled, the hint with WF_FLAG_ORDERED;
+  * the C++ host path, examples/operator_demo --op dense --kernel march."""
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from test_gpu_dense_mass_rules import MESH, ORACLE_VARIANT, ROOT, TOL, apply, dev, make, npts, relerr, tables
+from test_gpu_unstructured import build_mesh, oracle_mesh
+
+pytestmark = pytest.mark.gpu
+
+HINT = {"kernel": "mass_march"}
+GAUSS = [(p, "gauss_jacobi", 2 * p + 2) for p in range(1, 7)]     # M = P + 2
+GLL = [(p, "gll", p + 1) for p in range(4, 8)]                    # M = 4, 5, 5, 6 at P4..P7
+COMPILED = {(1, 3), (2, 4), (3, 5), (4, 6), (5, 7), (6, 8), (4, 4), (5, 5), (6, 5), (7, 6)}
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import wave_fenics_amd as w
+    w.lib()
+    torch.cuda.set_device(0)
+    return torch.device("cuda", 0)
+
+
+def check_march(op, y0, x, mx, gpu, m, what):
+    """kernel, sizes, plan and two applies onto y0: y0 + M x, then y0 + 2 M x."""
+    assert op.kernel == "march_idx", (what, op.kernel)
+    assert op.num_quads() == m ** 3, (what, op.num_quads())
+    assert op.info.plan_items > 0 and 0.0 < op.info.plan_fill <= 1.0, (what, op.info.plan_items, op.info.plan_fill)
+    y, xd = dev(y0, gpu), dev(x, gpu)
+    op.apply(xd, y)
+    err = relerr(y.cpu().numpy() - y0, mx)
+    print(what, "first apply", err)
+    assert err <= TOL, (what, "first apply", err)
+    op.apply(xd, y)
+    err = relerr(y.cpu().numpy() - y0, 2 * mx)
+    print(what, "second apply", err)
+    assert err <= TOL, (what, "second apply", err)
+
+
+def reference(oracle, om, phi, detJ, seed):
+    """x, M x from the oracle and a y0 of the same scale (an error in M x cannot hide)."""
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1, 1, om.ndofs)
+    mx = np.zeros(om.ndofs)
+    oracle.dense_mass_apply(om, phi, detJ, x, mx)
+    return x, mx, rng.uniform(-1, 1, om.ndofs) * np.abs(mx).max()
+
+
+def run_march(gpu, oracle, om, V, p, variant, quad, qd, seed=0, tuning=None, perm=None):
+    """Both constructors with the hint against the oracle; returns (M x, x, op built from the rule)."""
+    import wave_fenics_amd as w
+    pts, wts, phi1, phi, detJ = tables(oracle, om, p, variant, quad, qd)
+    m = phi1.shape[0]
+    x, mx, y0 = reference(oracle, om, phi, detJ, seed)
+    tun = dict(HINT, **(tuning or {}))
+    what = (p, variant, quad, qd, m, tuning)
+    op_rule = w.MassOperator(V, p, variant=variant, quad=quad, qdegree=qd, perm=perm, tuning=tun)
+    check_march(op_rule, y0, x, mx, gpu, m, what + ("rule",))
+    op_tab = w.MassOperator(V, p, phi1, detJ, perm=perm, tuning=tun)
+    check_march(op_tab, y0, x, mx, gpu, m, what + ("tables",))
+    return mx, x, op_rule
+
+
+# --------------------------------------------------------------------------- 1. every compiled pair
+@pytest.mark.parametrize("lz", [None, 3])
+@pytest.mark.parametrize("p,quad,qd", GAUSS + GLL)
+def test_compiled_pairs(gpu, oracle, p, quad, qd, lz):
+    """45 cells in 5 x 3 x 3: no default cross-section divides 5 x 3, so every degree has partly filled columns (P1:
+    15 of the 8 x 8 slots).  The plan's own choice for so small a mesh is one layer per work item; with lz = 3 the three
+    layers are one item, which reaches the three compile-time copies of the layer body and both LDS buffers."""
+    variant = "gll_warped" if p % 2 == 0 else "equispaced"
+    m, n = npts(quad, qd), p + 1
+    assert m != n and (p, m) in COMPILED
+    om, mesh, V = make(oracle, MESH, p)
+    mx, x, op = run_march(gpu, oracle, om, V, p, variant, quad, qd, seed=p * 100 + qd, tuning=None if lz is None else {"lz": lz})
+    assert op.info.plan_fill < 1.0 and (lz is None or op.info.plan_lz == lz)
+    assert op.flops() == 4.0 * om.ncells * m ** 3 * n ** 3
+    assert op.alg_bytes() == om.ncells * (8.0 * m ** 3 + 4.0 * n ** 3) + 16.0 * om.ndofs
+    # oracle-free, as test_rule_vs_oracle: sum(M 1) = |Omega| = 1, y^T M x = x^T M y, M > 0 when M >= n
+    if m >= 2:
+        assert abs(apply(op, np.ones(om.ndofs), gpu).sum() - 1.0) <= 1e-13
+    yv = np.random.default_rng(qd).uniform(-1, 1, om.ndofs)
+    mxd, myd = apply(op, x, gpu), apply(op, yv, gpu)
+    a, b = yv @ mxd, x @ myd
+    assert abs(a - b) <= 1e-13 * (np.abs(yv) @ np.abs(mxd))
+    if m >= n:
+        assert x @ mxd > 0
+
+
+# --------------------------------------------------------------------------- 2. layers and z segments
+@pytest.mark.parametrize("lz", [None, 2])
+@pytest.mark.parametrize("nz", [1, 2, 5])
+@pytest.mark.parametrize("p,quad,qd", [(2, "gauss_jacobi", 6), (4, "gll", 5)])
+def test_layers_and_segments(gpu, oracle, p, quad, qd, nz, lz):
+    """(2, 4): M > n, four cells share a wave; (4, 4): M < n.  lz = 2 cuts nz = 5 into items of 2, 2 and 1 layers."""
+    om, mesh, V = make(oracle, (2, 2, nz), p)
+    _, _, op = run_march(gpu, oracle, om, V, p, "gll_warped", quad, qd, seed=nz, tuning=None if lz is None else {"lz": lz})
+    if lz is not None:
+        assert op.info.plan_lz == lz
+    assert op.info.plan_items == (nz + op.info.plan_lz - 1) // op.info.plan_lz     # one column
+
+
+# --------------------------------------------------------------------------- 3. alternative cross-sections
+@pytest.mark.parametrize("p,quad,qd,block", [(4, "gauss_jacobi", 10, (2, 2, 0)), (4, "gll", 5, (2, 2, 0)),
+                                             (6, "gll", 7, (2, 1, 0))])
+def test_alternative_cross_sections(gpu, oracle, p, quad, qd, block):
+    om, mesh, V = make(oracle, (3, 3, 2), p)
+    _, _, op = run_march(gpu, oracle, om, V, p, "gll_warped", quad, qd, seed=8, tuning={"block": block})
+    # 3 x 3 cells: 2 x 2 columns of 2 x 2 cells, 2 x 3 columns of 2 x 1 cells (the defaults 4 x 2 and 2 x 2: 1 x 2, 2 x 2)
+    assert op.info.plan_items == {(2, 2, 0): 4, (2, 1, 0): 6}[block] * ((2 + op.info.plan_lz - 1) // op.info.plan_lz)
+
+
+# --------------------------------------------------------------------------- 4. re-oriented meshes
+@pytest.mark.parametrize("p,quad,qd", [(2, "gauss_jacobi", 6), (4, "gll", 5), (4, "gauss_jacobi", 10)])
+@pytest.mark.parametrize("kind", ["glued_rotated", "glued_reflected", "random_orient", "ogrid"])
+def test_reoriented_meshes(gpu, oracle, kind, p, quad, qd):
+    from wave_fenics_amd import mesh_io
+    mesh, nre = build_mesh(kind, p)
+    V = mesh_io.create_functionspace(mesh, p)
+    om = oracle_mesh(oracle, mesh, V)
+    _, _, op = run_march(gpu, oracle, om, V, p, "gll_warped", quad, qd, seed=p)
+    if nre is not None:
+        assert op.info.plan_reoriented == nre
+    if kind == "random_orient":
+        assert op.info.plan_reoriented > mesh.ncells // 2
+
+
+# --------------------------------------------------------------------------- 5. a table that is not symmetric
+def dense_phi(phi1):
+    """The oracle's phi[nq][nd] of a 1-D table: x fastest in points and in nodes."""
+    return np.kron(phi1, np.kron(phi1, phi1))
+
+
+@pytest.mark.parametrize("kind", ["random_orient", "box"])
+def test_table_that_does_not_read_the_same_backwards(gpu, oracle, kind):
+    """A random phi1[4][3] at P2 (explicit tables): phi1[M-1-q][n-1-a] != phi1[q][a], so no cell may be looked at in
+    a reversed frame -- on random_orient the cells that disagree with their column become components of their own."""
+    import wave_fenics_amd as w
+    from wave_fenics_amd import mesh_io
+    p = 2
+    # the construction of phi from phi1 used below is the oracle's own
+    _, _, t1, tphi, X, W = oracle.tabulate_mass_tables(p, "gll", "gauss_jacobi", 6)
+    assert t1.shape == (4, 3) and np.array_equal(dense_phi(t1), tphi)
+    if kind == "box":
+        om, mesh, V = make(oracle, (3, 2, 2), p)
+    else:
+        mesh, _ = build_mesh(kind, p)
+        V = mesh_io.create_functionspace(mesh, p)
+        om = oracle_mesh(oracle, mesh, V)
+    phi1 = np.random.default_rng(31).uniform(-1, 1, (4, 3))
+    assert np.abs(phi1[::-1, ::-1] - phi1).max() > 0.1
+    detJ = oracle.compute_detJ_generic(om, X, W)
+    x, mx, y0 = reference(oracle, om, dense_phi(phi1), detJ, seed=6)
+    op = w.MassOperator(V, p, phi1, detJ, tuning=HINT)
+    check_march(op, y0, x, mx, gpu, 4, (kind, "random table"))
+    assert op.info.plan_reoriented == 0
+
+
+# --------------------------------------------------------------------------- 6. element permutation
+def test_element_permutation(gpu, oracle):
+    """An element-ordered dofmap + perm (common/permute.hpp:10-27), as test_gpu_dense_mass_rules does, with the hint."""
+    import wave_fenics_amd as w
+    p, n = 3, (3, 2, 2)
+    om, mesh, V = make(oracle, n, p)
+    rng = np.random.default_rng(17)
+    eperm = rng.permutation((p + 1) ** 3).astype(np.int32)
+    inv = np.empty_like(eperm)
+    inv[eperm] = np.arange(eperm.size, dtype=np.int32)
+    Vp = w.FunctionSpace(mesh, p, np.ascontiguousarray(om.dofmap[:, inv]), w.IndexMap(om.ndofs), V.lattice,
+                         structured=False)
+    run_march(gpu, oracle, om, Vp, p, "equispaced", "gauss_jacobi", 8, seed=4, perm=eperm)
+
+
+# --------------------------------------------------------------------------- 7. square table
+def test_square_table_with_the_hint(gpu, oracle):
+    """nq1 == P+1: the hint is WF_KERNEL_FORCE_MARCH."""
+    p = 3
+    assert npts("gauss_jacobi", 6) == p + 1
+    om, mesh, V = make(oracle, (3, 2, 2), p)
+    run_march(gpu, oracle, om, V, p, "equispaced", "gauss_jacobi", 6, seed=2)
+
+
+# --------------------------------------------------------------------------- 8. errors
+def test_errors(gpu, oracle):
+    import wave_fenics_amd as w
+    from wave_fenics_amd._lib import WF_FLAG_ORDERED
+    om, mesh, V = make(oracle, (2, 2, 2), 2)
+    for bad in (lambda: w.StiffnessOperator(V, 2, structured=False, tuning=HINT),
+                lambda: w.StiffnessOperator(V, 2, tuning=HINT),
+                lambda: w.MassOperatorLumped(V, 2, structured=False, tuning=HINT),
+                lambda: w.MassOperator(V, 2, variant="gll_warped", quad="gauss_jacobi", qdegree=8, tuning=HINT),   # M = 5
+                lambda: w.MassOperator(V, 2, variant="gll_warped", quad="gauss_jacobi", qdegree=6, tuning=HINT,
+                                       flags=WF_FLAG_ORDERED)):
+        with pytest.raises(w.WavehipError):
+            bad()
+    with pytest.raises(w.WavehipError, match=r"\(2, 5\)"):
+        w.MassOperator(V, 2, variant="gll_warped", quad="gauss_jacobi", qdegree=8, tuning=HINT)
+    om7, mesh7, V7 = make(oracle, (1, 1, 1), 7)
+    assert npts("gauss_jacobi", 16) == 9
+    with pytest.raises(w.WavehipError, match=r"\(7, 9\)"):
+        w.MassOperator(V7, 7, variant="gll_warped", quad="gauss_jacobi", qdegree=16, tuning=HINT)
+    # the library is still usable afterwards
+    run_march(gpu, oracle, om, V, 2, "gll_warped", "gauss_jacobi", 6, seed=1)
+
+
+# --------------------------------------------------------------------------- 9. C++ host path
+def test_cxx_operator_demo_dense_march(gpu, tmp_path):
+    """examples/operator_demo --op dense --kernel march through wavehip::MassOperator(..., tuning): the default rule
+    (4-point GLL at P4) and Gauss of degree 10 (6 points).  On the undisplaced box, sum(M 1) = |Omega| = sum of the
+    lumped mass; the kernel id printed is WF_KERNEL_MARCH_IDX."""
+    from wave_fenics_amd._lib import WF_KERNEL_MARCH_IDX
+    out = str(tmp_path / "bin")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "examples"), f"OUT={out}",
+                           "CXXFLAGS=-O1 -std=c++17 -Wall -Werror", os.path.join(out, "operator_demo")])
+    for extra, m in (([], 4), (["--quad", "gauss", "--qdegree", "10"], 6)):
+        r = subprocess.run([os.path.join(out, "operator_demo"), "--op", "dense", "--degree", "4", "--size", "4",
+                            "--check", "--reps", "2", "--kernel", "march"] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout + r.stderr
+        s = re.search(r"check: sum\(y\) = (\S+)\s+sum\(lumped\) = (\S+)", r.stdout)
+        assert s, r.stdout
+        sy, sl = float(s.group(1)), float(s.group(2))
+        assert abs(sy - sl) <= 1e-12 * abs(sl) and abs(sl - 1.0) <= 1e-12, r.stdout
+        assert f"Number of quads: {m ** 3}" in r.stdout, r.stdout
+        assert f"Kernel id: {WF_KERNEL_MARCH_IDX}\n" in r.stdout, r.stdout

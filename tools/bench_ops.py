@@ -62,6 +62,46 @@ def lagrange(nodes, pts):
     return phi
 
 
+def gll_rule(m):
+    """m-point Gauss-Lobatto-Legendre rule on [0, 1] (the GLL rule of degree 2 m - 3, which tabulate_gll gives with the
+    nodes of degree m - 1)."""
+    pts, wts, _ = w.tabulate_gll(m - 1)
+    return pts, wts
+
+
+def bench_dense_rect(V, mesh, p, x, y, tag):
+    """Dense mass with a rectangular table: Gauss with P+2 points and the GLL rule of degree P+1 where it is not square
+    (4, 5, 5, 6 points at P4..P7), each on the default any-rule kernel and on the marching kernel asked for with
+    {"kernel": "mass_march"}.  The two operators are timed alternately, RECT_ROUNDS times (default 3): the median and the
+    spread of the rounds.  A pair the marching kernel is not compiled for prints its default line only."""
+    N, n = V.ndofs, p + 1
+    rules = [("gauss", gl_rule(p + 2), np.linspace(0, 1, n))]
+    mg = max(2, (p + 5) // 2)
+    if mg != n:
+        rules.append(("gll", gll_rule(mg), w.tabulate_gll(p)[0]))
+    rounds = int(os.environ.get("RECT_ROUNDS", "3"))
+    for label, (qp, qw), nodes in rules:
+        phi1, m = lagrange(nodes, qp), len(qp)
+        W3 = np.einsum("k,j,i->kji", qw, qw, qw).reshape(-1)
+        detq = np.tile(W3 / mesh.ncells, (mesh.ncells, 1))     # affine box: detJ = vol * w_q
+        ops = [("default", w.MassOperator(V, p, phi1, detq))]
+        try:
+            ops.append(("mass_march", w.MassOperator(V, p, phi1, detq, tuning={"kernel": "mass_march"})))
+        except w.WavehipError:
+            pass
+        del detq
+        ms = {name: [] for name, _ in ops}
+        for _ in range(rounds):
+            for name, op in ops:
+                ms[name].append(timeit(lambda: op.apply(x, y), reps=10))
+        for name, op in ops:
+            t = float(np.median(ms[name]))
+            report(f"dense mass P{p} {label} {m} points [{name}]", t, op.alg_bytes(), N,
+                   dict(tag, nq1=m, kernel=op.kernel, alg_bytes=op.alg_bytes(), ms_rounds=[round(v, 4) for v in ms[name]],
+                        ns_per_detJ_KB=round(t * 1e6 / (8.0 * mesh.ncells * m ** 3 / 1024), 4), lz=op.info.plan_lz))
+        del ops
+
+
 def bench_tet(dev):
     import time
     from wave_fenics_amd import tet
@@ -158,13 +198,14 @@ def main():
                 op = w.MassOperator(V, p, phi1, detq)
                 alg = mesh.ncells * (8.0 * m ** 3 + 4.0 * (p + 1) ** 3) + 16.0 * N
                 report(f"dense mass P{p} {label} (sum-factorised Phi^T D Phi)", timeit(lambda: op.apply(x, y), reps=10),
-                       alg, N, dict(tag, kernel=op.kernel, flops_ref_model=op.flops()))
+                       alg, N, dict(tag, kernel=op.kernel, alg_bytes=alg, flops_ref_model=op.flops()))
                 del op
                 if label != "gll-collocated":   # order-fixed accumulation next to the default form
                     op = w.MassOperator(V, p, phi1, detq, flags=WF_FLAG_ORDERED)
                     report(f"dense mass P{p} {label} ordered [{op.kernel}]", timeit(lambda: op.apply(x, y), reps=10),
                            op.alg_bytes(), N, dict(tag, kernel=op.kernel, flops_ref_model=op.flops()))
                     del op
+            bench_dense_rect(V, mesh, p, x, y, tag)
         if "vector" in only and p == 4:
             z = torch.zeros_like(x)
             report("axpy r=a*x+y", timeit(lambda: la.axpy(z, 0.5, x, y)), 24.0 * N, N)

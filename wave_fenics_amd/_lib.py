@@ -87,7 +87,7 @@ WF_UPDATER_DEFAULT, WF_UPDATER_INLINE, WF_UPDATER_CHAIN_ON_SIDE = 0, 1, 2
 (WF_KERNEL_NONE, WF_KERNEL_MARCH_BOX, WF_KERNEL_MARCH_IDX, WF_KERNEL_BATCH_UNIQUE, WF_KERNEL_BOX_BLOCK, WF_KERNEL_DIAGONAL,
  WF_KERNEL_MASS_DENSE_ANY, WF_KERNEL_DENSE_SIMPLEX, WF_KERNEL_ELEMENTWISE, WF_KERNEL_CELLS_ORDERED) = range(10)
 (WF_KERNEL_AUTO, WF_KERNEL_FORCE_BATCH, WF_KERNEL_FORCE_BOX_BLOCK, WF_KERNEL_FORCE_MASS_ANY, WF_KERNEL_FORCE_ELEMENTWISE,
- WF_KERNEL_FORCE_MARCH) = range(6)
+ WF_KERNEL_FORCE_MARCH, WF_KERNEL_FORCE_MASS_MARCH) = range(7)
 WF_OP_STIFFNESS, WF_OP_MASS_LUMPED, WF_OP_MASS_DENSE = 0, 1, 2
 WF_FLAG_NONE, WF_FLAG_NO_FABS, WF_FLAG_NO_CLAMP, WF_FLAG_MASS_ELEMENTWISE, WF_FLAG_TENSOR_X_SLOWEST = 0, 1, 2, 4, 8
 WF_FLAG_ORDERED = 16   # order-fixed accumulation: bitwise reproducible y on any mesh (include/wavehip.h)

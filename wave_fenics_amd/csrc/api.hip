@@ -747,11 +747,11 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
   return WF_OK;
 }
 
-// dense mass: det J * w in the blocked slot layout [item * lz + layer][k][t], t = slot_in_layer * n^2 + j n + i; empty
-// slots zero
+// dense mass: det J * w at the M^3 points of the rule (M = nq1) in the blocked slot layout [item * lz + layer][qk][t],
+// t = slot_in_layer * M^2 + qj M + qi; empty slots zero
 int plan_mass_detJ(const wf_op_desc* desc, const CallerFrame& fr, const MarchPlan& plan, wf_op* op)
 {
-  const int n = op->n, nd = op->nd, CB = op->plan.bx * op->plan.by, NTq = CB * n * n;
+  const int n = op->n, M = desc->nq1, nq = M * M * M, CB = op->plan.bx * op->plan.by, NTq = CB * M * M;
   const size_t nslots = (size_t)plan.nitems * plan.lz * CB;
   // det J * w per cell and point, host copy in the caller's cell order and point order
   std::vector<double> hd;
@@ -759,26 +759,27 @@ int plan_mass_detJ(const wf_op_desc* desc, const CallerFrame& fr, const MarchPla
   bool raw_points;   // hd is in the engine's (raw cell frame) point order already
   int rc;
   if ((rc = host_detJ(desc, hd, &hsrc, &raw_points)) != WF_OK) return rc;
-  PointMaps point_map{fr, n};
-  std::vector<double> blk(nslots * nd, 0.0);
+  PointMaps point_map{fr, M};
+  std::vector<double> blk(nslots * nq, 0.0);
   for (size_t q = 0; q < nslots; ++q) {
     const int32_t c = plan.slot_cell[q];
     if (c < 0) continue;
     const int code = plan.cell_orient[c];
     const size_t sub = q / CB, sl = q % CB;
-    const double* src = hsrc + (size_t)c * nd;
-    for (int k = 0; k < n; ++k)
-      for (int ji = 0; ji < n * n; ++ji) {
-        const int l = ji + n * n * k;
-        const int rp = raw_points ? orient_local_index(code, n, l % n, (l / n) % n, l / (n * n)) : point_map(code)[l];
-        blk[(sub * n + k) * NTq + sl * n * n + ji] = src[rp];
+    const double* src = hsrc + (size_t)c * nq;
+    for (int k = 0; k < M; ++k)
+      for (int ji = 0; ji < M * M; ++ji) {
+        const int l = ji + M * M * k;
+        const int rp = raw_points ? orient_local_index(code, M, l % M, (l / M) % M, l / (M * M)) : point_map(code)[l];
+        blk[(sub * M + k) * NTq + sl * M * M + ji] = src[rp];
       }
   }
   // A non-symmetric 1-D table kept the caller's frames (normalise in create_on_plan).
   if ((rc = dev_upload(&op->d_detJ, blk.data(), blk.size(), &op->device_bytes)) != WF_OK) return rc;
-  if ((rc = dev_upload(&op->d_phi1, desc->h_phi1, (size_t)n * n, &op->device_bytes)) != WF_OK) return rc;
-  for (int q = 0; q < n * n; ++q) op->dm.v[q] = desc->h_phi1[q];
-  op->nq1 = n;
+  if ((rc = dev_upload(&op->d_phi1, desc->h_phi1, (size_t)M * n, &op->device_bytes)) != WF_OK) return rc;
+  for (int q = 0; q < M * n; ++q) op->dm.v[q] = desc->h_phi1[q];
+  op->nq1 = M;
+  op->nq = nq;
   op->kernel = OpKernel::mass_march;
   return WF_OK;
 }
@@ -789,25 +790,38 @@ int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t*
   const int P = op->P, n = op->n;
   const wf_tuning& tun = op->tun;
   const int pkind = mass ? OP_KIND_MASS : OP_KIND_STIFFNESS;
-  int BX = tun.bx, BY = tun.by;   // stiffness: a compiled cross-section of the k-split kernel, else the default
-  march_idx_shape(pkind, P, &BX, &BY);
+  const int M = mass ? desc->nq1 : n;   // points of the 1-D table
+  int BX = tun.bx, BY = tun.by;   // a compiled cross-section of the k-split / the dense-mass kernel, else the default
+  if (!mass) {
+    march_idx_shape(pkind, P, &BX, &BY);
+  } else if (!mass_march_shape(P, M, &BX, &BY)) {
+    set_error("wf_op_create: WF_KERNEL_FORCE_MASS_MARCH: no marching kernel is compiled for (P, nq1) = (" + std::to_string(P)
+              + ", " + std::to_string(M) + ")");
+    return WF_ERR_UNSUPPORTED;
+  }
   // layers per work item: as many as the kernel's LDS budget per workgroup allows, at most 16
   int lz_max = mass ? 32 : 16;   // (the dense-mass kernel streams its index table: no LDS limit)
   while (!mass && lz_max > 1 && march_idx_lds_bytes(pkind, P, BX, BY, lz_max) > march_idx_lds_budget(pkind, P, BX, BY)) --lz_max;
   // A cell may be looked at with an axis reversed only if the 1-D table reads the same backwards,
-  // phi1[n-1-q][n-1-a] == phi1[q][a] (true for every symmetric node / point set; the GLL derivative
+  // phi1[M-1-q][n-1-a] == phi1[q][a] (true for every symmetric node / point set; the GLL derivative
   // matrix of the stiffness operator has the matching antisymmetry by construction).
   bool normalise = tun.orient == 0;
   if (mass)
-    for (int q = 0; q < n && normalise; ++q)
+    for (int q = 0; q < M && normalise; ++q)
       for (int a2 = 0; a2 < n; ++a2)
-        if (std::abs(desc->h_phi1[q * n + a2] - desc->h_phi1[(n - 1 - q) * n + (n - 1 - a2)]) > 1e-13) normalise = false;
+        if (std::abs(desc->h_phi1[q * n + a2] - desc->h_phi1[(M - 1 - q) * n + (n - 1 - a2)]) > 1e-13) normalise = false;
   MarchPlan plan;
   int rc;
   if ((rc = build_march_plan(P, (size_t)desc->ncells, tdm, BX, BY, lz_max, std::max(0, tun.lz), normalise, &plan)) != WF_OK) return rc;
   // mostly empty columns (a mesh one cell wide, a mesh shattered into tiny lattice components): the
   // marching kernel would read geometry for every slot -- batch kernel instead
-  if (plan.ok && plan.fill < kMinPlanFill && tun.kernel != WF_KERNEL_FORCE_MARCH) plan.ok = false;
+  const bool forced = tun.kernel == WF_KERNEL_FORCE_MARCH || tun.kernel == WF_KERNEL_FORCE_MASS_MARCH;
+  if (plan.ok && plan.fill < kMinPlanFill && !forced) plan.ok = false;
+  if (!plan.ok && mass && M != n) {   // a rectangular table is here on request only
+    set_error("wf_op_create: WF_KERNEL_FORCE_MASS_MARCH: the mesh does not tile into lattice columns ((P, nq1) = ("
+              + std::to_string(P) + ", " + std::to_string(M) + "))");
+    return WF_ERR_UNSUPPORTED;
+  }
   if (!plan.ok) return WF_OK;
 
   op->plan = MarchPlanDev{plan.nitems, plan.lz, plan.tile_size, BX, BY};
@@ -1093,10 +1107,14 @@ int wf_op_create(const wf_op_desc* desc, wf_op** out)
                "wf_op_create: WF_FLAG_ORDERED takes no wf_tuning field other than keep_cell_order");
   }
 
-  // the lattice-column plan serves the stiffness operator and the dense mass with a square 1-D table
+  WF_REQUIRE(tun.kernel != WF_KERNEL_FORCE_MASS_MARCH || desc->kind == WF_OP_MASS_DENSE,
+             "wf_op_create: WF_KERNEL_FORCE_MASS_MARCH applies to the dense mass only");
+  // the lattice-column plan serves the stiffness operator and the dense mass: with a square 1-D table by default, with
+  // a rectangular one on request (WF_KERNEL_FORCE_MASS_MARCH)
   const bool plan_stiffness = desc->kind == WF_OP_STIFFNESS;
-  const bool plan_mass = desc->kind == WF_OP_MASS_DENSE && desc->nq1 == n && desc->h_phi1
-                         && (desc->h_detJ || (have_mesh && desc->h_qpts1 && desc->h_qwts1));
+  const bool mass_table = desc->kind == WF_OP_MASS_DENSE && desc->nq1 >= 1 && desc->h_phi1
+                          && (desc->h_detJ || (have_mesh && desc->h_qpts1 && desc->h_qwts1));
+  const bool plan_mass = mass_table && (desc->nq1 == n || tun.kernel == WF_KERNEL_FORCE_MASS_MARCH);
   const bool force_batch = tun.kernel == WF_KERNEL_FORCE_BATCH || tun.kernel == WF_KERNEL_FORCE_ELEMENTWISE
                            || tun.kernel == WF_KERNEL_FORCE_MASS_ANY;
   int rc;
@@ -1367,6 +1385,8 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
     return WF_ERR_UNSUPPORTED;
   }
   WF_REQUIRE(kind == WF_OP_STIFFNESS || kind == WF_OP_MASS_LUMPED, "wf_op_create_box: kind must be stiffness or lumped mass");
+  WF_REQUIRE(!tuning || tuning->kernel != WF_KERNEL_FORCE_MASS_MARCH,
+             "wf_op_create_box: WF_KERNEL_FORCE_MASS_MARCH applies to the dense mass only");
   WF_REQUIRE(nx > 0 && ny > 0 && nz > 0 && h_xverts, "wf_op_create_box: bad mesh");
   const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
   WF_REQUIRE(NX * NY * NZ < ((size_t)1 << 31), "wf_op_create_box: dof lattice exceeds int32");
@@ -1476,7 +1496,7 @@ static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitem
     case OpKernel::lumped_elementwise:
       return launch_mass_lumped((int64_t)op->ncells * op->nd, op->d_dofmap, op->d_detJ, d_x, d_y, s);
     case OpKernel::diagonal: return wf_pointwise_mult_add(op->ndofs, op->d_mdiag, d_x, d_y, s);
-    case OpKernel::mass_march: return launch_mass_march(op->P, op->plan, op->d_detJ, op->d_phi1, d_x, d_y, s);
+    case OpKernel::mass_march: return launch_mass_march(op->P, op->nq1, op->plan, op->d_detJ, op->d_phi1, d_x, d_y, s);
     case OpKernel::mass_column:
       return launch_mass_dense_col(op->P, op->ncells, op->d_uoff, op->d_uniq, op->d_loc, op->d_phi1, op->d_detJ, d_x, d_y, s);
     case OpKernel::mass_any:   // with the unique-dof tile when creation built the lists (d_uoff)

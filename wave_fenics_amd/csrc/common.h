@@ -190,9 +190,10 @@ constexpr int OP_KIND_STIFFNESS = 0, OP_KIND_MASS = 1;
 void march_idx_shape(int kind, int P, int* bx, int* by);   // stiffness: keeps a compiled (*bx, *by) of the k-split kernel
 size_t march_idx_lds_bytes(int kind, int P, int BX, int BY, int lz);
 size_t march_idx_lds_budget(int kind, int P, int BX, int BY);
-// dense mass on the lattice columns (mass_march.hip)
-void mass_march_shape(int P, int* bx, int* by);
-int launch_mass_march(int P, const MarchPlanDev& pd, const double* d_detJblk, const double* d_phi1, const double* d_x,
+// dense mass on the lattice columns (mass_march.hip), 1-D table phi1[M][P + 1].  mass_march_shape: whether the pair
+// (P, M) is compiled; then keeps a compiled (*bx, *by) of the pair, else sets the pair's default
+bool mass_march_shape(int P, int M, int* bx, int* by);
+int launch_mass_march(int P, int M, const MarchPlanDev& pd, const double* d_detJblk, const double* d_phi1, const double* d_x,
                       double* d_y, hipStream_t s);
 int launch_stiffness_march_idx(int P, const MarchPlanDev& pd, const double* d_G6blk, const double* d_D,
                                const DMat& dm, double coeff, const double* d_x, double* d_y, const int32_t* d_items,

@@ -89,18 +89,19 @@ constexpr size_t march_ks_lds_bytes(int P, int BX, int BY, int lz, bool idx)
   const size_t d = (size_t)2 * (P + 1) * c.TP + (size_t)2 * P * c.TP + (size_t)2 * c.CB * c.n2 + (size_t)3 * c.CB * c.nd + 2 * c.n2 + 2;
   return d * sizeof(double) + (idx ? (size_t)(P * lz + 1) * c.TP * sizeof(int32_t) : 0);
 }
-// dense mass (mass_march.hip): whole cells per wave; the index table streams through a ring of 4 P + 1 planes, so the
-// footprint does not depend on the segment length
-constexpr int mass_workgroup_size(int P, int BX, int BY)
+// dense mass (mass_march.hip), 1-D table of M points: whole cells per wave (a cell takes max(P + 1, M)^2 lanes); the
+// index table streams through a ring of 4 P + 1 planes, so the footprint does not depend on the segment length
+constexpr int mass_workgroup_size(int P, int M, int BX, int BY)
 {
   const ColumnDims c = column_dims(P, BX, BY);
-  return 64 * ((c.CB + 64 / c.n2 - 1) / (64 / c.n2));
+  const int MX = M > c.n ? M : c.n, CW = 64 / (MX * MX);
+  return 64 * ((c.CB + CW - 1) / CW);
 }
-constexpr size_t mass_march_lds_bytes(int P, int BX, int BY, int /*lz*/)
+constexpr size_t mass_march_lds_bytes(int P, int M, int BX, int BY, int /*lz*/)
 {
   const ColumnDims c = column_dims(P, BX, BY);
-  const size_t WG = (size_t)mass_workgroup_size(P, BX, BY);
-  const size_t d = (size_t)2 * (P + 1) * c.TP + (size_t)2 * P * c.TP + (size_t)2 * c.CB * c.n2 + (size_t)c.CB * c.nd + WG + 2;
+  const size_t WG = (size_t)mass_workgroup_size(P, M, BX, BY), MX = M > c.n ? M : c.n;
+  const size_t d = (size_t)2 * (P + 1) * c.TP + (size_t)2 * P * c.TP + (size_t)2 * c.CB * c.n2 + (size_t)c.CB * c.n * MX * M + WG + 2;
   return d * sizeof(double) + ((size_t)(4 * P + 1) * c.TP + WG) * sizeof(int32_t);
 }
 

@@ -1,15 +1,17 @@
-// k_mass_march<P, BX, BY>: dense (sum-factorised) mass operator y += Phi^T diag(det J w) Phi x with a square
-// 1-D table Phi = phi1 (x) phi1 (x) phi1 on the lattice columns of ANY dofmap -- MassOperator::apply,
+// k_mass_march<P, M, BX, BY>: dense (sum-factorised) mass operator y += Phi^T diag(det J w) Phi x with the 1-D table
+// phi1[M][n] of an M-point rule, Phi = phi1 (x) phi1 (x) phi1, on the lattice columns of ANY dofmap -- MassOperator::apply,
 // common/cuda/mass.hpp:76-95 + mass_kernel.cu:5-37, the DGEMM pair of demo/gpu_operator/main.cpp:144-160
 // (k >> m ~ n), marching through the columns like the stiffness kernels (plan of generic_plan.cpp).
 //
 // Structure:
-//  * a cell lives inside ONE wave (n^2 = (P+1)^2 lanes; floor(64 / n^2) cells per wave), so the five passes of
-//    the element kernel exchange their data through wave-private LDS scratch with no workgroup barrier --
-//    LDS operations of one wave execute in order;
-//  * every pass is a "pencil" contraction in registers, in place: a lane reads the n values of one line of the
-//    cell, multiplies by the 1-D table held in VGPRs (n^2 doubles, the same in every lane: as scalar operands
-//    they would need 2 n^2 SGPRs) and writes the n results over them -- 2 n LDS accesses per lane and pass:
+//  * a cell lives inside ONE wave (MX^2 lanes, MX = max(n, M), n = P + 1; floor(64 / MX^2) cells per wave), so the
+//    five passes of the element kernel exchange their data through wave-private LDS scratch with no workgroup
+//    barrier -- LDS operations of one wave execute in order;
+//  * every pass is a "pencil" contraction in registers, in place: a lane reads the values of one line of the
+//    cell (n nodes or M points), multiplies by the 1-D table held in VGPRs (M n doubles, the same in every lane:
+//    as scalar operands they would need 2 M n SGPRs) and writes the results over them (M or n: the scratch
+//    A[n][MX][M] has room for either along y, and holds only point values along x).  i, j, k < n; qi, qj, qk < M;
+//    a lane is (p0, p1) = (lane % MX, lane / MX) and sits out the passes whose ranges it exceeds:
 //        X  : lane (j, k)   A[k][j][qi]   = sum_i  phi[qi][i] U[k][j][i]
 //        Y  : lane (qi, k)  A[k][qj][qi]  = sum_j  phi[qj][j] A[k][j][qi]
 //        Z  : lane (qi, qj) w[qk] = detJ[qk] sum_k phi[qk][k] A[k][qj][qi];  A[k][qj][qi] = sum_qk phi[qk][k] w[qk]
@@ -39,12 +41,24 @@ WF_COLUMN_TRACE(g_mass_trace, wf_debug_mass_trace, 12, 10)
 #define WF_MSTR(slot)
 #endif
 
-template <int P, int BX, int BY>
+// The compiled kernels X(P, M, BX, BY): the first cross-section of a pair (P, M) is its default.  Square tables
+// M = P + 1; Gauss rules of degree 2 P + 2 (M = P + 2); Basix' GLL rule of degree P + 1 where it is not square ((1, 3)
+// is also the Gauss pair).  (7, 9) does not fit a wave.
+#define WF_MASS_SHAPES(X)                                                                                         \
+  X(1, 2, 8, 8) X(2, 3, 7, 4) X(3, 4, 4, 4) X(4, 5, 4, 2) X(4, 5, 2, 2) X(5, 6, 2, 2) X(6, 7, 2, 2) X(6, 7, 2, 1) \
+  X(7, 8, 2, 1)                                                                                                   \
+  X(1, 3, 8, 8) X(2, 4, 7, 4) X(3, 5, 4, 4) X(4, 6, 4, 2) X(4, 6, 2, 2) X(5, 7, 2, 2) X(6, 8, 2, 2) X(6, 8, 2, 1) \
+  X(4, 4, 4, 2) X(4, 4, 2, 2) X(5, 5, 2, 2) X(6, 5, 2, 2) X(6, 5, 2, 1) X(7, 6, 2, 1)
+
+template <int P, int M, int BX, int BY>
 struct MassLayout : ColumnTile<P, BX, BY> {
   using T = ColumnTile<P, BX, BY>;
-  static constexpr int n2 = T::n2, nd = T::nd, CB = T::CB, TP = T::TP;
-  static constexpr int CW = 64 / n2;                      // cells per wave
-  static constexpr int WG = mass_workgroup_size(P, BX, BY);   // whole waves: ceil(CB / CW) of them
+  static constexpr int n2 = T::n2, CB = T::CB, TP = T::TP;
+  static constexpr int MX = M > P + 1 ? M : P + 1;        // lanes of a cell: MX^2
+  static constexpr int SX = M, SY = MX;                   // scratch of a cell A[n][SY][SX]
+  static constexpr int nd = T::n * SY * SX;
+  static constexpr int CW = 64 / (MX * MX);               // cells per wave
+  static constexpr int WG = mass_workgroup_size(P, M, BX, BY);   // whole waves: ceil(CB / CW) of them
   static constexpr int oUx = 0;                           // [2][(P + 1) TP]
   static constexpr int oO = oUx + 2 * (P + 1) * TP;       // [2][P TP] result tile of a layer, cells combined
   static constexpr int oCy = oO + 2 * P * TP;             // [2][CB n2]
@@ -56,7 +70,7 @@ struct MassLayout : ColumnTile<P, BX, BY> {
   static constexpr int RP = 4 * P + 1, RPT = RP * TP;
   // the ring is followed by a dump slot per thread for the table planes' out-of-tile last positions
   static constexpr size_t bytes = ndoubles * sizeof(double) + (size_t)(RPT + WG) * sizeof(int32_t);
-  static_assert(CW >= 1, "a cell does not fit a wave");
+  static_assert(MX <= 8, "a cell does not fit a wave");
 };
 
 struct MassArgs {
@@ -65,8 +79,8 @@ struct MassArgs {
   const int32_t* item_pattern;
   const int32_t* item_layers;
   const int32_t* pat_off;
-  const double* detJ;     // [item lz + layer][k][CB n2]
-  const double* phi1;     // [n][n] row-major: phi1[q][a]
+  const double* detJ;     // [item lz + layer][qk][CB M^2]
+  const double* phi1;     // [M][n] row-major: phi1[q][a]
   const double* x;
   double* y;
 };
@@ -94,11 +108,12 @@ __device__ __forceinline__ void wave_sync()
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int P, int BX, int BY>
-__global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(MassArgs a)
+template <int P, int M, int BX, int BY>
+__global__ __launch_bounds__((MassLayout<P, M, BX, BY>::WG), 2) void k_mass_march(MassArgs a)
 {
-  using L = MassLayout<P, BX, BY>;
+  using L = MassLayout<P, M, BX, BY>;
   constexpr int n = L::n, n2 = L::n2, nd = L::nd, CB = L::CB, CW = L::CW, WG = L::WG;
+  constexpr int MX = L::MX, M2 = M * M, SX = L::SX, SY = L::SY;
   constexpr int TX = L::TX, TP = L::TP;
   constexpr int NPOS = (P * TP + WG - 1) / WG;          // flush / x-prefetch positions per thread
   constexpr int NPOS0 = ((P + 1) * TP + WG - 1) / WG;   // prologue x positions per thread
@@ -111,9 +126,13 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
   constexpr int RPT = L::RPT;
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int cw = lane / n2, pq = lane % n2, p0 = pq % n, p1 = pq / n;
+  const int cw = lane / (MX * MX), pq = lane % (MX * MX), p0 = pq % MX, p1 = pq / MX;
   const int cl = wave * CW + cw;                       // cell of the layer
   const bool active = cw < CW && cl < CB;
+  // lanes of a cell with a line in the passes: X, X^T (j, k); Y, Y^T (qi, k); Z (qi, qj) -- all of them when M == n
+  const bool lane_x = (n == MX || p0 < n) && (n == MX || p1 < n);
+  const bool lane_y = (M == MX || p0 < M) && (n == MX || p1 < n);
+  const bool lane_z = (M == MX || p0 < M) && (M == MX || p1 < M);
   const int lx = cl % BX, ly = cl / BX;
   double* A = ms_smem + L::oA + (active ? cl : 0) * nd;
   const size_t item = blockIdx.x;
@@ -124,18 +143,18 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
   // that the compiler does not keep the n^2 wave-uniform values in SGPRs (it has ~100) and spill them
   int lane_zero;
   asm volatile("v_mov_b32 %0, 0" : "=v"(lane_zero));
-  double ph[n][n];
+  double ph[M][n];
 #pragma unroll
-  for (int q = 0; q < n; ++q)
+  for (int q = 0; q < M; ++q)
 #pragma unroll
     for (int c = 0; c < n; ++c) ph[q][c] = a.phi1[q * n + c + lane_zero];
 
   // det J w of this lane's quadrature column (qi, qj) = (p0, p1), all levels; two sets swapping roles
-  double dA[n], dB[n];
-  auto load_d = [&](double (&d)[n], int l) {
-    const double* dp = a.detJ + ((item * (size_t)a.lz + l) * n) * (size_t)(CB * n2) + (active ? cl * n2 + pq : 0);
+  double dA[M], dB[M];
+  auto load_d = [&](double (&d)[M], int l) {
+    const double* dp = a.detJ + ((item * (size_t)a.lz + l) * M) * (size_t)(CB * M2) + (active && lane_z ? cl * M2 + (M == MX ? pq : p1 * M + p0) : 0);
 #pragma unroll
-    for (int k = 0; k < n; ++k) d[k] = (WF_MASS_ABL & 8) ? 1.0 + k : __builtin_nontemporal_load(dp + (size_t)k * (CB * n2));
+    for (int k = 0; k < M; ++k) d[k] = (WF_MASS_ABL & 8) ? 1.0 + k : __builtin_nontemporal_load(dp + (size_t)k * (CB * M2));
   };
 
   // ---- prologue ---------------------------------------------------------------------------
@@ -155,7 +174,7 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
       Ux[pos] = off >= 0 ? a.x[gbase + off] : 0.0;
     }
   }
-  if (active) Cy[CB * n2 + cl * n2 + pq] = 0.0;   // carry into the first layer (buffer of "layer -1")
+  if (active && (n == MX || pq < n2)) Cy[CB * n2 + cl * n2 + pq] = 0.0;   // carry into the first layer (buffer of "layer -1")
   for (int e = t; e < 2 * P * TP; e += WG) O[e] = 0.0;
   __syncthreads();
 
@@ -210,21 +229,21 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
   };
 
   // pencil contraction out[q] = sum_c phi[q][c] in[c] (forward) or out[c] = sum_q phi[q][c] in[q] (transposed)
-  auto fwd = [&](const double (&in)[n], double (&out)[n]) {
+  auto fwd = [&](const double (&in)[n], double (&out)[M]) {
 #pragma unroll
-    for (int q = 0; q < n; ++q) {
+    for (int q = 0; q < M; ++q) {
       double s = 0.0;
 #pragma unroll
       for (int c = 0; c < n; ++c) s += ph[q][c] * in[c];
       out[q] = s;
     }
   };
-  auto bwd = [&](const double (&in)[n], double (&out)[n]) {
+  auto bwd = [&](const double (&in)[M], double (&out)[n]) {
 #pragma unroll
     for (int c = 0; c < n; ++c) {
       double s = 0.0;
 #pragma unroll
-      for (int q = 0; q < n; ++q) s += ph[q][c] * in[q];
+      for (int q = 0; q < M; ++q) s += ph[q][c] * in[q];
       out[c] = s;
     }
   };
@@ -234,7 +253,7 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
   // at the join, the wait-count state of the path without those loads -- in which the x / table loads are the
   // youngest -- and (c) then waited with vmcnt(0) for the det J stream of the NEXT layer (ISA before this change).
   // The stores of (c) sit in straight-line code: a thread's out-of-tile last position goes to a dump slot.
-  auto layer = [&](auto hn_tag, auto hn2_tag, double (&dcur)[n], double (&dnext)[n], int l, int b) {
+  auto layer = [&](auto hn_tag, auto hn2_tag, double (&dcur)[M], double (&dnext)[M], int l, int b) {
     constexpr bool has_next = decltype(hn_tag)::value, has_next2 = decltype(hn2_tag)::value;
     const double* Ub = Ux + b * (P + 1) * TP;
     double* Un = Ux + (b ^ 1) * (P + 1) * TP;
@@ -258,73 +277,81 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
     WF_MSTR(1);
 
     // (b) the five passes of the element kernel, wave-private, with the previous layer's flush between them
-    double in[n], out[n];
+    double vn[n], vm[M];   // a line's node values / point values
     flush_slot(Tprev, l, 0);
     const bool run_passes = active && !(WF_MASS_ABL & 16);
     if (run_passes) {
       // X: lane (j, k) = (p0, p1)
+      if (lane_x) {
 #pragma unroll
-      for (int c = 0; c < n; ++c) in[c] = Ub[ucell + p1 * TP + p0 * TX + c];
-      fwd(in, out);
+        for (int c = 0; c < n; ++c) vn[c] = Ub[ucell + p1 * TP + p0 * TX + c];
+        fwd(vn, vm);
 #pragma unroll
-      for (int q = 0; q < n; ++q) A[(p1 * n + p0) * n + q] = out[q];
+        for (int q = 0; q < M; ++q) A[(p1 * SY + p0) * SX + q] = vm[q];
+      }
       wave_sync();
     }
     WF_MSTR(2);
     flush_slot(Tprev, l, 1);
     if (run_passes) {
       // Y: lane (qi, k) = (p0, p1)
+      if (lane_y) {
 #pragma unroll
-      for (int c = 0; c < n; ++c) in[c] = A[(p1 * n + c) * n + p0];
-      fwd(in, out);
+        for (int c = 0; c < n; ++c) vn[c] = A[(p1 * SY + c) * SX + p0];
+        fwd(vn, vm);
 #pragma unroll
-      for (int q = 0; q < n; ++q) A[(p1 * n + q) * n + p0] = out[q];
+        for (int q = 0; q < M; ++q) A[(p1 * SY + q) * SX + p0] = vm[q];
+      }
       wave_sync();
     }
     WF_MSTR(3);
     flush_slot(Tprev, l, 2);
     if (run_passes) {
       // Z: lane (qi, qj) = (p0, p1): forward, times det J w, transposed
+      if (lane_z) {
 #pragma unroll
-      for (int c = 0; c < n; ++c) in[c] = A[(c * n + p1) * n + p0];
-      fwd(in, out);
+        for (int c = 0; c < n; ++c) vn[c] = A[(c * SY + p1) * SX + p0];
+        fwd(vn, vm);
 #pragma unroll
-      for (int q = 0; q < n; ++q) out[q] *= dcur[q];
-      bwd(out, in);
+        for (int q = 0; q < M; ++q) vm[q] *= dcur[q];
+        bwd(vm, vn);
 #pragma unroll
-      for (int c = 0; c < n; ++c) A[(c * n + p1) * n + p0] = in[c];
+        for (int c = 0; c < n; ++c) A[(c * SY + p1) * SX + p0] = vn[c];
+      }
       wave_sync();
     }
     WF_MSTR(4);
     flush_slot(Tprev, l, 3);
     if (run_passes) {
       // Y^T: lane (qi, k) = (p0, p1)
+      if (lane_y) {
 #pragma unroll
-      for (int q = 0; q < n; ++q) in[q] = A[(p1 * n + q) * n + p0];
-      bwd(in, out);
+        for (int q = 0; q < M; ++q) vm[q] = A[(p1 * SY + q) * SX + p0];
+        bwd(vm, vn);
 #pragma unroll
-      for (int c = 0; c < n; ++c) A[(p1 * n + c) * n + p0] = out[c];
+        for (int c = 0; c < n; ++c) A[(p1 * SY + c) * SX + p0] = vn[c];
+      }
       wave_sync();
     }
     WF_MSTR(5);
     flush_slot(Tprev, l, 4);
-    if (run_passes) {
+    if (run_passes && lane_x) {
       // X^T: lane (j, k) = (p0, p1); planes 0..P-1 -> O, plane P -> carry, plane 0 picks up the previous carry
 #pragma unroll
-      for (int q = 0; q < n; ++q) in[q] = A[(p1 * n + p0) * n + q];
-      bwd(in, out);
+      for (int q = 0; q < M; ++q) vm[q] = A[(p1 * SY + p0) * SX + q];
+      bwd(vm, vn);
       if (p1 == 0) {
 #pragma unroll
-        for (int c = 0; c < n; ++c) out[c] += Cy[(b ^ 1) * (CB * n2) + cl * n2 + p0 * n + c];
+        for (int c = 0; c < n; ++c) vn[c] += Cy[(b ^ 1) * (CB * n2) + cl * n2 + p0 * n + c];
       }
       if (p1 < P) {
         double* dst = Tb + ucell + p1 * TP + p0 * TX;
 #pragma unroll
-        for (int c = 0; c < n; ++c) lds_add(dst + c, out[c]);
+        for (int c = 0; c < n; ++c) lds_add(dst + c, vn[c]);
       } else {
         double* dst = Cy + b * (CB * n2) + cl * n2 + p0 * n;
 #pragma unroll
-        for (int c = 0; c < n; ++c) dst[c] = out[c];
+        for (int c = 0; c < n; ++c) dst[c] = vn[c];
       }
     }
     WF_MSTR(6);
@@ -363,7 +390,7 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
     __syncthreads();   // the one workgroup barrier of the layer
     WF_MSTR(8);
   };
-  auto layer_any = [&](double (&dcur)[n], double (&dnext)[n], int l, int b) {
+  auto layer_any = [&](double (&dcur)[M], double (&dnext)[M], int l, int b) {
     if (l + 2 < nl)
       layer(On{}, On{}, dcur, dnext, l, b);
     else if (l + 1 < nl)
@@ -404,46 +431,46 @@ __global__ __launch_bounds__((MassLayout<P, BX, BY>::WG), 2) void k_mass_march(M
   }
 }
 
-template <int P, int BX, int BY>
+template <int P, int M, int BX, int BY>
 static int launch_mass_t(const MassArgs& a, int nitems, size_t lds, hipStream_t s)
 {
   if (nitems == 0) return WF_OK;
-  WF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mass_march<P, BX, BY>),
+  WF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mass_march<P, M, BX, BY>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((k_mass_march<P, BX, BY>), dim3((unsigned)nitems), dim3(MassLayout<P, BX, BY>::WG), lds, s, a);
+  hipLaunchKernelGGL((k_mass_march<P, M, BX, BY>), dim3((unsigned)nitems), dim3(MassLayout<P, M, BX, BY>::WG), lds, s, a);
   return launch_status("mass_march");
 }
 
-// column cross-sections (the first of a degree is its default): whole cells per wave (floor(64 / n^2))
-// Smaller cross-sections (more, smaller workgroups per CU) measured slower at ~10 M dofs: P4 4x2 0.116 ms, 2x2
-// 0.155, 2x1 0.166; P6 2x2 0.126, 2x1 0.138, 1x1 0.182; P2 7x4 0.126, 7x2 0.140 (tools/bench_mass_lz.py).
-#define WF_MASS_SHAPES(X) \
-  X(1, 8, 8) X(2, 7, 4) X(3, 4, 4) X(4, 4, 2) X(4, 2, 2) X(5, 2, 2) X(6, 2, 2) X(6, 2, 1) X(7, 2, 1)
-
-#define X(PP, BXX, BYY)                                                                     \
-  static_assert(mass_march_lds_bytes(PP, BXX, BYY, 0) >= MassLayout<PP, BXX, BYY>::bytes, \
+// The compiled (degree, rule points, cross-section) combinations are WF_MASS_SHAPES above: whole cells per wave
+// (floor(64 / MX^2)).
+// Smaller cross-sections (more, smaller workgroups per CU) measured slower at ~10 M dofs with square tables: P4 4x2
+// 0.116 ms, 2x2 0.155, 2x1 0.166; P6 2x2 0.126, 2x1 0.138, 1x1 0.182; P2 7x4 0.126, 7x2 0.140 (tools/bench_mass_lz.py).
+#define X(PP, MM, BXX, BYY)                                                                           \
+  static_assert(mass_march_lds_bytes(PP, MM, BXX, BYY, 0) >= MassLayout<PP, MM, BXX, BYY>::bytes, \
                 "mass_march_lds_bytes does not cover MassLayout");
 WF_MASS_SHAPES(X)
 #undef X
 
-// keeps (*bx, *by) if that cross-section is compiled for the degree, else the degree's default
-void mass_march_shape(int P, int* bx, int* by)
+// Whether the pair (P, M) is compiled.  If so: keeps (*bx, *by) if that cross-section is compiled for the pair, else
+// sets the pair's default.
+bool mass_march_shape(int P, int M, int* bx, int* by)
 {
-#define X(PP, BXX, BYY) \
-  if (P == PP && *bx == BXX && *by == BYY) return;
+#define X(PP, MM, BXX, BYY) \
+  if (P == PP && M == MM && *bx == BXX && *by == BYY) return true;
   WF_MASS_SHAPES(X)
 #undef X
-#define X(PP, BXX, BYY) \
-  if (P == PP) {        \
-    *bx = BXX;          \
-    *by = BYY;          \
-    return;             \
+#define X(PP, MM, BXX, BYY) \
+  if (P == PP && M == MM) { \
+    *bx = BXX;              \
+    *by = BYY;              \
+    return true;            \
   }
   WF_MASS_SHAPES(X)
 #undef X
+  return false;
 }
 
-int launch_mass_march(int P, const MarchPlanDev& pd, const double* d_detJblk, const double* d_phi1, const double* d_x,
+int launch_mass_march(int P, int M, const MarchPlanDev& pd, const double* d_detJblk, const double* d_phi1, const double* d_x,
                       double* d_y, hipStream_t s)
 {
   MassArgs a{};
@@ -457,12 +484,12 @@ int launch_mass_march(int P, const MarchPlanDev& pd, const double* d_detJblk, co
   a.phi1 = d_phi1;
   a.x = d_x;
   a.y = d_y;
-  const size_t lds = mass_march_lds_bytes(P, pd.bx, pd.by, pd.lz);
-#define X(PP, BXX, BYY) \
-  if (P == PP && pd.bx == BXX && pd.by == BYY) return launch_mass_t<PP, BXX, BYY>(a, pd.nitems, lds, s);
+  const size_t lds = mass_march_lds_bytes(P, M, pd.bx, pd.by, pd.lz);
+#define X(PP, MM, BXX, BYY) \
+  if (P == PP && M == MM && pd.bx == BXX && pd.by == BYY) return launch_mass_t<PP, MM, BXX, BYY>(a, pd.nitems, lds, s);
   WF_MASS_SHAPES(X)
 #undef X
-  set_error("mass_march: cross-section not compiled");
+  set_error("mass_march: (degree, rule points, cross-section) not compiled");
   return WF_ERR_UNSUPPORTED;
 }
 

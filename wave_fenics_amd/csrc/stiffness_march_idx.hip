@@ -263,7 +263,7 @@ static bool march_idx_uses_ks(int P) { return P >= WF_IDX_KS_MINP; }
 void march_idx_shape(int kind, int P, int* bx, int* by)
 {
   if (kind == OP_KIND_MASS) {
-    mass_march_shape(P, bx, by);
+    mass_march_shape(P, P + 1, bx, by);   // (square table; a rectangular one: mass_march_shape itself)
     return;
   }
   if (march_idx_uses_ks(P)) {
@@ -290,7 +290,7 @@ WF_IDX_SHAPES(X)
 
 size_t march_idx_lds_bytes(int kind, int P, int BX, int BY, int lz)
 {
-  if (kind == OP_KIND_MASS) return mass_march_lds_bytes(P, BX, BY, lz);
+  if (kind == OP_KIND_MASS) return mass_march_lds_bytes(P, P + 1, BX, BY, lz);
   if (march_idx_uses_ks(P)) return march_ks_lds_bytes(P, BX, BY, lz, true);
   return march_idx_static_lds_bytes(P, BX, BY) + (size_t)(P * lz + 1) * column_dims(P, BX, BY).TP * sizeof(int32_t);
 }

@@ -133,7 +133,8 @@ def precompute_geometric_data(mesh, p: int, use_fabs: bool = True, clamp: bool =
 def make_tuning(tuning) -> "_lib.Tuning | None":
     """wf_tuning from a dict (kernel=, variant=, lz=, lz0=, block=(bx, by, bz), keep_cell_order=, orient=, geometry=,
     metric=, update=) or None.  `kernel` is a WF_KERNEL_FORCE_* value or one of "batch", "box_block", "mass_any",
-    "elementwise", "march"; `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"; `metric` a
+    "elementwise", "march", "mass_march" (dense mass with a rectangular 1-D table: the marching kernel on request; raises
+    WavehipError for a (degree, rule points) pair that is not compiled and on any other operator); `geometry` a wf_geometry_mode value or one of "auto", "per_point", "per_cell"; `metric` a
     wf_metric_mode value or one of "auto", "full", "axes"; `update` a wf_update_mode value or one of "auto", "atomic",
     "owner".  {"update": "owner"} gives the owner-computes separable box stiffness kernel (per-cell geometry, no atomics,
     bitwise reproducible) on a rectilinear box at degrees 1 to 7 and raises WavehipError on any other mesh; `variant`
@@ -145,7 +146,7 @@ def make_tuning(tuning) -> "_lib.Tuning | None":
         return tuning
     names = {"auto": 0, "batch": _lib.WF_KERNEL_FORCE_BATCH, "box_block": _lib.WF_KERNEL_FORCE_BOX_BLOCK,
              "mass_any": _lib.WF_KERNEL_FORCE_MASS_ANY, "elementwise": _lib.WF_KERNEL_FORCE_ELEMENTWISE,
-             "march": _lib.WF_KERNEL_FORCE_MARCH}
+             "march": _lib.WF_KERNEL_FORCE_MARCH, "mass_march": _lib.WF_KERNEL_FORCE_MASS_MARCH}
     t = _lib.Tuning()
     k = tuning.get("kernel", 0)
     t.kernel = names[k] if isinstance(k, str) else int(k)
