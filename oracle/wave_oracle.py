@@ -411,12 +411,16 @@ class StiffnessOperator:
 
 
 def stiffness_apply_sumfact(mesh: BoxMesh, G: np.ndarray, c0: float, x: np.ndarray, y: np.ndarray,
-                            fast: bool = False):
-    """Sum-factorised CPU variant (BASELINE.md 'Baseline B'), informative."""
+                            fast: bool = False, cells=None):
+    """Sum-factorised CPU variant (BASELINE.md 'Baseline B'), informative.  cells = (begin, end) restricts the
+    sum to that range of the mesh's cells, as StiffnessOperator.__call__ does; G stays indexed by the mesh's cells."""
     _, _, _, D = tabulate_1d_gll(mesh.p)
     D = np.ascontiguousarray(D)
     L = lib_fast() if fast else lib()
-    L.oracle_stiffness_apply_sumfact(0, mesh.ncells, mesh.p + 1, _ip(mesh.dofmap), _dp(G), _dp(D),
+    c_begin, c_end = (0, mesh.ncells) if cells is None else cells
+    if not 0 <= c_begin <= c_end <= mesh.ncells:
+        raise ValueError("cells must be a range inside the mesh")
+    L.oracle_stiffness_apply_sumfact(c_begin, c_end, mesh.p + 1, _ip(mesh.dofmap), _dp(G), _dp(D),
                                      c0, _dp(x), _dp(y))
 
 
