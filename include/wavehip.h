@@ -162,7 +162,7 @@ typedef enum {
  *                        (two creations give a bitwise equal m).
  *   wf_op_create_box*    builds the box's lexicographic dofmap and vertex map on the host and is then that dofmap operator
  *                        (wf_op_info_t.structured stays 1).
- *   wf_op_create_dense_simplex   WF_ERR_UNSUPPORTED.
+ *   wf_op_create_dense_simplex, wf_op_create_dense_simplex_mass   WF_ERR_UNSUPPORTED.
  * Any non-default wf_tuning field other than keep_cell_order is WF_ERR_INVALID together with the flag (there is no kernel
  * to choose); wf_op_set_ghost_faces / _dofs are WF_ERR_UNSUPPORTED as for the batch kernels.  The operator owns the
  * scratch v[ncells * nd] (counted in device_bytes): ONE APPLY PER OPERATOR MAY BE IN FLIGHT AT A TIME -- applies of one
@@ -181,8 +181,9 @@ typedef enum {
   WF_KERNEL_MASS_DENSE_ANY = 6, /* k_mass_dense: any tensor rule (nq1 != P+1 allowed)                       */
   WF_KERNEL_DENSE_SIMPLEX = 7,  /* k_stiffness_dense: MFMA fp64, affine simplices                           */
   WF_KERNEL_ELEMENTWISE = 8,    /* k_mass_lumped: one thread per element-local dof                          */
-  WF_KERNEL_CELLS_ORDERED = 9   /* WF_FLAG_ORDERED: cell batches store element-local results, one thread per y
+  WF_KERNEL_CELLS_ORDERED = 9,  /* WF_FLAG_ORDERED: cell batches store element-local results, one thread per y
                                    entry sums them in a fixed order (ordered.hip)                           */
+  WF_KERNEL_DENSE_SIMPLEX_MASS = 10 /* k_mass_dense_simplex: MFMA fp64, affine simplices, y += s_c A x       */
 } wf_kernel_id;
 
 /* ... and the explicit, thread-safe way to select one (tests, tuning runs).  Every field 0 =
@@ -331,6 +332,34 @@ typedef struct {
   int flags;                    /* WF_FLAG_NO_CLAMP; WF_FLAG_ORDERED: WF_ERR_UNSUPPORTED */
 } wf_dense_desc;
 int wf_op_create_dense_simplex(const wf_dense_desc* desc, wf_op** out);
+
+/* Dense (non-tensor-product) mass operator on affine simplex cells: the reference's MassOperator
+ * (common/cuda/mass.hpp:18-107, y_e = Phi^T (det J w .* (Phi x_e))) fed with an arbitrary dense table, as it would
+ * be for a tetrahedral space.  h_phi is the table of basis VALUES at the quadrature points, [nq][nd], taken as it
+ * is (mass.hpp tabulates values: there is no -1/0/1 clamp); h_weights [nq]; cells are affine tetrahedra given by
+ * h_geom_dofmap [ncells][4].  det J is constant on an affine cell, so the operator is applied as
+ *   y[dofmap[c][a]] += s_c sum_b A[a][b] x[dofmap[c][b]],   A = Phi^T diag(w) Phi,
+ * with A formed once on the host (long double, rounded once) and s_c = |det J_c|, or det J_c with its sign under
+ * WF_FLAG_NO_FABS (mass.hpp:35-39).  The cost of an apply does not depend on nq: any nq >= 1 is accepted.
+ * Compiled shapes: the tile counts ceil(nd/4), ceil(nd/16) of Lagrange P1..P4 (nd = 4, 10, 20, 35), which serve
+ * nd = 1..4, 9..12, 17..20 and 33..36; every other nd is WF_ERR_UNSUPPORTED at creation.  A degenerate cell (det J
+ * zero or not finite) is WF_ERR_INVALID at creation, wf_last_error names the cell.  All argument checks precede the
+ * first device call.  wf_op_info_t: kind WF_OP_MASS_DENSE, degree 0, kernel WF_KERNEL_DENSE_SIMPLEX_MASS, flops by the
+ * reference's model 4 ncells nq nd (mass.hpp:71), alg_bytes = ncells (8 + 4 nd) + 16 ndofs.  wf_op_apply_part (any
+ * part but WF_PART_ALL) and wf_op_set_ghost_* are WF_ERR_UNSUPPORTED: a batch kernel.  wf_cg takes the handle as it is
+ * (M a = b, the problem of demo/gpu_cg on a tetrahedral space). */
+typedef struct {
+  int nd, nq;                   /* dofs and quadrature points per cell            */
+  int ncells, ndofs;
+  const int32_t* h_dofmap;      /* [ncells][nd]                                   */
+  const double* h_phi;          /* [nq][nd], not clamped                          */
+  const double* h_weights;      /* [nq]                                           */
+  int nverts;
+  const double* h_xverts;       /* [nverts][3]                                    */
+  const int32_t* h_geom_dofmap; /* [ncells][4]                                    */
+  int flags;                    /* WF_FLAG_NO_FABS; WF_FLAG_ORDERED: WF_ERR_UNSUPPORTED; any other bit: WF_ERR_INVALID */
+} wf_dense_mass_desc;
+int wf_op_create_dense_simplex_mass(const wf_dense_mass_desc* desc, wf_op** out);
 
 /* op(x, y) / op.apply(x, y): y += A x.  operators.hpp:183, mass.hpp:76,
  * spectral_mass.hpp:84. */

@@ -111,14 +111,28 @@ def bench_tet(dev):
     t1 = time.time()
     op = tet.TetStiffnessOperator(V, p)
     t2 = time.time()
+    mass = tet.TetMassOperator(V, p)           # rule of degree 2p = 8: 125 points
+    t3 = time.time()
     N = V.ndofs
     x = torch.rand(N, dtype=torch.float64, device=dev)
     y = torch.zeros(N, dtype=torch.float64, device=dev)
-    ms = timeit(lambda: op(x, y))
+    # the two operators alternately, TET_ROUNDS times (default 5): the median and the spread of the rounds
+    rounds = int(os.environ.get("TET_ROUNDS", "5"))
+    ms_k, ms_m = [], []
+    for _ in range(rounds):
+        ms_k.append(timeit(lambda: op(x, y)))
+        ms_m.append(timeit(lambda: mass(x, y)))
+    ms = float(np.median(ms_k))
     report(f"tet P{p} dense stiffness (MFMA f64 16x16x4), Kuhn box {n}^3 cubes", ms, op.alg_bytes(), N,
            {"cells": V.ncells, "ndofs": N, "TFLOPs_dense_model": round(op.flops() / ms / 1e9, 2),
             "frac_of_f64_mfma_peak_78.6TF": round(op.flops() / ms / 1e9 / 78.6, 3),
-            "mesh_s": round(t1 - t0, 2), "setup_s": round(t2 - t1, 2)})
+            "ms_rounds": [round(v, 4) for v in ms_k], "mesh_s": round(t1 - t0, 2), "setup_s": round(t2 - t1, 2)})
+    ms = float(np.median(ms_m))
+    report(f"tet P{p} dense mass (MFMA f64 16x16x4, A = Phi^T W Phi), Kuhn box {n}^3 cubes, {mass.num_quads()}-point rule", ms,
+           mass.alg_bytes(), N,
+           {"cells": V.ncells, "ndofs": N, "kernel": mass.kernel, "alg_bytes": mass.alg_bytes(),
+            "ms_rounds": [round(v, 4) for v in ms_m], "ms_over_stiffness": round(ms / float(np.median(ms_k)), 3),
+            "setup_s": round(t3 - t2, 2)})
 
 
 def bench_tsmm(dev):

@@ -45,6 +45,15 @@ class DenseDesc(ctypes.Structure):
     ]
 
 
+class DenseMassDesc(ctypes.Structure):
+    _fields_ = [
+        ("nd", c_int), ("nq", c_int), ("ncells", c_int), ("ndofs", c_int),
+        ("h_dofmap", POINTER(c_int32)), ("h_phi", POINTER(c_double)), ("h_weights", POINTER(c_double)),
+        ("nverts", c_int), ("h_xverts", POINTER(c_double)), ("h_geom_dofmap", POINTER(c_int32)),
+        ("flags", c_int),
+    ]
+
+
 class OpInfo(ctypes.Structure):
     _fields_ = [
         ("kind", c_int), ("degree", c_int), ("num_cells", c_int), ("num_dofs_cell", c_int),
@@ -85,7 +94,8 @@ WF_COMM_ID_BYTES = 128
 WF_SUM, WF_MAX = 0, 1
 WF_UPDATER_DEFAULT, WF_UPDATER_INLINE, WF_UPDATER_CHAIN_ON_SIDE = 0, 1, 2
 (WF_KERNEL_NONE, WF_KERNEL_MARCH_BOX, WF_KERNEL_MARCH_IDX, WF_KERNEL_BATCH_UNIQUE, WF_KERNEL_BOX_BLOCK, WF_KERNEL_DIAGONAL,
- WF_KERNEL_MASS_DENSE_ANY, WF_KERNEL_DENSE_SIMPLEX, WF_KERNEL_ELEMENTWISE, WF_KERNEL_CELLS_ORDERED) = range(10)
+ WF_KERNEL_MASS_DENSE_ANY, WF_KERNEL_DENSE_SIMPLEX, WF_KERNEL_ELEMENTWISE, WF_KERNEL_CELLS_ORDERED,
+ WF_KERNEL_DENSE_SIMPLEX_MASS) = range(11)
 (WF_KERNEL_AUTO, WF_KERNEL_FORCE_BATCH, WF_KERNEL_FORCE_BOX_BLOCK, WF_KERNEL_FORCE_MASS_ANY, WF_KERNEL_FORCE_ELEMENTWISE,
  WF_KERNEL_FORCE_MARCH, WF_KERNEL_FORCE_MASS_MARCH) = range(7)
 WF_OP_STIFFNESS, WF_OP_MASS_LUMPED, WF_OP_MASS_DENSE = 0, 1, 2
@@ -122,6 +132,7 @@ SIGNATURES = {
                                        POINTER(c_void_p)]),
     "wf_op_set_ghost_dofs": (c_int, [c_void_p, _ip, c_int32]),
     "wf_op_create_dense_simplex": (c_int, [POINTER(DenseDesc), POINTER(c_void_p)]),
+    "wf_op_create_dense_simplex_mass": (c_int, [POINTER(DenseMassDesc), POINTER(c_void_p)]),
     "wf_op_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_op_set_ghost_faces": (c_int, [c_void_p, c_int, c_int, c_int]),
     "wf_op_apply_part": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

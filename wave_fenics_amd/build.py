@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libwavehip.so")
 SOURCES = [
     "tables.cpp", "mesh_io.cpp", "generic_plan.cpp", "function_space.cpp", "markers.cpp",
     "kernels.hip", "stiffness_march.hip", "stiffness_march_owner.hip", "stiffness_march_idx.hip", "stiffness_march_ks.hip",
-    "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "tsmm.hip", "vector_kernels.hip", "comm.hip", "cg.hip", "api.hip",
+    "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "mass_dense_simplex.hip", "tsmm.hip", "vector_kernels.hip", "comm.hip", "cg.hip", "api.hip",
 ]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "stiffness_core.h"),
            os.path.join(CSRC, "march_column.h"),

@@ -27,6 +27,7 @@ enum class OpKernel : int {
   mass_column,           // dense mass, square table, column threads on batch-unique dof lists
   mass_any,              // dense mass, any tensor rule
   dense_simplex,         // dense simplex operator (stiffness_dense.hip)
+  dense_simplex_mass,    // dense simplex mass (mass_dense_simplex.hip)
   ordered_stiffness,     // WF_FLAG_ORDERED (ordered.hip): cell batches store to v[slot], one thread per y entry sums its run
   ordered_mass,          // the same for the dense mass, any tensor rule
   ordered_lumped,        // the same for the lumped mass in the reference's sequence
@@ -77,6 +78,7 @@ struct wf_op {
   int plan_patterns = 0;
   DenseOpData* dense = nullptr;   // dense simplex operator (stiffness_dense.hip)
   int dense_clamp = 1;
+  DenseMassData* dense_mass = nullptr;   // dense simplex mass (mass_dense_simplex.hip)
   size_t device_bytes = 0;
   int plan_reoriented = 0;
   double plan_fill = 0.0;
@@ -136,6 +138,7 @@ void free_op(wf_op* op)
   (void)hipFree(op->plan.d_item_layers);
   (void)hipFree(op->plan.d_pat_off);
   dense_free(op->dense);
+  dense_mass_free(op->dense_mass);
   delete op;
 }
 
@@ -1466,6 +1469,40 @@ int wf_op_create_dense_simplex(const wf_dense_desc* desc, wf_op** out)
   return WF_OK;
 }
 
+int wf_op_create_dense_simplex_mass(const wf_dense_mass_desc* desc, wf_op** out)
+{
+  // every check, dense_mass_setup's included, precedes the first HIP call
+  WF_REQUIRE(desc && out, "wf_op_create_dense_simplex_mass: null argument");
+  *out = nullptr;
+  WF_REQUIRE(desc->nd > 0 && desc->nq > 0 && desc->ncells >= 0 && desc->ndofs >= 0 && desc->nverts >= 0,
+             "wf_op_create_dense_simplex_mass: bad sizes (nd, nq, ncells, ndofs, nverts)");
+  if (desc->flags & WF_FLAG_ORDERED) {
+    set_error("wf_op_create_dense_simplex_mass: WF_FLAG_ORDERED is not implemented for the dense simplex mass (its "
+              "persistent MFMA kernel adds with atomics)");
+    return WF_ERR_UNSUPPORTED;
+  }
+  if (desc->flags & ~(WF_FLAG_NO_FABS | WF_FLAG_ORDERED)) {
+    set_error("wf_op_create_dense_simplex_mass: unknown flag bit in flags = " + std::to_string(desc->flags)
+              + " (the operator takes WF_FLAG_NO_FABS only)");
+    return WF_ERR_INVALID;
+  }
+  WF_REQUIRE(desc->h_dofmap && desc->h_phi && desc->h_weights && desc->h_xverts && desc->h_geom_dofmap,
+             "wf_op_create_dense_simplex_mass: null array (h_dofmap, h_phi, h_weights, h_xverts, h_geom_dofmap)");
+  for (size_t e = 0; e < (size_t)desc->ncells * desc->nd; ++e)
+    WF_REQUIRE(desc->h_dofmap[e] >= 0 && desc->h_dofmap[e] < desc->ndofs, "wf_op_create_dense_simplex_mass: dofmap entry out of range");
+  for (size_t e = 0; e < (size_t)desc->ncells * 4; ++e)
+    WF_REQUIRE(desc->h_geom_dofmap[e] >= 0 && desc->h_geom_dofmap[e] < desc->nverts,
+               "wf_op_create_dense_simplex_mass: vertex index out of range");
+  OpPtr op = new_op(WF_OP_MASS_DENSE, 0, desc->nd, desc->nq, desc->ncells, desc->ndofs, 0.0, nullptr);
+  op->kernel = OpKernel::dense_simplex_mass;
+  int rc = dense_mass_setup(desc->nd, desc->nq, desc->ncells, desc->h_dofmap, desc->h_phi, desc->h_weights, desc->h_xverts,
+                            desc->h_geom_dofmap, fabs_flag(desc->flags), &op->dense_mass);
+  if (rc != WF_OK) return rc;
+  op->device_bytes = dense_mass_bytes(op->dense_mass);
+  *out = op.release();
+  return WF_OK;
+}
+
 // The one place that maps the kernel choice to a launch.  wf_op_apply runs every work item (d_items null, lz0 = lz);
 // wf_op_apply_part the items of one part of a marching operator, whose first z segment has lz0 layers.
 static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitems, const double* d_x, double* d_y, hipStream_t s)
@@ -1503,6 +1540,7 @@ static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitem
       return launch_mass_dense(op->P, op->nq1, op->ncells, op->d_dofmap, op->d_uoff, op->d_uniq, op->d_loc, op->unique_cb,
                                op->d_phi1, op->d_detJ, d_x, d_y, s);
     case OpKernel::dense_simplex: return launch_stiffness_dense(op->dense, op->coeff, op->dense_clamp, d_x, d_y, s);
+    case OpKernel::dense_simplex_mass: return launch_mass_dense_simplex(op->dense_mass, d_x, d_y, s);
     case OpKernel::ordered_stiffness:
     case OpKernel::ordered_mass:
     case OpKernel::ordered_lumped: {
@@ -1610,6 +1648,10 @@ int wf_op_apply_part(wf_op* op, const double* d_x, double* d_y, int part, void* 
   WF_REQUIRE(op && d_x && d_y, "wf_op_apply_part: null argument");
   if (part == WF_PART_ALL) return wf_op_apply(op, d_x, d_y, stream);
   WF_REQUIRE(part >= WF_PART_INTERIOR && part <= WF_PART_INTERIOR_B, "wf_op_apply_part: unknown part");
+  if (op->kernel == OpKernel::dense_simplex_mass) {
+    set_error("wf_op_apply_part: the dense simplex mass runs a batch kernel (no work items to split)");
+    return WF_ERR_UNSUPPORTED;
+  }
   if (!op->have_parts) {
     set_error("wf_op_apply_part: call wf_op_set_ghost_dofs / wf_op_set_ghost_faces first");
     return WF_ERR_INVALID;
@@ -1650,6 +1692,7 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
     case OpKernel::mass_column: kernel = WF_KERNEL_BATCH_UNIQUE; break;
     case OpKernel::mass_any: kernel = WF_KERNEL_MASS_DENSE_ANY; break;
     case OpKernel::dense_simplex: kernel = WF_KERNEL_DENSE_SIMPLEX, geometry = WF_GEOMETRY_PER_CELL; break;
+    case OpKernel::dense_simplex_mass: kernel = WF_KERNEL_DENSE_SIMPLEX_MASS; break;
     case OpKernel::ordered_stiffness: kernel = WF_KERNEL_CELLS_ORDERED, geometry = WF_GEOMETRY_PER_POINT, update = WF_UPDATE_ORDERED; break;
     case OpKernel::ordered_mass:
     case OpKernel::ordered_lumped: kernel = WF_KERNEL_CELLS_ORDERED, update = WF_UPDATE_ORDERED; break;
@@ -1663,12 +1706,15 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   info->num_quads = op->nq;
   info->ndofs = op->ndofs;
   info->structured = op->structured;
-  // mass.hpp:71; dense skernel: SURVEY 8a3
+  // mass.hpp:71; dense skernel: SURVEY 8a3.  (The dense simplex mass is reported by the reference's model too; its
+  // collapsed kernel executes 2 nd^2 per cell, whatever nq.)
   info->flops = (dense ? 12.0 : 4.0) * op->ncells * (double)op->nq * op->nd;
   if (geometry == WF_GEOMETRY_PER_CELL)
     info->alg_bytes = (double)op->ncells * (48.0 + 4.0 * op->nd) + 16.0 * op->ndofs;   // one G per cell
   else if (geometry == WF_GEOMETRY_PER_POINT)
     info->alg_bytes = (double)op->ncells * (48.0 * op->nq + 4.0 * op->nd) + 16.0 * op->ndofs;
+  else if (op->kernel == OpKernel::dense_simplex_mass)
+    info->alg_bytes = (double)op->ncells * (8.0 + 4.0 * op->nd) + 16.0 * op->ndofs;   // one scale per affine cell
   else if (op->kernel == OpKernel::diagonal)
     info->alg_bytes = 24.0 * op->ndofs;   // pre-assembled diagonal: read m, x, y + write y (SURVEY 8d counts 24)
   else

@@ -60,8 +60,7 @@ __device__ __forceinline__ double clamp101d(double v)
 // distinct 8-byte banks: rows pi(.) KP cover all even bank pairs, and the two rows of a half wave
 // in the second product are 8 KP = 16 (mod 32) doubles apart.  (KP = 4 KT + 1 with rows in natural
 // order had 2-way conflicts on a third of the lanes in both products.)
-__host__ __device__ constexpr int dense_pitch(int KT) { return 4 * KT + 2; }
-__device__ __forceinline__ int dense_row_perm(int j) { return (j >> 1) + 8 * (j & 1); }
+// (dense_pitch and dense_row_perm are in common.h: mass_dense_simplex.hip stores its matrix the same way)
 // NU: unique dofs of a batch per thread (numax <= NU * 64 NW), a compile-time bound for the
 // register-staged gather of the NEXT batch.
 // XR: output rows past the last whole 16-row tile that are NOT given an MFMA tile of their own
@@ -402,17 +401,6 @@ void dense_free(DenseOpData* d)
   delete d;
 }
 
-template <typename Tp>
-static int up(Tp** p, const std::vector<Tp>& h, size_t* total)
-{
-  *p = nullptr;
-  if (h.empty()) return WF_OK;
-  WF_HIP_CHECK(hipMalloc((void**)p, h.size() * sizeof(Tp)));
-  WF_HIP_CHECK(hipMemcpy(*p, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
-  *total += h.size() * sizeof(Tp);
-  return WF_OK;
-}
-
 // Compiled shapes (QT, KT, DT, XR): Lagrange P1..P4 on the tetrahedron with the m = p Gauss-Jacobi
 // rule, (nd, nq) = (4,1) (10,8) (20,27) (35,64), plus P4 with the m = 3 rule.  The XR = 0 form of a
 // shape serves every other (nd, nq) with the same tile counts.
@@ -433,6 +421,48 @@ static bool dense_shape_compiled(int QT, int KT, int DT)
   WF_DENSE_SHAPES(WF_DENSE_HAS)
 #undef WF_DENSE_HAS
   return false;
+}
+
+// Per-batch gather/scatter plan of the dense simplex kernels (this file and mass_dense_simplex.hip): for every batch of
+// NCB consecutive cells the sorted list of its distinct dofs (uniq, offsets uoff) and, packed two to a word in the
+// kernels' operand order, the position of every element-local dof in that list:
+// locP[b][ks / 2][lg][cell] holds the local index of dof 4 ks + lg in bits 16 (ks & 1) .. 16 (ks & 1) + 15.
+int dense_batch_plan(int nd, int KT, int NCB, int ncells, const int32_t* dofmap, DenseBatchPlan* plan)
+{
+  const int nbatch = (ncells + NCB - 1) / NCB;
+  const int KT2 = (KT + 1) / 2;
+  plan->locP.assign((size_t)nbatch * KT2 * 4 * NCB, 0);
+  plan->uoff.assign(nbatch + 1, 0);
+  plan->uniq.clear();
+  std::vector<uint32_t>& locP = plan->locP;
+  std::vector<int32_t>& uoff = plan->uoff;
+  std::vector<int32_t>& uniq = plan->uniq;
+  uniq.reserve((size_t)ncells * nd / 2);
+  std::vector<int32_t> tmp;
+  int numax = 0;
+  for (int b = 0; b < nbatch; ++b) {
+    const int c0 = b * NCB, nc = std::min(NCB, ncells - c0);
+    tmp.assign(dofmap + (size_t)c0 * nd, dofmap + (size_t)(c0 + nc) * nd);
+    std::sort(tmp.begin(), tmp.end());
+    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+    const int nu = (int)tmp.size();
+    if (nu > 65535) {
+      set_error("dense_setup: more than 65535 unique dofs in a batch");
+      return WF_ERR_UNSUPPORTED;
+    }
+    numax = std::max(numax, nu);
+    for (int c = 0; c < nc; ++c)
+      for (int k = 0; k < nd; ++k) {
+        const int32_t g = dofmap[(size_t)(c0 + c) * nd + k];
+        const int u = (int)(std::lower_bound(tmp.begin(), tmp.end(), g) - tmp.begin());
+        const int ks = k / 4, lg = k % 4;
+        locP[(((size_t)b * KT2 + ks / 2) * 4 + lg) * NCB + c] |= (uint32_t)u << (16 * (ks & 1));
+      }
+    uniq.insert(uniq.end(), tmp.begin(), tmp.end());
+    uoff[b + 1] = (int32_t)uniq.size();
+  }
+  plan->numax = std::max(numax, 1);
+  return WF_OK;
 }
 
 // Host setup: padded table, per-cell affine geometry C = |det J| K K^T, per-batch
@@ -495,34 +525,9 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
       return WF_ERR_INVALID;
     }
   }
-  const int KT2 = (d->KT + 1) / 2;
-  std::vector<uint32_t> locP((size_t)nbatch * KT2 * 4 * NCB, 0);
-  std::vector<int32_t> uoff(nbatch + 1, 0), uniq;
-  uniq.reserve((size_t)ncells * nd / 2);
-  std::vector<int32_t> tmp;
-  int numax = 0;
-  for (int b = 0; b < nbatch; ++b) {
-    const int c0 = b * NCB, nc = std::min(NCB, ncells - c0);
-    tmp.assign(dofmap + (size_t)c0 * nd, dofmap + (size_t)(c0 + nc) * nd);
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    const int nu = (int)tmp.size();
-    if (nu > 65535) {
-      set_error("dense_setup: more than 65535 unique dofs in a batch");
-      return WF_ERR_UNSUPPORTED;
-    }
-    numax = std::max(numax, nu);
-    for (int c = 0; c < nc; ++c)
-      for (int k = 0; k < nd; ++k) {
-        const int32_t g = dofmap[(size_t)(c0 + c) * nd + k];
-        const int u = (int)(std::lower_bound(tmp.begin(), tmp.end(), g) - tmp.begin());
-        const int ks = k / 4, lg = k % 4;
-        locP[(((size_t)b * KT2 + ks / 2) * 4 + lg) * NCB + c] |= (uint32_t)u << (16 * (ks & 1));
-      }
-    uniq.insert(uniq.end(), tmp.begin(), tmp.end());
-    uoff[b + 1] = (int32_t)uniq.size();
-  }
-  d->numax = std::max(numax, 1);
+  DenseBatchPlan plan;
+  if (int rc = dense_batch_plan(nd, d->KT, NCB, ncells, dofmap, &plan)) return rc;
+  d->numax = plan.numax;
   (void)ndofs;
   // batches in which the clamp is not the identity
   std::vector<uint8_t> clampb(nbatch, 0);
@@ -536,13 +541,13 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
     if (hit) clampb[c / NCB] = 1;
   }
   int rc;
-  if ((rc = up(&d->d_T, T, &d->bytes)) != WF_OK) return rc;
-  if ((rc = up(&d->d_w, w, &d->bytes)) != WF_OK) return rc;
-  if ((rc = up(&d->d_C, C, &d->bytes)) != WF_OK) return rc;
-  if ((rc = up(&d->d_locP, locP, &d->bytes)) != WF_OK) return rc;
-  if ((rc = up(&d->d_uoff, uoff, &d->bytes)) != WF_OK) return rc;
-  if ((rc = up(&d->d_uniq, uniq, &d->bytes)) != WF_OK) return rc;
-  if ((rc = up(&d->d_clampb, clampb, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_T, T, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_w, w, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_C, C, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_locP, plan.locP, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_uoff, plan.uoff, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_uniq, plan.uniq, &d->bytes)) != WF_OK) return rc;
+  if ((rc = upload_vec(&d->d_clampb, clampb, &d->bytes)) != WF_OK) return rc;
   *out = d.release();
   return WF_OK;
 }

@@ -169,7 +169,8 @@ GEOMETRY_MODES = {"auto": 0, "per_point": 1, "per_cell": 2}
 METRIC_MODES = {"auto": 0, "full": 1, "axes": 2}
 UPDATE_MODES = {"auto": 0, "atomic": 1, "owner": 2}
 KERNEL_NAMES = {0: "none", 1: "march_box", 2: "march_idx", 3: "batch_unique", 4: "box_block", 5: "diagonal",
-                6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise", 9: "cells_ordered"}
+                6: "mass_dense_any", 7: "dense_simplex", 8: "elementwise", 9: "cells_ordered",
+                10: "dense_simplex_mass"}
 
 
 class _Operator:

@@ -1,5 +1,6 @@
 """Tetrahedral (non-tensor-product) operator path: host-side tabulation, Kuhn box
-mesh and the dense MFMA stiffness operator (csrc/stiffness_dense.hip).
+mesh, the dense MFMA stiffness operator (csrc/stiffness_dense.hip) and the dense
+MFMA mass operator (csrc/mass_dense_simplex.hip).
 
 The reference has no tetrahedral operator class (its StiffnessOperator fixes
 `_ndofs = (bdegree+1)^3`, common/operators.hpp:154); its element kernel and cell
@@ -18,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import DenseDesc, check, lib
+from ._lib import DenseDesc, DenseMassDesc, check, lib
 from .box import create_box
 from .operators import _Operator, _dp, _ip
 
@@ -137,4 +138,32 @@ class TetStiffnessOperator(_Operator):
         d.c0, d.flags = c0, flags
         self._h = c_void_p()
         check(lib().wf_op_create_dense_simplex(ctypes.byref(d), ctypes.byref(self._h)))
+        self._info()
+
+
+class TetMassOperator(_Operator):
+    """y += M x on affine tetrahedra through wf_op_create_dense_simplex_mass: the reference's MassOperator
+    (common/cuda/mass.hpp:18-107) with the tetrahedral table of basis values, collapsed to one matrix
+    A = Phi^T diag(w) Phi and one scale |det J| per cell, on v_mfma_f64_16x16x4_f64.  The rule is the collapsed
+    Gauss-Jacobi rule of degree `qdegree` (default 2 * degree: exact for the mass matrix of affine cells); the table
+    is taken as tabulated, without the -1/0/1 clamp.  `flags`: WF_FLAG_NO_FABS keeps the sign of det J."""
+
+    def __init__(self, V: TetSpace, degree: int, qdegree: int | None = None, flags: int = 0):
+        super().__init__()
+        q = 2 * degree if qdegree is None else qdegree
+        X, W = tet_quadrature((q + 2) // 2)
+        phi, _ = tabulate_tet(degree, X)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        W = np.ascontiguousarray(W)
+        d = DenseMassDesc()
+        d.nd, d.nq = phi.shape[1], phi.shape[0]
+        d.ncells, d.ndofs = V.ncells, V.ndofs
+        dm = np.ascontiguousarray(V.dofmap, dtype=np.int32)
+        x = np.ascontiguousarray(V.x, dtype=np.float64)
+        gd = np.ascontiguousarray(V.geom_dofmap, dtype=np.int32)
+        d.h_dofmap, d.h_phi, d.h_weights = _ip(dm), _dp(phi), _dp(W)
+        d.nverts, d.h_xverts, d.h_geom_dofmap = x.shape[0], _dp(x), _ip(gd)
+        d.flags = flags
+        self._h = c_void_p()
+        check(lib().wf_op_create_dense_simplex_mass(ctypes.byref(d), ctypes.byref(self._h)))
         self._info()
