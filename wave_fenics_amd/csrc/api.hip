@@ -59,6 +59,7 @@ struct wf_op {
   double* d_D = nullptr;
   double* d_phi1 = nullptr;
   double* d_mdiag = nullptr;
+  bool diag_named_only = false;   // the vectors hold dofs no cell names: the diagonal apply leaves them alone
   // batch-unique gather/scatter lists of the batch kernels (null: the kernel scatters element-wise)
   int32_t* d_uoff = nullptr;
   int32_t* d_uniq = nullptr;
@@ -632,6 +633,16 @@ bool mass_collocated(const wf_op_desc* desc, int n)
   return true;
 }
 
+// Does the caller keep dofs in its vectors that no cell names (the dofs of deleted cells, padding)?  The gather /
+// scatter kernels never touch them; the pre-assembled diagonal has m = 0 there, and y += m .* x would still turn
+// whatever x holds in such an entry -- uninitialised memory, NaN -- into y.
+bool has_unnamed_dofs(const wf_op_desc* desc, int nd)
+{
+  std::vector<char> named((size_t)desc->ndofs, 0);
+  for (size_t e = 0; e < (size_t)desc->ncells * nd; ++e) named[desc->h_dofmap[e]] = 1;
+  return std::find(named.begin(), named.end(), 0) != named.end();
+}
+
 int create_mass_diagonal(const wf_op_desc* desc, const CallerFrame& fr, wf_op* op)
 {
   const int n = op->n, nd = op->nd;
@@ -653,6 +664,7 @@ int create_mass_diagonal(const wf_op_desc* desc, const CallerFrame& fr, wf_op* o
     }
   if ((rc = dev_upload(&op->d_mdiag, md.data(), md.size(), &op->device_bytes)) != WF_OK) return rc;
   op->nq1 = n;
+  op->diag_named_only = has_unnamed_dofs(desc, nd);
   op->kernel = OpKernel::diagonal;
   return WF_OK;
 }
@@ -1009,6 +1021,7 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
   op->device_bytes -= ncells * nd * sizeof(double);
   (void)hipFree(op->d_detJ);
   op->d_detJ = nullptr;
+  op->diag_named_only = has_unnamed_dofs(desc, nd);
   op->kernel = OpKernel::diagonal;
   return WF_OK;
 }
@@ -1532,7 +1545,9 @@ static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitem
       return launch_mass_lumped_u(op->ncells, op->nd, op->unique_cb, op->d_uoff, op->d_uniq, op->d_loc, op->d_detJ, d_x, d_y, s);
     case OpKernel::lumped_elementwise:
       return launch_mass_lumped((int64_t)op->ncells * op->nd, op->d_dofmap, op->d_detJ, d_x, d_y, s);
-    case OpKernel::diagonal: return wf_pointwise_mult_add(op->ndofs, op->d_mdiag, d_x, d_y, s);
+    case OpKernel::diagonal:
+      if (op->diag_named_only) return launch_diagonal_named(op->ndofs, op->d_mdiag, d_x, d_y, s);
+      return wf_pointwise_mult_add(op->ndofs, op->d_mdiag, d_x, d_y, s);
     case OpKernel::mass_march: return launch_mass_march(op->P, op->nq1, op->plan, op->d_detJ, op->d_phi1, d_x, d_y, s);
     case OpKernel::mass_column:
       return launch_mass_dense_col(op->P, op->ncells, op->d_uoff, op->d_uniq, op->d_loc, op->d_phi1, op->d_detJ, d_x, d_y, s);

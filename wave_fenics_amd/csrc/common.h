@@ -247,6 +247,8 @@ size_t dense_mass_bytes(const DenseMassData* d);
 int launch_mass_dense_simplex(const DenseMassData* d, const double* d_x, double* d_y, hipStream_t s);
 int launch_mass_lumped(int64_t nentries, const int32_t* d_dofmap, const double* d_detJ, const double* d_x,
                        double* d_y, hipStream_t s);
+// y[d] += m[d] x[d] where m[d] != 0: the pre-assembled diagonal on vectors that hold dofs no cell names (m = 0 there)
+int launch_diagonal_named(int64_t n, const double* d_m, const double* d_x, double* d_y, hipStream_t s);
 int launch_mass_lumped_u(int ncells, int nd, int CB, const int32_t* d_uoff, const int32_t* d_uniq,
                          const uint16_t* d_loc, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
 int mass_dense_cells_per_batch(int mx);

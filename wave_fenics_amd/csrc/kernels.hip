@@ -794,6 +794,16 @@ __global__ void k_mass_lumped(int64_t nentries, const int32_t* __restrict__ dofm
   }
 }
 
+// the pre-assembled diagonal on vectors with entries that no cell names: m = 0 there, and those entries of x must not
+// reach y (0 * NaN) -- the gather / scatter sequence above does nothing with them.  The test is m != 0, not "named": a
+// named dof whose contributions cancel exactly (possible only without the fabs of det J) is skipped as well, which
+// leaves y as a finite x would.  One entry per thread: it runs on dofmaps with unnamed dofs only.
+__global__ void k_diagonal_named(int64_t n, const double* __restrict__ m, const double* __restrict__ x, double* __restrict__ y)
+{
+  const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (d < n && m[d] != 0.0) y[d] += m[d] * x[d];
+}
+
 // batch-unique form of the lumped mass (default): x once per unique dof, the
 // batch summed in LDS, one global atomic per unique dof
 __global__ __launch_bounds__(256) void k_mass_lumped_u(int ncells, int nd, int CB, const int32_t* __restrict__ uoff,
@@ -1257,6 +1267,14 @@ int launch_mass_lumped(int64_t nentries, const int32_t* d_dofmap, const double* 
   if (nentries == 0) return WF_OK;
   hipLaunchKernelGGL(k_mass_lumped, dim3(grid_for((size_t)nentries, 256)), dim3(256), 0, s, nentries, d_dofmap,
                      d_detJ, d_x, d_y);
+  WF_LAUNCH_CHECK();
+  return WF_OK;
+}
+
+int launch_diagonal_named(int64_t n, const double* d_m, const double* d_x, double* d_y, hipStream_t s)
+{
+  if (n <= 0) return WF_OK;
+  hipLaunchKernelGGL(k_diagonal_named, dim3(grid_for((size_t)n, 256)), dim3(256), 0, s, n, d_m, d_x, d_y);
   WF_LAUNCH_CHECK();
   return WF_OK;
 }

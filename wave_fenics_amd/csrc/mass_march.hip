@@ -43,7 +43,8 @@ WF_COLUMN_TRACE(g_mass_trace, wf_debug_mass_trace, 12, 10)
 
 // The compiled kernels X(P, M, BX, BY): the first cross-section of a pair (P, M) is its default.  Square tables
 // M = P + 1; Gauss rules of degree 2 P + 2 (M = P + 2); Basix' GLL rule of degree P + 1 where it is not square ((1, 3)
-// is also the Gauss pair).  (7, 9) does not fit a wave.
+// is also the Gauss pair).  (7, 9) does not fit a wave.  (tests/nonbox_helpers.py MASS_BLOCK copies the defaults of the
+// square and the Gauss 2 P + 2 pairs: it predicts plan_fill from them.)
 #define WF_MASS_SHAPES(X)                                                                                         \
   X(1, 2, 8, 8) X(2, 3, 7, 4) X(3, 4, 4, 4) X(4, 5, 4, 2) X(4, 5, 2, 2) X(5, 6, 2, 2) X(6, 7, 2, 2) X(6, 7, 2, 1) \
   X(7, 8, 2, 1)                                                                                                   \

@@ -258,6 +258,7 @@ static int launch_t(const MarchPlanDev& pd, const double* d_G6blk, const double*
 static bool march_idx_uses_ks(int P) { return P >= WF_IDX_KS_MINP; }
 
 // the one cross-section per degree, with BX * BY == floor(256 / n^2) cells (geometry batch layout)
+// (tests/nonbox_helpers.py STIFFNESS_BLOCK copies these: it predicts plan_fill from them)
 #define WF_IDX_SHAPES(X) X(1, 8, 8) X(2, 7, 4) X(3, 4, 4) X(4, 5, 2)
 
 void march_idx_shape(int kind, int P, int* bx, int* by)

@@ -468,6 +468,7 @@ static int launch_ks_t(const KSArgs& a, const DMat& dm, int nwg, size_t lds, hip
 // bench.py, 0.2015 vs 0.2003 ms with x and y resident in the Infinity Cache -- and 5 % faster at P2, where
 // the two halves of a k-split column get 2 and 1 levels.  The P4 5x1 / 5x2 cross-sections stay compiled as a
 // tuning option for such comparisons.)
+// (tests/nonbox_helpers.py STIFFNESS_BLOCK copies the defaults of P >= 5: it predicts plan_fill from them)
 #define WF_KS_SHAPES(X)                                                                   \
   X(4, 5, 1) X(4, 5, 2)                                                                   \
   X(5, 3, 1) X(5, 7, 1) X(5, 2, 1)                                                        \
