@@ -8,7 +8,7 @@
 //
 //   planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]]
 //            [--size N] [--degree P] [--cfl C] [--steps S] [--length L] [--dump FILE]
-//            [--periodic xyz] [--reference-order] [--markers]
+//            [--periodic xyz] [--reference-order] [--markers] [--geometry auto|per_point|per_cell]
 //
 // One process per GPU: with WORLD_SIZE > 1 in the environment (RANK, LOCAL_RANK,
 // MASTER_PORT as torchrun exports them) --size is the number of cells per edge PER
@@ -19,6 +19,8 @@
 // its own RCCL neighbour).  --reference-order runs LinearGLLOpt::rk4, the
 // reference's unfused sequence of vector operations, instead of rk4_fused.
 // --dump writes u_n then v_n of this rank (float64, local lattice order).
+// --geometry (with --mesh): how the stiffness operator stores its geometry (wf_tuning.geometry).  per_cell asks for one
+// G_c per cell -- degrees 1 to 4, every cell affine, else an error -- and prints what was built; auto is the default.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -36,6 +38,7 @@ int main(int argc, char* argv[])
   const char *mesh_file = nullptr, *grid_name = "planar3d", *tags_name = "planar3d_boundaries";
   std::array<bool, 3> periodic{false, false, false};
   bool reference_order = false, markers = false;
+  int geometry = WF_GEOMETRY_AUTO;
   for (int i = 1; i < argc; ++i) {
     auto is = [&](const char* f) { return std::strcmp(argv[i], f) == 0 && i + 1 < argc; };
     if (is("--size")) size = std::atoi(argv[++i]);
@@ -48,13 +51,17 @@ int main(int argc, char* argv[])
     else if (is("--grid")) grid_name = argv[++i];
     else if (is("--tags")) tags_name = argv[++i];
     else if (std::strcmp(argv[i], "--markers") == 0) markers = true;
+    else if (is("--geometry") && std::strcmp(argv[i + 1], "auto") == 0) ++i, geometry = WF_GEOMETRY_AUTO;
+    else if (is("--geometry") && std::strcmp(argv[i + 1], "per_point") == 0) ++i, geometry = WF_GEOMETRY_PER_POINT;
+    else if (is("--geometry") && std::strcmp(argv[i + 1], "per_cell") == 0) ++i, geometry = WF_GEOMETRY_PER_CELL;
     else if (is("--periodic")) {
       for (const char* c = argv[++i]; *c; ++c)
         if (*c >= 'x' && *c <= 'z') periodic[*c - 'x'] = true;
     } else if (std::strcmp(argv[i], "--reference-order") == 0) reference_order = true;
     else {
       std::cerr << "usage: planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]] [--size N] [--degree P] [--cfl C]"
-                   " [--steps S] [--length L] [--dump FILE] [--periodic xyz] [--reference-order] [--markers]\n";
+                   " [--steps S] [--length L] [--dump FILE] [--periodic xyz] [--reference-order] [--markers]"
+                   " [--geometry auto|per_point|per_cell]\n";
       return 2;
     }
   }
@@ -77,6 +84,8 @@ int main(int argc, char* argv[])
     if (mesh_file) {
       // ---- the reference's path: mesh + facet tags from a file (main.cpp:39-45) ----
       if (exchange) throw std::runtime_error("--mesh runs on one rank");
+      wf_tuning tuning{};
+      tuning.geometry = geometry;
       auto [mesh, tags] = wavehip::read_mesh(mesh_file, grid_name, tags_name);
       auto V = wavehip::create_functionspace(mesh, degreeOfBasis);
       auto [timeStepSize, stepPerPeriod] = wavehip::cfl_time_step(mesh, degreeOfBasis, speedOfSound, sourceFrequency, CFL);
@@ -87,7 +96,12 @@ int main(int argc, char* argv[])
       if (nsteps_override > 0) finalTime = nsteps_override * timeStepSize - 1e-13;
       int nstep = (int)((finalTime - startTime) / timeStepSize + 1);
       wavehip::LinearGLLOpt eqn(V.space(), wavehip::boundary_set(V, tags, 1), wavehip::boundary_set(V, tags, 2), degreeOfBasis,
-                                speedOfSound, sourceFrequency, pressureAmplitude);
+                                speedOfSound, sourceFrequency, pressureAmplitude, geometry != WF_GEOMETRY_AUTO ? &tuning : nullptr);
+      if (geometry == WF_GEOMETRY_PER_CELL) {
+        const wf_op_info_t info = eqn.stiffness_info();
+        std::cout << "Stiffness geometry: " << (info.geometry == WF_GEOMETRY_PER_CELL ? "per_cell" : "per_point") << ", metric "
+                  << (info.metric == WF_METRIC_AXES ? "axes" : info.metric == WF_METRIC_FULL ? "full" : "none") << std::endl;
+      }
       std::cout << "Number of steps: " << nstep << std::endl;
       std::cout << "Degrees of freedom: " << V.ndofs << std::endl;
       eqn.init();
@@ -109,6 +123,7 @@ int main(int argc, char* argv[])
       return 0;
     }
 
+    if (geometry != WF_GEOMETRY_AUTO) throw std::runtime_error("--geometry applies to --mesh (a generated box chooses its own)");
     const auto procs = wavehip::decompose3d(world);
     const double L = domainLength;
     auto part = wavehip::create_distributed_box({size, size, size}, degreeOfBasis, world, rank, {0, 0, 0},

@@ -120,6 +120,16 @@ int wf_geometry_hex(int P, int ncells, int nverts, const double* h_xverts,
 int wf_geometry_hex_rule(int ncells, int nverts, const double* h_xverts, const int32_t* h_geom_dofmap, int nq1,
                          const double* h_points1, const double* h_weights1, int use_fabs, int clamp, double* h_G,
                          double* h_detJ);
+/* Per-cell geometry of affine hexahedra and the test that decides whether a stiffness operator may store it (host
+ * only; the rule of wf_op_create_box and of wf_op_create with WF_GEOMETRY_PER_CELL).  A cell qualifies when its edge
+ * vectors along each reference axis are bitwise equal, det J is non-zero and finite, and -- with clamp -- the reference's
+ * -1/0/1 clamp changes neither a cmap derivative at the degree-P GLL points nor a component of any G_c w_i w_j w_k.
+ * h_Gc [ncells][6] = G00 G01 G02 G11 G12 G22 of G_c = J^-1 J^-T |det J| (det J signed without use_fabs; weights left
+ * out), may be NULL; it is complete when every cell qualifies.  *first_bad = -1 then, else the first cell that does not;
+ * *reason says why (0 ok, 1 not affine, 2 det J zero / not finite, 3 the clamp would take effect).  Returns WF_OK
+ * either way. */
+int wf_geometry_hex_cell(int P, int64_t ncells, int64_t nverts, const double* h_xverts, const int32_t* h_geom_dofmap,
+                         int use_fabs, int clamp, double* h_Gc, int64_t* first_bad, int* reason);
 
 /* ---- operators -----------------------------------------------------------*/
 typedef enum {
@@ -225,24 +235,33 @@ typedef struct {
   int orient;        /* lattice plan: 0 = normalise cell orientations (default), 1 = require the
                         cells to agree as given                                                     */
   int geometry;      /* box stiffness, P <= 4 marching kernel (P5 to P7: with update = OWNER only):
-                        wf_geometry_mode                                                            */
-  int metric;        /* box stiffness with per-cell geometry: wf_metric_mode                        */
+                        wf_geometry_mode.  wf_op_create, stiffness at P <= 4: PER_CELL on request
+                        only (AUTO = PER_POINT there); no effect on the mass operators              */
+  int metric;        /* stiffness with per-cell geometry (box or wf_op_create): wf_metric_mode      */
   int update;        /* box stiffness, separable (axes) form: wf_update_mode; OWNER on request at
-                        P1 to P7                                                                    */
+                        P1 to P7.  wf_op_create with PER_CELL: OWNER is WF_ERR_UNSUPPORTED          */
 } wf_tuning;
 /* How a stiffness operator stores its geometry (wf_tuning.geometry, wf_op_info_t.geometry).  A box
  * whose cells are all affine (edge vectors along each reference axis bitwise equal, det J != 0, no
  * -1/0/1 clamp taking effect) needs one G_c = J^-1 J^-T |det J| per cell instead of one G per point.
  * At P5 to P7 the only per-cell kernel is the owner form (wf_tuning.update = WF_UPDATE_OWNER); without that
- * request the k-split kernel runs on per-point geometry and PER_CELL is WF_ERR_UNSUPPORTED. */
+ * request the k-split kernel runs on per-point geometry and PER_CELL is WF_ERR_UNSUPPORTED.
+ * wf_op_create (any dofmap, the lattice-column plan, stiffness at P1 to P4) stores per-cell geometry on request only:
+ * AUTO and PER_POINT keep G per point.  PER_CELL there derives G_c from the mesh (wf_geometry_hex_cell) and adopts the
+ * plan whatever its fill; it is WF_ERR_INVALID for a cell that does not qualify (wf_last_error names it), without a mesh,
+ * or with a batch kernel hint, and WF_ERR_UNSUPPORTED at P >= 5, with h_G, with WF_UPDATE_OWNER, or on a mesh that does
+ * not tile into lattice columns. */
 typedef enum {
-  WF_GEOMETRY_AUTO = 0,       /* tuning: per cell where the mesh allows it; info: no stiffness geometry */
+  WF_GEOMETRY_AUTO = 0,       /* tuning: box: per cell where the mesh allows it; wf_op_create: per point;
+                                 info: no stiffness geometry                                            */
   WF_GEOMETRY_PER_POINT = 1,  /* G at every quadrature point (48 B each)                                */
   WF_GEOMETRY_PER_CELL = 2    /* one G_c per affine cell (48 B); tuning: WF_ERR_INVALID if not affine   */
 } wf_geometry_mode;
 /* Which form of the per-cell box kernel runs (wf_tuning.metric, wf_op_info_t.metric).  When every G_c is
  * diagonal (a rectilinear box: off-diagonals exactly 0) the cell operator separates into one 1-D operator
- * A = D^T diag(w) D per axis, which takes about half the LDS reads and FMAs of the full tensor. */
+ * A = D^T diag(w) D per axis, which takes about half the LDS reads and FMAs of the full tensor.
+ * The same holds for wf_op_create with WF_GEOMETRY_PER_CELL; diagonal is decided on every cell's G_c (a cell's own frame
+ * and the plan's frame differ by a signed permutation of the axes). */
 typedef enum {
   WF_METRIC_AUTO = 0,         /* tuning: axes where every G_c is diagonal, else full                   */
   WF_METRIC_NONE = 0,         /* info: no per-cell geometry                                            */
@@ -259,7 +278,8 @@ typedef enum {
   WF_UPDATE_AUTO = 0,         /* tuning: owner at P4, atomic at P1 to P3; P5 to P7: the k-split kernel
                                  on per-point geometry (the owner form there is on request only)       */
   WF_UPDATE_NONE = 0,         /* info: not the separable box kernel                                     */
-  WF_UPDATE_ATOMIC = 1,       /* row atomics (also the only form of the full and per-point kernels)     */
+  WF_UPDATE_ATOMIC = 1,       /* row atomics (also the only form of the full and per-point kernels, and of
+                                 the per-cell forms of wf_op_create)                                    */
   WF_UPDATE_OWNER = 2,        /* owner computes (P1 to P7); tuning: WF_ERR_UNSUPPORTED unless the axes
                                  form runs (a rectilinear box)                                          */
   WF_UPDATE_ORDERED = 3       /* info only (WF_FLAG_ORDERED operators); wf_tuning.update = 3 stays an error */
@@ -400,8 +420,8 @@ typedef struct {
   int plan_reoriented;   /* cells whose local axes the plan rotated / reflected to make them agree */
   double plan_fill;      /* cells / cell slots of the plan's columns                     */
   int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
-  int metric;            /* wf_metric_mode of the per-cell box kernel (0: none)          */
-  int update;            /* wf_update_mode of the separable box kernel (0: none); WF_UPDATE_ORDERED */
+  int metric;            /* wf_metric_mode of the per-cell kernel, box or dofmap (0: none) */
+  int update;            /* wf_update_mode of the separable kernel, box or dofmap (0: none); WF_UPDATE_ORDERED */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
 int wf_op_destroy(wf_op* op);

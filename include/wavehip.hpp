@@ -183,17 +183,19 @@ protected:
 };
 }  // namespace detail
 
-/// StiffnessOperator(V, bdegree, params) -- common/operators.hpp:137-201
+/// StiffnessOperator(V, bdegree, params) -- common/operators.hpp:137-201.  tuning: the kernel selection of wf_tuning
+/// (read during construction only), e.g. geometry = WF_GEOMETRY_PER_CELL for a mesh of affine cells at degrees 1 to 4.
 template <typename T>
 class StiffnessOperator : public detail::OpBase {
   static_assert(sizeof(T) == sizeof(double), "fp64 only");
 
 public:
-  StiffnessOperator(const Space& V, int bdegree, std::map<std::string, double>& params)
+  StiffnessOperator(const Space& V, int bdegree, std::map<std::string, double>& params, const wf_tuning* tuning = nullptr)
   {
     wf_op_desc d = base_desc(V, WF_OP_STIFFNESS, bdegree);
     auto it = params.find("c0");
     d.c0 = it == params.end() ? 1500.0 : it->second;   // operators.hpp:114
+    d.tuning = tuning;
     check(wf_op_create(&d, &_op));
   }
 };

@@ -104,9 +104,10 @@ public:
 
   /// The mesh-file path (demo/cpu_planar3d/main.cpp:39-45, common/LinearGLL.hpp:53-128): any conforming
   /// hexahedral space plus the dof sets of Gamma_1 (source) and Gamma_2 (absorbing) with their collocated
-  /// facet masses (wavehip_mesh.hpp boundary_set).  One rank.
+  /// facet masses (wavehip_mesh.hpp boundary_set).  One rank.  tuning: the wf_tuning of the stiffness operator (read
+  /// during construction only).
   LinearGLLOpt(const Space& S, const BoundarySet& gamma1, const BoundarySet& gamma2, int degreeOfBasis, double speedOfSound,
-               double sourceFrequency, double pressureAmplitude)
+               double sourceFrequency, double pressureAmplitude, const wf_tuning* tuning = nullptr)
   {
     set_parameters(degreeOfBasis, speedOfSound, sourceFrequency, pressureAmplitude);
     N_ = S.ndofs;
@@ -131,7 +132,7 @@ public:
     idx2 = upload(gamma2.first);
     mG2 = upload(gamma2.second);
     std::map<std::string, double> params{{"c0", c0_}};
-    stiff_op = std::make_unique<StiffnessOperator<double>>(S, k_, params);   // LinearGLL.hpp:120-127
+    stiff_op = std::make_unique<StiffnessOperator<double>>(S, k_, params, tuning);   // LinearGLL.hpp:120-127
     stiffness(u_n->data());
   }
 
@@ -215,6 +216,13 @@ public:
   }
 
   ~LinearGLLOpt() { wf_boundary_destroy(bc_); }
+  /// what the stiffness operator of the loop runs (kernel, geometry, metric, ...)
+  wf_op_info_t stiffness_info() const
+  {
+    wf_op_info_t i{};
+    check(wf_op_info(stiff_op->handle(), &i));
+    return i;
+  }
   LinearGLLOpt(const LinearGLLOpt&) = delete;
   LinearGLLOpt& operator=(const LinearGLLOpt&) = delete;
 

@@ -1,0 +1,193 @@
+"""Shared meshes and references of the per-cell geometry of dofmap operators (wf_tuning.geometry = per_cell on
+wf_op_create; tests/test_idx_cell_host.py, tests/test_gpu_idx_cell_geometry.py).  No GPU in here.
+
+Every mesh is AFFINE by the bitwise rule (the edge vectors of a cell along a reference axis are bitwise equal): boxes
+whose vertex coordinates depend on one lattice index per axis, dyadic lattices where a shear is added.  The host test
+checks that with numpy, cell by cell, and that the "rectilinear" ones have exactly diagonal G_c.
+
+  unit         unit cubes (6, 3, 5): partial columns in x and y at every degree's cross-section
+  anisotropic  the same box with hi = (2, 1, 0.5)
+  graded       uneven spacings 3 * 2^-k per axis (exact coordinates; the factor 3 keeps every G_c w_i w_j w_k away from
+               1, where the rule refuses a cell because the -1/0/1 clamp might act: 8 * 0.125 at P1 on plain dyadic ones)
+  sheared      x += 0.25 y on a 0.125 lattice (a parallelepiped: G_c has a non-zero G01)
+each as given ("asis") and with every cell in a random one of the 48 orientations, cell 0 kept ("random"), plus
+  glued_rotated / glued_reflected   the two-block meshes of test_gpu_unstructured.build_mesh with perturb = 0
+  glued_mirrored                    block 2 with its local x reversed: det J < 0 in those cells (WF_FLAG_NO_FABS)
+  holed-<mask>                      nonbox_helpers' masks on the unperturbed HOLED_BOX, topological numbering
+"""
+from __future__ import annotations
+
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+
+from nonbox_helpers import HOLED_BOX, keep_mask
+
+N = (6, 3, 5)
+BASE = ("unit", "anisotropic", "graded", "sheared")
+RECTILINEAR = ("unit", "anisotropic", "graded", "glued_rotated", "glued_reflected", "glued_mirrored")
+PARITY_MESHES = tuple(f"{b}-{v}" for b in BASE for v in ("asis", "random")) + ("glued_rotated", "glued_reflected")
+HOLED = tuple(f"holed-{m}" for m in ("L", "cavity", "stair", "pillar"))
+# components of G_c as wf_geometry_hex_cell orders them
+COMP = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
+
+
+def lattice_x(vx, vy, vz):
+    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
+    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
+
+
+def box_with(n, x=None, hi=(1.0, 1.0, 1.0), perturb=0.0):
+    import wave_fenics_amd as w
+    box = w.create_box(n, hi=hi, perturb=perturb)
+    if x is not None:
+        box = w.BoxMesh(box.n, np.ascontiguousarray(x, dtype=np.float64), box.geom_dofmap, box.lo, box.hi)
+    return box
+
+
+def base_box(kind: str, n=N):
+    if kind == "unit":
+        return box_with(n, hi=tuple(float(m) for m in n))
+    if kind == "anisotropic":
+        return box_with(n, hi=(2.0, 1.0, 0.5))
+    if kind == "graded":   # spacings 3 * 2^-k: every coordinate and every edge is exact
+        rng = np.random.default_rng(7)
+        axes = [np.concatenate([[0.0], np.cumsum(3.0 * 0.5 ** rng.integers(0, 4, m))]) for m in n]
+        return box_with(n, x=lattice_x(*axes))
+    if kind == "sheared":
+        x = lattice_x(*[np.arange(m + 1) * 0.125 for m in n])
+        x[:, 0] += 0.25 * x[:, 1]
+        return box_with(n, x=x)
+    raise ValueError(kind)
+
+
+def random_orientations(mesh, seed=5):
+    from wave_fenics_amd import mesh_io
+    codes = np.random.default_rng(seed).integers(0, 48, mesh.ncells)
+    codes[0] = 0                 # the seed cell's frame is the lattice frame
+    return mesh_io.reorient_cells(mesh, np.arange(mesh.ncells), codes)
+
+
+@functools.lru_cache(maxsize=None)
+def affine_mesh(name: str):
+    """The mesh `name` (see the module docstring).  Cached: shared and left unchanged."""
+    import wave_fenics_amd as w
+    from wave_fenics_amd import mesh_io
+    if name == "glued_rotated":
+        box = w.create_box((6, 4, 3))
+        return mesh_io.reorient_cells(box, np.nonzero(np.arange(box.ncells) % 6 >= 3)[0], 8 * 2 + 2)
+    if name == "glued_reflected":
+        box = w.create_box((5, 4, 4))
+        return mesh_io.reorient_cells(box, np.nonzero(np.arange(box.ncells) % 5 >= 2)[0], 8 * 5 + 4)
+    if name == "glued_mirrored":
+        box = w.create_box((5, 4, 4))
+        return mesh_io.reorient_cells(box, np.nonzero(np.arange(box.ncells) % 5 >= 2)[0], 1)
+    if name.startswith("holed-"):
+        box = w.create_box(HOLED_BOX)
+        keep = keep_mask(name[len("holed-"):])
+        return w.BoxMesh(None, box.x, np.ascontiguousarray(box.geom_dofmap[keep]), box.lo, box.hi)
+    if name.startswith("column-"):   # (6, 3, nz) unit cubes: the layer loop
+        nz = int(name[len("column-"):])
+        return box_with((6, 3, nz), hi=(6.0, 3.0, float(nz)))
+    kind, variant = name.split("-")
+    mesh = base_box(kind)
+    return random_orientations(mesh) if variant == "random" else mesh
+
+
+def is_rectilinear(name: str) -> bool:
+    return name.split("-")[0] in RECTILINEAR or name.startswith(("holed-", "column-"))
+
+
+@functools.lru_cache(maxsize=None)
+def space(name: str, p: int):
+    from wave_fenics_amd import mesh_io
+    return mesh_io.create_functionspace(affine_mesh(name), p)
+
+
+def oracle_mesh(mesh, V, cells=None):
+    """The oracle's mesh of (mesh, V), or of the listed cells of it (same dof numbering)."""
+    from oracle import wave_oracle as o
+    gd, dm = np.ascontiguousarray(mesh.geom_dofmap), np.ascontiguousarray(V.dofmap)
+    if cells is not None:
+        gd, dm = np.ascontiguousarray(gd[cells]), np.ascontiguousarray(dm[cells])
+    return o.BoxMesh(None, V.degree, np.ascontiguousarray(mesh.x), gd, dm, V.ndofs, None)
+
+
+def cell_det_sign(mesh) -> np.ndarray:
+    """sign of det J per (affine) cell, from its edge vectors"""
+    xc = mesh.x[mesh.geom_dofmap]
+    J = np.stack([xc[:, 1] - xc[:, 0], xc[:, 2] - xc[:, 0], xc[:, 4] - xc[:, 0]], axis=2)
+    return np.sign(np.linalg.det(J))
+
+
+def reference_of(mesh, V, p: int, signed: bool = False, seed: int = 1234):
+    """x, y0 (random, at the scale of K x: accumulate semantics) and yref = y0 + K x by the oracle.  signed: the
+    operator of WF_FLAG_NO_FABS -- the oracle takes |det J|, so the cells with det J < 0 are applied on their own and
+    subtracted."""
+    from oracle import wave_oracle as o
+    rng = np.random.default_rng(seed)
+    x = rng.uniform(-1, 1, V.ndofs)
+    neg = np.nonzero(cell_det_sign(mesh) < 0)[0] if signed else np.zeros(0, dtype=np.int64)
+    Kx = np.zeros(V.ndofs)
+    if len(neg):
+        pos = np.setdiff1d(np.arange(mesh.ncells), neg)
+        o.StiffnessOperator(oracle_mesh(mesh, V, pos), p)(x, Kx)
+        Kneg = np.zeros(V.ndofs)
+        o.StiffnessOperator(oracle_mesh(mesh, V, neg), p)(x, Kneg)
+        Kx -= Kneg
+    else:
+        o.StiffnessOperator(oracle_mesh(mesh, V), p)(x, Kx)
+    y0 = rng.uniform(-1, 1, V.ndofs) * np.abs(Kx).max()
+    return SimpleNamespace(x=x, y0=y0, yref=y0 + Kx, scale=float(np.abs(y0 + Kx).max()), nneg=len(neg))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name: str, p: int, signed: bool = False):
+    """reference_of on a named mesh.  Cached: computed once, shared, left unchanged."""
+    return reference_of(affine_mesh(name), space(name, p), p, signed)
+
+
+def cell_geometry_longdouble(mesh, use_fabs: bool = True) -> np.ndarray:
+    """G_c = J^-1 J^-T |det J| (det J signed without use_fabs) of every cell from its edge vectors x1-x0, x2-x0, x4-x0,
+    in numpy long double: [ncells][6] in the order of COMP.  Exact zeros stay exact: the adjugate's entries are sums of
+    products, and a product with an exact zero factor is an exact zero."""
+    xc = mesh.x[mesh.geom_dofmap].astype(np.longdouble)
+    J = np.stack([xc[:, 1] - xc[:, 0], xc[:, 2] - xc[:, 0], xc[:, 4] - xc[:, 0]], axis=2)   # J[c][i][d]
+    a, b, c = J[:, 0], J[:, 1], J[:, 2]                                                  # rows of J
+    adjT = np.stack([np.cross(b, c), np.cross(c, a), np.cross(a, b)], axis=1)            # rows: cofactors of a row of J
+    det = np.einsum("ci,ci->c", a, adjT[:, 0])
+    Ji = np.transpose(adjT, (0, 2, 1)) / det[:, None, None]                               # J^-1 = adj / det
+    G = np.einsum("cak,cbk->cab", Ji, Ji) * (np.abs(det) if use_fabs else det)[:, None, None]
+    return np.stack([G[:, r, s] for r, s in COMP], axis=1)
+
+
+def is_bitwise_affine(mesh) -> np.ndarray:
+    """per cell: the four edges along each reference axis are bitwise equal"""
+    xc = mesh.x[mesh.geom_dofmap]
+    ok = np.ones(mesh.ncells, dtype=bool)
+    for d, pairs in enumerate((((1, 0), (3, 2), (5, 4), (7, 6)), ((2, 0), (3, 1), (6, 4), (7, 5)), ((4, 0), (5, 1), (6, 2), (7, 3)))):
+        e0 = xc[:, pairs[0][0]] - xc[:, pairs[0][1]]
+        for hi, lo in pairs[1:]:
+            ok &= np.all(xc[:, hi] - xc[:, lo] == e0, axis=1)
+    return ok
+
+
+# ---- the meshes a per-cell request must refuse ----
+def refusal_mesh(kind: str):
+    """(mesh, first bad cell or None when it is not predicted here, reason)"""
+    if kind == "perturbed":
+        mesh = box_with((4, 4, 3), perturb=0.2)
+        return mesh, int(np.nonzero(~is_bitwise_affine(mesh))[0][0]), 1
+    if kind == "one_vertex":   # a uniform box with one interior vertex moved: the first cell that touches it
+        n = (4, 4, 3)
+        mesh = box_with(n)
+        x = mesh.x.copy()
+        v = 2 + (n[0] + 1) * (2 + (n[1] + 1) * 1)
+        x[v, 1] += 0.01
+        mesh = box_with(n, x=x)
+        return mesh, int(np.nonzero((mesh.geom_dofmap == v).any(axis=1))[0][0]), 1
+    if kind == "tiny":   # h = 1e-7: G_c w_i w_j w_k = 1e-7 w^3 is below the clamp's 1e-8 at the corner points of degree >= 2
+        n = (3, 3, 3)
+        return box_with(n, hi=tuple(1e-7 * m for m in n)), 0, 3
+    raise ValueError(kind)

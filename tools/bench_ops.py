@@ -182,13 +182,16 @@ def main():
             if p >= 5:   # the owner form on request next to the default k-split kernel (OWNER_VARIANTS=1: every cross-section)
                 own = [{"update": "owner", "variant": v} for v in (0, 1, 2)] if "OWNER_VARIANTS" in os.environ else [{"update": "owner"}]
                 cases[1:1] = [(True, t) for t in own]
+            elif "KS" not in os.environ:   # per-cell geometry on request, next to the per-point dofmap operator
+                cases[2:2] = [(False, {"geometry": "per_cell"}), (False, {"geometry": "per_cell", "metric": "full"})]
             cases = [c + (0,) for c in cases]
             if p in (4, 6):   # order-fixed accumulation next to the default dofmap operator
                 cases.append((False, None, WF_FLAG_ORDERED))
             for structured, tuning, flags in cases:
                 op = w.StiffnessOperator(V, p, structured=structured, tuning=tuning, flags=flags)
                 report(f"stiffness P{p} " + ("box" if structured else "any dofmap") + f" [{op.kernel}]", timeit(lambda: op(x, y)),
-                       op.alg_bytes(), N, dict(tag, kernel=op.kernel, update=op.update, lz=op.info.plan_lz, tuning=str(tuning)))
+                       op.alg_bytes(), N, dict(tag, kernel=op.kernel, geometry=op.geometry, metric=op.metric, update=op.update, lz=op.info.plan_lz,
+                            tuning=str(tuning)))
                 del op
         if "mass" in only:
             op = w.SpectralMassOperator(V, p, structured=False)

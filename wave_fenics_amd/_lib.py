@@ -123,6 +123,7 @@ SIGNATURES = {
     "wf_quadrature_1d": (c_int, [c_int, c_int, POINTER(c_int), _dp, _dp]),
     "wf_tabulate_1d": (c_int, [c_int, c_int, c_int, _dp, c_int, _dp]),
     "wf_geometry_hex_rule": (c_int, [c_int, c_int, _dp, _ip, c_int, _dp, _dp, c_int, c_int, _dp, _dp]),
+    "wf_geometry_hex_cell": (c_int, [c_int, c_int64, c_int64, _dp, _ip, c_int, c_int, _dp, POINTER(c_int64), POINTER(c_int)]),
     "wf_reorder_dofmap": (c_int, [c_int, c_int, _ip, _ip, _ip]),
     "wf_lattice_numbering": (c_int, [c_int, ctypes.c_int64, ctypes.c_int32, _ip, _ip]),
     "wf_geometry_hex": (c_int, [c_int, c_int, c_int, _dp, _ip, c_int, c_int, _dp, _dp]),
@@ -226,4 +227,6 @@ def lib():
 def check(rc: int):
     if rc != 0:
         msg = lib().wf_last_error().decode(errors="replace")
-        raise WavehipError(f"libwavehip error {rc}: {msg}")
+        err = WavehipError(f"libwavehip error {rc}: {msg}")
+        err.status = rc   # the wf_status value
+        raise err

@@ -76,6 +76,7 @@ struct wf_op {
   int nitems[4] = {0, 0, 0, 0};
   int have_parts = 0;
   MarchPlanDev plan{};            // lattice columns of idx_march and mass_march
+  MarchGeom idx_geom = MarchGeom::point;   // geometry form of idx_march (per cell: d_Gcell in the plan's slot order)
   int plan_patterns = 0;
   DenseOpData* dense = nullptr;   // dense simplex operator (stiffness_dense.hip)
   int dense_clamp = 1;
@@ -188,16 +189,20 @@ int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB)
   return WF_OK;
 }
 
-// Per-cell geometry of a box (wf_op_create_box).  The trilinear map of a cell is affine when its edge vectors
-// along each reference axis are bitwise equal; J is then [x1-x0 | x2-x0 | x4-x0] everywhere and
-// G(q) = J^-1 J^-T |det J| w_q = G_c w_i w_j w_k.  Returns false -- the operator keeps per-point geometry -- unless
-//  * every cell is affine with det J != 0 (finite);
+// Per-cell geometry of hexahedral cells whose eight vertices vert(c, v) names (v = a + 2 b + 4 c', the tensor order of
+// h_geom_dofmap).  The trilinear map of a cell is affine when its edge vectors along each reference axis are bitwise
+// equal; J is then [x1-x0 | x2-x0 | x4-x0] everywhere and G(q) = J^-1 J^-T |det J| w_q = G_c w_i w_j w_k.
+// A cell qualifies when
+//  * it is affine (else reason 1) with det J != 0, finite (else reason 2);
 //  * with the reference's -1/0/1 clamp on: the clamp changes neither a cmap derivative at the rule's points nor a
 //    component of any G(q) (it maps |v| <= 1e-8 to 0 and v within 1e-5 of +-1 to +-1: per point that would
-//    be a change per-cell G_c w_i w_j w_k cannot express).  Components that are exactly 0 stay 0 either way.
+//    be a change per-cell G_c w_i w_j w_k cannot express; else reason 3).  Components that are exactly 0 stay 0 either way.
 // Computing G_c from the edge vectors avoids the cancellation of the sum over vertices x_v dphi_v.
-// Gc: [ncells][6] in cell order, components G00 G01 G02 G11 G12 G22 (the blocked layout's order).
-bool box_cell_geometry(int P, int nx, int ny, int nz, const double* xv, int use_fabs, int clamp, std::vector<double>& Gc)
+// Gc (may be null): [ncells][6] in cell order, components G00 G01 G02 G11 G12 G22 (the blocked layout's order).
+// Returns the first cell that does not qualify (Gc is then complete only below it), -1 when all do.
+template <class VertexOf>
+int64_t hex_cell_geometry(int P, size_t ncells, const double* xv, VertexOf&& vert, int use_fabs, int clamp, double* Gc,
+                          int* reason)
 {
   const int n = P + 1;
   std::vector<double> pts(n), wts(n);
@@ -213,6 +218,7 @@ bool box_cell_geometry(int P, int nx, int ny, int nz, const double* xv, int use_
     for (int j = 0; j < n; ++j)
       for (int i = 0; i < n; ++i) W.push_back(wts[i] * wts[j] * wts[k]);
   const double wmin = *std::min_element(W.begin(), W.end()), wmax = *std::max_element(W.begin(), W.end());
+  bool cmap_clamped = false;   // the same for every cell
   if (clamp) {
     for (int k = 0; k < n; ++k)
       for (int j = 0; j < n; ++j)
@@ -223,7 +229,7 @@ bool box_cell_geometry(int P, int nx, int ny, int nz, const double* xv, int use_
             const int a = v & 1, b = (v >> 1) & 1, c = (v >> 2) & 1;
             const double d[3] = {g[a] * f1[b] * f2[c], f0[a] * g[b] * f2[c], f0[a] * f1[b] * g[c]};
             for (double dv : d)
-              if (clamp101(dv) != dv) return false;
+              if (clamp101(dv) != dv) cmap_clamped = true;
           }
         }
   }
@@ -238,49 +244,59 @@ bool box_cell_geometry(int P, int nx, int ny, int nz, const double* xv, int use_
       if (v * w * (1.0 + slack) >= lo1 && v * w * (1.0 - slack) <= hi1) return false;
     return true;
   };
+  *reason = 0;
+  for (size_t cell = 0; cell < ncells; ++cell) {
+    const double* x[8];
+    for (int v = 0; v < 8; ++v) x[v] = xv + 3 * (size_t)vert(cell, v);
+    double J[9];   // J[i * 3 + d]: component i of the edge along reference axis d
+    for (int i = 0; i < 3; ++i) {
+      const double e[3] = {x[1][i] - x[0][i], x[2][i] - x[0][i], x[4][i] - x[0][i]};
+      // x1-x0 == x3-x2 == x5-x4 == x7-x6, x2-x0 == x3-x1 == x6-x4 == x7-x5, x4-x0 == x5-x1 == x6-x2 == x7-x3
+      if (!(x[3][i] - x[2][i] == e[0] && x[5][i] - x[4][i] == e[0] && x[7][i] - x[6][i] == e[0] &&
+            x[3][i] - x[1][i] == e[1] && x[6][i] - x[4][i] == e[1] && x[7][i] - x[5][i] == e[1] &&
+            x[5][i] - x[1][i] == e[2] && x[6][i] - x[2][i] == e[2] && x[7][i] - x[3][i] == e[2]))
+        return *reason = 1, (int64_t)cell;
+      for (int d = 0; d < 3; ++d) J[i * 3 + d] = e[d];
+    }
+    double det = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
+    if (!(det != 0.0) || !std::isfinite(det)) return *reason = 2, (int64_t)cell;
+    const double idet = 1.0 / det;
+    double Ji[9];
+    Ji[0] = (J[4] * J[8] - J[5] * J[7]) * idet;
+    Ji[1] = (J[2] * J[7] - J[1] * J[8]) * idet;
+    Ji[2] = (J[1] * J[5] - J[2] * J[4]) * idet;
+    Ji[3] = (J[5] * J[6] - J[3] * J[8]) * idet;
+    Ji[4] = (J[0] * J[8] - J[2] * J[6]) * idet;
+    Ji[5] = (J[2] * J[3] - J[0] * J[5]) * idet;
+    Ji[6] = (J[3] * J[7] - J[4] * J[6]) * idet;
+    Ji[7] = (J[1] * J[6] - J[0] * J[7]) * idet;
+    Ji[8] = (J[0] * J[4] - J[1] * J[3]) * idet;
+    if (use_fabs) det = std::fabs(det);
+    static const int comp[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    for (int m = 0; m < 6; ++m) {
+      const int a = comp[m][0], b = comp[m][1];
+      double s = 0.0;
+      for (int k = 0; k < 3; ++k) s += (Ji[a * 3 + k] * det) * Ji[b * 3 + k];
+      if (!std::isfinite(s)) return *reason = 2, (int64_t)cell;
+      if (clamp && (cmap_clamped || !clamp_free(s))) return *reason = 3, (int64_t)cell;
+      if (Gc) Gc[cell * 6 + m] = s;
+    }
+  }
+  return -1;
+}
+
+// Per-cell geometry of a box (wf_op_create_box): the rule above on the box's implicit vertex lattice.  Returns false --
+// the operator keeps per-point geometry -- unless every cell qualifies.
+bool box_cell_geometry(int P, int nx, int ny, int nz, const double* xv, int use_fabs, int clamp, std::vector<double>& Gc)
+{
   const size_t ncells = (size_t)nx * ny * nz;
   Gc.assign(ncells * 6, 0.0);
-  for (int cz = 0; cz < nz; ++cz)
-    for (int cy = 0; cy < ny; ++cy)
-      for (int cx = 0; cx < nx; ++cx) {
-        const double* x[8];
-        for (int v = 0; v < 8; ++v)
-          x[v] = xv + 3 * ((size_t)(cx + (v & 1)) + (size_t)(nx + 1) * ((cy + ((v >> 1) & 1)) + (size_t)(ny + 1) * (cz + ((v >> 2) & 1))));
-        double J[9];   // J[i * 3 + d]: component i of the edge along reference axis d
-        for (int i = 0; i < 3; ++i) {
-          const double e[3] = {x[1][i] - x[0][i], x[2][i] - x[0][i], x[4][i] - x[0][i]};
-          // x1-x0 == x3-x2 == x5-x4 == x7-x6, x2-x0 == x3-x1 == x6-x4 == x7-x5, x4-x0 == x5-x1 == x6-x2 == x7-x3
-          if (!(x[3][i] - x[2][i] == e[0] && x[5][i] - x[4][i] == e[0] && x[7][i] - x[6][i] == e[0] &&
-                x[3][i] - x[1][i] == e[1] && x[6][i] - x[4][i] == e[1] && x[7][i] - x[5][i] == e[1] &&
-                x[5][i] - x[1][i] == e[2] && x[6][i] - x[2][i] == e[2] && x[7][i] - x[3][i] == e[2]))
-            return false;
-          for (int d = 0; d < 3; ++d) J[i * 3 + d] = e[d];
-        }
-        double det = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6]) + J[2] * (J[3] * J[7] - J[4] * J[6]);
-        if (!(det != 0.0) || !std::isfinite(det)) return false;
-        const double idet = 1.0 / det;
-        double Ji[9];
-        Ji[0] = (J[4] * J[8] - J[5] * J[7]) * idet;
-        Ji[1] = (J[2] * J[7] - J[1] * J[8]) * idet;
-        Ji[2] = (J[1] * J[5] - J[2] * J[4]) * idet;
-        Ji[3] = (J[5] * J[6] - J[3] * J[8]) * idet;
-        Ji[4] = (J[0] * J[8] - J[2] * J[6]) * idet;
-        Ji[5] = (J[2] * J[3] - J[0] * J[5]) * idet;
-        Ji[6] = (J[3] * J[7] - J[4] * J[6]) * idet;
-        Ji[7] = (J[1] * J[6] - J[0] * J[7]) * idet;
-        Ji[8] = (J[0] * J[4] - J[1] * J[3]) * idet;
-        if (use_fabs) det = std::fabs(det);
-        static const int comp[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
-        double* gc = &Gc[((size_t)cx + (size_t)nx * (cy + (size_t)ny * cz)) * 6];
-        for (int m = 0; m < 6; ++m) {
-          const int a = comp[m][0], b = comp[m][1];
-          double s = 0.0;
-          for (int k = 0; k < 3; ++k) s += (Ji[a * 3 + k] * det) * Ji[b * 3 + k];
-          if (!std::isfinite(s) || (clamp && !clamp_free(s))) return false;
-          gc[m] = s;
-        }
-      }
-  return true;
+  auto vert = [&](size_t c, int v) {
+    const size_t cx = c % nx, cy = (c / nx) % ny, cz = c / ((size_t)nx * ny);
+    return (cx + (v & 1)) + (size_t)(nx + 1) * ((cy + ((v >> 1) & 1)) + (size_t)(ny + 1) * (cz + ((v >> 2) & 1)));
+  };
+  int reason;
+  return hex_cell_geometry(P, ncells, xv, vert, use_fabs, clamp, Gc.data(), &reason) < 0;
 }
 
 void default_box_block(int P, const wf_tuning& tun, int* bx, int* by, int* bz)
@@ -570,6 +586,22 @@ int wf_geometry_hex_rule(int ncells, int nverts, const double* h_xverts, const i
                            h_detJ, "wf_geometry_hex_rule");
 }
 
+int wf_geometry_hex_cell(int P, int64_t ncells, int64_t nverts, const double* h_xverts, const int32_t* h_geom_dofmap,
+                         int use_fabs, int clamp, double* h_Gc, int64_t* first_bad, int* reason)
+{
+  if (P < 1 || P > kMaxDegree) {
+    set_error("wf_geometry_hex_cell: degree must be 1..7");
+    return WF_ERR_UNSUPPORTED;
+  }
+  WF_REQUIRE(ncells >= 0 && nverts >= 0 && first_bad && reason && (ncells == 0 || (h_xverts && h_geom_dofmap)),
+             "wf_geometry_hex_cell: bad arguments");
+  for (size_t e = 0; e < (size_t)ncells * 8; ++e)
+    WF_REQUIRE(h_geom_dofmap[e] >= 0 && h_geom_dofmap[e] < nverts, "wf_geometry_hex_cell: vertex index out of range");
+  *first_bad = hex_cell_geometry(P, (size_t)ncells, h_xverts, [&](size_t c, int v) { return h_geom_dofmap[c * 8 + v]; },
+                                 use_fabs, clamp, h_Gc, reason);
+  return WF_OK;
+}
+
 }  // extern "C"
 
 // ---- operators -------------------------------------------------------------
@@ -692,11 +724,35 @@ struct PointMaps {
 };
 
 // stiffness geometry in slot order [item][layer][ly][lx]; missing cells stay zero (they contribute nothing)
-int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const MarchPlan& plan, wf_op* op)
+// h_Gc: per-cell geometry on request (wf_tuning.geometry), [ncells][6] in the cells' own frames; uploaded as
+// Gc[(item lz + layer) CB + cell][6] in the plan's frame, op->idx_geom already says which form reads it
+int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const MarchPlan& plan, const double* h_Gc, wf_op* op)
 {
   const int P = op->P, n = op->n, nd = op->nd, CB = op->plan.bx * op->plan.by;
   const size_t nslots = (size_t)plan.nitems * plan.lz * CB;
   int rc;
+  if (h_Gc) {
+    // G_c of a cell seen in the lattice frame, as h_G below: G'[a][b] = s_a s_b G[r_a][r_b].  Without fabs G_c carries
+    // the sign of the cell's own det J, which is what the per-point path restores with orient_sign.
+    if ((rc = upload_derivative_tables(op, true)) != WF_OK) return rc;
+    static const int comp[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    static const int sym[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+    std::vector<double> blk(nslots * 6, 0.0);
+    for (size_t q = 0; q < nslots; ++q) {
+      const int32_t c = plan.slot_cell[q];
+      if (c < 0) continue;
+      int ra[3], fl[3];
+      orient_decode(plan.cell_orient[c], ra, fl);
+      for (int m = 0; m < 6; ++m) {
+        const int a = comp[m][0], b2 = comp[m][1];
+        const double g = h_Gc[(size_t)c * 6 + sym[ra[a]][ra[b2]]];
+        blk[q * 6 + m] = (fl[a] ^ fl[b2]) ? -g : g;
+      }
+    }
+    if ((rc = dev_upload(&op->d_Gcell, blk.data(), blk.size(), &op->device_bytes)) != WF_OK) return rc;
+    op->kernel = OpKernel::idx_march;
+    return WF_OK;
+  }
   if ((rc = upload_derivative_tables(op, false)) != WF_OK) return rc;
   const size_t g6 = nslots * nd * 6;
   if ((rc = dev_alloc(&op->d_G6blk, g6, &op->device_bytes)) != WF_OK) return rc;
@@ -800,7 +856,9 @@ int plan_mass_detJ(const wf_op_desc* desc, const CallerFrame& fr, const MarchPla
 }
 
 // leaves op untouched (no kernel) when the mesh does not tile into lattice columns: the batch kernels take it
-int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t* tdm, bool mass, wf_op* op)
+// h_Gc: the stiffness operator with per-cell geometry (on request; op->idx_geom is set): any fill is adopted, and a mesh
+// that does not tile is an error
+int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t* tdm, bool mass, const double* h_Gc, wf_op* op)
 {
   const int P = op->P, n = op->n;
   const wf_tuning& tun = op->tun;
@@ -816,7 +874,8 @@ int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t*
   }
   // layers per work item: as many as the kernel's LDS budget per workgroup allows, at most 16
   int lz_max = mass ? 32 : 16;   // (the dense-mass kernel streams its index table: no LDS limit)
-  while (!mass && lz_max > 1 && march_idx_lds_bytes(pkind, P, BX, BY, lz_max) > march_idx_lds_budget(pkind, P, BX, BY)) --lz_max;
+  while (!mass && lz_max > 1 && march_idx_lds_bytes(pkind, P, BX, BY, lz_max, op->idx_geom) > march_idx_lds_budget(pkind, P, BX, BY, op->idx_geom))
+    --lz_max;
   // A cell may be looked at with an axis reversed only if the 1-D table reads the same backwards,
   // phi1[M-1-q][n-1-a] == phi1[q][a] (true for every symmetric node / point set; the GLL derivative
   // matrix of the stiffness operator has the matching antisymmetry by construction).
@@ -829,12 +888,16 @@ int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t*
   int rc;
   if ((rc = build_march_plan(P, (size_t)desc->ncells, tdm, BX, BY, lz_max, std::max(0, tun.lz), normalise, &plan)) != WF_OK) return rc;
   // mostly empty columns (a mesh one cell wide, a mesh shattered into tiny lattice components): the
-  // marching kernel would read geometry for every slot -- batch kernel instead
-  const bool forced = tun.kernel == WF_KERNEL_FORCE_MARCH || tun.kernel == WF_KERNEL_FORCE_MASS_MARCH;
+  // marching kernel would read geometry for every slot -- batch kernel instead (per-cell geometry is 48 B per slot)
+  const bool forced = tun.kernel == WF_KERNEL_FORCE_MARCH || tun.kernel == WF_KERNEL_FORCE_MASS_MARCH || h_Gc;
   if (plan.ok && plan.fill < kMinPlanFill && !forced) plan.ok = false;
   if (!plan.ok && mass && M != n) {   // a rectangular table is here on request only
     set_error("wf_op_create: WF_KERNEL_FORCE_MASS_MARCH: the mesh does not tile into lattice columns ((P, nq1) = ("
               + std::to_string(P) + ", " + std::to_string(M) + "))");
+    return WF_ERR_UNSUPPORTED;
+  }
+  if (!plan.ok && h_Gc) {
+    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: the mesh does not tile into lattice columns");
     return WF_ERR_UNSUPPORTED;
   }
   if (!plan.ok) return WF_OK;
@@ -847,8 +910,60 @@ int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t*
   if ((rc = dev_upload(&op->plan.d_item_pattern, plan.item_pattern.data(), plan.item_pattern.size(), &op->device_bytes)) != WF_OK) return rc;
   if ((rc = dev_upload(&op->plan.d_item_layers, plan.item_layers.data(), plan.item_layers.size(), &op->device_bytes)) != WF_OK) return rc;
   if ((rc = dev_upload(&op->plan.d_pat_off, plan.pat_off.data(), plan.pat_off.size(), &op->device_bytes)) != WF_OK) return rc;
-  if ((rc = mass ? plan_mass_detJ(desc, fr, plan, op) : plan_stiffness_geometry(desc, fr, plan, op)) != WF_OK) return rc;
+  if ((rc = mass ? plan_mass_detJ(desc, fr, plan, op) : plan_stiffness_geometry(desc, fr, plan, h_Gc, op)) != WF_OK) return rc;
   WF_HIP_CHECK(hipDeviceSynchronize());
+  return WF_OK;
+}
+
+// wf_tuning.geometry = WF_GEOMETRY_PER_CELL on wf_op_create (stiffness, ncells > 0): what else the request allows, the
+// per-cell geometry h_Gc [ncells][6] in the cells' own frames and the form that will read it (op->idx_geom).  Host only;
+// the order of the checks decides which error a bad request reports.
+int choose_idx_cell_geometry(const wf_op_desc* desc, bool have_mesh, wf_op* op, std::vector<double>& h_Gc)
+{
+  const wf_tuning& tun = op->tun;
+  const int P = op->P;
+  if (P > 4) {
+    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: the dofmap kernel has per-cell forms at degrees 1..4 (degree "
+              + std::to_string(P) + " runs the k-split kernel, per-point geometry only)");
+    return WF_ERR_UNSUPPORTED;
+  }
+  if (desc->h_G) {
+    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: per-cell geometry is derived from the mesh; h_G must be NULL");
+    return WF_ERR_UNSUPPORTED;
+  }
+  WF_REQUIRE(have_mesh, "wf_op_create: WF_GEOMETRY_PER_CELL needs the mesh (h_xverts, h_geom_dofmap)");
+  WF_REQUIRE(tun.kernel == WF_KERNEL_AUTO || tun.kernel == WF_KERNEL_FORCE_MARCH,
+             "wf_op_create: WF_GEOMETRY_PER_CELL: wf_tuning.kernel must be AUTO or FORCE_MARCH (only the marching kernel on "
+             "lattice columns reads per-cell geometry)");
+  WF_REQUIRE(tun.update >= WF_UPDATE_AUTO && tun.update <= WF_UPDATE_OWNER, "wf_op_create: wf_tuning.update out of range");
+  if (tun.update == WF_UPDATE_OWNER) {
+    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: the owner update needs the box's implicit lattice (wf_op_create_box)");
+    return WF_ERR_UNSUPPORTED;
+  }
+  WF_REQUIRE(tun.metric >= WF_METRIC_AUTO && tun.metric <= WF_METRIC_AXES, "wf_op_create: wf_tuning.metric out of range");
+  h_Gc.assign((size_t)desc->ncells * 6, 0.0);
+  int reason = 0;
+  const int32_t* gd = desc->h_geom_dofmap;
+  const int64_t bad = hex_cell_geometry(P, (size_t)desc->ncells, desc->h_xverts, [&](size_t c, int v) { return gd[c * 8 + v]; },
+                                        fabs_flag(desc->flags), clamp_flag(desc->flags), h_Gc.data(), &reason);
+  if (bad >= 0) {
+    static const char* kWhy[4] = {"", "is not affine (its edge vectors along a reference axis differ)",
+                                  "is degenerate (det J zero or not finite)",
+                                  "has geometry on which the -1/0/1 clamp takes effect (WF_FLAG_NO_CLAMP turns it off)"};
+    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: cell " + std::to_string(bad) + " " + kWhy[reason]);
+    return WF_ERR_INVALID;
+  }
+  // metric: the separable (axes) form when every G_c is diagonal -- off-diagonals exactly 0, either sign.  Taking a cell
+  // into the plan's frame permutes and negates components, so the cells' own frames decide.
+  bool diagonal = true;
+  size_t c = 0;
+  for (; c < h_Gc.size() && diagonal; c += 6) diagonal = h_Gc[c + 1] == 0.0 && h_Gc[c + 2] == 0.0 && h_Gc[c + 4] == 0.0;
+  if (tun.metric == WF_METRIC_AXES && !diagonal) {
+    set_error("wf_op_create: axes metric requested but the G_c of cell " + std::to_string(c / 6 - 1)
+              + " has a non-zero off-diagonal");
+    return WF_ERR_INVALID;
+  }
+  op->idx_geom = diagonal && tun.metric != WF_METRIC_FULL ? MarchGeom::cell_axes : MarchGeom::cell;
   return WF_OK;
 }
 
@@ -1141,10 +1256,14 @@ int wf_op_create(const wf_op_desc* desc, wf_op** out)
     std::vector<int32_t> tdm_store;
     const int32_t* tdm = nullptr;
     rc = tensor_dofmap(desc, fr, nd, tdm_store, &tdm);
+    // per-cell geometry of the stiffness operator, on request: decided on the host before the first device allocation
+    std::vector<double> h_Gc;
+    const bool per_cell = plan_stiffness && tun.geometry == WF_GEOMETRY_PER_CELL && ncells > 0 && !op->ordered;
+    if (rc == WF_OK && per_cell) rc = choose_idx_cell_geometry(desc, have_mesh, op.get(), h_Gc);
     if (rc == WF_OK && (plan_stiffness || plan_mass) && !force_batch && !op->ordered && ncells > 0) {
       if (plan_stiffness)
         WF_REQUIRE(desc->h_G || have_mesh, "wf_op_create: stiffness needs h_G or the mesh (h_xverts, h_geom_dofmap)");
-      rc = create_on_plan(desc, fr, tdm, plan_mass, op.get());
+      rc = create_on_plan(desc, fr, tdm, plan_mass, per_cell ? h_Gc.data() : nullptr, op.get());
     }
     // no kernel yet: the mesh does not tile into lattice columns, or the plan was not asked for
     if (rc == WF_OK && op->kernel == OpKernel::none) rc = create_batch(desc, fr, tdm, op.get());
@@ -1535,7 +1654,9 @@ static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitem
       return launch_stiffness_box(op->P, op->nx, op->ny, op->nz, op->box.bx, op->box.by, op->box.bz, op->d_G6blk, op->d_D, op->dm,
                                   op->coeff, d_x, d_y, s);
     case OpKernel::idx_march:
-      return launch_stiffness_march_idx(op->P, op->plan, op->d_G6blk, op->d_D, op->dm, op->coeff, d_x, d_y, d_items, nitems, s);
+      return launch_stiffness_march_idx(op->P, op->idx_geom, op->plan, op->idx_geom == MarchGeom::point ? op->d_G6blk : op->d_Gcell,
+                                        op->d_D, op->idx_geom == MarchGeom::cell_axes ? op->am : op->dm, op->coeff, d_x, d_y,
+                                        d_items, nitems, s);
     case OpKernel::generic_unique:
       return launch_stiffness_generic_u(op->P, op->ncells, op->d_uoff, op->d_uniq, op->d_loc, op->d_G6blk, op->d_D,
                                         op->dm, op->coeff, d_x, d_y, s);
@@ -1697,7 +1818,12 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
       kernel = WF_KERNEL_MARCH_BOX, geometry = WF_GEOMETRY_PER_CELL, metric = WF_METRIC_AXES, update = WF_UPDATE_OWNER;
       break;
     case OpKernel::box_block: kernel = WF_KERNEL_BOX_BLOCK, geometry = WF_GEOMETRY_PER_POINT; break;
-    case OpKernel::idx_march: kernel = WF_KERNEL_MARCH_IDX, geometry = WF_GEOMETRY_PER_POINT, plan = true; break;
+    case OpKernel::idx_march:
+      kernel = WF_KERNEL_MARCH_IDX, plan = true;
+      geometry = op->idx_geom == MarchGeom::point ? WF_GEOMETRY_PER_POINT : WF_GEOMETRY_PER_CELL;
+      metric = op->idx_geom == MarchGeom::cell ? WF_METRIC_FULL : op->idx_geom == MarchGeom::cell_axes ? WF_METRIC_AXES : WF_METRIC_NONE;
+      update = op->idx_geom == MarchGeom::cell_axes ? WF_UPDATE_ATOMIC : WF_UPDATE_NONE;
+      break;
     case OpKernel::generic_unique: kernel = WF_KERNEL_BATCH_UNIQUE, geometry = WF_GEOMETRY_PER_POINT; break;
     case OpKernel::generic_elementwise: kernel = WF_KERNEL_ELEMENTWISE, geometry = WF_GEOMETRY_PER_POINT; break;
     case OpKernel::lumped_unique: kernel = WF_KERNEL_BATCH_UNIQUE; break;

@@ -188,14 +188,18 @@ constexpr int OP_KIND_STIFFNESS = 0, OP_KIND_MASS = 1;
 // column cross-section, LDS need and LDS budget (per workgroup) of the indexed marching kernel of (kind, P); the
 // needs of the k-split and the dense-mass kernel themselves: march_ks_lds_bytes, mass_march_lds_bytes (march_column.h)
 void march_idx_shape(int kind, int P, int* bx, int* by);   // stiffness: keeps a compiled (*bx, *by) of the k-split kernel
-size_t march_idx_lds_bytes(int kind, int P, int BX, int BY, int lz);
-size_t march_idx_lds_budget(int kind, int P, int BX, int BY);
+// geom: the geometry form of the stiffness kernel at P <= 4 (the per-cell forms have less static LDS and run more
+// workgroups per CU)
+size_t march_idx_lds_bytes(int kind, int P, int BX, int BY, int lz, MarchGeom geom = MarchGeom::point);
+size_t march_idx_lds_budget(int kind, int P, int BX, int BY, MarchGeom geom = MarchGeom::point);
 // dense mass on the lattice columns (mass_march.hip), 1-D table phi1[M][P + 1].  mass_march_shape: whether the pair
 // (P, M) is compiled; then keeps a compiled (*bx, *by) of the pair, else sets the pair's default
 bool mass_march_shape(int P, int M, int* bx, int* by);
 int launch_mass_march(int P, int M, const MarchPlanDev& pd, const double* d_detJblk, const double* d_phi1, const double* d_x,
                       double* d_y, hipStream_t s);
-int launch_stiffness_march_idx(int P, const MarchPlanDev& pd, const double* d_G6blk, const double* d_D,
+// geom != point (P <= 4): d_geom is the per-cell geometry Gc[(item lz + layer) BX BY + cell][6] of affine cells and d_D
+// carries the weights and A as for launch_stiffness_march; dm is A instead of D for cell_axes
+int launch_stiffness_march_idx(int P, MarchGeom geom, const MarchPlanDev& pd, const double* d_geom, const double* d_D,
                                const DMat& dm, double coeff, const double* d_x, double* d_y, const int32_t* d_items,
                                int nitems, hipStream_t s);
 // k-split marching kernel (stiffness_march_ks.hip): the stiffness kernel of every degree

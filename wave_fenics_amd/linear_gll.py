@@ -84,7 +84,7 @@ def facet_lumped_mass(V, tag_of_face, tag: int):
 class LinearGLLOpt:
     def __init__(self, V, degreeOfBasis: int, speedOfSound: float, sourceFrequency: float,
                  pressureAmplitude: float, boundary=None, updater=None, device=None, structured=None,
-                 tags=None):
+                 tags=None, tuning=None):
         self.V = V
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.k_ = degreeOfBasis
@@ -131,8 +131,8 @@ class LinearGLLOpt:
         td = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, dtype=dt)
         self.idx1, self.mG1 = td(i1, torch.int32), td(m1, torch.float64)
         self.idx2, self.mG2 = td(i2, torch.int32), td(m2, torch.float64)
-        # LinearGLL.hpp:120-127
-        self.stiff_op = StiffnessOperator(V, self.k_, {"c0": self.c0_}, structured=structured)
+        # LinearGLL.hpp:120-127; tuning: the stiffness operator's make_tuning dict, e.g. {"geometry": "per_cell"}
+        self.stiff_op = StiffnessOperator(V, self.k_, {"c0": self.c0_}, structured=structured, tuning=tuning)
         # domain-decomposed run: interior cells overlap the forward ghost update
         self._split = False
         if self.updater is not None:

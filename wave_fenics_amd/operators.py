@@ -114,6 +114,22 @@ def compute_geometry_rule(mesh, points1, weights1, use_fabs: bool = False, clamp
     return G, detJ
 
 
+def hex_cell_geometry(mesh, p: int, use_fabs: bool = True, clamp: bool = True):
+    """The per-cell geometry of affine hexahedra and the test that allows it (wf_geometry_hex_cell, host only, no
+    device needed): (Gc[ncells][6] = G00 G01 G02 G11 G12 G22 of J^-1 J^-T |det J|, first_bad, reason).  first_bad is -1
+    when every cell qualifies, else the first cell that does not (Gc is complete only below it); reason 0 ok, 1 not
+    affine (edge vectors along a reference axis not bitwise equal), 2 det J zero or not finite, 3 the reference's
+    -1/0/1 clamp would take effect at the degree-p rule.  This is the rule behind tuning={"geometry": "per_cell"}."""
+    x = np.ascontiguousarray(mesh.x, dtype=np.float64)
+    gd = np.ascontiguousarray(mesh.geom_dofmap, dtype=np.int32)
+    ncells = gd.size // 8
+    Gc = np.zeros((ncells, 6))
+    bad, reason = ctypes.c_int64(-1), ctypes.c_int(0)
+    check(lib().wf_geometry_hex_cell(p, ncells, x.shape[0], _dp(x), _ip(gd), int(use_fabs), int(clamp), _dp(Gc),
+                                     ctypes.byref(bad), ctypes.byref(reason)))
+    return Gc, int(bad.value), int(reason.value)
+
+
 def precompute_geometric_data(mesh, p: int, use_fabs: bool = True, clamp: bool = True, want_G: bool = True):
     """precompute_geometric_data (common/precomputation.hpp:18-110) on the device;
     returns host arrays (G[ncells][nq][3][3], detJ[ncells][nq])."""
@@ -139,7 +155,10 @@ def make_tuning(tuning) -> "_lib.Tuning | None":
     "owner".  {"update": "owner"} gives the owner-computes separable box stiffness kernel (per-cell geometry, no atomics,
     bitwise reproducible) on a rectilinear box at degrees 1 to 7 and raises WavehipError on any other mesh; `variant`
     then indexes its three cross-sections.  "auto" picks it at degree 4 only; at degrees 5 to 7 "auto" keeps the k-split
-    kernel with per-point geometry."""
+    kernel with per-point geometry.  On an operator of any dofmap (structured=False, a mesh read from a file)
+    {"geometry": "per_cell"} stores one G_c per cell at degrees 1 to 4 when every cell is affine (hex_cell_geometry) and
+    raises WavehipError otherwise; "metric" then chooses between the full and the separable form as on a box, and
+    "auto" / "per_point" keep the per-point kernel."""
     if tuning is None:
         return None
     if isinstance(tuning, _lib.Tuning):
@@ -208,7 +227,8 @@ class _Operator:
 
     @property
     def metric(self) -> str:
-        """Form of the per-cell box kernel (wf_op_info_t.metric): "full", "axes" or "none" (no per-cell geometry)."""
+        """Form of the per-cell kernel, box or dofmap (wf_op_info_t.metric): "full", "axes" or "none" (no per-cell
+        geometry)."""
         return {1: "full", 2: "axes"}.get(self.info.metric, "none")
 
     @property
@@ -326,7 +346,10 @@ class StiffnessOperator(_Operator):
     reference layout [ncells][nq][3][3] is used as given.
     structured=None picks the implicit-dofmap box kernel when V says its dofmap
     is the lexicographic box numbering; structured=False forces the generic
-    (arbitrary dofmap, atomic scatter) kernel."""
+    (arbitrary dofmap, atomic scatter) kernel.  There tuning={"geometry": "per_cell"}
+    asks for one G_c per cell (degrees 1 to 4, every cell affine, G=None): the
+    marching kernel on lattice columns then streams 48 B per cell instead of 48 B
+    per point; op.geometry, op.metric report what was built."""
 
     def __init__(self, V: FunctionSpace, bdegree: int, params: dict | None = None, G=None, perm=None,
                  structured: bool | None = None, flags: int = 0, tuning=None):
