@@ -196,6 +196,49 @@ def test_parts_sum_to_the_full_apply(gpu, oracle, ghost, lz0):
         assert relerr(yb.cpu().numpy(), yall.cpu().numpy()) <= TOL_FORM, mode
 
 
+@pytest.mark.parametrize("structured", [True, False])
+def test_resplit_gives_back_the_old_item_lists(gpu, oracle, structured):
+    """wf_op_info_t.device_bytes across two interior / interface splits: the four work-item lists (interior, interface
+    and the two interior halves, 4 B per item) come on top of what the operator held before the first split, and a
+    second split with another ghost set replaces the lists of the first instead of adding to them.  The parts of either
+    split sum to the full apply."""
+    import torch
+    import wave_fenics_amd as w
+    from wave_fenics_amd._lib import WF_PART_INTERFACE, WF_PART_INTERIOR, WF_PART_INTERIOR_A, WF_PART_INTERIOR_B
+    p, n = 2, (3, 3, 6)
+    om, V = spaces(oracle, n, p)
+    # (the dofmap operator marches on request: at this size its plan fills too few cell slots for the default to take it)
+    tuning = {"lz": 2} if structured else {"lz": 2, "kernel": "march"}
+    op = w.StiffnessOperator(V, p, {"c0": 1500.0}, structured=structured, tuning=tuning)
+    assert op.kernel == ("march_box" if structured else "march_idx")
+    NX, NY, NZ = V.lattice
+    lat = np.arange(om.ndofs).reshape(NZ, NY, NX)
+    below = lat[0, :, :].ravel().astype(np.int32)
+    below_and_left = np.unique(np.concatenate([below, lat[:, :, 0].ravel()])).astype(np.int32)
+    x = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, om.ndofs)).to(gpu)
+    yall = torch.zeros_like(x)
+    op(x, yall)
+    before = op.info.device_bytes
+    assert before > 0 and op.info.items_interior == 0 and op.info.items_interface == 0
+    counts = []
+    for split in (0, 1):
+        if split == 0:
+            assert op.set_ghost_faces(False, False, True) if structured else op.set_ghost_dofs(below)
+        else:
+            assert op.set_ghost_dofs(below_and_left)
+        info = op.info
+        counts.append((info.items_interior, info.items_interface))
+        assert info.items_interface > 0
+        assert info.device_bytes == before + 4 * (2 * info.items_interior + info.items_interface), (split, counts)
+        for parts in ((WF_PART_INTERIOR, WF_PART_INTERFACE), (WF_PART_INTERIOR_A, WF_PART_INTERFACE, WF_PART_INTERIOR_B)):
+            y = torch.zeros_like(x)
+            for part in parts:
+                op.apply_part(x, y, part)
+            torch.cuda.synchronize()
+            assert relerr(y.cpu().numpy(), yall.cpu().numpy()) <= TOL_FORM, (split, parts)
+    assert counts[0][0] > 0 and counts[1] != counts[0], counts   # the second ghost set moved items to the interface
+
+
 @pytest.mark.parametrize("p,n", [(2, (7, 6, 9)), (4, (10, 9, 8))])
 def test_owner_applies_are_bitwise_repeatable(gpu, oracle, p, n):
     import torch

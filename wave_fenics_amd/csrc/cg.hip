@@ -16,7 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "common.h"
+#include "device_array.h"
 
 namespace wf {
 
@@ -103,17 +103,6 @@ __global__ void k_cg_roll(double* sc)
   sc[kS_pAp] = 0.0;
 }
 
-struct Bufs {
-  double *r = nullptr, *p = nullptr, *y = nullptr, *sc = nullptr;
-  ~Bufs()
-  {
-    (void)hipFree(r);
-    (void)hipFree(p);
-    (void)hipFree(y);
-    (void)hipFree(sc);
-  }
-};
-
 }  // namespace
 }  // namespace wf
 
@@ -133,16 +122,16 @@ extern "C" int wf_cg(const wf_cg_desc* d, double* d_x, const double* d_b, int* i
   if (iterations) *iterations = 0;
   if (rel_residual) *rel_residual = 0.0;
   if (n == 0 && !d->comm) return WF_OK;
-  Bufs B;
-  const size_t bytes = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
-  WF_HIP_CHECK(hipMalloc((void**)&B.r, bytes));
-  WF_HIP_CHECK(hipMalloc((void**)&B.p, bytes));
-  WF_HIP_CHECK(hipMalloc((void**)&B.y, bytes));
-  WF_HIP_CHECK(hipMalloc((void**)&B.sc, kS_count * sizeof(double)));
+  DevArray<double> buf_r, buf_p, buf_y, buf_sc;
+  const size_t len = (size_t)std::max<int64_t>(n, 1), bytes = len * sizeof(double);
+  int rc;
+  if ((rc = buf_r.alloc(len)) != WF_OK || (rc = buf_p.alloc(len)) != WF_OK || (rc = buf_y.alloc(len)) != WF_OK
+      || (rc = buf_sc.alloc(kS_count)) != WF_OK)
+    return rc;
+  const struct { double *r, *p, *y, *sc; } B{buf_r.data(), buf_p.data(), buf_y.data(), buf_sc.data()};
   WF_HIP_CHECK(hipMemsetAsync(B.sc, 0, kS_count * sizeof(double), s));
   const int32_t* d_ghost = nullptr;
   int32_t nghost = 0;
-  int rc;
   if (d->updater && (rc = wf_updater_ghosts(d->updater, &d_ghost, &nghost)) != WF_OK) return rc;
 
   // y = A v with the halo exchanges of a partitioned mesh around it (LinearGLL.hpp:164-176)

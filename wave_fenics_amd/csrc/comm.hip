@@ -21,7 +21,7 @@
 #include <memory>
 #include <thread>
 
-#include "common.h"
+#include "device_array.h"
 
 namespace {
 
@@ -107,7 +107,7 @@ RcclApi* rccl()
 struct wf_comm {
   ncclComm_t comm = nullptr;
   int rank = 0, nranks = 1;
-  double* d_scratch = nullptr;   // one double for barrier / scalar reductions
+  wf::DevArray<double> d_scratch;   // barrier / scalar reductions: one double in, one out
 };
 
 struct wf_updater {
@@ -115,10 +115,10 @@ struct wf_updater {
   int ndofs = 0;
   std::vector<int> send_nb, recv_nb;
   std::vector<int32_t> send_off, recv_off;   // displs_send_fwd / displs_recv_fwd (VectorUpdater.hpp:34-46)
-  int32_t* d_indices = nullptr;              // scatter_fwd_indices            (VectorUpdater.hpp:49-52)
-  int32_t* d_ghost_pos = nullptr;            // scatter_fwd_ghost_positions    (VectorUpdater.hpp:55-59)
-  double* d_send_buffer = nullptr;           // (VectorUpdater.hpp:62-63)
-  double* d_recv_buffer = nullptr;
+  wf::DevArray<int32_t> d_indices;           // scatter_fwd_indices            (VectorUpdater.hpp:49-52)
+  wf::DevArray<int32_t> d_ghost_pos;         // scatter_fwd_ghost_positions    (VectorUpdater.hpp:55-59)
+  wf::DevArray<double> d_send_buffer;        // (VectorUpdater.hpp:62-63)
+  wf::DevArray<double> d_recv_buffer;
   int32_t nsend = 0, nrecv = 0;
   int flags = 0;
   hipStream_t comm_stream = nullptr;         // the exchange runs here unless WF_UPDATER_INLINE
@@ -137,10 +137,6 @@ namespace {
 void free_updater(wf_updater* u)
 {
   if (!u) return;
-  (void)hipFree(u->d_indices);
-  (void)hipFree(u->d_ghost_pos);
-  (void)hipFree(u->d_send_buffer);
-  (void)hipFree(u->d_recv_buffer);
   if (u->ev_packed) (void)hipEventDestroy(u->ev_packed);
   if (u->ev_done) (void)hipEventDestroy(u->ev_done);
   if (u->ev_main) (void)hipEventDestroy(u->ev_main);
@@ -199,7 +195,7 @@ int wait_exchange(wf_updater* u, hipStream_t user, bool inl)
 int fwd_begin(wf_updater* u, const double* d_x, hipStream_t s, bool inl)
 {
   wf::MarkerScope mk("update_fwd_begin");
-  return begin(u, u->d_indices, u->nsend, d_x, u->d_send_buffer, u->send_off, u->send_nb, u->d_recv_buffer, u->recv_off,
+  return begin(u, u->d_indices.data(), u->nsend, d_x, u->d_send_buffer.data(), u->send_off, u->send_nb, u->d_recv_buffer.data(), u->recv_off,
                u->recv_nb, s, inl);
 }
 // VectorUpdater.hpp:133-143: wait, copy into the ghost entries
@@ -208,13 +204,13 @@ int fwd_end(wf_updater* u, double* d_x, hipStream_t s, bool inl)
   wf::MarkerScope mk("update_fwd_end");
   int rc = wait_exchange(u, s, inl);
   if (rc != WF_OK) return rc;
-  return wf_scatter_set(u->nrecv, u->d_ghost_pos, u->d_recv_buffer, d_x, s);
+  return wf_scatter_set(u->nrecv, u->d_ghost_pos.data(), u->d_recv_buffer.data(), d_x, s);
 }
 // VectorUpdater.hpp:157-189: the buffers swap roles: pack the ghost entries, send them to their owners
 int rev_begin(wf_updater* u, const double* d_x, hipStream_t s, bool inl)
 {
   wf::MarkerScope mk("update_rev_begin");
-  return begin(u, u->d_ghost_pos, u->nrecv, d_x, u->d_recv_buffer, u->recv_off, u->recv_nb, u->d_send_buffer, u->send_off,
+  return begin(u, u->d_ghost_pos.data(), u->nrecv, d_x, u->d_recv_buffer.data(), u->recv_off, u->recv_nb, u->d_send_buffer.data(), u->send_off,
                u->send_nb, s, inl);
 }
 // VectorUpdater.hpp:191-199: wait, accumulate into the owned entries (atomic add, scatter.cu:43)
@@ -223,7 +219,7 @@ int rev_end(wf_updater* u, double* d_x, hipStream_t s, bool inl)
   wf::MarkerScope mk("update_rev_end");
   int rc = wait_exchange(u, s, inl);
   if (rc != WF_OK) return rc;
-  return wf_scatter_add(u->nsend, u->d_indices, u->d_send_buffer, d_x, s);
+  return wf_scatter_add(u->nsend, u->d_indices.data(), u->d_send_buffer.data(), d_x, s);
 }
 inline bool is_inline(const wf_updater* u) { return (u->flags & WF_UPDATER_INLINE) != 0; }
 
@@ -255,8 +251,8 @@ int wf_comm_create(const char* id, int rank, int nranks, wf_comm** out)
   c->rank = rank;
   c->nranks = nranks;
   WF_NCCL_CHECK(api, api->CommInitRank(&c->comm, nranks, uid, rank));
-  WF_HIP_CHECK(hipMalloc((void**)&c->d_scratch, 2 * sizeof(double)));
-  WF_HIP_CHECK(hipMemset(c->d_scratch, 0, 2 * sizeof(double)));
+  if (int rc = c->d_scratch.alloc(2)) return rc;
+  WF_HIP_CHECK(hipMemset(c->d_scratch.data(), 0, c->d_scratch.bytes()));
   *out = c.release();
   return WF_OK;
 }
@@ -342,7 +338,7 @@ int wf_comm_allreduce(wf_comm* comm, int op, int64_t count, const double* d_in, 
 int wf_comm_barrier(wf_comm* comm, void* stream)
 {
   WF_REQUIRE(comm != nullptr, "wf_comm_barrier: null handle");
-  int rc = wf_comm_allreduce(comm, WF_SUM, 1, comm->d_scratch, comm->d_scratch + 1, stream);
+  int rc = wf_comm_allreduce(comm, WF_SUM, 1, comm->d_scratch.data(), comm->d_scratch.data() + 1, stream);
   if (rc != WF_OK) return rc;
   WF_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
   return WF_OK;
@@ -351,7 +347,7 @@ int wf_comm_barrier(wf_comm* comm, void* stream)
 int wf_comm_destroy(wf_comm* comm)
 {
   if (!comm) return WF_OK;
-  (void)hipFree(comm->d_scratch);
+  comm->d_scratch.reset();
   if (comm->comm && g_rccl) (void)g_rccl->CommDestroy(comm->comm);
   delete comm;
   return WF_OK;
@@ -395,16 +391,11 @@ int wf_updater_create(wf_comm* comm, const wf_updater_desc* desc, wf_updater** o
     WF_REQUIRE(desc->send_indices[i] >= 0 && desc->send_indices[i] < desc->ndofs, "wf_updater_create: send index out of range");
   for (int32_t i = 0; i < u->nrecv; ++i)
     WF_REQUIRE(desc->ghost_positions[i] >= 0 && desc->ghost_positions[i] < desc->ndofs, "wf_updater_create: ghost position out of range");
-  if (u->nsend) {
-    WF_HIP_CHECK(hipMalloc((void**)&u->d_indices, (size_t)u->nsend * sizeof(int32_t)));
-    WF_HIP_CHECK(hipMemcpy(u->d_indices, desc->send_indices, (size_t)u->nsend * sizeof(int32_t), hipMemcpyHostToDevice));
-    WF_HIP_CHECK(hipMalloc((void**)&u->d_send_buffer, (size_t)u->nsend * sizeof(double)));
-  }
-  if (u->nrecv) {
-    WF_HIP_CHECK(hipMalloc((void**)&u->d_ghost_pos, (size_t)u->nrecv * sizeof(int32_t)));
-    WF_HIP_CHECK(hipMemcpy(u->d_ghost_pos, desc->ghost_positions, (size_t)u->nrecv * sizeof(int32_t), hipMemcpyHostToDevice));
-    WF_HIP_CHECK(hipMalloc((void**)&u->d_recv_buffer, (size_t)u->nrecv * sizeof(double)));
-  }
+  int rc;
+  if ((rc = u->d_indices.upload(desc->send_indices, (size_t)u->nsend)) != WF_OK) return rc;
+  if ((rc = u->d_send_buffer.alloc((size_t)u->nsend)) != WF_OK) return rc;
+  if ((rc = u->d_ghost_pos.upload(desc->ghost_positions, (size_t)u->nrecv)) != WF_OK) return rc;
+  if ((rc = u->d_recv_buffer.alloc((size_t)u->nrecv)) != WF_OK) return rc;
   int prio_low = 0, prio_high = 0;
   WF_HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_low, &prio_high));
   WF_HIP_CHECK(hipStreamCreateWithPriority(&u->comm_stream, hipStreamNonBlocking, prio_high));
@@ -464,7 +455,7 @@ int wf_updater_info(const wf_updater* u, int* num_send, int* num_recv, int* num_
 int wf_updater_ghosts(const wf_updater* u, const int32_t** d_ghost_pos, int32_t* nghost)
 {
   WF_REQUIRE(u && d_ghost_pos && nghost, "wf_updater_ghosts: null argument");
-  *d_ghost_pos = u->d_ghost_pos;
+  *d_ghost_pos = u->d_ghost_pos.data();
   *nghost = u->nrecv;
   return WF_OK;
 }

@@ -211,15 +211,11 @@ int launch_stiffness_march_ks_box(int P, int bx, int by, int nx, int ny, int nz,
 int launch_stiffness_march_ks_idx(int P, int bx, int by, const MarchPlanDev& pd, const double* d_G6blk, const double* d_D,
                                   const DMat& dm, double coeff, const double* d_x, double* d_y, const int32_t* d_items,
                                   int nitems, hipStream_t s);
-// host vector to a fresh device array (empty: null), its bytes added to *total
-template <typename Tp>
-int upload_vec(Tp** p, const std::vector<Tp>& h, size_t* total)
+// host-side validation of indices a kernel will dereference: WF_ERR_INVALID with `message` unless every
+// idx[e], e < count, lies in [0, bound)
+inline int check_index_range(const int32_t* idx, size_t count, int64_t bound, const std::string& message)
 {
-  *p = nullptr;
-  if (h.empty()) return WF_OK;
-  WF_HIP_CHECK(hipMalloc((void**)p, h.size() * sizeof(Tp)));
-  WF_HIP_CHECK(hipMemcpy(*p, h.data(), h.size() * sizeof(Tp), hipMemcpyHostToDevice));
-  *total += h.size() * sizeof(Tp);
+  for (size_t e = 0; e < count; ++e) WF_REQUIRE(idx[e] >= 0 && idx[e] < bound, message);
   return WF_OK;
 }
 

@@ -281,7 +281,7 @@ int build_march_plan(int P, size_t ncells, const int32_t* tdm, int BX, int BY, i
   // ---- 3. columns and z segments = work items ----------------------------------
   // Segment length: work items run in rounds of the 512 resident workgroups (2 per CU) and each
   // pays ~1.5 layers of pipeline fill; pick the lz <= lz_max that minimises rounds * (lz + 1.5)
-  // (the rule of the box operator, api.hip).
+  // (the rule of the box operator, choose_box_stiffness in op_create_box.hip).
   if (lz_fixed > 0) {
     lz = std::min(lz_max, lz_fixed);
   } else {

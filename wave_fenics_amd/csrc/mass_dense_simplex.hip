@@ -29,7 +29,7 @@
 #include <cstring>
 #include <memory>
 
-#include "common.h"
+#include "device_array.h"
 
 namespace wf {
 
@@ -230,26 +230,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
 
 struct DenseMassData {
   int nd = 0, nq = 0, KT = 0, DT = 0, ncells = 0, nbatch = 0, numax = 0;
-  double* d_A = nullptr;
-  double* d_s = nullptr;
-  uint32_t* d_locP = nullptr;
-  int32_t* d_uoff = nullptr;
-  int32_t* d_uniq = nullptr;
-  size_t bytes = 0;
+  DevArray<double> d_A, d_s;
+  DevArray<uint32_t> d_locP;
+  DevArray<int32_t> d_uoff, d_uniq;
 };
 
-void dense_mass_free(DenseMassData* d)
-{
-  if (!d) return;
-  (void)hipFree(d->d_A);
-  (void)hipFree(d->d_s);
-  (void)hipFree(d->d_locP);
-  (void)hipFree(d->d_uoff);
-  (void)hipFree(d->d_uniq);
-  delete d;
-}
+void dense_mass_free(DenseMassData* d) { delete d; }
 
-size_t dense_mass_bytes(const DenseMassData* d) { return d ? d->bytes : 0; }
+size_t dense_mass_bytes(const DenseMassData* d)
+{
+  return d ? d->d_A.bytes() + d->d_s.bytes() + d->d_locP.bytes() + d->d_uoff.bytes() + d->d_uniq.bytes() : 0;
+}
 
 // Compiled tile pairs (KT, DT): Lagrange P1..P4 on the tetrahedron, nd = 4, 10, 20, 35.  Any nd with the same tile
 // counts runs on them; nq does not enter the kernel.
@@ -309,11 +300,11 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
     return WF_ERR_UNSUPPORTED;
   }
   int rc;
-  if ((rc = upload_vec(&d->d_A, A, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_s, sc, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_locP, plan.locP, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_uoff, plan.uoff, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_uniq, plan.uniq, &d->bytes)) != WF_OK) return rc;
+  if ((rc = d->d_A.upload(A)) != WF_OK) return rc;
+  if ((rc = d->d_s.upload(sc)) != WF_OK) return rc;
+  if ((rc = d->d_locP.upload(plan.locP)) != WF_OK) return rc;
+  if ((rc = d->d_uoff.upload(plan.uoff)) != WF_OK) return rc;
+  if ((rc = d->d_uniq.upload(plan.uniq)) != WF_OK) return rc;
   *out = d.release();
   return WF_OK;
 }
@@ -325,7 +316,7 @@ static int launch_mass_simplex_t(const DenseMassData* d, const double* d_x, doub
   const size_t lds = ((size_t)16 * DT * dense_pitch(KT) + 2 * d->numax) * sizeof(double);
   const unsigned nb = (unsigned)std::min(d->nbatch, kMassGridBound);   // persistent: A is staged into LDS once per workgroup
   hipLaunchKernelGGL((k_mass_dense_simplex<KT, DT, NW, NU>), dim3(nb), dim3(64 * NW), lds, s, d->nd, d->ncells, d->nbatch,
-                     d->numax, d->d_A, d->d_s, d->d_locP, d->d_uoff, d->d_uniq, d_x, d_y);
+                     d->numax, d->d_A.data(), d->d_s.data(), d->d_locP.data(), d->d_uoff.data(), d->d_uniq.data(), d_x, d_y);
   return launch_status("mass_dense_simplex");
 }
 

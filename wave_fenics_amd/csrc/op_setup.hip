@@ -1,0 +1,199 @@
+// Set-up steps shared by the operator creation paths (op.h): tables, geometry staging, batch-unique lists, the
+// caller's tensor frame.
+#include <cmath>
+#include <cstring>
+
+#include "op.h"
+
+namespace wf {
+
+OpPtr new_op(int kind, int P, int nd, int nq, int ncells, int ndofs, double c0, const wf_tuning* tuning)
+{
+  OpPtr op(new wf_op);
+  op->kind = kind;
+  op->P = P;
+  op->n = P + 1;
+  op->nd = nd;
+  op->nq = nq;
+  op->ncells = ncells;
+  op->ndofs = ndofs;
+  op->coeff = -1.0 * c0 * c0;   // operators.hpp:115
+  op->tun = tuning ? *tuning : wf_tuning{};
+  return op;
+}
+
+int upload_tables(int P, DevArray<double>& d_pts, DevArray<double>& d_wts)
+{
+  const int n = P + 1;
+  std::vector<double> pts(n), wts(n);
+  gll_points_weights(n, pts.data(), wts.data());
+  int rc = d_pts.upload(pts);
+  if (rc != WF_OK) return rc;
+  return d_wts.upload(wts);
+}
+
+// Batch-unique gather/scatter lists: for every batch of CB consecutive cells the
+// sorted list of its distinct dofs (uniq, offsets uoff) and the position of each
+// element-local dof in that list (loc).  Kernels read x once per unique dof, sum
+// the batch in LDS and issue one global atomic per unique dof.
+int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB)
+{
+  if (ncells == 0) return WF_OK;
+  if ((size_t)CB * nd > 65535) {
+    set_error("build_unique_lists: batch too large for 16-bit local indices");
+    return WF_ERR_UNSUPPORTED;
+  }
+  const size_t nbatch = (ncells + CB - 1) / CB;
+  std::vector<int32_t> tdm(ncells * nd);
+  WF_HIP_CHECK(hipMemcpy(tdm.data(), op->d_dofmap.data(), tdm.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  std::vector<int32_t> uoff(nbatch + 1, 0), uniq, tmp;
+  std::vector<uint16_t> loc(ncells * nd);
+  uniq.reserve(ncells * nd / 2);
+  for (size_t b = 0; b < nbatch; ++b) {
+    const size_t c0 = b * CB, nc = std::min<size_t>(CB, ncells - c0);
+    tmp.assign(tdm.begin() + c0 * nd, tdm.begin() + (c0 + nc) * nd);
+    std::sort(tmp.begin(), tmp.end());
+    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+    for (size_t e = c0 * nd; e < (c0 + nc) * nd; ++e)
+      loc[e] = (uint16_t)(std::lower_bound(tmp.begin(), tmp.end(), tdm[e]) - tmp.begin());
+    uniq.insert(uniq.end(), tmp.begin(), tmp.end());
+    uoff[b + 1] = (int32_t)uniq.size();
+  }
+  int rc;
+  if ((rc = op->d_uoff.upload(uoff)) != WF_OK) return rc;
+  if ((rc = op->d_uniq.upload(uniq)) != WF_OK) return rc;
+  if ((rc = op->d_loc.upload(loc)) != WF_OK) return rc;
+  op->unique_cb = CB;
+  return WF_OK;
+}
+
+// Geometry of every cell at the n1^3 points of a 1-D rule, computed from the mesh into whichever of the device arrays
+// d_G9[ncells][n1^3][9], d_G6blk (blocked by cells_per_batch(n1 - 1)) and d_detJ[ncells][n1^3] (det J * w) are given.
+// The kernel is generic in the number of points per direction.
+int mesh_geometry_rule(int n1, const double* h_pts, const double* h_wts, const HexMesh& mesh, int use_fabs, int clamp,
+                       double* d_G9, double* d_G6blk, double* d_detJ)
+{
+  DevArray<double> d_x, d_pts, d_wts;
+  DevArray<int32_t> d_gd;
+  int rc;
+  if ((rc = d_x.upload(mesh.xverts, (size_t)mesh.nverts * 3)) != WF_OK) return rc;
+  if ((rc = d_gd.upload(mesh.geom_dofmap, mesh.ncells * 8)) != WF_OK) return rc;
+  if ((rc = d_pts.upload(h_pts, (size_t)n1)) != WF_OK) return rc;
+  if ((rc = d_wts.upload(h_wts, (size_t)n1)) != WF_OK) return rc;
+  if ((rc = launch_geometry_hex(n1 - 1, (int)mesh.ncells, d_x.data(), d_gd.data(), d_pts.data(), d_wts.data(), use_fabs,
+                                clamp, d_G9, d_G6blk, d_detJ, nullptr)) != WF_OK)
+    return rc;
+  WF_HIP_CHECK(hipDeviceSynchronize());
+  return WF_OK;
+}
+
+// det J * w per cell and point of a dense mass with a square table, on the host: the caller's h_detJ (caller's point
+// order), else computed from the mesh at the caller's rule into hd (*raw_points: the engine's point order)
+int host_detJ(const wf_op_desc* desc, std::vector<double>& hd, const double** hsrc, bool* raw_points)
+{
+  *hsrc = desc->h_detJ;
+  *raw_points = !desc->h_detJ;
+  if (desc->h_detJ) return WF_OK;
+  const int n = desc->nq1;
+  DevArray<double> d_det;
+  hd.resize((size_t)desc->ncells * n * n * n);
+  int rc;
+  if ((rc = d_det.alloc(hd.size())) != WF_OK) return rc;
+  const HexMesh mesh{(size_t)desc->ncells, desc->nverts, desc->h_xverts, desc->h_geom_dofmap};
+  if ((rc = mesh_geometry_rule(n, desc->h_qpts1, desc->h_qwts1, mesh, fabs_flag(desc->flags), 0, nullptr, nullptr, d_det.data())) != WF_OK)
+    return rc;
+  WF_HIP_CHECK(hipMemcpy(hd.data(), d_det.data(), hd.size() * sizeof(double), hipMemcpyDeviceToHost));
+  *hsrc = hd.data();
+  return WF_OK;
+}
+
+// Uploads the 1-D tables to op->d_D: D, then its transpose (scalar-loaded by the k-split kernel); op->dm = D.
+// box: then the 1-D weights (per-cell marching kernel), then A = D^T diag(w) D (axes form: A[i][a] = sum_q D[q][i] w_q
+// D[q][a], summed in long double and rounded once); op->am = A.
+int upload_derivative_tables(wf_op* op, bool box)
+{
+  const int P = op->P, n = op->n;
+  std::vector<double> D(box ? 3 * n * n + n : 2 * n * n);
+  gll_derivative_matrix(P, D.data());
+  for (int q = 0; q < n; ++q)
+    for (int a2 = 0; a2 < n; ++a2) D[n * n + a2 * n + q] = D[q * n + a2];
+  for (int q = 0; q < n * n; ++q) op->dm.v[q] = D[q];
+  if (box) {
+    std::vector<double> pts(n);
+    double* w = D.data() + 2 * n * n;
+    gll_points_weights(n, pts.data(), w);
+    double* A = w + n;
+    for (int i = 0; i < n; ++i)
+      for (int a2 = i; a2 < n; ++a2) {
+        long double s = 0.0L;
+        for (int q = 0; q < n; ++q) s += (long double)D[q * n + i] * (long double)w[q] * (long double)D[q * n + a2];
+        A[i * n + a2] = A[a2 * n + i] = (double)s;
+      }
+    for (int q = 0; q < n * n; ++q) op->am.v[q] = A[q];
+  }
+  return op->d_D.upload(D);
+}
+
+// Stages geometry given as G[slot][nd][3][3] (the reference layout, precomputation.hpp:46) into the blocked upper
+// triangle d_G6blk, in slabs of 64 MiB to bound the temporary.  direct: the caller's array when it is in slot order
+// already; otherwise fill_slot(slot, dst) writes the nd * 9 values of a slot (zeros for an empty one).
+int stage_G9(int P, int CB, size_t nslots, const double* direct, const std::function<void(size_t, double*)>& fill_slot,
+             double* d_G6blk)
+{
+  const int n = P + 1, nd = n * n * n;
+  const size_t slab_slots = std::max<size_t>(CB, (((size_t)64 << 20) / (nd * 9 * sizeof(double))) / CB * CB);
+  DevArray<double> d_G9;
+  int rc;
+  if ((rc = d_G9.alloc(std::min(slab_slots, nslots) * nd * 9)) != WF_OK) return rc;
+  std::vector<double> slab;
+  for (size_t s0 = 0; s0 < nslots; s0 += slab_slots) {
+    const size_t ns = std::min(slab_slots, nslots - s0);
+    const double* hsrc = direct ? direct + s0 * nd * 9 : nullptr;
+    if (!hsrc) {
+      slab.resize(ns * nd * 9);
+      for (size_t q = 0; q < ns; ++q) fill_slot(s0 + q, &slab[q * nd * 9]);
+      hsrc = slab.data();
+    }
+    WF_HIP_CHECK(hipMemcpy(d_G9.data(), hsrc, ns * nd * 9 * sizeof(double), hipMemcpyHostToDevice));
+    // slabs start on a batch boundary, so the packed destination is offset by whole batches
+    if ((rc = launch_pack_G6(P, CB, (int)ns, d_G9.data(), d_G6blk + (s0 / CB) * CB * nd * 6, nullptr)) != WF_OK) return rc;
+    WF_HIP_CHECK(hipDeviceSynchronize());
+  }
+  return WF_OK;
+}
+
+CallerFrame::CallerFrame(const wf_op_desc* desc, int n) : xslow((desc->flags & WF_FLAG_TENSOR_X_SLOWEST) != 0), h_perm(desc->h_perm)
+{
+  if (!xslow) return;
+  eff_perm.resize((size_t)n * n * n);
+  for (int k = 0; k < n; ++k)
+    for (int j = 0; j < n; ++j)
+      for (int i = 0; i < n; ++i) {
+        const int lp = (i * n + j) * n + k;
+        eff_perm[i + n * (j + n * k)] = h_perm ? h_perm[lp] : lp;
+      }
+}
+
+std::vector<int32_t> CallerFrame::qmap(int m) const
+{
+  std::vector<int32_t> q((size_t)m * m * m);
+  for (int k = 0; k < m; ++k)
+    for (int j = 0; j < m; ++j)
+      for (int i = 0; i < m; ++i) q[i + m * (j + m * k)] = xslow ? (i * m + j) * m + k : i + m * (j + m * k);
+  return q;
+}
+
+const std::vector<int32_t>& PointMaps::operator()(int code)
+{
+  auto& m = maps[code];
+  if (m.empty()) {
+    const std::vector<int32_t> qm = fr.qmap(n);
+    m.resize((size_t)n * n * n);
+    for (int k = 0; k < n; ++k)
+      for (int j = 0; j < n; ++j)
+        for (int i = 0; i < n; ++i) m[i + n * (j + n * k)] = qm[orient_local_index(code, n, i, j, k)];
+  }
+  return m;
+}
+
+}  // namespace wf

@@ -24,7 +24,7 @@
 #include <cstring>
 #include <memory>
 
-#include "common.h"
+#include "device_array.h"
 
 namespace wf {
 
@@ -378,28 +378,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
 struct DenseOpData {
   int nd = 0, nq = 0, QT = 0, KT = 0, DT = 0, nbatch = 0, numax = 0, nw = 4;
-  double* d_T = nullptr;
-  double* d_w = nullptr;
-  double* d_C = nullptr;
-  uint32_t* d_locP = nullptr;
-  int32_t* d_uoff = nullptr;
-  int32_t* d_uniq = nullptr;
-  uint8_t* d_clampb = nullptr;
-  size_t bytes = 0;
+  DevArray<double> d_T, d_w, d_C;
+  DevArray<uint32_t> d_locP;
+  DevArray<int32_t> d_uoff, d_uniq;
+  DevArray<uint8_t> d_clampb;
 };
 
-void dense_free(DenseOpData* d)
-{
-  if (!d) return;
-  (void)hipFree(d->d_T);
-  (void)hipFree(d->d_w);
-  (void)hipFree(d->d_C);
-  (void)hipFree(d->d_locP);
-  (void)hipFree(d->d_uoff);
-  (void)hipFree(d->d_uniq);
-  (void)hipFree(d->d_clampb);
-  delete d;
-}
+void dense_free(DenseOpData* d) { delete d; }
 
 // Compiled shapes (QT, KT, DT, XR): Lagrange P1..P4 on the tetrahedron with the m = p Gauss-Jacobi
 // rule, (nd, nq) = (4,1) (10,8) (20,27) (35,64), plus P4 with the m = 3 rule.  The XR = 0 form of a
@@ -541,18 +526,23 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
     if (hit) clampb[c / NCB] = 1;
   }
   int rc;
-  if ((rc = upload_vec(&d->d_T, T, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_w, w, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_C, C, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_locP, plan.locP, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_uoff, plan.uoff, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_uniq, plan.uniq, &d->bytes)) != WF_OK) return rc;
-  if ((rc = upload_vec(&d->d_clampb, clampb, &d->bytes)) != WF_OK) return rc;
+  if ((rc = d->d_T.upload(T)) != WF_OK) return rc;
+  if ((rc = d->d_w.upload(w)) != WF_OK) return rc;
+  if ((rc = d->d_C.upload(C)) != WF_OK) return rc;
+  if ((rc = d->d_locP.upload(plan.locP)) != WF_OK) return rc;
+  if ((rc = d->d_uoff.upload(plan.uoff)) != WF_OK) return rc;
+  if ((rc = d->d_uniq.upload(plan.uniq)) != WF_OK) return rc;
+  if ((rc = d->d_clampb.upload(clampb)) != WF_OK) return rc;
   *out = d.release();
   return WF_OK;
 }
 
-size_t dense_bytes(const DenseOpData* d) { return d ? d->bytes : 0; }
+size_t dense_bytes(const DenseOpData* d)
+{
+  return d ? d->d_T.bytes() + d->d_w.bytes() + d->d_C.bytes() + d->d_locP.bytes() + d->d_uoff.bytes() + d->d_uniq.bytes()
+                 + d->d_clampb.bytes()
+           : 0;
+}
 
 template <int QT, int KT, int DT, int NW, int NU, int XR>
 static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,
@@ -576,9 +566,9 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
   const int wgs_per_cu = 2, ablate = 0, stagger = 0;
 #endif
   const unsigned nb = (unsigned)std::min(d->nbatch, 256 * wgs_per_cu);   // persistent: the table is staged into LDS once per workgroup
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * NW), lds, s, d->nd, d->nq, d->nbatch, d->numax, d->d_T, d->d_w, d->d_C,
-                     d->d_locP, d->d_uoff, d->d_uniq, d->d_clampb, coeff, do_clamp, d_x, d_y,
-                     ablate, stagger);
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * NW), lds, s, d->nd, d->nq, d->nbatch, d->numax, d->d_T.data(),
+                     d->d_w.data(), d->d_C.data(), d->d_locP.data(), d->d_uoff.data(), d->d_uniq.data(), d->d_clampb.data(),
+                     coeff, do_clamp, d_x, d_y, ablate, stagger);
   return launch_status("stiffness_dense");
 }
 

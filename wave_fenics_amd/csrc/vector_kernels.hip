@@ -8,7 +8,7 @@
 #include <vector>
 #include <type_traits>
 
-#include "common.h"
+#include "device_array.h"
 
 namespace wf {
 
@@ -437,12 +437,12 @@ int wf_dot(int64_t n, const double* d_x, const double* d_y, double* d_result, vo
 struct wf_boundary {
   int64_t n = 0;
   int32_t nb = 0, n1 = 0, n2 = 0;
-  unsigned long long* d_mask = nullptr;
-  uint32_t* d_prefix = nullptr;
-  double *d_c1 = nullptr, *d_c2 = nullptr;
+  wf::DevArray<unsigned long long> d_mask;
+  wf::DevArray<uint32_t> d_prefix;
+  wf::DevArray<double> d_c1, d_c2;
   // the plain index form as well (first right-hand side of a run, reference-order loop)
-  int32_t *d_idx1 = nullptr, *d_idx2 = nullptr;
-  double *d_m1 = nullptr, *d_m2 = nullptr;
+  wf::DevArray<int32_t> d_idx1, d_idx2;
+  wf::DevArray<double> d_m1, d_m2;
 };
 
 namespace {
@@ -479,10 +479,10 @@ int rk4_stage_impl(int64_t n, double bdt, double adt_next, int has_next, double*
   a.vn_next = d_vn_next;
   const bool use_bc = bcp && bcp->nb > 0;
   if (use_bc) {
-    a.bc.mask = bcp->d_mask;
-    a.bc.prefix = bcp->d_prefix;
-    a.bc.c1 = bcp->d_c1;
-    a.bc.c2 = bcp->d_c2;
+    a.bc.mask = bcp->d_mask.data();
+    a.bc.prefix = bcp->d_prefix.data();
+    a.bc.c1 = bcp->d_c1.data();
+    a.bc.c2 = bcp->d_c2.data();
     a.bc.s1 = s1_next;
     a.bc.s2 = s2;
   }
@@ -529,15 +529,6 @@ int wf_rk4_stage_bc(int64_t n, double bdt, double adt_next, int has_next, double
 
 int wf_boundary_destroy(wf_boundary* bc)
 {
-  if (!bc) return WF_OK;
-  (void)hipFree(bc->d_mask);
-  (void)hipFree(bc->d_prefix);
-  (void)hipFree(bc->d_c1);
-  (void)hipFree(bc->d_c2);
-  (void)hipFree(bc->d_idx1);
-  (void)hipFree(bc->d_idx2);
-  (void)hipFree(bc->d_m1);
-  (void)hipFree(bc->d_m2);
   delete bc;
   return WF_OK;
 }
@@ -548,8 +539,9 @@ int wf_boundary_create(int64_t n, int32_t n1, const int32_t* h_idx1, const doubl
   WF_REQUIRE(out && n >= 0 && n1 >= 0 && n2 >= 0, "wf_boundary_create: bad argument");
   *out = nullptr;
   WF_REQUIRE((n1 == 0 || (h_idx1 && h_m1)) && (n2 == 0 || (h_idx2 && h_m2)), "wf_boundary_create: null array");
-  for (int32_t i = 0; i < n1; ++i) WF_REQUIRE(h_idx1[i] >= 0 && h_idx1[i] < n, "wf_boundary_create: index out of range");
-  for (int32_t i = 0; i < n2; ++i) WF_REQUIRE(h_idx2[i] >= 0 && h_idx2[i] < n, "wf_boundary_create: index out of range");
+  int rc;
+  if ((rc = wf::check_index_range(h_idx1, (size_t)n1, n, "wf_boundary_create: index out of range")) != WF_OK) return rc;
+  if ((rc = wf::check_index_range(h_idx2, (size_t)n2, n, "wf_boundary_create: index out of range")) != WF_OK) return rc;
   const size_t nw = (size_t)((n + 63) / 64) + 1;   // + 1: the stage kernel reads two words per wave
   std::vector<unsigned long long> mask(nw, 0ull);
   for (int32_t i = 0; i < n1; ++i) mask[h_idx1[i] >> 6] |= 1ull << (h_idx1[i] & 63);
@@ -567,23 +559,15 @@ int wf_boundary_create(int64_t n, int32_t n1, const int32_t* h_idx1, const doubl
   std::vector<double> c1((size_t)nb, 0.0), c2((size_t)nb, 0.0);
   for (int32_t i = 0; i < n1; ++i) c1[rank(h_idx1[i])] += h_m1[i];   // a repeated index accumulates, like wf_boundary_apply
   for (int32_t i = 0; i < n2; ++i) c2[rank(h_idx2[i])] += h_m2[i];
-  std::unique_ptr<wf_boundary, int (*)(wf_boundary*)> bc(new wf_boundary, wf_boundary_destroy);
+  auto bc = std::make_unique<wf_boundary>();
   bc->n = n;
   bc->nb = nb;
   bc->n1 = n1;
   bc->n2 = n2;
-  auto up = [](auto** d, const auto* h, size_t cnt) -> int {
-    *d = nullptr;
-    if (cnt == 0) return WF_OK;
-    WF_HIP_CHECK(hipMalloc((void**)d, cnt * sizeof(**d)));
-    WF_HIP_CHECK(hipMemcpy(*d, h, cnt * sizeof(**d), hipMemcpyHostToDevice));
-    return WF_OK;
-  };
-  int rc;
-  if ((rc = up(&bc->d_mask, mask.data(), nw)) != WF_OK || (rc = up(&bc->d_prefix, prefix.data(), nw)) != WF_OK
-      || (rc = up(&bc->d_c1, c1.data(), (size_t)nb)) != WF_OK || (rc = up(&bc->d_c2, c2.data(), (size_t)nb)) != WF_OK
-      || (rc = up(&bc->d_idx1, h_idx1, (size_t)n1)) != WF_OK || (rc = up(&bc->d_m1, h_m1, (size_t)n1)) != WF_OK
-      || (rc = up(&bc->d_idx2, h_idx2, (size_t)n2)) != WF_OK || (rc = up(&bc->d_m2, h_m2, (size_t)n2)) != WF_OK)
+  if ((rc = bc->d_mask.upload(mask)) != WF_OK || (rc = bc->d_prefix.upload(prefix)) != WF_OK
+      || (rc = bc->d_c1.upload(c1)) != WF_OK || (rc = bc->d_c2.upload(c2)) != WF_OK
+      || (rc = bc->d_idx1.upload(h_idx1, (size_t)n1)) != WF_OK || (rc = bc->d_m1.upload(h_m1, (size_t)n1)) != WF_OK
+      || (rc = bc->d_idx2.upload(h_idx2, (size_t)n2)) != WF_OK || (rc = bc->d_m2.upload(h_m2, (size_t)n2)) != WF_OK)
     return rc;
   *out = bc.release();
   return WF_OK;
@@ -593,7 +577,8 @@ int wf_boundary_create(int64_t n, int32_t n1, const int32_t* h_idx1, const doubl
 int wf_boundary_apply_plan(const wf_boundary* bc, double s1, double s2, const double* d_v, double* d_b, void* stream)
 {
   WF_REQUIRE(bc && d_v && d_b, "wf_boundary_apply_plan: null argument");
-  return wf_boundary_apply(bc->n1, bc->d_idx1, bc->d_m1, s1, bc->n2, bc->d_idx2, bc->d_m2, s2, d_v, d_b, stream);
+  return wf_boundary_apply(bc->n1, bc->d_idx1.data(), bc->d_m1.data(), s1, bc->n2, bc->d_idx2.data(), bc->d_m2.data(), s2, d_v, d_b,
+                           stream);
 }
 
 int wf_boundary_apply(int32_t n1, const int32_t* d_idx1, const double* d_m1, double s1, int32_t n2,
