@@ -24,6 +24,12 @@
 //     and the rows k < P are broadcast reads from LDS (as the z rows of D in k_march_ks), and the kernel is built for
 //     two workgroups per CU instead of three (-DWF_OWNER_A_CONST: every such row a constant load from d_D instead).
 // The summation order of every y entry is fixed, so the apply is bitwise reproducible.
+//
+// P = 4, lane exchange ("r18"; -DWF_OWNER_LANE_EXCHANGE=0: the form above): a cell's 4 x 4 lines are one
+// 16-lane DPP row of a wave (lane = 16 c' + 4 j + i), so the in-cell operands of the +x / +y terms are the own x
+// values xz[P + k] of other lanes of the row and come by v_mov_b32_dpp (quad_perm for the x line, row_ror for the
+// y line) instead of from LDS; only the closing node of each line is read from the rectangle, and the -x / -y cell
+// lines are read by the lanes with i = 0 / j = 0 alone.
 #include <cstdlib>
 
 #include "march_column.h"
@@ -43,6 +49,54 @@ namespace wf {
 template <int P>
 constexpr int owner_waves() { return P >= 5 ? WF_OWNER_WAVES_HI : WF_OWNER_WAVES; }
 
+// P = 4: in-cell contraction operands from the registers of other lanes (1) or from LDS as at every other degree (0)
+#ifndef WF_OWNER_LANE_EXCHANGE
+#define WF_OWNER_LANE_EXCHANGE 1
+#endif
+
+template <int P>
+constexpr bool owner_lane_exchange() { return WF_OWNER_LANE_EXCHANGE != 0 && P == 4; }
+
+// Lane-exchange thread map: the BX BY = 16 cells of the column x-fastest, four per wave; lane = 16 c' + 4 j + i.
+// Returns the owned line ti + P BX tj of thread t.
+template <int P, int BX, int BY>
+constexpr int owner_lane_line(int t)
+{
+  const int c = 4 * (t / 64) + (t % 64) / 16, j = (t % 16) / 4, i = t % 4;
+  return P * (c % BX) + i + P * BX * (P * (c / BX) + j);
+}
+
+template <int P, int BX, int BY>
+constexpr bool owner_lane_map_is_bijection()
+{
+  if (P != 4 || BX * BY != 16) return false;
+  bool seen[256] = {};
+  for (int t = 0; t < 256; ++t) {
+    const int l = owner_lane_line<P, BX, BY>(t);
+    if (l < 0 || l >= P * BX * P * BY || seen[l]) return false;
+    seen[l] = true;
+  }
+  return true;
+}
+
+// v from another lane of the wave: CTRL = quad_perm (a | a << 2 | a << 4 | a << 6) or row_ror:n (0x120 + n).  Every
+// lane of the wave must be active; both controls have a source lane for every lane, so no bound or mask applies.
+template <int CTRL>
+__device__ __forceinline__ double dpp_move(double v)
+{
+  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+// a + b rounded on its own, never contracted with the product that made a or b
+__device__ __forceinline__ double add_rounded(double a, double b)
+{
+#pragma clang fp contract(off)
+  return a + b;
+}
+constexpr int dpp_quad(int a) { return a | a << 2 | a << 4 | a << 6; }
+constexpr int dpp_row_ror(int n) { return 0x120 + n; }
+
 template <int P, int BX, int BY>
 __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     int nx, int ny, int nz, int lz, int lz0, int gbx, int gby, const double* __restrict__ Gc, const double* __restrict__ dD, DMat am,
@@ -59,6 +113,8 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   constexpr int GCX = BX + 1, GC = GCX * (BY + 1), NG = 3 * GC;   // staged G00 | G11 | G22 of the cells
   constexpr int NGL = (NG + 255) / 256;
   static_assert(NL <= 256, "column does not fit a 256-thread workgroup");
+  constexpr bool lx = owner_lane_exchange<P>();
+  static_assert(!lx || owner_lane_map_is_bijection<P, BX, BY>(), "lane-exchange map is not onto the owned lines");
 
   // x planes 0..P of the layer + a dump row for positions past the rectangle (branchless rotate, see (c))
   __shared__ __attribute__((aligned(16))) double Ux[(P + 1) * RP + 256];
@@ -93,7 +149,7 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   const int I0 = LX * Bx, J0 = LY * By, cx0 = BX * Bx, cy0 = BY * By;
 
   // ---- the thread's line ---------------------------------------------------
-  const int tt = t < NL ? t : NL - 1;
+  const int tt = lx ? owner_lane_line<P, BX, BY>(t) : t < NL ? t : NL - 1;
   const int ti = tt % LX, tj = tt / LX, i = ti % P, j = tj % P;
   const int I = I0 + ti, J = J0 + tj;
   const bool own = t < NL && I < NX && J < NY;
@@ -113,6 +169,17 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   const double cwj = coeff * wk[j], cwi = coeff * wk[i], cwij = coeff * wk[i] * wk[j];
   if constexpr (a_lds)
     if (t < P * n) As[t] = dD[2 * n * n + n + t];
+  // lane exchange: row_ror:4m hands the lane the own value of another j of its i; which j is read off the rotate
+  // itself, and ajr[m] is the entry of row j of A for it (ajr[0]: the lane's own node, ajr[P]: the closing node)
+  [[maybe_unused]] double ajr[n];
+  if constexpr (lx) {
+    const int js[P] = {j, __builtin_amdgcn_mov_dpp(j, dpp_row_ror(4), 0xf, 0xf, false),
+                       __builtin_amdgcn_mov_dpp(j, dpp_row_ror(8), 0xf, 0xf, false),
+                       __builtin_amdgcn_mov_dpp(j, dpp_row_ror(12), 0xf, 0xf, false)};
+#pragma unroll
+    for (int m = 0; m < P; ++m) ajr[m] = dD[2 * n * n + n + j * n + js[m]];
+    ajr[P] = aj[P];
+  }
 
   // ---- staged positions (identical in every layer) -------------------------
   // position m: (I0 - P + c, J0 - P + r, pl); prefetch of the next layer: plane P*(kz+1) + pl + 1 -> LDS slot pl + 1
@@ -214,23 +281,73 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     store_g(gcur);
     __syncthreads();
     scales(sc);
+    // lane exchange: the shared plane's scales are the sum of two rounded products here and in the rotate, so a plane
+    // gets the same bits whether a z segment starts at it or runs through it (parts with lz0 against the whole apply)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) sf[q] = sc[q] + sp[q];
+    for (int q = 0; q < 4; ++q) sf[q] = lx ? add_rounded(sc[q], sp[q]) : sc[q] + sp[q];
     spz = sp[4];
 #pragma unroll
     for (int m = 0; m <= P; ++m) xz[P + m] = Ux[m * RP + rown + cown];
+  }
+  // lane exchange: the z term of the cell below the shared plane is formed once its P + 1 values are there (here, and
+  // at the end of every layer for the next), in the order a = 0..P of the sum in (b); the lower half of the window
+  // is then dead in the loop, which frees the registers that the lane moves need
+  [[maybe_unused]] double zpc = 0.0;
+  if constexpr (lx) {
+#pragma unroll
+    for (int a = 0; a < n; ++a) zpc += arow(P, a) * xz[a];
   }
 
   // the x / y terms of one plane (LDS slot k): sx, sy = the scales of the +x / -x / +y / -y cells
   auto xy_terms = [&](int k, double s0, double s1, double s2, double s3) {
     const double* L = Ux + k * RP;
     double xr = 0.0, xl = 0.0, ya = 0.0, yb = 0.0;
+    if constexpr (lx) {
+      const double xo = xz[P + k];
+      // -x / -y cells: only a lane on the cell's first line has them (its own node closes their line), so only
+      // those lanes read them; in the others, which had the scale 0.0, the term stays +0.0.  Only the reads are under
+      // the lane mask: the products are not, so that no wait for LDS falls inside a divergent branch.
+      const double xc = L[rown + cR + P], yc = L[(rA + P) * RX + cown];   // closing nodes of the +x / +y lines
+      double vl[P], vb[P];
 #pragma unroll
-    for (int a = 0; a < n; ++a) {
-      xr += ai[a] * L[rown + cR + a];
-      xl += arow(P, a) * L[rown + cR - P + a];
-      ya += aj[a] * L[(rA + a) * RX + cown];
-      yb += arow(P, a) * L[(rA - P + a) * RX + cown];
+      for (int a = 0; a < P; ++a) vl[a] = vb[a] = 0.0;
+      if (mi)
+#pragma unroll
+        for (int a = 0; a < P; ++a) vl[a] = L[rown + cR - P + a];
+      if (mj)
+#pragma unroll
+        for (int a = 0; a < P; ++a) vb[a] = L[(rA - P + a) * RX + cown];
+#pragma unroll
+      for (int a = 0; a < P; ++a) {
+        xl += arow(P, a) * vl[a];
+        yb += arow(P, a) * vb[a];
+      }
+      xl += arow(P, P) * (mi ? xo : 0.0);
+      yb += arow(P, P) * (mj ? xo : 0.0);
+      // the two sums are formed here, before the lane moves, and not where the compiler would sink them to (the `own`
+      // branch of the store, after the moves): the eight operands would stay live beside the moved values, which
+      // costs more than the 168 registers of three workgroups per CU
+      asm volatile("" : "+v"(xl), "+v"(yb));
+      // +x / +y cells: nodes 0..P-1 of the line from the lanes of the cell, the closing node from the rectangle.
+      // xr in the order a = 0..P as below; ya own node first, then in the order of the rotate (fixed per lane).
+      xr += ai[0] * dpp_move<dpp_quad(0)>(xo);
+      xr += ai[1] * dpp_move<dpp_quad(1)>(xo);
+      xr += ai[2] * dpp_move<dpp_quad(2)>(xo);
+      xr += ai[3] * dpp_move<dpp_quad(3)>(xo);
+      xr += ai[P] * xc;
+      ya += ajr[0] * xo;
+      ya += ajr[1] * dpp_move<dpp_row_ror(4)>(xo);
+      ya += ajr[2] * dpp_move<dpp_row_ror(8)>(xo);
+      ya += ajr[3] * dpp_move<dpp_row_ror(12)>(xo);
+      ya += ajr[P] * yc;
+    } else {
+#pragma unroll
+      for (int a = 0; a < n; ++a) {
+        xr += ai[a] * L[rown + cR + a];
+        xl += arow(P, a) * L[rown + cR - P + a];
+        ya += aj[a] * L[(rA + a) * RX + cown];
+        yb += arow(P, a) * L[(rA - P + a) * RX + cown];
+      }
     }
     return xr * s0 + xl * s1 + ya * s2 + yb * s3;
   };
@@ -267,8 +384,12 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
       double v;
       if (k == 0) {
         double zp = 0.0;
+        if constexpr (lx) {
+          zp = zpc;
+        } else {
 #pragma unroll
-        for (int a = 0; a < n; ++a) zp += arow(P, a) * xz[a];
+          for (int a = 0; a < n; ++a) zp += arow(P, a) * xz[a];
+        }
         v = wk[0] * xy_terms(0, sf[0], sf[1], sf[2], sf[3]) + zc * sc[4] + zp * spz;
       } else {
         v = wk[k] * xy_terms(k, sc[0], sc[1], sc[2], sc[3]) + zc * sc[4];
@@ -277,6 +398,11 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     }
 
     if constexpr (has_next) {
+      if constexpr (lx) {
+        zpc = 0.0;
+#pragma unroll
+        for (int a = 0; a < n; ++a) zpc += arow(P, a) * xz[P + a];
+      }
       double xcp[NCP];
 #pragma unroll
       for (int m = 0; m < NCP; ++m) {
@@ -306,7 +432,7 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
       double sn[5];
       scales(sn);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) sf[q] = sn[q] + sc[q];
+      for (int q = 0; q < 4; ++q) sf[q] = lx ? add_rounded(sn[q], sc[q]) : sn[q] + sc[q];
       spz = sc[4];
 #pragma unroll
       for (int q = 0; q < 5; ++q) sc[q] = sn[q];
