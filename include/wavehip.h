@@ -416,7 +416,9 @@ typedef struct {
   int items_interior, items_interface; /* work items per part (wf_op_set_ghost_*)     */
   int kernel;            /* wf_kernel_id: the kernel wf_op_apply launches               */
   int plan_items, plan_patterns, plan_lz; /* lattice-column plan (WF_KERNEL_MARCH_IDX): work items,
-                            distinct index tables, layers per item; 0 otherwise          */
+                            distinct index tables, layers per item; 0 otherwise.  plan_lz of a box marching
+                            operator: layers per z segment, or, when the whole apply runs by a run table
+                            (wf_op_get_runs), the layers of its longest run */
   int plan_reoriented;   /* cells whose local axes the plan rotated / reflected to make them agree */
   double plan_fill;      /* cells / cell slots of the plan's columns                     */
   int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
@@ -424,6 +426,28 @@ typedef struct {
   int update;            /* wf_update_mode of the separable kernel, box or dofmap (0: none); WF_UPDATE_ORDERED */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
+
+/* z segmentation of the box marching kernels (host only).  Work items run on `resident` workgroup slots, slot b mod nxcd
+ * of XCD b mod nxcd, in launch order as slots free up; an item of L layers costs L + prologue.  The uniform plan cuts
+ * every column into segments of *uniform_lz layers (the length that minimises rounds * (lz + 1.5) over equal cuts of at
+ * least 3 layers; lz > 0: lz layers) and costs rounds * (*uniform_lz + prologue).  When a
+ * plan of one run (column, z0, z1) per workgroup is strictly cheaper in this model, h_runs[3 r ..] receives run r in
+ * launch order (runs r = k mod nxcd are XCD k's, every XCD a contiguous range of columns, longest run first) and *nruns
+ * their number; otherwise *nruns = 0: the uniform plan stays.  It always stays for lz > 0 and when it needs one round
+ * with its columns cut (or too short to cut: nz < 6).  capacity: runs h_runs can hold (ncols * nz always suffices). */
+int wf_box_run_plan(int ncols, int nz, int resident, int nxcd, double prologue, int lz, int32_t* h_runs, int32_t capacity,
+                    int32_t* nruns, double* cost, double* uniform_cost, int32_t* uniform_lz);
+/* Box stiffness operator in the owner form (wf_op_info_t.update == WF_UPDATE_OWNER): plan wf_op_apply again.
+ * resident > 0: by wf_box_run_plan for that many workgroups (a small mesh then takes a plan of many rounds).
+ * resident = 0: as at creation, where a P4 operator without wf_tuning.lz whose uniform plan needs more than one round of
+ * the resident workgroups times the uniform plan and cuts of every column at the same layers (4 to 12 layers per run)
+ * on the device and keeps the fastest, and every other operator has no table.  Builds, replaces or drops the operator's
+ * run table (counted in device_bytes); the interior / interface parts keep their z segments.  Synchronises the device.  wf_op_get_runs: the table, h_runs[3 r ..] = (column, z0, z1) of workgroup r, column = x piece +
+ * pieces in x * y piece; *nruns = 0 without one (h_runs may be NULL to ask for the count). */
+int wf_op_replan_runs(wf_op* op, int resident);
+/* a caller's own table, checked to cover every layer of every column exactly once (nruns = 0: drop the table) */
+int wf_op_set_runs(wf_op* op, const int32_t* h_runs, int32_t nruns);
+int wf_op_get_runs(const wf_op* op, int32_t* h_runs, int32_t capacity, int32_t* nruns);
 int wf_op_destroy(wf_op* op);
 
 /* ---- a8/a9: free kernels --------------------------------------------------

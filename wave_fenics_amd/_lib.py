@@ -138,6 +138,11 @@ SIGNATURES = {
     "wf_op_set_ghost_faces": (c_int, [c_void_p, c_int, c_int, c_int]),
     "wf_op_apply_part": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "wf_op_info": (c_int, [c_void_p, POINTER(OpInfo)]),
+    "wf_box_run_plan": (c_int, [c_int, c_int, c_int, c_int, c_double, c_int, POINTER(c_int32), c_int32, POINTER(c_int32),
+                                POINTER(c_double), POINTER(c_double), POINTER(c_int32)]),
+    "wf_op_replan_runs": (c_int, [c_void_p, c_int]),
+    "wf_op_set_runs": (c_int, [c_void_p, POINTER(c_int32), c_int32]),
+    "wf_op_get_runs": (c_int, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
     "wf_op_destroy": (c_int, [c_void_p]),
     "wf_gather": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_scatter_add": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

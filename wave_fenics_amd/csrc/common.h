@@ -142,6 +142,7 @@ int march_resident(int P, int variant, MarchGeom geom);   // workgroups resident
 // no atomics.  Its own cross-section table (march_owner_variant); columns = lattice lines in pieces of P*BX x P*BY.
 bool march_owner_variant(int P, int variant, int* bx, int* by);
 // d_Gcell blocked by gbx x gby: the atomic form's cross-section at P <= 4, the owner cross-section itself at P >= 5
+// lz < 0: d_items is a run table of nitems entries (column, z0, z1), one per workgroup (box_run_plan.h)
 int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int lz, int lz0, int gbx, int gby,
                                  const double* d_Gcell,
                                  const double* d_D, const DMat& am, double coeff, const double* d_x, double* d_y,

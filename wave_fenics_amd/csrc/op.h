@@ -5,6 +5,7 @@
 #include <functional>
 #include <memory>
 
+#include "box_run_plan.h"
 #include "device_array.h"
 
 // What wf_op_apply launches.  Creation sets it once; apply, the interior / interface splits and wf_op_info switch on it.
@@ -73,6 +74,11 @@ struct wf_op {
   wf::DevArray<int32_t> d_items[4];
   int nitems[4] = {0, 0, 0, 0};
   int have_parts = 0;
+  // run table of the owner form's whole apply (box_run_plan.h): [runs][3] = (column, z0, z1) in launch order, on the
+  // device and as planned on the host; empty when the uniform z segments of box.lz run
+  wf::DevArray<int32_t> d_runs;
+  std::vector<int32_t> h_runs;
+  int runs_longest = 0;   // layers of the longest run
   // lattice columns of idx_march and mass_march: the arrays, and the view of them the launchers take
   wf::DevArray<int32_t> d_item_base, d_item_pattern, d_item_layers, d_pat_off;
   wf::MarchPlanDev plan{};
@@ -159,6 +165,14 @@ struct PointMaps {
   std::vector<std::vector<int32_t>> maps = std::vector<std::vector<int32_t>>(48);
   const std::vector<int32_t>& operator()(int code);
 };
+
+// ---- op_create_box.hip ----
+// Plans the whole apply of a box owner operator for `resident` workgroups by the model of box_run_plan.h: builds or drops
+// the run table.  box.lz, and with it the interior / interface parts, stay as they are.
+int plan_owner_runs(wf_op* op, int resident);
+// what creation does: the cut of the whole apply chosen by timing the uniform plan and aligned cuts on the device (P4,
+// more than one round, no wf_tuning.lz; every other operator: no table)
+int tune_owner_runs(wf_op* op);
 
 // ---- op_apply.hip ----
 size_t op_device_bytes(const wf_op* op);   // wf_op_info_t.device_bytes: what the handle holds now

@@ -16,7 +16,7 @@ size_t wf::op_device_bytes(const wf_op* op)
 {
   size_t total = dense_bytes(op->dense) + dense_mass_bytes(op->dense_mass);
   for (const DevArray<int32_t>* a : {&op->d_dofmap, &op->d_uoff, &op->d_uniq, &op->d_slot, &op->d_row_off, &op->d_items[0],
-                                     &op->d_items[1], &op->d_items[2], &op->d_items[3], &op->d_item_base, &op->d_item_pattern,
+                                     &op->d_items[1], &op->d_items[2], &op->d_items[3], &op->d_runs, &op->d_item_base, &op->d_item_pattern,
                                      &op->d_item_layers, &op->d_pat_off})
     total += a->bytes();
   for (const DevArray<double>* a : {&op->d_G6blk, &op->d_Gcell, &op->d_detJ, &op->d_D, &op->d_phi1, &op->d_mdiag, &op->d_v})
@@ -171,6 +171,10 @@ static int launch_op(const wf_op* op, int lz0, const int32_t* d_items, int nitem
       return launch_stiffness_march_ks_box(op->P, op->box.bx, op->box.by, op->nx, op->ny, op->nz, op->box.lz, lz0, G6blk, D,
                                            op->dm, op->coeff, d_x, d_y, d_items, nitems, s);
     case OpKernel::box_owner:
+      // the whole apply by the run table when the operator has one (lz < 0 says so to the launcher)
+      if (!d_items && op->d_runs.size())
+        return launch_stiffness_march_owner(op->P, op->box.variant, op->nx, op->ny, op->nz, -1, -1, op->box.bx, op->box.by, Gcell,
+                                            D, op->am, op->coeff, d_x, d_y, op->d_runs.data(), (int)(op->d_runs.size() / 3), s);
       return launch_stiffness_march_owner(op->P, op->box.variant, op->nx, op->ny, op->nz, op->box.lz, lz0, op->box.bx, op->box.by,
                                           Gcell, D, op->am, op->coeff, d_x, d_y, d_items, nitems, s);
     case OpKernel::box_block:
@@ -376,7 +380,7 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   info->kernel = kernel;
   info->plan_items = plan ? op->plan.nitems : 0;
   info->plan_patterns = plan ? op->plan_patterns : 0;
-  info->plan_lz = plan ? op->plan.lz : is_box_march(op->kernel) ? op->box.lz : 0;
+  info->plan_lz = plan ? op->plan.lz : op->d_runs.size() ? op->runs_longest : is_box_march(op->kernel) ? op->box.lz : 0;
   info->plan_reoriented = op->plan_reoriented;
   info->plan_fill = op->plan_fill;
   info->geometry = geometry;

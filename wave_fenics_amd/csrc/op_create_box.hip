@@ -120,26 +120,15 @@ int choose_box_stiffness(int P, int nx, int ny, int nz, const double* h_xverts, 
   if (!march) return WF_OK;
   // z segmentation: work items = columns x segments run in rounds of the resident workgroups (occupancy
   // query of the kernel that launches: 2 per CU for the per-point P4 kernel, 3 for the full per-cell one and 3 for
-  // the axes one); each item pays ~1.5 layers of
-  // pipeline fill.  Pick the segment length that minimises rounds * (lz + 1.5).
+  // the axes one); each item pays a prologue of pipeline fill, counted in layers (box_run_plan.h).  Pick the segment
+  // length that minimises rounds * (lz + prologue).
   const bool owner = *kernel == OpKernel::box_owner;
   const int ncols = owner ? box_owner_columns(P, nx, ny, ch->obx, ch->oby).count() : box_columns(nx, ny, ch->bx, ch->by).count();
   long resident = owner                                 ? march_owner_resident(P, ch->variant)
                   : *kernel == OpKernel::box_march ? march_resident(P, ch->variant, *geom)
                                                         : march_ks_resident(P, ch->bx, ch->by);
   if (resident <= 0) resident = 512;
-  double best = 1e300;
-  ch->lz = nz;
-  for (int nseg = 1; nseg <= nz; ++nseg) {
-    const int lz = (nz + nseg - 1) / nseg;
-    if (lz < 3 && nseg > 1) break;
-    const long items = (long)ncols * box_segments(nz, lz, lz);
-    const double cost = (double)((items + resident - 1) / resident) * (lz + 1.5);
-    if (cost < best - 1e-9) {
-      best = cost;
-      ch->lz = lz;
-    }
-  }
+  ch->lz = box_uniform_lz(ncols, nz, resident, kMarchPrologue, nullptr, nullptr);
   if (tun.lz > 0) ch->lz = tun.lz;
   return WF_OK;
 }
@@ -203,7 +192,174 @@ int create_box_ordered(int kind, int P, int nx, int ny, int nz, const double* h_
 
 }  // namespace
 
+int wf::plan_owner_runs(wf_op* op, int resident)
+{
+  // the plan's column sequence is the kernel's column index: x fastest, as the uniform order (y fastest measured slower)
+  const BoxColumns cols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby);
+  const BoxRunPlan plan = box_run_plan(cols.count(), op->nz, resident, kXcds, kOwnerPrologue, op->tun.lz);
+  op->h_runs.clear();
+  op->runs_longest = plan.longest;
+  for (const BoxRun& r : plan.runs) op->h_runs.insert(op->h_runs.end(), {r.col, r.z0, r.z1});
+  return op->d_runs.upload(op->h_runs);   // no runs: no array
+}
+
+namespace {
+
+// Aligned cut: every column cut at the same nseg places (lengths differ by at most one layer), the runs in segment-major
+// order and dealt to the XCDs in contiguous chunks, as the uniform order deals its items: neighbouring columns march
+// through the same layers at the same time, and what one reads as halo the other has just brought into the XCD's L2.
+std::vector<int32_t> aligned_runs(int ncols, int nz, int nseg)
+{
+  const size_t n = (size_t)ncols * nseg, q = n / kXcds, r = n % kXcds;
+  std::vector<int32_t> table(3 * n);
+  size_t xcd = 0, i = 0;   // run i of XCD xcd is entry kXcds * i + xcd
+  for (int s = 0; s < nseg; ++s)
+    for (int col = 0; col < ncols; ++col) {
+      int32_t* e = &table[3 * (kXcds * i + xcd)];
+      e[0] = col, e[1] = (int32_t)((long)nz * s / nseg), e[2] = (int32_t)((long)nz * (s + 1) / nseg);
+      if (++i == q + (xcd < r ? 1 : 0)) i = 0, ++xcd;
+    }
+  return table;
+}
+
+int install_runs(wf_op* op, std::vector<int32_t> table)
+{
+  op->h_runs = std::move(table);
+  int longest = 0;
+  for (size_t r = 0; r < op->h_runs.size(); r += 3) longest = std::max(longest, op->h_runs[r + 2] - op->h_runs[r + 1]);
+  op->runs_longest = op->h_runs.empty() ? op->box.lz : longest;
+  return op->d_runs.upload(op->h_runs);   // no runs: no array
+}
+
+// shortest of `reps` applies in microseconds
+int time_apply(wf_op* op, const double* d_x, double* d_y, hipEvent_t e0, hipEvent_t e1, int reps, float* us)
+{
+  for (int r = 0; r < reps + 2; ++r) {   // two untimed
+    WF_HIP_CHECK(hipEventRecord(e0, nullptr));
+    int rc = wf_op_apply(op, d_x, d_y, nullptr);
+    if (rc != WF_OK) return rc;
+    WF_HIP_CHECK(hipEventRecord(e1, nullptr));
+    WF_HIP_CHECK(hipEventSynchronize(e1));
+    float ms = 0.0f;
+    WF_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+    if (r >= 2) *us = std::min(*us, ms * 1e3f);
+  }
+  return WF_OK;
+}
+
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~EventPair()
+  {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+};
+
+}  // namespace
+
+// The cut of the whole apply, chosen by timing it ("r19"): the uniform plan against aligned cuts of 4 to 12
+// layers per run.  Only at P4, where the bits of y do not depend on the cut, without wf_tuning.lz, and where the uniform
+// plan needs more than one round of the resident workgroups: every other operator stays what it was.
+int wf::tune_owner_runs(wf_op* op)
+{
+  op->h_runs.clear();
+  op->runs_longest = op->box.lz;
+  int rc = op->d_runs.upload(op->h_runs);
+  const int ncols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby).count(), nz = op->nz;
+  long resident = march_owner_resident(op->P, op->box.variant);
+  if (resident <= 0) resident = 512;
+  if (rc != WF_OK || op->P != 4 || op->tun.lz > 0 || (long)ncols * box_segments(nz, op->box.lz, op->box.lz) <= resident) return rc;
+  const int lo = std::max(2, (nz + 11) / 12), hi = nz / 4, step = std::max(1, (hi - lo + 16) / 16);
+  DevArray<double> vectors;   // x | y of the timing; no room for them: the uniform plan stays
+  if (vectors.alloc(2 * (size_t)op->ndofs) != WF_OK) return (void)hipGetLastError(), WF_OK;
+  const double* d_x = vectors.data();
+  double* d_y = vectors.data() + op->ndofs;
+  WF_HIP_CHECK(hipMemset(vectors.data(), 0, vectors.bytes()));
+  EventPair ev;
+  WF_HIP_CHECK(hipEventCreate(&ev.e0));
+  WF_HIP_CHECK(hipEventCreate(&ev.e1));
+  std::vector<int> nsegs = {0};   // 0: the uniform plan
+  for (int nseg = lo; nseg <= hi; nseg += step) nsegs.push_back(nseg);
+  std::vector<float> us(nsegs.size(), 1e30f);
+  for (int pass = 0; pass < 3; ++pass)   // interleaved, so that a clock ramp after idle does not favour a candidate
+    for (size_t c = 0; c < nsegs.size(); ++c) {
+      if ((rc = install_runs(op, nsegs[c] ? aligned_runs(ncols, nz, nsegs[c]) : std::vector<int32_t>())) != WF_OK) return rc;
+      if ((rc = time_apply(op, d_x, d_y, ev.e0, ev.e1, 6, &us[c])) != WF_OK) return rc;
+    }
+  size_t best = 0;
+  for (size_t c = 1; c < nsegs.size(); ++c)
+    if (us[c] < us[best] && us[c] < 0.99f * us[0]) best = c;   // a table has to win by more than the timing's noise
+  return install_runs(op, nsegs[best] ? aligned_runs(ncols, nz, nsegs[best]) : std::vector<int32_t>());
+}
+
 extern "C" {
+
+int wf_box_run_plan(int ncols, int nz, int resident, int nxcd, double prologue, int lz, int32_t* h_runs, int32_t capacity,
+                    int32_t* nruns, double* cost, double* uniform_cost, int32_t* uniform_lz)
+{
+  WF_REQUIRE(ncols > 0 && nz > 0 && resident > 0 && nxcd > 0 && prologue >= 0.0 && nruns, "wf_box_run_plan: bad argument");
+  const BoxRunPlan plan = box_run_plan(ncols, nz, resident, nxcd, prologue, lz);
+  *nruns = (int32_t)plan.runs.size();
+  if (cost) *cost = plan.cost;
+  if (uniform_cost) *uniform_cost = plan.uniform_cost;
+  if (uniform_lz) *uniform_lz = plan.uniform_lz;
+  if (plan.runs.empty()) return WF_OK;
+  WF_REQUIRE(h_runs && (size_t)capacity >= plan.runs.size(), "wf_box_run_plan: h_runs holds fewer than *nruns runs");
+  static_assert(sizeof(BoxRun) == 3 * sizeof(int32_t), "BoxRun is the table's entry");
+  std::memcpy(h_runs, plan.runs.data(), plan.runs.size() * sizeof(BoxRun));
+  return WF_OK;
+}
+
+int wf_op_replan_runs(wf_op* op, int resident)
+{
+  WF_REQUIRE(op != nullptr && resident >= 0, "wf_op_replan_runs: bad argument");
+  if (op->kernel != OpKernel::box_owner) {
+    set_error("wf_op_replan_runs: only the owner form of the box stiffness operator runs by a run table");
+    return WF_ERR_UNSUPPORTED;
+  }
+  WF_HIP_CHECK(hipDeviceSynchronize());   // an apply in flight may still read the table this replaces
+  return resident > 0 ? plan_owner_runs(op, resident) : tune_owner_runs(op);
+}
+
+int wf_op_set_runs(wf_op* op, const int32_t* h_runs, int32_t nruns)
+{
+  WF_REQUIRE(op != nullptr && nruns >= 0 && (nruns == 0 || h_runs), "wf_op_set_runs: bad argument");
+  if (op->kernel != OpKernel::box_owner) {
+    set_error("wf_op_set_runs: only the owner form of the box stiffness operator runs by a run table");
+    return WF_ERR_UNSUPPORTED;
+  }
+  // the kernel trusts the table: every (column, layer) exactly once, every run inside its column
+  const int ncols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby).count(), nz = op->nz;
+  std::vector<char> seen((size_t)ncols * nz, 0);
+  size_t covered = 0;
+  int longest = 0;
+  for (int32_t r = 0; r < nruns; ++r) {
+    const int32_t col = h_runs[3 * r], z0 = h_runs[3 * r + 1], z1 = h_runs[3 * r + 2];
+    WF_REQUIRE(col >= 0 && col < ncols && z0 >= 0 && z0 < z1 && z1 <= nz, "wf_op_set_runs: run outside the mesh or empty");
+    for (int z = z0; z < z1; ++z) {
+      WF_REQUIRE(!seen[(size_t)col * nz + z], "wf_op_set_runs: a layer of a column is covered twice");
+      seen[(size_t)col * nz + z] = 1;
+    }
+    covered += (size_t)(z1 - z0);
+    longest = std::max(longest, z1 - z0);
+  }
+  WF_REQUIRE(nruns == 0 || covered == seen.size(), "wf_op_set_runs: the runs do not cover every layer of every column");
+  WF_HIP_CHECK(hipDeviceSynchronize());   // an apply in flight may still read the table this replaces
+  op->h_runs.assign(h_runs, h_runs + 3 * (size_t)nruns);
+  op->runs_longest = nruns ? longest : op->box.lz;
+  return op->d_runs.upload(op->h_runs);
+}
+
+int wf_op_get_runs(const wf_op* op, int32_t* h_runs, int32_t capacity, int32_t* nruns)
+{
+  WF_REQUIRE(op && nruns, "wf_op_get_runs: null argument");
+  *nruns = (int32_t)(op->h_runs.size() / 3);
+  if (op->h_runs.empty() || !h_runs) return WF_OK;
+  WF_REQUIRE((size_t)capacity >= op->h_runs.size() / 3, "wf_op_get_runs: h_runs holds fewer than *nruns runs");
+  std::memcpy(h_runs, op->h_runs.data(), op->h_runs.size() * sizeof(int32_t));
+  return WF_OK;
+}
 
 int wf_op_create_box(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0, int flags,
                      wf_op** out)
@@ -271,6 +427,7 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
       return rc;
   }
   WF_HIP_CHECK(hipDeviceSynchronize());
+  if (op->kernel == OpKernel::box_owner && (rc = tune_owner_runs(op.get())) != WF_OK) return rc;
   *out = op.release();
   return WF_OK;
 }

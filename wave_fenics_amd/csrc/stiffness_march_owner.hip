@@ -25,6 +25,9 @@
 //     two workgroups per CU instead of three (-DWF_OWNER_A_CONST: every such row a constant load from d_D instead).
 // The summation order of every y entry is fixed, so the apply is bitwise reproducible.
 //
+// Work of a workgroup: a z segment of the uniform cut (item = column + columns * segment, lz layers each), or, with
+// lz < 0, one run (column, z0, z1) of the operator's run table, which the host planned for this launch order.
+//
 // P = 4, lane exchange ("r18"; -DWF_OWNER_LANE_EXCHANGE=0: the form above): a cell's 4 x 4 lines are one
 // 16-lane DPP row of a wave (lane = 16 c' + 4 j + i), so the in-cell operands of the +x / +y terms are the own x
 // values xz[P + k] of other lanes of the row and come by v_mov_b32_dpp (quad_perm for the x line, row_ror for the
@@ -139,13 +142,18 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   const int nbxo = (NX + LX - 1) / LX, nbyo = (NY + LY - 1) / LY, ncols = nbxo * nbyo;
   // XCD-aware order: consecutive workgroups go round-robin to the 8 XCDs, so each XCD is given a contiguous run of
   // items instead; the halo lines a column reads then mostly belong to columns on the same XCD, and its L2 serves them
+  // lz < 0: `items` is the operator's run table instead ("r19"; box_run_plan.h), entry blockIdx.x =
+  // (column, z0, z1) of this workgroup, already in the order of its XCD.  Selects, not two branches that meet: the
+  // uniform cut is turned into the same three values, and the kernels at the register limit keep their allocation.
+  const bool table = lz < 0;
   const int nwg = (int)gridDim.x, xq = nwg / 8, xr = nwg % 8, xcd = (int)blockIdx.x % 8;
   const int b = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (int)blockIdx.x / 8;
-  const int item = items ? items[b] : b;
-  const int col = item % ncols, seg = item / ncols;
+  const int e = table ? 3 * (int)blockIdx.x : b;
+  const int w0 = items ? items[e] : b;   // the item, or the run's column
+  const int w1 = table ? items[e + 1] : 0, w2 = table ? items[e + 2] : 0;
+  const BoxSegment zs = box_segment(w0 / ncols, nz, lz, lz0);
+  const int col = table ? w0 : w0 % ncols, z0 = table ? w1 : zs.z0, z1 = table ? w2 : zs.z1;
   const int Bx = col % nbxo, By = col / nbxo;
-  const BoxSegment zs = box_segment(seg, nz, lz, lz0);
-  const int z0 = zs.z0, z1 = zs.z1;
   const int I0 = LX * Bx, J0 = LY * By, cx0 = BX * Bx, cy0 = BY * By;
 
   // ---- the thread's line ---------------------------------------------------

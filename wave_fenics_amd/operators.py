@@ -282,6 +282,28 @@ class _Operator:
         self._info()
         return True
 
+    def replan_runs(self, resident: int = 0):
+        """Plan the whole apply of a box owner operator again, for `resident` workgroups (0: the occupancy query, as at
+        creation).  The interior / interface parts keep their z segments."""
+        check(lib().wf_op_replan_runs(self._h, int(resident)))
+        self._info()
+
+    def set_runs(self, runs):
+        """Install a run table of the caller's, [runs][3] = (column, z0, z1) per workgroup in launch order; it must
+        cover every layer of every column exactly once.  An empty table drops the operator's."""
+        r = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1, 3)
+        check(lib().wf_op_set_runs(self._h, _ip(r) if r.size else None, r.shape[0]))
+        self._info()
+
+    def runs(self):
+        """The run table of the whole apply, [runs][3] = (column, z0, z1) per workgroup; empty without one."""
+        n = c_int32(0)
+        check(lib().wf_op_get_runs(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            check(lib().wf_op_get_runs(self._h, _ip(out), n.value, ctypes.byref(n)))
+        return out
+
     def part_fraction(self, part: int) -> float:
         """Share of the operator's work items in `part` (after set_ghost_faces)."""
         tot = self.info.items_interior + self.info.items_interface
@@ -486,6 +508,18 @@ def ordered_slots(dofmap, ndofs: int):
     slot = np.zeros(dm.shape, dtype=np.int32)
     check(lib().wf_ordered_slots(dm.shape[0], dm.shape[1], int(ndofs), _ip(dm), _ip(row_off), _ip(slot)))
     return row_off, slot
+
+
+def box_run_plan(ncols: int, nz: int, resident: int, nxcd: int = 8, prologue: float = 1.5, lz: int = 0):
+    """The z segmentation of a box marching operator of ncols columns and nz layers on `resident` workgroups
+    (wf_box_run_plan, host only).  Returns (runs, cost, uniform_cost, uniform_lz): runs[r] = (column, z0, z1) of workgroup
+    r, an empty [0][3] array when the uniform plan of uniform_lz layers per segment stays; costs in layers."""
+    runs = np.zeros((int(ncols) * int(nz), 3), dtype=np.int32)
+    n, ulz = c_int32(0), c_int32(0)
+    cost, ucost = c_double(0.0), c_double(0.0)
+    check(lib().wf_box_run_plan(int(ncols), int(nz), int(resident), int(nxcd), float(prologue), int(lz), _ip(runs),
+                                runs.shape[0], ctypes.byref(n), ctypes.byref(cost), ctypes.byref(ucost), ctypes.byref(ulz)))
+    return runs[:n.value].copy(), cost.value, ucost.value, ulz.value
 
 
 def segment_sum_add(n: int, row_off, vals, y, stream: int | None = None):
