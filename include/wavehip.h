@@ -394,6 +394,9 @@ int wf_op_apply(wf_op* op, const double* d_x, double* d_y, void* stream);
  *   wf_op_set_ghost_dofs : any marching operator (box or arbitrary dofmap), ghosts given as
  *                          positions in the local array -- the same list the updater gets
  *                          (wf_updater_desc.ghost_positions, any order, duplicates allowed);
+ *                          on a box operator the first z segment is short (wf_tuning.lz0) when every
+ *                          position of the lattice plane K = 0 is a ghost, as with ghost_z0 below, so
+ *                          that the same planes give the same work items through either call;
  *   wf_op_set_ghost_faces: box operators, ghosts = the lower lattice plane of the marked axes
  *                          (the Cartesian partition of SURVEY 8e).
  * WF_ERR_UNSUPPORTED for operators that run a batch kernel (no work items to sort). */

@@ -261,8 +261,11 @@ int wf_op_set_ghost_dofs(wf_op* op, const int32_t* h_ghost_positions, int32_t ng
   if (box) {
     const int NX = P * op->nx + 1, NY = P * op->ny + 1;
     const size_t plane = (size_t)NX * NY;
-    bool gz = false;   // a z ghost plane below
-    for (size_t g = 0; g < plane && !gz; ++g) gz = ghost[g] != 0;
+    // a z ghost plane below: every position of plane K = 0 is a ghost, which is what ghost_z0 of wf_op_set_ghost_faces
+    // says.  (A ghost anywhere in the plane is not enough: an x or y ghost plane alone holds the plane's edge, and the
+    // same planes then gave another segmentation through this call than through wf_op_set_ghost_faces.)
+    bool gz = true;
+    for (size_t g = 0; g < plane && gz; ++g) gz = ghost[g] != 0;
     // the owner form's columns are pieces of P*obx x P*oby lattice lines; its footprint reaches P lines / planes below
     // what it owns: [I0 - P, I0 + P obx] x [J0 - P, J0 + P oby] x [P z0 - P, P z1]
     const bool owner = op->kernel == OpKernel::box_owner;
