@@ -1,5 +1,9 @@
 """Diagnostic: time the cfg2 stiffness apply under the WF_ABLATE masks and box
-block shapes (interleaved rounds in one process).  Not part of the product."""
+block shapes (interleaved rounds in one process).  Not part of the product.
+
+MASKS=0,16 with an owner operator (e.g. "march:1" at P4) gives the prologue's share of the owner apply: under bit 16
+every run of k_stiffness_owner returns after its prologue, before its first layer.  SETTLE=1000 REPS=200 is the method
+of tools/owner_lz_sweep.py (past the power ramp, median of 200 HIP-event timings) that profiles/r20_summary.md uses."""
 import os
 import sys
 
@@ -13,8 +17,8 @@ os.environ.setdefault("WAVEHIP_LIB", os.path.join(ROOT, "examples", "bin", "libw
 import wave_fenics_amd as w  # noqa: E402
 
 
-def time_op(op, x, y, reps=20):
-    for _ in range(3):
+def time_op(op, x, y, reps=int(os.environ.get("REPS", "20")), settle=int(os.environ.get("SETTLE", "3"))):
+    for _ in range(settle):
         op(x, y)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
     for a, b in ev:

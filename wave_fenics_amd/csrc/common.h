@@ -71,6 +71,7 @@ inline int launch_status(const char* what)
 
 // Diagnostic ablation mask (profiling only; WF_ABLATE unset or 0 in production):
 // 1 = no scatter, 2 = geometry served from L2, 4 = no x gather, 8 = no contractions.
+// 16 = owner stiffness kernel: every run ends after its prologue (what a run costs before its first layer).
 inline int ablate_flags()
 {
 #ifdef WF_DIAG

@@ -111,7 +111,6 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   constexpr int LX = P * BX, LY = P * BY, NL = LX * LY;   // owned lines
   constexpr int RX = LX + P + 1, RY = LY + P + 1, RP = RX * RY;   // staged rectangle of one plane
   constexpr int NPF = (P * RP + 255) / 256;          // x prefetch positions per thread (planes 1..P)
-  constexpr int NPF0 = ((P + 1) * RP + 255) / 256;   // prologue positions (planes 0..P)
   constexpr int NCP = (RP + 255) / 256;              // positions of one plane
   constexpr int GCX = BX + 1, GC = GCX * (BY + 1), NG = 3 * GC;   // staged G00 | G11 | G22 of the cells
   constexpr int NGL = (NG + 255) / 256;
@@ -262,21 +261,25 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
 #pragma unroll
     for (int k = 0; k < P; ++k) yA[k] = (ablate & 1) ? 0.0 : y[plane * (size_t)(P * z0 + k) + yoff];
     // every plane load is in flight before the first is consumed: unconditional loads on clamped addresses, then
-    // the LDS stores (positions past the rectangle go to the dump row), as in the rotate (c)
-    const size_t base = plane * (size_t)(P * z0);
-    double xp[NPF0];
-    bool xin[NPF0];
+    // the LDS stores (positions past the rectangle go to the dump row), as in the rotate (c).  One decomposition of
+    // the staged positions serves both ("r20"): planes 1..P through poff, exactly as the rotate loads
+    // them, and plane 0 through the first NCP entries of poff from its own base (a position t + 256 m < RP of the
+    // P RP staged ones lies in the first plane of its block, so its offset is the one within any plane).
+    const double* xb = x + plane * (size_t)(P * z0) + plane;
+    double xp0[NCP], xp[NPF];
 #pragma unroll
-    for (int m = 0; m < NPF0; ++m) {
+    for (int m = 0; m < NCP; ++m) xp0[m] = (xb - plane)[t + 256 * m < RP && poff[m] >= 0 ? poff[m] : pclamp];
+#pragma unroll
+    for (int m = 0; m < NPF; ++m) xp[m] = xb[poff[m] >= 0 ? poff[m] : pclamp];
+#pragma unroll
+    for (int m = 0; m < NCP; ++m) {
       const int pos = t + 256 * m;
-      const int pl = pos / RP, r = pos % RP, II = I0 - P + r % RX, JJ = J0 - P + r / RX;
-      xin[m] = pos < (P + 1) * RP && II >= 0 && II < NX && JJ >= 0 && JJ < NY;
-      xp[m] = x[base + (xin[m] ? (size_t)II + (size_t)NX * JJ + plane * pl : (size_t)pclamp)];
+      Ux[tile_or_dump<RP>(m, pos, 0, (P + 1) * RP, t)] = (pos < RP && poff[m] >= 0) ? xp0[m] : 0.0;
     }
 #pragma unroll
-    for (int m = 0; m < NPF0; ++m) {
+    for (int m = 0; m < NPF; ++m) {
       const int pos = t + 256 * m;
-      Ux[tile_or_dump<(P + 1) * RP>(m, pos, 0, (P + 1) * RP, t)] = xin[m] ? xp[m] : 0.0;
+      Ux[tile_or_dump<P * RP>(m, pos, RP, (P + 1) * RP, t)] = poff[m] >= 0 ? xp[m] : 0.0;
     }
     store_g(gp);
     __syncthreads();
@@ -304,6 +307,22 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   if constexpr (lx) {
 #pragma unroll
     for (int a = 0; a < n; ++a) zpc += arow(P, a) * xz[a];
+  }
+
+  // diagnostic (WF_ABLATE bit 16, tools/ablate.py): the run ends after its prologue.  Everything the prologue forms
+  // goes into a store that never happens, so that none of it is removed.
+  if (ablate & 16) {
+    double u = zpc + spz;
+#pragma unroll
+    for (int m = 0; m <= 2 * P; ++m) u += xz[m];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) u += sc[q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) u += sf[q];
+#pragma unroll
+    for (int k = 0; k < P; ++k) u += yA[k];
+    if (u == 1.2345e300) y[yoff] = u;
+    return;
   }
 
   // the x / y terms of one plane (LDS slot k): sx, sy = the scales of the +x / -x / +y / -y cells
