@@ -312,6 +312,8 @@ typedef struct {
   const double* h_qpts1;
   const double* h_qwts1;
   const wf_tuning* tuning;     /* NULL = defaults                                */
+  const double* h_cell_coeff;  /* [ncells] cell coefficient a_c, rows of h_dofmap; NULL = none
+                                  (see "Cell coefficients" below)                 */
 } wf_op_desc;
 
 /* Op(V, degree[, params]) constructors: operators.hpp:53,149; mass.hpp:20;
@@ -327,6 +329,31 @@ int wf_op_create_box(int kind, int degree, int nx, int ny, int nz,
                      const double* h_xverts, double c0, int flags, wf_op** out);
 int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0, int flags,
                            const wf_tuning* tuning, wf_op** out);
+/* The box operator with a cell coefficient h_cell_coeff[nx ny nz], cell (cx, cy, cz) -> cx + nx (cy + ny cz); NULL gives
+ * the operator of the two entry points above, which are calls of this one. */
+int wf_op_create_box_coeff(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0,
+                           const double* h_cell_coeff, int flags, const wf_tuning* tuning, wf_op** out);
+
+/* Cell coefficients (heterogeneous media).  An operator created with h_cell_coeff applies
+ *   y += sum_c a_c P_c^T A_c P_c x,
+ * A_c the cell matrix of the operator without a coefficient -- for the stiffness operator with its -c0^2 factor and the
+ * reference's -1/0/1 clamp, both applied before a_c.  a_c is one double per cell in the caller's cell order: the rows of
+ * h_dofmap / h_geom_dofmap, on a box cx + nx (cy + ny cz).  The array is copied at creation; a medium cannot be changed
+ * afterwards, and a coefficient that varies inside a cell is out of scope.
+ *   - Every a_c must be finite; zero and negative values are allowed.  A NaN or infinite entry is WF_ERR_INVALID and
+ *     wf_last_error names the first such cell.  The check precedes the first device call.
+ *   - Hexahedral operators and the tetrahedral mass FOLD the coefficient into the geometry they store: every stored entry
+ *     (G per point, G_c per cell, det J w, s_c, the lumped diagonal's det J w before it is accumulated, the caller's h_G /
+ *     h_detJ) is the entry of the operator without a coefficient multiplied once by a_c and rounded once.  The apply reads
+ *     the same arrays with the same kernels: a heterogeneous medium costs what a homogeneous one costs.
+ *   - The tetrahedral stiffness forms clamp(w_q C_c) on the fly, so a coefficient folded into C_c would move the clamp
+ *     windows: its kernel has a variant that loads a_c next to C_c and scales by -c0^2 a_c after the clamp.  Its
+ *     alg_bytes is that of the operator without a coefficient plus 8 ncells.
+ *   - The coefficient does not enter kernel selection: kernel, geometry, metric, update, the plan fields and (but for the
+ *     tetrahedral stiffness) alg_bytes are those of the operator without it; the affine-cell test, the axes-form test and
+ *     the run-table tuning see the geometry without the coefficient.
+ *   - WF_FLAG_ORDERED: y stays a pure function of the inputs, the coefficient being one of them.
+ * With NULL no scaling step runs and no array is touched: the operator is bit for bit the one without the field. */
 
 /* Dense (non-tensor-product) stiffness operator on affine simplex cells: the
  * reference's skernel (common/operators.hpp:113-133) fed with arbitrary dense
@@ -350,6 +377,8 @@ typedef struct {
   const int32_t* h_geom_dofmap; /* [ncells][4]                                    */
   double c0;
   int flags;                    /* WF_FLAG_NO_CLAMP; WF_FLAG_ORDERED: WF_ERR_UNSUPPORTED */
+  const double* h_cell_coeff;   /* [ncells] cell coefficient a_c or NULL ("Cell coefficients"): applied inside the
+                                   kernel, after -c0^2 and the clamp; alg_bytes grows by 8 ncells            */
 } wf_dense_desc;
 int wf_op_create_dense_simplex(const wf_dense_desc* desc, wf_op** out);
 
@@ -378,6 +407,7 @@ typedef struct {
   const double* h_xverts;       /* [nverts][3]                                    */
   const int32_t* h_geom_dofmap; /* [ncells][4]                                    */
   int flags;                    /* WF_FLAG_NO_FABS; WF_FLAG_ORDERED: WF_ERR_UNSUPPORTED; any other bit: WF_ERR_INVALID */
+  const double* h_cell_coeff;   /* [ncells] cell coefficient a_c or NULL ("Cell coefficients"): folded into s_c */
 } wf_dense_mass_desc;
 int wf_op_create_dense_simplex_mass(const wf_dense_mass_desc* desc, wf_op** out);
 
@@ -427,6 +457,7 @@ typedef struct {
   int geometry;          /* wf_geometry_mode of the stiffness geometry that was built    */
   int metric;            /* wf_metric_mode of the per-cell kernel, box or dofmap (0: none) */
   int update;            /* wf_update_mode of the separable kernel, box or dofmap (0: none); WF_UPDATE_ORDERED */
+  int cell_coeff;        /* 1: created with a cell coefficient array (h_cell_coeff)      */
 } wf_op_info_t;
 int wf_op_info(const wf_op* op, wf_op_info_t* info); /* num_quads()/num_cells()/... mass.hpp:68-71 */
 
@@ -676,6 +707,12 @@ int wf_fs_locate_facets(int64_t ncells, const int32_t* h_cells, int64_t nfacets,
 int wf_fs_facet_mass(int degree, int64_t nverts, const double* h_xverts, int64_t ncells, const int32_t* h_cells,
                      const int32_t* h_dofmap, int64_t nfacets, const int32_t* h_cell, const int32_t* h_axis,
                      const int32_t* h_side, int64_t* nout, int32_t* h_idx, double* h_mass);
+/* wf_fs_facet_mass with every facet's contribution multiplied by h_cell_weight[cell of the facet] ([ncells], the
+ * admittance 1/(rho c) of a heterogeneous medium); h_cell_weight = NULL is wf_fs_facet_mass. */
+int wf_fs_facet_mass_weighted(int degree, int64_t nverts, const double* h_xverts, int64_t ncells, const int32_t* h_cells,
+                              const int32_t* h_dofmap, int64_t nfacets, const int32_t* h_cell, const int32_t* h_axis,
+                              const int32_t* h_side, const double* h_cell_weight, int64_t* nout, int32_t* h_idx,
+                              double* h_mass);
 int wf_fs_min_cell_diameter(int64_t nverts, const double* h_xverts, int64_t ncells, const int32_t* h_cells, double* hmin);
 
 #ifdef __cplusplus

@@ -145,6 +145,8 @@ public:
   std::size_t num_cells() const { return info().num_cells; }
   std::size_t num_dofs() const { return info().num_dofs_cell; }
   double flops() const { return info().flops; }
+  /// whether the operator was created with a cell coefficient array (wf_op_info_t.cell_coeff)
+  bool cell_coeff() const { return info().cell_coeff != 0; }
 
   /// y += A x   (common/operators.hpp:183, common/cuda/mass.hpp:76)
   template <typename Vector>
@@ -183,6 +185,10 @@ protected:
 };
 }  // namespace detail
 
+/// Every operator wrapper takes an optional cell_coeff: one double per cell in the order of the dofmap's rows (on a box
+/// cx + nx (cy + ny cz)), copied during construction; the operator is then sum_c a_c P_c^T A_c P_c (wavehip.h, "Cell
+/// coefficients").  nullptr is the operator without one.  It is the last argument of every wrapper, behind tuning / flags.
+///
 /// StiffnessOperator(V, bdegree, params) -- common/operators.hpp:137-201.  tuning: the kernel selection of wf_tuning
 /// (read during construction only), e.g. geometry = WF_GEOMETRY_PER_CELL for a mesh of affine cells at degrees 1 to 4.
 template <typename T>
@@ -190,12 +196,14 @@ class StiffnessOperator : public detail::OpBase {
   static_assert(sizeof(T) == sizeof(double), "fp64 only");
 
 public:
-  StiffnessOperator(const Space& V, int bdegree, std::map<std::string, double>& params, const wf_tuning* tuning = nullptr)
+  StiffnessOperator(const Space& V, int bdegree, std::map<std::string, double>& params, const wf_tuning* tuning = nullptr,
+                    const double* cell_coeff = nullptr)
   {
     wf_op_desc d = base_desc(V, WF_OP_STIFFNESS, bdegree);
     auto it = params.find("c0");
     d.c0 = it == params.end() ? 1500.0 : it->second;   // operators.hpp:114
     d.tuning = tuning;
+    d.h_cell_coeff = cell_coeff;
     check(wf_op_create(&d, &_op));
   }
 };
@@ -205,10 +213,11 @@ public:
 template <typename T>
 class MassOperatorLumped : public detail::OpBase {
 public:
-  MassOperatorLumped(const Space& V, int bdegree, int flags = WF_FLAG_NONE)
+  MassOperatorLumped(const Space& V, int bdegree, int flags = WF_FLAG_NONE, const double* cell_coeff = nullptr)
   {
     wf_op_desc d = base_desc(V, WF_OP_MASS_LUMPED, bdegree);
     d.flags |= flags;
+    d.h_cell_coeff = cell_coeff;
     check(wf_op_create(&d, &_op));
   }
 };
@@ -217,7 +226,10 @@ public:
 template <typename T>
 class SpectralMassOperator : public MassOperatorLumped<T> {
 public:
-  SpectralMassOperator(const Space& V, int bdegree) : MassOperatorLumped<T>(check_degree(V, bdegree), bdegree, WF_FLAG_NO_FABS) {}
+  SpectralMassOperator(const Space& V, int bdegree, const double* cell_coeff = nullptr)
+      : MassOperatorLumped<T>(check_degree(V, bdegree), bdegree, WF_FLAG_NO_FABS, cell_coeff)
+  {
+  }
 
 private:
   static const Space& check_degree(const Space& V, int bdegree)
@@ -233,20 +245,23 @@ private:
 template <typename T>
 class MassOperator : public detail::OpBase {
 public:
-  MassOperator(const Space& V, int degree, int nq1, const double* phi1, const double* detJ, const wf_tuning* tuning = nullptr)
+  MassOperator(const Space& V, int degree, int nq1, const double* phi1, const double* detJ, const wf_tuning* tuning = nullptr,
+               const double* cell_coeff = nullptr)
   {
     wf_op_desc d = base_desc(V, WF_OP_MASS_DENSE, degree);
     d.nq1 = nq1;
     d.h_phi1 = phi1;
     d.h_detJ = detJ;
     d.tuning = tuning;
+    d.h_cell_coeff = cell_coeff;
     check(wf_op_create(&d, &_op));
   }
   /// The reference's argument list (mass.hpp:20-21): element = degree + Lagrange variant
   /// (WF_VARIANT_GLL_WARPED / WF_VARIANT_EQUISPACED), quad_type (WF_QUAD_GLL /
   /// WF_QUAD_GAUSS_JACOBI) and quadrature degree qd.  Builds the 1-D table (tabulate_1d,
   /// precompute.hpp:179-189) on the host and det J * w at the rule's points on the device.
-  MassOperator(const Space& V, int degree, int variant, int quad_type, int qd, const wf_tuning* tuning = nullptr)
+  MassOperator(const Space& V, int degree, int variant, int quad_type, int qd, const wf_tuning* tuning = nullptr,
+               const double* cell_coeff = nullptr)
   {
     int nq1 = 0;
     double pts[WF_MAX_QUAD_POINTS], wts[WF_MAX_QUAD_POINTS];
@@ -260,6 +275,7 @@ public:
     d.h_qwts1 = wts;
     d.flags |= WF_FLAG_NO_FABS;   // mass.hpp:35-39: det J * w keeps its sign (compute_jacobian_determinant)
     d.tuning = tuning;
+    d.h_cell_coeff = cell_coeff;
     check(wf_op_create(&d, &_op));
   }
 };
@@ -268,9 +284,20 @@ public:
 template <typename T>
 class BoxStiffnessOperator : public detail::OpBase {
 public:
-  BoxStiffnessOperator(int degree, int nx, int ny, int nz, const double* xverts, double c0)
+  BoxStiffnessOperator(int degree, int nx, int ny, int nz, const double* xverts, double c0, const wf_tuning* tuning = nullptr,
+                       const double* cell_coeff = nullptr)
   {
-    check(wf_op_create_box(WF_OP_STIFFNESS, degree, nx, ny, nz, xverts, c0, WF_FLAG_NONE, &_op));
+    check(wf_op_create_box_coeff(WF_OP_STIFFNESS, degree, nx, ny, nz, xverts, c0, cell_coeff, WF_FLAG_NONE, tuning, &_op));
+  }
+};
+/// The lumped mass on the same box: the pre-assembled diagonal.
+template <typename T>
+class BoxMassOperatorLumped : public detail::OpBase {
+public:
+  BoxMassOperatorLumped(int degree, int nx, int ny, int nz, const double* xverts, int flags = WF_FLAG_NONE,
+                        const double* cell_coeff = nullptr)
+  {
+    check(wf_op_create_box_coeff(WF_OP_MASS_LUMPED, degree, nx, ny, nz, xverts, 0.0, cell_coeff, flags, nullptr, &_op));
   }
 };
 

@@ -1,0 +1,238 @@
+"""LinearGLLOpt(..., medium=): the wave model in a heterogeneous medium, (1 / (rho c^2)) p_tt = div((1 / rho) grad p)
+with dp/dn = g on Gamma_1 and dp/dn = -p_t / c on Gamma_2, against a numpy model built from the oracle's pieces; and the
+C++ wrappers' checksum program (tests/cxx/medium_checksum.cpp) against the Python operators.
+
+The bound and the step count are those of test_gpu_parity.py::test_rk4_cfg1_reference_cfl against oracle.LinearGLLOpt:
+20 steps, 1e-9 of max|u| and max|v|."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import medium_helpers as mh
+from medium_helpers import relerr
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TOL_RK4 = 1e-9
+STEPS = 20
+N = (4, 4, 6)
+HI = (0.01, 0.01, 0.015)
+FREQ, P0 = 0.5e6, 6e4
+TAGS = {0: 1, 1: 2, 2: 2, 3: 2, 4: 2, 5: 2}     # the default of LinearGLLOpt; oracle.box_facets tags the same way
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import wave_fenics_amd as w
+    w.lib()
+    torch.cuda.set_device(0)
+    return torch.device("cuda", 0)
+
+
+def two_layer(mesh, rho_scale=1.0):
+    """water-like below z = 0.4 of the height (the two lower of six layers of cells), bone-like above, with a density
+    contrast"""
+    from wave_fenics_amd.medium import Medium
+    return Medium.from_centroids(mesh, lambda xc: (np.where(xc[:, 2] < 0.4 * HI[2], 1500.0, 2800.0),
+                                                   rho_scale * np.where(xc[:, 2] < 0.4 * HI[2], 1000.0, 1850.0)))
+
+
+def weighted_facet_mass(oracle, om, tag, weight):
+    """sum over the tagged facets of weight[cell] * the facet's collocated mass, facet by facet on one-cell meshes (an
+    independent accumulation: nothing of the package enters)"""
+    m = np.zeros(om.ndofs)
+    for cells, lf, t in oracle.box_facets(om):
+        if t != tag:
+            continue
+        for c in cells:
+            one = oracle.BoxMesh((1, 1, 1), om.p, om.x, om.geom_dofmap[c:c + 1], om.dofmap[c:c + 1], om.ndofs, om.lattice)
+            m += weight[c] * _single_facet(oracle, one, lf)
+    return m
+
+
+def _single_facet(oracle, one, lf):
+    """collocated mass of local face lf of a one-cell mesh: w_a w_b |t_a x t_b| at the facet's GLL points"""
+    p, n = one.p, one.p + 1
+    pts, wts = oracle.gll_points_weights(n)
+    axis, side = lf // 2, lf % 2
+    ta, tb = [d for d in range(3) if d != axis]
+    bb, aa = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    aa, bb = aa.reshape(-1), bb.reshape(-1)
+    X = np.zeros((n * n, 3))
+    X[:, axis], X[:, ta], X[:, tb] = float(side), pts[aa], pts[bb]
+    _, dphi = oracle.cmap_tabulate(X)
+    J = np.einsum("vi,jqv->qij", one.x[one.geom_dofmap[0]], dphi)
+    nrm = np.linalg.norm(np.cross(J[:, :, ta], J[:, :, tb]), axis=1)
+    loc = np.zeros((n * n, 3), dtype=np.int64)
+    loc[:, axis], loc[:, ta], loc[:, tb] = side * p, aa, bb
+    out = np.zeros(one.ndofs)
+    np.add.at(out, one.dofmap[0][loc[:, 0] + n * (loc[:, 1] + n * loc[:, 2])], wts[aa] * wts[bb] * nrm)
+    return out
+
+
+def numpy_model(oracle, om, p, medium):
+    """oracle.LinearGLLOpt with m, mG1, mG2, the stiffness operator and f1 replaced by the heterogeneous ones"""
+    G, detJ = oracle.precompute_geometric_data(om, p)
+    Ga = np.ascontiguousarray(G * medium.stiff_coeff[:, None, None, None])
+
+    class Model(oracle.LinearGLLOpt):
+        def f1(self, t, u, v, result):
+            window = 0.5 * (1.0 - np.cos(self.freq0_ * np.pi * t / self.alpha_)) if t < self.T_ * self.alpha_ else 1.0
+            s1 = window * self.p0_ * self.w0_ * np.cos(self.w0_ * t)
+            self.u_n[:] = u
+            self.v_n[:] = v
+            self.b[:] = 0.0
+            oracle.stiffness_apply_sumfact(om, Ga, 1.0, self.u_n, self.b)
+            self.b += s1 * self.mG1 - self.mG2 * self.v_n
+            result[:] = self.b / self.m
+
+    ref = Model(om, p, 1.0, FREQ, P0)
+    ref.m = mh.lumped_reference(om, p, medium.mass_coeff, np.ones(om.ndofs))
+    ref.mG1 = weighted_facet_mass(oracle, om, 1, medium.admittance)
+    ref.mG2 = weighted_facet_mass(oracle, om, 2, medium.admittance)
+    return ref
+
+
+def setup(oracle, p):
+    import wave_fenics_amd as w
+    om = oracle.create_box(N, p, hi=HI)
+    mesh = w.BoxMesh(om.n, om.x.copy(), om.geom_dofmap.copy(), (0.0, 0.0, 0.0), HI)
+    V = w.create_functionspace(mesh, p)
+    assert np.array_equal(V.dofmap, om.dofmap)
+    return om, mesh, V
+
+
+def run(eqn, fused, dt):
+    eqn.init()
+    t, steps = (eqn.rk4_fused if fused else eqn.rk4)(0.0, STEPS * dt - 1e-13, dt)
+    assert steps == STEPS
+    return eqn.u_n.cpu().numpy(), eqn.v_n.cpu().numpy()
+
+
+@pytest.mark.parametrize("p", [2, 4])
+def test_model_two_layer_medium(gpu, oracle, p):
+    from wave_fenics_amd import medium as md
+    from wave_fenics_amd.linear_gll import LinearGLLOpt
+    om, mesh, V = setup(oracle, p)
+    med = two_layer(mesh)
+    assert np.unique(med.c).size == 2 and np.unique(med.rho).size == 2
+    dt, _ = md.cfl_time_step(mesh, p, med, FREQ, CFL=0.25)
+    ref = numpy_model(oracle, om, p, med)
+    ref.init()
+    _, steps = ref.rk4(0.0, STEPS * dt - 1e-13, dt)
+    assert steps == STEPS and np.abs(ref.u_n).max() > 0.0
+    results = {}
+    for structured in (True, False):
+        for fused in (False, True):
+            eqn = LinearGLLOpt(V, p, 1500.0, FREQ, P0, structured=structured, medium=med)
+            assert eqn.stiff_op.cell_coeff and eqn.mass_op.cell_coeff
+            u, v = run(eqn, fused, dt)
+            eu, ev = relerr(u, ref.u_n), relerr(v, ref.v_n)
+            print(f"MEDIUM model P{p} structured={structured} fused={fused}: u {eu:.3e} v {ev:.3e}")
+            assert eu <= TOL_RK4 and ev <= TOL_RK4, (p, structured, fused, eu, ev)
+            results[(structured, fused)] = u
+    # scaling rho by a uniform 2 leaves u unchanged
+    eqn2 = LinearGLLOpt(V, p, 1500.0, FREQ, P0, medium=two_layer(mesh, rho_scale=2.0))
+    u2, _ = run(eqn2, False, dt)
+    assert relerr(u2, results[(True, False)]) <= TOL_RK4
+
+
+@pytest.mark.parametrize("p", [2, 4])
+def test_model_uniform_medium_is_the_homogeneous_model(gpu, oracle, p):
+    from wave_fenics_amd import linear_gll
+    from wave_fenics_amd.linear_gll import LinearGLLOpt
+    from wave_fenics_amd.medium import Medium
+    om, mesh, V = setup(oracle, p)
+    dt, _ = linear_gll.cfl_time_step(mesh, p, 1500.0, FREQ, CFL=0.25)
+    hom = LinearGLLOpt(V, p, 1500.0, FREQ, P0)
+    assert not hom.stiff_op.cell_coeff and hom.medium is None
+    uh, vh = run(hom, False, dt)
+    for fused in (False, True):
+        eqn = LinearGLLOpt(V, p, 1500.0, FREQ, P0, medium=Medium(np.full(mesh.ncells, 1500.0), np.ones(mesh.ncells)))
+        u, v = run(eqn, fused, dt)
+        assert relerr(u, uh) <= TOL_RK4 and relerr(v, vh) <= TOL_RK4, (p, fused, relerr(u, uh), relerr(v, vh))
+
+
+def test_model_on_a_mesh_file(gpu, oracle, tmp_path):
+    """the route of a mesh read from a file: boundary= from mesh_io.boundary_sets with the admittance as cell weight,
+    together with medium=, against the same numpy model (dofs matched by their coordinates)"""
+    from wave_fenics_amd import medium as md
+    from wave_fenics_amd import mesh_io
+    from wave_fenics_amd.linear_gll import LinearGLLOpt
+    p = 2
+    om, mesh, _ = setup(oracle, p)
+    lat = np.arange(mesh.x.shape[0]).reshape(N[2] + 1, N[1] + 1, N[0] + 1)
+    faces = {0: lat[:, :, 0], 1: lat[:, :, -1], 2: lat[:, 0, :], 3: lat[:, -1, :], 4: lat[0], 5: lat[-1]}
+    fv, vals = [], []
+    for lf, plane in faces.items():
+        for i in range(plane.shape[0] - 1):
+            for j in range(plane.shape[1] - 1):
+                fv.append([plane[i, j], plane[i, j + 1], plane[i + 1, j], plane[i + 1, j + 1]])
+                vals.append(TAGS[lf])
+    path = str(tmp_path / "box.xdmf")
+    mesh_io.write_mesh(path, "mesh", mesh, "boundaries", mesh_io.MeshTags(np.asarray(fv, dtype=np.int32), np.asarray(vals, dtype=np.int32)))
+    fmesh, ftags = mesh_io.read_mesh(path, "mesh", "boundaries")
+    assert np.array_equal(fmesh.geom_dofmap, mesh.geom_dofmap)      # same cell order: the medium applies as it is
+    FV = mesh_io.create_functionspace(fmesh, p)
+    med = two_layer(fmesh)
+    dt, _ = md.cfl_time_step(fmesh, p, med, FREQ, CFL=0.25)
+    ref = numpy_model(oracle, om, p, med)
+    ref.init()
+    ref.rk4(0.0, STEPS * dt - 1e-13, dt)
+    f_of_box = mh.dof_match(oracle.dof_coordinates(om), FV.dof_coordinates)
+    for fused in (False, True):
+        eqn = LinearGLLOpt(FV, p, 1500.0, FREQ, P0, boundary=mesh_io.boundary_sets(FV, ftags, cell_weight=med.admittance), medium=med)
+        assert eqn.stiff_op.cell_coeff and eqn.stiff_op.kernel != "march_box"
+        u, v = run(eqn, fused, dt)
+        eu, ev = relerr(u[f_of_box], ref.u_n), relerr(v[f_of_box], ref.v_n)
+        print(f"MEDIUM model from a file P{p} fused={fused}: u {eu:.3e} v {ev:.3e}")
+        assert eu <= TOL_RK4 and ev <= TOL_RK4, (fused, eu, ev)
+
+
+def test_medium_with_updater_raises(gpu, oracle):
+    from wave_fenics_amd.linear_gll import LinearGLLOpt
+    _, mesh, V = setup(oracle, 2)
+    with pytest.raises(NotImplementedError):
+        LinearGLLOpt(V, 2, 1500.0, FREQ, P0, updater=object(), medium=two_layer(mesh))
+
+
+def test_cxx_checksum(gpu, tmp_path):
+    """tests/cxx/medium_checksum.cpp: the wrappers' box stiffness and lumped mass with a two-value coefficient; the
+    checksum sum_i y_i w_i against the same operators created in Python, to TOL of sum_i |y_i w_i|"""
+    import torch
+    import wave_fenics_amd as w
+    exe = str(tmp_path / "medium_checksum")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cxx", "medium_checksum.cpp"), "-o", exe,
+                           "-L", os.path.join(ROOT, "wave_fenics_amd"), "-lwavehip",
+                           "-Wl,-rpath," + os.path.join(ROOT, "wave_fenics_amd")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = {ln.split()[0]: ln.split() for ln in r.stdout.splitlines() if "checksum" in ln}
+    P, n = 4, (9, 3, 5)
+    coord = lambda m: np.array([0.75 * i + 0.75 * (i // 2) for i in range(m + 1)])
+    mesh = mh.ich.box_with(n, x=mh.ich.lattice_x(coord(n[0]), coord(n[1]), coord(n[2])))
+    V = w.create_functionspace(mesh, P)
+    cx, _, cz = mh.nh.cell_coords(n).T
+    a = np.where(cx + cz < 5, 1.0, 8.0)
+    i = np.arange(V.ndofs, dtype=np.int64)
+    x = ((i * 7919) % 1009) / 1024.0 - 0.5
+    wt = ((i * 104729) % 1013) / 1024.0 + 0.5
+    ops = {"stiffness": w.StiffnessOperator(V, P, {"c0": 1500.0}, cell_coeff=a), "lumped": w.MassOperatorLumped(V, P, cell_coeff=a)}
+    for name, op in ops.items():
+        y = torch.zeros(V.ndofs, dtype=torch.float64, device=gpu)
+        op(torch.from_numpy(x).to(gpu), y)
+        torch.cuda.synchronize()
+        yw = y.cpu().numpy() * wt
+        line = got[name]
+        assert line[2] == "1", line
+        cs, scale = float(line[4]), float(line[6])
+        print(f"MEDIUM cxx {name}: C++ {cs:.17e} Python {yw.sum():.17e} scale {scale:.3e}")
+        assert abs(scale - np.abs(yw).sum()) <= mh.TOL * scale
+        assert abs(cs - yw.sum()) <= mh.TOL * scale, (name, cs, yw.sum())

@@ -135,6 +135,114 @@ def bench_tet(dev):
             "setup_s": round(t3 - t2, 2)})
 
 
+def bench_medium(dev):
+    """Cell coefficients: the P4 box apply (owner kernel) and the P4 tetrahedral stiffness apply at ~10.2 M dofs, each with
+    and without a coefficient array, alternating in one process (MEDIUM_ROUNDS rounds, default 7; every timing after the
+    settle protocol of timeit).  A box coefficient is folded into the stored geometry: same kernel, same bytes.  The
+    tetrahedral stiffness runs its coefficient variant (one more double per cell)."""
+    from wave_fenics_amd import tet
+    rounds = int(os.environ.get("MEDIUM_ROUNDS", "7"))
+    p = 4
+
+    def alternate(plain, coeff, x, y):
+        ms = {"plain": [], "coeff": []}
+        for _ in range(rounds):
+            ms["plain"].append(timeit(lambda: plain(x, y)))
+            ms["coeff"].append(timeit(lambda: coeff(x, y)))
+        return ms
+
+    def lines(name, ops, ms, N, extra):
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        for k in ("plain", "coeff"):
+            op = ops[k]
+            report(f"{name} [{op.kernel}] " + ("with cell_coeff" if k == "coeff" else "without"), med[k], op.alg_bytes(), N,
+                   dict(extra, cell_coeff=op.cell_coeff, kernel=op.kernel, geometry=op.geometry, metric=op.metric, update=op.update,
+                        lz=op.info.plan_lz, alg_bytes=op.alg_bytes(), device_bytes=op.info.device_bytes,
+                        ms_rounds=[round(v, 4) for v in ms[k]], spread=round((max(ms[k]) - min(ms[k])) / med[k], 4),
+                        coeff_over_plain=round(med["coeff"] / med["plain"], 4)))
+
+    if "MEDIUM_SKIP_BOX" not in os.environ:
+        n = 54
+        mesh = w.create_box(n, hi=(float(n),) * 3)     # unit cubes: affine by the bitwise rule, the owner form
+        V = w.create_functionspace(mesh, p, build_dofmap=False)
+        a = 0.5 + np.modf(1.618033988749895 * np.arange(mesh.ncells))[0] * 3.5
+        ops = {"plain": w.StiffnessOperator(V, p), "coeff": w.StiffnessOperator(V, p, cell_coeff=a)}
+        N = V.ndofs
+        x = torch.rand(N, dtype=torch.float64, device=dev)
+        y = torch.zeros(N, dtype=torch.float64, device=dev)
+        lines(f"stiffness P{p} box {n}^3", ops, alternate(ops["plain"], ops["coeff"], x, y), N,
+              {"degree": p, "cells": mesh.ncells, "ndofs": N, "runs": [len(ops[k].runs()) for k in ("plain", "coeff")]})
+        del ops, x, y, V, mesh
+        torch.cuda.empty_cache()
+    n = int(os.environ.get("TET_N", "54"))
+    V = tet.create_kuhn_box(n, p)
+    a = 0.5 + np.modf(1.618033988749895 * np.arange(V.ncells))[0] * 3.5
+    ops = {"plain": tet.TetStiffnessOperator(V, p), "coeff": tet.TetStiffnessOperator(V, p, cell_coeff=a)}
+    N = V.ndofs
+    x = torch.rand(N, dtype=torch.float64, device=dev)
+    y = torch.zeros(N, dtype=torch.float64, device=dev)
+    lines(f"tet P{p} dense stiffness, Kuhn box {n}^3 cubes", ops, alternate(ops["plain"], ops["coeff"], x, y), N,
+          {"cells": V.ncells, "ndofs": N})
+
+
+def bench_tet_against(dev, other_path):
+    """The default (no coefficient) P4 tetrahedral stiffness apply of this library against ANOTHER build of libwavehip --
+    the parent commit's, say -- with both libraries loaded into this one process, the same operator created through each
+    and the applies alternating (MEDIUM_ROUNDS rounds, default 7).  `python tools/bench_ops.py tet-ab` with the other
+    library's path in WAVEHIP_LIB_B.  Only wf_op_create_dense_simplex, wf_op_apply and wf_op_destroy of the other library
+    are called, with this tree's descriptor: an older library reads the leading fields it knows."""
+    import ctypes
+    from wave_fenics_amd import _lib, tet
+    from wave_fenics_amd.operators import _dp, _ip
+    this, other = w.lib(), ctypes.CDLL(other_path)
+    other.wf_op_create_dense_simplex.restype = ctypes.c_int
+    other.wf_op_create_dense_simplex.argtypes = [ctypes.POINTER(_lib.DenseDesc), ctypes.POINTER(ctypes.c_void_p)]
+    other.wf_op_apply.restype = ctypes.c_int
+    other.wf_op_apply.argtypes = [ctypes.c_void_p] * 4
+    other.wf_op_destroy.argtypes = [ctypes.c_void_p]
+    p, n = 4, int(os.environ.get("TET_N", "54"))
+    V = tet.create_kuhn_box(n, p)
+    X, W = tet.tet_quadrature(p)                  # the rule of tet.TetStiffnessOperator: degree 2p - 2, m = p
+    dphi = np.ascontiguousarray(tet.clamp101(tet.tabulate_tet(p, X)[1]))
+    W = np.ascontiguousarray(W)
+    dm, xv, gd = (np.ascontiguousarray(V.dofmap, dtype=np.int32), np.ascontiguousarray(V.x, dtype=np.float64),
+                  np.ascontiguousarray(V.geom_dofmap, dtype=np.int32))
+    d = _lib.DenseDesc()
+    d.nd, d.nq, d.ncells, d.ndofs = dphi.shape[2], dphi.shape[1], V.ncells, V.ndofs
+    d.h_dofmap, d.h_dphi, d.h_weights = _ip(dm), _dp(dphi), _dp(W)
+    d.nverts, d.h_xverts, d.h_geom_dofmap = xv.shape[0], _dp(xv), _ip(gd)
+    d.c0, d.flags = 1500.0, 0
+    libs = {"this library": this, "other library": other}
+    handles = {}
+    for name, L in libs.items():
+        handles[name] = ctypes.c_void_p()
+        rc = L.wf_op_create_dense_simplex(ctypes.byref(d), ctypes.byref(handles[name]))
+        if rc != 0:
+            raise RuntimeError(f"{name}: wf_op_create_dense_simplex returned {rc}")
+    N = V.ndofs
+    x = torch.rand(N, dtype=torch.float64, device=dev)
+    y = torch.zeros(N, dtype=torch.float64, device=dev)
+    once = {}
+    for name, L in libs.items():
+        y.zero_()
+        L.wf_op_apply(handles[name], x.data_ptr(), y.data_ptr(), 0)
+        torch.cuda.synchronize()
+        once[name] = y.clone()
+    ms = {name: [] for name in libs}
+    for _ in range(int(os.environ.get("MEDIUM_ROUNDS", "7"))):
+        for name in ("other library", "this library"):
+            ms[name].append(timeit(lambda: libs[name].wf_op_apply(handles[name], x.data_ptr(), y.data_ptr(), 0)))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    for name in libs:
+        print(json.dumps({"op": f"tet P{p} dense stiffness without a coefficient, Kuhn box {n}^3 cubes, {name}", "ms": round(med[name], 4),
+                          "ms_rounds": [round(v, 4) for v in ms[name]], "cells": V.ncells, "ndofs": N,
+                          "this_over_other": round(med["this library"] / med["other library"], 4),
+                          "max_abs_diff_of_one_apply": float((once["this library"] - once["other library"]).abs().max()),
+                          "max_abs_y": float(once["this library"].abs().max())}), flush=True)
+    for name, L in libs.items():
+        L.wf_op_destroy(handles[name])
+
+
 def bench_tsmm(dev):
     # demo/gpu_tsmm/main.cpp: ndofs = 125, ncells = 100000, two products, GFLOPs = 4*ncells*nd^2/t
     for ncells, nd in ((100000, 125), (1000000, 125), (1000000, 64), (2000000, 27), (300000, 216), (200000, 343)):
@@ -159,6 +267,16 @@ def main():
     if "tsmm" in only:
         bench_tsmm(dev)
         only = [o for o in only if o != "tsmm"]
+        if not only:
+            return
+    if "tet-ab" in only:
+        bench_tet_against(dev, os.environ["WAVEHIP_LIB_B"])
+        only = [o for o in only if o != "tet-ab"]
+        if not only:
+            return
+    if "medium" in only:
+        bench_medium(dev)
+        only = [o for o in only if o != "medium"]
         if not only:
             return
     if "tet" in only:

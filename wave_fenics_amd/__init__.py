@@ -16,3 +16,4 @@ from .operators import (  # noqa: F401
     quadrature_1d, tabulate_1d, compute_geometry_rule, hex_cell_geometry, ordered_slots, segment_sum_add, box_run_plan,
 )
 from . import la  # noqa: F401
+from .medium import Medium  # noqa: F401

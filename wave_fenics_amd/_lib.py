@@ -33,6 +33,7 @@ class OpDesc(ctypes.Structure):
         ("nq1", c_int), ("h_phi1", POINTER(c_double)),
         ("h_qpts1", POINTER(c_double)), ("h_qwts1", POINTER(c_double)),
         ("tuning", POINTER(Tuning)),
+        ("h_cell_coeff", POINTER(c_double)),
     ]
 
 
@@ -42,6 +43,7 @@ class DenseDesc(ctypes.Structure):
         ("h_dofmap", POINTER(c_int32)), ("h_dphi", POINTER(c_double)), ("h_weights", POINTER(c_double)),
         ("nverts", c_int), ("h_xverts", POINTER(c_double)), ("h_geom_dofmap", POINTER(c_int32)),
         ("c0", c_double), ("flags", c_int),
+        ("h_cell_coeff", POINTER(c_double)),
     ]
 
 
@@ -51,6 +53,7 @@ class DenseMassDesc(ctypes.Structure):
         ("h_dofmap", POINTER(c_int32)), ("h_phi", POINTER(c_double)), ("h_weights", POINTER(c_double)),
         ("nverts", c_int), ("h_xverts", POINTER(c_double)), ("h_geom_dofmap", POINTER(c_int32)),
         ("flags", c_int),
+        ("h_cell_coeff", POINTER(c_double)),
     ]
 
 
@@ -62,7 +65,7 @@ class OpInfo(ctypes.Structure):
         ("items_interior", c_int), ("items_interface", c_int),
         ("kernel", c_int), ("plan_items", c_int), ("plan_patterns", c_int), ("plan_lz", c_int),
         ("plan_reoriented", c_int), ("plan_fill", c_double), ("geometry", c_int), ("metric", c_int),
-        ("update", c_int),
+        ("update", c_int), ("cell_coeff", c_int),
     ]
 
 
@@ -131,6 +134,8 @@ SIGNATURES = {
     "wf_op_create_box": (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_int, POINTER(c_void_p)]),
     "wf_op_create_box_tuned": (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_int, POINTER(Tuning),
                                        POINTER(c_void_p)]),
+    "wf_op_create_box_coeff": (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, c_double, _dp, c_int, POINTER(Tuning),
+                                       POINTER(c_void_p)]),
     "wf_op_set_ghost_dofs": (c_int, [c_void_p, _ip, c_int32]),
     "wf_op_create_dense_simplex": (c_int, [POINTER(DenseDesc), POINTER(c_void_p)]),
     "wf_op_create_dense_simplex_mass": (c_int, [POINTER(DenseMassDesc), POINTER(c_void_p)]),
@@ -195,6 +200,8 @@ SIGNATURES = {
     "wf_fs_build": (c_int, [c_int, c_int64, _dp, c_int64, _ip, POINTER(c_int64), _ip, _dp, c_int64]),
     "wf_fs_locate_facets": (c_int, [c_int64, _ip, c_int64, _ip, _ip, _ip, _ip]),
     "wf_fs_facet_mass": (c_int, [c_int, c_int64, _dp, c_int64, _ip, _ip, c_int64, _ip, _ip, _ip, POINTER(c_int64), _ip, _dp]),
+    "wf_fs_facet_mass_weighted": (c_int, [c_int, c_int64, _dp, c_int64, _ip, _ip, c_int64, _ip, _ip, _ip, _dp, POINTER(c_int64),
+                                          _ip, _dp]),
     "wf_fs_min_cell_diameter": (c_int, [c_int64, _dp, c_int64, _ip, POINTER(c_double)]),
     "wf_cg": (c_int, [POINTER(CGDesc), c_void_p, c_void_p, POINTER(c_int), POINTER(c_double), c_void_p]),
     "wf_boundary_apply": (c_int, [c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p, c_void_p, c_double,

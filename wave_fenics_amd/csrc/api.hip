@@ -102,8 +102,8 @@ static int geometry_hex_rule(int n, const double* h_pts, const double* h_wts, in
   DevArray<double> d_G, d_det;
   if (h_G && (rc = d_G.alloc((size_t)ncells * nq * 9)) != WF_OK) return rc;
   if (h_detJ && (rc = d_det.alloc((size_t)ncells * nq)) != WF_OK) return rc;
-  if ((rc = mesh_geometry_rule(n, h_pts, h_wts, {(size_t)ncells, nverts, h_xverts, h_geom_dofmap}, use_fabs, clamp, d_G.data(),
-                               nullptr, d_det.data())) != WF_OK)
+  if ((rc = mesh_geometry_rule(n, h_pts, h_wts, {(size_t)ncells, nverts, h_xverts, h_geom_dofmap}, use_fabs, clamp, nullptr,
+                               d_G.data(), nullptr, d_det.data())) != WF_OK)
     return rc;
   if (h_G) WF_HIP_CHECK(hipMemcpy(h_G, d_G.data(), d_G.bytes(), hipMemcpyDeviceToHost));
   if (h_detJ) WF_HIP_CHECK(hipMemcpy(h_detJ, d_det.data(), d_det.bytes(), hipMemcpyDeviceToHost));

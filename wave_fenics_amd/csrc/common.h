@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -107,18 +108,20 @@ void gll_derivative_matrix(int P, double* D);  // clamped, D[q*n + a]
 inline int cells_per_batch(int P) { return 256 / ((P + 1) * (P + 1)); }
 
 // ---- kernel launchers (kernels.hip) ----
+// d_cell_coeff (every geometry launcher; null: none): the cell coefficient a_c per cell in the order of the cells the
+// kernel is given; every entry written, det J w included, is then the entry without it times a_c
 int launch_geometry_hex(int P, int ncells, const double* d_xverts, const int32_t* d_geom_dofmap,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp,
-                        double* d_G9, double* d_G6blk, double* d_detJ, hipStream_t s);
+                        double* d_G9, double* d_G6blk, double* d_detJ, const double* d_cell_coeff, hipStream_t s);
 // lattice plans with a fill (cells per cell slot) below this keep the batch kernel: the marching kernels
 // read geometry for every slot of a column, empty or not
 constexpr double kMinPlanFill = 0.55;
 int launch_geometry_box(int P, int nx, int ny, int nz, int bx, int by, int bz, const double* d_xverts,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp,
-                        double* d_G6blk, double* d_detJ_lattice, hipStream_t s);
+                        double* d_G6blk, double* d_detJ_lattice, const double* d_cell_coeff, hipStream_t s);
 int launch_geometry_hex_slots(int P, int CB, int ncells, const double* d_xverts, const int32_t* d_geom_dofmap,
                               const int32_t* d_slot_of, const uint8_t* d_orient, const double* d_pts, const double* d_wts,
-                              int use_fabs, int clamp, double* d_G6blk, hipStream_t s);
+                              int use_fabs, int clamp, double* d_G6blk, const double* d_cell_coeff, hipStream_t s);
 int launch_pack_G6(int P, int CB, int ncells, const double* d_G9, double* d_G6blk, hipStream_t s);
 int launch_stiffness_generic(int P, int ncells, const int32_t* d_dofmap, const double* d_G6blk,
                              const double* d_D, const DMat& dm, double coeff, const double* d_x,
@@ -213,6 +216,16 @@ int launch_stiffness_march_ks_box(int P, int bx, int by, int nx, int ny, int nz,
 int launch_stiffness_march_ks_idx(int P, int bx, int by, const MarchPlanDev& pd, const double* d_G6blk, const double* d_D,
                                   const DMat& dm, double coeff, const double* d_x, double* d_y, const int32_t* d_items,
                                   int nitems, hipStream_t s);
+// a cell coefficient array (may be null): WF_ERR_INVALID naming the first cell whose entry is not finite
+inline int check_cell_coeff(const double* a, size_t ncells, const char* who)
+{
+  for (size_t c = 0; a && c < ncells; ++c)
+    if (!std::isfinite(a[c])) {
+      set_error(std::string(who) + ": h_cell_coeff[" + std::to_string(c) + "] is not finite (cell " + std::to_string(c) + ")");
+      return WF_ERR_INVALID;
+    }
+  return WF_OK;
+}
 // host-side validation of indices a kernel will dereference: WF_ERR_INVALID with `message` unless every
 // idx[e], e < count, lies in [0, bound)
 inline int check_index_range(const int32_t* idx, size_t count, int64_t bound, const std::string& message)
@@ -235,7 +248,8 @@ struct DenseBatchPlan {
 int dense_batch_plan(int nd, int KT, int NCB, int ncells, const int32_t* dofmap, DenseBatchPlan* plan);
 struct DenseOpData;
 int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, const double* dphi,
-                const double* weights, const double* xverts, const int32_t* geom_dofmap, DenseOpData** out);
+                const double* weights, const double* xverts, const int32_t* geom_dofmap, const double* cell_coeff,
+                DenseOpData** out);
 void dense_free(DenseOpData* d);
 size_t dense_bytes(const DenseOpData* d);
 int launch_stiffness_dense(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,
@@ -243,7 +257,8 @@ int launch_stiffness_dense(const DenseOpData* d, double coeff, int do_clamp, con
 // dense simplex mass (mass_dense_simplex.hip): y += s_c A x per cell, A = Phi^T diag(w) Phi, s_c = |det J_c|
 struct DenseMassData;
 int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const double* phi, const double* weights,
-                     const double* xverts, const int32_t* geom_dofmap, int use_fabs, DenseMassData** out);
+                     const double* xverts, const int32_t* geom_dofmap, int use_fabs, const double* cell_coeff,
+                     DenseMassData** out);
 void dense_mass_free(DenseMassData* d);
 size_t dense_mass_bytes(const DenseMassData* d);
 int launch_mass_dense_simplex(const DenseMassData* d, const double* d_x, double* d_y, hipStream_t s);

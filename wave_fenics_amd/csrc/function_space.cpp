@@ -243,6 +243,16 @@ int wf_fs_facet_mass(int degree, int64_t nverts, const double* h_xverts, int64_t
                      const int32_t* h_dofmap, int64_t nfacets, const int32_t* h_cell, const int32_t* h_axis,
                      const int32_t* h_side, int64_t* nout, int32_t* h_idx, double* h_mass)
 {
+  return wf_fs_facet_mass_weighted(degree, nverts, h_xverts, ncells, h_cells, h_dofmap, nfacets, h_cell, h_axis, h_side,
+                                   nullptr, nout, h_idx, h_mass);
+}
+
+// the same with every facet's contribution multiplied by the weight of its cell (null: no weight)
+int wf_fs_facet_mass_weighted(int degree, int64_t nverts, const double* h_xverts, int64_t ncells, const int32_t* h_cells,
+                              const int32_t* h_dofmap, int64_t nfacets, const int32_t* h_cell, const int32_t* h_axis,
+                              const int32_t* h_side, const double* h_cell_weight, int64_t* nout, int32_t* h_idx,
+                              double* h_mass)
+{
   WF_REQUIRE(degree >= 1 && degree <= kMaxDegree && nout, "wf_fs_facet_mass: bad argument");
   WF_REQUIRE(nfacets == 0 || (h_xverts && h_cells && h_dofmap && h_cell && h_axis && h_side && h_idx && h_mass),
              "wf_fs_facet_mass: null array");
@@ -276,7 +286,7 @@ int wf_fs_facet_mass(int degree, int64_t nverts, const double* h_xverts, int64_t
         l[axis] = side * P;
         l[ta] = a;
         l[tb] = b;
-        acc[h_dofmap[c * nd + l[0] + n * (l[1] + n * l[2])]] += ds;
+        acc[h_dofmap[c * nd + l[0] + n * (l[1] + n * l[2])]] += h_cell_weight ? ds * h_cell_weight[c] : ds;
       }
   }
   int64_t k = 0;

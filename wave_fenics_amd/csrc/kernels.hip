@@ -117,6 +117,18 @@ __device__ __forceinline__ void hex_point_geometry(const double (*xv)[3], double
   }
 }
 
+// Cell coefficient a_c (wavehip.h, "Cell coefficients"): the finished entries of a point -- G after the clamp, det J w --
+// times a_c, one rounding each.  The geometry kernels call it only when the operator has a coefficient array; c is
+// the kernel's own cell index, so the array comes in the order of the cells the kernel is given.
+__device__ __forceinline__ void scale_point_geometry(double a, double* G9, double* detJw)
+{
+  *detJw *= a;
+  if (G9) {
+#pragma unroll
+    for (int m = 0; m < 9; ++m) G9[m] *= a;
+  }
+}
+
 // Blocked symmetric geometry layout shared by the stiffness kernels:
 //   G6blk[batch][k][p][t][e],  t = cl * n^2 + (j * n + i) < NT = CB * n^2,
 //   (p, e) -> component: (0,0)=G00 (0,1)=G01 (1,0)=G02 (1,1)=G11 (2,0)=G12 (2,1)=G22
@@ -143,7 +155,7 @@ __global__ void k_geometry_hex(int n, int CB, int ncells, const double* __restri
                                const int32_t* __restrict__ geom_dofmap, const double* __restrict__ pts,
                                const double* __restrict__ wts, int use_fabs, int do_clamp,
                                double* __restrict__ G9out, double* __restrict__ G6blk,
-                               double* __restrict__ detJ)
+                               double* __restrict__ detJ, const double* __restrict__ cell_coeff)
 {
   const int nd = n * n * n;
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -161,6 +173,7 @@ __global__ void k_geometry_hex(int n, int CB, int ncells, const double* __restri
   const bool wantG = (G9out != nullptr) || (G6blk != nullptr);
   hex_point_geometry(xv, pts[i], pts[j], pts[k], wts[i] * wts[j] * wts[k], use_fabs, do_clamp,
                      wantG ? G9 : nullptr, &d);
+  if (cell_coeff) scale_point_geometry(cell_coeff[c], wantG ? G9 : nullptr, &d);
   if (detJ) detJ[gid] = d;
   if (G9out)
     for (int m = 0; m < 9; ++m) G9out[gid * 9 + m] = G9[m];
@@ -179,7 +192,7 @@ __global__ void k_geometry_hex_slots(int n, int CB, int ncells, const double* __
                                      const int32_t* __restrict__ geom_dofmap, const int32_t* __restrict__ slot_of,
                                      const int8_t* __restrict__ cell_sign,
                                      const double* __restrict__ pts, const double* __restrict__ wts, int use_fabs,
-                                     int do_clamp, double* __restrict__ G6blk)
+                                     int do_clamp, double* __restrict__ G6blk, const double* __restrict__ cell_coeff)
 {
   const int nd = n * n * n;
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -197,6 +210,7 @@ __global__ void k_geometry_hex_slots(int n, int CB, int ncells, const double* __
   hex_point_geometry(xv, pts[i], pts[j], pts[k], wts[i] * wts[j] * wts[k], use_fabs, do_clamp, G9, &d);
   if (!use_fabs && cell_sign && cell_sign[c] < 0)
     for (int m = 0; m < 9; ++m) G9[m] = -G9[m];
+  if (cell_coeff) scale_point_geometry(cell_coeff[c], G9, &d);
   const int slot = slot_of[c];
   store_g6(G6blk, n, CB * n * n, slot / CB, k, (slot % CB) * n * n + j * n + i, G9);
 }
@@ -222,7 +236,8 @@ __global__ void k_pack_G6(int n, int CB, int ncells, const double* __restrict__ 
 __global__ void k_geometry_box(int n, int nx, int ny, int nz, int bx, int by, int bz,
                                const double* __restrict__ xverts, const double* __restrict__ pts,
                                const double* __restrict__ wts, int use_fabs, int do_clamp,
-                               double* __restrict__ G6blk, double* __restrict__ mdiag)
+                               double* __restrict__ G6blk, double* __restrict__ mdiag,
+                               const double* __restrict__ cell_coeff)
 {
   const int P = n - 1, nd = n * n * n;
   const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -241,6 +256,7 @@ __global__ void k_geometry_box(int n, int nx, int ny, int nz, int bx, int by, in
   double G9[9], d;
   hex_point_geometry(xv, pts[i], pts[j], pts[k], wts[i] * wts[j] * wts[k], use_fabs, do_clamp,
                      G6blk ? G9 : nullptr, &d);
+  if (cell_coeff) scale_point_geometry(cell_coeff[c], G6blk ? G9 : nullptr, &d);
   if (mdiag) {
     const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1;
     const size_t g = (size_t)(P * cx + i) + NX * ((size_t)(P * cy + j) + NY * (size_t)(P * cz + k));
@@ -1112,27 +1128,27 @@ static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n
 
 int launch_geometry_hex(int P, int ncells, const double* d_xverts, const int32_t* d_geom_dofmap,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp, double* d_G9,
-                        double* d_G6blk, double* d_detJ, hipStream_t s)
+                        double* d_G6blk, double* d_detJ, const double* d_cell_coeff, hipStream_t s)
 {
   const int n = P + 1;
   const size_t N = (size_t)ncells * n * n * n;
   if (N == 0) return WF_OK;
   hipLaunchKernelGGL(k_geometry_hex, dim3(grid_for(N, 256)), dim3(256), 0, s, n, cells_per_batch(P), ncells,
-                     d_xverts, d_geom_dofmap, d_pts, d_wts, use_fabs, clamp, d_G9, d_G6blk, d_detJ);
+                     d_xverts, d_geom_dofmap, d_pts, d_wts, use_fabs, clamp, d_G9, d_G6blk, d_detJ, d_cell_coeff);
   WF_LAUNCH_CHECK();
   return WF_OK;
 }
 
 int launch_geometry_hex_slots(int P, int CB, int ncells, const double* d_xverts, const int32_t* d_geom_dofmap,
                               const int32_t* d_slot_of, const uint8_t* d_sign, const double* d_pts, const double* d_wts,
-                              int use_fabs, int clamp, double* d_G6blk, hipStream_t s)
+                              int use_fabs, int clamp, double* d_G6blk, const double* d_cell_coeff, hipStream_t s)
 {
   const int n = P + 1;
   const size_t N = (size_t)ncells * n * n * n;
   if (N == 0) return WF_OK;
   hipLaunchKernelGGL(k_geometry_hex_slots, dim3(grid_for(N, 256)), dim3(256), 0, s, n, CB, ncells,
                      d_xverts, d_geom_dofmap, d_slot_of, reinterpret_cast<const int8_t*>(d_sign), d_pts, d_wts, use_fabs,
-                     clamp, d_G6blk);
+                     clamp, d_G6blk, d_cell_coeff);
   WF_LAUNCH_CHECK();
   return WF_OK;
 }
@@ -1150,13 +1166,13 @@ int launch_pack_G6(int P, int CB, int ncells, const double* d_G9, double* d_G6bl
 
 int launch_geometry_box(int P, int nx, int ny, int nz, int bx, int by, int bz, const double* d_xverts,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp, double* d_G6blk,
-                        double* d_mdiag, hipStream_t s)
+                        double* d_mdiag, const double* d_cell_coeff, hipStream_t s)
 {
   const int n = P + 1;
   const size_t N = (size_t)nx * ny * nz * n * n * n;
   if (N == 0) return WF_OK;
   hipLaunchKernelGGL(k_geometry_box, dim3(grid_for(N, 256)), dim3(256), 0, s, n, nx, ny, nz, bx, by, bz,
-                     d_xverts, d_pts, d_wts, use_fabs, clamp, d_G6blk, d_mdiag);
+                     d_xverts, d_pts, d_wts, use_fabs, clamp, d_G6blk, d_mdiag, d_cell_coeff);
   WF_LAUNCH_CHECK();
   return WF_OK;
 }

@@ -249,7 +249,8 @@ size_t dense_mass_bytes(const DenseMassData* d)
 // Host setup: A = Phi^T diag(w) Phi in the padded LDS layout, s_c per cell slot, the batch plan of the dense simplex
 // kernels.  Nothing touches the device before every check has passed.
 int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const double* phi, const double* weights,
-                     const double* xverts, const int32_t* geom_dofmap, int use_fabs, DenseMassData** out)
+                     const double* xverts, const int32_t* geom_dofmap, int use_fabs, const double* cell_coeff,
+                     DenseMassData** out)
 {
   std::unique_ptr<DenseMassData, void (*)(DenseMassData*)> d(new DenseMassData, dense_mass_free);
   d->nd = nd;
@@ -291,6 +292,7 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
       return WF_ERR_INVALID;
     }
     sc[c] = use_fabs ? std::fabs(det) : det;
+    if (cell_coeff) sc[c] *= cell_coeff[c];   // the cell coefficient: folded into s_c, rounded once
   }
   DenseBatchPlan plan;
   if (int rc = dense_batch_plan(nd, d->KT, NCB, ncells, dofmap, &plan)) return rc;

@@ -51,6 +51,7 @@ struct wf_op {
   int nq1 = 0;
   int lz0_split = 1;   // length of the first z segment of the interior / interface parts
   double coeff = 0.0;
+  int cell_coeff = 0;   // created with a cell coefficient array: folded into the stored geometry (dense simplex: own array)
   wf::DMat dm{};
   wf::DMat am{};   // A = D^T diag(w) D: the 1-D operator of the separable box form (MarchGeom::cell_axes)
   wf::DevArray<int32_t> d_dofmap;
@@ -134,8 +135,9 @@ struct HexMesh {
 // the GLL points and weights of degree P on the device
 int upload_tables(int P, DevArray<double>& d_pts, DevArray<double>& d_wts);
 int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB);
+// h_cell_coeff (may be null): the cell coefficient per cell of `mesh`, folded into every array written
 int mesh_geometry_rule(int n1, const double* h_pts, const double* h_wts, const HexMesh& mesh, int use_fabs, int clamp,
-                       double* d_G9, double* d_G6blk, double* d_detJ);
+                       const double* h_cell_coeff, double* d_G9, double* d_G6blk, double* d_detJ);
 int host_detJ(const wf_op_desc* desc, std::vector<double>& hd, const double** hsrc, bool* raw_points);
 int upload_derivative_tables(wf_op* op, bool box);
 int stage_G9(int P, int CB, size_t nslots, const double* direct, const std::function<void(size_t, double*)>& fill_slot,

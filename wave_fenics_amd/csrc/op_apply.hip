@@ -108,11 +108,13 @@ int wf_op_create_dense_simplex(const wf_dense_desc* desc, wf_op** out)
   if ((rc = check_index_range(desc->h_geom_dofmap, (size_t)desc->ncells * 4, desc->nverts,
                               "wf_op_create_dense_simplex: vertex index out of range")) != WF_OK)
     return rc;
+  if ((rc = check_cell_coeff(desc->h_cell_coeff, (size_t)desc->ncells, "wf_op_create_dense_simplex")) != WF_OK) return rc;
   OpPtr op = new_op(WF_OP_STIFFNESS, 0, desc->nd, desc->nq, desc->ncells, desc->ndofs, desc->c0, nullptr);
+  op->cell_coeff = desc->h_cell_coeff != nullptr;
   op->kernel = OpKernel::dense_simplex;
   op->dense_clamp = clamp_flag(desc->flags);
   rc = dense_setup(desc->nd, desc->nq, desc->ncells, desc->ndofs, desc->h_dofmap, desc->h_dphi, desc->h_weights,
-                   desc->h_xverts, desc->h_geom_dofmap, &op->dense);
+                   desc->h_xverts, desc->h_geom_dofmap, desc->h_cell_coeff, &op->dense);
   if (rc != WF_OK) return rc;
   *out = op.release();
   return WF_OK;
@@ -144,10 +146,12 @@ int wf_op_create_dense_simplex_mass(const wf_dense_mass_desc* desc, wf_op** out)
   if ((rc = check_index_range(desc->h_geom_dofmap, (size_t)desc->ncells * 4, desc->nverts,
                               "wf_op_create_dense_simplex_mass: vertex index out of range")) != WF_OK)
     return rc;
+  if ((rc = check_cell_coeff(desc->h_cell_coeff, (size_t)desc->ncells, "wf_op_create_dense_simplex_mass")) != WF_OK) return rc;
   OpPtr op = new_op(WF_OP_MASS_DENSE, 0, desc->nd, desc->nq, desc->ncells, desc->ndofs, 0.0, nullptr);
+  op->cell_coeff = desc->h_cell_coeff != nullptr;
   op->kernel = OpKernel::dense_simplex_mass;
   rc = dense_mass_setup(desc->nd, desc->nq, desc->ncells, desc->h_dofmap, desc->h_phi, desc->h_weights, desc->h_xverts,
-                        desc->h_geom_dofmap, fabs_flag(desc->flags), &op->dense_mass);
+                        desc->h_geom_dofmap, fabs_flag(desc->flags), desc->h_cell_coeff, &op->dense_mass);
   if (rc != WF_OK) return rc;
   *out = op.release();
   return WF_OK;
@@ -375,6 +379,7 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
     info->alg_bytes = 24.0 * op->ndofs;   // pre-assembled diagonal: read m, x, y + write y (SURVEY 8d counts 24)
   else
     info->alg_bytes = (double)op->ncells * (8.0 * op->nq + 4.0 * op->nd) + 16.0 * op->ndofs;
+  if (dense && op->cell_coeff) info->alg_bytes += 8.0 * op->ncells;   // the one per-cell array the coefficient adds
   // order-fixed accumulation: per element-local entry the slot (4), the store and the load of v (8 + 8); the row offsets
   if (kernel == WF_KERNEL_CELLS_ORDERED) info->alg_bytes += 20.0 * op->ncells * op->nd + 4.0 * (op->ndofs + 1.0);
   info->device_bytes = op_device_bytes(op);
@@ -389,6 +394,7 @@ int wf_op_info(const wf_op* op, wf_op_info_t* info)
   info->geometry = geometry;
   info->metric = metric;
   info->update = update;
+  info->cell_coeff = op->cell_coeff;
   return WF_OK;
 }
 

@@ -97,6 +97,8 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
         const double g = h_Gc[(size_t)c * 6 + sym[ra[a]][ra[b2]]];
         blk[q * 6 + m] = (fl[a] ^ fl[b2]) ? -g : g;
       }
+      if (desc->h_cell_coeff)   // the cell coefficient follows the cell into its slot
+        for (int m = 0; m < 6; ++m) blk[q * 6 + m] *= desc->h_cell_coeff[c];
     }
     if ((rc = op->d_Gcell.upload(blk)) != WF_OK) return rc;
     op->kernel = OpKernel::idx_march;
@@ -111,7 +113,7 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
     // along lattice axis a, s = -1 when reversed) at the relabelled point -- the operator
     // D^T G D is the same in every frame
     PointMaps point_map{fr, n};
-    auto fill_slot = [&](size_t slot, double* dst) {
+    auto fill_slot_plain = [&](size_t slot, double* dst) {
       const int32_t c = plan.slot_cell[slot];
       if (c < 0) {
         std::fill(dst, dst + (size_t)nd * 9, 0.0);
@@ -132,6 +134,12 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
           for (int b2 = 0; b2 < 3; ++b2) dst[pt * 9 + a * 3 + b2] = ((fl[a] ^ fl[b2]) ? -1.0 : 1.0) * g9[ra[a] * 3 + ra[b2]];
       }
     };
+    auto fill_slot = [&](size_t slot, double* dst) {
+      fill_slot_plain(slot, dst);
+      const int32_t c = plan.slot_cell[slot];
+      if (desc->h_cell_coeff && c >= 0)   // the cell coefficient follows the cell into its slot
+        for (int e = 0; e < nd * 9; ++e) dst[e] *= desc->h_cell_coeff[c];
+    };
     if ((rc = stage_G9(P, CB, nslots, nullptr, fill_slot, op->d_G6blk.data())) != WF_OK) return rc;
   } else {
     // one geometry thread per (present cell, point), written to the cell's slot; a cell is handed
@@ -139,6 +147,7 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
     const size_t ncells = (size_t)desc->ncells;
     std::vector<int32_t> gd, slot_of;
     std::vector<uint8_t> sign;
+    std::vector<double> coeff;   // the cell coefficient of every listed cell (empty: none)
     gd.reserve(ncells * 8);
     slot_of.reserve(ncells);
     sign.reserve(ncells);
@@ -150,18 +159,20 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
       for (int v = 0; v < 8; ++v) gd.push_back(gsrc[orient_local_index(code, 2, v & 1, (v >> 1) & 1, (v >> 2) & 1)]);
       slot_of.push_back((int32_t)q);
       sign.push_back((uint8_t)(int8_t)orient_sign(code));
+      if (desc->h_cell_coeff) coeff.push_back(desc->h_cell_coeff[c]);
     }
-    DevArray<double> d_x, d_pts, d_wts;
+    DevArray<double> d_x, d_pts, d_wts, d_coeff;
     DevArray<int32_t> d_gd, d_slot;
     DevArray<uint8_t> d_sign;
     if ((rc = d_x.upload(desc->h_xverts, (size_t)desc->nverts * 3)) != WF_OK) return rc;
     if ((rc = d_gd.upload(gd)) != WF_OK) return rc;
     if ((rc = d_slot.upload(slot_of)) != WF_OK) return rc;
     if ((rc = d_sign.upload(sign)) != WF_OK) return rc;
+    if ((rc = d_coeff.upload(coeff)) != WF_OK) return rc;   // no coefficient: no array
     if ((rc = upload_tables(P, d_pts, d_wts)) != WF_OK) return rc;
     if ((rc = launch_geometry_hex_slots(P, CB, (int)slot_of.size(), d_x.data(), d_gd.data(), d_slot.data(), d_sign.data(),
                                         d_pts.data(), d_wts.data(), fabs_flag(desc->flags), clamp_flag(desc->flags),
-                                        op->d_G6blk.data(), nullptr)) != WF_OK)
+                                        op->d_G6blk.data(), d_coeff.data(), nullptr)) != WF_OK)
       return rc;
   }
   op->kernel = OpKernel::idx_march;
@@ -341,7 +352,8 @@ bool batch_cell_order(const wf_op_desc* desc, int nd, bool keep, std::vector<int
 // the caller's per-cell arrays in the internal cell order and the engine's point order (copies only where they differ)
 struct BatchInputs {
   std::vector<int32_t> cperm, p_geom;
-  std::vector<double> p_detJ;
+  std::vector<double> p_detJ, p_coeff;
+  const double* cell_coeff = nullptr;   // the cell coefficient in the internal cell order (null: none)
   bool identity_cells = true;
   bool have_mesh = false;
   HexMesh mesh{};
@@ -379,19 +391,21 @@ int batch_stiffness(const wf_op_desc* desc, const CallerFrame& fr, const BatchIn
   if ((rc = op->d_G6blk.alloc(g6)) != WF_OK) return rc;
   if (g6) WF_HIP_CHECK(hipMemset(op->d_G6blk.data(), 0, g6 * sizeof(double)));
   if (desc->h_G) {
-    const bool direct = in.identity_cells && !fr.xslow;
+    const bool direct = in.identity_cells && !fr.xslow && !in.cell_coeff;
     const std::vector<int32_t> qm = fr.qmap(n);
     auto fill_cell = [&](size_t c, double* dst) {
       const double* gsrc = desc->h_G + (size_t)in.cperm[c] * nd * 9;
       for (int q = 0; q < nd; ++q) std::memcpy(dst + (size_t)q * 9, gsrc + (size_t)qm[q] * 9, 9 * sizeof(double));
+      if (in.cell_coeff)
+        for (int e = 0; e < nd * 9; ++e) dst[e] *= in.cell_coeff[c];
     };
     return stage_G9(P, CB, ncells, direct ? desc->h_G : nullptr, fill_cell, op->d_G6blk.data());
   }
   if (in.have_mesh) {
     std::vector<double> pts(n), wts(n);
     gll_points_weights(n, pts.data(), wts.data());
-    return mesh_geometry_rule(n, pts.data(), wts.data(), in.mesh, fabs_flag(desc->flags), clamp_flag(desc->flags), nullptr,
-                              op->d_G6blk.data(), nullptr);
+    return mesh_geometry_rule(n, pts.data(), wts.data(), in.mesh, fabs_flag(desc->flags), clamp_flag(desc->flags), in.cell_coeff,
+                              nullptr, op->d_G6blk.data(), nullptr);
   }
   if (ncells) {
     set_error("wf_op_create: stiffness needs h_G or the mesh (h_xverts, h_geom_dofmap)");
@@ -437,7 +451,7 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
     if (!dense) gll_points_weights(n, pts.data(), wts.data());
     if ((rc = op->d_detJ.alloc(ncells * op->nq)) != WF_OK) return rc;
     if ((rc = mesh_geometry_rule(nq1, dense ? desc->h_qpts1 : pts.data(), dense ? desc->h_qwts1 : wts.data(), in.mesh,
-                                 fabs_flag(desc->flags), 0, nullptr, nullptr, op->d_detJ.data())) != WF_OK)
+                                 fabs_flag(desc->flags), 0, in.cell_coeff, nullptr, nullptr, op->d_detJ.data())) != WF_OK)
       return rc;
   } else if (ncells) {
     set_error("wf_op_create: mass needs h_detJ or the mesh (h_xverts, h_geom_dofmap)");
@@ -498,7 +512,15 @@ int create_batch(const wf_op_desc* desc, const CallerFrame& fr, const int32_t* t
       std::memcpy(&in.p_geom[c * 8], desc->h_geom_dofmap + (size_t)in.cperm[c] * 8, 8 * sizeof(int32_t));
     in.mesh.geom_dofmap = in.p_geom.data();
   }
-  if (desc->h_detJ && (!in.identity_cells || fr.xslow)) {
+  if (desc->h_cell_coeff) {
+    in.cell_coeff = desc->h_cell_coeff;
+    if (!in.identity_cells) {
+      in.p_coeff.resize(ncells);
+      for (size_t c = 0; c < ncells; ++c) in.p_coeff[c] = desc->h_cell_coeff[in.cperm[c]];
+      in.cell_coeff = in.p_coeff.data();
+    }
+  }
+  if (desc->h_detJ && (!in.identity_cells || fr.xslow || in.cell_coeff)) {
     const int mq = desc->kind == WF_OP_MASS_DENSE ? desc->nq1 : n;
     WF_REQUIRE(mq >= 1 && mq <= 16, "wf_op_create: bad nq1");
     const size_t nqm = (size_t)mq * mq * mq;
@@ -506,7 +528,7 @@ int create_batch(const wf_op_desc* desc, const CallerFrame& fr, const int32_t* t
     in.p_detJ.resize(ncells * nqm);
     for (size_t c = 0; c < ncells; ++c) {
       const double* src = desc->h_detJ + (size_t)in.cperm[c] * nqm;
-      for (size_t q = 0; q < nqm; ++q) in.p_detJ[c * nqm + q] = src[qm[q]];
+      for (size_t q = 0; q < nqm; ++q) in.p_detJ[c * nqm + q] = in.cell_coeff ? src[qm[q]] * in.cell_coeff[c] : src[qm[q]];
     }
     in.h_detJ = in.p_detJ.data();
   }
@@ -565,8 +587,11 @@ int wf_op_create(const wf_op_desc* desc, wf_op** out)
       && (rc = check_index_range(desc->h_geom_dofmap, ncells * 8, desc->nverts, "wf_op_create: vertex index out of range")) != WF_OK)
     return rc;
 
+  if ((rc = check_cell_coeff(desc->h_cell_coeff, ncells, "wf_op_create")) != WF_OK) return rc;
+
   const CallerFrame fr(desc, n);
   OpPtr op = new_op(desc->kind, P, nd, nd, desc->ncells, desc->ndofs, desc->c0, desc->tuning);
+  op->cell_coeff = desc->h_cell_coeff != nullptr;
   const wf_tuning& tun = op->tun;
   // order-fixed accumulation: one form per operator kind, always on the cell batches -- there is no kernel to choose
   op->ordered = (desc->flags & WF_FLAG_ORDERED) != 0;

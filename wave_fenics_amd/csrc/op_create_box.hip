@@ -152,8 +152,8 @@ int upload_box_cell_geometry(wf_op* op, const std::vector<double>& h_Gc)
 // WF_FLAG_ORDERED on a box: the box's lexicographic dofmap (dof (I, J, K) -> I + NX (J + NY K), tensor order) and vertex
 // map (vertex (a, b, c) -> a + (nx+1)(b + (ny+1) c)) built on the host, then the dofmap operator of wf_op_create -- a box
 // operator with the flag IS that dofmap operator, bit for bit.
-int create_box_ordered(int kind, int P, int nx, int ny, int nz, const double* h_xverts, double c0, int flags,
-                       const wf_tuning* tuning, wf_op** out)
+int create_box_ordered(int kind, int P, int nx, int ny, int nz, const double* h_xverts, double c0, const double* h_cell_coeff,
+                       int flags, const wf_tuning* tuning, wf_op** out)
 {
   const int n = P + 1, nd = n * n * n;
   const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
@@ -181,6 +181,7 @@ int create_box_ordered(int kind, int P, int nx, int ny, int nz, const double* h_
   d.c0 = c0;
   d.flags = flags;
   d.tuning = tuning;
+  d.h_cell_coeff = h_cell_coeff;   // the dofmap's rows are the box's cells in lexicographic order
   int rc = wf_op_create(&d, out);
   if (rc != WF_OK) return rc;
   (*out)->structured = 1;
@@ -364,11 +365,17 @@ int wf_op_get_runs(const wf_op* op, int32_t* h_runs, int32_t capacity, int32_t* 
 int wf_op_create_box(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0, int flags,
                      wf_op** out)
 {
-  return wf_op_create_box_tuned(kind, degree, nx, ny, nz, h_xverts, c0, flags, nullptr, out);
+  return wf_op_create_box_coeff(kind, degree, nx, ny, nz, h_xverts, c0, nullptr, flags, nullptr, out);
 }
 
 int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0, int flags,
                            const wf_tuning* tuning, wf_op** out)
+{
+  return wf_op_create_box_coeff(kind, degree, nx, ny, nz, h_xverts, c0, nullptr, flags, tuning, out);
+}
+
+int wf_op_create_box_coeff(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0,
+                           const double* h_cell_coeff, int flags, const wf_tuning* tuning, wf_op** out)
 {
   WF_REQUIRE(out != nullptr, "wf_op_create_box: null output");
   *out = nullptr;
@@ -384,9 +391,12 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
   WF_REQUIRE(NX * NY * NZ < ((size_t)1 << 31), "wf_op_create_box: dof lattice exceeds int32");
   const int n = P + 1, nd = n * n * n;
-  if (flags & WF_FLAG_ORDERED) return create_box_ordered(kind, P, nx, ny, nz, h_xverts, c0, flags, tuning, out);
+  const size_t ncells = (size_t)nx * ny * nz;
+  if (int bad = check_cell_coeff(h_cell_coeff, ncells, "wf_op_create_box")) return bad;
+  if (flags & WF_FLAG_ORDERED) return create_box_ordered(kind, P, nx, ny, nz, h_xverts, c0, h_cell_coeff, flags, tuning, out);
 
   OpPtr op = new_op(kind, P, nd, nd, nx * ny * nz, (int)(NX * NY * NZ), c0, tuning);
+  op->cell_coeff = h_cell_coeff != nullptr;
   op->nq1 = n;
   op->structured = 1;
   op->nx = nx;
@@ -400,9 +410,17 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
   if (kind == WF_OP_STIFFNESS
       && (rc = choose_box_stiffness(P, nx, ny, nz, h_xverts, flags, op->tun, &op->kernel, &op->box, &op->geom, h_Gc)) != WF_OK)
     return rc;
+  // The cell coefficient enters behind every choice: the affine-cell test, the axes test and the z segmentation have
+  // seen the geometry without it.  Per-cell geometry takes it here, in the caller's cell order; the device-built arrays
+  // take it in the geometry kernel.
+  if (h_cell_coeff && kind == WF_OP_STIFFNESS && op->geom != MarchGeom::point)
+    for (size_t e = 0; e < h_Gc.size(); ++e) h_Gc[e] *= h_cell_coeff[e / 6];
 
   if ((rc = upload_derivative_tables(op.get(), true)) != WF_OK) return rc;
-  DevArray<double> d_x, d_pts, d_wts;
+  DevArray<double> d_x, d_pts, d_wts, d_coeff;
+  if (h_cell_coeff && (kind != WF_OP_STIFFNESS || op->geom == MarchGeom::point)
+      && (rc = d_coeff.upload(h_cell_coeff, ncells)) != WF_OK)
+    return rc;
   const size_t nverts = (size_t)(nx + 1) * (ny + 1) * (nz + 1);
   if ((rc = d_x.upload(h_xverts, nverts * 3)) != WF_OK) return rc;
   if ((rc = upload_tables(P, d_pts, d_wts)) != WF_OK) return rc;
@@ -415,7 +433,7 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
     if ((rc = op->d_G6blk.alloc(g6)) != WF_OK) return rc;
     WF_HIP_CHECK(hipMemset(op->d_G6blk.data(), 0, g6 * sizeof(double)));
     if ((rc = launch_geometry_box(P, nx, ny, nz, op->box.bx, op->box.by, op->box.bz, d_x.data(), d_pts.data(), d_wts.data(),
-                                  fabs_flag(flags), clamp_flag(flags), op->d_G6blk.data(), nullptr, nullptr)) != WF_OK)
+                                  fabs_flag(flags), clamp_flag(flags), op->d_G6blk.data(), nullptr, d_coeff.data(), nullptr)) != WF_OK)
       return rc;
   } else {
     // pre-assembled lumped mass diagonal: y += m .* x is 24 B/dof instead of the
@@ -423,7 +441,7 @@ int wf_op_create_box_tuned(int kind, int degree, int nx, int ny, int nz, const d
     if ((rc = op->d_mdiag.alloc((size_t)op->ndofs)) != WF_OK) return rc;
     WF_HIP_CHECK(hipMemset(op->d_mdiag.data(), 0, (size_t)op->ndofs * sizeof(double)));
     if ((rc = launch_geometry_box(P, nx, ny, nz, 1, 1, 1, d_x.data(), d_pts.data(), d_wts.data(), fabs_flag(flags),
-                                  clamp_flag(flags), nullptr, op->d_mdiag.data(), nullptr)) != WF_OK)
+                                  clamp_flag(flags), nullptr, op->d_mdiag.data(), d_coeff.data(), nullptr)) != WF_OK)
       return rc;
   }
   WF_HIP_CHECK(hipDeviceSynchronize());

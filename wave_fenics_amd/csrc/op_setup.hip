@@ -71,36 +71,46 @@ int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB)
 // d_G9[ncells][n1^3][9], d_G6blk (blocked by cells_per_batch(n1 - 1)) and d_detJ[ncells][n1^3] (det J * w) are given.
 // The kernel is generic in the number of points per direction.
 int mesh_geometry_rule(int n1, const double* h_pts, const double* h_wts, const HexMesh& mesh, int use_fabs, int clamp,
-                       double* d_G9, double* d_G6blk, double* d_detJ)
+                       const double* h_cell_coeff, double* d_G9, double* d_G6blk, double* d_detJ)
 {
-  DevArray<double> d_x, d_pts, d_wts;
+  DevArray<double> d_x, d_pts, d_wts, d_coeff;
   DevArray<int32_t> d_gd;
   int rc;
   if ((rc = d_x.upload(mesh.xverts, (size_t)mesh.nverts * 3)) != WF_OK) return rc;
   if ((rc = d_gd.upload(mesh.geom_dofmap, mesh.ncells * 8)) != WF_OK) return rc;
   if ((rc = d_pts.upload(h_pts, (size_t)n1)) != WF_OK) return rc;
   if ((rc = d_wts.upload(h_wts, (size_t)n1)) != WF_OK) return rc;
+  if (h_cell_coeff && (rc = d_coeff.upload(h_cell_coeff, mesh.ncells)) != WF_OK) return rc;
   if ((rc = launch_geometry_hex(n1 - 1, (int)mesh.ncells, d_x.data(), d_gd.data(), d_pts.data(), d_wts.data(), use_fabs,
-                                clamp, d_G9, d_G6blk, d_detJ, nullptr)) != WF_OK)
+                                clamp, d_G9, d_G6blk, d_detJ, d_coeff.data(), nullptr)) != WF_OK)
     return rc;
   WF_HIP_CHECK(hipDeviceSynchronize());
   return WF_OK;
 }
 
 // det J * w per cell and point of a dense mass with a square table, on the host: the caller's h_detJ (caller's point
-// order), else computed from the mesh at the caller's rule into hd (*raw_points: the engine's point order)
+// order), else computed from the mesh at the caller's rule into hd (*raw_points: the engine's point order).  With a cell
+// coefficient every entry is det J w times a_c (a scaled copy of h_detJ in hd)
 int host_detJ(const wf_op_desc* desc, std::vector<double>& hd, const double** hsrc, bool* raw_points)
 {
   *hsrc = desc->h_detJ;
   *raw_points = !desc->h_detJ;
-  if (desc->h_detJ) return WF_OK;
   const int n = desc->nq1;
+  if (desc->h_detJ && desc->h_cell_coeff) {
+    const size_t nq = (size_t)n * n * n;
+    hd.resize((size_t)desc->ncells * nq);
+    for (size_t c = 0; c < (size_t)desc->ncells; ++c)
+      for (size_t q = 0; q < nq; ++q) hd[c * nq + q] = desc->h_detJ[c * nq + q] * desc->h_cell_coeff[c];
+    *hsrc = hd.data();
+  }
+  if (desc->h_detJ) return WF_OK;
   DevArray<double> d_det;
   hd.resize((size_t)desc->ncells * n * n * n);
   int rc;
   if ((rc = d_det.alloc(hd.size())) != WF_OK) return rc;
   const HexMesh mesh{(size_t)desc->ncells, desc->nverts, desc->h_xverts, desc->h_geom_dofmap};
-  if ((rc = mesh_geometry_rule(n, desc->h_qpts1, desc->h_qwts1, mesh, fabs_flag(desc->flags), 0, nullptr, nullptr, d_det.data())) != WF_OK)
+  if ((rc = mesh_geometry_rule(n, desc->h_qpts1, desc->h_qwts1, mesh, fabs_flag(desc->flags), 0, desc->h_cell_coeff, nullptr, nullptr,
+                               d_det.data())) != WF_OK)
     return rc;
   WF_HIP_CHECK(hipMemcpy(hd.data(), d_det.data(), hd.size() * sizeof(double), hipMemcpyDeviceToHost));
   *hsrc = hd.data();

@@ -69,11 +69,15 @@ __device__ __forceinline__ double clamp101d(double v)
 // kernel's MFMA cycles.  Those rows are instead accumulated lane-locally with VALU FMAs in the
 // shadow of the MFMAs (each lane owns the quadrature points q = lg mod 4 of its cell) and summed
 // over the four lane groups once per batch.
-template <int QT, int KT, int DT, int NW, int NU, int XR>
+// AC: the operator has a cell coefficient a_c (wavehip.h, "Cell coefficients"): Ag holds one per cell slot, loaded and
+// prefetched with the lane's C_c, and the factor of F is coeff * a_c.  It cannot be folded into C_c: the clamp windows
+// are windows of w_q C_c.  The AC = false instantiations never touch Ag and are the kernel without the parameter.
+template <int QT, int KT, int DT, int NW, int NU, int XR, bool AC>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_stiffness_dense(int nd, int nq, int nbatch, int numax,
                                                          const double* __restrict__ Tg,      // [3*16*QT][KP] padded table
                                                          const double* __restrict__ wq,      // [16*QT] weights (0 beyond nq)
                                                          const double* __restrict__ Cg,      // [nbatch*16*NW][6]
+                                                         const double* __restrict__ Ag,      // AC: [nbatch*16*NW] cell coefficients (padding 0)
                                                          const uint32_t* __restrict__ locP,  // [nbatch][ceil(KT/2)][4][16*NW]: local index of dof 4(2j)+lg | that of dof 4(2j+1)+lg << 16
                                                          const int32_t* __restrict__ uoff,   // [nbatch+1]
                                                          const int32_t* __restrict__ uniq,   // unique dofs of all batches
@@ -147,8 +151,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   };
   // Local indices travel as packed pairs: loaded as 16-bit values the compiler packs them two to a
   // register right after the load, i.e. waits for the prefetch it has just issued.
-  auto load_cell = [&](uint32_t (&loc)[KT2], double (&C)[6], int b) {
+  auto load_cell = [&](uint32_t (&loc)[KT2], double (&C)[6], double& ac, int b) {
     const int bb = b < nbatch ? b : nbatch - 1;
+    if constexpr (AC) ac = Ag[(size_t)bb * NCB + wave * 16 + lc];
 #pragma unroll
     for (int j = 0; j < KT2; ++j) loc[j] = locP[(((size_t)bb * KT2 + j) * 4 + lg) * NCB + wave * 16 + lc];
     const double* cp = Cg + ((size_t)bb * NCB + wave * 16 + lc) * 6;
@@ -160,6 +165,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   uint32_t loc[KT2], locn[KT2];
   auto loc_of = [&](int ks) -> uint32_t { return (loc[ks >> 1] >> (16 * (ks & 1))) & 0xffffu; };
   double C[6], Cn[6];
+  [[maybe_unused]] double ac = 1.0, acn = 1.0;   // AC: the lane's cell coefficient, this batch's and the next one's
   // prologue: first batch straight into LDS, indices of the second
   int nu_cur, nu_nxt;   // live entries of uq_cur / uq_nxt
   {
@@ -167,7 +173,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     load_uq(uq_cur, r0);
     nu_cur = count_of(r0);
     load_x(xr, uq_cur);
-    load_cell(loc, C, blockIdx.x);
+    load_cell(loc, C, ac, blockIdx.x);
     load_uq(uq_nxt, r1);
     nu_nxt = count_of(r1);
   }
@@ -193,6 +199,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // falls into one of its windows; the host marks the batches where that happens (same
     // double-precision products), every other batch skips ~200 VALU instructions per slab
     const bool clamp_here = do_clamp && clamp_cur;
+    double coeff_c = coeff;   // the factor of F: -c0^2, times the cell's coefficient
+    if constexpr (AC) coeff_c = coeff * ac;
     __syncthreads();   // Xu holds this batch's x values, Yu is zero
     WF_DTR(0);
 
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     WF_DTR(1);
     // gather of the next batch (registers) and index list of the one after it
     int32_t uq_nn[NU];
-    load_cell(locn, Cn, batch + G);
+    load_cell(locn, Cn, acn, batch + G);
     load_uq(uq_nn, rg2);
     const int nu_nn = count_of(rg2);
     const Range rg3 = load_range(batch + 3 * G);
@@ -284,9 +292,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
           g11 = clamp101d(g11); g12 = clamp101d(g12); g22 = clamp101d(g22);
         }
         const double w0 = W[0][r], w1 = W[1][r], w2 = W[2][r];
-        W[0][r] = coeff * (g00 * w0 + g01 * w1 + g02 * w2);
-        W[1][r] = coeff * (g01 * w0 + g11 * w1 + g12 * w2);
-        W[2][r] = coeff * (g02 * w0 + g12 * w1 + g22 * w2);
+        W[0][r] = coeff_c * (g00 * w0 + g01 * w1 + g02 * w2);
+        W[1][r] = coeff_c * (g01 * w0 + g11 * w1 + g12 * w2);
+        W[2][r] = coeff_c * (g02 * w0 + g12 * w1 + g22 * w2);
       }
       // ---- Y += T^T . F : accumulator register r of a tile is the B operand of k-step r
 #pragma unroll
@@ -355,6 +363,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     for (int j = 0; j < KT2; ++j) loc[j] = locn[j];
 #pragma unroll
     for (int e = 0; e < 6; ++e) C[e] = Cn[e];
+    if constexpr (AC) ac = acn;
     rg2 = rg3;
     clamp_cur = clamp_nxt;
     const int nu_old = nu_cur;
@@ -379,6 +388,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 struct DenseOpData {
   int nd = 0, nq = 0, QT = 0, KT = 0, DT = 0, nbatch = 0, numax = 0, nw = 4;
   DevArray<double> d_T, d_w, d_C;
+  DevArray<double> d_a;   // cell coefficients per cell slot of the batches; empty: none, the AC = false kernel runs
   DevArray<uint32_t> d_locP;
   DevArray<int32_t> d_uoff, d_uniq;
   DevArray<uint8_t> d_clampb;
@@ -453,7 +463,8 @@ int dense_batch_plan(int nd, int KT, int NCB, int ncells, const int32_t* dofmap,
 // Host setup: padded table, per-cell affine geometry C = |det J| K K^T, per-batch
 // unique-dof lists and local indices.
 int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, const double* dphi,
-                const double* weights, const double* xverts, const int32_t* geom_dofmap, DenseOpData** out)
+                const double* weights, const double* xverts, const int32_t* geom_dofmap, const double* cell_coeff,
+                DenseOpData** out)
 {
   std::unique_ptr<DenseOpData, void (*)(DenseOpData*)> d(new DenseOpData, dense_free);
   d->nd = nd;
@@ -529,6 +540,11 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
   if ((rc = d->d_T.upload(T)) != WF_OK) return rc;
   if ((rc = d->d_w.upload(w)) != WF_OK) return rc;
   if ((rc = d->d_C.upload(C)) != WF_OK) return rc;
+  if (cell_coeff) {   // in the batches' cell order, which is the caller's; padding slots 0
+    std::vector<double> a((size_t)nbatch * NCB, 0.0);
+    std::copy(cell_coeff, cell_coeff + ncells, a.begin());
+    if ((rc = d->d_a.upload(a)) != WF_OK) return rc;
+  }
   if ((rc = d->d_locP.upload(plan.locP)) != WF_OK) return rc;
   if ((rc = d->d_uoff.upload(plan.uoff)) != WF_OK) return rc;
   if ((rc = d->d_uniq.upload(plan.uniq)) != WF_OK) return rc;
@@ -539,12 +555,12 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
 
 size_t dense_bytes(const DenseOpData* d)
 {
-  return d ? d->d_T.bytes() + d->d_w.bytes() + d->d_C.bytes() + d->d_locP.bytes() + d->d_uoff.bytes() + d->d_uniq.bytes()
+  return d ? d->d_T.bytes() + d->d_w.bytes() + d->d_C.bytes() + d->d_a.bytes() + d->d_locP.bytes() + d->d_uoff.bytes() + d->d_uniq.bytes()
                  + d->d_clampb.bytes()
            : 0;
 }
 
-template <int QT, int KT, int DT, int NW, int NU, int XR>
+template <int QT, int KT, int DT, int NW, int NU, int XR, bool AC>
 static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,
                           hipStream_t s)
 {
@@ -554,7 +570,7 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
     set_error("stiffness_dense: tables do not fit LDS");
     return WF_ERR_UNSUPPORTED;
   }
-  auto kern = k_stiffness_dense<QT, KT, DT, NW, NU, XR>;
+  auto kern = k_stiffness_dense<QT, KT, DT, NW, NU, XR, AC>;
   if (lds > 64 * 1024)
     WF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)lds));
@@ -567,7 +583,7 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
 #endif
   const unsigned nb = (unsigned)std::min(d->nbatch, 256 * wgs_per_cu);   // persistent: the table is staged into LDS once per workgroup
   hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * NW), lds, s, d->nd, d->nq, d->nbatch, d->numax, d->d_T.data(),
-                     d->d_w.data(), d->d_C.data(), d->d_locP.data(), d->d_uoff.data(), d->d_uniq.data(), d->d_clampb.data(),
+                     d->d_w.data(), d->d_C.data(), d->d_a.data(), d->d_locP.data(), d->d_uoff.data(), d->d_uniq.data(), d->d_clampb.data(),
                      coeff, do_clamp, d_x, d_y, ablate, stagger);
   return launch_status("stiffness_dense");
 }
@@ -575,8 +591,10 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
 // NU = 5 covers the unique dofs of 64 well-numbered P4 cells (1154 on the Kuhn box); 9 is the worst case 64 * 35
 #define WF_DENSE_CASE(Q, K, D, X)                                                                                \
   if (d->QT == Q && d->KT == K && d->DT == D && (X == 0 || d->nd == 16 * (D - 1) + X))                            \
-    return d->numax <= 5 * 256 ? launch_dense_t<Q, K, D, 4, 5, X>(d, coeff, do_clamp, d_x, d_y, s)                \
-                               : launch_dense_t<Q, K, D, 4, 9, X>(d, coeff, do_clamp, d_x, d_y, s);
+    return d->numax <= 5 * 256 ? (d->d_a.size() ? launch_dense_t<Q, K, D, 4, 5, X, true>(d, coeff, do_clamp, d_x, d_y, s)    \
+                                                : launch_dense_t<Q, K, D, 4, 5, X, false>(d, coeff, do_clamp, d_x, d_y, s))  \
+                               : (d->d_a.size() ? launch_dense_t<Q, K, D, 4, 9, X, true>(d, coeff, do_clamp, d_x, d_y, s)    \
+                                                : launch_dense_t<Q, K, D, 4, 9, X, false>(d, coeff, do_clamp, d_x, d_y, s));
 
 // (dense_setup has refused every shape that is not in WF_DENSE_SHAPES)
 int launch_stiffness_dense(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,

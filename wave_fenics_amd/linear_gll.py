@@ -25,10 +25,15 @@ from . import la
 from .operators import MassOperatorLumped, StiffnessOperator
 
 
-def facet_lumped_mass(V, tag_of_face, tag: int):
+def facet_lumped_mass(V, tag_of_face, tag: int, cell_weight=None):
     """Collocated facet mass m_Gamma[i] = sum_facets w_q |J_facet| for the box
     faces carrying `tag` (tag_of_face maps local face 2*axis+side -> tag).
+    cell_weight [ncells] (or None): every facet's contribution times the value of its cell.
     Host-side setup (numpy); returns (dof indices int32, masses float64)."""
+    if cell_weight is not None:
+        cell_weight = np.ascontiguousarray(cell_weight, dtype=np.float64).reshape(-1)
+        if cell_weight.size != V.mesh.ncells:
+            raise ValueError(f"cell_weight has {cell_weight.size} entries, the mesh has {V.mesh.ncells} cells")
     from .operators import tabulate_gll
     mesh = V.mesh
     p = V.degree
@@ -66,6 +71,8 @@ def facet_lumped_mass(V, tag_of_face, tag: int):
             J = np.einsum("fvi,jqv->fqij", xc, dphi)
             nrm = np.linalg.norm(np.cross(J[:, :, :, ta], J[:, :, :, tb]), axis=2)
             wq = (w[aa] * w[bb])[None, :] * nrm
+            if cell_weight is not None:
+                wq = wq * cell_weight[cells][:, None]
             loc = np.zeros((n * n, 3), dtype=np.int64)
             loc[:, axis] = side * p
             loc[:, ta] = aa
@@ -84,7 +91,18 @@ def facet_lumped_mass(V, tag_of_face, tag: int):
 class LinearGLLOpt:
     def __init__(self, V, degreeOfBasis: int, speedOfSound: float, sourceFrequency: float,
                  pressureAmplitude: float, boundary=None, updater=None, device=None, structured=None,
-                 tags=None, tuning=None):
+                 tags=None, tuning=None, medium=None):
+        if medium is not None:
+            # (1/(rho c^2)) p_tt = div((1/rho) grad p), dp/dn = g on Gamma_1, dp/dn = -p_t / c on Gamma_2 (medium.py).
+            # The facet masses of both boundary sets carry the admittance 1 / (rho c) of the facet's cell: derived from
+            # tags they are weighted here; a caller's boundary= (a mesh read from a file) must carry it already --
+            # mesh_io.boundary_sets(V, tags, cell_weight=medium.admittance).
+            if updater is not None:
+                raise NotImplementedError("LinearGLLOpt: medium= on a partitioned mesh (updater=) is not implemented; the "
+                                          "operators themselves take per-local-cell coefficients on any partition")
+            if medium.ncells != V.mesh.ncells:
+                raise ValueError(f"medium has {medium.ncells} cells, the mesh has {V.mesh.ncells}")
+        self.medium = medium
         self.V = V
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
         self.k_ = degreeOfBasis
@@ -102,7 +120,10 @@ class LinearGLLOpt:
         self.m, self.b = z(), z()
         # LinearGLL.hpp:102-110: m = M 1, then scatter_rev(add)
         ones = torch.ones(N, dtype=torch.float64, device=self.device)
-        self.mass_op = MassOperatorLumped(V, self.k_, structured=structured)
+        if medium is None:
+            self.mass_op = MassOperatorLumped(V, self.k_, structured=structured)
+        else:
+            self.mass_op = MassOperatorLumped(V, self.k_, structured=structured, cell_coeff=medium.mass_coeff)
         self.mass_op(ones, self.m)
         if self.updater is not None:
             self.updater.scatter_rev(self.m)
@@ -115,6 +136,9 @@ class LinearGLLOpt:
                 from .distributed import owned_boundary
                 i1, m1 = owned_boundary(self.updater, V, tags, 1, self.device)
                 i2, m2 = owned_boundary(self.updater, V, tags, 2, self.device)
+            elif medium is not None:
+                i1, m1 = facet_lumped_mass(V, tags, 1, medium.admittance)
+                i2, m2 = facet_lumped_mass(V, tags, 2, medium.admittance)
             else:
                 i1, m1 = facet_lumped_mass(V, tags, 1)
                 i2, m2 = facet_lumped_mass(V, tags, 2)
@@ -132,7 +156,13 @@ class LinearGLLOpt:
         self.idx1, self.mG1 = td(i1, torch.int32), td(m1, torch.float64)
         self.idx2, self.mG2 = td(i2, torch.int32), td(m2, torch.float64)
         # LinearGLL.hpp:120-127; tuning: the stiffness operator's make_tuning dict, e.g. {"geometry": "per_cell"}
-        self.stiff_op = StiffnessOperator(V, self.k_, {"c0": self.c0_}, structured=structured, tuning=tuning)
+        if medium is None:
+            self.stiff_op = StiffnessOperator(V, self.k_, {"c0": self.c0_}, structured=structured, tuning=tuning)
+        else:
+            self.stiff_op = StiffnessOperator(V, self.k_, {"c0": 1.0}, structured=structured, tuning=tuning,
+                                              cell_coeff=medium.stiff_coeff)
+        # (the boundary term stays two scalars per stage: with a medium the facet masses carry the admittance 1 / (rho c),
+        # s1(t) = window p0 w0 cos(w0 t) and s2 = -1: _boundary_scalars)
         # domain-decomposed run: interior cells overlap the forward ghost update
         self._split = False
         if self.updater is not None:
@@ -149,6 +179,14 @@ class LinearGLLOpt:
         self.u_n.zero_()
         self.v_n.zero_()
 
+    def _boundary_scalars(self, window: float, t: float):
+        """(s1, s2) of the boundary term b[idx1] += s1 mG1, b[idx2] += s2 mG2 v at time t: c0^2 g(t) and -c0
+        (LinearGLL.hpp:153-162,175); with a medium window p0 w0 cos(w0 t) and -1 on admittance-weighted facet masses."""
+        if self.medium is None:
+            g = window * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
+            return self.c0_ ** 2 * g, -self.c0_
+        return window * self.p0_ * self.w0_ * math.cos(self.w0_ * t), -1.0
+
     def f0(self, t, u, v, result):
         la.copy(v, result)                                   # LinearGLL.hpp:141-144
 
@@ -158,7 +196,9 @@ class LinearGLLOpt:
             self.window_ = 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * t / self.alpha_))
         else:
             self.window_ = 1.0
-        self.g_ = self.window_ * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
+        # g(t) of LinearGLL.hpp:153-162; with a medium g = s1 / c differs from cell to cell and only s1 exists
+        self.g_ = self.window_ * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t) if self.medium is None else None
+        s1, s2 = self._boundary_scalars(self.window_, t)
         if self._split:
             # same operations as below, reordered so that the cells that read no ghost
             # value run while the halo of u is in flight (update_fwd_begin/_end,
@@ -166,8 +206,7 @@ class LinearGLLOpt:
             from .distributed import overlapped_apply
             la.fill(self.b, 0.0)
             overlapped_apply(self.stiff_op, self.updater, u, self.b)
-            la.boundary_apply(self.idx1, self.mG1, self.c0_ ** 2 * self.g_,
-                              self.idx2, self.mG2, -self.c0_, v, self.b)
+            la.boundary_apply(self.idx1, self.mG1, s1, self.idx2, self.mG2, s2, v, self.b)
             la.copy(u, self.u_n)
             la.copy(v, self.v_n)
             la.pointwise_div(self.b, self.m, result)
@@ -179,8 +218,7 @@ class LinearGLLOpt:
             la.copy(v, self.v_n)
             la.fill(self.b, 0.0)
             self.stiff_op(self.u_n, self.b)
-        la.boundary_apply(self.idx1, self.mG1, self.c0_ ** 2 * self.g_,
-                          self.idx2, self.mG2, -self.c0_, self.v_n, self.b)
+        la.boundary_apply(self.idx1, self.mG1, s1, self.idx2, self.mG2, s2, self.v_n, self.b)
         if self.updater is not None:
             self.updater.scatter_rev(self.b)
         la.pointwise_div(self.b, self.m, result)
@@ -253,6 +291,8 @@ def _rk4_fused(self, startTime: float, finalTime: float, timeStep: float, max_st
             window = 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * tn / self.alpha_))
         else:
             window = 1.0
+        if self.medium is not None:
+            return self._boundary_scalars(window, tn)[0]
         return self.c0_ ** 2 * window * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * tn)
 
     def rhs(x_u):
@@ -272,7 +312,7 @@ def _rk4_fused(self, startTime: float, finalTime: float, timeStep: float, max_st
                                    self.mG2.cpu().numpy())
     # fold_boundary = False keeps the boundary term a launch of its own after each stage kernel (for comparison)
     fold = getattr(self, "fold_boundary", True)
-    bc, s2 = self._bc, -self.c0_
+    bc, s2 = self._bc, -self.c0_ if self.medium is None else -1.0
     la.fill(b, 0.0)
     bc.apply(s1(t), s2, v0, b)           # boundary term of the first right-hand side; the stage kernels leave the others
     while t < tf:

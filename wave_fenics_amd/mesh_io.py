@@ -111,9 +111,10 @@ def locate_facets(mesh, tags: MeshTags, value: int):
     return list(zip(c.tolist(), a.tolist(), s_.tolist()))
 
 
-def facet_lumped_mass(V: FunctionSpace, facets):
+def facet_lumped_mass(V: FunctionSpace, facets, cell_weight=None):
     """Collocated facet masses m[i] = sum_facets w_q |dx/ds x dx/dt| (diagonal GLL form of
     inner(g, v) * ds(tag), demo/cpu_planar3d/forms.ufl:19-24) for a list of (cell, axis, side).
+    cell_weight [ncells]: every facet's contribution times the value of its cell (wf_fs_facet_mass_weighted).
     Returns (dof indices int32 ascending, masses)."""
     mesh, p = V.mesh, V.degree
     x = np.ascontiguousarray(mesh.x, dtype=np.float64)
@@ -124,15 +125,24 @@ def facet_lumped_mass(V: FunctionSpace, facets):
     cap = max(1, f.shape[0] * (p + 1) ** 2)
     idx, m = np.zeros(cap, dtype=np.int32), np.zeros(cap)
     nout = c_int64(0)
-    check(lib().wf_fs_facet_mass(p, x.shape[0], _dp(x), cells.shape[0], _ip(cells), _ip(dm), f.shape[0], _ip(fc), _ip(fa),
-                                 _ip(fs), ctypes.byref(nout), _ip(idx), _dp(m)))
+    if cell_weight is None:
+        check(lib().wf_fs_facet_mass(p, x.shape[0], _dp(x), cells.shape[0], _ip(cells), _ip(dm), f.shape[0], _ip(fc), _ip(fa),
+                                     _ip(fs), ctypes.byref(nout), _ip(idx), _dp(m)))
+    else:
+        cw = np.ascontiguousarray(cell_weight, dtype=np.float64).reshape(-1)
+        if cw.size != cells.shape[0]:
+            raise ValueError(f"cell_weight has {cw.size} entries, the mesh has {cells.shape[0]} cells")
+        check(lib().wf_fs_facet_mass_weighted(p, x.shape[0], _dp(x), cells.shape[0], _ip(cells), _ip(dm), f.shape[0], _ip(fc),
+                                              _ip(fa), _ip(fs), _dp(cw), ctypes.byref(nout), _ip(idx), _dp(m)))
     return idx[: nout.value].copy(), m[: nout.value].copy()
 
 
-def boundary_sets(V: FunctionSpace, tags: MeshTags, values=(1, 2)):
+def boundary_sets(V: FunctionSpace, tags: MeshTags, values=(1, 2), cell_weight=None):
     """The `boundary=` argument of LinearGLLOpt from the file's facet tags
-    (tag 1 = Gamma_1 source, tag 2 = Gamma_2 absorbing; common/LinearGLL.hpp:113-115)."""
-    return tuple(facet_lumped_mass(V, locate_facets(V.mesh, tags, v)) for v in values)
+    (tag 1 = Gamma_1 source, tag 2 = Gamma_2 absorbing; common/LinearGLL.hpp:113-115).  Together with
+    LinearGLLOpt(..., medium=m) pass cell_weight=m.admittance: the model takes a caller's sets as they are, and in a
+    heterogeneous medium both facet masses carry 1 / (rho c) of the facet's cell."""
+    return tuple(facet_lumped_mass(V, locate_facets(V.mesh, tags, v), cell_weight) for v in values)
 
 
 def cfl_time_step(mesh, degree: int, c0: float, freq: float, CFL: float = 0.5):

@@ -52,6 +52,16 @@ def _dp(a):
     return None if a is None else a.ctypes.data_as(POINTER(c_double))
 
 
+def _cell_coeff(cell_coeff, ncells: int):
+    """A cell coefficient argument as the contiguous float64 array [ncells] the C ABI takes, or None."""
+    if cell_coeff is None:
+        return None
+    a = np.ascontiguousarray(cell_coeff, dtype=np.float64).reshape(-1)
+    if a.size != ncells:
+        raise _lib.WavehipError(f"cell_coeff has {a.size} entries, the mesh has {ncells} cells")
+    return a
+
+
 def _ip(a):
     return None if a is None else a.ctypes.data_as(POINTER(c_int32))
 
@@ -198,8 +208,10 @@ class _Operator:
     def __init__(self):
         self._h = c_void_p()
 
-    def _create(self, desc: OpDesc, keep=(), tuning=None):
-        self._keep = keep
+    def _create(self, desc: OpDesc, keep=(), tuning=None, cell_coeff=None):
+        a = _cell_coeff(cell_coeff, desc.ncells)
+        self._keep = (keep, a)
+        desc.h_cell_coeff = _dp(a)
         t = make_tuning(tuning)
         if t is not None:
             desc.tuning = ctypes.pointer(t)
@@ -207,13 +219,19 @@ class _Operator:
         self._keep = ()
         self._info()
 
-    def _create_box(self, kind: int, p: int, mesh, c0: float, flags: int, tuning=None):
+    def _create_box(self, kind: int, p: int, mesh, c0: float, flags: int, tuning=None, cell_coeff=None):
         nx, ny, nz = mesh.n
         x = np.ascontiguousarray(mesh.x, dtype=np.float64)
+        a = _cell_coeff(cell_coeff, nx * ny * nz)
         t = make_tuning(tuning)
-        check(lib().wf_op_create_box_tuned(kind, p, nx, ny, nz, _dp(x), float(c0), flags,
+        check(lib().wf_op_create_box_coeff(kind, p, nx, ny, nz, _dp(x), float(c0), _dp(a), flags,
                                            ctypes.byref(t) if t is not None else None, ctypes.byref(self._h)))
         self._info()
+
+    @property
+    def cell_coeff(self) -> bool:
+        """Whether the operator was created with a cell coefficient array (wf_op_info_t.cell_coeff)."""
+        return bool(self.info.cell_coeff)
 
     @property
     def kernel(self) -> str:
@@ -371,10 +389,15 @@ class StiffnessOperator(_Operator):
     (arbitrary dofmap, atomic scatter) kernel.  There tuning={"geometry": "per_cell"}
     asks for one G_c per cell (degrees 1 to 4, every cell affine, G=None): the
     marching kernel on lattice columns then streams 48 B per cell instead of 48 B
-    per point; op.geometry, op.metric report what was built."""
+    per point; op.geometry, op.metric report what was built.
+
+    cell_coeff (every operator class of this module): one value a_c per cell in the mesh's cell order, or
+    None.  The operator is then sum_c a_c P_c^T A_c P_c with A_c the cell matrix without it (here with -c0^2
+    and the clamp applied first); the values are folded into the stored geometry at creation, so the apply
+    runs the same kernel at the same cost.  None is the operator as it always was."""
 
     def __init__(self, V: FunctionSpace, bdegree: int, params: dict | None = None, G=None, perm=None,
-                 structured: bool | None = None, flags: int = 0, tuning=None):
+                 structured: bool | None = None, flags: int = 0, tuning=None, cell_coeff=None):
         super().__init__()
         c0 = 1500.0 if not params else float(params.get("c0", 1500.0))
         self.c0 = c0
@@ -383,7 +406,7 @@ class StiffnessOperator(_Operator):
         if structured:
             if bdegree != V.degree:
                 raise _lib.WavehipError("structured operator: bdegree must equal the space's degree")
-            self._create_box(_lib.WF_OP_STIFFNESS, bdegree, V.mesh, c0, flags, tuning)
+            self._create_box(_lib.WF_OP_STIFFNESS, bdegree, V.mesh, c0, flags, tuning, cell_coeff)
             return
         d, keep = _base_desc(V, _lib.WF_OP_STIFFNESS, bdegree, perm)
         d.c0 = c0
@@ -396,7 +419,7 @@ class StiffnessOperator(_Operator):
             d.h_G = _dp(Gc)
         else:
             _attach_mesh(d, V, keep)
-        self._create(d, keep, tuning)
+        self._create(d, keep, tuning, cell_coeff)
 
 
 class MassOperatorLumped(_Operator):
@@ -404,12 +427,13 @@ class MassOperatorLumped(_Operator):
     mass y += M x.  detJ = |det J| w (fabs), as precompute_geometric_data."""
 
     def __init__(self, V: FunctionSpace, bdegree: int, detJ=None, perm=None, structured: bool | None = None,
-                 flags: int = 0, tuning=None):
+                 flags: int = 0, tuning=None, cell_coeff=None):
         super().__init__()
         if structured is None:
             structured = bool(getattr(V, "structured", False)) and detJ is None and perm is None
         if structured:
-            self._create_box(_lib.WF_OP_MASS_LUMPED, bdegree, V.mesh, 0.0, flags, tuning if flags & _lib.WF_FLAG_ORDERED else None)
+            self._create_box(_lib.WF_OP_MASS_LUMPED, bdegree, V.mesh, 0.0, flags, tuning if flags & _lib.WF_FLAG_ORDERED else None,
+                             cell_coeff)
             return
         d, keep = _base_desc(V, _lib.WF_OP_MASS_LUMPED, bdegree, perm)
         d.flags = flags
@@ -419,7 +443,7 @@ class MassOperatorLumped(_Operator):
             d.h_detJ = _dp(Dc)
         else:
             _attach_mesh(d, V, keep)
-        self._create(d, keep, tuning)
+        self._create(d, keep, tuning, cell_coeff)
 
 
 class SpectralMassOperator(MassOperatorLumped):
@@ -428,10 +452,10 @@ class SpectralMassOperator(MassOperatorLumped):
     precompute.hpp:102-116).  Degrees outside 2..7 are rejected like the
     reference's qdegree map (spectral_mass.hpp:42-48)."""
 
-    def __init__(self, V: FunctionSpace, bdegree: int, structured: bool | None = None):
+    def __init__(self, V: FunctionSpace, bdegree: int, structured: bool | None = None, cell_coeff=None):
         if bdegree < 2 or bdegree > 7:
             raise _lib.WavehipError("SpectralMassOperator: degree must be 2..7")
-        super().__init__(V, bdegree, structured=structured, flags=_lib.WF_FLAG_NO_FABS)
+        super().__init__(V, bdegree, structured=structured, flags=_lib.WF_FLAG_NO_FABS, cell_coeff=cell_coeff)
 
 
 class MassOperator(_Operator):
@@ -447,7 +471,7 @@ class MassOperator(_Operator):
 
     def __init__(self, V: FunctionSpace, degree: int, phi1: np.ndarray | None = None, detJ: np.ndarray | None = None,
                  perm=None, variant: str = "gll_warped", quad: str = "gll", qdegree: int | None = None, tuning=None,
-                 flags: int = 0):
+                 flags: int = 0, cell_coeff=None):
         super().__init__()
         d, keep = _base_desc(V, _lib.WF_OP_MASS_DENSE, degree, perm)
         d.flags = flags
@@ -477,7 +501,7 @@ class MassOperator(_Operator):
             qp, qw = np.ascontiguousarray(self.points1), np.ascontiguousarray(self.weights1)
             keep += [qp, qw]
             d.h_qpts1, d.h_qwts1 = _dp(qp), _dp(qw)
-        self._create(d, keep, tuning)
+        self._create(d, keep, tuning, cell_coeff)
 
 
 # ---------------------------------------------------------------------------

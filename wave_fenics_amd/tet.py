@@ -21,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import DenseDesc, DenseMassDesc, check, lib
 from .box import create_box
-from .operators import _Operator, _dp, _ip
+from .operators import _Operator, _cell_coeff, _dp, _ip
 
 
 def tet_nodes(p: int) -> np.ndarray:
@@ -115,10 +115,11 @@ def create_kuhn_box(n, p: int, perturb: float = 0.0, seed: int = 42, lo=(0.0, 0.
 
 class TetStiffnessOperator(_Operator):
     """y += K x on affine tetrahedra through wf_op_create_dense_simplex:
-    the dense skernel (common/operators.hpp:113-133) on v_mfma_f64_16x16x4_f64."""
+    the dense skernel (common/operators.hpp:113-133) on v_mfma_f64_16x16x4_f64.  cell_coeff: one value per cell or
+    None; the kernel then runs its coefficient variant, which scales by -c0^2 a_c after the clamp."""
 
     def __init__(self, V: TetSpace, degree: int, params: dict | None = None, qdegree: int | None = None,
-                 flags: int = 0):
+                 flags: int = 0, cell_coeff=None):
         super().__init__()
         c0 = 1500.0 if not params else float(params.get("c0", 1500.0))
         q = 2 * degree - 2 if qdegree is None else qdegree
@@ -136,6 +137,8 @@ class TetStiffnessOperator(_Operator):
         d.h_dofmap, d.h_dphi, d.h_weights = _ip(dm), _dp(dphi), _dp(W)
         d.nverts, d.h_xverts, d.h_geom_dofmap = x.shape[0], _dp(x), _ip(gd)
         d.c0, d.flags = c0, flags
+        a = _cell_coeff(cell_coeff, V.ncells)
+        d.h_cell_coeff = _dp(a)
         self._h = c_void_p()
         check(lib().wf_op_create_dense_simplex(ctypes.byref(d), ctypes.byref(self._h)))
         self._info()
@@ -146,9 +149,10 @@ class TetMassOperator(_Operator):
     (common/cuda/mass.hpp:18-107) with the tetrahedral table of basis values, collapsed to one matrix
     A = Phi^T diag(w) Phi and one scale |det J| per cell, on v_mfma_f64_16x16x4_f64.  The rule is the collapsed
     Gauss-Jacobi rule of degree `qdegree` (default 2 * degree: exact for the mass matrix of affine cells); the table
-    is taken as tabulated, without the -1/0/1 clamp.  `flags`: WF_FLAG_NO_FABS keeps the sign of det J."""
+    is taken as tabulated, without the -1/0/1 clamp.  `flags`: WF_FLAG_NO_FABS keeps the sign of det J.  cell_coeff: one
+    value per cell or None, folded into the cell's scale."""
 
-    def __init__(self, V: TetSpace, degree: int, qdegree: int | None = None, flags: int = 0):
+    def __init__(self, V: TetSpace, degree: int, qdegree: int | None = None, flags: int = 0, cell_coeff=None):
         super().__init__()
         q = 2 * degree if qdegree is None else qdegree
         X, W = tet_quadrature((q + 2) // 2)
@@ -164,6 +168,8 @@ class TetMassOperator(_Operator):
         d.h_dofmap, d.h_phi, d.h_weights = _ip(dm), _dp(phi), _dp(W)
         d.nverts, d.h_xverts, d.h_geom_dofmap = x.shape[0], _dp(x), _ip(gd)
         d.flags = flags
+        a = _cell_coeff(cell_coeff, V.ncells)
+        d.h_cell_coeff = _dp(a)
         self._h = c_void_p()
         check(lib().wf_op_create_dense_simplex_mass(ctypes.byref(d), ctypes.byref(self._h)))
         self._info()
