@@ -2,7 +2,7 @@
 tests/test_gpu_hex_geometry.py).  No GPU in here, and neither oracle/ nor the library computes any reference value.
 
 The set-up code writes G = J^-1 J^-T |det J| w and det J w per cell and point through hex_point_geometry
-(csrc/kernels.hip; common/precomputation.hpp:49-107) and, for affine cells, through the host rule cell_geometry
+(csrc/hex_geometry.hip; common/precomputation.hpp:49-107) and, for affine cells, through the host rule cell_geometry
 (csrc/hex_cell_geometry.cpp).  point_geometry_ld restates the per-point formula in numpy long double, operation by
 operation in the order the kernel evaluates it:
 

@@ -1,4 +1,4 @@
-"""The persistent loops of the hexahedral batch kernels (csrc/kernels.hip) at several batches per workgroup.
+"""The persistent loops of the hexahedral batch kernels (csrc/stiffness_batch.hip, csrc/mass_batch.hip) at several batches per workgroup.
 
 A mesh that does not tile into lattice columns runs k_stiffness_generic_up2<P> (P1..P4), k_stiffness_generic_up<P>
 (P5..P7) and, for the element-wise lumped mass, k_mass_lumped_u.  The stiffness launchers size their grid as

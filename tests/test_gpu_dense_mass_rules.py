@@ -1,5 +1,5 @@
 """The dense mass Phi^T diag(det J w) Phi (common/cuda/mass.hpp:18-107) with RECTANGULAR
-1-D tables, nq1 != P+1, on the MI355X: the any-rule kernel k_mass_dense (kernels.hip) and
+1-D tables, nq1 != P+1, on the MI355X: the any-rule kernel k_mass_dense (mass_batch.hip) and
 the host code around it (batch size, unique-dof tile, LDS size, device det J * w).
 
 Every case runs both constructors -- the reference's argument list (rule, 1-D table and
@@ -59,7 +59,7 @@ def npts(quad, qd):
 
 
 def cells_per_batch(mx):
-    """Cells per workgroup of k_mass_dense; mirrors mass_dense_cells_per_batch (kernels.hip)."""
+    """Cells per workgroup of k_mass_dense; mirrors mass_dense_cells_per_batch (mass_batch.hip)."""
     return max(1, min(1400 // mx ** 3, 32))
 
 

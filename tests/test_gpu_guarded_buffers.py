@@ -43,7 +43,7 @@ BY + 1, 5) cells at lz = 2.
                                                                  element-wise lumped mass
   tet                    4   -                                   72 Kuhn tetrahedra, P1-P4: batches of 64, 64 + 8
 
-  batch constants (csrc/kernels.hip): B = CB = 256 // (P+1)^2 cells for k_stiffness_generic_up2 (P1-P4) and _up (P5-P7)
+  batch constants (csrc/cell_batch.h, csrc/mass_batch.hip): B = CB = 256 // (P+1)^2 cells for k_stiffness_generic_up2 (P1-P4) and _up (P5-P7)
   ("batch"), k_stiffness_generic ("elementwise"), k_mass_lumped_u and k_mass_dense_col ("batch"); B = CBd =
   min(1400 // (P+1)^3, 32) for k_mass_dense without unique-dof lists (dense mass, "elementwise"); k_mass_lumped (lumped
   mass, "elementwise") takes 256 dofmap entries per workgroup, whatever the cells.
@@ -95,7 +95,7 @@ def cells_per_batch(p):
 
 
 def dense_cells_per_batch(p):
-    """CBd of k_mass_dense without unique-dof lists (mass_dense_cells_per_batch, csrc/kernels.hip), square table"""
+    """CBd of k_mass_dense without unique-dof lists (mass_dense_cells_per_batch, csrc/mass_batch.hip), square table"""
     return max(1, min(1400 // (p + 1) ** 3, 32))
 
 

@@ -1,5 +1,5 @@
 """The hexahedral geometry set-up on the device against a long-double reference (tests/hex_geometry_helpers.py):
-k_geometry_hex, k_geometry_hex_slots and k_geometry_box of csrc/kernels.hip, every flag combination, both clamp windows,
+k_geometry_hex, k_geometry_hex_slots and k_geometry_box of csrc/hex_geometry.hip, every flag combination, both clamp windows,
 the per-cell upload of the box operator and its fall-back to per-point geometry.
 
 a. k_geometry_hex entry by entry (precompute_geometric_data): every G entry and det J w within the helper's bound of

@@ -69,6 +69,8 @@ inline int launch_status(const char* what)
   do {                                                          \
     if (int _rc = ::wf::launch_status("kernel")) return _rc;    \
   } while (0)
+// workgroups of `block` threads for n work items, one each
+inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 // Diagnostic ablation mask (profiling only; WF_ABLATE unset or 0 in production):
 // 1 = no scatter, 2 = geometry served from L2, 4 = no x gather, 8 = no contractions.
@@ -104,18 +106,16 @@ struct DMat {
 void gll_points_weights(int n, double* pts, double* wts);
 void gll_derivative_matrix(int P, double* D);  // clamped, D[q*n + a]
 
-// cells per workgroup batch of the column-thread kernels: floor(256 / n^2)
-inline int cells_per_batch(int P) { return 256 / ((P + 1) * (P + 1)); }
+// cells per workgroup batch of the column-thread kernels: floor(256 / n^2).  For host code with a run-time P; the
+// kernels and their launchers take it from CellBatch<P> (cell_batch.h), which asserts that the two agree.
+constexpr int cells_per_batch(int P) { return 256 / ((P + 1) * (P + 1)); }
 
-// ---- kernel launchers (kernels.hip) ----
+// ---- geometry set-up (hex_geometry.hip) ----
 // d_cell_coeff (every geometry launcher; null: none): the cell coefficient a_c per cell in the order of the cells the
 // kernel is given; every entry written, det J w included, is then the entry without it times a_c
 int launch_geometry_hex(int P, int ncells, const double* d_xverts, const int32_t* d_geom_dofmap,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp,
                         double* d_G9, double* d_G6blk, double* d_detJ, const double* d_cell_coeff, hipStream_t s);
-// lattice plans with a fill (cells per cell slot) below this keep the batch kernel: the marching kernels
-// read geometry for every slot of a column, empty or not
-constexpr double kMinPlanFill = 0.55;
 int launch_geometry_box(int P, int nx, int ny, int nz, int bx, int by, int bz, const double* d_xverts,
                         const double* d_pts, const double* d_wts, int use_fabs, int clamp,
                         double* d_G6blk, double* d_detJ_lattice, const double* d_cell_coeff, hipStream_t s);
@@ -123,6 +123,8 @@ int launch_geometry_hex_slots(int P, int CB, int ncells, const double* d_xverts,
                               const int32_t* d_slot_of, const uint8_t* d_orient, const double* d_pts, const double* d_wts,
                               int use_fabs, int clamp, double* d_G6blk, const double* d_cell_coeff, hipStream_t s);
 int launch_pack_G6(int P, int CB, int ncells, const double* d_G9, double* d_G6blk, hipStream_t s);
+
+// ---- cell-batch stiffness kernels (stiffness_batch.hip) ----
 int launch_stiffness_generic(int P, int ncells, const int32_t* d_dofmap, const double* d_G6blk,
                              const double* d_D, const DMat& dm, double coeff, const double* d_x,
                              double* d_y, hipStream_t s);
@@ -132,6 +134,37 @@ int launch_stiffness_generic_u(int P, int ncells, const int32_t* d_uoff, const i
 int launch_stiffness_box(int P, int nx, int ny, int nz, int bx, int by, int bz, const double* d_G6blk,
                          const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_y,
                          hipStream_t s);
+
+// ---- cell-batch mass kernels (mass_batch.hip) ----
+int launch_mass_lumped(int64_t nentries, const int32_t* d_dofmap, const double* d_detJ, const double* d_x,
+                       double* d_y, hipStream_t s);
+// y[d] += m[d] x[d] where m[d] != 0: the pre-assembled diagonal on vectors that hold dofs no cell names (m = 0 there)
+int launch_diagonal_named(int64_t n, const double* d_m, const double* d_x, double* d_y, hipStream_t s);
+int launch_mass_lumped_u(int ncells, int nd, int CB, const int32_t* d_uoff, const int32_t* d_uniq,
+                         const uint16_t* d_loc, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
+int mass_dense_cells_per_batch(int mx);
+int launch_mass_dense_col(int P, int ncells, const int32_t* d_uoff, const int32_t* d_uniq, const uint16_t* d_loc,
+                          const double* d_phi1, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
+int launch_mass_dense(int P, int nq1, int ncells, const int32_t* d_dofmap, const int32_t* d_uoff,
+                      const int32_t* d_uniq, const uint16_t* d_loc, int CBu, const double* d_phi1,
+                      const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
+// pass 1 of the order-fixed accumulation (ordered.hip): the kernel above it with v[slot[c][l]] = element-local value
+int launch_mass_dense_ordered(int P, int nq1, int ncells, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_phi1,
+                              const double* d_detJ, const double* d_x, double* d_v, hipStream_t s);
+int launch_mass_lumped_ordered(int64_t nentries, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_detJ,
+                               const double* d_x, double* d_v, hipStream_t s);
+
+// ---- order-fixed accumulation (ordered.hip): the plan and the stiffness pass 1; pass 2 is wf_segment_sum_add ----
+// ordered_slots: the stable counting sort of a flattened dofmap (wf_ordered_slots)
+int ordered_slots(int64_t nentries, int32_t ndofs, const int32_t* dofmap, int32_t* row_off, int32_t* slot);
+// pass 1, stiffness: k_stiffness_generic (stiffness_elementwise.h) with v[slot[c][l]] = element-local value
+int launch_stiffness_ordered(int P, int ncells, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_G6blk,
+                             const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_v, hipStream_t s);
+
+// ---- marching kernels (stiffness_march*.hip, mass_march.hip) ----
+// lattice plans with a fill (cells per cell slot) below this keep the batch kernel: the marching kernels
+// read geometry for every slot of a column, empty or not
+constexpr double kMinPlanFill = 0.55;
 bool march_variant(int P, int variant, int* bx, int* by);
 // Geometry form of the box marching kernel (stiffness_march.hip): G at every point, one full G_c per affine cell, or
 // one diagonal G_c per rectilinear affine cell (the separable operator: one 1-D operator A = D^T diag(w) D per axis).
@@ -262,26 +295,5 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
 void dense_mass_free(DenseMassData* d);
 size_t dense_mass_bytes(const DenseMassData* d);
 int launch_mass_dense_simplex(const DenseMassData* d, const double* d_x, double* d_y, hipStream_t s);
-int launch_mass_lumped(int64_t nentries, const int32_t* d_dofmap, const double* d_detJ, const double* d_x,
-                       double* d_y, hipStream_t s);
-// y[d] += m[d] x[d] where m[d] != 0: the pre-assembled diagonal on vectors that hold dofs no cell names (m = 0 there)
-int launch_diagonal_named(int64_t n, const double* d_m, const double* d_x, double* d_y, hipStream_t s);
-int launch_mass_lumped_u(int ncells, int nd, int CB, const int32_t* d_uoff, const int32_t* d_uniq,
-                         const uint16_t* d_loc, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
-int mass_dense_cells_per_batch(int mx);
-int launch_mass_dense_col(int P, int ncells, const int32_t* d_uoff, const int32_t* d_uniq, const uint16_t* d_loc,
-                          const double* d_phi1, const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
-int launch_mass_dense(int P, int nq1, int ncells, const int32_t* d_dofmap, const int32_t* d_uoff,
-                      const int32_t* d_uniq, const uint16_t* d_loc, int CBu, const double* d_phi1,
-                      const double* d_detJ, const double* d_x, double* d_y, hipStream_t s);
-// order-fixed accumulation (ordered.hip): pass 1 of the cell-batch kernels, v[slot[c][l]] = element-local value; pass 2
-// is wf_segment_sum_add.  ordered_slots: the stable counting sort of a flattened dofmap (wf_ordered_slots).
-int ordered_slots(int64_t nentries, int32_t ndofs, const int32_t* dofmap, int32_t* row_off, int32_t* slot);
-int launch_stiffness_ordered(int P, int ncells, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_G6blk,
-                             const double* d_D, const DMat& dm, double coeff, const double* d_x, double* d_v, hipStream_t s);
-int launch_mass_dense_ordered(int P, int nq1, int ncells, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_phi1,
-                              const double* d_detJ, const double* d_x, double* d_v, hipStream_t s);
-int launch_mass_lumped_ordered(int64_t nentries, const int32_t* d_dofmap, const int32_t* d_slot, const double* d_detJ,
-                               const double* d_x, double* d_v, hipStream_t s);
 
 }  // namespace wf

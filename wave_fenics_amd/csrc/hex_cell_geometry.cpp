@@ -25,7 +25,7 @@ int64_t cell_geometry(int P, size_t ncells, const double* xv, VertexOf&& vert, i
   const int n = P + 1;
   std::vector<double> pts(n), wts(n);
   gll_points_weights(n, pts.data(), wts.data());
-  auto clamp101 = [](double v) {   // as kernels.hip
+  auto clamp101 = [](double v) {   // as hex_geometry.hip
     if (std::fabs(v + 1.0) <= 1e-8 + 1e-5) v = -1.0;
     if (std::fabs(v) <= 1e-8) v = 0.0;
     if (std::fabs(v - 1.0) <= 1e-8 + 1e-5) v = 1.0;

@@ -14,7 +14,7 @@ enum class OpKernel : int {
   box_march,             // box, one thread per column, P <= 4 (stiffness_march.hip); geometry form: wf_op.geom
   box_ksplit,            // box, the k-split kernel (stiffness_march_ks.hip)
   box_owner,             // box, owner-computes separable form (stiffness_march_owner.hip)
-  box_block,             // box, single-pass block kernel (kernels.hip)
+  box_block,             // box, single-pass block kernel (stiffness_batch.hip)
   idx_march,             // lattice columns found in a caller's dofmap (stiffness_march_idx.hip); geometry form: wf_op.geom
   generic_unique,        // batch stiffness with batch-unique dof lists
   generic_elementwise,   // batch stiffness, element-wise atomics
