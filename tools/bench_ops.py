@@ -186,61 +186,77 @@ def bench_medium(dev):
 
 
 def bench_tet_against(dev, other_path):
-    """The default (no coefficient) P4 tetrahedral stiffness apply of this library against ANOTHER build of libwavehip --
-    the parent commit's, say -- with both libraries loaded into this one process, the same operator created through each
-    and the applies alternating (MEDIUM_ROUNDS rounds, default 7).  `python tools/bench_ops.py tet-ab` with the other
-    library's path in WAVEHIP_LIB_B.  Only wf_op_create_dense_simplex, wf_op_apply and wf_op_destroy of the other library
-    are called, with this tree's descriptor: an older library reads the leading fields it knows."""
+    """The default (no coefficient) P4 tetrahedral stiffness apply and mass apply of this library against ANOTHER build of
+    libwavehip -- the parent commit's, say -- with both libraries loaded into this one process, the same operator created
+    through each and the applies alternating (MEDIUM_ROUNDS rounds, default 7), first for the stiffness, then for the
+    mass.  `python tools/bench_ops.py tet-ab` with the other library's path in WAVEHIP_LIB_B.  Only
+    wf_op_create_dense_simplex, wf_op_create_dense_simplex_mass, wf_op_apply and wf_op_destroy of the other library are
+    called, with this tree's descriptors: an older library reads the leading fields it knows."""
     import ctypes
     from wave_fenics_amd import _lib, tet
     from wave_fenics_amd.operators import _dp, _ip
-    this, other = w.lib(), ctypes.CDLL(other_path)
-    other.wf_op_create_dense_simplex.restype = ctypes.c_int
-    other.wf_op_create_dense_simplex.argtypes = [ctypes.POINTER(_lib.DenseDesc), ctypes.POINTER(ctypes.c_void_p)]
+    libs = {"this library": w.lib(), "other library": ctypes.CDLL(other_path)}
+    other = libs["other library"]
+    for create, desc in (("wf_op_create_dense_simplex", _lib.DenseDesc), ("wf_op_create_dense_simplex_mass", _lib.DenseMassDesc)):
+        getattr(other, create).restype = ctypes.c_int
+        getattr(other, create).argtypes = [ctypes.POINTER(desc), ctypes.POINTER(ctypes.c_void_p)]
     other.wf_op_apply.restype = ctypes.c_int
     other.wf_op_apply.argtypes = [ctypes.c_void_p] * 4
     other.wf_op_destroy.argtypes = [ctypes.c_void_p]
     p, n = 4, int(os.environ.get("TET_N", "54"))
     V = tet.create_kuhn_box(n, p)
-    X, W = tet.tet_quadrature(p)                  # the rule of tet.TetStiffnessOperator: degree 2p - 2, m = p
-    dphi = np.ascontiguousarray(tet.clamp101(tet.tabulate_tet(p, X)[1]))
-    W = np.ascontiguousarray(W)
     dm, xv, gd = (np.ascontiguousarray(V.dofmap, dtype=np.int32), np.ascontiguousarray(V.x, dtype=np.float64),
                   np.ascontiguousarray(V.geom_dofmap, dtype=np.int32))
-    d = _lib.DenseDesc()
-    d.nd, d.nq, d.ncells, d.ndofs = dphi.shape[2], dphi.shape[1], V.ncells, V.ndofs
-    d.h_dofmap, d.h_dphi, d.h_weights = _ip(dm), _dp(dphi), _dp(W)
-    d.nverts, d.h_xverts, d.h_geom_dofmap = xv.shape[0], _dp(xv), _ip(gd)
-    d.c0, d.flags = 1500.0, 0
-    libs = {"this library": this, "other library": other}
-    handles = {}
-    for name, L in libs.items():
-        handles[name] = ctypes.c_void_p()
-        rc = L.wf_op_create_dense_simplex(ctypes.byref(d), ctypes.byref(handles[name]))
-        if rc != 0:
-            raise RuntimeError(f"{name}: wf_op_create_dense_simplex returned {rc}")
     N = V.ndofs
     x = torch.rand(N, dtype=torch.float64, device=dev)
     y = torch.zeros(N, dtype=torch.float64, device=dev)
-    once = {}
-    for name, L in libs.items():
-        y.zero_()
-        L.wf_op_apply(handles[name], x.data_ptr(), y.data_ptr(), 0)
-        torch.cuda.synchronize()
-        once[name] = y.clone()
-    ms = {name: [] for name in libs}
-    for _ in range(int(os.environ.get("MEDIUM_ROUNDS", "7"))):
-        for name in ("other library", "this library"):
-            ms[name].append(timeit(lambda: libs[name].wf_op_apply(handles[name], x.data_ptr(), y.data_ptr(), 0)))
-    med = {k: float(np.median(v)) for k, v in ms.items()}
-    for name in libs:
-        print(json.dumps({"op": f"tet P{p} dense stiffness without a coefficient, Kuhn box {n}^3 cubes, {name}", "ms": round(med[name], 4),
-                          "ms_rounds": [round(v, 4) for v in ms[name]], "cells": V.ncells, "ndofs": N,
-                          "this_over_other": round(med["this library"] / med["other library"], 4),
-                          "max_abs_diff_of_one_apply": float((once["this library"] - once["other library"]).abs().max()),
-                          "max_abs_y": float(once["this library"].abs().max())}), flush=True)
-    for name, L in libs.items():
-        L.wf_op_destroy(handles[name])
+
+    def mesh_fields(d, nd, nq):
+        d.nd, d.nq, d.ncells, d.ndofs = nd, nq, V.ncells, V.ndofs
+        d.h_dofmap, d.nverts, d.h_xverts, d.h_geom_dofmap = _ip(dm), xv.shape[0], _dp(xv), _ip(gd)
+        d.flags = 0
+
+    def alternate(what, create, d):
+        handles = {}
+        for name, L in libs.items():
+            handles[name] = ctypes.c_void_p()
+            rc = getattr(L, create)(ctypes.byref(d), ctypes.byref(handles[name]))
+            if rc != 0:
+                raise RuntimeError(f"{name}: {create} returned {rc}")
+        once = {}
+        for name, L in libs.items():
+            y.zero_()
+            L.wf_op_apply(handles[name], x.data_ptr(), y.data_ptr(), 0)
+            torch.cuda.synchronize()
+            once[name] = y.clone()
+        ms = {name: [] for name in libs}
+        for _ in range(int(os.environ.get("MEDIUM_ROUNDS", "7"))):
+            for name in ("other library", "this library"):
+                ms[name].append(timeit(lambda: libs[name].wf_op_apply(handles[name], x.data_ptr(), y.data_ptr(), 0)))
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        for name in libs:
+            print(json.dumps({"op": f"tet P{p} dense {what} without a coefficient, Kuhn box {n}^3 cubes, {name}", "ms": round(med[name], 4),
+                              "ms_rounds": [round(v, 4) for v in ms[name]], "cells": V.ncells, "ndofs": N,
+                              "this_over_other": round(med["this library"] / med["other library"], 4),
+                              "max_abs_diff_of_one_apply": float((once["this library"] - once["other library"]).abs().max()),
+                              "max_abs_y": float(once["this library"].abs().max())}), flush=True)
+        for name, L in libs.items():
+            L.wf_op_destroy(handles[name])
+
+    X, W = tet.tet_quadrature(p)                  # the rule of tet.TetStiffnessOperator: degree 2p - 2, m = p
+    dphi = np.ascontiguousarray(tet.clamp101(tet.tabulate_tet(p, X)[1]))
+    W = np.ascontiguousarray(W)
+    d = _lib.DenseDesc()
+    mesh_fields(d, dphi.shape[2], dphi.shape[1])
+    d.h_dphi, d.h_weights, d.c0 = _dp(dphi), _dp(W), 1500.0
+    alternate("stiffness", "wf_op_create_dense_simplex", d)
+    X, W = tet.tet_quadrature(p + 1)              # the rule of tet.TetMassOperator: degree 2p, 125 points
+    phi = np.ascontiguousarray(tet.tabulate_tet(p, X)[0], dtype=np.float64)
+    W = np.ascontiguousarray(W)
+    d = _lib.DenseMassDesc()
+    mesh_fields(d, phi.shape[1], phi.shape[0])
+    d.h_phi, d.h_weights = _dp(phi), _dp(W)
+    alternate("mass", "wf_op_create_dense_simplex_mass", d)
 
 
 def bench_tsmm(dev):

@@ -267,33 +267,4 @@ inline int check_index_range(const int32_t* idx, size_t count, int64_t bound, co
   return WF_OK;
 }
 
-// dense simplex operators (stiffness_dense.hip, mass_dense_simplex.hip): 64-cell batches, 16 cells per wave.
-// LDS layout of an MFMA A-operand table shared by both kernels: row pitch and row order (stiffness_dense.hip).
-__host__ __device__ constexpr int dense_pitch(int KT) { return 4 * KT + 2; }
-__host__ __device__ constexpr int dense_row_perm(int j) { return (j >> 1) + 8 * (j & 1); }
-// per-batch unique-dof lists and packed local indices (dense_batch_plan, stiffness_dense.hip)
-struct DenseBatchPlan {
-  std::vector<uint32_t> locP;   // [nbatch][ceil(KT/2)][4][NCB]
-  std::vector<int32_t> uoff;    // [nbatch + 1]
-  std::vector<int32_t> uniq;    // unique dofs of all batches
-  int numax = 1;                // most unique dofs of a batch (at least 1)
-};
-int dense_batch_plan(int nd, int KT, int NCB, int ncells, const int32_t* dofmap, DenseBatchPlan* plan);
-struct DenseOpData;
-int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, const double* dphi,
-                const double* weights, const double* xverts, const int32_t* geom_dofmap, const double* cell_coeff,
-                DenseOpData** out);
-void dense_free(DenseOpData* d);
-size_t dense_bytes(const DenseOpData* d);
-int launch_stiffness_dense(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,
-                           hipStream_t s);
-// dense simplex mass (mass_dense_simplex.hip): y += s_c A x per cell, A = Phi^T diag(w) Phi, s_c = |det J_c|
-struct DenseMassData;
-int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const double* phi, const double* weights,
-                     const double* xverts, const int32_t* geom_dofmap, int use_fabs, const double* cell_coeff,
-                     DenseMassData** out);
-void dense_mass_free(DenseMassData* d);
-size_t dense_mass_bytes(const DenseMassData* d);
-int launch_mass_dense_simplex(const DenseMassData* d, const double* d_x, double* d_y, hipStream_t s);
-
 }  // namespace wf

@@ -6,11 +6,10 @@
 //   Y[nd][cells]   = A . U[nd][cells]                       (MFMA, f64 16x16x4, k = nd)
 //   y[dof]        += s_c Y[.][c],  s_c = |det J_c| (det J_c with WF_FLAG_NO_FABS, mass.hpp:35-39)
 //
-// The cost does not depend on nq.  The decomposition is that of k_stiffness_dense (stiffness_dense.hip): one wave owns
-// 16 cells (the N dimension), four waves a batch of 64 cells; x enters through the batch's unique-dof tile in LDS, the
-// results are summed per unique dof in LDS and leave with one global atomic per unique dof; workgroups are persistent
-// and stage A into LDS once.  DT KT MFMAs per batch (27 at P4, against 288 in the stiffness kernel): the kernel is
-// not bound by the matrix pipe.
+// The cost does not depend on nq.  The decomposition is that of k_stiffness_dense (stiffness_dense.hip), and what the
+// two kernels share -- batch shape, LDS layout of the matrix, prefetch pieces and the rules of the batch pipeline, the
+// device plan -- is dense_simplex.h.  DT KT MFMAs per batch (27 at P4, against 288 in the stiffness kernel): the kernel
+// is not bound by the matrix pipe.
 //
 // Measured (P4 Kuhn box of 54^3 cubes, 944 784 cells, 10.2 M dofs, 125-point rule; five rounds alternating with the
 // stiffness apply and with every variant below in one process): 0.135 ms against 0.493 ms for k_stiffness_dense,
@@ -29,7 +28,7 @@
 #include <cstring>
 #include <memory>
 
-#include "device_array.h"
+#include "dense_simplex.h"
 
 namespace wf {
 
@@ -48,10 +47,10 @@ constexpr int kMassGridBound = 256 * kMassWgsPerCU;
 // KT = ceil(nd/4) k-steps, DT = ceil(nd/16) output tiles; A lives in LDS as [16 DT][KP], KP = dense_pitch(KT), with
 // output row 16 dt + m stored at row 16 dt + dense_row_perm(m): the A operand of tile dt and k-step ks is
 // A[16 dt + lc][4 ks + lg], and with that pitch and row order the 32 lanes an LDS read serves at a time touch 32
-// distinct 8-byte banks (the reasoning above dense_pitch in stiffness_dense.hip: it is that kernel's first product).
+// distinct 8-byte banks (dense_simplex.h).
 // The B operand of k-step ks is dof 4 ks + lg of cell lc; accumulator register r of tile dt is dof 4 (4 dt + r) + lg of
 // the same cell, so the packed local indices loc serve the gather and the scatter.
-// NU: unique dofs of a batch per thread (numax <= NU * 64 NW).
+// NU: unique dofs of a batch per thread (DenseBatchShape).
 template <int KT, int DT, int NW, int NU>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWgsPerCU))) void k_mass_dense_simplex(
     int nd, int ncells, int nbatch, int numax,
@@ -62,7 +61,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
     const int32_t* __restrict__ uniq,   // unique dofs of all batches
     const double* __restrict__ x, double* __restrict__ y)
 {
-  constexpr int KP = dense_pitch(KT), NT = 64 * NW, NCB = 16 * NW, KT2 = (KT + 1) / 2;
+  using Shape = DenseBatchShape<KT, NW, NU>;
+  constexpr int KP = Shape::KP, NT = Shape::NT, NCB = Shape::NCB, KT2 = Shape::KT2;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* A = smem;              // [16 DT][KP]
   double* Xu = A + 16 * DT * KP; // [numax]  x at the unique dofs of the batch
@@ -78,34 +78,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
   // during the iteration) and is consumed at the end of iteration b + G: a whole iteration covers its latency, and no
   // load ever waits on an index that was fetched behind a global atomic.
   const int G = gridDim.x;
-  // per-batch scalars are fetched with VECTOR loads (stiffness_dense.hip: a pending scalar load turns every LDS wait
-  // into lgkmcnt(0))
-  auto vgpr_zero = [&]() {
-    int z = 0;
-    asm volatile("" : "+v"(z));
-    return z;
-  };
-  auto vload_i32 = [&](const int32_t* p) { return p[vgpr_zero()]; };
-  struct Range {
-    int32_t lo, hi;   // uoff[b], uoff[b + 1]  (b clamped to a valid batch; `live` says whether b < nbatch)
-    bool live;
-  };
-  auto load_range = [&](int b) {
-    const int bb = b < nbatch ? b : nbatch - 1;
-    return Range{vload_i32(uoff + bb), vload_i32(uoff + bb + 1), b < nbatch};
-  };
-  // All prefetch loads are unconditional, on clamped indices (a thread past the end of a batch's unique-dof list
-  // re-reads the last entry, a batch past the end re-reads the last batch); whether an entry is live is decided where
-  // it is used (nu_*: number of unique dofs of the batch).
-  auto load_uq = [&](int32_t (&uq)[NU], const Range& rg) {
-#pragma unroll
-    for (int m = 0; m < NU; ++m) uq[m] = uniq[min(rg.lo + t + NT * m, rg.hi - 1)];
-  };
-  auto count_of = [&](const Range& rg) { return rg.live ? rg.hi - rg.lo : 0; };
-  auto load_x = [&](double (&xr)[NU], const int32_t (&uq)[NU]) {
-#pragma unroll
-    for (int m = 0; m < NU; ++m) xr[m] = x[uq[m]];
-  };
+  // the prefetch pieces and their rules: dense_simplex.h
+  auto load_range = [&](int b) { return dense_load_range(uoff, nbatch, b); };
+  auto load_uq = [&](int32_t (&uq)[NU], const DenseRange& rg) { dense_load_uq<NT>(uq, uniq, rg, t); };
+  // count_of and the locP load of load_cell are the same lines as in k_stiffness_dense: as shared functions they changed
+  // the code (profiles/r23_summary.md)
+  auto count_of = [&](const DenseRange& rg) { return rg.live ? rg.hi - rg.lo : 0; };
+  auto load_x = [&](double (&xr)[NU], const int32_t (&uq)[NU]) { dense_load_x(xr, x, uq); };
   auto load_cell = [&](uint32_t (&loc)[KT2], double& s, int b) {
     const int bb = b < nbatch ? b : nbatch - 1;
 #pragma unroll
@@ -115,12 +94,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
   int32_t uq_cur[NU], uq_nxt[NU];   // unique dofs (this thread's share) of the batch being computed / of the next one
   double xr[NU];                    // x at uq_nxt
   uint32_t loc[KT2], locn[KT2];
-  auto loc_of = [&](int ks) -> uint32_t { return (loc[ks >> 1] >> (16 * (ks & 1))) & 0xffffu; };
+  auto loc_of = [&](int ks) { return dense_loc_of(loc, ks); };
   double sc, scn;
   int nu_cur, nu_nxt;   // live entries of uq_cur / uq_nxt
   // prologue: first batch straight into LDS, list and x values of the second
   {
-    const Range r0 = load_range(blockIdx.x), r1 = load_range(blockIdx.x + G);
+    const DenseRange r0 = load_range(blockIdx.x), r1 = load_range(blockIdx.x + G);
     load_uq(uq_cur, r0);
     nu_cur = count_of(r0);
     load_x(xr, uq_cur);
@@ -137,7 +116,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
     }
     load_x(xr, uq_nxt);
   }
-  Range rg2 = load_range(blockIdx.x + 2 * G);   // range of the batch whose unique-dof list is fetched next
+  DenseRange rg2 = load_range(blockIdx.x + 2 * G);   // range of the batch whose unique-dof list is fetched next
 
   for (int batch = blockIdx.x; batch < nbatch; batch += G) {
     __syncthreads();   // Xu holds this batch's x values, Yu is zero (first round: A is staged)
@@ -154,10 +133,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
     load_cell(locn, scn, batch + G);
     load_uq(uq_nn, rg2);
     const int nu_nn = count_of(rg2);
-    const Range rg3 = load_range(batch + 3 * G);
+    const DenseRange rg3 = load_range(batch + 3 * G);
 
     // ---- Y = A . U.  The A operands come from LDS two k-steps ahead in rotating registers: written as "read, then
-    // MFMA" every k-step pays the LDS latency (stiffness_dense.hip).
+    // MFMA" every k-step pays the LDS latency.  (The rotation of the first product of k_stiffness_dense, with DT row
+    // sets 16 KP apart: stiffness_dense.hip explains it.)
     double4_t Y[DT];
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) Y[dt] = double4_t{0.0, 0.0, 0.0, 0.0};
@@ -191,9 +171,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
         if (ks < KT && cell_live && 4 * ks + lg < nd) atomicAdd(&Yu[loc_of(ks < KT ? ks : 0)], sc * Y[dt][r]);
       }
     __syncthreads();   // Yu complete; every wave has taken its operands out of Xu
-    // Order matters: every consumer of a prefetched register (xr, uq_nn, locn, scn, the next ranges) and the issue of
-    // the next x gather come BEFORE the first global atomic.  On gfx9 loads and atomics share vmcnt and the compiler
-    // waits for vmcnt(0) once both kinds are pending (stiffness_dense.hip).
+    // End-of-batch stage, the same lines as in k_stiffness_dense (stiffness_dense.hip) but for the x gather, which is
+    // issued here for batch + 2G; written out in both, see rule 3 of dense_simplex.h: every consumer of a prefetched
+    // register (xr, uq_nn, locn, scn, the next ranges) and that gather come BEFORE the first global atomic.
     double yv[NU];
     int32_t uq_old[NU];
 #pragma unroll
@@ -229,25 +209,28 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kMassWg
 }
 
 struct DenseMassData {
-  int nd = 0, nq = 0, KT = 0, DT = 0, ncells = 0, nbatch = 0, numax = 0;
+  int nd = 0, nq = 0, KT = 0, DT = 0, ncells = 0;
   DevArray<double> d_A, d_s;
-  DevArray<uint32_t> d_locP;
-  DevArray<int32_t> d_uoff, d_uniq;
+  DenseBatchPlanDev plan;
 };
 
 void dense_mass_free(DenseMassData* d) { delete d; }
 
 size_t dense_mass_bytes(const DenseMassData* d)
 {
-  return d ? d->d_A.bytes() + d->d_s.bytes() + d->d_locP.bytes() + d->d_uoff.bytes() + d->d_uniq.bytes() : 0;
+  return d ? d->d_A.bytes() + d->d_s.bytes() + d->plan.bytes() : 0;
 }
 
 // Compiled tile pairs (KT, DT): Lagrange P1..P4 on the tetrahedron, nd = 4, 10, 20, 35.  Any nd with the same tile
 // counts runs on them; nq does not enter the kernel.
 #define WF_MASS_SIMPLEX_SHAPES(F) F(1, 1) F(3, 1) F(5, 2) F(9, 3)
 
+#define WF_MASS_HAS(K, D) || (KT == K && DT == D)
+static bool mass_simplex_shape_compiled(int KT, int DT) { return false WF_MASS_SIMPLEX_SHAPES(WF_MASS_HAS); }
+#undef WF_MASS_HAS
+
 // Host setup: A = Phi^T diag(w) Phi in the padded LDS layout, s_c per cell slot, the batch plan of the dense simplex
-// kernels.  Nothing touches the device before every check has passed.
+// kernels.  Nothing touches the device before every check on the caller's data has passed.
 int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const double* phi, const double* weights,
                      const double* xverts, const int32_t* geom_dofmap, int use_fabs, const double* cell_coeff,
                      DenseMassData** out)
@@ -258,17 +241,13 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
   d->KT = (nd + 3) / 4;
   d->DT = (nd + 15) / 16;
   d->ncells = ncells;
-  bool compiled = false;
-#define WF_MASS_HAS(K, D) compiled = compiled || (d->KT == K && d->DT == D);
-  WF_MASS_SIMPLEX_SHAPES(WF_MASS_HAS)
-#undef WF_MASS_HAS
-  if (!compiled) {
+  if (!mass_simplex_shape_compiled(d->KT, d->DT)) {
     set_error("wf_op_create_dense_simplex_mass: nd = " + std::to_string(nd) + " (ceil(nd/4) = " + std::to_string(d->KT)
               + ", ceil(nd/16) = " + std::to_string(d->DT) + ") is a shape not compiled (supported: the tile counts of "
               "tetrahedron P1..P4, nd = 1..4, 9..12, 17..20, 33..36)");
     return WF_ERR_UNSUPPORTED;
   }
-  constexpr int NCB = 64;
+  constexpr int NCB = kDenseBatchCells;
   const int KP = dense_pitch(d->KT);
   std::vector<double> A((size_t)16 * d->DT * KP, 0.0);
   for (int a = 0; a < nd; ++a)
@@ -278,15 +257,10 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
       A[(size_t)(16 * (a / 16) + dense_row_perm(a % 16)) * KP + b] = (double)s;
     }
   const int nbatch = (ncells + NCB - 1) / NCB;
-  d->nbatch = nbatch;
   std::vector<double> sc((size_t)nbatch * NCB, 0.0);
   for (int c = 0; c < ncells; ++c) {
-    const int32_t* v = geom_dofmap + (size_t)c * 4;
     long double J[9];
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) J[i * 3 + j] = (long double)xverts[(size_t)v[j + 1] * 3 + i] - xverts[(size_t)v[0] * 3 + i];
-    const double det = (double)(J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6])
-                                + J[2] * (J[3] * J[7] - J[4] * J[6]));
+    const double det = (double)tet_jacobian(xverts, geom_dofmap + (size_t)c * 4, J);
     if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) {   // det J = 0, NaN, infinite
       set_error("wf_op_create_dense_simplex_mass: cell " + std::to_string(c) + " is degenerate (det J is zero or not finite)");
       return WF_ERR_INVALID;
@@ -294,19 +268,14 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
     sc[c] = use_fabs ? std::fabs(det) : det;
     if (cell_coeff) sc[c] *= cell_coeff[c];   // the cell coefficient: folded into s_c, rounded once
   }
-  DenseBatchPlan plan;
-  if (int rc = dense_batch_plan(nd, d->KT, NCB, ncells, dofmap, &plan)) return rc;
-  d->numax = plan.numax;
-  if (d->numax > 9 * 4 * NCB) {   // cannot happen: 64 cells of nd <= 36 dofs
+  int rc;
+  if ((rc = d->plan.build(nd, d->KT, ncells, dofmap)) != WF_OK) return rc;
+  if (d->plan.numax > dense_nu(d->plan.numax) * kDenseThreads) {   // cannot happen: 64 cells of nd <= 36 dofs
     set_error("mass_dense_simplex: more unique dofs in a batch than the kernel holds");
     return WF_ERR_UNSUPPORTED;
   }
-  int rc;
   if ((rc = d->d_A.upload(A)) != WF_OK) return rc;
   if ((rc = d->d_s.upload(sc)) != WF_OK) return rc;
-  if ((rc = d->d_locP.upload(plan.locP)) != WF_OK) return rc;
-  if ((rc = d->d_uoff.upload(plan.uoff)) != WF_OK) return rc;
-  if ((rc = d->d_uniq.upload(plan.uniq)) != WF_OK) return rc;
   *out = d.release();
   return WF_OK;
 }
@@ -314,24 +283,24 @@ int dense_mass_setup(int nd, int nq, int ncells, const int32_t* dofmap, const do
 template <int KT, int DT, int NW, int NU>
 static int launch_mass_simplex_t(const DenseMassData* d, const double* d_x, double* d_y, hipStream_t s)
 {
+  const DenseBatchPlanDev& pl = d->plan;
   // at most (16 * 3 * 38 + 2 * 2304) * 8 = 51456 B: below the 64 KB a kernel may take without an attribute
-  const size_t lds = ((size_t)16 * DT * dense_pitch(KT) + 2 * d->numax) * sizeof(double);
-  const unsigned nb = (unsigned)std::min(d->nbatch, kMassGridBound);   // persistent: A is staged into LDS once per workgroup
-  hipLaunchKernelGGL((k_mass_dense_simplex<KT, DT, NW, NU>), dim3(nb), dim3(64 * NW), lds, s, d->nd, d->ncells, d->nbatch,
-                     d->numax, d->d_A.data(), d->d_s.data(), d->d_locP.data(), d->d_uoff.data(), d->d_uniq.data(), d_x, d_y);
+  const size_t lds = ((size_t)16 * DT * dense_pitch(KT) + 2 * pl.numax) * sizeof(double);
+  const unsigned nb = (unsigned)std::min(pl.nbatch, kMassGridBound);   // persistent: A is staged into LDS once per workgroup
+  hipLaunchKernelGGL((k_mass_dense_simplex<KT, DT, NW, NU>), dim3(nb), dim3(64 * NW), lds, s, d->nd, d->ncells, pl.nbatch,
+                     pl.numax, d->d_A.data(), d->d_s.data(), pl.locP.data(), pl.uoff.data(), pl.uniq.data(), d_x, d_y);
   return launch_status("mass_dense_simplex");
 }
 
-// NU = 5 covers the unique dofs of 64 well-numbered P4 cells; 9 is the worst case 64 * 36
-#define WF_MASS_CASE(K, D)                                                                     \
-  if (d->KT == K && d->DT == D)                                                                \
-    return d->numax <= 5 * 256 ? launch_mass_simplex_t<K, D, 4, 5>(d, d_x, d_y, s)             \
-                               : launch_mass_simplex_t<K, D, 4, 9>(d, d_x, d_y, s);
+#define WF_MASS_CASE(K, D)                                                                                                          \
+  if (d->KT == K && d->DT == D)                                                                                                     \
+    return dense_nu(d->plan.numax) == kDenseNuSmall ? launch_mass_simplex_t<K, D, kDenseWaves, kDenseNuSmall>(d, d_x, d_y, s)       \
+                                                    : launch_mass_simplex_t<K, D, kDenseWaves, kDenseNuLarge>(d, d_x, d_y, s);
 
 // (dense_mass_setup has refused every shape that is not in WF_MASS_SIMPLEX_SHAPES)
 int launch_mass_dense_simplex(const DenseMassData* d, const double* d_x, double* d_y, hipStream_t s)
 {
-  if (d->nbatch == 0) return WF_OK;
+  if (d->plan.nbatch == 0) return WF_OK;
   WF_MASS_SIMPLEX_SHAPES(WF_MASS_CASE)
   set_error("mass_dense_simplex: shape not compiled");
   return WF_ERR_UNSUPPORTED;

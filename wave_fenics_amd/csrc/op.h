@@ -8,6 +8,8 @@
 #include "box_run_plan.h"
 #include "device_array.h"
 
+namespace wf { struct DenseOpData; struct DenseMassData; }   // the dense simplex operators own their arrays (dense_simplex.h)
+
 // What wf_op_apply launches.  Creation sets it once; apply, the interior / interface splits and wf_op_info switch on it.
 enum class OpKernel : int {
   none = 0,

@@ -1,6 +1,7 @@
 // What is done with an operator handle once it exists: the launch switch, the interior / interface splits of the
 // marching operators, wf_op_info and wf_op_destroy -- and the two dense simplex creators, whose set-up lives with their
 // kernels (stiffness_dense.hip, mass_dense_simplex.hip).
+#include "dense_simplex.h"
 #include "march_column.h"
 #include "op.h"
 

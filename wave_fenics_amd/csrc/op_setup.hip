@@ -1,8 +1,9 @@
 // Set-up steps shared by the operator creation paths (op.h): tables, geometry staging, batch-unique lists, the
-// caller's tensor frame.
+// caller's tensor frame; the batch plan of the dense simplex operators.
 #include <cmath>
 #include <cstring>
 
+#include "dense_simplex.h"
 #include "op.h"
 
 namespace wf {
@@ -65,6 +66,45 @@ int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB)
   if ((rc = op->d_loc.upload(loc)) != WF_OK) return rc;
   op->unique_cb = CB;
   return WF_OK;
+}
+
+// The same for the 64-cell batches of the dense simplex kernels (dense_simplex.h), with the local indices packed two to
+// a word in the kernels' operand order: locP[b][ks / 2][lg][cell] holds the local index of dof 4 ks + lg in bits
+// 16 (ks & 1) .. 16 (ks & 1) + 15.
+int DenseBatchPlanDev::build(int nd, int KT, int ncells, const int32_t* dofmap)
+{
+  constexpr int NCB = kDenseBatchCells;
+  const int KT2 = (KT + 1) / 2;   // DenseBatchShape::KT2 of a run-time KT
+  nbatch = (ncells + NCB - 1) / NCB;
+  std::vector<uint32_t> h_locP((size_t)nbatch * KT2 * 4 * NCB, 0);
+  std::vector<int32_t> h_uoff(nbatch + 1, 0), h_uniq, tmp;
+  h_uniq.reserve((size_t)ncells * nd / 2);
+  numax = 1;
+  for (int b = 0; b < nbatch; ++b) {
+    const int c0 = b * NCB, nc = std::min(NCB, ncells - c0);
+    tmp.assign(dofmap + (size_t)c0 * nd, dofmap + (size_t)(c0 + nc) * nd);
+    std::sort(tmp.begin(), tmp.end());
+    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
+    const int nu = (int)tmp.size();
+    if (nu > 65535) {
+      set_error("dense_setup: more than 65535 unique dofs in a batch");
+      return WF_ERR_UNSUPPORTED;
+    }
+    numax = std::max(numax, nu);
+    for (int c = 0; c < nc; ++c)
+      for (int k = 0; k < nd; ++k) {
+        const int32_t g = dofmap[(size_t)(c0 + c) * nd + k];
+        const int u = (int)(std::lower_bound(tmp.begin(), tmp.end(), g) - tmp.begin());
+        const int ks = k / 4, lg = k % 4;
+        h_locP[(((size_t)b * KT2 + ks / 2) * 4 + lg) * NCB + c] |= (uint32_t)u << (16 * (ks & 1));
+      }
+    h_uniq.insert(h_uniq.end(), tmp.begin(), tmp.end());
+    h_uoff[b + 1] = (int32_t)h_uniq.size();
+  }
+  int rc;
+  if ((rc = locP.upload(h_locP)) != WF_OK) return rc;
+  if ((rc = uoff.upload(h_uoff)) != WF_OK) return rc;
+  return uniq.upload(h_uniq);
 }
 
 // Geometry of every cell at the n1^3 points of a 1-D rule, computed from the mesh into whichever of the device arrays

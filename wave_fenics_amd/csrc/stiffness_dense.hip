@@ -17,14 +17,16 @@
 // Gather/scatter ("permute/scatter stress"): per batch of 64 cells the host
 // computes the list of unique dofs; x is read once per unique dof into LDS, the
 // cell results are summed per unique dof in LDS (ds_add_f64) and leave with one
-// global atomic per unique dof.
+// global atomic per unique dof.  What this kernel shares with k_mass_dense_simplex (mass_dense_simplex.hip) -- batch
+// shape, LDS layout of the table, prefetch pieces and the rules of the batch pipeline, the device plan -- is
+// dense_simplex.h.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 
-#include "device_array.h"
+#include "dense_simplex.h"
 
 namespace wf {
 
@@ -53,16 +55,9 @@ __device__ __forceinline__ double clamp101d(double v)
 }
 
 // QT = ceil(nq/16), KT = ceil(nd/4), DT = ceil(nd/16); KP = row pitch of T in LDS.
-// LDS bank layout (64 banks x 4 B; a ds_read_b64 is served 32 lanes at a time): the first product
-// reads T[row(lc)][4 ks + lg] (16 rows x 2 columns per half wave), the second T[row(lg)][16 dt + lc]
-// (2 rows x 16 columns).  With KP = 4 KT + 2 (twice an odd number) and the 16 quadrature points of
-// a slab assigned to MFMA rows in the order pi(j) = (j >> 1) + 8 (j & 1), both patterns touch 32
-// distinct 8-byte banks: rows pi(.) KP cover all even bank pairs, and the two rows of a half wave
-// in the second product are 8 KP = 16 (mod 32) doubles apart.  (KP = 4 KT + 1 with rows in natural
-// order had 2-way conflicts on a third of the lanes in both products.)
-// (dense_pitch and dense_row_perm are in common.h: mass_dense_simplex.hip stores its matrix the same way)
-// NU: unique dofs of a batch per thread (numax <= NU * 64 NW), a compile-time bound for the
-// register-staged gather of the NEXT batch.
+// The table's rows are stored in the order dense_row_perm at the pitch dense_pitch(KT): the first product reads
+// T[row(lc)][4 ks + lg], the second T[row(lg)][16 dt + lc], both without bank conflicts (dense_simplex.h).
+// NU: unique dofs of a batch per thread (DenseBatchShape).
 // XR: output rows past the last whole 16-row tile that are NOT given an MFMA tile of their own
 // (nd = 16 (DT - 1) + XR, XR <= 4; 0 = pad nd to 16 DT as before).  P4 tetrahedra have nd = 35:
 // a third tile would spend 16 rows of matrix-core time on 3 rows of result, a fifth of the
@@ -86,8 +81,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                                                          double* __restrict__ y, int ablate_arg, int stagger)
 {
   [[maybe_unused]] const int ablate = WF_ABLATE_FLAGS(ablate_arg);
-  constexpr int NQP = 16 * QT, KP = dense_pitch(KT), NT = 64 * NW, NCB = 16 * NW;
-  constexpr int DTM = XR > 0 ? DT - 1 : DT, XN = XR > 0 ? XR : 1, KT2 = (KT + 1) / 2;
+  using Shape = DenseBatchShape<KT, NW, NU>;
+  constexpr int NQP = 16 * QT, KP = Shape::KP, NT = Shape::NT, NCB = Shape::NCB, KT2 = Shape::KT2;
+  constexpr int DTM = XR > 0 ? DT - 1 : DT, XN = XR > 0 ? XR : 1;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* T = smem;                 // [3*NQP][KP]
   double* sw = T + 3 * NQP * KP;    // [NQP]
@@ -115,42 +111,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // only memory latency left on the critical path is the scatter's.  Inside the MFMA section no
   // global load is consumed (loads retire in order).
   const int G = gridDim.x;
-  // Per-batch scalars (unique-dof range, clamp flag) are fetched with VECTOR loads one batch before
-  // they are needed: as scalar loads their (cold, ~1 us) latency sat in front of the MFMA section,
-  // and a pending s_load also turns every LDS wait into lgkmcnt(0).
-  auto vgpr_zero = [&]() {   // an opaque per-lane 0: pointer + this stays a global pointer but lives in VGPRs
-    int z = 0;
-    asm volatile("" : "+v"(z));
-    return z;
+  // the prefetch pieces and their rules: dense_simplex.h
+  auto load_range = [&](int b) { return dense_load_range(uoff, nbatch, b); };
+  auto load_uq = [&](int32_t (&uq)[NU], const DenseRange& rg) { dense_load_uq<NT>(uq, uniq, rg, t); };
+  // count_of and the locP load of load_cell are the same lines as in k_mass_dense_simplex: as shared functions they changed
+  // the code (profiles/r23_summary.md)
+  auto count_of = [&](const DenseRange& rg) { return rg.live ? rg.hi - rg.lo : 0; };
+  auto load_clamp = [&](int b) -> int {   // a per-batch scalar: a vector load
+    return clampb[(b < nbatch ? b : nbatch - 1) + dense_vgpr_zero()];
   };
-  auto vload_i32 = [&](const int32_t* p) { return p[vgpr_zero()]; };
-  struct Range {
-    int32_t lo, hi;   // uoff[b], uoff[b + 1]  (b clamped to a valid batch; `live` says whether b < nbatch)
-    bool live;
-  };
-  auto load_range = [&](int b) {
-    const int bb = b < nbatch ? b : nbatch - 1;
-    return Range{vload_i32(uoff + bb), vload_i32(uoff + bb + 1), b < nbatch};
-  };
-  // All prefetch loads are unconditional, on clamped indices (a thread past the end of a batch's
-  // unique-dof list re-reads the last entry, a batch past the end re-reads the last batch): guards
-  // around loads become branches, and at every join the compiler's vmcnt bookkeeping falls back to
-  // waiting for loads it has just issued.  Whether an entry is live is decided where it is used
-  // (nu_*: number of unique dofs of the batch).
-  auto load_uq = [&](int32_t (&uq)[NU], const Range& rg) {
-#pragma unroll
-    for (int m = 0; m < NU; ++m) uq[m] = uniq[min(rg.lo + t + NT * m, rg.hi - 1)];
-  };
-  auto count_of = [&](const Range& rg) { return rg.live ? rg.hi - rg.lo : 0; };
-  auto load_clamp = [&](int b) -> int {
-    return clampb[(b < nbatch ? b : nbatch - 1) + vgpr_zero()];
-  };
-  auto load_x = [&](double (&xr)[NU], const int32_t (&uq)[NU]) {
+  auto load_x = [&](double (&xr)[NU], const int32_t (&uq)[NU]) {   // dense_load_x, but for the ablation
 #pragma unroll
     for (int m = 0; m < NU; ++m) xr[m] = (ablate & 4) ? 1.0 + m : x[uq[m]];
   };
-  // Local indices travel as packed pairs: loaded as 16-bit values the compiler packs them two to a
-  // register right after the load, i.e. waits for the prefetch it has just issued.
   auto load_cell = [&](uint32_t (&loc)[KT2], double (&C)[6], double& ac, int b) {
     const int bb = b < nbatch ? b : nbatch - 1;
     if constexpr (AC) ac = Ag[(size_t)bb * NCB + wave * 16 + lc];
@@ -163,13 +136,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   int32_t uq_cur[NU], uq_nxt[NU];     // unique dofs (this thread's share) of the batch being computed / of the next one
   double xr[NU];
   uint32_t loc[KT2], locn[KT2];
-  auto loc_of = [&](int ks) -> uint32_t { return (loc[ks >> 1] >> (16 * (ks & 1))) & 0xffffu; };
+  auto loc_of = [&](int ks) { return dense_loc_of(loc, ks); };
   double C[6], Cn[6];
   [[maybe_unused]] double ac = 1.0, acn = 1.0;   // AC: the lane's cell coefficient, this batch's and the next one's
   // prologue: first batch straight into LDS, indices of the second
   int nu_cur, nu_nxt;   // live entries of uq_cur / uq_nxt
   {
-    const Range r0 = load_range(blockIdx.x), r1 = load_range(blockIdx.x + G);
+    const DenseRange r0 = load_range(blockIdx.x), r1 = load_range(blockIdx.x + G);
     load_uq(uq_cur, r0);
     nu_cur = count_of(r0);
     load_x(xr, uq_cur);
@@ -177,7 +150,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     load_uq(uq_nxt, r1);
     nu_nxt = count_of(r1);
   }
-  Range rg2 = load_range(blockIdx.x + 2 * G);   // range of the batch whose unique-dof list is fetched next
+  DenseRange rg2 = load_range(blockIdx.x + 2 * G);   // range of the batch whose unique-dof list is fetched next
   int clamp_cur = load_clamp(blockIdx.x);
 #pragma unroll
   for (int m = 0; m < NU; ++m) {
@@ -217,7 +190,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     load_cell(locn, Cn, acn, batch + G);
     load_uq(uq_nn, rg2);
     const int nu_nn = count_of(rg2);
-    const Range rg3 = load_range(batch + 3 * G);
+    const DenseRange rg3 = load_range(batch + 3 * G);
     const int clamp_nxt = load_clamp(batch + G);
 
     double4_t Y[DTM];
@@ -240,6 +213,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
       for (int e = 0; e < 3; ++e) W[e] = double4_t{0.0, 0.0, 0.0, 0.0};
       const double* Ta = T + (16 * qt + dense_row_perm(lc)) * KP + lg;   // + e NQP KP + 4 ks
+      // (k_mass_dense_simplex rotates its DT row sets, 16 KP apart, in the same way: written out in both)
       double a3[3][3];   // rotating operand sets, reads two k-steps ahead (no copies: a copy waits for the read just issued)
 #pragma unroll
       for (int e = 0; e < 3; ++e) a3[0][e] = Ta[e * NQP * KP];
@@ -337,10 +311,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     WF_DTR(3);
     __syncthreads();   // Yu complete; every wave has taken its operands out of Xu
     WF_DTR(4);
-    // Order matters: every consumer of a prefetched register (xr, uq_nn, locn, Cn, the next ranges)
-    // comes BEFORE the first global atomic.  On gfx9 loads and atomics share vmcnt and the compiler
-    // waits for vmcnt(0) once both kinds are pending, so an atomic issued earlier put its whole
-    // round trip (~0.5 us, five times per batch) in front of the next consumer.
+    // End-of-batch stage, the same lines as in k_mass_dense_simplex (mass_dense_simplex.hip), which also issues its
+    // x gather here; written out in both, see rule 3 of dense_simplex.h: every consumer of a prefetched register (xr,
+    // uq_nn, locn, Cn, the next ranges) comes BEFORE the first global atomic.
     double yv[NU];
     int32_t uq_old[NU];
 #pragma unroll
@@ -386,11 +359,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 struct DenseOpData {
-  int nd = 0, nq = 0, QT = 0, KT = 0, DT = 0, nbatch = 0, numax = 0, nw = 4;
+  int nd = 0, nq = 0, QT = 0, KT = 0, DT = 0;
   DevArray<double> d_T, d_w, d_C;
   DevArray<double> d_a;   // cell coefficients per cell slot of the batches; empty: none, the AC = false kernel runs
-  DevArray<uint32_t> d_locP;
-  DevArray<int32_t> d_uoff, d_uniq;
+  DenseBatchPlanDev plan;
   DevArray<uint8_t> d_clampb;
 };
 
@@ -409,56 +381,9 @@ void dense_free(DenseOpData* d) { delete d; }
   F(2, 9, 3, 3)            \
   F(2, 9, 3, 0)
 
-static bool dense_shape_compiled(int QT, int KT, int DT)
-{
-#define WF_DENSE_HAS(Q, K, D, X) \
-  if (QT == Q && KT == K && DT == D) return true;
-  WF_DENSE_SHAPES(WF_DENSE_HAS)
+#define WF_DENSE_HAS(Q, K, D, X) || (QT == Q && KT == K && DT == D)
+static bool dense_shape_compiled(int QT, int KT, int DT) { return false WF_DENSE_SHAPES(WF_DENSE_HAS); }
 #undef WF_DENSE_HAS
-  return false;
-}
-
-// Per-batch gather/scatter plan of the dense simplex kernels (this file and mass_dense_simplex.hip): for every batch of
-// NCB consecutive cells the sorted list of its distinct dofs (uniq, offsets uoff) and, packed two to a word in the
-// kernels' operand order, the position of every element-local dof in that list:
-// locP[b][ks / 2][lg][cell] holds the local index of dof 4 ks + lg in bits 16 (ks & 1) .. 16 (ks & 1) + 15.
-int dense_batch_plan(int nd, int KT, int NCB, int ncells, const int32_t* dofmap, DenseBatchPlan* plan)
-{
-  const int nbatch = (ncells + NCB - 1) / NCB;
-  const int KT2 = (KT + 1) / 2;
-  plan->locP.assign((size_t)nbatch * KT2 * 4 * NCB, 0);
-  plan->uoff.assign(nbatch + 1, 0);
-  plan->uniq.clear();
-  std::vector<uint32_t>& locP = plan->locP;
-  std::vector<int32_t>& uoff = plan->uoff;
-  std::vector<int32_t>& uniq = plan->uniq;
-  uniq.reserve((size_t)ncells * nd / 2);
-  std::vector<int32_t> tmp;
-  int numax = 0;
-  for (int b = 0; b < nbatch; ++b) {
-    const int c0 = b * NCB, nc = std::min(NCB, ncells - c0);
-    tmp.assign(dofmap + (size_t)c0 * nd, dofmap + (size_t)(c0 + nc) * nd);
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    const int nu = (int)tmp.size();
-    if (nu > 65535) {
-      set_error("dense_setup: more than 65535 unique dofs in a batch");
-      return WF_ERR_UNSUPPORTED;
-    }
-    numax = std::max(numax, nu);
-    for (int c = 0; c < nc; ++c)
-      for (int k = 0; k < nd; ++k) {
-        const int32_t g = dofmap[(size_t)(c0 + c) * nd + k];
-        const int u = (int)(std::lower_bound(tmp.begin(), tmp.end(), g) - tmp.begin());
-        const int ks = k / 4, lg = k % 4;
-        locP[(((size_t)b * KT2 + ks / 2) * 4 + lg) * NCB + c] |= (uint32_t)u << (16 * (ks & 1));
-      }
-    uniq.insert(uniq.end(), tmp.begin(), tmp.end());
-    uoff[b + 1] = (int32_t)uniq.size();
-  }
-  plan->numax = std::max(numax, 1);
-  return WF_OK;
-}
 
 // Host setup: padded table, per-cell affine geometry C = |det J| K K^T, per-batch
 // unique-dof lists and local indices.
@@ -472,13 +397,12 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
   d->QT = (nq + 15) / 16;
   d->KT = (nd + 3) / 4;
   d->DT = (nd + 15) / 16;
-  d->nw = 4;
   if (!dense_shape_compiled(d->QT, d->KT, d->DT)) {
     set_error("stiffness_dense: (nd, nq) shape not compiled (supported: tetrahedron P1..P4)");
     return WF_ERR_UNSUPPORTED;
   }
 
-  const int NCB = 16 * d->nw;
+  constexpr int NCB = kDenseBatchCells;
   const int NQP = 16 * d->QT, KP = dense_pitch(d->KT);
   std::vector<double> T((size_t)3 * NQP * KP, 0.0), w(NQP, 0.0);
   for (int dir = 0; dir < 3; ++dir)
@@ -486,15 +410,10 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
       for (int k = 0; k < nd; ++k) T[((size_t)dir * NQP + q) * KP + k] = dphi[((size_t)dir * nq + q) * nd + k];
   for (int q = 0; q < nq; ++q) w[q] = weights[q];
   const int nbatch = (ncells + NCB - 1) / NCB;
-  d->nbatch = nbatch;
   std::vector<double> C((size_t)nbatch * NCB * 6, 0.0);
   for (int c = 0; c < ncells; ++c) {
-    const int32_t* v = geom_dofmap + (size_t)c * 4;
     double J[9];
-    for (int i = 0; i < 3; ++i)
-      for (int j = 0; j < 3; ++j) J[i * 3 + j] = xverts[(size_t)v[j + 1] * 3 + i] - xverts[(size_t)v[0] * 3 + i];
-    const double det = J[0] * (J[4] * J[8] - J[5] * J[7]) - J[1] * (J[3] * J[8] - J[5] * J[6])
-                       + J[2] * (J[3] * J[7] - J[4] * J[6]);
+    const double det = tet_jacobian(xverts, geom_dofmap + (size_t)c * 4, J);
     const double id = 1.0 / det;
     double K[9];
     K[0] = (J[4] * J[8] - J[5] * J[7]) * id;
@@ -521,9 +440,6 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
       return WF_ERR_INVALID;
     }
   }
-  DenseBatchPlan plan;
-  if (int rc = dense_batch_plan(nd, d->KT, NCB, ncells, dofmap, &plan)) return rc;
-  d->numax = plan.numax;
   (void)ndofs;
   // batches in which the clamp is not the identity
   std::vector<uint8_t> clampb(nbatch, 0);
@@ -537,6 +453,7 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
     if (hit) clampb[c / NCB] = 1;
   }
   int rc;
+  if ((rc = d->plan.build(nd, d->KT, ncells, dofmap)) != WF_OK) return rc;
   if ((rc = d->d_T.upload(T)) != WF_OK) return rc;
   if ((rc = d->d_w.upload(w)) != WF_OK) return rc;
   if ((rc = d->d_C.upload(C)) != WF_OK) return rc;
@@ -545,9 +462,6 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
     std::copy(cell_coeff, cell_coeff + ncells, a.begin());
     if ((rc = d->d_a.upload(a)) != WF_OK) return rc;
   }
-  if ((rc = d->d_locP.upload(plan.locP)) != WF_OK) return rc;
-  if ((rc = d->d_uoff.upload(plan.uoff)) != WF_OK) return rc;
-  if ((rc = d->d_uniq.upload(plan.uniq)) != WF_OK) return rc;
   if ((rc = d->d_clampb.upload(clampb)) != WF_OK) return rc;
   *out = d.release();
   return WF_OK;
@@ -555,8 +469,7 @@ int dense_setup(int nd, int nq, int ncells, int ndofs, const int32_t* dofmap, co
 
 size_t dense_bytes(const DenseOpData* d)
 {
-  return d ? d->d_T.bytes() + d->d_w.bytes() + d->d_C.bytes() + d->d_a.bytes() + d->d_locP.bytes() + d->d_uoff.bytes() + d->d_uniq.bytes()
-                 + d->d_clampb.bytes()
+  return d ? d->d_T.bytes() + d->d_w.bytes() + d->d_C.bytes() + d->d_a.bytes() + d->plan.bytes() + d->d_clampb.bytes()
            : 0;
 }
 
@@ -565,7 +478,8 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
                           hipStream_t s)
 {
   constexpr int NQP = 16 * QT, KP = dense_pitch(KT);
-  const size_t lds = ((size_t)3 * NQP * KP + NQP + 2 * d->numax) * sizeof(double);
+  const DenseBatchPlanDev& pl = d->plan;
+  const size_t lds = ((size_t)3 * NQP * KP + NQP + 2 * pl.numax) * sizeof(double);
   if (lds > 160 * 1024) {
     set_error("stiffness_dense: tables do not fit LDS");
     return WF_ERR_UNSUPPORTED;
@@ -581,26 +495,26 @@ static int launch_dense_t(const DenseOpData* d, double coeff, int do_clamp, cons
 #else
   const int wgs_per_cu = 2, ablate = 0, stagger = 0;
 #endif
-  const unsigned nb = (unsigned)std::min(d->nbatch, 256 * wgs_per_cu);   // persistent: the table is staged into LDS once per workgroup
-  hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * NW), lds, s, d->nd, d->nq, d->nbatch, d->numax, d->d_T.data(),
-                     d->d_w.data(), d->d_C.data(), d->d_a.data(), d->d_locP.data(), d->d_uoff.data(), d->d_uniq.data(), d->d_clampb.data(),
+  const unsigned nb = (unsigned)std::min(pl.nbatch, 256 * wgs_per_cu);   // persistent: the table is staged into LDS once per workgroup
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(64 * NW), lds, s, d->nd, d->nq, pl.nbatch, pl.numax, d->d_T.data(),
+                     d->d_w.data(), d->d_C.data(), d->d_a.data(), pl.locP.data(), pl.uoff.data(), pl.uniq.data(), d->d_clampb.data(),
                      coeff, do_clamp, d_x, d_y, ablate, stagger);
   return launch_status("stiffness_dense");
 }
 
-// NU = 5 covers the unique dofs of 64 well-numbered P4 cells (1154 on the Kuhn box); 9 is the worst case 64 * 35
-#define WF_DENSE_CASE(Q, K, D, X)                                                                                \
-  if (d->QT == Q && d->KT == K && d->DT == D && (X == 0 || d->nd == 16 * (D - 1) + X))                            \
-    return d->numax <= 5 * 256 ? (d->d_a.size() ? launch_dense_t<Q, K, D, 4, 5, X, true>(d, coeff, do_clamp, d_x, d_y, s)    \
-                                                : launch_dense_t<Q, K, D, 4, 5, X, false>(d, coeff, do_clamp, d_x, d_y, s))  \
-                               : (d->d_a.size() ? launch_dense_t<Q, K, D, 4, 9, X, true>(d, coeff, do_clamp, d_x, d_y, s)    \
-                                                : launch_dense_t<Q, K, D, 4, 9, X, false>(d, coeff, do_clamp, d_x, d_y, s));
+// the XR form of a shape where nd fits it, with the coefficient variant where the operator has one
+#define WF_DENSE_LAUNCH(Q, K, D, X, NU)                                                                                        \
+  (d->d_a.size() ? launch_dense_t<Q, K, D, kDenseWaves, NU, X, true>(d, coeff, do_clamp, d_x, d_y, s)                          \
+                 : launch_dense_t<Q, K, D, kDenseWaves, NU, X, false>(d, coeff, do_clamp, d_x, d_y, s))
+#define WF_DENSE_CASE(Q, K, D, X)                                                                                              \
+  if (d->QT == Q && d->KT == K && d->DT == D && (X == 0 || d->nd == 16 * (D - 1) + X))                                          \
+    return dense_nu(d->plan.numax) == kDenseNuSmall ? WF_DENSE_LAUNCH(Q, K, D, X, kDenseNuSmall) : WF_DENSE_LAUNCH(Q, K, D, X, kDenseNuLarge);
 
 // (dense_setup has refused every shape that is not in WF_DENSE_SHAPES)
 int launch_stiffness_dense(const DenseOpData* d, double coeff, int do_clamp, const double* d_x, double* d_y,
                            hipStream_t s)
 {
-  if (d->nbatch == 0) return WF_OK;
+  if (d->plan.nbatch == 0) return WF_OK;
   WF_DENSE_SHAPES(WF_DENSE_CASE)
   set_error("stiffness_dense: (nd, nq) shape not compiled (supported: tetrahedron P1..P4)");
   return WF_ERR_UNSUPPORTED;
