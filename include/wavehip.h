@@ -715,6 +715,47 @@ int wf_fs_facet_mass_weighted(int degree, int64_t nverts, const double* h_xverts
                               double* h_mass);
 int wf_fs_min_cell_diameter(int64_t nverts, const double* h_xverts, int64_t ncells, const int32_t* h_cells, double* hmin);
 
+/* ---- the same for the box (host only) --------------------------------------------------------
+ * mesh::create_box + fem::create_functionspace (demo/gpu_operator/main.cpp:60-72) on n[3] cells in this engine's
+ * lexicographic numbering, and the Cartesian partition of a weak-scaled box (idea of demo/gpu_cg/mesh.hpp:37-63).
+ * wavehip_box.hpp and the Python package are wrappers over these entries and hold no rule of their own.
+ * wf_box_mesh: vertices h_x [nverts][3], vertex (a, b, c) -> a + (nx+1)(b + (ny+1)c) at lo + (hi-lo)/n * a, the last
+ *   point exactly hi (numpy.linspace); h_geom_dofmap [ncells][8], vertex v = a + 2b + 4c of cell cx + nx (cy + ny cz).
+ * wf_box_dofmap: h_dofmap [ncells][(P+1)^3], tensor order, dof (I, J, K) -> I + NX (J + NY K), NX = P nx + 1.
+ * wf_box_facet_mass: wf_fs_facet_mass_weighted (the same loop) on the faces 2*axis + side whose face_tag equals tag
+ *   (tag != 0; face_tag 0 = untagged), with the implicit dofmap: no array of ncells (P+1)^3 entries is needed.
+ *   h_cell_weight [ncells] or NULL.  Ascending dofs.  With h_idx = h_mass = NULL only *nout is set; the arrays of the
+ *   second call hold that many entries.
+ * wf_decompose3d: nproc = px py pz with px >= py >= pz, the smallest (px - pz, px).
+ * wf_box_partition: the part of rank `rank` of nproc = px py pz ranks, n[3] cells PER RANK, rank = rz + pz (ry + py rx).
+ *   A lattice point shared by several ranks belongs to the lowest one, so a rank's ghosts are the lower planes of its
+ *   local lattice where a lower neighbour exists; on a periodic axis (periodic[a] != 0; NULL = none) every rank's lower
+ *   plane is ghost and the neighbours wrap (a rank can be its own neighbour).  Local vectors keep the lattice numbering.
+ *   The lists are those of wf_updater_desc: neighbours ascending; the directions (dx, dy, dz) in {0,1}^3 that reach one
+ *   neighbour are concatenated in loop order (dz fastest), on the sending and on the receiving side alike; inside a
+ *   direction x runs fastest.  At most 7 neighbours each way: neighbour arrays of 7, offset arrays of 8 entries always
+ *   suffice.  With all six arrays NULL only *info is filled (all six or none; the array of
+ *   an empty index list may stay NULL). */
+typedef struct {
+  int procs[3], coords[3];
+  int owned_lo[3];               /* first owned lattice index per axis (0 or 1)                     */
+  int lattice[3];                /* local lattice (P n + 1 per axis), ghosts included                */
+  int64_t size_global;           /* dofs of the whole box                                           */
+  int64_t num_owned;
+  int num_send_neighbors, num_recv_neighbors;
+  int32_t num_send_indices, num_recv_indices;
+  int face_tag[6];               /* cfg1: global face x = lo -> 1, other global faces -> 2, else 0  */
+} wf_box_partition_info;
+int wf_box_mesh(const int* n /* [3] */, const double* lo /* [3] */, const double* hi /* [3] */, double* h_x,
+                int32_t* h_geom_dofmap);
+int wf_box_dofmap(int degree, const int* n, int32_t* h_dofmap);
+int wf_box_facet_mass(int degree, const int* n, const double* h_x, const int* face_tag /* [6] */, int tag,
+                      const double* h_cell_weight, int64_t* nout, int32_t* h_idx, double* h_mass);
+int wf_decompose3d(int nproc, int* procs /* [3] */);
+int wf_box_partition(const int* n, int degree, int nproc, int rank, const int* periodic /* [3] */,
+                     wf_box_partition_info* info, int* send_neighbors, int32_t* send_offsets, int32_t* send_indices,
+                     int* recv_neighbors, int32_t* recv_offsets, int32_t* ghost_positions);
+
 #ifdef __cplusplus
 }
 #endif

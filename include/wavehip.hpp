@@ -20,6 +20,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "wavehip.h"
@@ -29,6 +30,18 @@ namespace wavehip {
 inline void check(int rc)
 {
   if (rc != WF_OK) throw std::runtime_error(std::string("wavehip: ") + wf_last_error());
+}
+
+/// demo/cpu_planar3d/main.cpp:48-66: the time step CFL h / (c0 P^2) for the smallest cell diameter h (mesh::h,
+/// wf_fs_min_cell_diameter), rounded down to a whole number of steps per source period: (time step, steps per period)
+inline std::pair<double, int> cfl_time_step(std::int64_t nverts, const double* x, std::int64_t ncells, const std::int32_t* cells,
+                                            int degree, double c0, double freq, double CFL)
+{
+  double h = 0.0;
+  check(wf_fs_min_cell_diameter(nverts, x, ncells, cells, &h));
+  const double dt = CFL * h / (c0 * degree * degree), period = 1.0 / freq;
+  const int spp = (int)(period / dt + 1);
+  return {period / spp, spp};
 }
 
 // ---- utils::set_device (common/cuda/utils.hpp:22-38) ----------------------

@@ -140,11 +140,7 @@ inline std::pair<std::vector<std::int32_t>, std::vector<double>> boundary_set(co
 /// demo/cpu_planar3d/main.cpp:48-66: (time step, steps per period) from mesh::h = the smallest cell diameter
 inline std::pair<double, int> cfl_time_step(const FileMesh& mesh, int degree, double c0, double freq, double CFL = 0.5)
 {
-  double h = 0.0;
-  check(wf_fs_min_cell_diameter(mesh.nverts(), mesh.x.data(), mesh.ncells(), mesh.cells.data(), &h));
-  const double dt = CFL * h / (c0 * degree * degree), period = 1.0 / freq;
-  const int spp = (int)(period / dt + 1);
-  return {period / spp, spp};
+  return cfl_time_step(mesh.nverts(), mesh.x.data(), mesh.ncells(), mesh.cells.data(), degree, c0, freq, CFL);
 }
 
 }  // namespace wavehip

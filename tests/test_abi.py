@@ -69,9 +69,12 @@ def test_unsupported_degree_is_an_error(wlib):
 
 def test_box_mesh_matches_oracle(oracle):
     import wave_fenics_amd as w
-    for p, n, pert in [(2, (3, 2, 4), 0.2), (4, (2, 2, 2), 0.0)]:
-        om = oracle.create_box(n, p, perturb=pert)
-        m = w.create_box(n, perturb=pert)
+    unit = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+    offset = ((0.1, -0.3, 0.0), (1.3, 0.9, 2.0))      # neither unit nor at the origin
+    for p, n, pert, (lo, hi) in [(2, (3, 2, 4), 0.2, unit), (4, (2, 2, 2), 0.0, unit), (2, (3, 2, 4), 0.0, offset),
+                                 (3, (3, 2, 4), 0.2, offset), (1, (1, 1, 1), 0.0, unit), (5, (1, 1, 1), 0.0, offset)]:
+        om = oracle.create_box(n, p, lo=lo, hi=hi, perturb=pert)
+        m = w.create_box(n, lo=lo, hi=hi, perturb=pert)
         V = w.create_functionspace(m, p)
         assert np.array_equal(m.x, om.x) and np.array_equal(m.geom_dofmap, om.geom_dofmap)
         assert np.array_equal(V.dofmap, om.dofmap) and V.ndofs == om.ndofs

@@ -251,4 +251,4 @@ def test_weighted_facet_mass(oracle, wlib, tmp_path, p):
         dense[f_of_box[ib]] = mb
         fi, fm = (sa, sb)[k]
         assert np.array_equal(np.nonzero(dense)[0], fi)
-        assert np.abs(fm - dense[fi]).max() <= 1e-14 * np.abs(dense).max()
+        assert np.array_equal(mh.bits(fm), mh.bits(dense[fi]))       # one loop behind both paths, the facets in one order

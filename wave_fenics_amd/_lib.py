@@ -80,6 +80,17 @@ class UpdaterDesc(ctypes.Structure):
     ]
 
 
+class BoxPartitionInfo(ctypes.Structure):
+    """wf_box_partition_info"""
+    _fields_ = [
+        ("procs", c_int * 3), ("coords", c_int * 3), ("owned_lo", c_int * 3), ("lattice", c_int * 3),
+        ("size_global", c_int64), ("num_owned", c_int64),
+        ("num_send_neighbors", c_int), ("num_recv_neighbors", c_int),
+        ("num_send_indices", c_int32), ("num_recv_indices", c_int32),
+        ("face_tag", c_int * 6),
+    ]
+
+
 MATVEC_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 
 
@@ -108,7 +119,7 @@ WF_UPDATE_NONE, WF_UPDATE_ATOMIC, WF_UPDATE_OWNER, WF_UPDATE_ORDERED = 0, 1, 2, 
 WF_PART_ALL, WF_PART_INTERIOR, WF_PART_INTERFACE, WF_PART_INTERIOR_A, WF_PART_INTERIOR_B = 0, 1, 2, 3, 4
 
 # every symbol include/wavehip.h declares: name -> (restype, argtypes)
-_dp, _ip, _vp = POINTER(c_double), POINTER(c_int32), c_void_p
+_DP, _IP, _VP = POINTER(c_double), POINTER(c_int32), c_void_p
 SIGNATURES = {
     "wf_last_error": (c_char_p, []),
     "wf_version": (c_char_p, []),
@@ -121,22 +132,22 @@ SIGNATURES = {
     "wf_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_size_t]),
     "wf_memset": (c_int, [c_void_p, c_int, c_size_t, c_void_p]),
     "wf_sync": (c_int, [c_void_p]),
-    "wf_tabulate_gll": (c_int, [c_int, _dp, _dp, _dp]),
-    "wf_tabulate_dense": (c_int, [c_int, _dp]),
-    "wf_quadrature_1d": (c_int, [c_int, c_int, POINTER(c_int), _dp, _dp]),
-    "wf_tabulate_1d": (c_int, [c_int, c_int, c_int, _dp, c_int, _dp]),
-    "wf_geometry_hex_rule": (c_int, [c_int, c_int, _dp, _ip, c_int, _dp, _dp, c_int, c_int, _dp, _dp]),
-    "wf_geometry_hex_cell": (c_int, [c_int, c_int64, c_int64, _dp, _ip, c_int, c_int, _dp, POINTER(c_int64), POINTER(c_int)]),
-    "wf_reorder_dofmap": (c_int, [c_int, c_int, _ip, _ip, _ip]),
-    "wf_lattice_numbering": (c_int, [c_int, ctypes.c_int64, ctypes.c_int32, _ip, _ip]),
-    "wf_geometry_hex": (c_int, [c_int, c_int, c_int, _dp, _ip, c_int, c_int, _dp, _dp]),
+    "wf_tabulate_gll": (c_int, [c_int, _DP, _DP, _DP]),
+    "wf_tabulate_dense": (c_int, [c_int, _DP]),
+    "wf_quadrature_1d": (c_int, [c_int, c_int, POINTER(c_int), _DP, _DP]),
+    "wf_tabulate_1d": (c_int, [c_int, c_int, c_int, _DP, c_int, _DP]),
+    "wf_geometry_hex_rule": (c_int, [c_int, c_int, _DP, _IP, c_int, _DP, _DP, c_int, c_int, _DP, _DP]),
+    "wf_geometry_hex_cell": (c_int, [c_int, c_int64, c_int64, _DP, _IP, c_int, c_int, _DP, POINTER(c_int64), POINTER(c_int)]),
+    "wf_reorder_dofmap": (c_int, [c_int, c_int, _IP, _IP, _IP]),
+    "wf_lattice_numbering": (c_int, [c_int, ctypes.c_int64, ctypes.c_int32, _IP, _IP]),
+    "wf_geometry_hex": (c_int, [c_int, c_int, c_int, _DP, _IP, c_int, c_int, _DP, _DP]),
     "wf_op_create": (c_int, [POINTER(OpDesc), POINTER(c_void_p)]),
-    "wf_op_create_box": (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_int, POINTER(c_void_p)]),
-    "wf_op_create_box_tuned": (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, c_double, c_int, POINTER(Tuning),
+    "wf_op_create_box": (c_int, [c_int, c_int, c_int, c_int, c_int, _DP, c_double, c_int, POINTER(c_void_p)]),
+    "wf_op_create_box_tuned": (c_int, [c_int, c_int, c_int, c_int, c_int, _DP, c_double, c_int, POINTER(Tuning),
                                        POINTER(c_void_p)]),
-    "wf_op_create_box_coeff": (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, c_double, _dp, c_int, POINTER(Tuning),
+    "wf_op_create_box_coeff": (c_int, [c_int, c_int, c_int, c_int, c_int, _DP, c_double, _DP, c_int, POINTER(Tuning),
                                        POINTER(c_void_p)]),
-    "wf_op_set_ghost_dofs": (c_int, [c_void_p, _ip, c_int32]),
+    "wf_op_set_ghost_dofs": (c_int, [c_void_p, _IP, c_int32]),
     "wf_op_create_dense_simplex": (c_int, [POINTER(DenseDesc), POINTER(c_void_p)]),
     "wf_op_create_dense_simplex_mass": (c_int, [POINTER(DenseMassDesc), POINTER(c_void_p)]),
     "wf_op_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -153,7 +164,7 @@ SIGNATURES = {
     "wf_scatter_add": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_scatter_set": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_transform1": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "wf_ordered_slots": (c_int, [c_int64, c_int, c_int32, _ip, _ip, _ip]),
+    "wf_ordered_slots": (c_int, [c_int64, c_int, c_int32, _IP, _IP, _IP]),
     "wf_segment_sum_add": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_tsmm": (c_int, [c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_copy": (c_int, [c_int64, c_void_p, c_void_p, c_void_p]),
@@ -164,7 +175,7 @@ SIGNATURES = {
     "wf_pointwise_mult_add": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_dot": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_rk4_stage": (c_int, [c_int64, c_double, c_double, c_int] + [c_void_p] * 12),
-    "wf_boundary_create": (c_int, [c_int64, c_int32, _ip, _dp, c_int32, _ip, _dp, POINTER(c_void_p)]),
+    "wf_boundary_create": (c_int, [c_int64, c_int32, _IP, _DP, c_int32, _IP, _DP, POINTER(c_void_p)]),
     "wf_boundary_destroy": (c_int, [c_void_p]),
     "wf_boundary_apply_plan": (c_int, [c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "wf_rk4_stage_bc": (c_int, [c_int64, c_double, c_double, c_int] + [c_void_p] * 11 + [c_void_p, c_double, c_double, c_void_p]),
@@ -188,21 +199,27 @@ SIGNATURES = {
     "wf_op_apply_overlapped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "wf_mesh_open": (c_int, [c_char_p, c_char_p, POINTER(c_void_p)]),
     "wf_mesh_sizes": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),
-    "wf_mesh_read": (c_int, [c_void_p, _dp, _ip]),
+    "wf_mesh_read": (c_int, [c_void_p, _DP, _IP]),
     "wf_mesh_tags_size": (c_int, [c_void_p, c_char_p, POINTER(c_int64)]),
-    "wf_mesh_read_tags": (c_int, [c_void_p, c_char_p, _ip, _ip]),
+    "wf_mesh_read_tags": (c_int, [c_void_p, c_char_p, _IP, _IP]),
     "wf_mesh_close": (c_int, [c_void_p]),
-    "wf_mesh_write": (c_int, [c_char_p, c_char_p, c_int64, _dp, c_int64, _ip, c_char_p, c_int64, _ip, _ip]),
+    "wf_mesh_write": (c_int, [c_char_p, c_char_p, c_int64, _DP, c_int64, _IP, c_char_p, c_int64, _IP, _IP]),
     "wf_markers_enable": (c_int, [c_int]),
     "wf_marker_push": (c_int, [c_char_p]),
     "wf_marker_pop": (c_int, []),
     "wf_marker_mark": (c_int, [c_char_p]),
-    "wf_fs_build": (c_int, [c_int, c_int64, _dp, c_int64, _ip, POINTER(c_int64), _ip, _dp, c_int64]),
-    "wf_fs_locate_facets": (c_int, [c_int64, _ip, c_int64, _ip, _ip, _ip, _ip]),
-    "wf_fs_facet_mass": (c_int, [c_int, c_int64, _dp, c_int64, _ip, _ip, c_int64, _ip, _ip, _ip, POINTER(c_int64), _ip, _dp]),
-    "wf_fs_facet_mass_weighted": (c_int, [c_int, c_int64, _dp, c_int64, _ip, _ip, c_int64, _ip, _ip, _ip, _dp, POINTER(c_int64),
-                                          _ip, _dp]),
-    "wf_fs_min_cell_diameter": (c_int, [c_int64, _dp, c_int64, _ip, POINTER(c_double)]),
+    "wf_fs_build": (c_int, [c_int, c_int64, _DP, c_int64, _IP, POINTER(c_int64), _IP, _DP, c_int64]),
+    "wf_fs_locate_facets": (c_int, [c_int64, _IP, c_int64, _IP, _IP, _IP, _IP]),
+    "wf_fs_facet_mass": (c_int, [c_int, c_int64, _DP, c_int64, _IP, _IP, c_int64, _IP, _IP, _IP, POINTER(c_int64), _IP, _DP]),
+    "wf_fs_facet_mass_weighted": (c_int, [c_int, c_int64, _DP, c_int64, _IP, _IP, c_int64, _IP, _IP, _IP, _DP, POINTER(c_int64),
+                                          _IP, _DP]),
+    "wf_fs_min_cell_diameter": (c_int, [c_int64, _DP, c_int64, _IP, POINTER(c_double)]),
+    "wf_box_mesh": (c_int, [POINTER(c_int), _DP, _DP, _DP, _IP]),
+    "wf_box_dofmap": (c_int, [c_int, POINTER(c_int), _IP]),
+    "wf_box_facet_mass": (c_int, [c_int, POINTER(c_int), _DP, POINTER(c_int), c_int, _DP, POINTER(c_int64), _IP, _DP]),
+    "wf_decompose3d": (c_int, [c_int, POINTER(c_int)]),
+    "wf_box_partition": (c_int, [POINTER(c_int), c_int, c_int, c_int, POINTER(c_int), POINTER(BoxPartitionInfo),
+                                 POINTER(c_int), _IP, _IP, POINTER(c_int), _IP, _IP]),
     "wf_cg": (c_int, [POINTER(CGDesc), c_void_p, c_void_p, POINTER(c_int), POINTER(c_double), c_void_p]),
     "wf_boundary_apply": (c_int, [c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p, c_void_p, c_double,
                                   c_void_p, c_void_p, c_void_p]),
@@ -234,6 +251,16 @@ def lib():
             fn.argtypes = args
         _LIB = L
     return _LIB
+
+
+def _dp(a):
+    """a float64 numpy array (or None) as the const double* of a C ABI call"""
+    return None if a is None else a.ctypes.data_as(_DP)
+
+
+def _ip(a):
+    """an int32 numpy array (or None) as the const int32_t* of a C ABI call"""
+    return None if a is None else a.ctypes.data_as(_IP)
 
 
 def check(rc: int):

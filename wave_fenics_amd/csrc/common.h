@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -105,6 +107,19 @@ struct DMat {
 // ---- host tabulation (tables.cpp) ----
 void gll_points_weights(int n, double* pts, double* wts);
 void gll_derivative_matrix(int P, double* D);  // clamped, D[q*n + a]
+
+// ---- collocated facet masses (function_space.cpp, host only) ----
+// The loop behind wf_fs_facet_mass_weighted and wf_box_facet_mass: acc[dof] += w_a w_b |dx/ds x dx/dt| (times
+// cell_weight[cell] if given) over the GLL points of every listed facet (cell, axis, side), facets in list order.
+// vertex(c, v): row of xverts of vertex v = a + 2b + 4c of cell c, -1 if the mesh names none; dof(c, l): the dof at
+// element-local (l[0], l[1], l[2]) of cell c.
+struct FacetList {
+  int64_t count;
+  const int32_t *cell, *axis, *side;
+};
+int facet_mass(int P, const FacetList& facets, int64_t ncells, const double* xverts,
+               const std::function<int64_t(int64_t, int)>& vertex, const std::function<int32_t(int64_t, const int*)>& dof,
+               const double* cell_weight, std::map<int32_t, double>& acc);
 
 // cells per workgroup batch of the column-thread kernels: floor(256 / n^2).  For host code with a run-time P; the
 // kernels and their launchers take it from CellBatch<P> (cell_batch.h), which asserts that the two agree.

@@ -58,6 +58,47 @@ const int kFaceVerts[6][4] = {{0, 2, 4, 6}, {1, 3, 5, 7}, {0, 1, 4, 5}, {2, 3, 6
 
 }  // namespace
 
+// The one facet-mass loop (common.h): wf_fs_facet_mass_weighted gives it the rows of a caller's cells and dofmap,
+// wf_box_facet_mass (box_space.cpp) the implicit numbering of the box.
+int wf::facet_mass(int P, const FacetList& facets, int64_t ncells, const double* xverts,
+                   const std::function<int64_t(int64_t, int)>& vertex, const std::function<int32_t(int64_t, const int*)>& dof,
+                   const double* cell_weight, std::map<int32_t, double>& acc)
+{
+  const int n = P + 1;
+  std::vector<double> pts(n), wts(n);
+  gll_points_weights(n, pts.data(), wts.data());
+  for (int64_t f = 0; f < facets.count; ++f) {
+    const int64_t c = facets.cell[f];
+    const int axis = facets.axis[f], side = facets.side[f];
+    WF_REQUIRE(c >= 0 && c < ncells && axis >= 0 && axis < 3 && (side == 0 || side == 1), "facet mass: bad facet");
+    const int ta = axis == 0 ? 1 : 0, tb = axis == 2 ? 1 : 2;
+    double xv[8][3];
+    for (int q = 0; q < 8; ++q) {
+      const int64_t v = vertex(c, q);
+      WF_REQUIRE(v >= 0, "facet mass: vertex index out of range");
+      for (int d = 0; d < 3; ++d) xv[q][d] = xverts[(size_t)v * 3 + d];
+    }
+    for (int b = 0; b < n; ++b)
+      for (int a = 0; a < n; ++a) {
+        double X[3];
+        X[axis] = (double)side;
+        X[ta] = pts[a];
+        X[tb] = pts[b];
+        double t0[3], t1[3];
+        q1_tangent(xv, X, ta, t0);
+        q1_tangent(xv, X, tb, t1);
+        const double cx = t0[1] * t1[2] - t0[2] * t1[1], cy = t0[2] * t1[0] - t0[0] * t1[2], cz = t0[0] * t1[1] - t0[1] * t1[0];
+        const double ds = std::sqrt(cx * cx + cy * cy + cz * cz) * wts[a] * wts[b];
+        int l[3];
+        l[axis] = side * P;
+        l[ta] = a;
+        l[tb] = b;
+        acc[dof(c, l)] += cell_weight ? ds * cell_weight[c] : ds;
+      }
+  }
+  return WF_OK;
+}
+
 extern "C" {
 
 // fem::create_functionspace(mesh, Lagrange(hexahedron, degree, gll_warped)) for an arbitrary
@@ -256,39 +297,15 @@ int wf_fs_facet_mass_weighted(int degree, int64_t nverts, const double* h_xverts
   WF_REQUIRE(degree >= 1 && degree <= kMaxDegree && nout, "wf_fs_facet_mass: bad argument");
   WF_REQUIRE(nfacets == 0 || (h_xverts && h_cells && h_dofmap && h_cell && h_axis && h_side && h_idx && h_mass),
              "wf_fs_facet_mass: null array");
-  const int P = degree, n = P + 1, nd = n * n * n;
-  std::vector<double> pts(n), wts(n);
-  gll_points_weights(n, pts.data(), wts.data());
+  const int n = degree + 1, nd = n * n * n;
+  auto vertex = [&](int64_t c, int q) -> int64_t {
+    const int32_t v = h_cells[c * 8 + q];
+    return v >= 0 && v < nverts ? v : -1;
+  };
+  auto dof = [&](int64_t c, const int* l) { return h_dofmap[c * nd + l[0] + n * (l[1] + n * l[2])]; };
   std::map<int32_t, double> acc;
-  for (int64_t f = 0; f < nfacets; ++f) {
-    const int64_t c = h_cell[f];
-    const int axis = h_axis[f], side = h_side[f];
-    WF_REQUIRE(c >= 0 && c < ncells && axis >= 0 && axis < 3 && (side == 0 || side == 1), "wf_fs_facet_mass: bad facet");
-    const int ta = axis == 0 ? 1 : 0, tb = axis == 2 ? 1 : 2;
-    double xv[8][3];
-    for (int q = 0; q < 8; ++q) {
-      const int32_t v = h_cells[c * 8 + q];
-      WF_REQUIRE(v >= 0 && v < nverts, "wf_fs_facet_mass: vertex index out of range");
-      for (int d = 0; d < 3; ++d) xv[q][d] = h_xverts[(size_t)v * 3 + d];
-    }
-    for (int b = 0; b < n; ++b)
-      for (int a = 0; a < n; ++a) {
-        double X[3];
-        X[axis] = (double)side;
-        X[ta] = pts[a];
-        X[tb] = pts[b];
-        double t0[3], t1[3];
-        q1_tangent(xv, X, ta, t0);
-        q1_tangent(xv, X, tb, t1);
-        const double cx = t0[1] * t1[2] - t0[2] * t1[1], cy = t0[2] * t1[0] - t0[0] * t1[2], cz = t0[0] * t1[1] - t0[1] * t1[0];
-        const double ds = std::sqrt(cx * cx + cy * cy + cz * cz) * wts[a] * wts[b];
-        int l[3];
-        l[axis] = side * P;
-        l[ta] = a;
-        l[tb] = b;
-        acc[h_dofmap[c * nd + l[0] + n * (l[1] + n * l[2])]] += h_cell_weight ? ds * h_cell_weight[c] : ds;
-      }
-  }
+  if (int rc = facet_mass(degree, FacetList{nfacets, h_cell, h_axis, h_side}, ncells, h_xverts, vertex, dof, h_cell_weight, acc))
+    return rc;
   int64_t k = 0;
   for (const auto& kv : acc) {
     h_idx[k] = kv.first;

@@ -23,27 +23,20 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+import ctypes
+
 import numpy as np
 
-from .box import BoxMesh, FunctionSpace, IndexMap, create_box, create_functionspace
+from ._lib import BoxPartitionInfo, _ip, check, lib
+from .box import BoxMesh, FunctionSpace, IndexMap, _int3, create_box, create_functionspace
 
 
 def decompose3d(nproc: int):
     """Split nproc into px >= py >= pz, as balanced as possible
-    (1 -> 1x1x1, 2 -> 2x1x1, 4 -> 2x2x1, 8 -> 2x2x2; cf. demo/gpu_cg/mesh.hpp:37-48)."""
-    best = None
-    for a in range(1, nproc + 1):
-        if nproc % a:
-            continue
-        for b in range(1, nproc // a + 1):
-            if (nproc // a) % b:
-                continue
-            c = nproc // a // b
-            dims = tuple(sorted((a, b, c), reverse=True))
-            score = (dims[0] - dims[2], dims[0])
-            if best is None or score < best[0]:
-                best = (score, dims)
-    return best[1]
+    (1 -> 1x1x1, 2 -> 2x1x1, 4 -> 2x2x1, 8 -> 2x2x2; cf. demo/gpu_cg/mesh.hpp:37-48): wf_decompose3d."""
+    procs = (ctypes.c_int * 3)()
+    check(lib().wf_decompose3d(int(nproc), procs))
+    return tuple(procs)
 
 
 def rank_coords(rank: int, procs):
@@ -72,11 +65,8 @@ class BoxPartition:
     send_fwd: dict = field(default_factory=dict)   # owned dofs the neighbour holds as ghosts
     recv_fwd: dict = field(default_factory=dict)   # my ghosts owned by the neighbour
     periodic: tuple = (False, False, False)        # axes whose upper face is identified with the lower one
-
-    @property
-    def num_owned(self) -> int:
-        NX, NY, NZ = self.V.lattice
-        return (NX - self.owned_lo[0]) * (NY - self.owned_lo[1]) * (NZ - self.owned_lo[2])
+    num_owned: int = 0
+    face_tag: tuple = (0,) * 6                     # cfg1 tag of local face 2*axis + side, 0 = none (boundary_tags)
 
     def owned_mask(self) -> np.ndarray:
         NX, NY, NZ = self.V.lattice
@@ -90,15 +80,6 @@ class BoxPartition:
         return m.reshape(-1)
 
 
-def _axis_range(kind: int, lo: int, hi: int):
-    """kind -1: the lower plane (index 0); +1: the upper plane (index hi); 0: the owned range."""
-    if kind < 0:
-        return np.array([0])
-    if kind > 0:
-        return np.array([hi])
-    return np.arange(lo, hi + 1)
-
-
 def create_distributed_box(n, degree: int, nproc: int, rank: int, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0),
                            perturb: float = 0.0, seed: int = 42, build_dofmap: bool = False,
                            periodic=(False, False, False)) -> BoxPartition:
@@ -107,66 +88,38 @@ def create_distributed_box(n, degree: int, nproc: int, rank: int, lo=(0.0, 0.0, 
     periodic[a] identifies the upper face of axis a with the lower one: the lower
     plane of EVERY rank is then a ghost plane and the neighbour relation wraps
     around, so a rank can be its own neighbour (with one rank per axis the exchange
-    is a send/recv to self -- used to run the RCCL path on a single GPU)."""
+    is a send/recv to self -- used to run the RCCL path on a single GPU).
+    The partition, the ownership and the index lists are wf_box_partition's."""
     if np.isscalar(n):
         n = (int(n),) * 3
-    procs = decompose3d(nproc)
-    c = rank_coords(rank, procs)
-    p = degree
+    periodic = tuple(bool(v) for v in periodic)
+    info = BoxPartitionInfo()
+    head = (_int3(n), int(degree), int(nproc), int(rank), (ctypes.c_int * 3)(*periodic), ctypes.byref(info))
+    check(lib().wf_box_partition(*head, *[None] * 6))
+    snb, rnb = np.zeros(7, dtype=np.intc), np.zeros(7, dtype=np.intc)
+    soff, roff = np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.int32)
+    sidx, ridx = np.empty(info.num_send_indices, dtype=np.int32), np.empty(info.num_recv_indices, dtype=np.int32)
+    nbp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    check(lib().wf_box_partition(*head, nbp(snb), _ip(soff), _ip(sidx), nbp(rnb), _ip(roff), _ip(ridx)))
+    procs, c = tuple(info.procs), tuple(info.coords)
     gn = tuple(procs[a] * n[a] for a in range(3))
     # local mesh = the rank's slab of the global vertex lattice (global coordinates;
     # the perturbation is drawn on the global mesh so that ranks agree on shared vertices)
-    gmesh_x = None
-    if perturb > 0.0:
-        gmesh_x = create_box(gn, lo, hi, perturb, seed).x.reshape(gn[2] + 1, gn[1] + 1, gn[0] + 1, 3)
     h = [(hi[a] - lo[a]) / gn[a] for a in range(3)]
     llo = tuple(lo[a] + h[a] * n[a] * c[a] for a in range(3))
     lhi = tuple(lo[a] + h[a] * n[a] * (c[a] + 1) for a in range(3))
     mesh = create_box(n, llo, lhi)
-    if gmesh_x is not None:
+    if perturb > 0.0:
+        gmesh_x = create_box(gn, lo, hi, perturb, seed).x.reshape(gn[2] + 1, gn[1] + 1, gn[0] + 1, 3)
         sl = tuple(slice(c[a] * n[a], (c[a] + 1) * n[a] + 1) for a in range(3))
         mesh.x = np.ascontiguousarray(gmesh_x[sl[2], sl[1], sl[0]].reshape(-1, 3))
-    V = create_functionspace(mesh, p, build_dofmap=build_dofmap)
-    NX, NY, NZ = V.lattice
-    periodic = tuple(bool(v) for v in periodic)
-    owned_lo = tuple(1 if (c[a] > 0 or periodic[a]) else 0 for a in range(3))
-    part = BoxPartition(procs, rank, c, tuple(n), p, mesh, V,
-                        size_global=int(np.prod([p * gn[a] + (0 if periodic[a] else 1) for a in range(3)])),
-                        owned_lo=owned_lo, periodic=periodic)
-    V.index_map = IndexMap(NX * NY * NZ, 0, part.size_global)   # whole local lattice; see module docstring
-    hi_idx = (NX - 1, NY - 1, NZ - 1)
-
-    def lattice_indices(kinds):
-        ix = _axis_range(kinds[0], owned_lo[0], hi_idx[0])
-        iy = _axis_range(kinds[1], owned_lo[1], hi_idx[1])
-        iz = _axis_range(kinds[2], owned_lo[2], hi_idx[2])
-        K, J, I = np.meshgrid(iz, iy, ix, indexing="ij")
-        return (I + NX * (J + NY * K)).reshape(-1).astype(np.int32)
-
-    for dx in (0, 1):
-        for dy in (0, 1):
-            for dz in (0, 1):
-                if (dx, dy, dz) == (0, 0, 0):
-                    continue
-                d = (dx, dy, dz)
-                wrap = lambda q: tuple(q[a] % procs[a] if periodic[a] else q[a] for a in range(3))
-                # upper neighbour +d holds my upper plane(s) as ghosts
-                up = wrap(tuple(c[a] + d[a] for a in range(3)))
-                if all(0 <= up[a] < procs[a] for a in range(3)):
-                    _append(part.send_fwd, coords_rank(up, procs), lattice_indices(d))
-                # lower neighbour -d owns my lower plane(s)
-                dn = wrap(tuple(c[a] - d[a] for a in range(3)))
-                if all(0 <= dn[a] < procs[a] for a in range(3)):
-                    _append(part.recv_fwd, coords_rank(dn, procs), lattice_indices(tuple(-v for v in d)))
-    return part
-
-
-def _append(lists: dict, nb: int, idx: np.ndarray):
-    """Several directions can lead to the same neighbour on a periodic partition
-    (always to the rank itself when an axis has one rank): their segments are
-    concatenated in direction order, which is the same on the sending and the
-    receiving side."""
-    lists[nb] = np.concatenate([lists[nb], idx]) if nb in lists else idx
+    V = create_functionspace(mesh, degree, build_dofmap=build_dofmap)
+    V.index_map = IndexMap(V.ndofs, 0, info.size_global)   # whole local lattice; see module docstring
+    segments = lambda nb, off, idx, k: {int(nb[i]): idx[off[i]:off[i + 1]].copy() for i in range(k)}
+    return BoxPartition(procs, rank, c, tuple(n), degree, mesh, V, size_global=info.size_global,
+                        owned_lo=tuple(info.owned_lo), send_fwd=segments(snb, soff, sidx, info.num_send_neighbors),
+                        recv_fwd=segments(rnb, roff, ridx, info.num_recv_neighbors), periodic=periodic,
+                        num_owned=info.num_owned, face_tag=tuple(info.face_tag))
 
 
 def boundary_tags(part: BoxPartition) -> dict:
@@ -174,15 +127,7 @@ def boundary_tags(part: BoxPartition) -> dict:
     (SURVEY 8d): global face x = lo -> tag 1 (Gamma_1), every other global face
     -> tag 2 (Gamma_2); interfaces between ranks carry no tag.
     Key = local face 2*axis + side."""
-    tags = {}
-    for axis in range(3):
-        if part.periodic[axis]:
-            continue
-        if part.coords[axis] == 0:
-            tags[2 * axis] = 1 if axis == 0 else 2
-        if part.coords[axis] == part.procs[axis] - 1:
-            tags[2 * axis + 1] = 2
-    return tags
+    return {f: t for f, t in enumerate(part.face_tag) if t}
 
 
 class HipKernels:
@@ -261,7 +206,7 @@ class VectorUpdater:
     # -- native transport (csrc/comm.hip) ----------------------------------------
     def _init_native(self, comm):
         import ctypes
-        from ctypes import POINTER, c_int, c_int32, c_void_p
+        from ctypes import POINTER, c_int, c_void_p
 
         from . import _lib
         from .comm import Comm
@@ -276,12 +221,11 @@ class VectorUpdater:
         rnb = np.asarray(self.recv_neighbors, dtype=np.intc)
         soff = np.concatenate([[0], np.cumsum([self.part.send_fwd[r].size for r in self.send_neighbors])]).astype(np.int32)
         roff = np.concatenate([[0], np.cumsum([self.part.recv_fwd[r].size for r in self.recv_neighbors])]).astype(np.int32)
-        ip = lambda a: a.ctypes.data_as(POINTER(c_int32))
         d.num_send_neighbors, d.num_recv_neighbors = len(snb), len(rnb)
         d.send_neighbors = snb.ctypes.data_as(POINTER(c_int))
         d.recv_neighbors = rnb.ctypes.data_as(POINTER(c_int))
-        d.send_offsets, d.recv_offsets = ip(soff), ip(roff)
-        d.send_indices, d.ghost_positions = ip(self.h_indices), ip(self.h_ghost_pos)
+        d.send_offsets, d.recv_offsets = _ip(soff), _ip(roff)
+        d.send_indices, d.ghost_positions = _ip(self.h_indices), _ip(self.h_ghost_pos)
         d.flags = _lib.WF_UPDATER_DEFAULT
         self._h = c_void_p()
         _lib.check(_lib.lib().wf_updater_create(self.comm._h if self.comm is not None else None, ctypes.byref(d),

@@ -16,12 +16,16 @@ applied by the owner of each boundary dof with the fully assembled facet mass
 (distributed.owned_boundary), so no ghost value of v is ever read."""
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import la
+from ._lib import _dp, _ip, check, lib
+from .box import _int3
+from .mesh_io import cfl_time_step  # noqa: F401  (demo/cpu_planar3d/main.cpp:48-66: one function for box and file meshes)
 from .operators import MassOperatorLumped, StiffnessOperator
 
 
@@ -29,63 +33,21 @@ def facet_lumped_mass(V, tag_of_face, tag: int, cell_weight=None):
     """Collocated facet mass m_Gamma[i] = sum_facets w_q |J_facet| for the box
     faces carrying `tag` (tag_of_face maps local face 2*axis+side -> tag).
     cell_weight [ncells] (or None): every facet's contribution times the value of its cell.
-    Host-side setup (numpy); returns (dof indices int32, masses float64)."""
+    Host-side setup (wf_box_facet_mass: the loop of mesh_io.facet_lumped_mass on the implicit box numbering);
+    returns (dof indices int32 ascending, masses float64)."""
+    mesh = V.mesh
     if cell_weight is not None:
         cell_weight = np.ascontiguousarray(cell_weight, dtype=np.float64).reshape(-1)
-        if cell_weight.size != V.mesh.ncells:
-            raise ValueError(f"cell_weight has {cell_weight.size} entries, the mesh has {V.mesh.ncells} cells")
-    from .operators import tabulate_gll
-    mesh = V.mesh
-    p = V.degree
-    n = p + 1
-    pts, w, _ = tabulate_gll(p)
-    nx, ny, nz = mesh.n
-    NX, NY, NZ = V.lattice
-    cz, cy, cx = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
-    cid = cx + nx * (cy + ny * cz)
-    m = {}
-    acc = np.zeros(NX * NY * NZ)
-    touched = np.zeros(NX * NY * NZ, dtype=bool)
-    for axis, (cc, nn_) in enumerate(((cx, nx), (cy, ny), (cz, nz))):
-        for side in (0, 1):
-            if tag_of_face.get(2 * axis + side) != tag:
-                continue
-            cells = cid[cc == (0 if side == 0 else nn_ - 1)].reshape(-1)
-            ta, tb = [d for d in range(3) if d != axis]
-            bb, aa = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
-            aa, bb = aa.reshape(-1), bb.reshape(-1)
-            X = np.zeros((n * n, 3))
-            X[:, axis] = float(side)
-            X[:, ta] = pts[aa]
-            X[:, tb] = pts[bb]
-            # Q1 derivative table, vertex v = a + 2b + 4c
-            dphi = np.zeros((3, n * n, 8))
-            for v in range(8):
-                bits = (v & 1, (v >> 1) & 1, (v >> 2) & 1)
-                f = [X[:, d] if bits[d] else 1.0 - X[:, d] for d in range(3)]
-                g = [np.ones(n * n) if bits[d] else -np.ones(n * n) for d in range(3)]
-                dphi[0, :, v] = g[0] * f[1] * f[2]
-                dphi[1, :, v] = f[0] * g[1] * f[2]
-                dphi[2, :, v] = f[0] * f[1] * g[2]
-            xc = mesh.x[mesh.geom_dofmap[cells]]
-            J = np.einsum("fvi,jqv->fqij", xc, dphi)
-            nrm = np.linalg.norm(np.cross(J[:, :, :, ta], J[:, :, :, tb]), axis=2)
-            wq = (w[aa] * w[bb])[None, :] * nrm
-            if cell_weight is not None:
-                wq = wq * cell_weight[cells][:, None]
-            loc = np.zeros((n * n, 3), dtype=np.int64)
-            loc[:, axis] = side * p
-            loc[:, ta] = aa
-            loc[:, tb] = bb
-            ccx, ccy, ccz = cells % nx, (cells // nx) % ny, cells // (nx * ny)
-            I = p * ccx[:, None] + loc[None, :, 0]
-            Jd = p * ccy[:, None] + loc[None, :, 1]
-            K = p * ccz[:, None] + loc[None, :, 2]
-            dofs = (I + NX * (Jd + NY * K)).reshape(-1)
-            np.add.at(acc, dofs, wq.reshape(-1))
-            touched[dofs] = True
-    idx = np.nonzero(touched)[0].astype(np.int32)
-    return idx, acc[idx]
+        if cell_weight.size != mesh.ncells:
+            raise ValueError(f"cell_weight has {cell_weight.size} entries, the mesh has {mesh.ncells} cells")
+    x = np.ascontiguousarray(mesh.x, dtype=np.float64)
+    face_tag = (ctypes.c_int * 6)(*(int(tag_of_face.get(f, 0)) for f in range(6)))
+    nout = ctypes.c_int64(0)
+    args = (V.degree, _int3(mesh.n), _dp(x), face_tag, int(tag), _dp(cell_weight), ctypes.byref(nout))
+    check(lib().wf_box_facet_mass(*args, None, None))
+    idx, m = np.empty(nout.value, dtype=np.int32), np.empty(nout.value)
+    check(lib().wf_box_facet_mass(*args, _ip(idx), _dp(m)))
+    return idx, m
 
 
 class LinearGLLOpt:
@@ -352,14 +314,3 @@ def _rk4_fused(self, startTime: float, finalTime: float, timeStep: float, max_st
 
 
 LinearGLLOpt.rk4_fused = _rk4_fused
-
-
-def cfl_time_step(mesh, degree: int, c0: float, freq: float, CFL: float = 0.5):
-    """demo/cpu_planar3d/main.cpp:48-66."""
-    xc = mesh.x[mesh.geom_dofmap]
-    d = np.linalg.norm(xc[:, :, None, :] - xc[:, None, :, :], axis=3)
-    h = d.reshape(mesh.ncells, -1).max(axis=1).min()
-    dt = CFL * h / (c0 * degree ** 2)
-    period = 1.0 / freq
-    stepPerPeriod = int(period / dt + 1)
-    return period / stepPerPeriod, stepPerPeriod

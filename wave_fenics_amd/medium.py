@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .mesh_io import whole_steps
+
 
 class Medium:
     """Medium(c, rho=None): sound speed and density per cell ([ncells] each; rho = None is rho = 1).  Both must be
@@ -71,6 +73,4 @@ def cfl_time_step(mesh, degree: int, medium: Medium, freq: float, CFL: float = 0
         raise ValueError(f"medium has {medium.ncells} cells, the mesh has {mesh.ncells}")
     # per cell the expression of the homogeneous function, so that a uniform medium gives its dt bit for bit
     dt = (CFL * cell_diameters(mesh) / (medium.c * degree ** 2)).min()
-    period = 1.0 / freq
-    stepPerPeriod = int(period / dt + 1)
-    return period / stepPerPeriod, stepPerPeriod
+    return whole_steps(dt, freq)

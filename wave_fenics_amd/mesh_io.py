@@ -10,21 +10,13 @@ by parity with the box meshes, not by a reference file ("parity unpinned")."""
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, c_double, c_int32, c_int64, c_void_p
+from ctypes import c_double, c_int64, c_void_p
 from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import _dp, _ip, check, lib
 from .box import BoxMesh, FunctionSpace, IndexMap
-
-
-def _dp(a):
-    return a.ctypes.data_as(POINTER(c_double))
-
-
-def _ip(a):
-    return a.ctypes.data_as(POINTER(c_int32))
 
 
 @dataclass
@@ -145,16 +137,22 @@ def boundary_sets(V: FunctionSpace, tags: MeshTags, values=(1, 2), cell_weight=N
     return tuple(facet_lumped_mass(V, locate_facets(V.mesh, tags, v), cell_weight) for v in values)
 
 
+def whole_steps(dt: float, freq: float):
+    """The time step rounded down to a whole number of steps per source period (demo/cpu_planar3d/main.cpp:60-66):
+    (period / steps, steps) with steps = int(period / dt + 1)."""
+    period = 1.0 / freq
+    spp = int(period / dt + 1)
+    return period / spp, spp
+
+
 def cfl_time_step(mesh, degree: int, c0: float, freq: float, CFL: float = 0.5):
-    """demo/cpu_planar3d/main.cpp:48-66 (mesh::h = largest vertex distance of a cell)."""
+    """demo/cpu_planar3d/main.cpp:48-66 (mesh::h = largest vertex distance of a cell, the smallest over the cells:
+    wf_fs_min_cell_diameter) for box and file meshes alike."""
     x = np.ascontiguousarray(mesh.x, dtype=np.float64)
     cells = np.ascontiguousarray(mesh.geom_dofmap, dtype=np.int32)
     h = c_double(0.0)
     check(lib().wf_fs_min_cell_diameter(x.shape[0], _dp(x), cells.shape[0], _ip(cells), ctypes.byref(h)))
-    dt = CFL * h.value / (c0 * degree ** 2)
-    period = 1.0 / freq
-    spp = int(period / dt + 1)
-    return period / spp, spp
+    return whole_steps(CFL * h.value / (c0 * degree ** 2), freq)
 
 
 # ---------------------------------------------------------------------------

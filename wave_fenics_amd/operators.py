@@ -12,12 +12,12 @@ WavehipError (the reference throws std::runtime_error)."""
 from __future__ import annotations
 
 import ctypes
-from ctypes import POINTER, c_double, c_int32, c_void_p
+from ctypes import c_double, c_int32, c_void_p
 
 import numpy as np
 
 from . import _lib
-from ._lib import OpDesc, OpInfo, check, lib
+from ._lib import OpDesc, OpInfo, _dp, _ip, check, lib
 from .box import FunctionSpace
 
 
@@ -48,10 +48,6 @@ def _check_vec(t, n: int, name: str):
             raise _lib.WavehipError(f"{name}: vector has {t.numel()} entries, operator needs {n}")
 
 
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(POINTER(c_double))
-
-
 def _cell_coeff(cell_coeff, ncells: int):
     """A cell coefficient argument as the contiguous float64 array [ncells] the C ABI takes, or None."""
     if cell_coeff is None:
@@ -60,10 +56,6 @@ def _cell_coeff(cell_coeff, ncells: int):
     if a.size != ncells:
         raise _lib.WavehipError(f"cell_coeff has {a.size} entries, the mesh has {ncells} cells")
     return a
-
-
-def _ip(a):
-    return None if a is None else a.ctypes.data_as(POINTER(c_int32))
 
 
 # ---------------------------------------------------------------------------
