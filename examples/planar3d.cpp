@@ -9,6 +9,7 @@
 //   planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]]
 //            [--size N] [--degree P] [--cfl C] [--steps S] [--length L] [--dump FILE]
 //            [--periodic xyz] [--reference-order] [--markers] [--geometry auto|per_point|per_cell]
+//            [--scheme rk4|leapfrog]
 //
 // One process per GPU: with WORLD_SIZE > 1 in the environment (RANK, LOCAL_RANK,
 // MASTER_PORT as torchrun exports them) --size is the number of cells per edge PER
@@ -18,6 +19,8 @@
 // --periodic identifies opposite faces of the named axes (a single rank is then
 // its own RCCL neighbour).  --reference-order runs LinearGLLOpt::rk4, the
 // reference's unfused sequence of vector operations, instead of rk4_fused.
+// --scheme leapfrog runs LinearGLLOpt::leapfrog, the second-order central-difference scheme (one stiffness apply per
+// step, constant step) instead of RK4; rk4 is the default.
 // --dump writes u_n then v_n of this rank (float64, local lattice order).
 // --geometry (with --mesh): how the stiffness operator stores its geometry (wf_tuning.geometry).  per_cell asks for one
 // G_c per cell -- degrees 1 to 4, every cell affine, else an error -- and prints what was built; auto is the default.
@@ -37,7 +40,7 @@ int main(int argc, char* argv[])
   const char* dump = nullptr;
   const char *mesh_file = nullptr, *grid_name = "planar3d", *tags_name = "planar3d_boundaries";
   std::array<bool, 3> periodic{false, false, false};
-  bool reference_order = false, markers = false;
+  bool reference_order = false, markers = false, leapfrog = false;
   int geometry = WF_GEOMETRY_AUTO;
   for (int i = 1; i < argc; ++i) {
     auto is = [&](const char* f) { return std::strcmp(argv[i], f) == 0 && i + 1 < argc; };
@@ -54,6 +57,8 @@ int main(int argc, char* argv[])
     else if (is("--geometry") && std::strcmp(argv[i + 1], "auto") == 0) ++i, geometry = WF_GEOMETRY_AUTO;
     else if (is("--geometry") && std::strcmp(argv[i + 1], "per_point") == 0) ++i, geometry = WF_GEOMETRY_PER_POINT;
     else if (is("--geometry") && std::strcmp(argv[i + 1], "per_cell") == 0) ++i, geometry = WF_GEOMETRY_PER_CELL;
+    else if (is("--scheme") && std::strcmp(argv[i + 1], "rk4") == 0) ++i, leapfrog = false;
+    else if (is("--scheme") && std::strcmp(argv[i + 1], "leapfrog") == 0) ++i, leapfrog = true;
     else if (is("--periodic")) {
       for (const char* c = argv[++i]; *c; ++c)
         if (*c >= 'x' && *c <= 'z') periodic[*c - 'x'] = true;
@@ -61,7 +66,7 @@ int main(int argc, char* argv[])
     else {
       std::cerr << "usage: planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]] [--size N] [--degree P] [--cfl C]"
                    " [--steps S] [--length L] [--dump FILE] [--periodic xyz] [--reference-order] [--markers]"
-                   " [--geometry auto|per_point|per_cell]\n";
+                   " [--geometry auto|per_point|per_cell] [--scheme rk4|leapfrog]\n";
       return 2;
     }
   }
@@ -106,7 +111,9 @@ int main(int argc, char* argv[])
       std::cout << "Degrees of freedom: " << V.ndofs << std::endl;
       eqn.init();
       auto t0 = std::chrono::steady_clock::now();
-      int steps = reference_order ? eqn.rk4(startTime, finalTime, timeStepSize) : eqn.rk4_fused(startTime, finalTime, timeStepSize);
+      int steps = leapfrog          ? eqn.leapfrog(startTime, finalTime, timeStepSize)
+                    : reference_order ? eqn.rk4(startTime, finalTime, timeStepSize)
+                                      : eqn.rk4_fused(startTime, finalTime, timeStepSize);
       wavehip::check(wf_sync(nullptr));
       double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       std::cout << "Steps taken: " << steps << std::endl;
@@ -155,7 +162,9 @@ int main(int argc, char* argv[])
     eqn.init();
     if (comm) comm->barrier();
     auto t0 = std::chrono::steady_clock::now();
-    int steps = reference_order ? eqn.rk4(startTime, finalTime, timeStepSize) : eqn.rk4_fused(startTime, finalTime, timeStepSize);
+    int steps = leapfrog          ? eqn.leapfrog(startTime, finalTime, timeStepSize)
+                  : reference_order ? eqn.rk4(startTime, finalTime, timeStepSize)
+                                    : eqn.rk4_fused(startTime, finalTime, timeStepSize);
     if (comm) comm->barrier();
     double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (rank == 0) {

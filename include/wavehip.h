@@ -559,6 +559,25 @@ int wf_rk4_stage_bc(int64_t n, double bdt, double adt_next, int has_next, double
                     const double* d_u0, const double* d_v0, double* d_un, double* d_vn_next, const wf_boundary* bc,
                     double s1_next, double s2, void* stream);
 
+/* Leapfrog (central difference, explicit Newmark beta = 0, gamma = 1/2) step of  m u'' + d u' - K u = s1 c1  with the
+ * lumped mass m and the diagonal absorbing term d = -s2 c2 taken centred (implicit, at no cost: it is diagonal).
+ * One stiffness apply and this one pass per step.  On entry d_b holds K u (the apply accumulated onto zeros, sign
+ * convention of f1: u'' = b / m); with dt2 = dt*dt and hdt = (-s2)*(0.5*dt) computed by the host, per dof
+ *   outside both boundary sets, and every dof of wf_leapfrog_step:
+ *       a = b/m;  u_next = dt2*a + (2*u - u_prev)
+ *   dof r of the plan's union set (c1, c2 the plan's facet masses, 0 where the dof is in one set only):
+ *       h = hdt*c2[r];  u_next = (dt2*(b + s1*c1[r]) + ((2*m)*u - (m - h)*u_prev)) / (m + h)
+ *   d_v non-null:  v = (u_next - u_prev) / (2*dt), the central velocity at the time of u
+ *   b = +0.0 everywhere, ready for the next apply.
+ * The expressions are evaluated as written (no fused multiply-add), so every compiled form gives the same bits.
+ * d_u_next may be d_u_prev (in place); it must not overlap d_u, d_b or d_m, and d_v must not overlap any other
+ * vector.  Refused (WF_ERR_INVALID, nothing written): a forbidden overlap, s2 > 0, dt <= 0, a plan built for another
+ * n, a null vector or plan.  n <= 0 is a no-op.  48 B/dof of HBM traffic, 56 with d_v. */
+int wf_leapfrog_step(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                     double* d_u_next, double* d_v, void* stream);
+int wf_leapfrog_step_bc(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                        double* d_u_next, double* d_v, const wf_boundary* bc, double s1, double s2, void* stream);
+
 /* ---- a14: ghost exchange over RCCL ----------------------------------------
  * demo/gpu_scatter_mpi/VectorUpdater.hpp:21-230 (GPU pack + CUDA-aware MPI per
  * IndexMap neighbour) and la::Vector::scatter_fwd / scatter_rev(add) of

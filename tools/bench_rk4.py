@@ -6,7 +6,9 @@ ghost exchange, LinearGLLOpt.rk4_fused -- launched like bench.py:
   python tools/bench_rk4.py [--steps K] [--size N]                      (1 GPU)
   python -m torch.distributed.run --nproc-per-node N tools/bench_rk4.py (N GPUs)
 
-Prints one JSON line: ms per RK4 time step and dof-stages/s over all ranks."""
+Prints one JSON line: ms per RK4 time step and dof-stages/s over all ranks.
+--scheme leapfrog times LinearGLLOpt.leapfrog at the same step instead (the same keys, per leapfrog step; the timed
+window includes the scheme's start-up and finish, two extra stiffness applies)."""
 import argparse
 import json
 import os
@@ -24,6 +26,8 @@ def main():
     ap.add_argument("--size", type=int, default=54)
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--unfused", action="store_true")
+    ap.add_argument("--scheme", choices=["rk4", "leapfrog"], default="rk4",
+                    help="leapfrog: LinearGLLOpt.leapfrog at the same step (one stiffness apply per step; ms_per_rk4_step is then ms per leapfrog step)")
     ap.add_argument("--periodic", default="", help="axes identified with their opposite face (one rank: RCCL exchange with itself)")
     args = ap.parse_args()
     import torch
@@ -53,7 +57,8 @@ def main():
     eqn = LinearGLLOpt(part.V, p, 1500.0, 0.5e6, 6e4, updater=updater, tags=boundary_tags(part), device=dev)
     dt, _ = cfl_time_step(part.mesh, p, 1500.0, 0.5e6, CFL=0.25)
     eqn.init()
-    run = eqn.rk4 if args.unfused else eqn.rk4_fused
+    run = eqn.leapfrog if args.scheme == "leapfrog" else eqn.rk4 if args.unfused else eqn.rk4_fused
+    applies = 1.0 if args.scheme == "leapfrog" else 4.0
 
     def sync():
         if world > 1:
@@ -73,7 +78,7 @@ def main():
     ok = bool(torch.isfinite(eqn.u_n).all())
     if rank == 0:
         print(json.dumps({"metric": "RK4 time step, P4 hex box, full loop (4 x [ghost fwd, K, boundary, ghost rev, vector algebra])",
-                          "ms_per_rk4_step": el / args.steps * 1e3, "dof_stages_per_s": 4.0 * part.size_global * args.steps / el,
+                          "ms_per_rk4_step": el / args.steps * 1e3, "dof_stages_per_s": applies * part.size_global * args.steps / el, "scheme": args.scheme,
                           "n_gpus": world, "global_dofs": part.size_global, "cells_per_gpu": part.mesh.ncells,
                           "fused": not args.unfused, "periodic": args.periodic,
                           "exchange": updater.transport if updater is not None else None, "finite": ok, "scaling": "weak"}), flush=True)

@@ -179,6 +179,8 @@ SIGNATURES = {
     "wf_boundary_destroy": (c_int, [c_void_p]),
     "wf_boundary_apply_plan": (c_int, [c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "wf_rk4_stage_bc": (c_int, [c_int64, c_double, c_double, c_int] + [c_void_p] * 11 + [c_void_p, c_double, c_double, c_void_p]),
+    "wf_leapfrog_step": (c_int, [c_int64, c_double] + [c_void_p] * 7),
+    "wf_leapfrog_step_bc": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
     "wf_comm_unique_id": (c_int, [c_char_p]),
     "wf_comm_create": (c_int, [c_char_p, c_int, c_int, POINTER(c_void_p)]),
     "wf_comm_rendezvous_file": (c_int, [c_char_p, c_int, c_double, c_char_p]),

@@ -318,6 +318,125 @@ __global__ void __launch_bounds__(256) k_rk4_stage(int64_t nvec, int ntail, Stag
     stage_entry<1, HAS_NEXT, false, BC>(a, threadIdx.x, (int64_t)VEC * nvec);
 }
 
+// One step of the central-difference (leapfrog, explicit Newmark beta = 0, gamma = 1/2) scheme on
+// m u'' + d u' - K u = s1 c1 with the diagonal absorbing term d = -s2 c2 taken centred, in one pass after the
+// stiffness apply that left K u in b:
+//   dof outside the boundary sets:  a = b / m ; u_next = dt2 a + (2 u - u_prev)
+//   dof r of the union set:         h = hdt c2[r] ; u_next = (dt2 (b + s1 c1[r]) + ((2 m) u - (m - h) u_prev)) / (m + h)
+//   v = (u_next - u_prev) / (2 dt)  (HAS_V) ; b = +0.0
+// dt2 = dt^2, hdt = -s2 dt / 2, tdt = 2 dt from the host.  u_next may alias u_prev (every thread reads its entry
+// before it writes it).  HBM traffic per dof: b, m, u, u_prev read, u_next, b written = 48 B (56 B with v).
+// u_next and b are what the next stiffness apply touches and are stored plainly, u is read plainly (the apply just
+// read it); b, m, u_prev (and v) bypass the caches as in the stage kernel.  The boundary sets are the stage kernel's
+// plan: bitmap word per 64 dofs fetched once per wave, whole waves without a boundary dof skip the block.
+struct LeapfrogArgs {
+  double dt2, hdt, tdt;
+  double* b;
+  const double* m;
+  const double* u;
+  const double* up;
+  double* un;
+  double* v;
+  BoundaryPlanDev bc;   // s1 = the coefficient of the Gamma_1 term at the current time; s2 is folded into hdt
+};
+
+// the two update expressions, evaluated as written (no contraction: every compiled form gives the same bits)
+__device__ __forceinline__ double leapfrog_plain(double b, double m, double u, double up, double dt2)
+{
+#pragma clang fp contract(off)
+  const double a = b / m;
+  return dt2 * a + (2.0 * u - up);
+}
+__device__ __forceinline__ double leapfrog_boundary(double b, double m, double u, double up, double dt2, double hdt, double s1,
+                                                    double c1, double c2)
+{
+#pragma clang fp contract(off)
+  const double h = hdt * c2;
+  return (dt2 * (b + s1 * c1) + ((2.0 * m) * u - (m - h) * up)) / (m + h);
+}
+
+template <int VEC, bool NT, bool BC, bool HAS_V>
+__device__ __forceinline__ void leapfrog_entry(const LeapfrogArgs& a, int64_t g, int64_t off)
+{
+  using V = typename std::conditional<VEC == 2, double2, double>::type;
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  auto ld = [off](const double* p, int64_t g) -> V { return reinterpret_cast<const V*>(p + off)[g]; };
+  auto ldnt = [off](const double* p, int64_t g) -> V {
+    if constexpr (NT && VEC == 2) {
+      const d2v v = __builtin_nontemporal_load(reinterpret_cast<const d2v*>(p + off) + g);
+      return make_double2(v.x, v.y);
+    } else
+      return reinterpret_cast<const V*>(p + off)[g];
+  };
+  auto st = [off](double* p, int64_t g, V v) { reinterpret_cast<V*>(p + off)[g] = v; };
+  const double dt2 = a.dt2;
+  const V bb = ldnt(a.b, g), mm = ldnt(a.m, g), uu = ld(a.u, g), pp = ldnt(a.up, g);
+  V nn, zero;
+  if constexpr (VEC == 2) {
+    nn = make_double2(leapfrog_plain(bb.x, mm.x, uu.x, pp.x, dt2), leapfrog_plain(bb.y, mm.y, uu.y, pp.y, dt2));
+    zero = make_double2(0.0, 0.0);
+  } else {
+    nn = leapfrog_plain(bb, mm, uu, pp, dt2);
+    zero = 0.0;
+  }
+  if constexpr (BC) {
+    const BoundaryPlanDev& bc = a.bc;
+    const int64_t d0 = off + (int64_t)VEC * g;          // first dof of this entry
+    unsigned long long word;
+    bool any = true;
+    if constexpr (VEC == 2) {
+      // as in stage_entry: a wave covers 128 consecutive dofs = two mask words, fetched with scalar loads
+      const int64_t w0 = __builtin_amdgcn_readfirstlane((int)(d0 >> 6));
+      const unsigned long long wa = bc.mask[w0], wb = bc.mask[w0 + 1];   // mask has one spare word at the end
+      any = (wa | wb) != 0ull;
+      word = (d0 >> 6) == w0 ? wa : wb;
+    } else {
+      word = bc.mask[d0 >> 6];
+    }
+    if (any) {
+      const unsigned bits = (unsigned)(word >> (d0 & 63)) & (VEC == 2 ? 3u : 1u);   // VEC == 2: d0 is even, both dofs in one word
+      if (bits) {
+        const unsigned long long below = word & ((1ull << (d0 & 63)) - 1ull);
+        int64_t r = (int64_t)bc.prefix[d0 >> 6] + __popcll(below);
+        if constexpr (VEC == 2) {
+          if (bits & 1u) {
+            nn.x = leapfrog_boundary(bb.x, mm.x, uu.x, pp.x, dt2, a.hdt, bc.s1, bc.c1[r], bc.c2[r]);
+            ++r;
+          }
+          if (bits & 2u) nn.y = leapfrog_boundary(bb.y, mm.y, uu.y, pp.y, dt2, a.hdt, bc.s1, bc.c1[r], bc.c2[r]);
+        } else {
+          nn = leapfrog_boundary(bb, mm, uu, pp, dt2, a.hdt, bc.s1, bc.c1[r], bc.c2[r]);
+        }
+      }
+    }
+  }
+  st(a.un, g, nn);
+  if constexpr (HAS_V) {
+    if constexpr (VEC == 2) {
+      d2v w;
+      w.x = (nn.x - pp.x) / a.tdt;
+      w.y = (nn.y - pp.y) / a.tdt;
+      if constexpr (NT)
+        __builtin_nontemporal_store(w, reinterpret_cast<d2v*>(a.v + off) + g);
+      else
+        reinterpret_cast<d2v*>(a.v + off)[g] = w;
+    } else {
+      (a.v + off)[g] = (nn - pp) / a.tdt;
+    }
+  }
+  st(a.b, g, zero);
+}
+
+// nvec entries of width VEC, then the odd last dof of a 16-byte sweep by the first thread of the last block
+template <int VEC, bool NT, bool BC, bool HAS_V>
+__global__ void __launch_bounds__(256) k_leapfrog_step(int64_t nvec, int ntail, LeapfrogArgs a)
+{
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < nvec; g += (int64_t)gridDim.x * blockDim.x)
+    leapfrog_entry<VEC, NT, BC, HAS_V>(a, g, 0);
+  if (VEC > 1 && blockIdx.x == gridDim.x - 1 && (int)threadIdx.x < ntail)
+    leapfrog_entry<1, false, BC, HAS_V>(a, threadIdx.x, (int64_t)VEC * nvec);
+}
+
 }  // namespace wf
 
 using namespace wf;
@@ -505,9 +624,80 @@ int rk4_stage_impl(int64_t n, double bdt, double adt_next, int has_next, double*
   return WF_OK;
 }
 
+int leapfrog_step_impl(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                       double* d_u_next, double* d_v, const wf_boundary* bcp, double s1, double s2, void* stream)
+{
+  if (n <= 0) return WF_OK;
+  WF_REQUIRE(d_b && d_m && d_u && d_u_prev && d_u_next, "wf_leapfrog_step: null vector");
+  WF_REQUIRE(dt > 0.0, "wf_leapfrog_step: the time step must be positive");
+  WF_REQUIRE(!(s2 > 0.0), "wf_leapfrog_step_bc: s2 > 0 is a negative absorbing coefficient");
+  // two vectors of n entries that share memory (u_next and u_prev may be the same vector, not shifted ones)
+  auto overlap = [n](const double* p, const double* q) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), c = reinterpret_cast<uintptr_t>(q), len = (uintptr_t)n * sizeof(double);
+    return a < c + len && c < a + len;
+  };
+  WF_REQUIRE(!overlap(d_u_next, d_u) && !overlap(d_u_next, d_b) && !overlap(d_u_next, d_m),
+             "wf_leapfrog_step: u_next must not alias u, b or m");
+  WF_REQUIRE(d_u_next == d_u_prev || !overlap(d_u_next, d_u_prev), "wf_leapfrog_step: u_next overlaps u_prev without being u_prev");
+  WF_REQUIRE(!d_v || (!overlap(d_v, d_b) && !overlap(d_v, d_m) && !overlap(d_v, d_u) && !overlap(d_v, d_u_prev)
+                      && !overlap(d_v, d_u_next)),
+             "wf_leapfrog_step: v must not alias another vector of the call");
+  WF_REQUIRE(!bcp || bcp->n == n, "wf_leapfrog_step_bc: the boundary plan was built for another vector length");
+  MarkerScope mk("wf_leapfrog_step");
+  hipStream_t st = (hipStream_t)stream;
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = aligned(d_b) && aligned(d_m) && aligned(d_u) && aligned(d_u_prev) && aligned(d_u_next) && (!d_v || aligned(d_v));
+  wf::LeapfrogArgs a{};
+  a.dt2 = dt * dt;
+  a.hdt = (-s2) * (0.5 * dt);
+  a.tdt = 2.0 * dt;
+  a.b = d_b;
+  a.m = d_m;
+  a.u = d_u;
+  a.up = d_u_prev;
+  a.un = d_u_next;
+  a.v = d_v;
+  const bool use_bc = bcp && bcp->nb > 0;
+  if (use_bc) {
+    a.bc.mask = bcp->d_mask.data();
+    a.bc.prefix = bcp->d_prefix.data();
+    a.bc.c1 = bcp->d_c1.data();
+    a.bc.c2 = bcp->d_c2.data();
+    a.bc.s1 = s1;   // s2 enters through hdt
+  }
+  const int64_t nvec = vec ? n / 2 : n;
+  const int ntail = vec ? (int)(n - 2 * nvec) : 0;
+  const unsigned grid = capped_grid((size_t)std::max<int64_t>(nvec, 1), 256);
+#define WF_LEAPFROG(VEC, NT_, BC_, V_) \
+  hipLaunchKernelGGL((wf::k_leapfrog_step<VEC, NT_, BC_, V_>), dim3(grid), dim3(256), 0, st, nvec, ntail, a)
+  if (vec) {
+    if (d_v) { if (use_bc) WF_LEAPFROG(2, true, true, true); else WF_LEAPFROG(2, true, false, true); }
+    else     { if (use_bc) WF_LEAPFROG(2, true, true, false); else WF_LEAPFROG(2, true, false, false); }
+  } else {
+    if (d_v) { if (use_bc) WF_LEAPFROG(1, false, true, true); else WF_LEAPFROG(1, false, false, true); }
+    else     { if (use_bc) WF_LEAPFROG(1, false, true, false); else WF_LEAPFROG(1, false, false, false); }
+  }
+#undef WF_LEAPFROG
+  WF_LAUNCH_CHECK();
+  return WF_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int wf_leapfrog_step(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                     double* d_u_next, double* d_v, void* stream)
+{
+  return leapfrog_step_impl(n, dt, d_b, d_m, d_u, d_u_prev, d_u_next, d_v, nullptr, 0.0, 0.0, stream);
+}
+
+int wf_leapfrog_step_bc(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                        double* d_u_next, double* d_v, const wf_boundary* bc, double s1, double s2, void* stream)
+{
+  WF_REQUIRE(bc != nullptr, "wf_leapfrog_step_bc: null boundary plan");
+  return leapfrog_step_impl(n, dt, d_b, d_m, d_u, d_u_prev, d_u_next, d_v, bc, s1, s2, stream);
+}
 
 int wf_rk4_stage(int64_t n, double bdt, double adt_next, int has_next, double* d_b, const double* d_m,
                  const double* d_vn, const double* d_u_read, const double* d_v_read, double* d_u, double* d_v,

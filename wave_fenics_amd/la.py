@@ -77,6 +77,19 @@ def rk4_stage(b, m, vn, u_read, v_read, u, v, bdt: float, adt_next: float = 0.0,
                              _ptr(un) if has_next else z, _ptr(vn_next) if has_next else z, _stream(b)))
 
 
+def leapfrog_step(b, m, u, u_prev, u_next, dt: float, v=None, bc=None, s1: float = 0.0, s2: float = 0.0):
+    """One central-difference step (wf_leapfrog_step): b holds K u on entry and +0.0 on return,
+    u_next = dt^2 b/m + (2 u - u_prev); with bc (a BoundaryPlan) the dofs of its sets take the source term s1 c1 and the
+    absorbing term -s2 c2 u' centred (wf_leapfrog_step_bc).  u_next may be u_prev; v (optional) receives
+    (u_next - u_prev) / (2 dt)."""
+    vp = _ptr(v) if v is not None else 0
+    if bc is not None:
+        check(lib().wf_leapfrog_step_bc(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_next), vp,
+                                        bc._h, float(s1), float(s2), _stream(b)))
+        return
+    check(lib().wf_leapfrog_step(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_next), vp, _stream(b)))
+
+
 class BoundaryPlan:
     """wf_boundary_create: the two boundary dof sets of the form L (LinearGLL.hpp:113-115, forms.ufl:19-24) as a
     bitmap + coefficient arrays, so that the fused RK4 stage can leave the next right-hand side's boundary

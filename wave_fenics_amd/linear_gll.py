@@ -8,6 +8,9 @@ absorbing Gamma_2) with their collocated facet masses; the FFCx form
 L = c0^2 (g v ds(1) - 1/c0 v_n v ds(2)) (demo/cpu_planar3d/forms.ufl:19-24)
 is applied in its diagonal GLL form by wf_boundary_apply.
 
+Not in the reference: leapfrog() integrates the same equation with the second-order central-difference scheme (one
+stiffness apply per step, wf_leapfrog_step_bc), stable_time_step() gives a stable step for it.
+
 Ghost exchange: `updater` (a VectorUpdater) supplies scatter_fwd / scatter_rev
 where the reference calls la::Vector::scatter_fwd / scatter_rev(add)
 (LinearGLL.hpp:110,127,164,176,284-285); None on one rank.  The forward update
@@ -314,3 +317,111 @@ def _rk4_fused(self, startTime: float, finalTime: float, timeStep: float, max_st
 
 
 LinearGLLOpt.rk4_fused = _rk4_fused
+
+
+def _leapfrog(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
+    """Second-order central-difference (leapfrog, explicit Newmark beta = 0, gamma = 1/2) integration of
+    m u'' + d u' - K u = s1(t) mG1, d = -s2 mG2 scattered to the dofs, from the state (u_n, v_n) to the state
+    (u_n, v_n) like rk4(): ONE stiffness apply and one streaming pass (wf_leapfrog_step_bc, 48 B/dof) per step against
+    the four applies of RK4.  The absorbing term is taken centred, d (u^{n+1} - u^{n-1}) / (2 dt): it is diagonal, so the
+    implicit solve is a division, and the stability limit stays that of the undamped scheme, dt < 2 / sqrt(lambda_max)
+    (stable_time_step) -- RK4 loses stability at dofs that carry several absorbing faces.
+
+    Start-up: a^0 = (K u^0 + s1(t0) mG1 - d v^0) / m and u^{-1} = u^0 - dt v^0 + dt^2/2 a^0 (one apply).  Finish: one more
+    apply and update into a scratch vector give v_n = (u^{n+1} - u^{n-1}) / (2 dt), the central velocity at the final
+    time, without advancing u -- so a run split in two equals the continuous run up to rounding.
+
+    The step is constant: steps are counted by `while t < finalTime` and the last step is NOT shortened to land on
+    finalTime (a shortened step would break the two-level recurrence).  Returns (t, steps)."""
+    from .distributed import overlapped_apply
+    t, tf, dt = startTime, finalTime, timeStep
+    step = 0
+    upd = self.updater
+    b, m = self.b, self.m
+    u = self.u_n.clone()                       # u^n
+    w = torch.zeros_like(u)                    # u^{n-1}, overwritten in place by u^{n+1}
+    scratch = torch.zeros_like(u)
+
+    def s1(tn):
+        window = 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * tn / self.alpha_)) if tn < self.T_ * self.alpha_ else 1.0
+        return self._boundary_scalars(window, tn)[0]
+
+    def rhs(x_u):
+        """b += K x_u (+ ghost updates), as in rk4_fused; b is zero on entry"""
+        if self._split:
+            overlapped_apply(self.stiff_op, upd, x_u, b)
+            return
+        if upd is not None:
+            upd.scatter_fwd(x_u)
+        self.stiff_op(x_u, b)
+        if upd is not None:
+            upd.scatter_rev(b)
+
+    if getattr(self, "_bc", None) is None:
+        self._bc = la.BoundaryPlan(b.numel(), self.idx1.cpu().numpy(), self.mG1.cpu().numpy(), self.idx2.cpu().numpy(),
+                                   self.mG2.cpu().numpy())
+    bc, s2 = self._bc, -self.c0_ if self.medium is None else -1.0
+    # start-up: scratch = a^0, w = u^{-1}
+    la.fill(b, 0.0)
+    rhs(u)
+    bc.apply(s1(t), s2, self.v_n, b)
+    la.pointwise_div(b, m, scratch)
+    la.axpy(w, -dt, self.v_n, u)
+    la.axpy(w, 0.5 * dt * dt, scratch, w)
+    la.fill(b, 0.0)
+    while t < tf:
+        rhs(u)
+        la.leapfrog_step(b, m, u, w, w, dt, bc=bc, s1=s1(t), s2=s2)
+        u, w = w, u
+        t += dt
+        step += 1
+        if max_steps is not None and step >= max_steps:
+            break
+    # finish: the step after the last one, into scratch, for the central velocity at t
+    rhs(u)
+    la.leapfrog_step(b, m, u, w, scratch, dt, v=self.v_n, bc=bc, s1=s1(t), s2=s2)
+    la.copy(u, self.u_n)
+    if upd is not None:
+        upd.scatter_fwd(self.u_n)
+        upd.scatter_fwd(self.v_n)
+    return t, step
+
+
+def _max_eigenvalue(self, iters: int = 100):
+    """Largest eigenvalue of -M^{-1} K (lumped mass, the model's stiffness operator) by `iters` power iterations; the
+    value returned is the Rayleigh quotient -x^T K x / x^T M x of the last iterate.  It approaches lambda_max from
+    BELOW (a Rayleigh quotient never exceeds it): on small P2 and P4 boxes it was 0.9992 and 0.9995 of the converged
+    value after 100 iterations and 0.996 after 50, so keep a safety factor in the step derived from it.  One rank."""
+    if self.updater is not None:
+        raise NotImplementedError("LinearGLLOpt.max_eigenvalue on a partitioned mesh (updater=) is not implemented")
+    if iters < 1:
+        raise ValueError("max_eigenvalue needs at least one iteration")
+    n = self.m.numel()
+    x = torch.from_numpy(np.random.default_rng(0).uniform(-1.0, 1.0, n)).to(self.device)
+    y, mx = torch.zeros_like(x), torch.zeros_like(x)
+    lam = 0.0
+    for _ in range(iters):
+        la.fill(y, 0.0)
+        self.stiff_op(x, y)                                  # y = K x
+        la.fill(mx, 0.0)
+        la.pointwise_mult_add(self.m, x, mx)                 # mx = M x
+        lam = -la.inner_product(x, y) / la.inner_product(x, mx)
+        la.pointwise_div(y, self.m, mx)                      # next iterate M^{-1} K x, normalised
+        nrm = math.sqrt(la.inner_product(mx, mx))
+        if not nrm > 0.0:
+            break
+        la.scale(1.0 / nrm, mx)
+        x, mx = mx, x
+    return lam
+
+
+def _stable_time_step(self, safety: float = 0.9, iters: int = 100):
+    """safety * 2 / sqrt(lambda_max(-M^{-1} K)): a stable step of leapfrog() (its limit is 2 / sqrt(lambda_max), with or
+    without the absorbing term).  max_eigenvalue approaches lambda_max from below, so the limit is overestimated by
+    up to ~0.04 % after 100 iterations; safety covers it.  One rank."""
+    return safety * 2.0 / math.sqrt(self.max_eigenvalue(iters))
+
+
+LinearGLLOpt.leapfrog = _leapfrog
+LinearGLLOpt.max_eigenvalue = _max_eigenvalue
+LinearGLLOpt.stable_time_step = _stable_time_step
