@@ -1,0 +1,93 @@
+"""Owner form of the box stiffness operator at P4: x planes by direct-to-LDS loads ("r25").
+
+The 4x4 and 8x2 cross-sections load a layer's x planes straight into one of two LDS buffers, 16 bytes per lane, while
+the other buffer is being read, with one barrier per layer; what lies outside the mesh is zeroed once per run and never
+loaded, and a piece that straddles the mesh's last lattice line in x is loaded 8 bytes wide.  2x8 keeps the register
+form.  What can go wrong is what a load may touch (x is only 8-byte aligned), which buffer a layer reads, and the
+mesh edges, so, following tests/test_gpu_owner_prologue.py and with its helpers:
+
+  * boxes of one cell, of a closing lattice line that is a column of its own, and of partial columns on both axes;
+  * cuts of 1, 2, 3 and 4 layers per run and whole columns (from 2 layers on both buffers and both copies of the layer
+    body run live, and a run ends in either buffer), and a caller's table of one-layer runs listed top layer first;
+  * x and y in guarded buffers at both alignments, the padding of x NaN: the padding must stay intact, y finite, every
+    cut bit-equal to the default cut and within 1e-12 of the oracle;
+  * interior + interface parts bit-equal to the whole apply;
+  * one P2 and one P6 case against the oracle: the other degrees still run."""
+import numpy as np
+import pytest
+
+from test_gpu_owner_prologue import BOXES, P4_SHAPES, TOL, case, guarded_apply
+from test_gpu_owner_run_table import owner, owner_columns, relerr
+
+pytestmark = pytest.mark.gpu
+
+assert BOXES == [(1, 1, 1), (8, 2, 2), (9, 3, 3), (17, 5, 2)] and TOL == 1e-12
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    import wave_fenics_amd as w
+    w.lib()
+    return torch.device("cuda", 0)
+
+
+@pytest.mark.parametrize("n", BOXES, ids=lambda n: "x".join(map(str, n)))
+@pytest.mark.parametrize("variant", sorted(P4_SHAPES))
+def test_p4_cuts(gpu, oracle, variant, n):
+    p, nz = 4, n[2]
+    V, x, y0, yref = case(oracle, n, p)
+    op = owner(V, p, variant=variant)
+    y_default = guarded_apply(op, V, x, y0, gpu, "default cut")
+    e = relerr(y_default, yref)
+    print(f"P4 variant {variant} {n}: default cut lz {op.info.plan_lz}, oracle {e:.3e}")
+    assert e <= TOL
+    cuts = {f"lz {lz}": owner(V, p, variant=variant, lz=lz) for lz in (1, 2, 3, 4)}
+    cuts["whole columns"] = owner(V, p, variant=variant, lz=nz)
+    assert cuts["lz 1"].info.plan_lz == 1 and cuts["whole columns"].info.plan_lz == nz
+    bx, by = P4_SHAPES[variant]
+    ncols = owner_columns(n, p, bx, by)
+    table = np.array([(c, z, z + 1) for z in reversed(range(nz)) for c in range(ncols)], dtype=np.int32)
+    op.set_runs(table)
+    assert np.array_equal(op.runs(), table)
+    cuts["one-layer runs, top layer first"] = op
+    for name, cut in cuts.items():
+        y = guarded_apply(cut, V, x, y0, gpu, name)
+        eo = relerr(y, yref)
+        off = int((y.view(np.int64) != y_default.view(np.int64)).sum())
+        print(f"  {name}: oracle {eo:.3e}, entries off the default cut {off}")
+        assert eo <= TOL, name
+        assert off == 0, name
+
+
+@pytest.mark.parametrize("variant", sorted(P4_SHAPES))
+def test_p4_parts_equal_the_whole_apply(gpu, oracle, variant):
+    """interior + interface (first z segment short under the ghost plane) against the whole apply, bit for bit"""
+    import torch
+    from wave_fenics_amd._lib import WF_PART_INTERFACE, WF_PART_INTERIOR
+    p, n = 4, (9, 3, 3)
+    V, x_np, y0_np, yref = case(oracle, n, p)
+    op = owner(V, p, variant=variant)
+    assert op.set_ghost_faces(True, True, True)
+    # every column of so small a box may touch a ghost face, so only the interface list has to be non-empty
+    assert op.info.items_interface > 0
+    x, y0 = torch.from_numpy(x_np.copy()).to(gpu), torch.from_numpy(y0_np.copy()).to(gpu)
+    yall = y0.clone()
+    op(x, yall)
+    y = y0.clone()
+    op.apply_part(x, y, WF_PART_INTERIOR)
+    op.apply_part(x, y, WF_PART_INTERFACE)
+    torch.cuda.synchronize()
+    assert torch.equal(y, yall), (variant, int((y != yall).sum()))
+    assert relerr(yall.cpu().numpy(), yref) <= TOL
+
+
+@pytest.mark.parametrize("p", [2, 6])
+def test_other_degrees_still_run(gpu, oracle, p):
+    n = (9, 3, 3)
+    V, x, y0, yref = case(oracle, n, p)
+    y = guarded_apply(owner(V, p), V, x, y0, gpu, f"P{p}")
+    e = relerr(y, yref)
+    print(f"P{p} {n}: oracle {e:.3e}")
+    assert e <= TOL

@@ -33,9 +33,19 @@
 // values xz[P + k] of other lanes of the row and come by v_mov_b32_dpp (quad_perm for the x line, row_ror for the
 // y line) instead of from LDS; only the closing node of each line is read from the rectangle, and the -x / -y cell
 // lines are read by the lanes with i = 0 / j = 0 alone.
+//
+// P = 4, 4x4 and 8x2, direct-to-LDS x planes ("r25"; -DWF_OWNER_DMA=0: the form above): the rectangle's
+// rows are padded to an even length and a plane is cut into 16-byte pieces (owner_pieces.h), piece t of every plane owned
+// by thread t.  A wave fills its 64 pieces of a plane with one global_load_lds_dwordx4 (lane-linear LDS image, per-lane
+// source, 8-byte aligned); pieces outside the mesh are zeroed once per run and never loaded, pieces that straddle the
+// mesh's last line in x take the register path, 8 bytes wide.  There are two buffers of P + 1 plane slots (and of G_c):
+// layer kz reads one while planes 1..P of layer kz + 1 land in the other, plane P is copied across before the layer's
+// only barrier, whose wait for the loads is the one the planes need, and the unroll by two keeps every LDS offset a
+// compile-time constant.  No floating-point sum changes, so y keeps the bits of the register form.
 #include <cstdlib>
 
 #include "march_column.h"
+#include "owner_pieces.h"
 #include "stiffness_core.h"
 
 namespace wf {
@@ -59,6 +69,24 @@ constexpr int owner_waves() { return P >= 5 ? WF_OWNER_WAVES_HI : WF_OWNER_WAVES
 
 template <int P>
 constexpr bool owner_lane_exchange() { return WF_OWNER_LANE_EXCHANGE != 0 && P == 4; }
+
+// P = 4: the x planes by direct-to-LDS loads into two buffers, one barrier per layer (1; DESIGN §4.2, "r25") or through
+// registers into one buffer as at every other degree (0).  A cross-section whose plane has more than 256 pieces (2 x 8:
+// 259) stays on the register form.
+#ifndef WF_OWNER_DMA
+#define WF_OWNER_DMA 1
+#endif
+
+template <int P, int BX, int BY>
+constexpr bool owner_dma() { return WF_OWNER_DMA != 0 && P == 4 && owner_rect(P, BX, BY).NPC <= 256; }
+
+// 16 bytes per lane from src (per lane, 8-byte aligned) to the LDS image that starts at dst (the same in every lane
+// of the wave): lane l's bytes land at dst + 16 l.  Lanes that are masked off neither read nor write.
+__device__ __forceinline__ void load_to_lds16(const double* src, double* dst)
+{
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
 
 // Lane-exchange thread map: the BX BY = 16 cells of the column x-fastest, four per wave; lane = 16 c' + 4 j + i.
 // Returns the owned line ti + P BX tj of thread t.
@@ -109,18 +137,24 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   [[maybe_unused]] const int ablate = WF_ABLATE_FLAGS(ablate_arg);
   constexpr int n = P + 1;
   constexpr int LX = P * BX, LY = P * BY, NL = LX * LY;   // owned lines
-  constexpr int RX = LX + P + 1, RY = LY + P + 1, RP = RX * RY;   // staged rectangle of one plane
+  // direct-to-LDS form: the rectangle's rows padded to an even length, a plane in 16-byte pieces (owner_pieces.h),
+  // two buffers of P + 1 plane slots and of the staged G_c
+  constexpr bool dma = owner_dma<P, BX, BY>();
+  constexpr int NB = dma ? 2 : 1;
+  constexpr int RX = dma ? owner_rect(P, BX, BY).RX : LX + P + 1, RY = LY + P + 1, RP = RX * RY;   // staged rectangle of one plane
+  constexpr int NPC = RP / 2, UB = (P + 1) * RP;   // pieces of a plane, doubles of a buffer
   constexpr int NPF = (P * RP + 255) / 256;          // x prefetch positions per thread (planes 1..P)
   constexpr int NCP = (RP + 255) / 256;              // positions of one plane
   constexpr int GCX = BX + 1, GC = GCX * (BY + 1), NG = 3 * GC;   // staged G00 | G11 | G22 of the cells
   constexpr int NGL = (NG + 255) / 256;
   static_assert(NL <= 256, "column does not fit a 256-thread workgroup");
+  static_assert(!dma || (RP % 2 == 0 && NPC <= 256), "a plane is not one 16-byte piece per thread");
   constexpr bool lx = owner_lane_exchange<P>();
   static_assert(!lx || owner_lane_map_is_bijection<P, BX, BY>(), "lane-exchange map is not onto the owned lines");
 
   // x planes 0..P of the layer + a dump row for positions past the rectangle (branchless rotate, see (c))
-  __shared__ __attribute__((aligned(16))) double Ux[(P + 1) * RP + 256];
-  __shared__ __attribute__((aligned(16))) double Gs[NGL * 256];
+  __shared__ __attribute__((aligned(16))) double Ux[dma ? NB * UB : UB + 256];
+  __shared__ __attribute__((aligned(16))) double Gs[NB * NGL * 256];
   // A[k][a] for the rows indexed by the plane (k, a compile-time after unrolling).  P >= 5: rows k < P from LDS (filled
   // before the prologue's first barrier), row P from am.v; P <= 4: am.v
 #ifdef WF_OWNER_A_CONST
@@ -200,6 +234,11 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
       poff[m] = (int32_t)((size_t)II + (size_t)NX * JJ + plane * pl);
   }
   const int32_t pclamp = (int32_t)((size_t)I0 + (size_t)NX * J0);   // first owned position: always inside the mesh
+  // direct-to-LDS form: the thread's piece of every plane (threads NPC.. have none), and where a wave's 64 pieces of
+  // plane slot 0 of buffer 0 start in LDS
+  [[maybe_unused]] const OwnerPiece pc = dma ? owner_piece(P, BX, BY, NX, NY, I0, J0, t) : OwnerPiece{PIECE_NONE, 0, 0};
+  [[maybe_unused]] const bool pc_in = pc.kind == PIECE_INSIDE, pc_edge = pc.kind == PIECE_STRADDLING;
+  [[maybe_unused]] double* const wave_img = dma ? Ux + 128 * __builtin_amdgcn_readfirstlane(t >> 6) : Ux;
 
   // G_c entries staged by this thread: entry e = comp * GC + cell, cell (lcx, lcy) = (cx0 - 1 + lcx, cy0 - 1 + lcy).
   // Gc is blocked by gbx x gby: the atomic form's cross-section at P <= 4 (the operator's geometry does not depend on the
@@ -221,17 +260,22 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
 #pragma unroll
     for (int q = 0; q < NGL; ++q) g[q] = Gc[gbase[q] + gstride * kz];
   };
-  auto store_g = [&](const double (&g)[NGL]) {
+  auto store_g = [&](const double (&g)[NGL], int gb = 0) {   // gb: buffer of the direct-to-LDS form
 #pragma unroll
-    for (int q = 0; q < NGL; ++q) Gs[t + 256 * q] = gval[q] ? g[q] : 0.0;
+    for (int q = 0; q < NGL; ++q)
+      if constexpr (dma)
+        Gs[gb * (NGL * 256) + t + 256 * q] = gval[q] ? g[q] : 0.0;
+      else
+        Gs[t + 256 * q] = gval[q] ? g[q] : 0.0;
   };
   // the thread's five scales of one layer from the staged G_c: x term (+x cell, -x cell), y term (+y, -y), z term
   const bool mi = i == 0, mj = j == 0;
   const int lR = (ti - i) / P + 1, lA = (tj - j) / P + 1;   // staged cell of the +x / +y cell
-  auto scales = [&](double (&s)[5]) {
+  auto scales = [&](double (&s)[5], int gb = 0) {
     const double* g0 = Gs;
     const double* g1 = Gs + GC;
     const double* g2 = Gs + 2 * GC;
+    if constexpr (dma) g0 += gb * (NGL * 256), g1 += gb * (NGL * 256), g2 += gb * (NGL * 256);
     const int AR = lA * GCX + lR, AL = AR - 1, BR = AR - GCX, BL = BR - 1;
     const double x_ar = g0[AR], x_br = g0[BR], x_al = g0[AL], x_bl = g0[BL];
     const double y_ar = g1[AR], y_al = g1[AL], y_br = g1[BR], y_bl = g1[BL];
@@ -260,26 +304,47 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     }
 #pragma unroll
     for (int k = 0; k < P; ++k) yA[k] = (ablate & 1) ? 0.0 : y[plane * (size_t)(P * z0 + k) + yoff];
-    // every plane load is in flight before the first is consumed: unconditional loads on clamped addresses, then
-    // the LDS stores (positions past the rectangle go to the dump row), as in the rotate (c).  One decomposition of
-    // the staged positions serves both ("r20"): planes 1..P through poff, exactly as the rotate loads
-    // them, and plane 0 through the first NCP entries of poff from its own base (a position t + 256 m < RP of the
-    // P RP staged ones lies in the first plane of its block, so its offset is the one within any plane).
-    const double* xb = x + plane * (size_t)(P * z0) + plane;
-    double xp0[NCP], xp[NPF];
+    if constexpr (dma) {
+      // direct-to-LDS form: what lies outside the mesh is set to +0.0 once, in both buffers, and never loaded; every
+      // other piece of planes 0..P goes to buffer 0, a wave's 64 pieces by one load per plane, the straddling pieces'
+      // positions in the mesh by 8-byte loads.  Nothing has read this LDS before, and the barriers below come after
+      // the wait for all of these loads.
+      if (pc.kind == PIECE_OUTSIDE || pc_edge)
 #pragma unroll
-    for (int m = 0; m < NCP; ++m) xp0[m] = (xb - plane)[t + 256 * m < RP && poff[m] >= 0 ? poff[m] : pclamp];
+        for (int m = 0; m < NB * (P + 1); ++m) Ux[m * RP + 2 * t] = Ux[m * RP + 2 * t + 1] = 0.0;
+      const double* xb = x + plane * (size_t)(P * z0) + pc.off;
+      if (pc_in)
 #pragma unroll
-    for (int m = 0; m < NPF; ++m) xp[m] = xb[poff[m] >= 0 ? poff[m] : pclamp];
+        for (int m = 0; m <= P; ++m) load_to_lds16(xb + plane * m, wave_img + m * RP);
+      if (pc_edge) {
+        double xe[P + 1];
 #pragma unroll
-    for (int m = 0; m < NCP; ++m) {
-      const int pos = t + 256 * m;
-      Ux[tile_or_dump<RP>(m, pos, 0, (P + 1) * RP, t)] = (pos < RP && poff[m] >= 0) ? xp0[m] : 0.0;
-    }
+        for (int m = 0; m <= P; ++m) xe[m] = xb[plane * m];
 #pragma unroll
-    for (int m = 0; m < NPF; ++m) {
-      const int pos = t + 256 * m;
-      Ux[tile_or_dump<P * RP>(m, pos, RP, (P + 1) * RP, t)] = poff[m] >= 0 ? xp[m] : 0.0;
+        for (int m = 0; m <= P; ++m) Ux[m * RP + 2 * t + pc.half] = xe[m];
+      }
+    } else {
+      // every plane load is in flight before the first is consumed: unconditional loads on clamped addresses, then
+      // the LDS stores (positions past the rectangle go to the dump row), as in the rotate (c).  One decomposition of
+      // the staged positions serves both ("r20"): planes 1..P through poff, exactly as the rotate loads
+      // them, and plane 0 through the first NCP entries of poff from its own base (a position t + 256 m < RP of the
+      // P RP staged ones lies in the first plane of its block, so its offset is the one within any plane).
+      const double* xb = x + plane * (size_t)(P * z0) + plane;
+      double xp0[NCP], xp[NPF];
+#pragma unroll
+      for (int m = 0; m < NCP; ++m) xp0[m] = (xb - plane)[t + 256 * m < RP && poff[m] >= 0 ? poff[m] : pclamp];
+#pragma unroll
+      for (int m = 0; m < NPF; ++m) xp[m] = xb[poff[m] >= 0 ? poff[m] : pclamp];
+#pragma unroll
+      for (int m = 0; m < NCP; ++m) {
+        const int pos = t + 256 * m;
+        Ux[tile_or_dump<RP>(m, pos, 0, (P + 1) * RP, t)] = (pos < RP && poff[m] >= 0) ? xp0[m] : 0.0;
+      }
+#pragma unroll
+      for (int m = 0; m < NPF; ++m) {
+        const int pos = t + 256 * m;
+        Ux[tile_or_dump<P * RP>(m, pos, RP, (P + 1) * RP, t)] = poff[m] >= 0 ? xp[m] : 0.0;
+      }
     }
     store_g(gp);
     __syncthreads();
@@ -325,9 +390,10 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     return;
   }
 
-  // the x / y terms of one plane (LDS slot k): sx, sy = the scales of the +x / -x / +y / -y cells
-  auto xy_terms = [&](int k, double s0, double s1, double s2, double s3) {
+  // the x / y terms of one plane (LDS slot k of buffer cb): sx, sy = the scales of the +x / -x / +y / -y cells
+  auto xy_terms = [&](int k, double s0, double s1, double s2, double s3, int cb = 0) {
     const double* L = Ux + k * RP;
+    if constexpr (dma) L += cb * UB;
     double xr = 0.0, xl = 0.0, ya = 0.0, yb = 0.0;
     if constexpr (lx) {
       const double xo = xz[P + k];
@@ -388,15 +454,28 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
   };
 
   // One layer: owned planes P*kz .. P*kz + P - 1.  ycur holds their y (prefetched), ynext receives the next layer's.
-  auto layer = [&](auto hn_tag, double (&ycur)[P], double (&ynext)[P], int kz) {
+  // Direct-to-LDS form: the layer reads buffer cb and fills the other one (a compile-time value at every call).
+  auto layer = [&](auto hn_tag, double (&ycur)[P], double (&ynext)[P], int kz, int cb = 0) {
     constexpr bool has_next = decltype(hn_tag)::value;
+    [[maybe_unused]] const int nb = 1 - cb;
     // (a) next layer's x planes, G_c and y: in flight during this layer's arithmetic.  Unconditional loads on
     // clamped addresses; what is live is decided where the registers are consumed, in (c).
-    [[maybe_unused]] double xn[NPF], gn[NGL];
+    [[maybe_unused]] double xn[NPF], gn[NGL], xe[P];
     if constexpr (has_next) {
       const double* xb = x + plane * (size_t)(P * (kz + 1) + 1);
+      if constexpr (dma) {
+        // planes 1..P of the next layer straight into the other buffer, which nobody reads during this layer (its
+        // last readers passed the previous layer's barrier); the straddling pieces' positions through registers
+        if (pc_in)
 #pragma unroll
-      for (int m = 0; m < NPF; ++m) xn[m] = xb[poff[m] >= 0 ? poff[m] : pclamp];
+          for (int m = 0; m < P; ++m) load_to_lds16(xb + plane * m + pc.off, wave_img + nb * UB + (m + 1) * RP);
+        if (pc_edge)
+#pragma unroll
+          for (int m = 0; m < P; ++m) xe[m] = xb[plane * m + pc.off];
+      } else {
+#pragma unroll
+        for (int m = 0; m < NPF; ++m) xn[m] = xb[poff[m] >= 0 ? poff[m] : pclamp];
+      }
       load_g(gn, kz + 1);
 #pragma unroll
       for (int k = 0; k < P; ++k) ynext[k] = (ablate & 1) ? 0.0 : y[plane * (size_t)(P * (kz + 1) + k) + yoff];
@@ -417,9 +496,9 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
 #pragma unroll
           for (int a = 0; a < n; ++a) zp += arow(P, a) * xz[a];
         }
-        v = wk[0] * xy_terms(0, sf[0], sf[1], sf[2], sf[3]) + zc * sc[4] + zp * spz;
+        v = wk[0] * xy_terms(0, sf[0], sf[1], sf[2], sf[3], cb) + zc * sc[4] + zp * spz;
       } else {
-        v = wk[k] * xy_terms(k, sc[0], sc[1], sc[2], sc[3]) + zc * sc[4];
+        v = wk[k] * xy_terms(k, sc[0], sc[1], sc[2], sc[3], cb) + zc * sc[4];
       }
       store_y((size_t)(P * kz + k), ycur[k] + v);
     }
@@ -430,34 +509,52 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
 #pragma unroll
         for (int a = 0; a < n; ++a) zpc += arow(P, a) * xz[P + a];
       }
-      double xcp[NCP];
+      if constexpr (dma) {
+        // (c) plane P of this buffer -> slot 0 of the other (its zeros with it), the straddling pieces' positions and
+        // the next G_c; then the layer's one barrier.  Its wait for every load of (a) is the wait the planes need: a
+        // wave's direct loads are ordered for the readers by that wait followed by the barrier.
+        if (t < NPC) {
+          const double c0 = Ux[cb * UB + P * RP + 2 * t], c1 = Ux[cb * UB + P * RP + 2 * t + 1];
+          Ux[nb * UB + 2 * t] = c0;
+          Ux[nb * UB + 2 * t + 1] = c1;
+        }
+        if (pc_edge)
 #pragma unroll
-      for (int m = 0; m < NCP; ++m) {
-        const int pos = t + 256 * m;
-        xcp[m] = pos < RP ? Ux[P * RP + pos] : 0.0;
-      }
-      __syncthreads();
-      // (c) rotate: plane P -> slot 0, the prefetched planes -> slots 1..P, G_c of the next layer.  No per-lane
-      // branch between the loads and these stores: a thread's last position past the rectangle goes to the dump row.
+          for (int m = 0; m < P; ++m) Ux[nb * UB + (m + 1) * RP + 2 * t + pc.half] = xe[m];
+      } else {
+        double xcp[NCP];
 #pragma unroll
-      for (int m = 0; m < NCP; ++m) {
-        const int pos = t + 256 * m;
-        Ux[tile_or_dump<RP>(m, pos, 0, (P + 1) * RP, t)] = xcp[m];
-      }
+        for (int m = 0; m < NCP; ++m) {
+          const int pos = t + 256 * m;
+          xcp[m] = pos < RP ? Ux[P * RP + pos] : 0.0;
+        }
+        __syncthreads();
+        // (c) rotate: plane P -> slot 0, the prefetched planes -> slots 1..P, G_c of the next layer.  No per-lane
+        // branch between the loads and these stores: a thread's last position past the rectangle goes to the dump row.
 #pragma unroll
-      for (int m = 0; m < NPF; ++m) {
-        const int pos = t + 256 * m;
-        Ux[tile_or_dump<P * RP>(m, pos, RP, (P + 1) * RP, t)] = poff[m] >= 0 ? xn[m] : 0.0;
+        for (int m = 0; m < NCP; ++m) {
+          const int pos = t + 256 * m;
+          Ux[tile_or_dump<RP>(m, pos, 0, (P + 1) * RP, t)] = xcp[m];
+        }
+#pragma unroll
+        for (int m = 0; m < NPF; ++m) {
+          const int pos = t + 256 * m;
+          Ux[tile_or_dump<P * RP>(m, pos, RP, (P + 1) * RP, t)] = poff[m] >= 0 ? xn[m] : 0.0;
+        }
       }
-      store_g(gn);
+      store_g(gn, nb);
       __syncthreads();
       // the z window rotates by P; the new scales, the shared plane's sums
 #pragma unroll
       for (int m = 0; m <= P; ++m) xz[m] = xz[m + P];
 #pragma unroll
-      for (int m = 1; m <= P; ++m) xz[P + m] = Ux[m * RP + rown + cown];
+      for (int m = 1; m <= P; ++m)
+        if constexpr (dma)
+          xz[P + m] = Ux[nb * UB + m * RP + rown + cown];
+        else
+          xz[P + m] = Ux[m * RP + rown + cown];
       double sn[5];
-      scales(sn);
+      scales(sn, nb);
 #pragma unroll
       for (int q = 0; q < 4; ++q) sf[q] = lx ? add_rounded(sn[q], sc[q]) : sn[q] + sc[q];
       spz = sc[4];
@@ -466,25 +563,32 @@ __global__ __launch_bounds__(256, (owner_waves<P>())) void k_stiffness_owner(
     }
   };
 
-  // unrolled by two: the y registers swap roles instead of being copied (a copy would wait for the prefetch)
+  // unrolled by two: the y registers swap roles instead of being copied (a copy would wait for the prefetch), and the
+  // direct-to-LDS form's two buffers swap with them
   for (int kz = z0; kz < z1; kz += 2) {
     if (kz + 1 < z1) {
-      layer(On{}, yA, yB, kz);
+      layer(On{}, yA, yB, kz, 0);
       if (kz + 2 < z1)
-        layer(On{}, yB, yA, kz + 1);
+        layer(On{}, yB, yA, kz + 1, dma ? 1 : 0);
       else
-        layer(Off{}, yB, yA, kz + 1);
+        layer(Off{}, yB, yA, kz + 1, dma ? 1 : 0);
     } else {
-      layer(Off{}, yA, yB, kz);
+      layer(Off{}, yA, yB, kz, 0);
     }
   }
 
   // ---- epilogue: the mesh's top plane P*nz (LDS slot P), owned by the last segment: the last layer's cells only --
+  // Direct-to-LDS form: a run of an odd number of layers ends in buffer 0, of an even number in buffer 1.
   if (z1 == nz) {
     double zp = 0.0;
 #pragma unroll
     for (int a = 0; a < n; ++a) zp += arow(P, a) * xz[P + a];
-    const double v = wk[0] * xy_terms(P, sc[0], sc[1], sc[2], sc[3]) + zp * sc[4];
+    double xy;
+    if constexpr (dma)
+      xy = ((z1 - z0) & 1) ? xy_terms(P, sc[0], sc[1], sc[2], sc[3], 0) : xy_terms(P, sc[0], sc[1], sc[2], sc[3], 1);
+    else
+      xy = xy_terms(P, sc[0], sc[1], sc[2], sc[3]);
+    const double v = wk[0] * xy + zp * sc[4];
     const size_t K = (size_t)P * nz;
     const double y0 = (ablate & 1) ? 0.0 : y[plane * K + yoff];
     store_y(K, y0 + v);
