@@ -1,0 +1,154 @@
+"""The scenarios, references and bookkeeping of the partitioned time-stepping tests (test_partition_scenario_host.py,
+test_gpu_partition_models.py).
+
+Two scenarios on the global box [0, 0.01]^3, c0 = 1500, f = 0.5 MHz:
+
+* "random": no source (pressureAmplitude = 0), u0 = uniform(-1, 1) and v0 = uniform(-1, 1) / (STEPS dt) drawn with
+  np.random.default_rng(SEED) on the GLOBAL dof numbering, every absorbing face active.  Every plane where two ranks meet
+  carries a value of the size of the global maximum from the first step on, so an error made there -- a facet mass
+  not assembled across ranks, a ghost entry not refreshed, a reverse add lost -- is an error of the result.
+* "rest": from rest with the source (p0 = 6e4) on x = 0, the scenario of the older model tests; it keeps the s1 c1 term
+  of a source face cut by a rank interface in the run.
+
+The references are the single-domain oracle on the global mesh (oracle.make_periodic first in the periodic case):
+leapfrog_helpers.leapfrog for leapfrog, oracle.LinearGLLOpt.rk4 for RK4.  Local vectors are the global ones taken
+through dist_helpers.local_to_global, ghosts included."""
+import numpy as np
+
+import leapfrog_helpers as lh
+
+C0, FREQ, P0 = 1500.0, 0.5e6, 6e4
+STEPS, HI, SEED = 20, (0.01, 0.01, 0.01), 11
+SCENARIOS = ("random", "rest")
+
+# name: world, procs, degree, cells per rank, periodic axes, CFL of the leapfrog runs, CFL of the RK4 runs.  The smallest
+# shapes at which each feature exists: absorbing faces cut by an x interface; the source face cut in y, an edge shared by
+# four ranks and the owner kernel at P4; a z ghost plane between different ranks and corner peers (7 neighbours); the
+# same peer on both sides in x with a self-neighbour in y and no source face.  (The host test runs all four; the GPU test
+# leaves the 8-rank case out, see test_gpu_partition_models.GPU_CASES.)
+CASES = {
+    "w2_p2": dict(world=2, procs=(2, 1, 1), p=2, n=(3, 4, 4), periodic=(False, False, False), cfl_lf=0.5, cfl_rk=0.25),
+    "w4_p4": dict(world=4, procs=(2, 2, 1), p=4, n=(3, 3, 4), periodic=(False, False, False), cfl_lf=0.25, cfl_rk=0.25),
+    "w8_p4": dict(world=8, procs=(2, 2, 2), p=4, n=(2, 2, 2), periodic=(False, False, False), cfl_lf=0.5, cfl_rk=0.25),
+    "w2_p2_periodic": dict(world=2, procs=(2, 1, 1), p=2, n=(3, 4, 4), periodic=(True, True, False), cfl_lf=0.5, cfl_rk=0.25),
+}
+_MESH, _REF = {}, {}
+
+
+def global_cells(case):
+    c = CASES[case]
+    return tuple(c["procs"][a] * c["n"][a] for a in range(3))
+
+
+def global_lattice(case):
+    """points per axis of the global dof numbering (a periodic axis has lost its upper plane)"""
+    c = CASES[case]
+    return tuple(c["p"] * g + (0 if per else 1) for g, per in zip(global_cells(case), c["periodic"]))
+
+
+def global_mesh(oracle, case):
+    """the oracle's mesh of the whole box (periodic axes identified), built once and never modified afterwards"""
+    if case not in _MESH:
+        c = CASES[case]
+        om = oracle.create_box(global_cells(case), c["p"], hi=HI)
+        if any(c["periodic"]):
+            oracle.make_periodic(om, c["periodic"])
+        G = global_lattice(case)
+        assert om.ndofs == G[0] * G[1] * G[2]
+        _MESH[case] = om
+    return _MESH[case]
+
+
+def time_step(oracle, case, scheme):
+    c = CASES[case]
+    return oracle.cfl_time_step(global_mesh(oracle, case), c["p"], C0, FREQ, CFL=c["cfl_lf" if scheme == "leapfrog" else "cfl_rk"])[0]
+
+
+def initial_state(ndofs, dt, scenario):
+    """(u0, v0, pressure amplitude) on the global numbering"""
+    if scenario == "rest":
+        return np.zeros(ndofs), np.zeros(ndofs), P0
+    rng = np.random.default_rng(SEED)
+    u0 = rng.uniform(-1.0, 1.0, ndofs)
+    v0 = rng.uniform(-1.0, 1.0, ndofs) / (STEPS * dt)
+    return u0, v0, 0.0
+
+
+def interface_planes(case):
+    """{name: boolean mask over the global dofs} of every lattice plane on which two ranks (or a rank and itself, through
+    a periodic axis) meet"""
+    c = CASES[case]
+    G = global_lattice(case)
+    K, J, I = np.meshgrid(np.arange(G[2]), np.arange(G[1]), np.arange(G[0]), indexing="ij")
+    coord = (I.reshape(-1), J.reshape(-1), K.reshape(-1))
+    planes = {}
+    for a in range(3):
+        at = [c["p"] * c["n"][a] * r for r in range(1, c["procs"][a])] + ([0] if c["periodic"][a] else [])
+        for i in at:
+            planes[f"{'xyz'[a]}={i}"] = coord[a] == i
+    assert planes
+    return planes
+
+
+def reference(oracle, case, scheme, scenario, steps=STEPS, halve_mG2=None):
+    """(dt, u_n, v_n) of the single-domain oracle after `steps` steps, computed once per key.  halve_mG2: a mask of global
+    dofs whose absorbing facet mass is halved (the mutant of the host test: masses not assembled across ranks)."""
+    key = (case, scheme, scenario, steps)
+    if halve_mG2 is None and key in _REF:
+        return _REF[key]
+    c = CASES[case]
+    om = global_mesh(oracle, case)
+    dt = time_step(oracle, case, scheme)
+    u0, v0, p0 = initial_state(om.ndofs, dt, scenario)
+    ref = oracle.LinearGLLOpt(om, c["p"], C0, FREQ, p0)
+    if halve_mG2 is not None:
+        assert (ref.mG2[halve_mG2] > 0.0).any(), "the mutant needs absorbing dofs on the interface planes"
+        ref.mG2 = np.where(halve_mG2, 0.5 * ref.mG2, ref.mG2)
+    ref.init()
+    ref.u_n[:] = u0
+    ref.v_n[:] = v0
+    if scheme == "leapfrog":
+        t, n = lh.leapfrog(ref, *lh.oracle_parts(ref), 0.0, steps * dt - 1e-13, dt)
+    else:
+        t, n = ref.rk4(0.0, steps * dt - 1e-13, dt)
+    assert n == steps
+    out = (dt, ref.u_n.copy(), ref.v_n.copy())
+    for a in out[1:]:
+        a.setflags(write=False)
+    if halve_mG2 is None:
+        _REF[key] = out
+    return out
+
+
+def relerr(a, b):
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+def to_local(xg, l2g):
+    """global -> local, ghosts included"""
+    return np.ascontiguousarray(np.asarray(xg)[l2g])
+
+
+def assemble_owned(ndofs, ranks, key):
+    """local owned -> global: ranks = [{"l2g", "owned", key: local vector}, ...].  Returns (global vector, how many ranks
+    own each global dof); a partition is sound when the count is 1 everywhere."""
+    xg, count = np.zeros(ndofs), np.zeros(ndofs, dtype=np.int64)
+    for r in ranks:
+        own = r["owned"]
+        xg[r["l2g"][own]] = r[key][own]
+        np.add.at(count, r["l2g"][own], 1)
+    return xg, count
+
+
+def ghost_mismatches(xg, ranks, key):
+    """number of local entries (the ghosts; the owned ones by construction) whose bits differ from the owner's"""
+    bad = 0
+    for r in ranks:
+        got, want = np.ascontiguousarray(r[key]).view(np.uint64), np.ascontiguousarray(xg[r["l2g"]]).view(np.uint64)
+        bad += int(np.count_nonzero(got != want))
+    return bad
+
+
+def differing_entries(a, b):
+    """entries whose bits differ"""
+    return int(np.count_nonzero(np.ascontiguousarray(a).view(np.uint64) != np.ascontiguousarray(b).view(np.uint64)))
