@@ -33,8 +33,11 @@ inline void axpy(array<double>& r, double alpha, const array<double>& x, const a
 }  // namespace kernels
 
 class LinearGLLOpt {
+public:
+  using BoundarySet = std::pair<std::vector<std::int32_t>, std::vector<double>>;   // dofs and their collocated facet masses
+
 protected:
-  int k_;         // degree of basis function
+  int k_;        // degree of basis function
   double c0_;     // speed of sound (m/s)
   double freq0_;  // source frequency (Hz)
   double p0_;     // pressure amplitude (Pa)
@@ -61,10 +64,23 @@ protected:
       window_ = 1.0;
     return window_ * p0_ * w0_ / c0_ * std::cos(w0_ * t);
   }
-  void boundary(double g, const double* v)
+  /// the two scalars of the boundary term b[idx1] += s1 mG1, b[idx2] += s2 mG2 v (LinearGLL.hpp:175) at time t
+  double s1(double t) { return c0_ * c0_ * source(t); }
+  double s2() const { return -c0_; }
+  void boundary(double t, const double* v)
   {
-    check(wf_boundary_apply((std::int32_t)idx1->size(), idx1->data(), mG1->data(), c0_ * c0_ * g,
-                            (std::int32_t)idx2->size(), idx2->data(), mG2->data(), -c0_, v, b->data(), nullptr));
+    check(wf_boundary_apply((std::int32_t)idx1->size(), idx1->data(), mG1->data(), s1(t), (std::int32_t)idx2->size(), idx2->data(),
+                            mG2->data(), s2(), v, b->data(), nullptr));
+  }
+  /// the boundary sets as the fused passes read them, created on first use
+  wf_boundary* plan()
+  {
+    if (!bc_) {
+      const auto i1 = idx1->copy_to_host(), i2 = idx2->copy_to_host();
+      const auto a1 = mG1->copy_to_host(), a2 = mG2->copy_to_host();
+      check(wf_boundary_create(N_, (std::int32_t)i1.size(), i1.data(), a1.data(), (std::int32_t)i2.size(), i2.data(), a2.data(), &bc_));
+    }
+    return bc_;
   }
   /// b += K u (+ ghost exchange on a partitioned mesh); b is zero on entry
   void stiffness(double* u)
@@ -95,12 +111,37 @@ protected:
     a->set(h);
     return a;
   }
+  /// What both constructors end with, stiff_op in place: the vectors, m = M 1 with scatter_rev(add) (LinearGLL.hpp:102-110;
+  /// the forward update keeps the ghost entries of m consistent: b / m runs over the whole array), the boundary sets on
+  /// the device and the first stiffness apply (LinearGLL.hpp:120-127).
+  void setup(detail::OpBase&& mass, const BoundarySet& gamma1, const BoundarySet& gamma2)
+  {
+    auto filled = [&](double value) {
+      auto a = std::make_unique<array<double>>((std::size_t)N_);
+      check(wf_fill(N_, value, a->data(), nullptr));
+      return a;
+    };
+    u_n = filled(0.0);
+    v_n = filled(0.0);
+    m = filled(0.0);
+    b = filled(0.0);
+    const auto ones = filled(1.0);
+    mass.apply(ones->data(), m->data());
+    if (updater_) {
+      updater_->update_rev(m->data());
+      updater_->update_fwd(m->data());
+    }
+    check(wf_sync(nullptr));
+    idx1 = upload(gamma1.first);
+    mG1 = upload(gamma1.second);
+    idx2 = upload(gamma2.first);
+    mG2 = upload(gamma2.second);
+    stiffness(u_n->data());
+  }
 
 public:
   const BoxSpace* V = nullptr;   // the box constructor's space (nullptr for the general-Space constructor)
   std::unique_ptr<array<double>> u_n, v_n;
-
-  using BoundarySet = std::pair<std::vector<std::int32_t>, std::vector<double>>;
 
   /// The mesh-file path (demo/cpu_planar3d/main.cpp:39-45, common/LinearGLL.hpp:53-128): any conforming
   /// hexahedral space plus the dof sets of Gamma_1 (source) and Gamma_2 (absorbing) with their collocated
@@ -111,29 +152,9 @@ public:
   {
     set_parameters(degreeOfBasis, speedOfSound, sourceFrequency, pressureAmplitude);
     N_ = S.ndofs;
-    auto zeros = [&]() {
-      auto a = std::make_unique<array<double>>((std::size_t)N_);
-      check(wf_fill(N_, 0.0, a->data(), nullptr));
-      return a;
-    };
-    u_n = zeros();
-    v_n = zeros();
-    m = zeros();
-    b = zeros();
-    {   // LinearGLL.hpp:102-110: m = M * 1
-      array<double> ones((std::size_t)N_);
-      check(wf_fill(N_, 1.0, ones.data(), nullptr));
-      MassOperatorLumped<double> mass(S, k_);
-      mass.apply(ones.data(), m->data());
-      check(wf_sync(nullptr));
-    }
-    idx1 = upload(gamma1.first);
-    mG1 = upload(gamma1.second);
-    idx2 = upload(gamma2.first);
-    mG2 = upload(gamma2.second);
     std::map<std::string, double> params{{"c0", c0_}};
-    stiff_op = std::make_unique<StiffnessOperator<double>>(S, k_, params, tuning);   // LinearGLL.hpp:120-127
-    stiffness(u_n->data());
+    stiff_op = std::make_unique<StiffnessOperator<double>>(S, k_, params, tuning);
+    setup(MassOperatorLumped<double>(S, k_), gamma1, gamma2);
   }
 
   LinearGLLOpt(const BoxSpace& V_, const std::map<int, int>& facet_tags, int degreeOfBasis, double speedOfSound,
@@ -144,41 +165,7 @@ public:
     if (updater && !part) throw std::runtime_error("LinearGLLOpt: a VectorUpdater needs its BoxPartition");
     set_parameters(degreeOfBasis, speedOfSound, sourceFrequency, pressureAmplitude);
     N_ = V->ndofs();
-    auto zeros = [&]() {
-      auto a = std::make_unique<array<double>>((std::size_t)N_);
-      check(wf_fill(N_, 0.0, a->data(), nullptr));
-      return a;
-    };
-    u_n = zeros();
-    v_n = zeros();
-    m = zeros();
-    b = zeros();
-    // LinearGLL.hpp:102-110: m = M * 1, scatter_rev(add)
-    {
-      array<double> ones((std::size_t)N_);
-      check(wf_fill(N_, 1.0, ones.data(), nullptr));
-      wf_op* mass = nullptr;
-      check(wf_op_create_box(WF_OP_MASS_LUMPED, k_, V->mesh->n[0], V->mesh->n[1], V->mesh->n[2], V->mesh->x.data(), 0.0,
-                             WF_FLAG_NONE, &mass));
-      check(wf_op_apply(mass, ones.data(), m->data(), nullptr));
-      if (updater_) {
-        updater_->update_rev(m->data());
-        updater_->update_fwd(m->data());   // ghost entries of m stay consistent (b / m runs over the whole array)
-      }
-      check(wf_sync(nullptr));
-      wf_op_destroy(mass);
-    }
     // LinearGLL.hpp:113-115: boundary form L
-    auto up_i = [](const std::vector<std::int32_t>& h) {
-      auto a = std::make_unique<array<std::int32_t>>(h.size());
-      a->set(h);
-      return a;
-    };
-    auto up_d = [](const std::vector<double>& h) {
-      auto a = std::make_unique<array<double>>(h.size());
-      a->set(h);
-      return a;
-    };
     auto facet = [&](int tag) {
       auto f = facet_lumped_mass(*V, facet_tags, tag);
       if (!updater_) return f;
@@ -198,21 +185,15 @@ public:
         }
       return out;
     };
-    auto f1 = facet(1);
-    auto f2 = facet(2);
-    idx1 = up_i(f1.first);
-    mG1 = up_d(f1.second);
-    idx2 = up_i(f2.first);
-    mG2 = up_d(f2.second);
-    // LinearGLL.hpp:120-127
-    stiff_op = std::make_unique<BoxStiffnessOperator<double>>(k_, V->mesh->n[0], V->mesh->n[1], V->mesh->n[2],
-                                                              V->mesh->x.data(), c0_);
+    const auto f1 = facet(1), f2 = facet(2);
+    const auto& n = V->mesh->n;
+    stiff_op = std::make_unique<BoxStiffnessOperator<double>>(k_, n[0], n[1], n[2], V->mesh->x.data(), c0_);
     if (updater_) {
       const int rc = wf_op_set_ghost_faces(stiff_op->handle(), part->owned_lo[0], part->owned_lo[1], part->owned_lo[2]);
       if (rc != WF_OK && rc != WF_ERR_UNSUPPORTED) check(rc);
       split_ = rc == WF_OK;
     }
-    stiffness(u_n->data());
+    setup(BoxMassOperatorLumped<double>(k_, n[0], n[1], n[2], V->mesh->x.data()), f1, f2);
   }
 
   ~LinearGLLOpt() { wf_boundary_destroy(bc_); }
@@ -239,12 +220,11 @@ public:
   /// dv/dt = f1(t, u, v)  (LinearGLL.hpp:151-192)
   void f1(double& t, array<double>& u, array<double>& v, array<double>& result)
   {
-    const double g = source(t);
     check(wf_fill(N_, 0.0, b->data(), nullptr));
     stiffness(u.data());        // scatter_fwd(u); K; scatter_rev(b)
     kernels::copy(u, *u_n);
     kernels::copy(v, *v_n);
-    boundary(g, v_n->data());
+    boundary(t, v_n->data());
     check(wf_pointwise_div(N_, b->data(), m->data(), result.data(), nullptr));
   }
 
@@ -307,13 +287,8 @@ public:
     const double c_runge[4] = {0.0, 0.5, 0.5, 1.0};
     // The boundary term of each right-hand side is left in b by the stage kernel in front of it
     // (wf_rk4_stage_bc), the first one by a plain launch: a stage is two launches, stiffness + vector algebra.
-    if (!bc_) {
-      const auto i1 = idx1->copy_to_host(), i2 = idx2->copy_to_host();
-      const auto a1 = mG1->copy_to_host(), a2 = mG2->copy_to_host();
-      check(wf_boundary_create(N_, (std::int32_t)i1.size(), i1.data(), a1.data(), (std::int32_t)i2.size(), i2.data(), a2.data(), &bc_));
-    }
     check(wf_fill(N_, 0.0, b->data(), nullptr));
-    check(wf_boundary_apply_plan(bc_, c0_ * c0_ * source(t), -c0_, v0->data(), b->data(), nullptr));
+    check(wf_boundary_apply_plan(plan(), s1(t), s2(), v0->data(), b->data(), nullptr));
     while (t < tf) {
       dt = std::min(dt, tf - t);
       double* x_u = u0->data();           // stage 0 reads u0 / v0 directly (a_0 = 0)
@@ -325,10 +300,10 @@ public:
         const double* vr = i == 0 ? v0->data() : v_->data();
         const int has_next = i < 3;
         // time of the next right-hand side: the next stage, or stage 0 of the next step
-        const double g_next = source(has_next ? t + c_runge[i + 1] * dt : t + dt);
+        const double s1_next = s1(has_next ? t + c_runge[i + 1] * dt : t + dt);
         check(wf_rk4_stage_bc(N_, dt * b_runge[i], has_next ? dt * a_runge[i + 1] : 0.0, has_next, b->data(), m->data(), x_v,
-                              ur, vr, u_->data(), v_->data(), u0->data(), v0->data(), un->data(), vn_next, bc_,
-                              c0_ * c0_ * g_next, -c0_, nullptr));
+                              ur, vr, u_->data(), v_->data(), u0->data(), v0->data(), un->data(), vn_next, plan(), s1_next,
+                              s2(), nullptr));
         if (has_next) {
           x_u = un->data();
           x_v = vn_next;
@@ -361,29 +336,23 @@ public:
     auto mk = [&]() { return std::make_unique<array<double>>((std::size_t)N_); };
     auto u = mk(), w = mk(), scratch = mk();   // u^n, u^{n-1} (overwritten by u^{n+1}), a^0 / the finishing update
     kernels::copy(*u_n, *u);
-    if (!bc_) {
-      const auto i1 = idx1->copy_to_host(), i2 = idx2->copy_to_host();
-      const auto a1 = mG1->copy_to_host(), a2 = mG2->copy_to_host();
-      check(wf_boundary_create(N_, (std::int32_t)i1.size(), i1.data(), a1.data(), (std::int32_t)i2.size(), i2.data(), a2.data(), &bc_));
-    }
     check(wf_fill(N_, 0.0, b->data(), nullptr));
     stiffness(u->data());
-    check(wf_boundary_apply_plan(bc_, c0_ * c0_ * source(t), -c0_, v_n->data(), b->data(), nullptr));
+    check(wf_boundary_apply_plan(plan(), s1(t), s2(), v_n->data(), b->data(), nullptr));
     check(wf_pointwise_div(N_, b->data(), m->data(), scratch->data(), nullptr));
     kernels::axpy(*w, -dt, *v_n, *u, N_);
     kernels::axpy(*w, 0.5 * dt * dt, *scratch, *w, N_);
     check(wf_fill(N_, 0.0, b->data(), nullptr));
     while (t < tf) {
       stiffness(u->data());
-      check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), w->data(), nullptr, bc_, c0_ * c0_ * source(t),
-                                -c0_, nullptr));
+      check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), w->data(), nullptr, plan(), s1(t), s2(), nullptr));
       std::swap(u, w);
       t += dt;
       step += 1;
     }
     stiffness(u->data());
-    check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), scratch->data(), v_n->data(), bc_,
-                              c0_ * c0_ * source(t), -c0_, nullptr));
+    check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), scratch->data(), v_n->data(), plan(), s1(t),
+                              s2(), nullptr));
     kernels::copy(*u, *u_n);
     finish();
     return step;

@@ -1,4 +1,5 @@
-"""Every path of csrc/vector_kernels.hip, entry by entry, against numpy in long double.
+"""Every path of csrc/vector_kernels.hip and the stage and boundary kernels of csrc/time_step.hip, entry by entry, against
+numpy in long double.
 
 The streaming kernels of the RK4 loop (fill, copy, axpy, scale, pointwise_div, pointwise_mult_add, dot, the boundary
 term, gather / scatter / transform1) and the fused stage `wf_rk4_stage(_bc)` are driven through the C ABI

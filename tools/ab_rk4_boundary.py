@@ -1,5 +1,7 @@
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+"""rk4_fused with the boundary term folded into the stage kernel (LinearGLLOpt.fold_boundary, the default) against a
+boundary launch of its own after every stage: ms per step, best of three."""
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import wave_fenics_amd as w
 from wave_fenics_amd.linear_gll import LinearGLLOpt, cfl_time_step
 dev = torch.device("cuda", 0)

@@ -28,6 +28,7 @@ import torch
 from . import la
 from ._lib import _dp, _ip, check, lib
 from .box import _int3
+from .distributed import overlapped_apply
 from .mesh_io import cfl_time_step  # noqa: F401  (demo/cpu_planar3d/main.cpp:48-66: one function for box and file meshes)
 from .operators import MassOperatorLumped, StiffnessOperator
 
@@ -54,6 +55,11 @@ def facet_lumped_mass(V, tag_of_face, tag: int, cell_weight=None):
 
 
 class LinearGLLOpt:
+    #: rk4_fused: the stage kernel leaves the next right-hand side's boundary term in b (wf_rk4_stage_bc).  False keeps
+    #: the boundary term a launch of its own after each stage kernel, for comparison (tools/ab_rk4_boundary.py).
+    fold_boundary = True
+    _bc = None   # la.BoundaryPlan of the fused loops (_boundary_plan)
+
     def __init__(self, V, degreeOfBasis: int, speedOfSound: float, sourceFrequency: float,
                  pressureAmplitude: float, boundary=None, updater=None, device=None, structured=None,
                  tags=None, tuning=None, medium=None):
@@ -144,45 +150,86 @@ class LinearGLLOpt:
         self.u_n.zero_()
         self.v_n.zero_()
 
+    # ---- the pieces every time loop shares ----
+    def _window(self, t: float) -> float:
+        """The source's start-up ramp over alpha_ periods (LinearGLL.hpp:153-159)."""
+        if t < self.T_ * self.alpha_:
+            return 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * t / self.alpha_))
+        return 1.0
+
+    def _g(self, window: float, t: float) -> float:
+        """g(t) of LinearGLL.hpp:153-162 (no medium: with one g = s1 / c differs from cell to cell and only s1 exists)."""
+        return window * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
+
+    @property
+    def _s2(self) -> float:
+        """Coefficient of the Gamma_2 term: -c0 (LinearGLL.hpp:175); -1 with a medium (admittance-weighted facet masses)."""
+        return -self.c0_ if self.medium is None else -1.0
+
     def _boundary_scalars(self, window: float, t: float):
         """(s1, s2) of the boundary term b[idx1] += s1 mG1, b[idx2] += s2 mG2 v at time t: c0^2 g(t) and -c0
         (LinearGLL.hpp:153-162,175); with a medium window p0 w0 cos(w0 t) and -1 on admittance-weighted facet masses."""
         if self.medium is None:
-            g = window * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
-            return self.c0_ ** 2 * g, -self.c0_
-        return window * self.p0_ * self.w0_ * math.cos(self.w0_ * t), -1.0
+            return self.c0_ ** 2 * self._g(window, t), self._s2
+        return window * self.p0_ * self.w0_ * math.cos(self.w0_ * t), self._s2
+
+    def _s1(self, t: float) -> float:
+        """Coefficient of the Gamma_1 term at time t."""
+        return self._boundary_scalars(self._window(t), t)[0]
+
+    def _s1_fused(self, t: float) -> float:
+        """_s1(t) as rk4_fused rounds it.  Without a medium that loop has always taken the product from left to right,
+        ((c0^2 window) p0 w0 / c0) cos(w0 t), where _boundary_scalars forms c0^2 (window p0 w0 / c0 cos(w0 t)): equal up to
+        the last bit only.  Both spellings stay, so that neither loop's results change."""
+        if self.medium is not None:
+            return self._s1(t)
+        return self.c0_ ** 2 * self._window(t) * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
+
+    def _rhs(self, x, b):
+        """b += K x with the ghost exchange of a partitioned mesh around it: forward halo of x, reverse halo of b."""
+        if self._split:
+            # interior cells beside the halo of x, the interface cells and the reverse halo of b
+            overlapped_apply(self.stiff_op, self.updater, x, b)
+            return
+        if self.updater is not None:
+            self.updater.scatter_fwd(x)
+        self.stiff_op(x, b)
+        if self.updater is not None:
+            self.updater.scatter_rev(b)
+
+    def _boundary_plan(self):
+        """The boundary sets as the fused passes read them (la.BoundaryPlan), built on first use."""
+        if self._bc is None:
+            self._bc = la.BoundaryPlan(self.b.numel(), self.idx1.cpu().numpy(), self.mG1.cpu().numpy(), self.idx2.cpu().numpy(),
+                                       self.mG2.cpu().numpy())
+        return self._bc
 
     def f0(self, t, u, v, result):
         la.copy(v, result)                                   # LinearGLL.hpp:141-144
 
     def f1(self, t, u, v, result):
         # LinearGLL.hpp:151-192
-        if t < self.T_ * self.alpha_:
-            self.window_ = 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * t / self.alpha_))
-        else:
-            self.window_ = 1.0
-        # g(t) of LinearGLL.hpp:153-162; with a medium g = s1 / c differs from cell to cell and only s1 exists
-        self.g_ = self.window_ * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t) if self.medium is None else None
+        self.window_ = self._window(t)
+        self.g_ = self._g(self.window_, t) if self.medium is None else None
         s1, s2 = self._boundary_scalars(self.window_, t)
         if self._split:
             # same operations as below, reordered so that the cells that read no ghost
             # value run while the halo of u is in flight (update_fwd_begin/_end,
             # VectorUpdater.hpp:106-143)
-            from .distributed import overlapped_apply
             la.fill(self.b, 0.0)
-            overlapped_apply(self.stiff_op, self.updater, u, self.b)
+            self._rhs(u, self.b)
             la.boundary_apply(self.idx1, self.mG1, s1, self.idx2, self.mG2, s2, v, self.b)
             la.copy(u, self.u_n)
             la.copy(v, self.v_n)
             la.pointwise_div(self.b, self.m, result)
             return
-        else:
-            if self.updater is not None:
-                self.updater.scatter_fwd(u)
-            la.copy(u, self.u_n)
-            la.copy(v, self.v_n)
-            la.fill(self.b, 0.0)
-            self.stiff_op(self.u_n, self.b)
+        # the reference's order: the apply reads the copy u_n, the reverse halo of b follows the boundary term
+        if self.updater is not None:
+            self.updater.scatter_fwd(u)
+        la.copy(u, self.u_n)
+        la.copy(v, self.v_n)
+        la.fill(self.b, 0.0)
+        self.stiff_op(self.u_n, self.b)
         la.boundary_apply(self.idx1, self.mG1, s1, self.idx2, self.mG2, s2, self.v_n, self.b)
         if self.updater is not None:
             self.updater.scatter_rev(self.b)
@@ -227,201 +274,138 @@ class LinearGLLOpt:
             self.updater.scatter_fwd(self.v_n)
         return t, step
 
+    def rk4_fused(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
+        """The same RK4 integration as rk4() (LinearGLL.hpp:198-287) with the vector
+        algebra between two stiffness applies fused into one pass (wf_rk4_stage_bc) and
+        the stage-0 copies removed by pointer rotation: per stage
+        K (116 B/dof at P4) + 96 B/dof instead of K + 208 B/dof.  The diagonal boundary term
+        of the NEXT right-hand side is left in b by the stage kernel (instead of zeros), so a
+        stage is two launches: stiffness apply, fused vector algebra.  Same arithmetic
+        expressions as the unfused loop (b receives the boundary term before the stiffness
+        contributions instead of after them)."""
+        t, tf, dt = startTime, finalTime, timeStep
+        step = 0
+        new = lambda: torch.zeros_like(self.u_n)
+        u0, v0 = self.u_n.clone(), self.v_n.clone()      # solution at the start of the step
+        u_, v_ = new(), new()                              # running solution of the step
+        un, vn_a, vn_b = new(), new(), new()
+        b, m = self.b, self.m
+        a_runge = [0.0, 0.5, 0.5, 1.0]
+        b_runge = [1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0]
+        c_runge = [0.0, 0.5, 0.5, 1.0]
+        bc, s1, s2, rhs, fold = self._boundary_plan(), self._s1_fused, self._s2, self._rhs, self.fold_boundary
+        la.fill(b, 0.0)
+        bc.apply(s1(t), s2, v0, b)           # boundary term of the first right-hand side; the stage kernels leave the others
+        while t < tf:
+            dt = min(dt, tf - t)
+            # stage 0: un = u0, vn = v0 (a_0 = 0), read straight from u0 / v0
+            x_u, x_v = u0, v0
+            vn_next = vn_a
+            for i in range(4):
+                rhs(x_u, b)                  # b holds the boundary term of this right-hand side on entry
+                last = i == 3
+                ur, vr = (u0, v0) if i == 0 else (u_, v_)
+                if not last:
+                    la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], dt * a_runge[i + 1], u0, v0, un, vn_next,
+                                 bc=bc if fold else None, s1_next=s1(t + c_runge[i + 1] * dt), s2=s2)
+                    if not fold:
+                        bc.apply(s1(t + c_runge[i + 1] * dt), s2, vn_next, b)
+                    x_u, x_v = un, vn_next
+                    vn_next = vn_b if vn_next is vn_a else vn_a
+                else:
+                    # the next right-hand side is stage 0 of the next step: v = the updated solution, time t + dt
+                    # (after the last step b is left holding a boundary term nobody reads; f1 / rk4 zero b themselves)
+                    la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], bc=bc if fold else None, s1_next=s1(t + dt), s2=s2)
+                    if not fold:
+                        bc.apply(s1(t + dt), s2, v_, b)
+            u0, u_ = u_, u0          # the new solution becomes the next step's u0
+            v0, v_ = v_, v0
+            t += dt
+            step += 1
+            if max_steps is not None and step >= max_steps:
+                break
+        la.copy(u0, self.u_n)
+        la.copy(v0, self.v_n)
+        if self.updater is not None:
+            self.updater.scatter_fwd(self.u_n)
+            self.updater.scatter_fwd(self.v_n)
+        return t, step
 
-def _rk4_fused(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
-    """The same RK4 integration as rk4() (LinearGLL.hpp:198-287) with the vector
-    algebra between two stiffness applies fused into one pass (wf_rk4_stage_bc) and
-    the stage-0 copies removed by pointer rotation: per stage
-    K (116 B/dof at P4) + 96 B/dof instead of K + 208 B/dof.  The diagonal boundary term
-    of the NEXT right-hand side is left in b by the stage kernel (instead of zeros), so a
-    stage is two launches: stiffness apply, fused vector algebra.  Same arithmetic
-    expressions as the unfused loop (b receives the boundary term before the stiffness
-    contributions instead of after them)."""
-    from .distributed import overlapped_apply
-    t, tf, dt = startTime, finalTime, timeStep
-    step = 0
-    new = lambda: torch.zeros_like(self.u_n)
-    u0, v0 = self.u_n.clone(), self.v_n.clone()      # solution at the start of the step
-    u_, v_ = new(), new()                              # running solution of the step
-    un, vn_a, vn_b = new(), new(), new()
-    b, m = self.b, self.m
-    a_runge = [0.0, 0.5, 0.5, 1.0]
-    b_runge = [1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0]
-    c_runge = [0.0, 0.5, 0.5, 1.0]
-    upd = self.updater
+    def leapfrog(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
+        """Second-order central-difference (leapfrog, explicit Newmark beta = 0, gamma = 1/2) integration of
+        m u'' + d u' - K u = s1(t) mG1, d = -s2 mG2 scattered to the dofs, from the state (u_n, v_n) to the state
+        (u_n, v_n) like rk4(): ONE stiffness apply and one streaming pass (wf_leapfrog_step_bc, 48 B/dof) per step against
+        the four applies of RK4.  The absorbing term is taken centred, d (u^{n+1} - u^{n-1}) / (2 dt): it is diagonal, so the
+        implicit solve is a division, and the stability limit stays that of the undamped scheme, dt < 2 / sqrt(lambda_max)
+        (stable_time_step) -- RK4 loses stability at dofs that carry several absorbing faces.
 
-    def s1(tn):
-        """c0^2 g(t): the coefficient of the Gamma_1 term (LinearGLL.hpp:153-162)."""
-        if tn < self.T_ * self.alpha_:
-            window = 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * tn / self.alpha_))
-        else:
-            window = 1.0
-        if self.medium is not None:
-            return self._boundary_scalars(window, tn)[0]
-        return self.c0_ ** 2 * window * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * tn)
+        Start-up: a^0 = (K u^0 + s1(t0) mG1 - d v^0) / m and u^{-1} = u^0 - dt v^0 + dt^2/2 a^0 (one apply).  Finish: one more
+        apply and update into a scratch vector give v_n = (u^{n+1} - u^{n-1}) / (2 dt), the central velocity at the final
+        time, without advancing u -- so a run split in two equals the continuous run up to rounding.
 
-    def rhs(x_u):
-        """b += K x_u (+ ghost updates); b holds the boundary term of this right-hand side on entry."""
-        if self._split:
-            # interior cells beside the halo of u, the interface cells and the reverse halo of b
-            overlapped_apply(self.stiff_op, upd, x_u, b)
-            return
-        if upd is not None:
-            upd.scatter_fwd(x_u)
-        self.stiff_op(x_u, b)
-        if upd is not None:
-            upd.scatter_rev(b)
+        The step is constant: steps are counted by `while t < finalTime` and the last step is NOT shortened to land on
+        finalTime (a shortened step would break the two-level recurrence).  Returns (t, steps)."""
+        t, tf, dt = startTime, finalTime, timeStep
+        step = 0
+        b, m = self.b, self.m
+        u = self.u_n.clone()                       # u^n
+        w = torch.zeros_like(u)                    # u^{n-1}, overwritten in place by u^{n+1}
+        scratch = torch.zeros_like(u)
+        bc, s1, s2, rhs = self._boundary_plan(), self._s1, self._s2, self._rhs
+        # start-up: scratch = a^0, w = u^{-1}
+        la.fill(b, 0.0)
+        rhs(u, b)
+        bc.apply(s1(t), s2, self.v_n, b)
+        la.pointwise_div(b, m, scratch)
+        la.axpy(w, -dt, self.v_n, u)
+        la.axpy(w, 0.5 * dt * dt, scratch, w)
+        la.fill(b, 0.0)
+        while t < tf:
+            rhs(u, b)                              # b is zero on entry
+            la.leapfrog_step(b, m, u, w, w, dt, bc=bc, s1=s1(t), s2=s2)
+            u, w = w, u
+            t += dt
+            step += 1
+            if max_steps is not None and step >= max_steps:
+                break
+        # finish: the step after the last one, into scratch, for the central velocity at t
+        rhs(u, b)
+        la.leapfrog_step(b, m, u, w, scratch, dt, v=self.v_n, bc=bc, s1=s1(t), s2=s2)
+        la.copy(u, self.u_n)
+        if self.updater is not None:
+            self.updater.scatter_fwd(self.u_n)
+            self.updater.scatter_fwd(self.v_n)
+        return t, step
 
-    if getattr(self, "_bc", None) is None:
-        self._bc = la.BoundaryPlan(b.numel(), self.idx1.cpu().numpy(), self.mG1.cpu().numpy(), self.idx2.cpu().numpy(),
-                                   self.mG2.cpu().numpy())
-    # fold_boundary = False keeps the boundary term a launch of its own after each stage kernel (for comparison)
-    fold = getattr(self, "fold_boundary", True)
-    bc, s2 = self._bc, -self.c0_ if self.medium is None else -1.0
-    la.fill(b, 0.0)
-    bc.apply(s1(t), s2, v0, b)           # boundary term of the first right-hand side; the stage kernels leave the others
-    while t < tf:
-        dt = min(dt, tf - t)
-        # stage 0: un = u0, vn = v0 (a_0 = 0), read straight from u0 / v0
-        x_u, x_v = u0, v0
-        vn_next = vn_a
-        for i in range(4):
-            rhs(x_u)
-            last = i == 3
-            ur, vr = (u0, v0) if i == 0 else (u_, v_)
-            if not last:
-                la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], dt * a_runge[i + 1], u0, v0, un, vn_next,
-                             bc=bc if fold else None, s1_next=s1(t + c_runge[i + 1] * dt), s2=s2)
-                if not fold:
-                    bc.apply(s1(t + c_runge[i + 1] * dt), s2, vn_next, b)
-                x_u, x_v = un, vn_next
-                vn_next = vn_b if vn_next is vn_a else vn_a
-            else:
-                # the next right-hand side is stage 0 of the next step: v = the updated solution, time t + dt
-                # (after the last step b is left holding a boundary term nobody reads; f1 / rk4 zero b themselves)
-                la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], bc=bc if fold else None, s1_next=s1(t + dt), s2=s2)
-                if not fold:
-                    bc.apply(s1(t + dt), s2, v_, b)
-        u0, u_ = u_, u0          # the new solution becomes the next step's u0
-        v0, v_ = v_, v0
-        t += dt
-        step += 1
-        if max_steps is not None and step >= max_steps:
-            break
-    la.copy(u0, self.u_n)
-    la.copy(v0, self.v_n)
-    if upd is not None:
-        upd.scatter_fwd(self.u_n)
-        upd.scatter_fwd(self.v_n)
-    return t, step
+    def max_eigenvalue(self, iters: int = 100):
+        """Largest eigenvalue of -M^{-1} K (lumped mass, the model's stiffness operator) by `iters` power iterations; the
+        value returned is the Rayleigh quotient -x^T K x / x^T M x of the last iterate.  It approaches lambda_max from
+        BELOW (a Rayleigh quotient never exceeds it): on small P2 and P4 boxes it was 0.9992 and 0.9995 of the converged
+        value after 100 iterations and 0.996 after 50, so keep a safety factor in the step derived from it.  One rank."""
+        if self.updater is not None:
+            raise NotImplementedError("LinearGLLOpt.max_eigenvalue on a partitioned mesh (updater=) is not implemented")
+        if iters < 1:
+            raise ValueError("max_eigenvalue needs at least one iteration")
+        n = self.m.numel()
+        x = torch.from_numpy(np.random.default_rng(0).uniform(-1.0, 1.0, n)).to(self.device)
+        y, mx = torch.zeros_like(x), torch.zeros_like(x)
+        lam = 0.0
+        for _ in range(iters):
+            la.fill(y, 0.0)
+            self.stiff_op(x, y)                                  # y = K x
+            la.fill(mx, 0.0)
+            la.pointwise_mult_add(self.m, x, mx)                 # mx = M x
+            lam = -la.inner_product(x, y) / la.inner_product(x, mx)
+            la.pointwise_div(y, self.m, mx)                      # next iterate M^{-1} K x, normalised
+            nrm = math.sqrt(la.inner_product(mx, mx))
+            if not nrm > 0.0:
+                break
+            la.scale(1.0 / nrm, mx)
+            x, mx = mx, x
+        return lam
 
-
-LinearGLLOpt.rk4_fused = _rk4_fused
-
-
-def _leapfrog(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
-    """Second-order central-difference (leapfrog, explicit Newmark beta = 0, gamma = 1/2) integration of
-    m u'' + d u' - K u = s1(t) mG1, d = -s2 mG2 scattered to the dofs, from the state (u_n, v_n) to the state
-    (u_n, v_n) like rk4(): ONE stiffness apply and one streaming pass (wf_leapfrog_step_bc, 48 B/dof) per step against
-    the four applies of RK4.  The absorbing term is taken centred, d (u^{n+1} - u^{n-1}) / (2 dt): it is diagonal, so the
-    implicit solve is a division, and the stability limit stays that of the undamped scheme, dt < 2 / sqrt(lambda_max)
-    (stable_time_step) -- RK4 loses stability at dofs that carry several absorbing faces.
-
-    Start-up: a^0 = (K u^0 + s1(t0) mG1 - d v^0) / m and u^{-1} = u^0 - dt v^0 + dt^2/2 a^0 (one apply).  Finish: one more
-    apply and update into a scratch vector give v_n = (u^{n+1} - u^{n-1}) / (2 dt), the central velocity at the final
-    time, without advancing u -- so a run split in two equals the continuous run up to rounding.
-
-    The step is constant: steps are counted by `while t < finalTime` and the last step is NOT shortened to land on
-    finalTime (a shortened step would break the two-level recurrence).  Returns (t, steps)."""
-    from .distributed import overlapped_apply
-    t, tf, dt = startTime, finalTime, timeStep
-    step = 0
-    upd = self.updater
-    b, m = self.b, self.m
-    u = self.u_n.clone()                       # u^n
-    w = torch.zeros_like(u)                    # u^{n-1}, overwritten in place by u^{n+1}
-    scratch = torch.zeros_like(u)
-
-    def s1(tn):
-        window = 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * tn / self.alpha_)) if tn < self.T_ * self.alpha_ else 1.0
-        return self._boundary_scalars(window, tn)[0]
-
-    def rhs(x_u):
-        """b += K x_u (+ ghost updates), as in rk4_fused; b is zero on entry"""
-        if self._split:
-            overlapped_apply(self.stiff_op, upd, x_u, b)
-            return
-        if upd is not None:
-            upd.scatter_fwd(x_u)
-        self.stiff_op(x_u, b)
-        if upd is not None:
-            upd.scatter_rev(b)
-
-    if getattr(self, "_bc", None) is None:
-        self._bc = la.BoundaryPlan(b.numel(), self.idx1.cpu().numpy(), self.mG1.cpu().numpy(), self.idx2.cpu().numpy(),
-                                   self.mG2.cpu().numpy())
-    bc, s2 = self._bc, -self.c0_ if self.medium is None else -1.0
-    # start-up: scratch = a^0, w = u^{-1}
-    la.fill(b, 0.0)
-    rhs(u)
-    bc.apply(s1(t), s2, self.v_n, b)
-    la.pointwise_div(b, m, scratch)
-    la.axpy(w, -dt, self.v_n, u)
-    la.axpy(w, 0.5 * dt * dt, scratch, w)
-    la.fill(b, 0.0)
-    while t < tf:
-        rhs(u)
-        la.leapfrog_step(b, m, u, w, w, dt, bc=bc, s1=s1(t), s2=s2)
-        u, w = w, u
-        t += dt
-        step += 1
-        if max_steps is not None and step >= max_steps:
-            break
-    # finish: the step after the last one, into scratch, for the central velocity at t
-    rhs(u)
-    la.leapfrog_step(b, m, u, w, scratch, dt, v=self.v_n, bc=bc, s1=s1(t), s2=s2)
-    la.copy(u, self.u_n)
-    if upd is not None:
-        upd.scatter_fwd(self.u_n)
-        upd.scatter_fwd(self.v_n)
-    return t, step
-
-
-def _max_eigenvalue(self, iters: int = 100):
-    """Largest eigenvalue of -M^{-1} K (lumped mass, the model's stiffness operator) by `iters` power iterations; the
-    value returned is the Rayleigh quotient -x^T K x / x^T M x of the last iterate.  It approaches lambda_max from
-    BELOW (a Rayleigh quotient never exceeds it): on small P2 and P4 boxes it was 0.9992 and 0.9995 of the converged
-    value after 100 iterations and 0.996 after 50, so keep a safety factor in the step derived from it.  One rank."""
-    if self.updater is not None:
-        raise NotImplementedError("LinearGLLOpt.max_eigenvalue on a partitioned mesh (updater=) is not implemented")
-    if iters < 1:
-        raise ValueError("max_eigenvalue needs at least one iteration")
-    n = self.m.numel()
-    x = torch.from_numpy(np.random.default_rng(0).uniform(-1.0, 1.0, n)).to(self.device)
-    y, mx = torch.zeros_like(x), torch.zeros_like(x)
-    lam = 0.0
-    for _ in range(iters):
-        la.fill(y, 0.0)
-        self.stiff_op(x, y)                                  # y = K x
-        la.fill(mx, 0.0)
-        la.pointwise_mult_add(self.m, x, mx)                 # mx = M x
-        lam = -la.inner_product(x, y) / la.inner_product(x, mx)
-        la.pointwise_div(y, self.m, mx)                      # next iterate M^{-1} K x, normalised
-        nrm = math.sqrt(la.inner_product(mx, mx))
-        if not nrm > 0.0:
-            break
-        la.scale(1.0 / nrm, mx)
-        x, mx = mx, x
-    return lam
-
-
-def _stable_time_step(self, safety: float = 0.9, iters: int = 100):
-    """safety * 2 / sqrt(lambda_max(-M^{-1} K)): a stable step of leapfrog() (its limit is 2 / sqrt(lambda_max), with or
-    without the absorbing term).  max_eigenvalue approaches lambda_max from below, so the limit is overestimated by
-    up to ~0.04 % after 100 iterations; safety covers it.  One rank."""
-    return safety * 2.0 / math.sqrt(self.max_eigenvalue(iters))
-
-
-LinearGLLOpt.leapfrog = _leapfrog
-LinearGLLOpt.max_eigenvalue = _max_eigenvalue
-LinearGLLOpt.stable_time_step = _stable_time_step
+    def stable_time_step(self, safety: float = 0.9, iters: int = 100):
+        """safety * 2 / sqrt(lambda_max(-M^{-1} K)): a stable step of leapfrog() (its limit is 2 / sqrt(lambda_max), with or
+        without the absorbing term).  max_eigenvalue approaches lambda_max from below, so the limit is overestimated by
+        up to ~0.04 % after 100 iterations; safety covers it.  One rank."""
+        return safety * 2.0 / math.sqrt(self.max_eigenvalue(iters))
