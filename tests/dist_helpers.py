@@ -50,3 +50,13 @@ def init_pg(rank, world, port, backend="gloo"):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group(backend, rank=rank, world_size=world)
+
+
+def periodic_setup(oracle, n, p, periodic, perturb, hi=(1.0, 1.0, 1.0)):
+    """The one-rank partition of a periodic box, the oracle's mesh and its periodic dof numbering."""
+    from wave_fenics_amd.distributed import create_distributed_box
+    part = create_distributed_box(n, p, 1, 0, hi=hi, perturb=perturb, periodic=periodic, build_dofmap=True)
+    om = oracle.create_box(n, p, hi=hi, perturb=perturb)
+    assert np.array_equal(om.x, part.mesh.x)
+    l2g = oracle.make_periodic(om, periodic)          # local lattice index -> periodic dof number
+    return part, om, l2g

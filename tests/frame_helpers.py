@@ -23,6 +23,9 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from support import oracle_module as _oracle
+from support import relerr  # noqa: F401
+
 FRAMES = ("id", "perm", "xslow", "xslow+perm")
 HI = (1.0, 0.37, 2.3)        # the anisotropic box of test_gpu_parity.test_x_slowest_tensor_order
 PERTURB = 0.2
@@ -177,11 +180,6 @@ def rows_differing(a, b) -> float:
 # ---------------------------------------------------------------------------------------------------------------------
 # meshes: (mesh, V, oracle mesh) with the canonical dofmap
 # ---------------------------------------------------------------------------------------------------------------------
-def _oracle():
-    from oracle import wave_oracle
-    return wave_oracle
-
-
 @functools.lru_cache(maxsize=None)
 def box_of(n, p: int):
     """The anisotropic perturbed box n as a dofmap operator's space."""
@@ -215,7 +213,8 @@ def mesh_case(name: str, p: int):
         return SimpleNamespace(name=name, mesh=c.mesh, V=c.V, om=c.om, p=p, reoriented=False)
     if name in ("sheared", "sheared_random"):
         from idx_cell_helpers import oracle_mesh, random_orientations
-        from test_gpu_affine_geometry import lattice_x, spaces
+        from owner_helpers import spaces
+        from support import lattice_x
         x = lattice_x(*[np.arange(m + 1) * h for m, h in zip(SHEARED_N, SHEARED_H)])
         x[:, 0] += 0.25 * x[:, 1]
         om, V = spaces(o, SHEARED_N, p, x=x)
@@ -325,11 +324,6 @@ def mass_reference(name: str, p: int, kind: str, coeff: bool = False):
     case, t = mesh_case(name, p), mass_canon(name, p, kind)
     detJ = t.detJ if not coeff else np.ascontiguousarray(t.detJ * coefficient(case.om.ncells)[:, None])
     return _vectors(case.om.ndofs, 300 + p, lambda x, y: o.dense_mass_apply(case.om, t.phi, detJ, x, y))
-
-
-def relerr(a, b, scale=None):
-    s = float(np.abs(b).max()) if scale is None else scale
-    return float(np.abs(np.asarray(a) - np.asarray(b)).max() / max(s, 1e-300))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

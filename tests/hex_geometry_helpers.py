@@ -74,8 +74,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
-LD = np.longdouble
-assert np.finfo(LD).eps < 2.0 ** -60, "the reference needs a long double wider than float64"
+from support import LD
+
 U = LD(2.0) ** -53
 T0 = 1e-8                 # half width of the zero window
 T1 = 1e-8 + 1e-5          # of the windows at +-1, as the kernel forms it
@@ -271,7 +271,7 @@ def operator_n(p: int):
 # meshes
 # ---------------------------------------------------------------------------------------------------------------------
 def _uniform(n, h, reverse_x=False):
-    from test_gpu_affine_geometry import lattice_x
+    from support import lattice_x
     ax = [np.arange(m + 1) * hh for m, hh in zip(n, h)]
     if reverse_x:
         ax[0] = -ax[0]
@@ -280,7 +280,7 @@ def _uniform(n, h, reverse_x=False):
 
 def mesh_coordinates(name: str, p: int, n):
     """vertex coordinates of the box `name` on n cells (None: the unit box's own; perturbed boxes are made by spaces)"""
-    from test_gpu_affine_geometry import lattice_x
+    from support import lattice_x
     if name == "sheared":
         x = lattice_x(*[np.arange(m + 1) * 0.125 for m in n])
         x[:, 0] += 0.25 * x[:, 1]
@@ -305,7 +305,7 @@ def mesh_case(name: str, p: int, n=N_ENTRY, structured: bool = True, reorient_se
     import wave_fenics_amd as w
     from oracle import wave_oracle as o
     from wave_fenics_amd import mesh_io
-    from test_gpu_affine_geometry import spaces
+    from owner_helpers import spaces
     if name in ("perturbed", "mirrored", "half_mirrored"):
         om, V = spaces(o, n, p, perturb=0.2)
         if name == "mirrored":

@@ -22,7 +22,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from nonbox_helpers import HOLED_BOX, keep_mask
+from nonbox_helpers import HOLED_BOX, keep_mask, oracle_mesh  # noqa: F401
+from support import lattice_x
 
 N = (6, 3, 5)
 BASE = ("unit", "anisotropic", "graded", "sheared")
@@ -31,11 +32,6 @@ PARITY_MESHES = tuple(f"{b}-{v}" for b in BASE for v in ("asis", "random")) + ("
 HOLED = tuple(f"holed-{m}" for m in ("L", "cavity", "stair", "pillar"))
 # components of G_c as wf_geometry_hex_cell orders them
 COMP = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
-
-
-def lattice_x(vx, vy, vz):
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
 
 
 def box_with(n, x=None, hi=(1.0, 1.0, 1.0), perturb=0.0):
@@ -103,15 +99,6 @@ def is_rectilinear(name: str) -> bool:
 def space(name: str, p: int):
     from wave_fenics_amd import mesh_io
     return mesh_io.create_functionspace(affine_mesh(name), p)
-
-
-def oracle_mesh(mesh, V, cells=None):
-    """The oracle's mesh of (mesh, V), or of the listed cells of it (same dof numbering)."""
-    from oracle import wave_oracle as o
-    gd, dm = np.ascontiguousarray(mesh.geom_dofmap), np.ascontiguousarray(V.dofmap)
-    if cells is not None:
-        gd, dm = np.ascontiguousarray(gd[cells]), np.ascontiguousarray(dm[cells])
-    return o.BoxMesh(None, V.degree, np.ascontiguousarray(mesh.x), gd, dm, V.ndofs, None)
 
 
 def cell_det_sign(mesh) -> np.ndarray:

@@ -20,9 +20,8 @@ Bounds, eps = 2^-52, one rounding = eps/2 of the rounded value, the library eval
   |got - ref| <= 2 eps (|u_next| + |u_prev|) / (2 dt), ref from the u_next the device wrote."""
 import numpy as np
 
-LD = np.longdouble
-assert np.finfo(LD).eps < 2.0 ** -60, "the reference needs a long double wider than float64"
-EPS = 2.0 ** -52
+from support import EPS, LD  # noqa: F401
+
 BOUND_PLAIN, BOUND_BOUNDARY, BOUND_V = 3.0, 5.0, 2.0      # in units of eps * magnitude
 
 

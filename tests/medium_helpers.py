@@ -24,20 +24,13 @@ import numpy as np
 
 import idx_cell_helpers as ich
 import nonbox_helpers as nh
+from support import bits, relerr  # noqa: F401
 
 TOL = 1e-12
 TOL_FORM = 1e-13
 C0 = 1500.0
 GOLDEN = (1.0 + 5.0 ** 0.5) / 2.0
 FIELDS = ("distinct", "slab", "zeros")
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
 
 
 def dof_match(coords_a, coords_b):

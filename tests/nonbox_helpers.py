@@ -18,6 +18,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from support import oracle_module as _oracle
+
 HOLED_BOX = (6, 5, 7)           # 210 cells: the largest mesh of these tests
 # cross-section (BX, BY) of the plan's columns per degree, the defaults: the first entry of a degree in WF_IDX_SHAPES
 # (csrc/stiffness_march_idx.hip, P <= 4), WF_KS_SHAPES (csrc/stiffness_march_ks.hip, P >= 5) and WF_MASS_SHAPES
@@ -27,6 +29,11 @@ STIFFNESS_BLOCK = {1: (8, 8), 2: (7, 4), 3: (4, 4), 4: (5, 2), 5: (3, 1), 6: (2,
 MASS_BLOCK = {1: (8, 8), 2: (7, 4), 3: (4, 4), 4: (4, 2), 5: (2, 2), 6: (2, 2), 7: (2, 1)}
 MASKS = ("L", "cavity", "stair", "pillar")
 PERTURB = 0.2
+
+
+def ORDERED():
+    from wave_fenics_amd._lib import WF_FLAG_ORDERED
+    return WF_FLAG_ORDERED
 
 
 def cell_coords(n) -> np.ndarray:
@@ -102,16 +109,14 @@ def expected_fill(coords, lz: int, block) -> float:
     return len(c) / (len(items) * bx * by * lz)
 
 
-def _oracle():
-    from oracle import wave_oracle
-    return wave_oracle
-
-
-def oracle_mesh(mesh, V):
-    """The oracle's mesh of a (mesh, space) pair, as test_gpu_unstructured.oracle_mesh."""
+def oracle_mesh(mesh, V, cells=None):
+    """The oracle's mesh of a (mesh, space) pair, as test_gpu_unstructured.oracle_mesh, or of the listed cells of it
+    (same dof numbering)."""
     o = _oracle()
-    return o.BoxMesh(None, V.degree, np.ascontiguousarray(mesh.x), np.ascontiguousarray(mesh.geom_dofmap),
-                     np.ascontiguousarray(V.dofmap), V.ndofs, None)
+    gd, dm = np.ascontiguousarray(mesh.geom_dofmap), np.ascontiguousarray(V.dofmap)
+    if cells is not None:
+        gd, dm = np.ascontiguousarray(gd[cells]), np.ascontiguousarray(dm[cells])
+    return o.BoxMesh(None, V.degree, np.ascontiguousarray(mesh.x), gd, dm, V.ndofs, None)
 
 
 def holed_box(n, p: int, keep, route: str, shuffle: int | None = None):

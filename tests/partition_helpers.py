@@ -16,6 +16,7 @@ through dist_helpers.local_to_global, ghosts included."""
 import numpy as np
 
 import leapfrog_helpers as lh
+from support import relerr  # noqa: F401
 
 C0, FREQ, P0 = 1500.0, 0.5e6, 6e4
 STEPS, HI, SEED = 20, (0.01, 0.01, 0.01), 11
@@ -118,10 +119,6 @@ def reference(oracle, case, scheme, scenario, steps=STEPS, halve_mG2=None):
     if halve_mG2 is None:
         _REF[key] = out
     return out
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def to_local(xg, l2g):

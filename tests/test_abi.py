@@ -7,15 +7,9 @@ import re
 import numpy as np
 import pytest
 
+from support import wlib  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def wlib():
-    from wave_fenics_amd import build
-    build.build()
-    from wave_fenics_amd import _lib
-    return _lib
 
 
 def test_header_symbols_exported(wlib):

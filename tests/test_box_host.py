@@ -8,21 +8,9 @@ import numpy as np
 import pytest
 
 import box_helpers as bh
+from support import bits, wpackage as wlib  # noqa: F401
 
 TAGS = {0: 1, 1: 2, 2: 2, 3: 2, 4: 2, 5: 2}
-
-
-@pytest.fixture(scope="module")
-def wlib():
-    from wave_fenics_amd import build
-    build.build()
-    import wave_fenics_amd as w
-    w.lib()
-    return w
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -9,19 +9,12 @@ import numpy as np
 import pytest
 
 import frame_helpers as fh
+from support import wpackage as w  # noqa: F401
 
 STIFFNESS_CASES = [(m, p) for m in ("box", "random_orient", "stair") for p in range(1, 8)] \
     + [(m, p) for m in ("sheared", "sheared_random") for p in range(1, 5)]
 MASS_CASES = [(m, p) for m in ("box", "random_orient") for p in (2, 3, 4, 6)]
 MOVES = 1e-3
-
-
-@pytest.fixture(scope="module")
-def w(oracle):
-    from wave_fenics_amd import build
-    build.build()
-    import wave_fenics_amd
-    return wave_fenics_amd
 
 
 def moved(y, yref):

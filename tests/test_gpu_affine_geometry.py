@@ -7,48 +7,14 @@ per-point geometry forced (1e-13: the two differ only in how G is rounded)."""
 import numpy as np
 import pytest
 
+from owner_helpers import apply_from_zero as apply
+from owner_helpers import spaces
+from support import gpu, lattice_x, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL_ORACLE = 1e-12
 TOL_POINT = 1e-13
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def lattice_x(vx, vy, vz):
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
-
-
-def spaces(oracle, n, p, x=None, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), perturb=0.0):
-    """(oracle mesh, FunctionSpace) of the box n; x replaces the vertex coordinates when given."""
-    import wave_fenics_amd as w
-    om = oracle.create_box(n, p, lo=lo, hi=hi, perturb=perturb)
-    mesh = w.create_box(n, lo=lo, hi=hi, perturb=perturb)
-    if x is not None:
-        om.x = np.ascontiguousarray(x, dtype=np.float64)
-        mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
-    assert np.array_equal(mesh.x, om.x)
-    return om, w.create_functionspace(mesh, p)
-
-
-def apply(op, x, gpu):
-    import torch
-    y = torch.zeros(op.info.ndofs, dtype=torch.float64, device=gpu)
-    op(torch.from_numpy(x).to(gpu), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
 
 
 def check_box(oracle, gpu, p, om, V, expect, seed=0):

@@ -62,6 +62,8 @@ from dataclasses import dataclass
 import numpy as np
 import pytest
 
+from support import cells_per_batch, gpu  # noqa: F401
+
 gpu_test = pytest.mark.gpu
 
 C0 = 1500.0
@@ -79,10 +81,6 @@ BOXES = {1: (81, 81, 80), 2: (62, 61, 61), 3: (47, 46, 46), 4: (38, 37, 37), 5: 
 CASES = ([("mixed", p) for p in range(1, 8)] + [("renumbered", 2), ("renumbered", 6)]
          + [("whole", 2), ("plus_one", 2), ("whole", 5), ("plus_one", 5)])
 case_params = pytest.mark.parametrize("kind,p", CASES, ids=[f"{k}_P{p}" for k, p in CASES])
-
-
-def cells_per_batch(p):
-    return 256 // (p + 1) ** 2
 
 
 def lds_bytes(p):
@@ -247,14 +245,6 @@ def test_reference_slice(oracle, kind, p):
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
 
 
 def apply_twice(op, x, y0, gpu):

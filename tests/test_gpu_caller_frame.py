@@ -54,6 +54,7 @@ import pytest
 
 import frame_helpers as fh
 from guard_helpers import compiled_shapes
+from support import open_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -71,12 +72,8 @@ STATS = {}
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    yield torch.device("cuda", 0)
+    dev = open_gpu()
+    yield dev
     for family, s in STATS.items():
         print(f"FRAME-FAMILY {family}: operators {s['n']} worst oracle {s['oracle']:.3e} worst twin {s['twin']:.3e} "
               f"bitwise twins {s['bitwise']} of {s['twins']}")

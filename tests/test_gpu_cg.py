@@ -8,17 +8,9 @@ import os
 import numpy as np
 import pytest
 
+from support import gpu  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
 
 
 def numpy_cg(A, b, kmax, rtol):

@@ -9,39 +9,10 @@ Tolerances: index work bit-exact; one apply 1e-12; 20 RK4 steps 1e-9."""
 import numpy as np
 import pytest
 
+from dist_helpers import periodic_setup
+from support import comm, gpu, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
-def comm(gpu):
-    from wave_fenics_amd.comm import Comm
-    c = Comm.single()
-    assert c.rccl_version() >= 20000
-    yield c
-    c.close()
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def periodic_setup(oracle, n, p, periodic, perturb, hi=(1.0, 1.0, 1.0)):
-    from wave_fenics_amd.distributed import create_distributed_box
-    part = create_distributed_box(n, p, 1, 0, hi=hi, perturb=perturb, periodic=periodic, build_dofmap=True)
-    om = oracle.create_box(n, p, hi=hi, perturb=perturb)
-    assert np.array_equal(om.x, part.mesh.x)
-    l2g = oracle.make_periodic(om, periodic)          # local lattice index -> periodic dof number
-    return part, om, l2g
 
 
 def test_allreduce_and_barrier(gpu, comm):

@@ -25,6 +25,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import dev, gpu, make, relerr  # noqa: F401
 from test_gpu_unstructured import build_mesh, oracle_mesh
 
 pytestmark = pytest.mark.gpu
@@ -34,31 +35,12 @@ TOL = 1e-12
 ORACLE_VARIANT = {"gll_warped": "gll", "equispaced": "equispaced"}
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-def dev(a, gpu):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
 def npts(quad, qd):
     """Basix' point count of the 1-D rule of degree qd."""
     return max(2, (qd + 4) // 2) if quad == "gll" else (qd + 2) // 2
 
 
-def cells_per_batch(mx):
+def mass_dense_cells_per_batch(mx):
     """Cells per workgroup of k_mass_dense; mirrors mass_dense_cells_per_batch (mass_batch.hip)."""
     return max(1, min(1400 // mx ** 3, 32))
 
@@ -68,17 +50,8 @@ def lds_bytes(p, m, unique):
     batch-unique lists, the unique-dof tile [CB * n^3] (launch_mass_dense)."""
     n = p + 1
     mx = max(n, m)
-    CB = cells_per_batch(mx)
+    CB = mass_dense_cells_per_batch(mx)
     return 8 * (2 * CB * mx ** 3 + m * n + (CB * n ** 3 if unique else 0))
-
-
-def make(oracle, n, p, perturb=0.2):
-    import wave_fenics_amd as w
-    om = oracle.create_box(n, p, perturb=perturb)
-    mesh = w.create_box(n, perturb=perturb)
-    V = w.create_functionspace(mesh, p)
-    assert np.array_equal(V.dofmap, om.dofmap) and np.array_equal(mesh.x, om.x)
-    return om, mesh, V
 
 
 def tables(oracle, om, p, variant, quad, qd):
@@ -141,7 +114,7 @@ def test_rule_vs_oracle(gpu, oracle, p, quad, qd):
     variant = "gll_warped" if p % 2 == 0 else "equispaced"
     m, n = npts(quad, qd), p + 1
     assert m != n
-    CB = cells_per_batch(max(m, n))
+    CB = mass_dense_cells_per_batch(max(m, n))
     om, mesh, V = make(oracle, MESH, p)
     assert CB == 1 or (om.ncells > CB and om.ncells % CB != 0)
     mx, x, op = run_case(gpu, oracle, om, V, p, variant, quad, qd, seed=p * 100 + qd)
@@ -174,7 +147,7 @@ def test_exact_rules_agree(gpu, p):
 @pytest.mark.parametrize("p,quad,qd", [(2, "gauss_jacobi", 6), (4, "gll", 5)])
 def test_one_cell(gpu, oracle, p, quad, qd):
     om, mesh, V = make(oracle, (1, 1, 1), p)
-    assert om.ncells < cells_per_batch(max(p + 1, npts(quad, qd)))
+    assert om.ncells < mass_dense_cells_per_batch(max(p + 1, npts(quad, qd)))
     run_case(gpu, oracle, om, V, p, "gll_warped", quad, qd, seed=5)
 
 
@@ -183,7 +156,7 @@ def test_sixteen_points_above_64k_lds(gpu, oracle, p, n):
     """nq1 = 16 (Gauss of degree 30): the launch raises the workgroup's dynamic LDS limit.
     P3 carries the unique-dof tile, P7 gathers and scatters through the dofmap."""
     m = npts("gauss_jacobi", 30)
-    assert m == 16 and cells_per_batch(m) == 1
+    assert m == 16 and mass_dense_cells_per_batch(m) == 1
     assert lds_bytes(p, m, unique=p <= 3) > 65536
     om, mesh, V = make(oracle, n, p)
     run_case(gpu, oracle, om, V, p, "equispaced", "gauss_jacobi", 30, seed=p)
@@ -194,7 +167,7 @@ def test_grid_stride_batches(gpu, oracle, p, qd, n):
     """More batches than the 2048 workgroups launched: every workgroup loops.  P2 reloads the
     unique-dof tile in each iteration, P4 runs the dofmap path."""
     m = npts("gauss_jacobi", qd)
-    CB = cells_per_batch(max(p + 1, m))
+    CB = mass_dense_cells_per_batch(max(p + 1, m))
     ncells = n[0] * n[1] * n[2]
     nbatch = (ncells + CB - 1) // CB
     assert (m, CB) == {2: (2, 32), 4: (6, 6)}[p]

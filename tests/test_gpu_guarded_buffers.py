@@ -59,9 +59,9 @@ import pytest
 from guard_helpers import MIN_NORMAL, NAN, NEG_ZERO, batch_pad, box_pad, compiled_shapes, guarded
 from nonbox_helpers import STIFFNESS_BLOCK, holed_case
 from nonbox_helpers import oracle_mesh as space_oracle_mesh
-from test_gpu_affine_geometry import lattice_x, spaces
-from test_gpu_dense_mass_rules import make, tables
-from test_gpu_owner_run_table import graded
+from owner_helpers import graded, spaces
+from support import cells_per_batch, gpu, lattice_x, make, owner_columns  # noqa: F401
+from test_gpu_dense_mass_rules import tables
 
 pytestmark = pytest.mark.gpu
 
@@ -79,21 +79,6 @@ BATCH_BOX = {1: (5, 5, 6), 2: (4, 4, 5), 3: (4, 3, 4), 4: (3, 3, 3), 5: (3, 3, 2
 TET_BOX = (3, 2, 2)
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-def cells_per_batch(p):
-    """CB of the column-thread batch kernels (cells_per_batch, csrc/common.h)"""
-    return 256 // (p + 1) ** 2
-
-
 def dense_cells_per_batch(p):
     """CBd of k_mass_dense without unique-dof lists (mass_dense_cells_per_batch, csrc/mass_batch.hip), square table"""
     return max(1, min(1400 // (p + 1) ** 3, 32))
@@ -105,10 +90,6 @@ def segments(nz, lz, lz0):
 
 def columns(n, bx, by):
     return -(-n[0] // bx) * -(-n[1] // by)
-
-
-def owner_columns(n, p, bx, by):
-    return -(-(p * n[0] + 1) // (p * bx)) * -(-(p * n[1] + 1) // (p * by))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -25,25 +25,13 @@ import numpy as np
 import pytest
 
 import hex_geometry_helpers as h
+from support import bits, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LD = h.LD
 INVALID, UNSUPPORTED = -1, -2     # wf_status
 WORST = {}                        # (kernel, case name) -> (worst |got - ref| / bound on the device, case)
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def record(kernel, case, got, ref, bound):

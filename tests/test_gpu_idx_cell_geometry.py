@@ -14,6 +14,7 @@ import pytest
 
 import idx_cell_helpers as h
 from nonbox_helpers import STIFFNESS_BLOCK
+from support import dev, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,21 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL_ORACLE = 1e-12
 TOL_POINT = 1e-13
 C0 = {"c0": 1500.0}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-def dev(a, gpu):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
 
 
 def stiffness(V, p, flags=0, **tuning):

@@ -23,6 +23,7 @@ import pytest
 import leapfrog_helpers as lh
 import test_gpu_vector_kernels as vk
 from leapfrog_helpers import LD
+from support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,15 +32,6 @@ BCS = ["none", "empty", "ends", "pair_both", "pair_even", "pair_odd", "word_seam
        "repeated", "random30"]
 DT, S1, S2 = lh.KERNEL_DT, lh.KERNEL_S1, lh.KERNEL_S2
 WORST = {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
 
 
 def run(gpu, host, shift, has_v, inplace, plan):

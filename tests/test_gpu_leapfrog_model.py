@@ -13,6 +13,7 @@ import pytest
 
 import leapfrog_helpers as lh
 from medium_helpers import relerr
+from support import comm, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,24 +23,6 @@ N, HI = (4, 4, 6), (0.01, 0.01, 0.015)
 STEPS = 20
 TOL = 1e-9
 _REF = {}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
-def comm(gpu):
-    from wave_fenics_amd.comm import Comm
-    c = Comm.single()
-    yield c
-    c.close()
 
 
 def space(oracle, n, p, hi):

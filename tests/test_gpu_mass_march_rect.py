@@ -20,7 +20,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_dense_mass_rules import MESH, ORACLE_VARIANT, ROOT, TOL, apply, dev, make, npts, relerr, tables
+from support import dev, gpu, make, relerr  # noqa: F401
+from test_gpu_dense_mass_rules import MESH, ORACLE_VARIANT, ROOT, TOL, apply, npts, tables
 from test_gpu_unstructured import build_mesh, oracle_mesh
 
 pytestmark = pytest.mark.gpu
@@ -29,16 +30,6 @@ HINT = {"kernel": "mass_march"}
 GAUSS = [(p, "gauss_jacobi", 2 * p + 2) for p in range(1, 7)]     # M = P + 2
 GLL = [(p, "gll", p + 1) for p in range(4, 8)]                    # M = 4, 5, 5, 6 at P4..P7
 COMPILED = {(1, 3), (2, 4), (3, 5), (4, 6), (5, 7), (6, 8), (4, 4), (5, 5), (6, 5), (7, 6)}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
 
 
 def check_march(op, y0, x, mx, gpu, m, what):

@@ -12,6 +12,7 @@ import pytest
 
 import medium_helpers as mh
 from medium_helpers import relerr
+from support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,16 +23,6 @@ N = (4, 4, 6)
 HI = (0.01, 0.01, 0.015)
 FREQ, P0 = 0.5e6, 6e4
 TAGS = {0: 1, 1: 2, 2: 2, 3: 2, 4: 2, 5: 2}     # the default of LinearGLLOpt; oracle.box_facets tags the same way
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
 
 
 def two_layer(mesh, rho_scale=1.0):

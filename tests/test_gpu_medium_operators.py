@@ -11,25 +11,11 @@ import pytest
 
 import medium_helpers as mh
 from medium_helpers import TOL, TOL_FORM, bits, relerr
+from support import dev, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ORDERED, ELEMENTWISE, NO_FABS, NO_CLAMP = 16, 4, 1, 2
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-def dev(a, gpu):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
 
 
 def applied(op, x, gpu, y0=None):

@@ -27,6 +27,8 @@ import numpy as np
 import pytest
 
 import nonbox_helpers as nh
+from nonbox_helpers import ORDERED
+from support import dev, open_gpu, relerr
 from test_gpu_cg import numpy_cg
 
 pytestmark = pytest.mark.gpu
@@ -49,27 +51,14 @@ AUTO = {}                 # (operator, case, degree, lz) -> kernel
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
+    dev = open_gpu()
     t0 = time.time()
-    yield torch.device("cuda", 0)
+    yield dev
     print(f"\nnonbox: wall time of the module {time.time() - t0:.1f} s")
     for (opname, kernel), (err, where) in sorted(WORST.items()):
         print(f"nonbox: worst {opname:10s} {kernel:14s} {err:.3e}  {where}")
     for key, kernel in sorted(AUTO.items(), key=str):
         print(f"nonbox: auto {key} -> {kernel}")
-
-
-def dev(a, gpu):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def record(opname, op, err, where, hint=None):
@@ -85,11 +74,6 @@ def tuning(hint, lz):
     if lz is not None:
         t["lz"] = lz
     return t
-
-
-def ORDERED():
-    from wave_fenics_amd._lib import WF_FLAG_ORDERED
-    return WF_FLAG_ORDERED
 
 
 def ELEMENTWISE():

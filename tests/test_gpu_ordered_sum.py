@@ -15,6 +15,8 @@ multiple of CB.  Every test asserts kernel == "cells_ordered" and update == "ord
 import numpy as np
 import pytest
 
+from nonbox_helpers import ORDERED
+from support import dev, gpu, relerr  # noqa: F401
 from test_gpu_owner_high_degree import DEFAULT, form
 from test_gpu_unstructured import build_mesh, oracle_mesh
 
@@ -23,30 +25,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-12
 # degree -> box (cells); CB = 64, 28, 16, 10, 7, 5, 4
 BOXES = {1: (5, 4, 4), 2: (5, 4, 4), 3: (3, 3, 2), 4: (3, 2, 2), 5: (3, 2, 2), 6: (3, 2, 2), 7: (3, 3, 2)}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-def ORDERED():
-    from wave_fenics_amd._lib import WF_FLAG_ORDERED
-    return WF_FLAG_ORDERED
-
-
-def dev(a, gpu):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def box(oracle, p, perturb=0.2, n=None):

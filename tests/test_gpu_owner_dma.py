@@ -16,21 +16,13 @@ mesh edges, so, following tests/test_gpu_owner_prologue.py and with its helpers:
 import numpy as np
 import pytest
 
+from owner_helpers import owner
+from support import gpu, owner_columns, relerr  # noqa: F401
 from test_gpu_owner_prologue import BOXES, P4_SHAPES, TOL, case, guarded_apply
-from test_gpu_owner_run_table import owner, owner_columns, relerr
 
 pytestmark = pytest.mark.gpu
 
 assert BOXES == [(1, 1, 1), (8, 2, 2), (9, 3, 3), (17, 5, 2)] and TOL == 1e-12
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
 
 
 @pytest.mark.parametrize("n", BOXES, ids=lambda n: "x".join(map(str, n)))

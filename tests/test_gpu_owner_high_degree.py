@@ -13,6 +13,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from dist_helpers import periodic_setup
+from owner_helpers import apply, graded, graded_axes, inputs, reference, spaces, stiffness
+from support import comm, gpu, lattice_x, relerr  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TOL_ORACLE = 1e-12
@@ -24,78 +28,8 @@ DEFAULT = ("march_box", "per_point", "none", "none")
 gpu_test = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
-def comm(gpu):
-    from wave_fenics_amd.comm import Comm
-    c = Comm.single()
-    assert c.rccl_version() >= 20000
-    yield c
-    c.close()
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def lattice_x(vx, vy, vz):
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
-
-
-def spaces(oracle, n, p, x=None, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), perturb=0.0):
-    import wave_fenics_amd as w
-    om = oracle.create_box(n, p, lo=lo, hi=hi, perturb=perturb)
-    mesh = w.create_box(n, lo=lo, hi=hi, perturb=perturb)
-    if x is not None:
-        om.x = np.ascontiguousarray(x, dtype=np.float64)
-        mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
-    return om, w.create_functionspace(mesh, p)
-
-
-def graded_axes(n, seed=11):
-    rng = np.random.default_rng(seed)
-    return [np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 2.0, m))]) for m in n]
-
-
-def graded(oracle, n, p, seed=11):
-    return spaces(oracle, n, p, x=lattice_x(*graded_axes(n, seed)))
-
-
-def stiffness(V, p, flags=0, **tuning):
-    import wave_fenics_amd as w
-    return w.StiffnessOperator(V, p, {"c0": 1500.0}, structured=True, flags=flags, tuning=tuning or None)
-
-
 def form(op):
     return (op.kernel, op.geometry, op.metric, op.update)
-
-
-def apply(op, x, y0, gpu):
-    import torch
-    y = torch.from_numpy(y0.copy()).to(gpu)
-    op(torch.from_numpy(x).to(gpu), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-def inputs(om, seed):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(-1, 1, om.ndofs), rng.uniform(-1, 1, om.ndofs) * 1e6
-
-
-def reference(oracle, om, p, x, y0):
-    y = y0.copy()
-    oracle.StiffnessOperator(om, p)(x, y)
-    return y
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -252,15 +186,6 @@ def test_parts_sum_to_the_full_apply(gpu, oracle, ghost, lz0):
             op.apply_part(x, yb, part)
         torch.cuda.synchronize()
         assert relerr(yb.cpu().numpy(), yall.cpu().numpy()) <= TOL_FORM, mode
-
-
-def periodic_setup(oracle, n, p, periodic, perturb, hi=(1.0, 1.0, 1.0)):
-    from wave_fenics_amd.distributed import create_distributed_box
-    part = create_distributed_box(n, p, 1, 0, hi=hi, perturb=perturb, periodic=periodic, build_dofmap=True)
-    om = oracle.create_box(n, p, hi=hi, perturb=perturb)
-    assert np.array_equal(om.x, part.mesh.x)
-    l2g = oracle.make_periodic(om, periodic)          # local lattice index -> periodic dof number
-    return part, om, l2g
 
 
 @gpu_test

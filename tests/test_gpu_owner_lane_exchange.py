@@ -10,6 +10,9 @@ import itertools
 import numpy as np
 import pytest
 
+from owner_helpers import apply, box, graded, owner
+from support import gpu, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 P = 4
@@ -20,78 +23,12 @@ VARIANTS = {0: "4x4", 1: "8x2", 2: "2x8"}
 PARTIAL = {1: [(9, 3, 3), (8, 2, 2)], 0: [(5, 5, 3), (4, 4, 2)], 2: [(3, 9, 2), (2, 8, 2)]}
 
 
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def graded(oracle, n, seed=11):
-    import wave_fenics_amd as w
-    rng = np.random.default_rng(seed)
-    vx, vy, vz = [np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 2.0, m))]) for m in n]
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    pts = np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
-    lo, hi = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
-    om = oracle.create_box(n, P, lo=lo, hi=hi)
-    om.x = np.ascontiguousarray(pts, dtype=np.float64)
-    mesh = w.create_box(n, lo=lo, hi=hi)
-    mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
-    return om, w.create_functionspace(mesh, P)
-
-
-def stiffness(V, **tuning):
-    import wave_fenics_amd as w
-    return w.StiffnessOperator(V, P, {"c0": 1500.0}, structured=True, tuning=tuning)
-
-
-def owner(V, variant, **tuning):
-    op = stiffness(V, variant=variant, update="owner", **tuning)
-    assert (op.kernel, op.metric, op.update) == ("march_box", "axes", "owner")
-    return op
-
-
-def apply(op, x, y0, gpu):
-    import torch
-    y = torch.from_numpy(y0.copy()).to(gpu)
-    op(torch.from_numpy(np.array(x)).to(gpu), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-_boxes = {}
-
-
-def box(oracle, n, gpu):
-    """One graded box: the spaces, x, y0 at the scale of K x, the oracle's y and the atomic form's, computed once."""
-    if n not in _boxes:
-        om, V = graded(oracle, n)
-        rng = np.random.default_rng(sum(n))
-        x = rng.uniform(-1, 1, om.ndofs)
-        kx = np.zeros(om.ndofs)
-        oracle.StiffnessOperator(om, P)(x, kx)
-        y0 = rng.uniform(-1, 1, om.ndofs) * np.abs(kx).max()
-        atom = stiffness(V, update="atomic")
-        assert atom.update == "atomic"
-        _boxes[n] = (V, x, y0, y0 + kx, apply(atom, x, y0, gpu))
-        for a in _boxes[n][1:]:
-            a.setflags(write=False)
-    return _boxes[n]
-
-
 _matrix = {}
 
 
 def oracle_matrix(oracle):
     if "K" not in _matrix:
-        om, V = graded(oracle, (3, 3, 3), seed=4)
+        om, V = graded(oracle, (3, 3, 3), P, seed=4)
         op = oracle.StiffnessOperator(om, P)
         K = np.zeros((om.ndofs, om.ndofs))
         e = np.zeros(om.ndofs)
@@ -111,7 +48,7 @@ def test_full_matrix(gpu, oracle, variant):
     V, Kref = oracle_matrix(oracle)
     n = V.ndofs
     assert n == 2197
-    op = owner(V, variant)
+    op = owner(V, P, variant=variant)
     X = torch.eye(n, dtype=torch.float64, device=gpu)
     Y = torch.zeros(n, n, dtype=torch.float64, device=gpu)
     for c in range(n):
@@ -128,9 +65,9 @@ def test_full_matrix(gpu, oracle, variant):
 
 @pytest.mark.parametrize("variant,n", [(v, n) for v in sorted(PARTIAL) for n in PARTIAL[v]])
 def test_partial_columns(gpu, oracle, variant, n):
-    V, x, y0, yref, yatom = box(oracle, n, gpu)
+    V, x, y0, yref, yatom = box(oracle, n, P, sum(n), gpu)
     for lz in (1, 2, n[2]):
-        op = owner(V, variant, lz=lz)
+        op = owner(V, P, variant=variant, lz=lz)
         assert op.info.plan_lz == lz
         y = apply(op, x, y0, gpu)
         eo, ea = relerr(y, yref), relerr(y, yatom)
@@ -147,7 +84,7 @@ def test_ghost_split(gpu, oracle, ghost, lz0):
     import torch
     from wave_fenics_amd._lib import WF_PART_INTERFACE, WF_PART_INTERIOR
     n = (9, 3, 3)
-    V, x_np, _, _, _ = box(oracle, n, gpu)
+    V, x_np, _, _, _ = box(oracle, n, P, sum(n), gpu)
     NX, NY, NZ = V.lattice
     lat = np.arange(V.ndofs).reshape(NZ, NY, NX)
     gpos = np.unique(np.concatenate([lat[:, :, 0].ravel() if ghost[0] else [], lat[:, 0, :].ravel() if ghost[1] else [],
@@ -157,7 +94,7 @@ def test_ghost_split(gpu, oracle, ghost, lz0):
     if gpos.size:
         xp[torch.from_numpy(gpos).to(gpu)] = float("nan")
     for variant in sorted(VARIANTS):
-        op = owner(V, variant, lz=3, lz0=lz0)
+        op = owner(V, P, variant=variant, lz=3, lz0=lz0)
         assert op.set_ghost_faces(*[bool(g) for g in ghost])
         assert (op.info.items_interface > 0) == any(ghost)
         yall = torch.zeros_like(x)
@@ -177,8 +114,8 @@ def test_ghost_split(gpu, oracle, ghost, lz0):
 @pytest.mark.parametrize("variant", sorted(VARIANTS))
 def test_repeatable(gpu, oracle, variant):
     import torch
-    V, x_np, y0_np, _, _ = box(oracle, PARTIAL[variant][0], gpu)
-    op = owner(V, variant)
+    V, x_np, y0_np, _, _ = box(oracle, PARTIAL[variant][0], P, sum(PARTIAL[variant][0]), gpu)
+    op = owner(V, P, variant=variant)
     x, y0 = torch.from_numpy(x_np.copy()).to(gpu), torch.from_numpy(y0_np.copy()).to(gpu)
     first = None
     for _ in range(50):

@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 from guard_helpers import MIN_NORMAL, NAN, NEG_ZERO, box_pad, guarded
-from test_gpu_owner_run_table import graded, owner, owner_columns, relerr
+from owner_helpers import graded, owner
+from support import gpu, owner_columns, relerr  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,15 +27,6 @@ BOXES = [(1, 1, 1), (8, 2, 2), (9, 3, 3), (17, 5, 2)]
 # (degree, wf_tuning.variant - 1 or None for the degree's default cross-section)
 FORMS = [(4, 0), (4, 1), (4, 2), (2, None), (6, None)]
 P4_SHAPES = {0: (4, 4), 1: (8, 2), 2: (2, 8)}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
 
 
 _cases = {}

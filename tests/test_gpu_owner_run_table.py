@@ -11,6 +11,9 @@ the re-plan, that of an operator of 3 layers per segment, and the sum of the int
 import numpy as np
 import pytest
 
+from owner_helpers import apply, box, graded, owner
+from support import gpu, owner_columns, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL_ORACLE = 1e-12   # of max|y_ref|, as tests/test_gpu_owner_lane_exchange.py and tests/test_gpu_owner_update.py
@@ -21,71 +24,6 @@ VARIANTS = {0: "4x4", 1: "8x2", 2: "2x8"}
 BOXES_P4 = {0: [(9, 41, 7), (8, 72, 6)], 1: [(17, 21, 7), (16, 36, 6)], 2: [(21, 17, 7), (36, 16, 6)]}
 # default owner cross-sections: P2 8x8, P6 2x3; partial columns in x and y, 33 columns of 7 layers
 BOXES_P = {2: (17, 81, 7), 6: (5, 31, 7)}
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def graded(oracle, n, p, seed=11):
-    import wave_fenics_amd as w
-    rng = np.random.default_rng(seed)
-    vx, vy, vz = [np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 2.0, m))]) for m in n]
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    pts = np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
-    lo, hi = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
-    om = oracle.create_box(n, p, lo=lo, hi=hi)
-    om.x = np.ascontiguousarray(pts, dtype=np.float64)
-    mesh = w.create_box(n, lo=lo, hi=hi)
-    mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
-    return om, w.create_functionspace(mesh, p)
-
-
-def owner(V, p, **tuning):
-    import wave_fenics_amd as w
-    op = w.StiffnessOperator(V, p, {"c0": 1500.0}, structured=True, tuning=dict(update="owner", **tuning))
-    assert (op.kernel, op.metric, op.update) == ("march_box", "axes", "owner")
-    return op
-
-
-def apply(op, x, y0, gpu):
-    import torch
-    y = torch.from_numpy(y0.copy()).to(gpu)
-    op(torch.from_numpy(np.array(x)).to(gpu), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-_boxes = {}
-
-
-def box(oracle, n, p):
-    """One graded box: the space, x, a random y0 at the scale of K x and the oracle's y0 + K x, computed once."""
-    if (n, p) not in _boxes:
-        om, V = graded(oracle, n, p)
-        rng = np.random.default_rng(sum(n) + p)
-        x = rng.uniform(-1, 1, om.ndofs)
-        kx = np.zeros(om.ndofs)
-        oracle.StiffnessOperator(om, p)(x, kx)
-        y0 = rng.uniform(-1, 1, om.ndofs) * np.abs(kx).max()
-        assert np.abs(y0).min() > 0.0
-        _boxes[(n, p)] = (V, x, y0, y0 + kx)
-        for a in _boxes[(n, p)][1:]:
-            a.setflags(write=False)
-    return _boxes[(n, p)]
-
-
-def owner_columns(n, p, bx, by):
-    return -(-(p * n[0] + 1) // (p * bx)) * -(-(p * n[1] + 1) // (p * by))
 
 
 def check_table(op, ncols, nz, bytes_without):
@@ -110,7 +48,7 @@ def check_table(op, ncols, nz, bytes_without):
 def test_p4_bitwise(gpu, oracle, variant, n):
     import wave_fenics_amd as w
     p = 4
-    V, x, y0, yref = box(oracle, n, p)
+    V, x, y0, yref, _ = box(oracle, n, p, sum(n) + p)
     bx, by = {0: (4, 4), 1: (8, 2), 2: (2, 8)}[variant]
     ncols = owner_columns(n, p, bx, by)
     assert ncols == (33 if n[2] == 7 else 57)
@@ -147,7 +85,7 @@ def test_p4_parts_equal_the_replanned_apply(gpu, oracle, variant):
     import torch
     from wave_fenics_amd._lib import WF_PART_INTERFACE, WF_PART_INTERIOR
     p, n = 4, BOXES_P4[variant][0]
-    V, x_np, y0_np, _ = box(oracle, n, p)
+    V, x_np, y0_np, _, _ = box(oracle, n, p, sum(n) + p)
     op = owner(V, p, variant=variant)
     assert op.set_ghost_faces(True, True, True)
     info = op.info
@@ -171,7 +109,7 @@ def test_other_degrees(gpu, oracle, p):
     """P2 and P6 owner operators (the body there does not promise equal bits for a plane at the start and in the middle of
     a run): the re-planned apply against the uniform one and against the oracle."""
     n = BOXES_P[p]
-    V, x, y0, yref = box(oracle, n, p)
+    V, x, y0, yref, _ = box(oracle, n, p, sum(n) + p)
     bx, by = {2: (8, 8), 6: (2, 3)}[p]
     ncols = owner_columns(n, p, bx, by)
     assert ncols == 33
@@ -207,7 +145,7 @@ def test_a_callers_table(gpu, oracle):
     the operator keeps what it had."""
     import wave_fenics_amd as w
     p, variant, n = 4, 1, BOXES_P4[1][0]
-    V, x, y0, _ = box(oracle, n, p)
+    V, x, y0, _, _ = box(oracle, n, p, sum(n) + p)
     ncols = owner_columns(n, p, 8, 2)
     op = owner(V, p, variant=variant)
     before = op.info.device_bytes

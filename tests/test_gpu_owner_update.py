@@ -8,69 +8,13 @@ import itertools
 import numpy as np
 import pytest
 
+from owner_helpers import apply, graded, inputs, reference, spaces, stiffness
+from support import gpu, lattice_x, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL_ORACLE = 1e-12
 TOL_FORM = 1e-13
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def lattice_x(vx, vy, vz):
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
-
-
-def spaces(oracle, n, p, x=None, hi=(1.0, 1.0, 1.0)):
-    import wave_fenics_amd as w
-    lo = (0.0, 0.0, 0.0)
-    om = oracle.create_box(n, p, lo=lo, hi=hi)
-    mesh = w.create_box(n, lo=lo, hi=hi)
-    if x is not None:
-        om.x = np.ascontiguousarray(x, dtype=np.float64)
-        mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
-    return om, w.create_functionspace(mesh, p)
-
-
-def graded(oracle, n, p, seed=11):
-    rng = np.random.default_rng(seed)
-    axes = [np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 2.0, m))]) for m in n]
-    return spaces(oracle, n, p, x=lattice_x(*axes))
-
-
-def stiffness(V, p, flags=0, **tuning):
-    import wave_fenics_amd as w
-    return w.StiffnessOperator(V, p, {"c0": 1500.0}, structured=True, flags=flags, tuning=tuning or None)
-
-
-def apply(op, x, y0, gpu):
-    import torch
-    y = torch.from_numpy(y0.copy()).to(gpu)
-    op(torch.from_numpy(x).to(gpu), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-def inputs(om, seed):
-    rng = np.random.default_rng(seed)
-    return rng.uniform(-1, 1, om.ndofs), rng.uniform(-1, 1, om.ndofs) * 1e6
-
-
-def reference(oracle, om, p, x, y0):
-    y = y0.copy()
-    oracle.StiffnessOperator(om, p)(x, y)
-    return y
 
 
 # nx, ny multiples of the default cross-section (the closing lattice line is a column of its own) and not

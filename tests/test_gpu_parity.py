@@ -10,37 +10,11 @@ import os
 import numpy as np
 import pytest
 
+from support import dev, gpu, make, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def dev(a, gpu, dtype=None):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-    return t if dtype is None else t.to(dtype)
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
-
-
-def make(oracle, n, p, perturb=0.2):
-    import wave_fenics_amd as w
-    om = oracle.create_box(n, p, perturb=perturb)
-    mesh = w.create_box(n, perturb=perturb)
-    V = w.create_functionspace(mesh, p)
-    assert np.array_equal(V.dofmap, om.dofmap) and np.array_equal(mesh.x, om.x)
-    return om, mesh, V
 
 
 @pytest.mark.parametrize("p,n", [(1, (5, 4, 3)), (2, (4, 3, 3)), (3, (3, 3, 2)), (4, (3, 2, 2)), (4, (6, 5, 1)),

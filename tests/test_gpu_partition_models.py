@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import partition_helpers as ph
+from support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +31,6 @@ CPUS = 16                                   # what a run is given; nothing here 
 LEAPFROG = {"lf_box_split": (True, True), "lf_box_unsplit": (True, False), "lf_map_split": (False, True),
             "lf_map_unsplit": (False, False)}          # name: (structured, split)
 APPLY_SEED = 5
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
 
 
 def _worker(rank, world, port, case, dts, q):

@@ -46,7 +46,8 @@ import pytest
 
 from guard_helpers import MIN_NORMAL, NAN, NEG_ZERO, box_pad, guarded
 from nonbox_helpers import STIFFNESS_BLOCK
-from test_gpu_guarded_buffers import C0, KS_SHAPES, MARCH_SHAPES, OWNER_SHAPES, columns, owner_columns, stiffness_box
+from support import bits, gpu, owner_columns  # noqa: F401
+from test_gpu_guarded_buffers import C0, KS_SHAPES, MARCH_SHAPES, OWNER_SHAPES, columns, stiffness_box
 
 pytestmark = pytest.mark.gpu
 
@@ -65,16 +66,6 @@ FAMILIES = {"point": ("perturbed", {"geometry": "per_point"}, ("march_box", "per
             "idx": ("perturbed", {"kernel": "march"}, ("march_idx", "per_point", "none", "none"))}
 OPERATORS = ([(f, p) for f in ("point", "cell_full", "axes_atomic") for p in range(1, 5)] + [("ksplit", p) for p in range(4, 8)]
              + [("owner", p) for p in range(1, 8)] + [("idx", p) for p in (2, 4, 6)])
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
 
 
 def cross_section(family, p):
@@ -114,10 +105,6 @@ def ghost_sets(lattice, p, bx, lz):
             ("segment boundary", lat[p * lz, 1, 1:2], None, False),
             ("below a column", lat[1, 1, p * bx - p:p * bx - p + 1], None, False)]
     return [(name, np.asarray(g, dtype=np.int32), faces, zp) for name, g, faces, zp in sets]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64)
 
 
 class Bench:

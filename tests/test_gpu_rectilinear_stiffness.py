@@ -7,40 +7,14 @@ full-tensor per-cell form and with per-point geometry (1e-13: only the rounding 
 import numpy as np
 import pytest
 
+from owner_helpers import apply_from_zero as apply
+from owner_helpers import spaces, stiffness
+from support import gpu, lattice_x, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TOL_ORACLE = 1e-12
 TOL_FORM = 1e-13
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def lattice_x(vx, vy, vz):
-    Z, Y, X = np.meshgrid(vz, vy, vx, indexing="ij")
-    return np.stack([X.reshape(-1), Y.reshape(-1), Z.reshape(-1)], axis=1).copy()
-
-
-def spaces(oracle, n, p, x=None, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), perturb=0.0):
-    """(oracle mesh, FunctionSpace) of the box n; x replaces the vertex coordinates when given."""
-    import wave_fenics_amd as w
-    om = oracle.create_box(n, p, lo=lo, hi=hi, perturb=perturb)
-    mesh = w.create_box(n, lo=lo, hi=hi, perturb=perturb)
-    if x is not None:
-        om.x = np.ascontiguousarray(x, dtype=np.float64)
-        mesh = w.BoxMesh(mesh.n, om.x.copy(), mesh.geom_dofmap, lo, hi)
-    assert np.array_equal(mesh.x, om.x)
-    return om, w.create_functionspace(mesh, p)
 
 
 def rectilinear(oracle, case, n, p):
@@ -54,19 +28,6 @@ def rectilinear(oracle, case, n, p):
     rng = np.random.default_rng(11)
     axes = [np.concatenate([[0.0], np.cumsum(rng.uniform(0.5, 2.0, m))]) for m in n]
     return spaces(oracle, n, p, x=lattice_x(*axes))
-
-
-def stiffness(V, p, flags=0, **tuning):
-    import wave_fenics_amd as w
-    return w.StiffnessOperator(V, p, {"c0": 1500.0}, structured=True, flags=flags, tuning=tuning or None)
-
-
-def apply(op, x, gpu):
-    import torch
-    y = torch.zeros(op.info.ndofs, dtype=torch.float64, device=gpu)
-    op(torch.from_numpy(x).to(gpu), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
 
 
 # odd sizes: partial columns of every compiled cross-section in x and y

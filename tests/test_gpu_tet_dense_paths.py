@@ -56,14 +56,12 @@ from dataclasses import dataclass, field
 import numpy as np
 import pytest
 
+from support import EPS, LD, gpu, ratio, relerr, wlib  # noqa: F401
+from tet_mass_helpers import NCB, batch_unique, created, cross, generic_parts, lagrange_tables, named_cases, nu_of
+
 gpu_test = pytest.mark.gpu
 
-LD = np.longdouble
-assert np.finfo(LD).eps < 2.0 ** -60, "the reference needs a long double wider than float64"
-
-EPS = 2.0 ** -52
 C0 = 1500.0
-NCB = 64                          # cells per batch (16 per wave, four waves)
 GRID = 512                        # workgroups of the persistent grid
 TOL = 1e-12                       # max-norm tolerance against the float64 oracle
 WIN0, WIN1 = 1e-8, 1e-8 + 1e-5    # half widths of the clamp windows at 0 and at +-1 (np.isclose defaults)
@@ -72,25 +70,6 @@ PAD = 16                          # sentinel entries around a shifted vector
 SENTINEL = -7.0e77
 WORST = {}                        # (nd, nq, NU) -> (worst ratio, its B)
 T0 = time.time()
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
-
-
-@pytest.fixture(scope="module")
-def wlib():
-    """the library for the host-only checks (creation errors precede any launch)"""
-    from wave_fenics_amd import build
-    build.build()
-    from wave_fenics_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -128,27 +107,9 @@ class Case:
         return self.nd + 3 * self.nq + self.v + 8
 
 
-def batch_unique(dm):
-    """unique dofs of every batch of 64 cells, as dense_setup counts them"""
-    return np.array([np.unique(dm[b:b + NCB]).size for b in range(0, dm.shape[0], NCB)])
-
-
-def nu_of(case):
-    return 5 if batch_unique(case.dm).max() <= 5 * 256 else 9
-
-
 def lds_bytes(case):
     QT, KT = (case.nq + 15) // 16, (case.nd + 3) // 4
     return 8 * (3 * 16 * QT * (4 * KT + 2) + 16 * QT + 2 * int(batch_unique(case.dm).max()))
-
-
-def lagrange_tables(p, qdegree=None):
-    """the tables tet.TetStiffnessOperator hands over: P_p on the tetrahedron, collapsed Gauss-Jacobi rule"""
-    from wave_fenics_amd import tet
-    q = 2 * p - 2 if qdegree is None else qdegree
-    X, W = tet.tet_quadrature((q + 2) // 2)
-    _, dphi = tet.tabulate_tet(p, X)
-    return np.ascontiguousarray(tet.clamp101(dphi)), np.ascontiguousarray(W)
 
 
 def vectors(rng, ndofs):
@@ -185,30 +146,18 @@ def mesh_case(name, p, n, *, qdegree=None, perturb=0.2, ncells=None, shuffle=Fal
         inverted = np.ones(gd.shape[0], dtype=bool) if invert >= 1.0 else rng.random(gd.shape[0]) < invert
         swap = (jacobian(xv, gd, np.float64)[3] < 0.0) != inverted
         gd[swap] = gd[swap][:, [0, 2, 1, 3]]
-    dphi, W = lagrange_tables(p, qdegree)
+    q = 2 * p - 2 if qdegree is None else qdegree
+    dphi, W = lagrange_tables(p, (q + 2) // 2, gradients=True)
     x, y0 = vectors(rng, ndofs)
     return Case(name, dphi.shape[2], dphi.shape[1], dphi, W, np.ascontiguousarray(xv), np.ascontiguousarray(gd, dtype=np.int32),
                 np.ascontiguousarray(dm, dtype=np.int32), ndofs, x, y0, inverted)
 
 
 def generic_case(name, nd, nq, ncells, pool, seed):
-    """Tables and weights from a seeded generator on the cells of a perturbed Kuhn box; every cell takes nd distinct
-    dofs out of `pool` (None: dofs of its own), so the sharing is the case's choice."""
-    from wave_fenics_amd import tet
-    V = tet.create_kuhn_box((3, 3, 3), 1, perturb=0.2)
-    rng = np.random.default_rng(seed)
-    cells = rng.permutation(V.ncells)[:ncells]
-    dphi = rng.uniform(-1.0, 1.0, (3, nq, nd))
-    W = rng.uniform(0.5, 1.5, nq) / (6.0 * nq)
-    if pool is None:
-        ndofs = ncells * nd
-        dm = np.arange(ndofs).reshape(ncells, nd)
-    else:
-        ndofs = pool
-        dm = np.stack([rng.choice(pool, nd, replace=False) for _ in range(ncells)])
+    """Gradient tables and weights from a seeded generator (tet_mass_helpers.generic_parts)."""
+    rng, dphi, W, xv, gd, dm, ndofs = generic_parts(nd, nq, ncells, pool, seed, (3, nq, nd))
     x, y0 = vectors(rng, ndofs)
-    return Case(name, nd, nq, dphi, W, np.array(V.x, dtype=np.float64), np.ascontiguousarray(V.geom_dofmap[cells], dtype=np.int32),
-                np.ascontiguousarray(dm, dtype=np.int32), ndofs, x, y0)
+    return Case(name, nd, nq, dphi, W, xv, gd, dm, ndofs, x, y0)
 
 
 def c6(case):
@@ -310,23 +259,12 @@ NU9_CASES = ["P4_scattered", "P4_broken", "g36x64_broken", "P4q4_scattered", "g3
 BIG = {f"P2_b{nb}": functools.partial(mesh_case, f"P2_b{nb}", 2, (26, 26, 25), ncells=nc, seed=nb)
        for nb, nc in BATCH_COUNTS.items()}
 BIG["P4_b513"] = lambda: mesh_case("P4_b513", 4, (18, 18, 17), ncells=513 * NCB, shuffle=True, renumber=True, seed=513)
-
-
-@functools.lru_cache(maxsize=None)
-def small(name):
-    c = SMALL[name]()
-    c.name = name
-    return c
+small = named_cases(SMALL)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # references
 # ---------------------------------------------------------------------------------------------------------------------
-def cross(a, b):
-    return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
-                     a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
-
-
 def jacobian(xv, gd, dtype):
     """columns of J (edge vectors v_j - v_0) and det J of every cell"""
     xc = np.asarray(xv, dtype=dtype)[gd]
@@ -385,19 +323,6 @@ def oracle_apply(oracle, case, clamp):
     return y
 
 
-def ratio(got, ref, mag, B):
-    """worst |got - ref| / (eps mag); every entry must satisfy |got - ref| <= B eps mag (absolute: exact where mag is 0)"""
-    err = np.abs(np.asarray(got, dtype=LD) - ref)
-    ok = err <= B * LD(EPS) * mag
-    pos = mag > 0
-    worst = float(np.max(err[pos] / (LD(EPS) * mag[pos]))) if pos.any() else 0.0
-    return worst, bool(ok.all()), int(np.argmin(ok))
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # the operator through the C ABI
 # ---------------------------------------------------------------------------------------------------------------------
@@ -449,12 +374,6 @@ class DenseOp:
             pass
 
 
-def created(case, flags=0):
-    op = DenseOp(case, flags)
-    assert op.rc == 0, (case.name, op.rc, op.message)
-    return op
-
-
 def record(case, worst):
     key = (case.nd, case.nq, nu_of(case))
     if worst >= WORST.get(key, (-1.0, 0))[0]:
@@ -474,7 +393,7 @@ def check_small(gpu, oracle, name, flags=0, applies=1):
     clamp = not (flags & NO_CLAMP)
     ref, mag = reference(case, clamp)
     yo = oracle_apply(oracle, case, clamp)
-    op = created(case, flags)
+    op = created(case, flags, DenseOp)
     for k in range(applies):
         got = op.host(gpu, case.x, case.y0)
         check_entries(case, got, ref, mag, f"{name} flags {flags} apply {k}")
@@ -688,14 +607,14 @@ def test_alternating_handles_with_different_lds(gpu, oracle):
     alternately: the limit is an attribute of the function, not of the handle"""
     a, b = small("P4_scattered"), small("P4_broken")
     assert lds_bytes(a) != lds_bytes(b) and min(lds_bytes(a), lds_bytes(b)) > 64 * 1024
-    ops = {c.name: created(c) for c in (a, b)}
+    ops = {c.name: created(c, Op=DenseOp) for c in (a, b)}
     refs = {c.name: reference(c, True) for c in (a, b)}
     for k, c in enumerate((a, b, a, b, b, a)):
         got = ops[c.name].host(gpu, c.x, c.y0)
         check_entries(c, got, *refs[c.name], f"alternating, step {k}: {c.name}")
     # and a handle of the NU = 5 instantiation of the same shape in between
     c = small("P4_control")
-    check_entries(c, created(c).host(gpu, c.x, c.y0), *reference(c, True), "alternating: P4_control")
+    check_entries(c, created(c, Op=DenseOp).host(gpu, c.x, c.y0), *reference(c, True), "alternating: P4_control")
     got = ops[a.name].host(gpu, a.x, a.y0)
     check_entries(a, got, *refs[a.name], "alternating, after NU = 5")
 
@@ -732,7 +651,7 @@ def test_8_byte_aligned_vectors(gpu, oracle, name):
     bx, by = torch.from_numpy(hx).to(gpu), torch.from_numpy(hy).to(gpu)
     dx, dy = bx[PAD + 1:PAD + 1 + case.ndofs], by[PAD + 1:PAD + 1 + case.ndofs]
     assert bx.data_ptr() % 16 == 0 and dx.data_ptr() % 16 == 8 and dy.data_ptr() % 16 == 8
-    op = created(case)
+    op = created(case, Op=DenseOp)
     op(dx, dy)
     torch.cuda.synchronize()
     gx, gy = bx.cpu().numpy(), by.cpu().numpy()
@@ -752,7 +671,7 @@ def test_repeatable_to_the_entry_bound(gpu, name):
     sums free, so bitwise equality is not the claim; each apply is itself within B of the reference)"""
     case = small(name)
     ref, mag = reference(case, True)
-    op = created(case)
+    op = created(case, Op=DenseOp)
     a, b = op.host(gpu, case.x, case.y0), op.host(gpu, case.x, case.y0)
     check_entries(case, a, ref, mag, f"{name} first apply")
     check_entries(case, b, ref, mag, f"{name} second apply")
@@ -774,7 +693,7 @@ def test_persistent_loop(gpu, oracle, name):
     nb = int(name.split("_b")[1])
     assert case.nbatch == nb and (nu_of(case) == 9) == name.startswith("P4")
     yo = oracle_apply(oracle, case, True)
-    op = created(case)
+    op = created(case, Op=DenseOp)
     for k in range(2):
         got = op.host(gpu, case.x, case.y0)
         err = relerr(got, yo)

@@ -40,6 +40,7 @@ import time
 import numpy as np
 import pytest
 
+from support import gpu  # noqa: F401
 from tet_mass_helpers import (BIG, EPS, GRID, LD, NCB, NO_FABS, NU9_CASES, ORIENTATION_CASES, PAD, SENTINEL, SMALL, TOL,
                               MassOp, batch_unique, created, det_j, empty_case, lds_bytes, mesh_case, nu_of, ratio, reference,
                               relerr, small, small_reference, upright_of)
@@ -47,15 +48,6 @@ from tet_mass_helpers import (BIG, EPS, GRID, LD, NCB, NO_FABS, NU9_CASES, ORIEN
 gpu_test = pytest.mark.gpu
 WORST = {}                        # (nd, NU) -> (worst ratio, its B)
 T0 = time.time()
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
 
 
 def check_entries(case, got, ref, mag, what, B=None):

@@ -27,29 +27,12 @@ import time
 import numpy as np
 import pytest
 
+from support import dev, gpu, relerr  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    torch.cuda.set_device(0)
-    return torch.device("cuda", 0)
-
-
-def dev(a, gpu):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(gpu)
-
-
-def relerr(a, b):
-    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
 
 
 def build_mesh(kind: str, p: int):

@@ -36,12 +36,10 @@ No entry is skipped or masked; the bounds are absolute, so zero entries need no 
 import numpy as np
 import pytest
 
+from support import EPS, LD, gpu, ratio, relerr  # noqa: F401
+
 gpu_test = pytest.mark.gpu
 
-LD = np.longdouble
-assert np.finfo(LD).eps < 2.0 ** -60, "the reference needs a long double wider than float64"
-
-EPS = 2.0 ** -52
 BOUND = 2.0                      # in units of eps * magnitude
 G = 16                           # sentinel entries in front of and behind every vector
 SENTINEL = -7.0e77               # finite, so that it compares equal to itself
@@ -50,15 +48,6 @@ FULL = 10218313                  # the bench vector length (P4, 54^3 cells), odd
 BDT, ADT = 2.6180339887e-3, 7.853981634e-3
 S1, S2 = 0.8137, -1483.7
 WORST = {}                       # kernel -> worst |got - ref| / (eps * magnitude) seen on the device
-
-
-@pytest.fixture(scope="module")
-def gpu():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    import wave_fenics_amd as w
-    w.lib()
-    return torch.device("cuda", 0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -121,19 +110,8 @@ def junk(n):
     return 777.0 + np.arange(n, dtype=np.float64)
 
 
-def ratio(got, ref, mag):
-    """max |got - ref| / (eps * mag) over the entries; every entry must satisfy |got - ref| <= BOUND * eps * mag
-    (an absolute bound: where mag is 0 the entry has to be exact)."""
-    err = np.abs(np.asarray(got, dtype=LD) - np.asarray(ref, dtype=LD))
-    mag = np.asarray(mag, dtype=LD)
-    ok = err <= BOUND * LD(EPS) * mag
-    pos = mag > 0
-    worst = float(np.max(err[pos] / (LD(EPS) * mag[pos]))) if pos.any() else 0.0
-    return worst, bool(ok.all()), int(np.argmin(ok)) if ok.size else -1
-
-
 def within(kernel, got, ref, mag, what):
-    worst, ok, where = ratio(got, ref, mag)
+    worst, ok, where = ratio(got, ref, mag, BOUND)
     if kernel is not None:
         WORST[kernel] = max(WORST.get(kernel, 0.0), worst)
     assert ok, f"{what}: entry {where} is {worst:.3f} eps of its magnitude from the reference (bound {BOUND})"
@@ -369,7 +347,7 @@ def test_reference_headroom():
                 lo, hi = stage_reference(np.float64, h, BDT, ADT, has_next), stage_reference(LD, h, BDT, ADT, has_next)
                 mag = stage_magnitudes(h, BDT, ADT, has_next)
                 for k in hi:
-                    r, ok, where = ratio(lo[k], hi[k], mag[k])
+                    r, ok, where = ratio(lo[k], hi[k], mag[k], BOUND)
                     assert ok, (n, shape, has_next, k, where, r)
                     worst["stage"] = max(worst["stage"], r)
         for name in SETS:
@@ -378,7 +356,7 @@ def test_reference_headroom():
             vp = values(rng, dofs.size)
             lo, _ = boundary_term(np.float64, c1, c2, S1, S2, vp)
             hi, mag = boundary_term(LD, c1, c2, S1, S2, vp)
-            r, ok, where = ratio(lo, hi, mag)
+            r, ok, where = ratio(lo, hi, mag, BOUND)
             assert ok, (n, name, where, r)
             worst["boundary term"] = max(worst["boundary term"], r)
     for k, r in worst.items():
@@ -759,8 +737,6 @@ def test_full_size(gpu, shift):
 # ---------------------------------------------------------------------------------------------------------------------
 # GPU: operators on vectors that are only 8-byte aligned
 # ---------------------------------------------------------------------------------------------------------------------
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def apply_shifted(op, x, y0, gpu):

@@ -124,7 +124,7 @@ def test_headroom_and_non_vacuity():
             G, d = h.point_geometry_f64(c.mesh.x, c.mesh.geom_dofmap, pts, wts, use_fabs, clamp)
             assert np.all(np.abs(G - r.G) <= 0.5 * r.G_bound) and np.all(np.abs(d - r.detJw) <= 0.5 * r.detJw_bound)
     for p in h.DEGREES:
-        from test_gpu_affine_geometry import lattice_x
+        from support import lattice_x
         c, far = h.mesh_case("far", p), h.reference("far", p, True, False)
         x0 = lattice_x(*[np.arange(m + 1.0) for m in c.n])
         near = h.point_geometry_ld(x0, c.mesh.geom_dofmap, c.pts, c.wts, True, False)

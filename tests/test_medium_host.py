@@ -5,16 +5,7 @@ import numpy as np
 import pytest
 
 import medium_helpers as mh
-
-
-@pytest.fixture(scope="module")
-def wlib():
-    """the library, for host-only entry points (the coefficient checks precede the first device call)"""
-    from wave_fenics_amd import build
-    build.build()
-    import wave_fenics_amd as w
-    w.lib()
-    return w
+from support import wpackage as wlib  # noqa: F401
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import nonbox_helpers as nh
+from support import relerr, wpackage as w  # noqa: F401
 from test_ordered_plan import numpy_plan
 
 # the folded reference against the oracle on the periodic dofmap: the four cases it was measured on (<= 5e-17 of
@@ -16,18 +17,6 @@ FOLD_CASES = [((3, 3, 3), (True, True, True), 2), ((1, 3, 2), (True, False, True
 PERIODIC = [((3, 3, 3), (True, False, False)), ((3, 3, 3), (True, True, True)), ((4, 3, 5), (False, False, True)),
             ((7, 4, 3), (True, True, False)), ((2, 3, 3), (True, False, False)), ((2, 2, 2), (True, True, True)),
             ((1, 3, 3), (True, False, False)), ((3, 3, 1), (False, False, True))]
-
-
-@pytest.fixture(scope="module")
-def w(oracle):
-    from wave_fenics_amd import build
-    build.build()
-    import wave_fenics_amd
-    return wave_fenics_amd
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 # --------------------------------------------------------------------------- the meshes

@@ -6,13 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
-
-@pytest.fixture(scope="module")
-def w():
-    from wave_fenics_amd import build
-    build.build()
-    import wave_fenics_amd
-    return wave_fenics_amd
+from support import wpackage as w  # noqa: F401
 
 
 def numpy_plan(dofmap, ndofs):

@@ -6,20 +6,12 @@ import ctypes
 import numpy as np
 import pytest
 
+from support import wlib  # noqa: F401
 from tet_mass_helpers import (EPS, GRID, LD, NCB, NO_FABS, NU9_CASES, ORDERED, ORIENTATION_CASES, SMALL, SMALL_COUNTS, BIG,
                               Case, MassOp, batch_unique, collapsed_float64, det_j, generic_case, lds_bytes, nu_of, ratio,
                               reference, relerr, small, small_reference, upright_of, TOL)
 
 INVALID, UNSUPPORTED = -1, -2
-
-
-@pytest.fixture(scope="module")
-def wlib():
-    from wave_fenics_amd import build
-    build.build()
-    from wave_fenics_amd import _lib
-    _lib.lib()
-    return _lib
 
 
 def refused(case, status, *words, flags=0, null=None):

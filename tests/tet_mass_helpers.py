@@ -22,10 +22,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-LD = np.longdouble
-assert np.finfo(LD).eps < 2.0 ** -60, "the reference needs a long double wider than float64"
+from support import EPS, LD, ratio, relerr  # noqa: F401
 
-EPS = 2.0 ** -52
 NCB = 64                 # cells per batch (16 per wave, four waves)
 # kMassGridBound = 256 * kMassWgsPerCU of csrc/mass_dense_simplex.hip (the constants under the comment "Workgroups per
 # CU of the persistent grid"): the launch uses min(nbatch, GRID) workgroups.  The persistent-loop cases assume it.
@@ -89,11 +87,14 @@ def lds_bytes(case):
     return 8 * (16 * DT * (4 * KT + 2) + 2 * int(batch_unique(case.dm).max()))
 
 
-def lagrange_tables(p, m):
-    """values of P_p on the tetrahedron at the m^3 points of the collapsed Gauss-Jacobi rule (degree 2 m - 1), unclamped"""
+def lagrange_tables(p, m, gradients=False):
+    """values of P_p on the tetrahedron at the m^3 points of the collapsed Gauss-Jacobi rule (degree 2 m - 1), unclamped;
+    gradients: the clamped gradient tables [3][nq][nd] that tet.TetStiffnessOperator hands over instead"""
     from wave_fenics_amd import tet
     X, W = tet.tet_quadrature(m)
-    phi, _ = tet.tabulate_tet(p, X)
+    phi, dphi = tet.tabulate_tet(p, X)
+    if gradients:
+        return np.ascontiguousarray(tet.clamp101(dphi)), np.ascontiguousarray(W)
     return np.ascontiguousarray(phi, dtype=np.float64), np.ascontiguousarray(W, dtype=np.float64)
 
 
@@ -140,19 +141,6 @@ def collapsed_float64(case, flags=0):
     y = case.y0.copy()
     np.add.at(y, case.dm, (case.x[case.dm] @ A.T) * scales(case, flags, np.float64)[:, None])
     return y
-
-
-def ratio(got, ref, mag, B):
-    """worst |got - ref| / (eps mag); every entry must satisfy |got - ref| <= B eps mag (absolute: exact where mag is 0)"""
-    err = np.abs(np.asarray(got, dtype=LD) - ref)
-    ok = err <= B * LD(EPS) * mag
-    pos = mag > 0
-    worst = float(np.max(err[pos] / (LD(EPS) * mag[pos]))) if pos.any() else 0.0
-    return worst, bool(ok.all()), int(np.argmin(ok))
-
-
-def relerr(a, b):
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def vectors(rng, case_dm, ndofs, typical):
@@ -210,14 +198,15 @@ def mesh_case(name, p, n, *, m=None, perturb=0.2, ncells=None, shuffle=False, re
                 np.ascontiguousarray(dm, dtype=np.int32), ndofs, x, y0, inverted, upright)
 
 
-def generic_case(name, nd, nq, ncells, pool, seed):
-    """Table and (positive) weights from a seeded generator on the cells of a perturbed Kuhn box; every cell takes nd
-    distinct dofs out of `pool` (None: dofs of its own), so the sharing is the case's choice."""
+def generic_parts(nd, nq, ncells, pool, seed, table_shape):
+    """The seeded draws of a generic case on the cells of a perturbed Kuhn box: the generator (for the vectors, drawn
+    last), a table of `table_shape` in (-1, 1), positive weights, vertices, geometry dofmap, dofmap and ndofs.  Every
+    cell takes nd distinct dofs out of `pool` (None: dofs of its own), so the sharing is the case's choice."""
     from wave_fenics_amd import tet
     V = tet.create_kuhn_box((3, 3, 3), 1, perturb=0.2)
     rng = np.random.default_rng(seed)
     cells = rng.permutation(V.ncells)[:ncells]
-    phi = rng.uniform(-1.0, 1.0, (nq, nd))
+    table = rng.uniform(-1.0, 1.0, table_shape)
     W = rng.uniform(0.5, 1.5, nq) / (6.0 * nq)
     if pool is None:
         ndofs = ncells * nd
@@ -227,8 +216,14 @@ def generic_case(name, nd, nq, ncells, pool, seed):
         dm = np.stack([rng.choice(pool, nd, replace=False) for _ in range(ncells)])
     xv = np.array(V.x, dtype=np.float64)
     gd = np.ascontiguousarray(V.geom_dofmap[cells], dtype=np.int32)
+    return rng, table, W, xv, gd, np.ascontiguousarray(dm, dtype=np.int32), ndofs
+
+
+def generic_case(name, nd, nq, ncells, pool, seed):
+    """Table and (positive) weights from a seeded generator (generic_parts)."""
+    rng, phi, W, xv, gd, dm, ndofs = generic_parts(nd, nq, ncells, pool, seed, (nq, nd))
     x, y0 = vectors(rng, dm, ndofs, typical_entry(phi, W, xv, gd))
-    return Case(name, nd, nq, phi, W, xv, gd, np.ascontiguousarray(dm, dtype=np.int32), ndofs, x, y0)
+    return Case(name, nd, nq, phi, W, xv, gd, dm, ndofs, x, y0)
 
 
 def upright_of(case):
@@ -283,11 +278,17 @@ BIG = {
 }
 
 
-@functools.lru_cache(maxsize=None)
-def small(name):
-    c = SMALL[name]()
-    c.name = name
-    return c
+def named_cases(table):
+    """small(name) over a table of case constructors: built once per name, named, shared."""
+    @functools.lru_cache(maxsize=None)
+    def small(name):
+        c = table[name]()
+        c.name = name
+        return c
+    return small
+
+
+small = named_cases(SMALL)
 
 
 @functools.lru_cache(maxsize=None)
@@ -362,7 +363,7 @@ class MassOp:
             pass
 
 
-def created(case, flags=0):
-    op = MassOp(case, flags)
+def created(case, flags=0, Op=MassOp):
+    op = Op(case, flags)
     assert op.rc == 0, (case.name, op.rc, op.message)
     return op
