@@ -2,7 +2,7 @@
 with a one-to-one dof numbering (tests/test_nonbox_host.py, tests/test_gpu_nonbox.py).  No GPU in here.
 
   * holed_box: a perturbed box with cells deleted -- tile positions of the lattice-column plan
-    (csrc/generic_plan.cpp) that no cell covers, away from the end of the mesh.  Two numberings: "subset" keeps
+    (csrc/march_plan.cpp) that no cell covers, away from the end of the mesh.  Two numberings: "subset" keeps
     the box space's dof numbers (the dofs inside the hole stay in the vectors, named by no cell), "topological"
     numbers the remaining mesh afresh (csrc/function_space.cpp).
   * periodic_box: the box space with the dofs of opposite faces identified (oracle.make_periodic): one dof at

@@ -2,7 +2,7 @@
 (builders and references: tests/nonbox_helpers.py; their host side: tests/test_nonbox_host.py).
 
   * HOLED meshes, a 6 x 5 x 7 box with cells deleted (re-entrant corner "L", inclusion "cavity", "stair", "pillar"):
-    the lattice-column plan (csrc/generic_plan.cpp) then has tile positions that no cell covers AWAY from the end of
+    the lattice-column plan (csrc/march_plan.cpp) then has tile positions that no cell covers AWAY from the end of
     the mesh -- a present cell above an absent one inside one work item, items whose first layers are empty, a hole
     between two present slots of a layer.  The plan's own segment rule picks one layer per item on meshes this small,
     so the gaps inside an item appear with wf_tuning.lz fixed (3 and 8; mass: 5).

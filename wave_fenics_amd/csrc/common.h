@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "march_plan.h"
 #include "wavehip.h"
 
 // Diagnostic ablation flags (WF_ABLATE environment variable: skip the scatter, serve geometry from
@@ -230,30 +231,12 @@ inline BoxColumns box_owner_columns(int P, int nx, int ny, int bx, int by)
   return box_columns(P * nx + 1, P * ny + 1, P * bx, P * by);
 }
 inline int box_segments(int nz, int lz, int lz0) { return 1 + (std::max(nz - lz0, 0) + lz - 1) / lz; }
-// indexed marching kernels for arbitrary dofmaps (generic_plan.cpp, stiffness_march_idx.hip, stiffness_march_ks.hip)
-struct MarchPlan {
-  bool ok = false;                      // false: the mesh does not tile into lattice columns
-  int BX = 0, BY = 0, lz = 0, nitems = 0, npatterns = 0, tile_size = 0;
-  int reoriented = 0, ncomponents = 0;  // cells looked at in a rotated / reflected frame; lattice components
-  double fill = 0.0;                    // cells / cell slots
-  std::vector<int32_t> slot_cell;       // [nitems * lz * BX * BY] cell index or -1, slot order [layer][ly][lx]
-  std::vector<uint8_t> cell_orient;     // [ncells] orientation code (orient_decode)
-  std::vector<int32_t> item_base;       // [nitems] smallest dof of the item
-  std::vector<int32_t> item_pattern;    // [nitems]
-  std::vector<int32_t> item_layers;     // [nitems] non-empty layers (<= lz)
-  std::vector<std::array<int32_t, 4>> item_key;   // [nitems] (lattice component, column x, column y, z segment)
-  std::vector<int32_t> pat_off;         // [npatterns][tile_size] dof - base per tile position, -1 = uncovered
-};
+// indexed marching kernels for arbitrary dofmaps (stiffness_march_idx.hip, stiffness_march_ks.hip): the plan is
+// MarchPlan of march_plan.h, this is the view of its device arrays the launchers take
 struct MarchPlanDev {
   int nitems = 0, lz = 0, tile_size = 0, bx = 0, by = 0;
   int32_t *d_item_base = nullptr, *d_item_pattern = nullptr, *d_item_layers = nullptr, *d_pat_off = nullptr;
 };
-// cell orientations: lattice axis m of a cell runs along its own axis raw_axis[m], reversed when flip[m]
-void orient_decode(int code, int raw_axis[3], int flip[3]);
-int orient_local_index(int code, int n, int i, int j, int k);   // raw tensor index of lattice-frame node (i, j, k)
-int orient_sign(int code);                                       // +1 rotation, -1 reflection
-int build_march_plan(int P, size_t ncells, const int32_t* tdm, int BX, int BY, int lz_max, int lz_fixed, bool normalise,
-                     MarchPlan* plan);
 constexpr int OP_KIND_STIFFNESS = 0, OP_KIND_MASS = 1;
 // column cross-section, LDS need and LDS budget (per workgroup) of the indexed marching kernel of (kind, P); the
 // needs of the k-split and the dense-mass kernel themselves: march_ks_lds_bytes, mass_march_lds_bytes (march_column.h)

@@ -41,6 +41,13 @@ class DevArray {
     return WF_OK;
   }
   int upload(const std::vector<T>& host) { return upload(host.data(), host.size()); }
+  // the whole array back on the host
+  int download(std::vector<T>& host) const
+  {
+    host.resize(n_);
+    if (n_) WF_HIP_CHECK(hipMemcpy(host.data(), p_, n_ * sizeof(T), hipMemcpyDeviceToHost));
+    return WF_OK;
+  }
   void reset()
   {
     if (p_) (void)hipFree(p_);

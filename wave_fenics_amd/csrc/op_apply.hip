@@ -288,24 +288,13 @@ int wf_op_set_ghost_dofs(wf_op* op, const int32_t* h_ghost_positions, int32_t ng
       return false;
     });
   }
-  // an item is interface iff its dof tile (base + pattern offsets) contains a ghost position
-  std::vector<int32_t> items[4];
-  const int nit = op->plan.nitems;
-  const size_t tsize = (size_t)op->plan.tile_size;
-  std::vector<int32_t> base(nit), pat(nit), pat_off((size_t)op->plan_patterns * tsize);
-  WF_HIP_CHECK(hipMemcpy(base.data(), op->d_item_base.data(), (size_t)nit * sizeof(int32_t), hipMemcpyDeviceToHost));
-  WF_HIP_CHECK(hipMemcpy(pat.data(), op->d_item_pattern.data(), (size_t)nit * sizeof(int32_t), hipMemcpyDeviceToHost));
-  WF_HIP_CHECK(hipMemcpy(pat_off.data(), op->d_pat_off.data(), pat_off.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (int it = 0; it < nit; ++it) {
-    const int32_t* off = &pat_off[(size_t)pat[it] * tsize];
-    bool iface = false;
-    for (size_t e = 0; e < tsize; ++e)
-      if (off[e] >= 0 && ghost[(size_t)base[it] + off[e]]) {
-        iface = true;
-        break;
-      }
-    items[iface ? 1 : 0].push_back(it);
-  }
+  // the plan's item arrays are read back from the handle's device copies: the handle keeps no host copy
+  std::vector<int32_t> items[4], base, pat, pat_off;
+  int rc;
+  if ((rc = op->d_item_base.download(base)) != WF_OK) return rc;
+  if ((rc = op->d_item_pattern.download(pat)) != WF_OK) return rc;
+  if ((rc = op->d_pat_off.download(pat_off)) != WF_OK) return rc;
+  split_items_by_ghost(base, pat, pat_off, op->plan.tile_size, ghost, items[0], items[1]);
   return set_item_lists(op, items);
 }
 

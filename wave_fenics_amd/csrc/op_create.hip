@@ -69,7 +69,7 @@ int create_mass_diagonal(const wf_op_desc* desc, const CallerFrame& fr, wf_op* o
   return WF_OK;
 }
 
-// ---- path 2: marching over lattice columns found in the caller's mesh (generic_plan.cpp): the default of the
+// ---- path 2: marching over lattice columns found in the caller's mesh (march_plan.cpp): the default of the
 // stiffness operator and of the dense mass with a square 1-D table ----
 
 // stiffness geometry in slot order [item][layer][ly][lx]; missing cells stay zero (they contribute nothing)
@@ -81,22 +81,14 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
   const size_t nslots = (size_t)plan.nitems * plan.lz * CB;
   int rc;
   if (h_Gc) {
-    // G_c of a cell seen in the lattice frame, as h_G below: G'[a][b] = s_a s_b G[r_a][r_b].  Without fabs G_c carries
+    // G_c of a cell seen in the lattice frame, as h_G below (orient_tensor).  Without fabs G_c carries
     // the sign of the cell's own det J, which is what the per-point path restores with orient_sign.
     if ((rc = upload_derivative_tables(op, true)) != WF_OK) return rc;
-    static const int comp[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
-    static const int sym[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
     std::vector<double> blk(nslots * 6, 0.0);
     for (size_t q = 0; q < nslots; ++q) {
       const int32_t c = plan.slot_cell[q];
       if (c < 0) continue;
-      int ra[3], fl[3];
-      orient_decode(plan.cell_orient[c], ra, fl);
-      for (int m = 0; m < 6; ++m) {
-        const int a = comp[m][0], b2 = comp[m][1];
-        const double g = h_Gc[(size_t)c * 6 + sym[ra[a]][ra[b2]]];
-        blk[q * 6 + m] = (fl[a] ^ fl[b2]) ? -g : g;
-      }
+      orient_tensor(plan.cell_orient[c], kSym6, h_Gc + (size_t)c * 6, &blk[q * 6]);
       if (desc->h_cell_coeff)   // the cell coefficient follows the cell into its slot
         for (int m = 0; m < 6; ++m) blk[q * 6 + m] *= desc->h_cell_coeff[c];
     }
@@ -109,9 +101,7 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
   if ((rc = op->d_G6blk.alloc(g6)) != WF_OK) return rc;
   WF_HIP_CHECK(hipMemset(op->d_G6blk.data(), 0, g6 * sizeof(double)));
   if (desc->h_G) {
-    // G of a cell seen in the lattice frame: G'[a][b] = s_a s_b G[r_a][r_b] (r = the cell's own axis
-    // along lattice axis a, s = -1 when reversed) at the relabelled point -- the operator
-    // D^T G D is the same in every frame
+    // G of a cell seen in the lattice frame (orient_tensor) at the relabelled point
     PointMaps point_map{fr, n};
     auto fill_slot_plain = [&](size_t slot, double* dst) {
       const int32_t c = plan.slot_cell[slot];
@@ -126,13 +116,7 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
         for (int pt = 0; pt < nd; ++pt) std::memcpy(dst + (size_t)pt * 9, gsrc + (size_t)pm[pt] * 9, 9 * sizeof(double));
         return;
       }
-      int ra[3], fl[3];
-      orient_decode(code, ra, fl);
-      for (int pt = 0; pt < nd; ++pt) {
-        const double* g9 = gsrc + (size_t)pm[pt] * 9;
-        for (int a = 0; a < 3; ++a)
-          for (int b2 = 0; b2 < 3; ++b2) dst[pt * 9 + a * 3 + b2] = ((fl[a] ^ fl[b2]) ? -1.0 : 1.0) * g9[ra[a] * 3 + ra[b2]];
-      }
+      for (int pt = 0; pt < nd; ++pt) orient_tensor(code, kFull9, gsrc + (size_t)pm[pt] * 9, dst + (size_t)pt * 9);
     };
     auto fill_slot = [&](size_t slot, double* dst) {
       fill_slot_plain(slot, dst);
@@ -155,8 +139,8 @@ int plan_stiffness_geometry(const wf_op_desc* desc, const CallerFrame& fr, const
       const int32_t c = plan.slot_cell[q];
       if (c < 0) continue;
       const int code = plan.cell_orient[c];
-      const int32_t* gsrc = desc->h_geom_dofmap + (size_t)c * 8;
-      for (int v = 0; v < 8; ++v) gd.push_back(gsrc[orient_local_index(code, 2, v & 1, (v >> 1) & 1, (v >> 2) & 1)]);
+      gd.resize(gd.size() + 8);
+      orient_vertices(code, desc->h_geom_dofmap + (size_t)c * 8, &gd[gd.size() - 8]);
       slot_of.push_back((int32_t)q);
       sign.push_back((uint8_t)(int8_t)orient_sign(code));
       if (desc->h_cell_coeff) coeff.push_back(desc->h_cell_coeff[c]);
@@ -192,6 +176,7 @@ int plan_mass_detJ(const wf_op_desc* desc, const CallerFrame& fr, const MarchPla
   int rc;
   if ((rc = host_detJ(desc, hd, &hsrc, &raw_points)) != WF_OK) return rc;
   PointMaps point_map{fr, M};
+  OrientMaps raw_map{M};   // hd is in the cells' own frames: the orientation alone
   std::vector<double> blk(nslots * nq, 0.0);
   for (size_t q = 0; q < nslots; ++q) {
     const int32_t c = plan.slot_cell[q];
@@ -199,12 +184,9 @@ int plan_mass_detJ(const wf_op_desc* desc, const CallerFrame& fr, const MarchPla
     const int code = plan.cell_orient[c];
     const size_t sub = q / CB, sl = q % CB;
     const double* src = hsrc + (size_t)c * nq;
+    const std::vector<int32_t>& pm = raw_points ? raw_map(code) : point_map(code);
     for (int k = 0; k < M; ++k)
-      for (int ji = 0; ji < M * M; ++ji) {
-        const int l = ji + M * M * k;
-        const int rp = raw_points ? orient_local_index(code, M, l % M, (l / M) % M, l / (M * M)) : point_map(code)[l];
-        blk[(sub * M + k) * NTq + sl * M * M + ji] = src[rp];
-      }
+      for (int ji = 0; ji < M * M; ++ji) blk[(sub * M + k) * NTq + sl * M * M + ji] = src[pm[ji + M * M * k]];
   }
   // A non-symmetric 1-D table kept the caller's frames (normalise in create_on_plan).
   if ((rc = op->d_detJ.upload(blk)) != WF_OK) return rc;
@@ -252,13 +234,14 @@ int create_on_plan(const wf_op_desc* desc, const CallerFrame& fr, const int32_t*
   // marching kernel would read geometry for every slot -- batch kernel instead (per-cell geometry is 48 B per slot)
   const bool forced = tun.kernel == WF_KERNEL_FORCE_MARCH || tun.kernel == WF_KERNEL_FORCE_MASS_MARCH || h_Gc;
   if (plan.ok && plan.fill < kMinPlanFill && !forced) plan.ok = false;
+  const std::string why = std::string(": ") + plan_reason_text(plan.reason);
   if (!plan.ok && mass && M != n) {   // a rectangular table is here on request only
     set_error("wf_op_create: WF_KERNEL_FORCE_MASS_MARCH: the mesh does not tile into lattice columns ((P, nq1) = ("
-              + std::to_string(P) + ", " + std::to_string(M) + "))");
+              + std::to_string(P) + ", " + std::to_string(M) + "))" + why);
     return WF_ERR_UNSUPPORTED;
   }
   if (!plan.ok && h_Gc) {
-    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: the mesh does not tile into lattice columns");
+    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: the mesh does not tile into lattice columns" + why);
     return WF_ERR_UNSUPPORTED;
   }
   if (!plan.ok) return WF_OK;

@@ -237,13 +237,30 @@ const std::vector<int32_t>& PointMaps::operator()(int code)
 {
   auto& m = maps[code];
   if (m.empty()) {
-    const std::vector<int32_t> qm = fr.qmap(n);
-    m.resize((size_t)n * n * n);
-    for (int k = 0; k < n; ++k)
-      for (int j = 0; j < n; ++j)
-        for (int i = 0; i < n; ++i) m[i + n * (j + n * k)] = qm[orient_local_index(code, n, i, j, k)];
+    const std::vector<int32_t> qm = fr.qmap(n), om = orient_node_map(code, n);
+    m.resize(om.size());
+    for (size_t l = 0; l < om.size(); ++l) m[l] = qm[om[l]];
   }
   return m;
 }
 
 }  // namespace wf
+
+// The dof numbering that follows the lattice plan of the stiffness operator (plan_numbering, march_plan.h).
+// h_dofmap: tensor-ordered (x fastest) [ncells][(P+1)^3]; h_new_of_old[ndofs]: new index of every old dof.
+extern "C" int wf_lattice_numbering(int degree, int64_t ncells, int32_t ndofs, const int32_t* h_dofmap, int32_t* h_new_of_old)
+{
+  using namespace wf;
+  WF_REQUIRE(degree >= 1 && degree <= 7, "wf_lattice_numbering: degree must be 1..7");
+  WF_REQUIRE(ncells >= 0 && ndofs >= 0 && (ncells == 0 || h_dofmap) && (ndofs == 0 || h_new_of_old), "wf_lattice_numbering: bad arguments");
+  const int P = degree, n = P + 1, nd = n * n * n;
+  for (int64_t e = 0; e < ncells * nd; ++e)
+    WF_REQUIRE(h_dofmap[e] >= 0 && h_dofmap[e] < ndofs, "wf_lattice_numbering: dofmap entry out of range");
+  int BX = 0, BY = 0;
+  march_idx_shape(OP_KIND_STIFFNESS, P, &BX, &BY);
+  MarchPlan plan;
+  int rc = build_march_plan(P, (size_t)ncells, h_dofmap, BX, BY, 8, 8, true, &plan);
+  if (rc != WF_OK) return rc;
+  plan_numbering(plan, (size_t)ncells, nd, h_dofmap, ndofs, h_new_of_old);
+  return WF_OK;
+}

@@ -164,7 +164,7 @@ _AXIS_PERMS = [(0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)]
 
 def orientation_vertex_map(code: int) -> np.ndarray:
     """Vertex relabelling of one of the 48 orientations of the reference cube (code = 8 * perm +
-    flips, the convention of csrc/generic_plan.cpp): new local vertex v' (bits along the new axes)
+    flips, the convention of csrc/march_plan.cpp): new local vertex v' (bits along the new axes)
     is old vertex map[v']: new axis m runs along old axis perm[m], reversed if bit m of flips."""
     perm, flips = _AXIS_PERMS[code >> 3], code & 7
     out = np.zeros(8, dtype=np.int64)
