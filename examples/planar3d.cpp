@@ -9,7 +9,7 @@
 //   planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]]
 //            [--size N] [--degree P] [--cfl C] [--steps S] [--length L] [--dump FILE]
 //            [--periodic xyz] [--reference-order] [--markers] [--geometry auto|per_point|per_cell]
-//            [--scheme rk4|leapfrog]
+//            [--scheme rk4|leapfrog] [--amplitude P0] [--source x,y,z,f] [--receiver x,y,z]... [--traces FILE]
 //
 // One process per GPU: with WORLD_SIZE > 1 in the environment (RANK, LOCAL_RANK,
 // MASTER_PORT as torchrun exports them) --size is the number of cells per edge PER
@@ -22,6 +22,10 @@
 // --scheme leapfrog runs LinearGLLOpt::leapfrog, the second-order central-difference scheme (one stiffness apply per
 // step, constant step) instead of RK4; rk4 is the default.
 // --dump writes u_n then v_n of this rank (float64, local lattice order).
+// --amplitude sets the pressure amplitude of the plane source on Gamma_1 (60000 Pa; 0 silences it).
+// --source adds a point source s(t) delta(x - (x,y,z)), a Ricker wavelet of frequency f, unit amplitude and delay 1.5/f;
+// --receiver (repeatable) records u at a point at the start time and after every step; --traces writes the record as
+// text, one row per recorded time: t, then one column per receiver (%.17g).  One rank.
 // --geometry (with --mesh): how the stiffness operator stores its geometry (wf_tuning.geometry).  per_cell asks for one
 // G_c per cell -- degrees 1 to 4, every cell affine, else an error -- and prints what was built; auto is the default.
 #include <chrono>
@@ -42,6 +46,20 @@ int main(int argc, char* argv[])
   std::array<bool, 3> periodic{false, false, false};
   bool reference_order = false, markers = false, leapfrog = false;
   int geometry = WF_GEOMETRY_AUTO;
+  double amplitude = 60000;
+  const char* traces = nullptr;
+  std::vector<std::array<double, 3>> source_xyz, receiver_xyz;
+  std::vector<wf_wavelet> wavelets;
+  auto numbers = [](const char* text, int count, double* out) {   // "a,b,c": exactly count numbers
+    char* end = nullptr;
+    for (int k = 0; k < count; ++k) {
+      out[k] = std::strtod(text, &end);
+      if (end == text || *end != (k + 1 < count ? ',' : '\0')) return false;
+      text = end + 1;
+    }
+    return true;
+  };
+  bool bad_numbers = false;
   for (int i = 1; i < argc; ++i) {
     auto is = [&](const char* f) { return std::strcmp(argv[i], f) == 0 && i + 1 < argc; };
     if (is("--size")) size = std::atoi(argv[++i]);
@@ -51,6 +69,24 @@ int main(int argc, char* argv[])
     else if (is("--length")) domainLength = std::atof(argv[++i]);
     else if (is("--dump")) dump = argv[++i];
     else if (is("--mesh")) mesh_file = argv[++i];
+    else if (is("--amplitude")) amplitude = std::atof(argv[++i]);
+    else if (is("--traces")) traces = argv[++i];
+    else if (is("--source")) {
+      double v[4] = {0.0, 0.0, 0.0, 0.0};
+      if (!numbers(argv[++i], 4, v) || !(v[3] > 0.0)) {
+        bad_numbers = true;
+        break;
+      }
+      source_xyz.push_back({v[0], v[1], v[2]});
+      wavelets.push_back(wavehip::ricker(v[3], 1.5 / v[3]));
+    } else if (is("--receiver")) {
+      double v[3] = {0.0, 0.0, 0.0};
+      if (!numbers(argv[++i], 3, v)) {
+        bad_numbers = true;
+        break;
+      }
+      receiver_xyz.push_back({v[0], v[1], v[2]});
+    }
     else if (is("--grid")) grid_name = argv[++i];
     else if (is("--tags")) tags_name = argv[++i];
     else if (std::strcmp(argv[i], "--markers") == 0) markers = true;
@@ -66,10 +102,37 @@ int main(int argc, char* argv[])
     else {
       std::cerr << "usage: planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]] [--size N] [--degree P] [--cfl C]"
                    " [--steps S] [--length L] [--dump FILE] [--periodic xyz] [--reference-order] [--markers]"
-                   " [--geometry auto|per_point|per_cell] [--scheme rk4|leapfrog]\n";
+                   " [--geometry auto|per_point|per_cell] [--scheme rk4|leapfrog] [--amplitude P0] [--source x,y,z,f]"
+                   " [--receiver x,y,z]... [--traces FILE]\n";
       return 2;
     }
   }
+  if (bad_numbers || (traces && receiver_xyz.empty())) {
+    std::cerr << "usage: --source x,y,z,f (f > 0), --receiver x,y,z; --traces needs a --receiver\n";
+    return 2;
+  }
+  // the point sources and receivers of a model on the space S; the record as text
+  std::unique_ptr<wavehip::Sources> sources;
+  std::unique_ptr<wavehip::Receivers> receivers;
+  auto attach_points = [&](wavehip::LinearGLLOpt& eqn, const wavehip::Space& S) {
+    if (!source_xyz.empty()) sources = std::make_unique<wavehip::Sources>(S, source_xyz, wavelets);
+    if (!receiver_xyz.empty()) receivers = std::make_unique<wavehip::Receivers>(S, receiver_xyz);
+    eqn.set_sources(sources.get());
+    eqn.set_receivers(receivers.get());
+  };
+  auto write_traces = [&]() {
+    if (!traces) return;
+    FILE* f = std::fopen(traces, "w");
+    if (!f) throw std::runtime_error("cannot open traces file");
+    const auto rows = receivers->traces();
+    const std::size_t R = (std::size_t)receivers->size();
+    for (std::size_t r = 0; r < receivers->rows(); ++r) {
+      std::fprintf(f, "%.17g", receivers->times()[r]);
+      for (std::size_t c = 0; c < R; ++c) std::fprintf(f, " %.17g", rows[r * R + c]);
+      std::fprintf(f, "\n");
+    }
+    std::fclose(f);
+  };
   try {
     std::cout.precision(15);
     const int world = wavehip::Comm::env_int("WORLD_SIZE", 1), rank = wavehip::Comm::env_int("RANK", 0);
@@ -82,7 +145,7 @@ int main(int argc, char* argv[])
     // Material / source parameters (demo/cpu_planar3d/main.cpp:25-33)
     double speedOfSound = 1500.0;
     double sourceFrequency = 0.5e6;
-    double pressureAmplitude = 60000;
+    double pressureAmplitude = amplitude;
     double period = 1 / sourceFrequency;
     if (markers) wavehip::check(wf_markers_enable(1));   // roctx ranges (nvtxMarkA in demo/gpu_scatter_mpi/main.cpp:101-121)
 
@@ -109,6 +172,7 @@ int main(int argc, char* argv[])
       }
       std::cout << "Number of steps: " << nstep << std::endl;
       std::cout << "Degrees of freedom: " << V.ndofs << std::endl;
+      attach_points(eqn, V.space());
       eqn.init();
       auto t0 = std::chrono::steady_clock::now();
       int steps = leapfrog          ? eqn.leapfrog(startTime, finalTime, timeStepSize)
@@ -127,6 +191,7 @@ int main(int argc, char* argv[])
         std::fwrite(v.data(), sizeof(double), v.size(), f);
         std::fclose(f);
       }
+      write_traces();
       return 0;
     }
 
@@ -159,6 +224,12 @@ int main(int argc, char* argv[])
       std::cout << "Degrees of freedom: " << part->size_global << std::endl;
     }
 
+    wavehip::BoxSpace Vpoints;   // the box space WITH its dofmap, which the point location reads
+    if (!source_xyz.empty() || !receiver_xyz.empty()) {
+      if (exchange) throw std::runtime_error("--source / --receiver run on one rank");
+      Vpoints = wavehip::create_functionspace(mesh, degreeOfBasis);
+      attach_points(eqn, Vpoints.space());
+    }
     eqn.init();
     if (comm) comm->barrier();
     auto t0 = std::chrono::steady_clock::now();
@@ -183,6 +254,7 @@ int main(int argc, char* argv[])
       std::fwrite(v.data(), sizeof(double), v.size(), f);
       std::fclose(f);
     }
+    write_traces();
   } catch (const std::exception& e) {
     std::cerr << "error: " << e.what() << std::endl;
     return 1;

@@ -775,6 +775,68 @@ int wf_box_partition(const int* n, int degree, int nproc, int rank, const int* p
                      wf_box_partition_info* info, int* send_neighbors, int32_t* send_offsets, int32_t* send_indices,
                      int* recv_neighbors, int32_t* recv_offsets, int32_t* ghost_positions);
 
+/* ---- point sources and receivers ---------------------------------------------------------------
+ * Not in the reference (its only source is the plane term of Gamma_1, its only output a whole vector).
+ *
+ * Host, no device call (point_locate.cpp):
+ * wf_points_locate: the cell and the reference coordinates of each of npoints physical points h_xyz [npoints][3] in
+ *   the hexahedral mesh h_xverts [nverts][3], h_cells [ncells][8] (vertex v = a + 2b + 4c, as wf_geometry_hex).
+ *   Reference coordinates are those of wf_tabulate_gll and wf_geometry_hex: xi in [0, 1]^3.  The trilinear map of the
+ *   cell is inverted by Newton's method from the cell centre (at most 20 iterations); a cell accepts the point when
+ *   the iteration converges and max |2 xi - 1| <= 1 + tol, i.e. every coordinate lies in [-tol/2, 1 + tol/2]; xi is
+ *   then clamped to [0, 1].  A point on a face, edge or vertex shared by several cells goes to the LOWEST cell index.
+ *   h_cell [npoints] receives the cell or -1 (in no cell: not an error of the call), h_ref [npoints][3] xi (0 there).
+ *   Cells may be perturbed (non-affine) hexahedra.
+ * wf_points_weights: h_w [npoints][3][P+1], the 1-D Lagrange basis on the GLL nodes of wf_tabulate_gll(P) at each
+ *   reference coordinate, in barycentric form; a coordinate equal to a node (compared exactly) gives an exact 0/1 row.
+ *   P outside 1..7: WF_ERR_UNSUPPORTED.
+ * wf_sources_merge: the CSR wf_sources_create builds, for inspection: the unique dofs that nsrc point sources touch,
+ *   ascending (h_dof [*nunique], h_off [*nunique + 1]); within a dof the sources ascending (h_src, h_weight
+ *   [*nentries]).  h_dofs [nsrc][(P+1)^3], h_w [nsrc][3][P+1] are the rows of each source's point; the weight of entry
+ *   l = i + n (j + n k) is (wx[i] * wy[j]) * wz[k]; entries whose weight is exactly zero are dropped.  Any output array
+ *   may be NULL (the first call sizes the second).
+ *
+ * Device (points.hip):
+ * wf_points_create: a set of points on a space of ndofs dofs.  h_dofs [npoints][nd], nd = (P+1)^3: the dofmap row of
+ *   each point's cell in element-local tensor order l = i + n (j + n k); h_w as wf_points_weights writes it.  Indices
+ *   outside [0, ndofs) are refused (WF_ERR_INVALID).
+ * wf_points_sample: d_out[r] = sum_l (wx[i] wy[j]) wz[k] d_x[dofs[r][l]], l ascending per lane, lanes summed by a
+ *   fixed butterfly: bitwise repeatable and independent of how many points are sampled together.  d_x holds ndofs
+ *   entries; d_out holds npoints entries and may point anywhere inside a larger buffer.
+ * wf_sources_create: nsrc point sources, source s at point h_point_of_source[s] of the plan, with wavelet
+ *   h_wavelets[s].  A source is the right-hand side f = s(t) delta(x - x_s) of the equation as the model states it --
+ *   u_tt - c0^2 Lap u = f, or (1/(rho c^2)) p_tt - div((1/rho) grad p) = f with a medium -- so its load is
+ *   b[d] += s(t) phi_d(x_s).  The plan may be destroyed afterwards.
+ *     WF_WAVELET_RICKER:  s(t) = amplitude (1 - 2a) e^{-a}, a = (pi frequency (t - delay))^2
+ *     WF_WAVELET_SAMPLED: s(t) = amplitude times the linear interpolation of h_samples [nsamples] on t_start + k dt,
+ *                         zero outside the table; nsamples >= 2, dt > 0
+ * wf_sources_add: d_b[d] += sum over the sources at dof d, in source order, of weight * s(t): one thread and one
+ *   update per unique dof, no atomics; the wavelets are evaluated on the device in fp64. */
+typedef struct wf_points wf_points;
+typedef struct wf_sources wf_sources;
+enum { WF_WAVELET_RICKER = 0, WF_WAVELET_SAMPLED = 1 };
+typedef struct {
+  int kind;
+  double amplitude, frequency, delay;
+  int nsamples;
+  const double* h_samples;
+  double t_start, dt;
+} wf_wavelet;
+int wf_points_locate(int64_t nverts, const double* h_xverts, int64_t ncells, const int32_t* h_cells, int64_t npoints,
+                     const double* h_xyz, double tol, int32_t* h_cell, double* h_ref);
+int wf_points_weights(int P, int64_t npoints, const double* h_ref, double* h_w);
+int wf_sources_merge(int P, int nsrc, const int32_t* h_dofs, const double* h_w, int32_t* nunique, int32_t* nentries,
+                     int32_t* h_dof, int32_t* h_off, int32_t* h_src, double* h_weight);
+int wf_points_create(int P, int64_t ndofs, int npoints, const int32_t* h_dofs, const double* h_w, wf_points** out);
+int wf_points_destroy(wf_points* plan);
+int wf_points_info(const wf_points* plan, int* npoints, int* nd, int* degree);
+int wf_points_sample(const wf_points* plan, const double* d_x, double* d_out, void* stream);
+int wf_sources_create(const wf_points* plan, int nsrc, const int32_t* h_point_of_source, const wf_wavelet* h_wavelets,
+                      wf_sources** out);
+int wf_sources_destroy(wf_sources* src);
+int wf_sources_info(const wf_sources* src, int* nsources, int* nunique, int* nentries);
+int wf_sources_add(const wf_sources* src, double t, double* d_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,8 @@
 // dolfinx::fem::FunctionSpace.
 #pragma once
 
+#include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
@@ -501,5 +503,107 @@ void scale(Scalar alpha, Vector& x, void* stream = nullptr)
   check(wf_scale((std::int64_t)x.map()->size_local(), (double)alpha, x.mutable_array().data(), stream));
 }
 }  // namespace linalg
+
+// ---- point sources and receivers (wf_points_*, wf_sources_*; not in the reference) ----
+/// Physical points located in the mesh of a Space (wf_points_locate, reference coordinates in [0, 1]^3) with their
+/// dofmap rows and interpolation weights on the device.  Throws naming the first point that lies in no cell.
+class Points {
+public:
+  Points(const Space& V, const std::vector<std::array<double, 3>>& xyz, double tol = 1e-10) : _n((int)xyz.size())
+  {
+    const int n1 = V.degree + 1, nd = n1 * n1 * n1;
+    std::vector<double> p(3 * xyz.size()), ref(3 * xyz.size()), w(3 * xyz.size() * n1);
+    std::vector<std::int32_t> cell(xyz.size()), dofs(xyz.size() * nd);
+    for (std::size_t i = 0; i < xyz.size(); ++i) std::copy(xyz[i].begin(), xyz[i].end(), p.begin() + 3 * i);
+    check(wf_points_locate(V.nverts, V.x, V.ncells, V.geom_dofmap, _n, p.data(), tol, cell.data(), ref.data()));
+    for (std::size_t i = 0; i < xyz.size(); ++i) {
+      if (cell[i] < 0) throw std::runtime_error("wavehip::Points: point " + std::to_string(i) + " lies in no cell of the mesh");
+      std::copy(V.dofmap + (std::size_t)cell[i] * nd, V.dofmap + (std::size_t)(cell[i] + 1) * nd, dofs.begin() + i * nd);
+    }
+    check(wf_points_weights(V.degree, _n, ref.data(), w.data()));
+    check(wf_points_create(V.degree, V.ndofs, _n, dofs.data(), w.data(), &_p));
+  }
+  Points(const Points&) = delete;
+  Points& operator=(const Points&) = delete;
+  ~Points() { wf_points_destroy(_p); }
+  int size() const { return _n; }
+  const wf_points* handle() const { return _p; }
+
+private:
+  wf_points* _p = nullptr;
+  int _n = 0;
+};
+
+/// s(t) = amplitude (1 - 2a) e^{-a}, a = (pi frequency (t - delay))^2
+inline wf_wavelet ricker(double frequency, double delay, double amplitude = 1.0)
+{
+  wf_wavelet w{};
+  w.kind = WF_WAVELET_RICKER, w.amplitude = amplitude, w.frequency = frequency, w.delay = delay;
+  return w;
+}
+
+/// Point sources f = s_i(t) delta(x - x_i), the right-hand side of the equation as the model states it
+/// (u_tt - c0^2 Lap u = f): add(t, b) does b[d] += sum_i s_i(t) phi_d(x_i) in one launch, one writer per dof.
+class Sources {
+public:
+  Sources(const Space& V, const std::vector<std::array<double, 3>>& xyz, const std::vector<wf_wavelet>& wavelets)
+  {
+    if (xyz.size() != wavelets.size()) throw std::runtime_error("wavehip::Sources: one wavelet per point");
+    Points pts(V, xyz);
+    std::vector<std::int32_t> point_of(xyz.size());
+    for (std::size_t i = 0; i < xyz.size(); ++i) point_of[i] = (std::int32_t)i;
+    check(wf_sources_create(pts.handle(), (int)xyz.size(), point_of.data(), wavelets.data(), &_s));
+  }
+  Sources(const Sources&) = delete;
+  Sources& operator=(const Sources&) = delete;
+  ~Sources() { wf_sources_destroy(_s); }
+  void add(double t, double* d_b, void* stream = nullptr) const { check(wf_sources_add(_s, t, d_b, stream)); }
+  const wf_sources* handle() const { return _s; }
+
+private:
+  wf_sources* _s = nullptr;
+};
+
+/// Receivers: sample(x, out) evaluates a device vector at the points; record(x, t) appends a row to a device buffer that
+/// doubles when full; traces() copies the recorded rows [rows][size()] to the host, times() are their times.
+class Receivers {
+public:
+  Receivers(const Space& V, const std::vector<std::array<double, 3>>& xyz) : _pts(V, xyz) {}
+  int size() const { return _pts.size(); }
+  void sample(const double* d_x, double* d_out, void* stream = nullptr) const { check(wf_points_sample(_pts.handle(), d_x, d_out, stream)); }
+  void record(const double* d_x, double t)
+  {
+    const std::size_t R = (std::size_t)size();
+    if (R && (!_buf || (_rows + 1) * R > _buf->size())) {   // 64 rows at first, then twice as many
+      auto grown = std::make_unique<array<double>>(_buf ? 2 * _buf->size() : 64 * R);
+      if (_buf && _rows) check(wf_copy((std::int64_t)(_rows * R), _buf->data(), grown->data(), nullptr));
+      check(wf_sync(nullptr));
+      _buf = std::move(grown);
+    }
+    if (R) sample(d_x, _buf->data() + _rows * R);   // without receivers only the times are kept
+    ++_rows;
+    _times.push_back(t);
+  }
+  std::size_t rows() const { return _rows; }
+  const std::vector<double>& times() const { return _times; }
+  std::vector<double> traces() const
+  {
+    std::vector<double> out(_rows * (std::size_t)size());
+    check(wf_sync(nullptr));
+    if (!out.empty()) check(wf_memcpy_d2h(out.data(), _buf->data(), out.size() * sizeof(double)));
+    return out;
+  }
+  void reset()
+  {
+    _rows = 0;
+    _times.clear();
+  }
+
+private:
+  Points _pts;
+  std::unique_ptr<array<double>> _buf;
+  std::size_t _rows = 0;
+  std::vector<double> _times;
+};
 
 }  // namespace wavehip

@@ -54,6 +54,16 @@ protected:
   wf_boundary* bc_ = nullptr;                  // boundary plan of the fused loop (created on first use)
   VectorUpdater<double>* updater_ = nullptr;   // nullptr on one rank
   bool split_ = false;                         // interior / interface overlap available
+  const Sources* sources_ = nullptr;           // point sources added to every right-hand side (set_sources)
+  Receivers* receivers_ = nullptr;             // records u at the start time and after every step (set_receivers)
+  void add_sources(double t)
+  {
+    if (sources_) sources_->add(t, b->data());
+  }
+  void record(const array<double>& u, double t)
+  {
+    if (receivers_) receivers_->record(u.data(), t);
+  }
 
   double source(double t)
   {
@@ -207,6 +217,23 @@ public:
   LinearGLLOpt(const LinearGLLOpt&) = delete;
   LinearGLLOpt& operator=(const LinearGLLOpt&) = delete;
 
+  /// Point sources f = s(t) delta(x - x_s), the right-hand side of u_tt - c0^2 Lap u = f: every loop adds
+  /// b[d] += s(t) phi_d(x_s) at the time argument at which it evaluates the plane source (rk4: in f1 after the boundary
+  /// term; rk4_fused: a launch after each stage kernel, and once before the loop; leapfrog: after K u, start-up and
+  /// finish included).  Receivers record u at the start time and after every step (steps + 1 rows per call).  One rank;
+  /// nullptr (the default) switches either off, and the loops then issue the launches they always did.  The objects
+  /// must outlive the model's loops.
+  void set_sources(const Sources* s)
+  {
+    if (s && updater_) throw std::runtime_error("LinearGLLOpt: point sources on a partitioned mesh are not implemented");
+    sources_ = s;
+  }
+  void set_receivers(Receivers* r)
+  {
+    if (r && updater_) throw std::runtime_error("LinearGLLOpt: receivers on a partitioned mesh are not implemented");
+    receivers_ = r;
+  }
+
   /// Set the initial values of u and v (LinearGLL.hpp:131-134)
   void init()
   {
@@ -225,6 +252,7 @@ public:
     kernels::copy(u, *u_n);
     kernels::copy(v, *v_n);
     boundary(t, v_n->data());
+    add_sources(t);
     check(wf_pointwise_div(N_, b->data(), m->data(), result.data(), nullptr));
   }
 
@@ -245,6 +273,7 @@ public:
     const double b_runge[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
     const double c_runge[4] = {0.0, 0.5, 0.5, 1.0};
     double tn;
+    record(*u_, t);
     while (t < tf) {
       dt = std::min(dt, tf - t);
       kernels::copy(*u_, *u0);
@@ -262,6 +291,7 @@ public:
       }
       t += dt;
       step += 1;
+      record(*u_, t);
     }
     kernels::copy(*u_, *u_n);
     kernels::copy(*v_, *v_n);
@@ -289,6 +319,8 @@ public:
     // (wf_rk4_stage_bc), the first one by a plain launch: a stage is two launches, stiffness + vector algebra.
     check(wf_fill(N_, 0.0, b->data(), nullptr));
     check(wf_boundary_apply_plan(plan(), s1(t), s2(), v0->data(), b->data(), nullptr));
+    add_sources(t);
+    record(*u0, t);
     while (t < tf) {
       dt = std::min(dt, tf - t);
       double* x_u = u0->data();           // stage 0 reads u0 / v0 directly (a_0 = 0)
@@ -304,6 +336,7 @@ public:
         check(wf_rk4_stage_bc(N_, dt * b_runge[i], has_next ? dt * a_runge[i + 1] : 0.0, has_next, b->data(), m->data(), x_v,
                               ur, vr, u_->data(), v_->data(), u0->data(), v0->data(), un->data(), vn_next, plan(), s1_next,
                               s2(), nullptr));
+        add_sources(has_next ? t + c_runge[i + 1] * dt : t + dt);
         if (has_next) {
           x_u = un->data();
           x_v = vn_next;
@@ -314,6 +347,7 @@ public:
       std::swap(v0, v_);
       t += dt;
       step += 1;
+      record(*u0, t);
     }
     kernels::copy(*u0, *u_n);
     kernels::copy(*v0, *v_n);
@@ -339,18 +373,23 @@ public:
     check(wf_fill(N_, 0.0, b->data(), nullptr));
     stiffness(u->data());
     check(wf_boundary_apply_plan(plan(), s1(t), s2(), v_n->data(), b->data(), nullptr));
+    add_sources(t);
+    record(*u, t);
     check(wf_pointwise_div(N_, b->data(), m->data(), scratch->data(), nullptr));
     kernels::axpy(*w, -dt, *v_n, *u, N_);
     kernels::axpy(*w, 0.5 * dt * dt, *scratch, *w, N_);
     check(wf_fill(N_, 0.0, b->data(), nullptr));
     while (t < tf) {
       stiffness(u->data());
+      add_sources(t);
       check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), w->data(), nullptr, plan(), s1(t), s2(), nullptr));
       std::swap(u, w);
       t += dt;
       step += 1;
+      record(*u, t);
     }
     stiffness(u->data());
+    add_sources(t);
     check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), scratch->data(), v_n->data(), plan(), s1(t),
                               s2(), nullptr));
     kernels::copy(*u, *u_n);

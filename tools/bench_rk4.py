@@ -8,7 +8,10 @@ ghost exchange, LinearGLLOpt.rk4_fused -- launched like bench.py:
 
 Prints one JSON line: ms per RK4 time step and dof-stages/s over all ranks.
 --scheme leapfrog times LinearGLLOpt.leapfrog at the same step instead (the same keys, per leapfrog step; the timed
-window includes the scheme's start-up and finish, two extra stiffness applies)."""
+window includes the scheme's start-up and finish, two extra stiffness applies).
+--receivers N / --sources S (one rank): the same loop with N point receivers recorded every step and S Ricker point
+sources, against the loop without them -- two models in one process, timed alternately --rounds times after one warm-up
+each; prints medians and ranges of both and the difference per step."""
 import argparse
 import json
 import os
@@ -28,6 +31,9 @@ def main():
     ap.add_argument("--unfused", action="store_true")
     ap.add_argument("--scheme", choices=["rk4", "leapfrog"], default="rk4",
                     help="leapfrog: LinearGLLOpt.leapfrog at the same step (one stiffness apply per step; ms_per_rk4_step is then ms per leapfrog step)")
+    ap.add_argument("--receivers", type=int, default=0, help="point receivers recorded every step (A/B against the plain loop)")
+    ap.add_argument("--sources", type=int, default=0, help="Ricker point sources (A/B against the plain loop)")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating timed runs per variant of the A/B")
     ap.add_argument("--periodic", default="", help="axes identified with their opposite face (one rank: RCCL exchange with itself)")
     args = ap.parse_args()
     import torch
@@ -64,6 +70,46 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
+
+    if args.receivers or args.sources:
+        if updater is not None:
+            sys.exit("--receivers / --sources run on one rank without --periodic")
+        import statistics
+
+        import numpy as np
+        from wave_fenics_amd import points
+        V = w.create_functionspace(part.mesh, p)      # with its dofmap, which the point location reads
+        rng = np.random.default_rng(0)
+        rec = points.Receivers(V, rng.uniform(0.05 * L, 0.95 * L, size=(args.receivers, 3)), device=dev) if args.receivers else None
+        src = points.Sources(V, rng.uniform(0.3 * L, 0.7 * L, size=(args.sources, 3)),
+                             [points.ricker(0.5e6, 3.0e-6, 1.0e9)] * args.sources) if args.sources else None
+        with_points = LinearGLLOpt(V, p, 1500.0, 0.5e6, 6e4, tags=boundary_tags(part), device=dev, sources=src, receivers=rec)
+        with_points.init()
+        models = {"plain": eqn, "points": with_points}
+        name = "leapfrog" if args.scheme == "leapfrog" else "rk4" if args.unfused else "rk4_fused"
+        times = {k: [] for k in models}
+        t_at = {k: 0.0 for k in models}
+        for rnd in range(args.rounds + 1):            # round 0 is the warm-up of both
+            steps = args.warmup if rnd == 0 else args.steps
+            for k, model in models.items():
+                if rec is not None:
+                    rec.reset()
+                sync()
+                t0 = time.perf_counter()
+                t_at[k], done = getattr(model, name)(t_at[k], 1.0e9, dt, max_steps=steps)
+                sync()
+                if rnd:
+                    times[k].append((time.perf_counter() - t0) / done * 1e3)
+        med = {k: statistics.median(v) for k, v in times.items()}
+        print(json.dumps({"metric": f"{name} step with and without point sources / receivers, ms per step", "scheme": args.scheme,
+                          "receivers": args.receivers, "sources": args.sources, "rounds": args.rounds, "steps": args.steps,
+                          "global_dofs": part.size_global,
+                          "plain_ms": {"median": med["plain"], "min": min(times["plain"]), "max": max(times["plain"])},
+                          "points_ms": {"median": med["points"], "min": min(times["points"]), "max": max(times["points"])},
+                          "difference_us_per_step": (med["points"] - med["plain"]) * 1e3,
+                          "unique_source_dofs": src.num_unique_dofs if src is not None else 0,
+                          "finite": bool(torch.isfinite(with_points.u_n).all() and torch.isfinite(eqn.u_n).all())}), flush=True)
+        return
 
     run(0.0, args.warmup * dt - 1e-13, dt)
     sync()

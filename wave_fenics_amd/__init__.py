@@ -17,3 +17,4 @@ from .operators import (  # noqa: F401
 )
 from . import la  # noqa: F401
 from .medium import Medium  # noqa: F401
+from . import points  # noqa: F401

@@ -91,6 +91,12 @@ class BoxPartitionInfo(ctypes.Structure):
     ]
 
 
+class Wavelet(ctypes.Structure):
+    """wf_wavelet"""
+    _fields_ = [("kind", c_int), ("amplitude", c_double), ("frequency", c_double), ("delay", c_double),
+                ("nsamples", c_int), ("h_samples", POINTER(c_double)), ("t_start", c_double), ("dt", c_double)]
+
+
 MATVEC_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_void_p)
 
 
@@ -116,6 +122,7 @@ WF_OP_STIFFNESS, WF_OP_MASS_LUMPED, WF_OP_MASS_DENSE = 0, 1, 2
 WF_FLAG_NONE, WF_FLAG_NO_FABS, WF_FLAG_NO_CLAMP, WF_FLAG_MASS_ELEMENTWISE, WF_FLAG_TENSOR_X_SLOWEST = 0, 1, 2, 4, 8
 WF_FLAG_ORDERED = 16   # order-fixed accumulation: bitwise reproducible y on any mesh (include/wavehip.h)
 WF_UPDATE_NONE, WF_UPDATE_ATOMIC, WF_UPDATE_OWNER, WF_UPDATE_ORDERED = 0, 1, 2, 3   # ORDERED: wf_op_info_t.update only
+WF_WAVELET_RICKER, WF_WAVELET_SAMPLED = 0, 1
 WF_PART_ALL, WF_PART_INTERIOR, WF_PART_INTERFACE, WF_PART_INTERIOR_A, WF_PART_INTERIOR_B = 0, 1, 2, 3, 4
 
 # every symbol include/wavehip.h declares: name -> (restype, argtypes)
@@ -225,6 +232,17 @@ SIGNATURES = {
     "wf_cg": (c_int, [POINTER(CGDesc), c_void_p, c_void_p, POINTER(c_int), POINTER(c_double), c_void_p]),
     "wf_boundary_apply": (c_int, [c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p, c_void_p, c_double,
                                   c_void_p, c_void_p, c_void_p]),
+    "wf_points_locate": (c_int, [c_int64, _DP, c_int64, _IP, c_int64, _DP, c_double, _IP, _DP]),
+    "wf_points_weights": (c_int, [c_int, c_int64, _DP, _DP]),
+    "wf_sources_merge": (c_int, [c_int, c_int, _IP, _DP, _IP, _IP, _IP, _IP, _IP, _DP]),
+    "wf_points_create": (c_int, [c_int, c_int64, c_int, _IP, _DP, POINTER(c_void_p)]),
+    "wf_points_destroy": (c_int, [c_void_p]),
+    "wf_points_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "wf_points_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wf_sources_create": (c_int, [c_void_p, c_int, _IP, POINTER(Wavelet), POINTER(c_void_p)]),
+    "wf_sources_destroy": (c_int, [c_void_p]),
+    "wf_sources_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "wf_sources_add": (c_int, [c_void_p, c_double, c_void_p, c_void_p]),
 }
 
 _LIB = None

@@ -10,6 +10,11 @@ is applied in its diagonal GLL form by wf_boundary_apply.
 
 Not in the reference: leapfrog() integrates the same equation with the second-order central-difference scheme (one
 stiffness apply per step, wf_leapfrog_step_bc), stable_time_step() gives a stable step for it.
+sources= (points.Sources) adds point sources f = s(t) delta(x - x_s) to the right-hand side of the equation as the model
+states it (u_tt - c0^2 Lap u = f; with a medium (1/(rho c^2)) p_tt - div((1/rho) grad p) = f): b[d] += s(t) phi_d(x_s) at
+exactly the time argument at which each loop evaluates the plane source s1.  receivers= (points.Receivers) records u at
+the start time and after every step of rk4 / rk4_fused / leapfrog (steps + 1 rows per call; trace_times).  With both
+None the loops issue the launches they always did.
 
 Ghost exchange: `updater` (a VectorUpdater) supplies scatter_fwd / scatter_rev
 where the reference calls la::Vector::scatter_fwd / scatter_rev(add)
@@ -62,7 +67,11 @@ class LinearGLLOpt:
 
     def __init__(self, V, degreeOfBasis: int, speedOfSound: float, sourceFrequency: float,
                  pressureAmplitude: float, boundary=None, updater=None, device=None, structured=None,
-                 tags=None, tuning=None, medium=None):
+                 tags=None, tuning=None, medium=None, sources=None, receivers=None):
+        if updater is not None and (sources is not None or receivers is not None):
+            raise NotImplementedError("LinearGLLOpt: sources= / receivers= on a partitioned mesh (updater=) are not implemented; "
+                                      "points.locate and the point kernels work on one rank's mesh")
+        self.sources, self.receivers = sources, receivers
         if medium is not None:
             # (1/(rho c^2)) p_tt = div((1/rho) grad p), dp/dn = g on Gamma_1, dp/dn = -p_t / c on Gamma_2 (medium.py).
             # The facet masses of both boundary sets carry the admittance 1 / (rho c) of the facet's cell: derived from
@@ -150,6 +159,11 @@ class LinearGLLOpt:
         self.u_n.zero_()
         self.v_n.zero_()
 
+    @property
+    def trace_times(self):
+        """The time of every row of receivers.traces"""
+        return [] if self.receivers is None else self.receivers.times
+
     # ---- the pieces every time loop shares ----
     def _window(self, t: float) -> float:
         """The source's start-up ramp over alpha_ periods (LinearGLL.hpp:153-159)."""
@@ -219,6 +233,8 @@ class LinearGLLOpt:
             la.fill(self.b, 0.0)
             self._rhs(u, self.b)
             la.boundary_apply(self.idx1, self.mG1, s1, self.idx2, self.mG2, s2, v, self.b)
+            if self.sources is not None:
+                self.sources.add(t, self.b)
             la.copy(u, self.u_n)
             la.copy(v, self.v_n)
             la.pointwise_div(self.b, self.m, result)
@@ -231,6 +247,8 @@ class LinearGLLOpt:
         la.fill(self.b, 0.0)
         self.stiff_op(self.u_n, self.b)
         la.boundary_apply(self.idx1, self.mG1, s1, self.idx2, self.mG2, s2, self.v_n, self.b)
+        if self.sources is not None:
+            self.sources.add(t, self.b)
         if self.updater is not None:
             self.updater.scatter_rev(self.b)
         la.pointwise_div(self.b, self.m, result)
@@ -249,6 +267,9 @@ class LinearGLLOpt:
         a_runge = [0.0, 0.5, 0.5, 1.0]
         b_runge = [1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0]
         c_runge = [0.0, 0.5, 0.5, 1.0]
+        rec = self.receivers
+        if rec is not None:
+            rec.record(u_, t)
         while t < tf:
             dt = min(dt, tf - t)
             la.copy(u_, u0)
@@ -265,6 +286,8 @@ class LinearGLLOpt:
                 la.axpy(v_, dt * b_runge[i], kv, v_, nl)
             t += dt
             step += 1
+            if rec is not None:
+                rec.record(u_, t)
             if max_steps is not None and step >= max_steps:
                 break
         la.copy(u_, self.u_n)
@@ -296,6 +319,11 @@ class LinearGLLOpt:
         bc, s1, s2, rhs, fold = self._boundary_plan(), self._s1_fused, self._s2, self._rhs, self.fold_boundary
         la.fill(b, 0.0)
         bc.apply(s1(t), s2, v0, b)           # boundary term of the first right-hand side; the stage kernels leave the others
+        src, rec = self.sources, self.receivers
+        if src is not None:
+            src.add(t, b)                    # likewise the point sources: a launch after each stage kernel leaves the others
+        if rec is not None:
+            rec.record(u0, t)
         while t < tf:
             dt = min(dt, tf - t)
             # stage 0: un = u0, vn = v0 (a_0 = 0), read straight from u0 / v0
@@ -310,6 +338,8 @@ class LinearGLLOpt:
                                  bc=bc if fold else None, s1_next=s1(t + c_runge[i + 1] * dt), s2=s2)
                     if not fold:
                         bc.apply(s1(t + c_runge[i + 1] * dt), s2, vn_next, b)
+                    if src is not None:
+                        src.add(t + c_runge[i + 1] * dt, b)
                     x_u, x_v = un, vn_next
                     vn_next = vn_b if vn_next is vn_a else vn_a
                 else:
@@ -318,10 +348,14 @@ class LinearGLLOpt:
                     la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], bc=bc if fold else None, s1_next=s1(t + dt), s2=s2)
                     if not fold:
                         bc.apply(s1(t + dt), s2, v_, b)
+                    if src is not None:
+                        src.add(t + dt, b)
             u0, u_ = u_, u0          # the new solution becomes the next step's u0
             v0, v_ = v_, v0
             t += dt
             step += 1
+            if rec is not None:
+                rec.record(u0, t)
             if max_steps is not None and step >= max_steps:
                 break
         la.copy(u0, self.u_n)
@@ -356,20 +390,31 @@ class LinearGLLOpt:
         la.fill(b, 0.0)
         rhs(u, b)
         bc.apply(s1(t), s2, self.v_n, b)
+        src, rec = self.sources, self.receivers
+        if src is not None:
+            src.add(t, b)
+        if rec is not None:
+            rec.record(u, t)
         la.pointwise_div(b, m, scratch)
         la.axpy(w, -dt, self.v_n, u)
         la.axpy(w, 0.5 * dt * dt, scratch, w)
         la.fill(b, 0.0)
         while t < tf:
             rhs(u, b)                              # b is zero on entry
+            if src is not None:
+                src.add(t, b)
             la.leapfrog_step(b, m, u, w, w, dt, bc=bc, s1=s1(t), s2=s2)
             u, w = w, u
             t += dt
             step += 1
+            if rec is not None:
+                rec.record(u, t)
             if max_steps is not None and step >= max_steps:
                 break
         # finish: the step after the last one, into scratch, for the central velocity at t
         rhs(u, b)
+        if src is not None:
+            src.add(t, b)
         la.leapfrog_step(b, m, u, w, scratch, dt, v=self.v_n, bc=bc, s1=s1(t), s2=s2)
         la.copy(u, self.u_n)
         if self.updater is not None:
