@@ -657,6 +657,7 @@ int wf_op_apply_overlapped(wf_op* op, wf_updater* u, double* d_x, double* d_y, v
  * device::cg(x, b, matvec, kmax, rtol) of demo/gpu_cg/CUDA/cg.hpp:38-121: solves
  * A x = b for a symmetric positive definite operator, x holding the initial guess;
  * stops when ||r||^2 / ||r0||^2 < rtol^2 (cg.hpp:103) or after kmax iterations.
+ * rtol = 0 runs kmax iterations unless the residual vanishes first (then its = k, res = 0).
  * A is an operator handle or a callback with the library's accumulate semantics
  * (y += A v; wf_cg zeroes y first).  On a partitioned mesh pass the updater and
  * its communicator: the halo of the direction is updated before, the product

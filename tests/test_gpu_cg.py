@@ -8,54 +8,10 @@ import os
 import numpy as np
 import pytest
 
+from cg_helpers import assemble, dense_mass_setup, numpy_cg
 from support import gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def numpy_cg(A, b, kmax, rtol):
-    """Textbook CG with the reference's stopping rule (cg.hpp:103)."""
-    x = np.zeros_like(b)
-    r = b.copy()
-    p = r.copy()
-    rr0 = rr = r @ r
-    k = 0
-    while k < kmax:
-        k += 1
-        y = A @ p
-        alpha = rr / (p @ y)
-        x += alpha * p
-        r -= alpha * y
-        rr_new = r @ r
-        if rr_new / rr0 < rtol * rtol:
-            break
-        p = r + (rr_new / rr) * p
-        rr = rr_new
-    return x, k
-
-
-def assemble(oracle, om, phi, detJ):
-    """The oracle's mass matrix, column by column (A e_j)."""
-    A = np.zeros((om.ndofs, om.ndofs))
-    e, col = np.zeros(om.ndofs), np.zeros(om.ndofs)
-    for j in range(om.ndofs):
-        e[:] = 0.0
-        e[j] = 1.0
-        col[:] = 0.0
-        oracle.dense_mass_apply(om, phi, detJ, e, col)
-        A[:, j] = col
-    return A
-
-
-def dense_mass_setup(oracle, p, n, perturb=0.2):
-    """Consistent (non-diagonal) mass: GLL-warped basis, Gauss rule of degree 2P."""
-    import wave_fenics_amd as w
-    om = oracle.create_box(n, p, perturb=perturb)
-    mesh = w.create_box(n, perturb=perturb)
-    V = w.create_functionspace(mesh, p)
-    pts, wts, phi1, phi, X, W = oracle.tabulate_mass_tables(p, "gll", "gauss_jacobi", 2 * p)
-    detJ = oracle.compute_detJ_generic(om, X, W)
-    return om, V, phi1, np.abs(detJ), assemble(oracle, om, phi, np.abs(detJ))
 
 
 @pytest.mark.parametrize("p,n", [(2, (3, 3, 2)), (3, (2, 2, 2))])

@@ -113,8 +113,9 @@ extern "C" int wf_updater_ghosts(const wf_updater* u, const int32_t** d_ghost_po
 
 extern "C" int wf_cg(const wf_cg_desc* d, double* d_x, const double* d_b, int* iterations, double* rel_residual, void* stream)
 {
-  WF_REQUIRE(d && d_x && d_b, "wf_cg: null argument");
+  WF_REQUIRE(d, "wf_cg: null argument");
   WF_REQUIRE(d->n >= 0 && d->kmax >= 0 && d->rtol >= 0.0, "wf_cg: bad size / kmax / rtol");
+  WF_REQUIRE((d_x && d_b) || d->n == 0, "wf_cg: null argument");   // an empty vector has no address
   WF_REQUIRE(d->op || d->matvec, "wf_cg: needs an operator handle or a matvec callback");
   WF_REQUIRE(!d->updater || d->comm, "wf_cg: an updater needs its communicator (global reductions)");
   hipStream_t s = (hipStream_t)stream;
@@ -139,7 +140,9 @@ extern "C" int wf_cg(const wf_cg_desc* d, double* d_x, const double* d_b, int* i
     int e;
     if (d->updater && (e = wf_updater_fwd(d->updater, v, s)) != WF_OK) return e;
     WF_HIP_CHECK(hipMemsetAsync(y, 0, bytes, s));     // the operators accumulate (y += A v)
-    if (d->matvec) {
+    if (n == 0) {
+      // a rank without entries has no product to form; it still takes part in the exchanges and the all-reduces
+    } else if (d->matvec) {
       if ((e = d->matvec(d->user, v, y, s)) != WF_OK) {
         set_error("wf_cg: matvec callback failed");
         return e;
@@ -192,7 +195,9 @@ extern "C" int wf_cg(const wf_cg_desc* d, double* d_x, const double* d_b, int* i
         set_error("wf_cg: residual is not finite (operator not positive definite?)");
         return WF_ERR_INVALID;
       }
-      if (rr / rr0 < rtol2) break;                                   // cg.hpp:103
+      // cg.hpp:103; an exactly zero residual is the solution whatever rtol (0 / rr0 < 0 is false, and the next pass
+      // would form alpha = 0 / 0)
+      if (rr == 0.0 || rr / rr0 < rtol2) break;
       if (n) hipLaunchKernelGGL(k_cg_direction, dim3(grid_for(n)), dim3(256), 0, s, n, B.sc, B.r, B.p);
       hipLaunchKernelGGL(k_cg_roll, dim3(1), dim3(1), 0, s, B.sc);
     }
