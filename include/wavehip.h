@@ -613,11 +613,9 @@ int wf_comm_destroy(wf_comm* comm);
  * be its own neighbour (periodic partition). */
 typedef enum {
   WF_UPDATER_DEFAULT = 0,
-  WF_UPDATER_INLINE = 1,  /* enqueue the exchange on the caller's stream instead of the
+  WF_UPDATER_INLINE = 1   /* enqueue the exchange on the caller's stream instead of the
                              updater's communication stream (begin/end then do not overlap) */
-  WF_UPDATER_CHAIN_ON_SIDE = 2 /* wf_op_apply_overlapped: halo chain on the updater's high-priority
-                             stream and the interior on the caller's (default: the reverse)   */
-} wf_updater_flags;
+} wf_updater_flags;       /* any other bit is refused (WF_ERR_INVALID) */
 typedef struct {
   int ndofs;                          /* local array length: owned + ghosts               */
   int num_send_neighbors;

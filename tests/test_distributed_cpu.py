@@ -76,6 +76,34 @@ def test_periodic_partition_lists():
         assert np.array_equal(np.sort(allg), np.arange(parts[0].size_global))      # every global dof owned exactly once
 
 
+def test_periodic_partition_ghost_lists():
+    """part.ghosts holds the flat lists of the cases of test_periodic_partition_lists: neighbours ascending without
+    duplicates, offsets from 0 to the length of the index array, and send_fwd / recv_fwd are its segments.  On one
+    rank such an exchange is a send to self, which the torch transport refuses."""
+    from dist_helpers import TorchIndexKernels
+    from wave_fenics_amd.distributed import VectorUpdater, create_distributed_box
+    cases = [(1, (2, 2, 2), 2, (True, False, False)), (1, (2, 1, 2), 3, (True, True, True)),
+             (2, (2, 2, 1), 2, (True, True, False)), (4, (1, 2, 2), 2, (True, True, True)),
+             (8, (1, 1, 1), 2, (True, False, True)), (2, (2, 2, 2), 1, (False, True, False))]
+    for world, n, p, per in cases:
+        for r in range(world):
+            part = create_distributed_box(n, p, world, r, periodic=per)
+            g = part.ghosts
+            assert g.ndofs == part.V.ndofs
+            for nb, off, idx, segs in ((g.send_neighbors, g.send_offsets, g.send_indices, part.send_fwd),
+                                       (g.recv_neighbors, g.recv_offsets, g.ghost_positions, part.recv_fwd)):
+                assert nb.size >= 1 and np.all(np.diff(nb) > 0)
+                assert off.size == nb.size + 1 and off[0] == 0 and off[-1] == idx.size and np.all(np.diff(off) >= 0)
+                assert idx.dtype == np.int32 and list(segs) == nb.tolist()
+                for i, rank in enumerate(nb):
+                    assert segs[rank].dtype == np.int32 and np.array_equal(segs[rank], idx[off[i]:off[i + 1]])
+            if world == 1:
+                with pytest.raises(RuntimeError, match="self-neighbour .* needs transport='native'"):
+                    VectorUpdater(part, kernels=TorchIndexKernels, transport="torch")
+                with pytest.raises(RuntimeError, match="self-neighbour .* needs transport='native'"):
+                    VectorUpdater(part, kernels=TorchIndexKernels)
+
+
 def test_cxx_partition_matches_python(tmp_path):
     """include/wavehip_box.hpp create_distributed_box (the C++ host side of
     VectorUpdater) names the same neighbours and the same dofs in the same order as

@@ -1,5 +1,5 @@
 """Native RCCL ghost exchange (wf_comm_* / wf_updater_* / wf_op_apply_overlapped,
-csrc/comm.hip) on ONE MI355X: a one-rank communicator on a periodic partition is
+csrc/comm.hip, csrc/updater.hip) on ONE MI355X: a one-rank communicator on a periodic partition is
 its own neighbour, so every update is a real grouped ncclSend/ncclRecv to self
 through device buffers -- the code path the multi-GPU run uses, with the same
 index lists.  The answer is the CPU oracle on the periodic mesh

@@ -112,7 +112,7 @@ WF_VARIANT_GLL_WARPED, WF_VARIANT_EQUISPACED = 0, 1
 WF_MAX_QUAD_POINTS = 16
 WF_COMM_ID_BYTES = 128
 WF_SUM, WF_MAX = 0, 1
-WF_UPDATER_DEFAULT, WF_UPDATER_INLINE, WF_UPDATER_CHAIN_ON_SIDE = 0, 1, 2
+WF_UPDATER_DEFAULT, WF_UPDATER_INLINE = 0, 1
 (WF_KERNEL_NONE, WF_KERNEL_MARCH_BOX, WF_KERNEL_MARCH_IDX, WF_KERNEL_BATCH_UNIQUE, WF_KERNEL_BOX_BLOCK, WF_KERNEL_DIAGONAL,
  WF_KERNEL_MASS_DENSE_ANY, WF_KERNEL_DENSE_SIMPLEX, WF_KERNEL_ELEMENTWISE, WF_KERNEL_CELLS_ORDERED,
  WF_KERNEL_DENSE_SIMPLEX_MASS) = range(11)

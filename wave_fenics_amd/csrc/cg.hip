@@ -16,7 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 
-#include "device_array.h"
+#include "comm.h"
 
 namespace wf {
 
@@ -107,9 +107,6 @@ __global__ void k_cg_roll(double* sc)
 }  // namespace wf
 
 using namespace wf;
-
-// defined in comm.hip
-extern "C" int wf_updater_ghosts(const wf_updater* u, const int32_t** d_ghost_pos, int32_t* nghost);
 
 extern "C" int wf_cg(const wf_cg_desc* d, double* d_x, const double* d_b, int* iterations, double* rel_residual, void* stream)
 {

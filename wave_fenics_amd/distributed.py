@@ -4,7 +4,7 @@ Replaces demo/gpu_scatter_mpi/VectorUpdater.hpp:21-230 (GPU pack + CUDA-aware
 MPI point-to-point over the IndexMap neighbourhood) and the
 la::Vector::scatter_fwd / scatter_rev(add) calls of common/LinearGLL.hpp:164-176:
 one process per GPU.  Two transports carry the same index lists:
-  "native": wf_updater_* of the C ABI (csrc/comm.hip) -- a grouped ncclSend/ncclRecv
+  "native": wf_updater_* of the C ABI (csrc/updater.hip) -- a grouped ncclSend/ncclRecv
             per neighbour on an RCCL communicator created inside libwavehip, i.e.
             one message per xGMI link for the 2x2x2 partition; the default for
             device vectors;
@@ -21,14 +21,16 @@ where a lower neighbour exists.  Local vectors use the local lattice numbering
 lattice implicitly; the owned/ghost split is carried by the index lists."""
 from __future__ import annotations
 
-from dataclasses import dataclass, field
-
 import ctypes
+from dataclasses import dataclass
+from functools import partialmethod
 
 import numpy as np
 
-from ._lib import BoxPartitionInfo, _ip, check, lib
+from ._lib import WF_PART_INTERFACE, WF_PART_INTERIOR, WF_UPDATER_DEFAULT, BoxPartitionInfo, UpdaterDesc, _ip, check, lib
 from .box import BoxMesh, FunctionSpace, IndexMap, _int3, create_box, create_functionspace
+from .comm import Comm
+from .operators import _ptr, _stream, gather, scatter, scatter_set
 
 
 def decompose3d(nproc: int):
@@ -51,6 +53,23 @@ def coords_rank(c, procs):
 
 
 @dataclass
+class GhostLists:
+    """wavehip::GhostLists: the flat index lists as wf_box_partition fills them and wf_updater_desc takes them."""
+    # Neighbour ranks ascending, one segment per neighbour; int32 local lattice indices.
+    ndofs: int
+    send_neighbors: np.ndarray      # intc
+    send_offsets: np.ndarray        # int32, [len(send_neighbors) + 1], first entry 0
+    send_indices: np.ndarray        # segment i: the owned dofs send_neighbors[i] holds as ghosts
+    recv_neighbors: np.ndarray
+    recv_offsets: np.ndarray
+    ghost_positions: np.ndarray     # segment i: the ghosts recv_neighbors[i] owns, in the order it sends them
+
+
+def _segments(nb, off, idx) -> dict:
+    return {int(r): idx[off[i]:off[i + 1]] for i, r in enumerate(nb)}
+
+
+@dataclass
 class BoxPartition:
     procs: tuple
     rank: int
@@ -61,12 +80,14 @@ class BoxPartition:
     V: FunctionSpace
     size_global: int            # global number of (owned) dofs
     owned_lo: tuple             # first owned lattice index per axis (0 or 1)
-    # neighbour lists, keyed by neighbour rank (ascending); int32 local lattice indices
-    send_fwd: dict = field(default_factory=dict)   # owned dofs the neighbour holds as ghosts
-    recv_fwd: dict = field(default_factory=dict)   # my ghosts owned by the neighbour
+    ghosts: GhostLists          # the neighbour lists
     periodic: tuple = (False, False, False)        # axes whose upper face is identified with the lower one
     num_owned: int = 0
     face_tag: tuple = (0,) * 6                     # cfg1 tag of local face 2*axis + side, 0 = none (boundary_tags)
+
+    # the lists keyed by neighbour rank (ascending): the owned dofs the neighbour holds as ghosts / my ghosts it owns
+    send_fwd = property(lambda self: _segments(self.ghosts.send_neighbors, self.ghosts.send_offsets, self.ghosts.send_indices))
+    recv_fwd = property(lambda self: _segments(self.ghosts.recv_neighbors, self.ghosts.recv_offsets, self.ghosts.ghost_positions))
 
     def owned_mask(self) -> np.ndarray:
         NX, NY, NZ = self.V.lattice
@@ -115,10 +136,10 @@ def create_distributed_box(n, degree: int, nproc: int, rank: int, lo=(0.0, 0.0, 
         mesh.x = np.ascontiguousarray(gmesh_x[sl[2], sl[1], sl[0]].reshape(-1, 3))
     V = create_functionspace(mesh, degree, build_dofmap=build_dofmap)
     V.index_map = IndexMap(V.ndofs, 0, info.size_global)   # whole local lattice; see module docstring
-    segments = lambda nb, off, idx, k: {int(nb[i]): idx[off[i]:off[i + 1]].copy() for i in range(k)}
+    ns, nr = info.num_send_neighbors, info.num_recv_neighbors
+    ghosts = GhostLists(V.ndofs, snb[:ns], soff[:ns + 1], sidx, rnb[:nr], roff[:nr + 1], ridx)
     return BoxPartition(procs, rank, c, tuple(n), degree, mesh, V, size_global=info.size_global,
-                        owned_lo=tuple(info.owned_lo), send_fwd=segments(snb, soff, sidx, info.num_send_neighbors),
-                        recv_fwd=segments(rnb, roff, ridx, info.num_recv_neighbors), periodic=periodic,
+                        owned_lo=tuple(info.owned_lo), ghosts=ghosts, periodic=periodic,
                         num_owned=info.num_owned, face_tag=tuple(info.face_tag))
 
 
@@ -135,18 +156,131 @@ class HipKernels:
 
     @staticmethod
     def gather(idx, src, out):
-        from .operators import gather
         gather(idx.numel(), idx, src, out)
 
     @staticmethod
     def scatter_set(idx, src, out):
-        from .operators import scatter_set
         scatter_set(idx.numel(), idx, src, out)
 
     @staticmethod
     def scatter_add(idx, src, out):
-        from .operators import scatter
         scatter(idx.numel(), idx, src, out)
+
+
+class _NativeExchange:
+    """wf_updater_* and wf_op_apply_overlapped of the C ABI (csrc/updater.hip); owns the wf_updater handle."""
+
+    def __init__(self, ghosts: GhostLists, device, active: bool, group, kernels, comm):
+        if device.type != "cuda":
+            raise RuntimeError("transport='native' exchanges device vectors (RCCL)")
+        self.comm = Comm.from_torch_distributed(group) if (comm is None and active) else comm
+        g, nbp = ghosts, lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        d = UpdaterDesc(g.ndofs, len(g.send_neighbors), nbp(g.send_neighbors), _ip(g.send_offsets), _ip(g.send_indices),
+                        len(g.recv_neighbors), nbp(g.recv_neighbors), _ip(g.recv_offsets), _ip(g.ghost_positions),
+                        WF_UPDATER_DEFAULT)
+        self.handle = ctypes.c_void_p()
+        check(lib().wf_updater_create(self.comm._h if self.comm is not None else None, ctypes.byref(d),
+                                      ctypes.byref(self.handle)))
+
+    def _call(self, fn: str, x):
+        check(getattr(lib(), fn)(self.handle, _ptr(x), _stream(x)))
+
+    fwd_begin = partialmethod(_call, "wf_updater_fwd_begin")
+    fwd_end = partialmethod(_call, "wf_updater_fwd_end")
+    rev_begin = partialmethod(_call, "wf_updater_rev_begin")
+    rev_end = partialmethod(_call, "wf_updater_rev_end")
+
+    def overlapped_apply(self, op, x, y):
+        check(lib().wf_op_apply_overlapped(op._h, self.handle, _ptr(x), _ptr(y), _stream(x)))
+
+    def close(self):
+        if self.handle is not None and self.handle.value:
+            lib().wf_updater_destroy(self.handle)
+            self.handle = None
+
+
+class _TorchExchange:
+    """ONE torch.distributed all_to_all_single per update on `group`; pack/unpack through `kernels` (libwavehip's
+    gather/scatter unless a test passes a double)."""
+
+    def __init__(self, ghosts: GhostLists, device, active: bool, group, kernels, comm):
+        import torch
+        import torch.distributed as dist
+        world = dist.get_world_size(group) if dist.is_initialized() else 1
+        if world == 1 and active:
+            raise RuntimeError("a self-neighbour (periodic) exchange on one rank needs transport='native'")
+        self.active, self.group = active, group     # active: read by overlapped_apply alone
+        self.kernels = HipKernels if kernels is None else kernels
+        # entries per rank of the group, 0 for a rank that is no neighbour
+        self.send_sizes = np.bincount(ghosts.send_neighbors, np.diff(ghosts.send_offsets), world).astype(int).tolist()
+        self.recv_sizes = np.bincount(ghosts.recv_neighbors, np.diff(ghosts.recv_offsets), world).astype(int).tolist()
+        self.d_indices = torch.from_numpy(ghosts.send_indices).to(device)          # scatter_fwd_indices
+        self.d_ghost_pos = torch.from_numpy(ghosts.ghost_positions).to(device)
+        # zero-length exchanges (a rank with no ghosts / no upper neighbour) keep a valid allocation behind the view
+        buffer = lambda n: torch.zeros(max(n, 1), dtype=torch.float64, device=device)[:n]
+        self.d_send_buffer, self.d_recv_buffer = buffer(self.d_indices.numel()), buffer(self.d_ghost_pos.numel())
+        # a transport that cannot read device memory (gloo) is staged through the host
+        self.staged = dist.is_initialized() and dist.get_backend(group) == "gloo" and device.type == "cuda"
+        if self.staged:
+            self.h_send = torch.zeros(max(self.d_indices.numel(), self.d_ghost_pos.numel()), dtype=torch.float64).pin_memory()
+            self.h_recv = torch.zeros_like(self.h_send).pin_memory()
+        self._work = self._side = None  # pending exchange; stream of overlapped_apply, created on first use
+
+    def _post(self, out, out_sizes, inp, in_sizes):
+        import torch.distributed as dist
+        if self.staged:
+            import torch
+            hs, hr = self.h_send[: inp.numel()], self.h_recv[: out.numel()]
+            hs.copy_(inp)
+            torch.cuda.current_stream().synchronize()
+            dist.all_to_all_single(hr, hs, out_sizes, in_sizes, group=self.group)
+            out.copy_(hr, non_blocking=True)
+            return
+        self._work = dist.all_to_all_single(out, inp, out_sizes, in_sizes, group=self.group, async_op=True)
+
+    def _wait(self):
+        if self._work is not None:
+            self._work.wait()
+            self._work = None
+
+    def fwd_begin(self, x):
+        self.kernels.gather(self.d_indices, x, self.d_send_buffer)                  # VectorUpdater.hpp:110-111
+        self._post(self.d_recv_buffer, self.recv_sizes, self.d_send_buffer, self.send_sizes)
+
+    def fwd_end(self, x):
+        self._wait()
+        self.kernels.scatter_set(self.d_ghost_pos, self.d_recv_buffer, x)           # VectorUpdater.hpp:139-142
+
+    def rev_begin(self, x):
+        self.kernels.gather(self.d_ghost_pos, x, self.d_recv_buffer)                # VectorUpdater.hpp:165-168
+        self._post(self.d_send_buffer, self.send_sizes, self.d_recv_buffer, self.recv_sizes)
+
+    def rev_end(self, x):
+        self._wait()
+        self.kernels.scatter_add(self.d_indices, self.d_send_buffer, x)             # VectorUpdater.hpp:196-198
+
+    def overlapped_apply(self, op, x, y):
+        import torch
+        if not self.active:             # nothing to exchange, and perhaps no process group: the operator, unsplit
+            return op(x, y)
+        main = torch.cuda.current_stream(x.device)
+        side = self._side = self._side or torch.cuda.Stream(device=x.device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            self.fwd_begin(x)
+            self.fwd_end(x)
+            op.apply_part(x, y, WF_PART_INTERFACE)
+            self.rev_begin(y)
+        op.apply_part(x, y, WF_PART_INTERIOR)
+        # the reverse add lands on owned entries of y that the interior part may hold between its read and its write
+        # (the owner-computes box kernel updates y with plain loads and stores), so it waits for the interior part
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            self.rev_end(y)
+        main.wait_stream(side)
+
+    def close(self):
+        pass
 
 
 class VectorUpdater:
@@ -167,80 +301,26 @@ class VectorUpdater:
         import torch
         import torch.distributed as dist
         self.part = part
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.device = torch.device("cpu") if device is None else device
-        self.kernels = HipKernels if kernels is None else kernels
-        self.backend = dist.get_backend(group) if dist.is_initialized() else None
+        backend = dist.get_backend(group) if dist.is_initialized() else None
         if transport is None:
-            transport = "native" if (self.device.type == "cuda" and self.backend != "gloo" and kernels is None) else "torch"
+            transport = "native" if (self.device.type == "cuda" and backend != "gloo" and kernels is None) else "torch"
         if transport not in ("native", "torch"):
             raise ValueError("transport must be 'native' or 'torch'")
         self.transport = transport
-        # neighbours in ascending rank order; displacements and sizes per neighbour (VectorUpdater.hpp:34-46)
-        self.send_neighbors = sorted(part.send_fwd)
-        self.recv_neighbors = sorted(part.recv_fwd)
-        cat = lambda L: np.concatenate(L).astype(np.int32) if L else np.zeros(0, dtype=np.int32)
-        self.h_indices = cat([part.send_fwd[r] for r in self.send_neighbors])       # scatter_fwd_indices
-        self.h_ghost_pos = cat([part.recv_fwd[r] for r in self.recv_neighbors])     # ghost positions
+        g = part.ghosts
+        self.send_neighbors, self.recv_neighbors = g.send_neighbors.tolist(), g.recv_neighbors.tolist()
+        self.h_indices, self.h_ghost_pos = g.send_indices, g.ghost_positions
         self.active = bool(self.send_neighbors or self.recv_neighbors)
-        self._work = None
-        if transport == "native":
-            self._init_native(comm)
-            return
-        if self.world == 1 and self.active:
-            raise RuntimeError("a self-neighbour (periodic) exchange on one rank needs transport='native'")
-        self.send_sizes = [int(part.send_fwd[r].size) if r in part.send_fwd else 0 for r in range(self.world)]
-        self.recv_sizes = [int(part.recv_fwd[r].size) if r in part.recv_fwd else 0 for r in range(self.world)]
-        self.d_indices = torch.from_numpy(self.h_indices).to(self.device)
-        self.d_ghost_pos = torch.from_numpy(self.h_ghost_pos).to(self.device)
-        # zero-length exchanges (a rank with no ghosts / no upper neighbour) keep a valid allocation behind the view
-        self.d_send_buffer = torch.zeros(max(self.d_indices.numel(), 1), dtype=torch.float64, device=self.device)[: self.d_indices.numel()]
-        self.d_recv_buffer = torch.zeros(max(self.d_ghost_pos.numel(), 1), dtype=torch.float64, device=self.device)[: self.d_ghost_pos.numel()]
-        # a transport that cannot read device memory (gloo) is staged through the host
-        self.staged = self.backend == "gloo" and self.device.type == "cuda"
-        if self.staged:
-            self.h_send = torch.zeros(max(self.d_indices.numel(), self.d_ghost_pos.numel()), dtype=torch.float64).pin_memory()
-            self.h_recv = torch.zeros_like(self.h_send).pin_memory()
+        make = _NativeExchange if transport == "native" else _TorchExchange
+        self._exchange = make(g, self.device, self.active, group, kernels, comm)
 
-    # -- native transport (csrc/comm.hip) ----------------------------------------
-    def _init_native(self, comm):
-        import ctypes
-        from ctypes import POINTER, c_int, c_void_p
-
-        from . import _lib
-        from .comm import Comm
-        if self.device.type != "cuda":
-            raise RuntimeError("transport='native' exchanges device vectors (RCCL)")
-        self.comm = comm
-        if self.comm is None and self.active:
-            self.comm = Comm.from_torch_distributed(self.group)
-        d = _lib.UpdaterDesc()
-        d.ndofs = int(self.part.V.ndofs)
-        snb = np.asarray(self.send_neighbors, dtype=np.intc)
-        rnb = np.asarray(self.recv_neighbors, dtype=np.intc)
-        soff = np.concatenate([[0], np.cumsum([self.part.send_fwd[r].size for r in self.send_neighbors])]).astype(np.int32)
-        roff = np.concatenate([[0], np.cumsum([self.part.recv_fwd[r].size for r in self.recv_neighbors])]).astype(np.int32)
-        d.num_send_neighbors, d.num_recv_neighbors = len(snb), len(rnb)
-        d.send_neighbors = snb.ctypes.data_as(POINTER(c_int))
-        d.recv_neighbors = rnb.ctypes.data_as(POINTER(c_int))
-        d.send_offsets, d.recv_offsets = _ip(soff), _ip(roff)
-        d.send_indices, d.ghost_positions = _ip(self.h_indices), _ip(self.h_ghost_pos)
-        d.flags = _lib.WF_UPDATER_DEFAULT
-        self._h = c_void_p()
-        _lib.check(_lib.lib().wf_updater_create(self.comm._h if self.comm is not None else None, ctypes.byref(d),
-                                                ctypes.byref(self._h)))
-
-    def _native(self, fn: str, x):
-        from . import _lib
-        from .operators import _ptr, _stream
-        _lib.check(getattr(_lib.lib(), fn)(self._h, _ptr(x), _stream(x)))
+    # native transport only: its RCCL communicator and its wf_updater handle (None once closed)
+    comm = property(lambda self: self._exchange.comm)
+    _h = property(lambda self: self._exchange.handle)
 
     def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            from . import _lib
-            _lib.lib().wf_updater_destroy(self._h)
-            self._h = None
+        self._exchange.close()
 
     def __del__(self):
         try:
@@ -248,61 +328,21 @@ class VectorUpdater:
         except Exception:
             pass
 
-    # -- torch transport ------------------------------------------------------------
-    def _exchange(self, out, out_sizes, inp, in_sizes):
-        import torch.distributed as dist
-        if self.staged:
-            import torch
-            hs, hr = self.h_send[: inp.numel()], self.h_recv[: out.numel()]
-            hs.copy_(inp)
-            torch.cuda.current_stream().synchronize()
-            dist.all_to_all_single(hr, hs, out_sizes, in_sizes, group=self.group)
-            out.copy_(hr, non_blocking=True)
-            return None
-        return dist.all_to_all_single(out, inp, out_sizes, in_sizes, group=self.group, async_op=True)
-
-    def _wait(self):
-        if self._work is not None:
-            self._work.wait()
-            self._work = None
+    def _step(self, name: str, x):
+        if self.active:
+            getattr(self._exchange, name)(x)
 
     # -- forward: owners -> ghosts --------------------------------------------
-    def update_fwd_begin(self, x):
-        if not self.active:
-            return
-        if self.transport == "native":
-            return self._native("wf_updater_fwd_begin", x)
-        self.kernels.gather(self.d_indices, x, self.d_send_buffer)                  # VectorUpdater.hpp:110-111
-        self._work = self._exchange(self.d_recv_buffer, self.recv_sizes, self.d_send_buffer, self.send_sizes)
-
-    def update_fwd_end(self, x):
-        if not self.active:
-            return
-        if self.transport == "native":
-            return self._native("wf_updater_fwd_end", x)
-        self._wait()
-        self.kernels.scatter_set(self.d_ghost_pos, self.d_recv_buffer, x)           # VectorUpdater.hpp:139-142
+    update_fwd_begin = partialmethod(_step, "fwd_begin")
+    update_fwd_end = partialmethod(_step, "fwd_end")
 
     def update_fwd(self, x):
         self.update_fwd_begin(x)
         self.update_fwd_end(x)
 
     # -- reverse: ghosts -> owners (add) ---------------------------------------
-    def update_rev_begin(self, x):
-        if not self.active:
-            return
-        if self.transport == "native":
-            return self._native("wf_updater_rev_begin", x)
-        self.kernels.gather(self.d_ghost_pos, x, self.d_recv_buffer)                # VectorUpdater.hpp:165-168
-        self._work = self._exchange(self.d_send_buffer, self.send_sizes, self.d_recv_buffer, self.recv_sizes)
-
-    def update_rev_end(self, x):
-        if not self.active:
-            return
-        if self.transport == "native":
-            return self._native("wf_updater_rev_end", x)
-        self._wait()
-        self.kernels.scatter_add(self.d_indices, self.d_send_buffer, x)             # VectorUpdater.hpp:196-198
+    update_rev_begin = partialmethod(_step, "rev_begin")
+    update_rev_end = partialmethod(_step, "rev_end")
 
     def update_rev(self, x):
         self.update_rev_begin(x)
@@ -312,46 +352,21 @@ class VectorUpdater:
     scatter_rev = update_rev
 
 
-_SIDE_STREAMS = {}
-
-
 def overlapped_apply(op, updater: VectorUpdater, x, y):
     """y += A x on a domain-decomposed mesh with BOTH halo directions hidden
     (LinearGLL.hpp:164-176 = scatter_fwd(x); apply; scatter_rev(y)):
 
-        side stream : update_fwd(x) -> apply(INTERFACE) -> update_rev(y)
-        main stream : apply(INTERIOR)                       (reads no ghost value)
+        halo chain : update_fwd(x) -> apply(INTERFACE) -> update_rev(y)
+        beside it  : apply(INTERIOR)                       (reads no ghost value)
 
     The interior part is one launch (splitting it further costs whole rounds of
     workgroups: 3 launches took 0.36 ms against 0.26 ms for the unsplit operator at
     cfg2), the interface cells and the two exchanges run beside it on a second HIP
     stream and fill its tail.  Requires op.set_ghost_faces(...) == True.
     Native transport: the whole sequence is wf_op_apply_overlapped of the C ABI."""
-    import torch
-    from ._lib import WF_PART_INTERFACE, WF_PART_INTERIOR
     if not x.is_cuda:
         raise RuntimeError("overlapped_apply needs device vectors")
-    if updater.transport == "native":
-        from . import _lib
-        from .operators import _ptr, _stream
-        _lib.check(_lib.lib().wf_op_apply_overlapped(op._h, updater._h, _ptr(x), _ptr(y), _stream(x)))
-        return
-    main = torch.cuda.current_stream(x.device)
-    side = _SIDE_STREAMS.get(x.device)
-    if side is None:
-        side = _SIDE_STREAMS[x.device] = torch.cuda.Stream(device=x.device)
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        updater.update_fwd(x)
-        op.apply_part(x, y, WF_PART_INTERFACE)
-        updater.update_rev_begin(y)
-    op.apply_part(x, y, WF_PART_INTERIOR)
-    # the reverse add lands on owned entries of y that the interior part may hold between its read and its write
-    # (the owner-computes box kernel updates y with plain loads and stores), so it waits for the interior part
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        updater.update_rev_end(y)
-    main.wait_stream(side)
+    updater._exchange.overlapped_apply(op, x, y)
 
 
 def owned_boundary_set(updater: VectorUpdater, V, idx, m, device):
