@@ -150,6 +150,17 @@ def _clamp(a: Num, stats: dict):
     return out, changed, inside & ~changed
 
 
+def clamp_with_bound(G, G_bound):
+    """clamp101 on values G [c][...] that carry the bounds G_bound (2 e, as point_geometry_ld returns them): (clamped G,
+    its bound, the mask of changed entries, the smallest window margin); for references that form G outside
+    _evaluate, such as a per-cell G_c times the weights"""
+    stats = {"margin": np.inf, "margin_value": np.inf}
+    shape = G.shape
+    f = G.dtype.type(BOUND_FACTOR)
+    num, mask, _ = _clamp(Num(G.reshape(shape[0], -1), G_bound.reshape(shape[0], -1) / f), stats)
+    return num.v.reshape(shape), (f * num.e).reshape(shape), mask.reshape(shape), float(np.min(stats["margin"]))
+
+
 def _evaluate(xverts, geom_dofmap, pts, wts, use_fabs, clamp, dtype, points=None):
     """hex_point_geometry of the kernel at the tensor points pts^3 (or the listed ones of them), for every cell, in
     `dtype`"""
