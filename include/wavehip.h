@@ -484,6 +484,49 @@ int wf_op_set_runs(wf_op* op, const int32_t* h_runs, int32_t nruns);
 int wf_op_get_runs(const wf_op* op, int32_t* h_runs, int32_t capacity, int32_t* nruns);
 int wf_op_destroy(wf_op* op);
 
+/* ---- cell forms: lambda^T A_c u per cell ----------------------------------------------------------
+ * Not in the reference.  Every operator here is sum_c a_c P_c^T A_c P_c; a cell form evaluates
+ *   e_c(lambda, u) = (P_c lambda)^T A^_c (P_c u),   one number per cell,
+ * A^_c being the cell matrix the operator stores: for the stiffness operator with -c0^2, the -1/0/1 clamp and a_c, for
+ * the lumped mass a_c det J w.  Without a coefficient e_c is d(lambda^T A u) / d a_c, the sensitivity kernel of an
+ * adjoint-state inversion; with lambda = u it is the cell's share of the discrete energy.  One sum-factorised pass: the
+ * geometry of an apply, two gathered vectors, one plain store per cell.
+ *   Kinds     desc->kind = WF_OP_STIFFNESS or WF_OP_MASS_LUMPED; WF_OP_MASS_DENSE is WF_ERR_UNSUPPORTED.
+ *   Set-up    that of wf_op_create: h_perm, WF_FLAG_TENSOR_X_SLOWEST, h_G / h_detJ or the mesh, WF_FLAG_NO_FABS,
+ *             WF_FLAG_NO_CLAMP and h_cell_coeff (folded in once) mean what they mean there.  WF_FLAG_ORDERED and
+ *             WF_FLAG_MASS_ELEMENTWISE are WF_ERR_INVALID: the form is order-fixed and element-wise by construction.
+ *   Output    d_out [ncells] in the caller's cell order: the rows of h_dofmap; on a box cx + nx (cy + ny cz).
+ *   Geometry  of the stiffness form: wf_tuning.geometry, the only tuning field that may be non-zero (any other is
+ *             WF_ERR_INVALID).  AUTO: one G_c per cell (48 B, times a_c) when the mesh is given, h_G is NULL and every
+ *             cell qualifies by the rule of wf_geometry_hex_cell; otherwise G per point.  PER_POINT forces G per point.
+ *             PER_CELL is WF_ERR_INVALID for a cell that does not qualify (wf_last_error names the first) or without the
+ *             mesh, and WF_ERR_UNSUPPORTED with h_G.  The lumped form ignores the field.
+ *   Order     a thread sums its column (i, j, .) with k ascending, one thread sums the n^2 columns of its cell with
+ *             j n + i ascending and stores out[c]: no atomics, bitwise reproducible; e_c depends neither on where the
+ *             cell sits in the caller's order, nor on the other cells, nor on the launch.
+ *   Checks    every argument check precedes the first device call.
+ *   Streams   an evaluation holds no scratch state: any number of evaluations of one handle may be in flight on
+ *             different streams.  d_lambda == d_u is allowed; d_out must not overlap either.
+ *   Ranks     cells are rank-local and disjoint, so a partitioned mesh needs no exchange: the caller passes lambda and
+ *             u with valid ghost entries and owns the cells it passes.
+ *   alg_bytes stiffness ncells (48 nd | 48) + 4 nd ncells + 8 ncells + 16 ndofs; lumped ncells (12 nd + 8) + 16 ndofs. */
+typedef struct wf_cell_form wf_cell_form;
+typedef struct {
+  int kind, degree, num_cells, ndofs;
+  int geometry;          /* wf_geometry_mode of the stiffness form that was built; lumped: WF_GEOMETRY_AUTO */
+  int cell_coeff;        /* 1: created with a cell coefficient array                                        */
+  double alg_bytes;      /* algorithmic HBM bytes per evaluation                                            */
+  size_t device_bytes;   /* device memory owned by the handle                                               */
+} wf_cell_form_info_t;
+int wf_cell_form_create(const wf_op_desc* desc, wf_cell_form** out);
+int wf_cell_form_create_box(int kind, int degree, int nx, int ny, int nz, const double* h_xverts, double c0,
+                            const double* h_cell_coeff, int flags, const wf_tuning* tuning, wf_cell_form** out);
+/* out[c] = (accumulate ? out[c] : 0) + alpha * e_c(lambda, u), c = row of h_dofmap; d_lambda == d_u allowed */
+int wf_cell_form_eval(const wf_cell_form* f, const double* d_lambda, const double* d_u, double alpha, int accumulate,
+                      double* d_out, void* stream);
+int wf_cell_form_info(const wf_cell_form* f, wf_cell_form_info_t* info);
+int wf_cell_form_destroy(wf_cell_form* f);
+
 /* ---- a8/a9: free kernels --------------------------------------------------
  * common/cuda/scatter.hpp:7-14, transform.hpp:7-8 (the reference passes a block
  * size; launch geometry is internal here). */

@@ -316,6 +316,65 @@ public:
   }
 };
 
+/// Cell form of an operator: e_c(lambda, u) = (P_c lambda)^T A_c (P_c u), one number per cell in the order of the
+/// dofmap's rows (wavehip.h, "cell forms").  kind: WF_OP_STIFFNESS (params["c0"], default 1500) or WF_OP_MASS_LUMPED.
+/// tuning may set geometry only.  The box constructor is the form on mesh::create_box with this engine's numbering.
+/// eval holds no scratch state: evaluations of one form may be in flight on different streams.
+template <typename T>
+class CellForm {
+  static_assert(sizeof(T) == sizeof(double), "fp64 only");
+
+public:
+  CellForm(const Space& V, int degree, int kind, std::map<std::string, double>& params, const wf_tuning* tuning = nullptr,
+           const double* cell_coeff = nullptr, int flags = WF_FLAG_NONE)
+  {
+    wf_op_desc d{};
+    d.kind = kind;
+    d.degree = degree;
+    d.ncells = V.ncells;
+    d.ndofs = V.ndofs;
+    d.h_dofmap = V.dofmap;
+    d.h_perm = V.perm;
+    d.flags = V.tensor_flags | flags;
+    d.nverts = V.nverts;
+    d.h_xverts = V.x;
+    d.h_geom_dofmap = V.geom_dofmap;
+    auto it = params.find("c0");
+    d.c0 = it == params.end() ? 1500.0 : it->second;
+    d.tuning = tuning;
+    d.h_cell_coeff = cell_coeff;
+    check(wf_cell_form_create(&d, &_f));
+  }
+  CellForm(int kind, int degree, int nx, int ny, int nz, const double* xverts, double c0, const wf_tuning* tuning = nullptr,
+           const double* cell_coeff = nullptr, int flags = WF_FLAG_NONE)
+  {
+    check(wf_cell_form_create_box(kind, degree, nx, ny, nz, xverts, c0, cell_coeff, flags, tuning, &_f));
+  }
+  CellForm(const CellForm&) = delete;
+  CellForm& operator=(const CellForm&) = delete;
+  ~CellForm() { wf_cell_form_destroy(_f); }
+
+  /// out[c] = (accumulate ? out[c] : 0) + alpha e_c(lambda, u); lambda may be u
+  void eval(const double* d_lambda, const double* d_u, double* d_out, double alpha = 1.0, bool accumulate = false,
+            void* stream = nullptr) const
+  {
+    check(wf_cell_form_eval(_f, d_lambda, d_u, alpha, accumulate ? 1 : 0, d_out, stream));
+  }
+  wf_cell_form_info_t info() const
+  {
+    wf_cell_form_info_t i{};
+    check(wf_cell_form_info(_f, &i));
+    return i;
+  }
+  std::size_t num_cells() const { return info().num_cells; }
+  int geometry() const { return info().geometry; }
+  bool cell_coeff() const { return info().cell_coeff != 0; }
+  wf_cell_form* handle() const { return _f; }
+
+private:
+  wf_cell_form* _f = nullptr;
+};
+
 // ---- communicator + VectorUpdater (demo/gpu_scatter_mpi/VectorUpdater.hpp) ----
 /// RCCL communicator behind the C ABI.  The reference's launcher is mpirun; a
 /// launcher that exports RANK / WORLD_SIZE / LOCAL_RANK (torchrun --no-python,

@@ -185,6 +185,49 @@ def bench_medium(dev):
           {"cells": V.ncells, "ndofs": N})
 
 
+def bench_cellform(dev):
+    """Cell forms on the cfg2 box (P4, 54^3 cells, ~10.2 M dofs) next to the applies that read the same data, alternating
+    in one process (CELLFORM_ROUNDS rounds, default 5; every timing after the settle protocol of timeit):
+      (a) the default stiffness apply;  (b) the apply under tuning = {"kernel": "elementwise"}, per-point geometry -- the
+      kernel whose body the per-point form shares, and its yardstick;  (c) the per-point form;  (d) the per-cell form;
+      (e) the lumped form.  One line per leg: median and range of the rounds."""
+    rounds = int(os.environ.get("CELLFORM_ROUNDS", "5"))
+    p, n = 4, int(os.environ.get("CELLFORM_N", "54"))
+    mesh = w.create_box(n)
+    V = w.create_functionspace(mesh, p, build_dofmap=True)
+    N = V.ndofs
+    x = torch.rand(N, dtype=torch.float64, device=dev)
+    lam = torch.rand(N, dtype=torch.float64, device=dev)
+    y = torch.zeros(N, dtype=torch.float64, device=dev)
+    out = torch.zeros(mesh.ncells, dtype=torch.float64, device=dev)
+    apply_default = w.StiffnessOperator(V, p)
+    apply_elementwise = w.StiffnessOperator(V, p, structured=False, tuning={"kernel": "elementwise", "keep_cell_order": True})
+    form_point = w.CellForm(V, p, tuning={"geometry": "per_point"})
+    form_cell = w.CellForm(V, p)
+    form_lumped = w.CellForm(V, p, "mass_lumped")
+    assert (apply_elementwise.kernel, form_point.geometry, form_cell.geometry) == ("elementwise", "per_point", "per_cell")
+    legs = [("a", f"stiffness apply [{apply_default.kernel} {apply_default.update}]", lambda: apply_default(x, y), apply_default.alg_bytes(),
+             apply_default.info.device_bytes),
+            ("b", "stiffness apply [elementwise, per point]", lambda: apply_elementwise(x, y), apply_elementwise.alg_bytes(),
+             apply_elementwise.info.device_bytes),
+            ("c", "cell form stiffness [per point]", lambda: form_point.eval(lam, x, out=out), form_point.info.alg_bytes,
+             form_point.info.device_bytes),
+            ("d", "cell form stiffness [per cell]", lambda: form_cell.eval(lam, x, out=out), form_cell.info.alg_bytes,
+             form_cell.info.device_bytes),
+            ("e", "cell form lumped mass", lambda: form_lumped.eval(lam, x, out=out), form_lumped.info.alg_bytes,
+             form_lumped.info.device_bytes)]
+    ms = {leg[0]: [] for leg in legs}
+    for _ in range(rounds):
+        for key, _, fn, _, _ in legs:
+            ms[key].append(timeit(fn))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    for key, name, _, alg_bytes, device_bytes in legs:
+        report(f"({key}) {name} P{p} box {n}^3", med[key], alg_bytes, N,
+               {"cells": mesh.ncells, "ndofs": N, "alg_bytes": alg_bytes, "device_bytes": device_bytes,
+                "ms_rounds": [round(v, 4) for v in ms[key]], "ms_min": round(min(ms[key]), 4), "ms_max": round(max(ms[key]), 4),
+                "over_b": round(med[key] / med["b"], 4)})
+
+
 def bench_tet_against(dev, other_path):
     """The default (no coefficient) P4 tetrahedral stiffness apply and mass apply of this library against ANOTHER build of
     libwavehip -- the parent commit's, say -- with both libraries loaded into this one process, the same operator created
@@ -288,6 +331,11 @@ def main():
     if "tet-ab" in only:
         bench_tet_against(dev, os.environ["WAVEHIP_LIB_B"])
         only = [o for o in only if o != "tet-ab"]
+        if not only:
+            return
+    if "cellform" in only:
+        bench_cellform(dev)
+        only = [o for o in only if o != "cellform"]
         if not only:
             return
     if "medium" in only:

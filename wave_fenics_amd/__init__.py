@@ -11,7 +11,7 @@ There is no CPU fallback: importing the operators without libwavehip raises.
 from ._lib import lib, check, WavehipError  # noqa: F401
 from .box import BoxMesh, FunctionSpace, IndexMap, create_box, create_functionspace, lattice_numbering, renumber  # noqa: F401
 from .operators import (  # noqa: F401
-    StiffnessOperator, MassOperator, SpectralMassOperator, MassOperatorLumped,
+    StiffnessOperator, MassOperator, SpectralMassOperator, MassOperatorLumped, CellForm,
     gather, scatter, transform1, tsmm, tabulate_gll, tabulate_dense, precompute_geometric_data,
     quadrature_1d, tabulate_1d, compute_geometry_rule, hex_cell_geometry, ordered_slots, segment_sum_add, box_run_plan,
 )

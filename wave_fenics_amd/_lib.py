@@ -69,6 +69,14 @@ class OpInfo(ctypes.Structure):
     ]
 
 
+class CellFormInfo(ctypes.Structure):
+    """wf_cell_form_info_t"""
+    _fields_ = [
+        ("kind", c_int), ("degree", c_int), ("num_cells", c_int), ("ndofs", c_int), ("geometry", c_int),
+        ("cell_coeff", c_int), ("alg_bytes", c_double), ("device_bytes", c_size_t),
+    ]
+
+
 class UpdaterDesc(ctypes.Structure):
     _fields_ = [
         ("ndofs", c_int),
@@ -243,6 +251,12 @@ SIGNATURES = {
     "wf_sources_destroy": (c_int, [c_void_p]),
     "wf_sources_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "wf_sources_add": (c_int, [c_void_p, c_double, c_void_p, c_void_p]),
+    "wf_cell_form_create": (c_int, [POINTER(OpDesc), POINTER(c_void_p)]),
+    "wf_cell_form_create_box": (c_int, [c_int, c_int, c_int, c_int, c_int, _DP, c_double, _DP, c_int, POINTER(Tuning),
+                                        POINTER(c_void_p)]),
+    "wf_cell_form_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p]),
+    "wf_cell_form_info": (c_int, [c_void_p, POINTER(CellFormInfo)]),
+    "wf_cell_form_destroy": (c_int, [c_void_p]),
 }
 
 _LIB = None

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libwavehip.so")
 SOURCES = [
     "tables.cpp", "mesh_io.cpp", "march_plan.cpp", "box_run_plan.cpp", "function_space.cpp", "box_space.cpp", "markers.cpp", "point_locate.cpp",
     "hex_geometry.hip", "stiffness_batch.hip", "mass_batch.hip", "stiffness_march.hip", "stiffness_march_owner.hip", "stiffness_march_idx.hip", "stiffness_march_ks.hip",
-    "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "mass_dense_simplex.hip", "tsmm.hip", "vector_kernels.hip", "time_step.hip", "comm.hip", "updater.hip", "cg.hip", "points.hip", "api.hip",
+    "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "mass_dense_simplex.hip", "tsmm.hip", "vector_kernels.hip", "time_step.hip", "comm.hip", "updater.hip", "cg.hip", "points.hip", "cell_form.hip", "api.hip",
     "hex_cell_geometry.cpp", "op_setup.hip", "op_create.hip", "op_create_box.hip", "op_apply.hip",
 ]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_array.h"), os.path.join(CSRC, "op.h"),

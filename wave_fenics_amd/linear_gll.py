@@ -35,7 +35,7 @@ from ._lib import _dp, _ip, check, lib
 from .box import _int3
 from .distributed import overlapped_apply
 from .mesh_io import cfl_time_step  # noqa: F401  (demo/cpu_planar3d/main.cpp:48-66: one function for box and file meshes)
-from .operators import MassOperatorLumped, StiffnessOperator
+from .operators import CellForm, MassOperatorLumped, StiffnessOperator
 
 
 def facet_lumped_mass(V, tag_of_face, tag: int, cell_weight=None):
@@ -93,6 +93,8 @@ class LinearGLLOpt:
         self.T_ = 1.0 / self.freq0_
         self.alpha_ = 4.0
         self.updater = updater
+        self._structured = structured
+        self._cell_forms = None   # (stiffness form, lumped-mass form), built on first use (cell_forms)
         self.size_local = V.index_map.size_local
         N = V.ndofs
         z = lambda: torch.zeros(N, dtype=torch.float64, device=self.device)
@@ -454,3 +456,28 @@ class LinearGLLOpt:
         without the absorbing term).  max_eigenvalue approaches lambda_max from below, so the limit is overestimated by
         up to ~0.04 % after 100 iterations; safety covers it.  One rank."""
         return safety * 2.0 / math.sqrt(self.max_eigenvalue(iters))
+
+    def cell_forms(self):
+        """(stiffness form, lumped-mass form) of the model's operators: operators.CellForm with the model's c0, or with
+        the medium's stiff_coeff / mass_coeff as cell_coeff.  Built on first use and kept.  One rank."""
+        if self.updater is not None:
+            raise NotImplementedError("LinearGLLOpt.cell_forms on a partitioned mesh (updater=) is not implemented")
+        if self._cell_forms is None:
+            if self.medium is None:
+                self._cell_forms = (CellForm(self.V, self.k_, "stiffness", {"c0": self.c0_}, structured=self._structured),
+                                    CellForm(self.V, self.k_, "mass_lumped", structured=self._structured))
+            else:
+                self._cell_forms = (CellForm(self.V, self.k_, "stiffness", {"c0": 1.0}, structured=self._structured,
+                                             cell_coeff=self.medium.stiff_coeff),
+                                    CellForm(self.V, self.k_, "mass_lumped", structured=self._structured,
+                                             cell_coeff=self.medium.mass_coeff))
+        return self._cell_forms
+
+    def cell_energy(self, out=None):
+        """The discrete energy per cell, 1/2 e^M_c(v_n, v_n) - 1/2 e^K_c(u_n, u_n) (K carries its minus sign, so both
+        terms are non-negative); its sum is 1/2 v^T (m .* v) - 1/2 u^T K u.  Returns out [ncells].  One rank."""
+        if self.updater is not None:
+            raise NotImplementedError("LinearGLLOpt.cell_energy on a partitioned mesh (updater=) is not implemented")
+        kform, mform = self.cell_forms()
+        out = mform.eval(self.v_n, self.v_n, out=out, alpha=0.5)
+        return kform.eval(self.u_n, self.u_n, out=out, alpha=-0.5, accumulate=True)

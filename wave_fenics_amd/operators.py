@@ -438,6 +438,96 @@ class MassOperatorLumped(_Operator):
         self._create(d, keep, tuning, cell_coeff)
 
 
+class CellForm:
+    """Cell form of an operator: e_c(lambda, u) = (P_c lambda)^T A_c (P_c u), one number per cell (wf_cell_form,
+    include/wavehip.h).  A_c is the cell matrix the operator of the same arguments stores: for kind="stiffness" with
+    -c0^2, the clamp and cell_coeff, for kind="mass_lumped" cell_coeff det J w.  Without cell_coeff e_c is the
+    derivative of lambda^T A u with respect to the cell's coefficient; with lambda = u the cell's share of the energy.
+
+    The constructor arguments and the box / dofmap choice (`structured`) are those of StiffnessOperator and
+    MassOperatorLumped.  tuning may hold "geometry" only ("auto": one G_c per cell where every cell is affine, else G
+    per point; "per_point"; "per_cell": raises WavehipError naming the first cell that does not qualify).  The result
+    is in the mesh's cell order, bitwise reproducible, and independent of where a cell sits in that order."""
+
+    KINDS = {"stiffness": _lib.WF_OP_STIFFNESS, "mass_lumped": _lib.WF_OP_MASS_LUMPED, "mass_dense": _lib.WF_OP_MASS_DENSE}
+
+    def __init__(self, V: FunctionSpace, degree: int, kind: str = "stiffness", params: dict | None = None, G=None,
+                 detJ=None, perm=None, structured: bool | None = None, cell_coeff=None, tuning=None, flags: int = 0):
+        self._h = c_void_p()
+        if kind not in self.KINDS:
+            raise _lib.WavehipError(f"CellForm: kind must be one of {sorted(self.KINDS)}")
+        k = self.KINDS[kind]
+        self.kind = kind
+        self.c0 = 1500.0 if not params else float(params.get("c0", 1500.0))
+        t = make_tuning(tuning)
+        a = _cell_coeff(cell_coeff, V.mesh.ncells)
+        if structured is None:
+            structured = bool(getattr(V, "structured", False)) and G is None and detJ is None and perm is None
+        if structured:
+            if degree != V.degree:
+                raise _lib.WavehipError("structured cell form: degree must equal the space's degree")
+            nx, ny, nz = V.mesh.n
+            x = np.ascontiguousarray(V.mesh.x, dtype=np.float64)
+            check(lib().wf_cell_form_create_box(k, degree, nx, ny, nz, _dp(x), self.c0, _dp(a), flags,
+                                                ctypes.byref(t) if t is not None else None, ctypes.byref(self._h)))
+        else:
+            d, keep = _base_desc(V, k, degree, perm)
+            d.c0 = self.c0
+            d.flags = flags
+            if k == _lib.WF_OP_STIFFNESS and G is not None:
+                Gc = np.ascontiguousarray(G, dtype=np.float64)
+                if Gc.size != V.mesh.ncells * (degree + 1) ** 3 * 9:
+                    raise _lib.WavehipError("G must be [ncells][nq][3][3]")
+                keep.append(Gc)
+                d.h_G = _dp(Gc)
+            elif k != _lib.WF_OP_STIFFNESS and detJ is not None:
+                Dc = np.ascontiguousarray(detJ, dtype=np.float64)
+                keep.append(Dc)
+                d.h_detJ = _dp(Dc)
+            else:
+                _attach_mesh(d, V, keep)
+            d.h_cell_coeff = _dp(a)
+            if t is not None:
+                d.tuning = ctypes.pointer(t)
+            check(lib().wf_cell_form_create(ctypes.byref(d), ctypes.byref(self._h)))
+        info = _lib.CellFormInfo()
+        check(lib().wf_cell_form_info(self._h, ctypes.byref(info)))
+        self.info = info
+
+    @property
+    def geometry(self) -> str:
+        """How the stiffness form stores its geometry: "per_point", "per_cell", or "none" (lumped mass)."""
+        return {1: "per_point", 2: "per_cell"}.get(self.info.geometry, "none")
+
+    def eval(self, lam, u, out=None, alpha: float = 1.0, accumulate: bool = False, stream: int | None = None):
+        """out[c] = (out[c] if accumulate else 0) + alpha e_c(lam, u); returns out (a new device vector when None).
+        lam may be u.  Any number of evaluations may be in flight on different streams."""
+        _check_vec(lam, self.info.ndofs, "lam")
+        _check_vec(u, self.info.ndofs, "u")
+        if out is None:
+            if accumulate:
+                raise _lib.WavehipError("CellForm.eval: accumulate needs out")
+            import torch
+            out = torch.empty(self.info.num_cells, dtype=torch.float64, device=u.device)
+        _check_vec(out, self.info.num_cells, "out")
+        s = _stream(u) if stream is None else stream
+        check(lib().wf_cell_form_eval(self._h, _ptr(lam), _ptr(u), float(alpha), int(bool(accumulate)), _ptr(out), s))
+        return out
+
+    __call__ = eval
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib().wf_cell_form_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class SpectralMassOperator(MassOperatorLumped):
     """SpectralMassOperator(V, bdegree) -- common/cuda/spectral_mass.hpp:24-100.
     Same lumped mass; detJ = det(J) w WITHOUT fabs (spectral_mass.hpp:58-64 via
