@@ -150,6 +150,23 @@ struct Space {
 };
 
 namespace detail {
+/// the descriptor of wf_op_create and wf_cell_form_create on the space V: sizes, dofmap, tensor frame and mesh
+inline wf_op_desc hex_desc(const Space& V, int kind, int degree)
+{
+  wf_op_desc d{};
+  d.kind = kind;
+  d.degree = degree;
+  d.ncells = V.ncells;
+  d.ndofs = V.ndofs;
+  d.h_dofmap = V.dofmap;
+  d.h_perm = V.perm;
+  d.flags = V.tensor_flags;
+  d.nverts = V.nverts;
+  d.h_xverts = V.x;
+  d.h_geom_dofmap = V.geom_dofmap;
+  return d;
+}
+
 class OpBase {
 public:
   OpBase() = default;
@@ -181,21 +198,6 @@ protected:
     check(wf_op_info(_op, &i));
     return i;
   }
-  static wf_op_desc base_desc(const Space& V, int kind, int degree)
-  {
-    wf_op_desc d{};
-    d.kind = kind;
-    d.degree = degree;
-    d.ncells = V.ncells;
-    d.ndofs = V.ndofs;
-    d.h_dofmap = V.dofmap;
-    d.h_perm = V.perm;
-    d.flags = V.tensor_flags;
-    d.nverts = V.nverts;
-    d.h_xverts = V.x;
-    d.h_geom_dofmap = V.geom_dofmap;
-    return d;
-  }
   wf_op* _op = nullptr;
 };
 }  // namespace detail
@@ -214,7 +216,7 @@ public:
   StiffnessOperator(const Space& V, int bdegree, std::map<std::string, double>& params, const wf_tuning* tuning = nullptr,
                     const double* cell_coeff = nullptr)
   {
-    wf_op_desc d = base_desc(V, WF_OP_STIFFNESS, bdegree);
+    wf_op_desc d = detail::hex_desc(V, WF_OP_STIFFNESS, bdegree);
     auto it = params.find("c0");
     d.c0 = it == params.end() ? 1500.0 : it->second;   // operators.hpp:114
     d.tuning = tuning;
@@ -230,7 +232,7 @@ class MassOperatorLumped : public detail::OpBase {
 public:
   MassOperatorLumped(const Space& V, int bdegree, int flags = WF_FLAG_NONE, const double* cell_coeff = nullptr)
   {
-    wf_op_desc d = base_desc(V, WF_OP_MASS_LUMPED, bdegree);
+    wf_op_desc d = detail::hex_desc(V, WF_OP_MASS_LUMPED, bdegree);
     d.flags |= flags;
     d.h_cell_coeff = cell_coeff;
     check(wf_op_create(&d, &_op));
@@ -263,7 +265,7 @@ public:
   MassOperator(const Space& V, int degree, int nq1, const double* phi1, const double* detJ, const wf_tuning* tuning = nullptr,
                const double* cell_coeff = nullptr)
   {
-    wf_op_desc d = base_desc(V, WF_OP_MASS_DENSE, degree);
+    wf_op_desc d = detail::hex_desc(V, WF_OP_MASS_DENSE, degree);
     d.nq1 = nq1;
     d.h_phi1 = phi1;
     d.h_detJ = detJ;
@@ -283,7 +285,7 @@ public:
     check(wf_quadrature_1d(quad_type, qd, &nq1, pts, wts));
     std::vector<double> phi1((std::size_t)nq1 * (degree + 1));
     check(wf_tabulate_1d(degree, variant, nq1, pts, 0, phi1.data()));
-    wf_op_desc d = base_desc(V, WF_OP_MASS_DENSE, degree);
+    wf_op_desc d = detail::hex_desc(V, WF_OP_MASS_DENSE, degree);
     d.nq1 = nq1;
     d.h_phi1 = phi1.data();
     d.h_qpts1 = pts;
@@ -328,17 +330,8 @@ public:
   CellForm(const Space& V, int degree, int kind, std::map<std::string, double>& params, const wf_tuning* tuning = nullptr,
            const double* cell_coeff = nullptr, int flags = WF_FLAG_NONE)
   {
-    wf_op_desc d{};
-    d.kind = kind;
-    d.degree = degree;
-    d.ncells = V.ncells;
-    d.ndofs = V.ndofs;
-    d.h_dofmap = V.dofmap;
-    d.h_perm = V.perm;
-    d.flags = V.tensor_flags | flags;
-    d.nverts = V.nverts;
-    d.h_xverts = V.x;
-    d.h_geom_dofmap = V.geom_dofmap;
+    wf_op_desc d = detail::hex_desc(V, kind, degree);
+    d.flags |= flags;
     auto it = params.find("c0");
     d.c0 = it == params.end() ? 1500.0 : it->second;
     d.tuning = tuning;

@@ -1,12 +1,14 @@
 // Walks the host-only box entries (csrc/box_space.cpp with function_space.cpp and tables.cpp) over the partition and
 // facet-mass cases of tests/test_box_host.py, each with the size-only call followed by the fill call into arrays of
-// exactly the reported sizes.  Built as a stand-alone program with -fsanitize=address,undefined by
+// exactly the reported sizes, and builds the box description of csrc/box_mesh.h at four (degree, box) pairs, compared
+// entry by entry with wf_box_dofmap, wf_box_mesh and box_vertex.  Built as a stand-alone program with -fsanitize=address,undefined by
 // tests/test_box_host.py::test_box_space_sanitized: the sanitizers see every read and write of the library code.
 // Prints one checksum line; exit status 0 when every call returned what it should.
 #include <cstdint>
 #include <cstdio>
 #include <vector>
 
+#include "box_mesh.h"
 #include "wavehip.h"
 
 static int failures = 0;
@@ -96,6 +98,41 @@ static double walk_facets(const int* n, int p, bool weighted)
   return sum + h;
 }
 
+// The box as a dofmap mesh (csrc/box_mesh.h): the description the box entry points hand to the dofmap entry points,
+// entry by entry against wf_box_dofmap, wf_box_mesh and box_vertex, and every field of its descriptor.
+static long long walk_box_desc(int p, int nx, int ny, int nz)
+{
+  const int n[3] = {nx, ny, nz}, nd = (p + 1) * (p + 1) * (p + 1);
+  const std::size_t ncells = (std::size_t)nx * ny * nz, nverts = (std::size_t)(nx + 1) * (ny + 1) * (nz + 1);
+  const double lo[3] = {0.0, 0.0, 0.0}, hi[3] = {1.0, 2.0, 3.0};
+  std::vector<double> x(nverts * 3), coeff(ncells, 1.5);
+  std::vector<std::int32_t> gd(ncells * 8), dm(ncells * nd);
+  EXPECT(wf_box_mesh(n, lo, hi, x.data(), gd.data()) == WF_OK);
+  EXPECT(wf_box_dofmap(p, n, dm.data()) == WF_OK);
+  EXPECT(wf::check_box_args("walk", p, nx, ny, nz, x.data()) == WF_OK);
+  wf_tuning tun{};
+  const wf::BoxDesc box(WF_OP_MASS_LUMPED, p, nx, ny, nz, x.data(), 1500.0, coeff.data(), WF_FLAG_ORDERED, &tun);
+  const wf_op_desc& d = box.desc;
+  EXPECT(box.dofmap.size() == dm.size() && box.geom_dofmap.size() == gd.size());
+  EXPECT(d.h_dofmap == box.dofmap.data() && d.h_geom_dofmap == box.geom_dofmap.data() && d.h_xverts == x.data());
+  EXPECT(d.kind == WF_OP_MASS_LUMPED && d.degree == p && d.ncells == (int)ncells && d.nverts == (int)nverts);
+  EXPECT(d.ndofs == (p * nx + 1) * (p * ny + 1) * (p * nz + 1));
+  EXPECT(d.c0 == 1500.0 && d.flags == WF_FLAG_ORDERED && d.tuning == &tun && d.h_cell_coeff == coeff.data());
+  EXPECT(!d.h_perm && !d.h_G && !d.h_detJ && d.nq1 == 0 && !d.h_phi1 && !d.h_qpts1 && !d.h_qwts1);
+  long long sum = 0;
+  for (std::size_t e = 0; e < dm.size() && e < box.dofmap.size(); ++e) {
+    EXPECT(box.dofmap[e] == dm[e] && dm[e] >= 0 && dm[e] < d.ndofs);
+    sum += box.dofmap[e];
+  }
+  for (std::size_t c = 0; c < ncells && 8 * c < box.geom_dofmap.size(); ++c)
+    for (int v = 0; v < 8; ++v) {
+      const std::int32_t got = box.geom_dofmap[c * 8 + v];
+      EXPECT(got == gd[c * 8 + v] && got == (std::int32_t)wf::box_vertex(nx, ny, c, v) && got >= 0 && got < d.nverts);
+      sum += got;
+    }
+  return sum;
+}
+
 int main()
 {
   const int cases[][8] = {  // world, nx, ny, nz, degree, periodic x y z
@@ -109,6 +146,12 @@ int main()
   double fsum = 0.0;
   for (const auto& b : boxes)
     for (int weighted = 0; weighted < 2; ++weighted) fsum += walk_facets(b, b[3], weighted != 0);
+  const int descs[][4] = {{1, 1, 1, 1}, {2, 2, 1, 3}, {4, 1, 2, 2}, {7, 1, 1, 2}};   // degree, nx, ny, nz
+  long long dsum = 0;
+  for (const auto& b : descs) dsum += walk_box_desc(b[0], b[1], b[2], b[3]);
+  EXPECT(wf::check_box_args("walk", 8, 1, 1, 1, &fsum) == WF_ERR_UNSUPPORTED);
+  EXPECT(wf::check_box_args("walk", 2, 1, 0, 1, &fsum) == WF_ERR_INVALID && wf::check_box_args("walk", 2, 1, 1, 1, nullptr) == WF_ERR_INVALID);
+  EXPECT(wf::check_box_args("walk", 2, 2, 1, 1 << 30, &fsum) == WF_ERR_INVALID);
   // refusals leave the outputs alone
   wf_box_partition_info info;
   const int n[3] = {2, 2, 2}, zero[3] = {2, 0, 2};
@@ -116,6 +159,7 @@ int main()
   EXPECT(wf_box_partition(zero, 2, 4, 0, nullptr, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == WF_ERR_INVALID);
   EXPECT(wf_box_partition(n, 9, 4, 0, nullptr, &info, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == WF_ERR_INVALID);
   EXPECT(wf_box_partition(n, 2, 4, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == WF_ERR_INVALID);
-  std::printf("partition checksum %lld, facet checksum %.17g, %d failures\n", isum, fsum, failures);
+  std::printf("partition checksum %lld, facet checksum %.17g, box description checksum %lld, %d failures\n", isum, fsum, dsum,
+              failures);
   return failures ? 1 : 0;
 }

@@ -201,7 +201,8 @@ def test_bad_arguments(wlib):
 def test_box_space_sanitized(tmp_path):
     """memory safety of the host code: box_space.cpp, function_space.cpp and tables.cpp built into a stand-alone program
     with AddressSanitizer and UndefinedBehaviorSanitizer (host code only; nothing of it is loaded into this process),
-    walking the cases above with the size-only call followed by the fill call into arrays of exactly those sizes"""
+    walking the cases above with the size-only call followed by the fill call into arrays of exactly those sizes, and the
+    box written out as a dofmap mesh (csrc/box_mesh.h) against wf_box_dofmap, wf_box_mesh and box_vertex"""
     import os
     import subprocess
     from wave_fenics_amd import build

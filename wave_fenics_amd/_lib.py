@@ -297,6 +297,25 @@ def _ip(a):
     return None if a is None else a.ctypes.data_as(_IP)
 
 
+class Handle:
+    """Owner of one library handle, self._h (a c_void_p), freed by the wf_*_destroy function a subclass names: close()
+    once or many times, or the garbage collector.  A closed object holds the null handle, which every entry point
+    refuses."""
+    _destroy: str = ""
+
+    def close(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            getattr(lib(), self._destroy)(h)
+        self._h = c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def check(rc: int):
     if rc != 0:
         msg = lib().wf_last_error().decode(errors="replace")

@@ -16,7 +16,7 @@ SOURCES = [
     "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "mass_dense_simplex.hip", "tsmm.hip", "vector_kernels.hip", "time_step.hip", "comm.hip", "updater.hip", "cg.hip", "points.hip", "cell_form.hip", "api.hip",
     "hex_cell_geometry.cpp", "op_setup.hip", "op_create.hip", "op_create_box.hip", "op_apply.hip",
 ]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_array.h"), os.path.join(CSRC, "op.h"),
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_array.h"), os.path.join(CSRC, "op.h"), os.path.join(CSRC, "box_mesh.h"),
            os.path.join(CSRC, "stiffness_core.h"), os.path.join(CSRC, "cell_batch.h"), os.path.join(CSRC, "stiffness_elementwise.h"),
            os.path.join(CSRC, "march_column.h"), os.path.join(CSRC, "box_run_plan.h"), os.path.join(CSRC, "march_plan.h"), os.path.join(CSRC, "dense_simplex.h"), os.path.join(CSRC, "owner_pieces.h"), os.path.join(CSRC, "points_plan.h"), os.path.join(CSRC, "comm.h"),
            os.path.join(ROOT, "include", "wavehip.h")]

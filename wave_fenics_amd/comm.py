@@ -10,11 +10,13 @@ import ctypes
 from ctypes import c_int, c_void_p
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import Handle, check, lib
 from .operators import _ptr, _stream
 
 
-class Comm:
+class Comm(Handle):
+    _destroy = "wf_comm_destroy"
+
     def __init__(self, handle: c_void_p, rank: int, size: int):
         self._h = handle
         self.rank = rank
@@ -86,14 +88,3 @@ class Comm:
 
     def barrier(self, stream: int = 0):
         check(lib().wf_comm_barrier(self._h, stream))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().wf_comm_destroy(self._h)
-            self._h = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

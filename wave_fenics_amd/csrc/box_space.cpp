@@ -66,6 +66,60 @@ void emit_segments(std::vector<Segment>& segs, const int* lattice, const int* ow
 
 }  // namespace
 
+// ---- the box as a dofmap mesh (box_mesh.h) ----
+void wf::fill_box_dofmap(int P, int nx, int ny, int nz, int32_t* dofmap)
+{
+  const int n = P + 1, nd = n * n * n;
+  const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1;
+  for (int cz = 0; cz < nz; ++cz)
+    for (int cy = 0; cy < ny; ++cy)
+      for (int cx = 0; cx < nx; ++cx) {
+        const size_t c = (size_t)cx + (size_t)nx * (cy + (size_t)ny * cz);
+        const size_t base = (size_t)P * cx + NX * ((size_t)P * cy + NY * ((size_t)P * cz));
+        for (int k = 0; k < n; ++k)
+          for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) dofmap[c * nd + i + n * (j + n * k)] = (int32_t)(base + i + NX * (j + NY * k));
+      }
+}
+
+void wf::fill_box_vertex_map(int nx, int ny, int nz, int32_t* geom_dofmap)
+{
+  const size_t ncells = (size_t)nx * ny * nz;
+  for (size_t c = 0; c < ncells; ++c)
+    for (int v = 0; v < 8; ++v) geom_dofmap[c * 8 + v] = (int32_t)box_vertex(nx, ny, c, v);
+}
+
+int wf::check_box_args(const char* who, int degree, int nx, int ny, int nz, const double* h_xverts)
+{
+  if (int rc = check_hex_degree(degree, who)) return rc;
+  WF_REQUIRE(nx > 0 && ny > 0 && nz > 0 && h_xverts, std::string(who) + ": bad mesh");
+  const size_t NX = (size_t)degree * nx + 1, NY = (size_t)degree * ny + 1, NZ = (size_t)degree * nz + 1;
+  WF_REQUIRE(NX * NY * NZ < ((size_t)1 << 31), std::string(who) + ": dof lattice exceeds int32");
+  return WF_OK;
+}
+
+wf::BoxDesc::BoxDesc(int kind, int P, int nx, int ny, int nz, const double* h_xverts, double c0, const double* h_cell_coeff,
+                     int flags, const wf_tuning* tuning)
+{
+  const size_t ncells = (size_t)nx * ny * nz, nd = (size_t)(P + 1) * (P + 1) * (P + 1);
+  dofmap.resize(ncells * nd);
+  geom_dofmap.resize(ncells * 8);
+  fill_box_dofmap(P, nx, ny, nz, dofmap.data());
+  fill_box_vertex_map(nx, ny, nz, geom_dofmap.data());
+  desc.kind = kind;
+  desc.degree = P;
+  desc.ncells = (int)ncells;
+  desc.ndofs = (int)(((size_t)P * nx + 1) * ((size_t)P * ny + 1) * ((size_t)P * nz + 1));
+  desc.h_dofmap = dofmap.data();
+  desc.nverts = (nx + 1) * (ny + 1) * (nz + 1);
+  desc.h_xverts = h_xverts;
+  desc.h_geom_dofmap = geom_dofmap.data();
+  desc.c0 = c0;
+  desc.flags = flags;
+  desc.tuning = tuning;
+  desc.h_cell_coeff = h_cell_coeff;
+}
+
 extern "C" {
 
 int wf_box_mesh(const int* n, const double* lo, const double* hi, double* h_x, int32_t* h_geom_dofmap)
@@ -86,9 +140,7 @@ int wf_box_mesh(const int* n, const double* lo, const double* hi, double* h_x, i
         // numpy.linspace: lo + step * i, the last point exactly hi
         for (int d = 0; d < 3; ++d) h_x[v * 3 + d] = i[d] == n[d] ? hi[d] : lo[d] + step[d] * i[d];
       }
-  const size_t ncells = (size_t)nx * ny * nz;
-  for (size_t cell = 0; cell < ncells; ++cell)
-    for (int q = 0; q < 8; ++q) h_geom_dofmap[cell * 8 + q] = (int32_t)box_vertex(nx, ny, cell, q);
+  fill_box_vertex_map(nx, ny, nz, h_geom_dofmap);
   return WF_OK;
 }
 
@@ -98,14 +150,7 @@ int wf_box_dofmap(int degree, const int* n, int32_t* h_dofmap)
   int64_t N[3];
   WF_REQUIRE(!box_sizes_error(n) && box_lattice(degree, n, N), "wf_box_dofmap: n must be three positive cell counts, fewer than 2^31 dofs");
   WF_REQUIRE(h_dofmap, "wf_box_dofmap: null output");
-  const int P = degree, nn = P + 1;
-  int32_t* out = h_dofmap;
-  for (int cz = 0; cz < n[2]; ++cz)
-    for (int cy = 0; cy < n[1]; ++cy)
-      for (int cx = 0; cx < n[0]; ++cx)
-        for (int k = 0; k < nn; ++k)
-          for (int j = 0; j < nn; ++j)
-            for (int i = 0; i < nn; ++i) *out++ = (int32_t)((P * cx + i) + N[0] * ((P * cy + j) + N[1] * (P * cz + k)));
+  fill_box_dofmap(degree, n[0], n[1], n[2], h_dofmap);
   return WF_OK;
 }
 

@@ -186,19 +186,13 @@ int launch_cell_form(const wf_cell_form* f, const double* d_lam, const double* d
 // and the tables of the box set-up (D, D^T, the 1-D weights).  The per-point arrays are never allocated.
 int create_per_cell(const wf_op_desc* desc, std::vector<double>& h_Gc, wf_op* op)
 {
-  const size_t ncells = (size_t)desc->ncells;
   const CallerFrame fr(desc, op->n);
   std::vector<int32_t> store;
-  const int32_t* tdm = desc->h_dofmap;
+  const int32_t* tdm = nullptr;
   int rc;
-  if (fr.perm()) {
-    store.resize(ncells * op->nd);
-    if ((rc = wf_reorder_dofmap(desc->ncells, op->nd, fr.perm(), desc->h_dofmap, store.data())) != WF_OK) return rc;
-    tdm = store.data();
-  }
-  if (desc->h_cell_coeff)
-    for (size_t e = 0; e < h_Gc.size(); ++e) h_Gc[e] *= desc->h_cell_coeff[e / 6];
-  if ((rc = op->d_dofmap.upload(tdm, ncells * op->nd)) != WF_OK) return rc;
+  if ((rc = tensor_dofmap(desc, fr, op->nd, store, &tdm)) != WF_OK) return rc;
+  scale_cell_geometry(h_Gc, desc->h_cell_coeff);
+  if ((rc = op->d_dofmap.upload(tdm, (size_t)desc->ncells * op->nd)) != WF_OK) return rc;
   if ((rc = upload_derivative_tables(op, true)) != WF_OK) return rc;
   return op->d_Gcell.upload(h_Gc);
 }
@@ -217,10 +211,8 @@ int wf_cell_form_create(const wf_op_desc* desc, wf_cell_form** out)
   }
   WF_REQUIRE(desc->kind == WF_OP_STIFFNESS || desc->kind == WF_OP_MASS_LUMPED, "wf_cell_form_create: unknown operator kind");
   const int P = desc->degree;
-  if (P < 1 || P > kMaxDegree) {
-    set_error("wf_cell_form_create: degree must be 1..7 (hexahedron)");
-    return WF_ERR_UNSUPPORTED;
-  }
+  int rc;
+  if ((rc = check_hex_degree(P, "wf_cell_form_create")) != WF_OK) return rc;
   WF_REQUIRE(!(desc->flags & WF_FLAG_ORDERED),
              "wf_cell_form_create: WF_FLAG_ORDERED does not apply (the form is order-fixed by construction)");
   WF_REQUIRE(!(desc->flags & WF_FLAG_MASS_ELEMENTWISE),
@@ -231,27 +223,11 @@ int wf_cell_form_create(const wf_op_desc* desc, wf_cell_form** out)
   const wf_tuning none{};
   WF_REQUIRE(std::memcmp(&tun, &none, sizeof(wf_tuning)) == 0, "wf_cell_form_create: takes no wf_tuning field other than geometry");
   WF_REQUIRE(geometry >= WF_GEOMETRY_AUTO && geometry <= WF_GEOMETRY_PER_CELL, "wf_cell_form_create: wf_tuning.geometry out of range");
-  WF_REQUIRE(desc->ncells >= 0 && desc->ndofs >= 0, "wf_cell_form_create: negative size");
-  WF_REQUIRE(desc->h_dofmap || desc->ncells == 0, "wf_cell_form_create: dofmap missing");
+  if ((rc = check_hex_arrays(desc, "wf_cell_form_create")) != WF_OK) return rc;
   const int n = P + 1, nd = n * n * n;
   const size_t ncells = (size_t)desc->ncells;
   const bool have_mesh = desc->h_xverts && desc->h_geom_dofmap;
   const bool stiffness = desc->kind == WF_OP_STIFFNESS;
-  int rc;
-  if ((rc = check_index_range(desc->h_dofmap, ncells * nd, desc->ndofs, "wf_cell_form_create: dofmap entry out of range")) != WF_OK)
-    return rc;
-  if (desc->h_perm) {
-    std::vector<char> seen(nd, 0);
-    for (int k = 0; k < nd; ++k) {
-      WF_REQUIRE(desc->h_perm[k] >= 0 && desc->h_perm[k] < nd && !seen[desc->h_perm[k]],
-                 "wf_cell_form_create: perm is not a permutation");
-      seen[desc->h_perm[k]] = 1;
-    }
-  }
-  if (have_mesh
-      && (rc = check_index_range(desc->h_geom_dofmap, ncells * 8, desc->nverts, "wf_cell_form_create: vertex index out of range")) != WF_OK)
-    return rc;
-  if ((rc = check_cell_coeff(desc->h_cell_coeff, ncells, "wf_cell_form_create")) != WF_OK) return rc;
   if (stiffness)
     WF_REQUIRE(desc->h_G || have_mesh || ncells == 0, "wf_cell_form_create: stiffness needs h_G or the mesh (h_xverts, h_geom_dofmap)");
   else
@@ -260,23 +236,14 @@ int wf_cell_form_create(const wf_op_desc* desc, wf_cell_form** out)
   // geometry of the stiffness form, decided on the host: per cell where the mesh allows it or on request
   std::vector<double> h_Gc;
   bool per_cell = false;
-  if (stiffness && geometry == WF_GEOMETRY_PER_CELL && desc->h_G) {
-    set_error("wf_cell_form_create: WF_GEOMETRY_PER_CELL: per-cell geometry is derived from the mesh; h_G must be NULL");
-    return WF_ERR_UNSUPPORTED;
-  }
+  if (stiffness && geometry == WF_GEOMETRY_PER_CELL && desc->h_G) return per_cell_refuses_G("wf_cell_form_create");
   if (stiffness && geometry != WF_GEOMETRY_PER_POINT && !desc->h_G && have_mesh && ncells > 0) {
     h_Gc.assign(ncells * 6, 0.0);
     int reason = 0;
     const int64_t bad = hex_cell_geometry(P, ncells, desc->h_xverts, desc->h_geom_dofmap, fabs_flag(desc->flags),
                                           clamp_flag(desc->flags), h_Gc.data(), &reason);
     per_cell = bad < 0;
-    if (bad >= 0 && geometry == WF_GEOMETRY_PER_CELL) {
-      static const char* kWhy[4] = {"", "is not affine (its edge vectors along a reference axis differ)",
-                                    "is degenerate (det J zero or not finite)",
-                                    "has geometry on which the -1/0/1 clamp takes effect (WF_FLAG_NO_CLAMP turns it off)"};
-      set_error("wf_cell_form_create: WF_GEOMETRY_PER_CELL: cell " + std::to_string(bad) + " " + kWhy[reason]);
-      return WF_ERR_INVALID;
-    }
+    if (bad >= 0 && geometry == WF_GEOMETRY_PER_CELL) return per_cell_refusal("wf_cell_form_create", bad, reason);
   }
 
   std::unique_ptr<wf_cell_form> f(new wf_cell_form);
@@ -311,42 +278,10 @@ int wf_cell_form_create_box(int kind, int degree, int nx, int ny, int nz, const 
 {
   WF_REQUIRE(out != nullptr, "wf_cell_form_create_box: null output");
   *out = nullptr;
-  const int P = degree;
-  if (P < 1 || P > kMaxDegree) {
-    set_error("wf_cell_form_create_box: degree must be 1..7 (hexahedron)");
-    return WF_ERR_UNSUPPORTED;
-  }
-  WF_REQUIRE(nx > 0 && ny > 0 && nz > 0 && h_xverts, "wf_cell_form_create_box: bad mesh");
-  const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
-  WF_REQUIRE(NX * NY * NZ < ((size_t)1 << 31), "wf_cell_form_create_box: dof lattice exceeds int32");
-  // the box's lexicographic dofmap and vertex map on the host, as for WF_FLAG_ORDERED box operators
-  const int n = P + 1, nd = n * n * n;
-  const size_t ncells = (size_t)nx * ny * nz;
-  std::vector<int32_t> dm(ncells * nd), gd(ncells * 8);
-  for (int cz = 0; cz < nz; ++cz)
-    for (int cy = 0; cy < ny; ++cy)
-      for (int cx = 0; cx < nx; ++cx) {
-        const size_t c = (size_t)cx + (size_t)nx * (cy + (size_t)ny * cz);
-        const size_t base = (size_t)P * cx + NX * ((size_t)P * cy + NY * ((size_t)P * cz));
-        for (int k = 0; k < n; ++k)
-          for (int j = 0; j < n; ++j)
-            for (int i = 0; i < n; ++i) dm[c * nd + i + n * (j + n * k)] = (int32_t)(base + i + NX * (j + NY * k));
-        for (int v = 0; v < 8; ++v) gd[c * 8 + v] = (int32_t)box_vertex(nx, ny, c, v);
-      }
-  wf_op_desc d{};
-  d.kind = kind;
-  d.degree = P;
-  d.ncells = (int)ncells;
-  d.ndofs = (int)(NX * NY * NZ);
-  d.h_dofmap = dm.data();
-  d.nverts = (nx + 1) * (ny + 1) * (nz + 1);
-  d.h_xverts = h_xverts;
-  d.h_geom_dofmap = gd.data();
-  d.c0 = c0;
-  d.flags = flags;
-  d.tuning = tuning;
-  d.h_cell_coeff = h_cell_coeff;
-  return wf_cell_form_create(&d, out);
+  if (int rc = check_box_args("wf_cell_form_create_box", degree, nx, ny, nz, h_xverts)) return rc;
+  // the box written out as a dofmap mesh, as for WF_FLAG_ORDERED box operators
+  const BoxDesc box(kind, degree, nx, ny, nz, h_xverts, c0, h_cell_coeff, flags, tuning);
+  return wf_cell_form_create(&box.desc, out);
 }
 
 int wf_cell_form_eval(const wf_cell_form* f, const double* d_lambda, const double* d_u, double alpha, int accumulate,

@@ -1,10 +1,12 @@
 // The operator handle (wf_op) and the set-up steps its creation paths share.
 //   op_setup.hip       the shared steps          op_create.hip   wf_op_create and its three paths
 //   op_create_box.hip  the box creation path     op_apply.hip    launch, interior / interface splits, info, destroy
+//   box_mesh.h         the box as a dofmap mesh (box_space.cpp)
 #pragma once
 #include <functional>
 #include <memory>
 
+#include "box_mesh.h"
 #include "box_run_plan.h"
 #include "device_array.h"
 
@@ -108,12 +110,23 @@ inline int clamp_flag(int flags) { return (flags & WF_FLAG_NO_CLAMP) ? 0 : 1; }
 // the 1-D table a marching stiffness launch takes by value: A for the separable form, else D
 inline const DMat& march_table(const wf_op* op) { return op->geom == MarchGeom::cell_axes ? op->am : op->dm; }
 
-// vertex v = a + 2 b + 4 c of cell `cell` (x fastest) on the implicit vertex lattice of an nx x ny x nz box
-inline size_t box_vertex(int nx, int ny, size_t cell, int v)
+// ---- what every entry point on a hexahedral wf_op_desc checks (wf_op_create, wf_cell_form_create and the box entry
+// points in front of them); `who` names the entry point in the message ----
+// WF_ERR_UNSUPPORTED unless the degree is one the kernels are compiled for
+inline int check_hex_degree(int P, const char* who)
 {
-  const size_t cx = cell % nx, cy = (cell / nx) % ny, cz = cell / ((size_t)nx * ny);
-  return (cx + (v & 1)) + (size_t)(nx + 1) * ((cy + ((v >> 1) & 1)) + (size_t)(ny + 1) * (cz + ((v >> 2) & 1)));
+  if (P >= 1 && P <= kMaxDegree) return WF_OK;
+  set_error(std::string(who) + ": degree must be 1..7 (hexahedron)");   // mass.hpp:91-92 "Not implemented"
+  return WF_ERR_UNSUPPORTED;
 }
+// The arrays of a descriptor whose degree holds, every index a kernel will dereference included.  In this order: the
+// sizes, a missing dofmap, the dofmap's range, h_perm a permutation, the vertex range, the cell coefficients
+// (op_setup.hip).
+int check_hex_arrays(const wf_op_desc* desc, const char* who);
+// WF_GEOMETRY_PER_CELL asked of a mesh that does not allow it: hex_cell_geometry's first bad cell and its reason
+int per_cell_refusal(const char* who, int64_t bad, int reason);
+// ... and of a descriptor that hands over geometry of its own
+int per_cell_refuses_G(const char* who);
 
 // ---- per-cell geometry of affine hexahedra (hex_cell_geometry.cpp, host only) ----
 // geom_dofmap[ncells][8] names the vertices of every cell.  Returns the first cell that does not qualify (*reason says
@@ -142,6 +155,8 @@ int mesh_geometry_rule(int n1, const double* h_pts, const double* h_wts, const H
                        const double* h_cell_coeff, double* d_G9, double* d_G6blk, double* d_detJ);
 int host_detJ(const wf_op_desc* desc, std::vector<double>& hd, const double** hsrc, bool* raw_points);
 int upload_derivative_tables(wf_op* op, bool box);
+// per-cell geometry h_Gc [ncells][6] times the cell coefficient a_c (h_cell_coeff may be null: nothing to do)
+void scale_cell_geometry(std::vector<double>& h_Gc, const double* h_cell_coeff);
 int stage_G9(int P, int CB, size_t nslots, const double* direct, const std::function<void(size_t, double*)>& fill_slot,
              double* d_G6blk);
 
@@ -161,6 +176,9 @@ struct CallerFrame {
   // point permutation of per-point input arrays of an m^3 rule: engine point q <- caller point qmap[q]
   std::vector<int32_t> qmap(int m) const;
 };
+// tensor-ordered dofmap in the caller's cell order (permute.hpp:10-27 when the caller's element ordering differs):
+// *tdm is h_dofmap itself, or store
+int tensor_dofmap(const wf_op_desc* desc, const CallerFrame& fr, int nd, std::vector<int32_t>& store, const int32_t** tdm);
 
 // engine point index (lattice frame of the cell, x fastest) -> the caller's point index, per orientation
 struct PointMaps {

@@ -9,18 +9,6 @@ using namespace wf;
 
 namespace {
 
-// tensor-ordered dofmap in the caller's cell order (permute.hpp:10-27 when the caller's element ordering differs):
-// *tdm is h_dofmap itself, or store
-int tensor_dofmap(const wf_op_desc* desc, const CallerFrame& fr, int nd, std::vector<int32_t>& store, const int32_t** tdm)
-{
-  *tdm = desc->h_dofmap;
-  if (!fr.perm() || desc->ncells == 0) return WF_OK;
-  store.resize((size_t)desc->ncells * nd);
-  int rc = wf_reorder_dofmap(desc->ncells, nd, fr.perm(), desc->h_dofmap, store.data());
-  *tdm = store.data();
-  return rc;
-}
-
 // ---- path 1: dense mass with a COLLOCATED rule (the quadrature points are the nodes, phi1 = identity: the GLL rule of
 // demo/gpu_operator_monolithic/main.cpp:94-96 and of LinearGLL): Phi^T D Phi is the diagonal sum_cells det J w.
 // It is assembled once and applied as y += m .* x (24 B/dof) -- the result of the dense evaluation up to the
@@ -272,10 +260,7 @@ int choose_idx_cell_geometry(const wf_op_desc* desc, bool have_mesh, wf_op* op, 
               + std::to_string(P) + " runs the k-split kernel, per-point geometry only)");
     return WF_ERR_UNSUPPORTED;
   }
-  if (desc->h_G) {
-    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: per-cell geometry is derived from the mesh; h_G must be NULL");
-    return WF_ERR_UNSUPPORTED;
-  }
+  if (desc->h_G) return per_cell_refuses_G("wf_op_create");
   WF_REQUIRE(have_mesh, "wf_op_create: WF_GEOMETRY_PER_CELL needs the mesh (h_xverts, h_geom_dofmap)");
   WF_REQUIRE(tun.kernel == WF_KERNEL_AUTO || tun.kernel == WF_KERNEL_FORCE_MARCH,
              "wf_op_create: WF_GEOMETRY_PER_CELL: wf_tuning.kernel must be AUTO or FORCE_MARCH (only the marching kernel on "
@@ -290,13 +275,7 @@ int choose_idx_cell_geometry(const wf_op_desc* desc, bool have_mesh, wf_op* op, 
   int reason = 0;
   const int64_t bad = hex_cell_geometry(P, (size_t)desc->ncells, desc->h_xverts, desc->h_geom_dofmap, fabs_flag(desc->flags),
                                         clamp_flag(desc->flags), h_Gc.data(), &reason);
-  if (bad >= 0) {
-    static const char* kWhy[4] = {"", "is not affine (its edge vectors along a reference axis differ)",
-                                  "is degenerate (det J zero or not finite)",
-                                  "has geometry on which the -1/0/1 clamp takes effect (WF_FLAG_NO_CLAMP turns it off)"};
-    set_error("wf_op_create: WF_GEOMETRY_PER_CELL: cell " + std::to_string(bad) + " " + kWhy[reason]);
-    return WF_ERR_INVALID;
-  }
+  if (bad >= 0) return per_cell_refusal("wf_op_create", bad, reason);
   // metric: the separable (axes) form when every G_c is diagonal -- off-diagonals exactly 0, either sign.  Taking a cell
   // into the plan's frame permutes and negates components, so the cells' own frames decide.
   const int64_t offdiag = first_offdiagonal_cell(h_Gc);
@@ -543,34 +522,14 @@ int wf_op_create(const wf_op_desc* desc, wf_op** out)
   WF_REQUIRE(desc && out, "wf_op_create: null argument");
   *out = nullptr;
   const int P = desc->degree;
-  if (P < 1 || P > kMaxDegree) {
-    set_error("wf_op_create: degree must be 1..7 (hexahedron)");   // mass.hpp:91-92 "Not implemented"
-    return WF_ERR_UNSUPPORTED;
-  }
+  int rc;
+  if ((rc = check_hex_degree(P, "wf_op_create")) != WF_OK) return rc;
   WF_REQUIRE(desc->kind == WF_OP_STIFFNESS || desc->kind == WF_OP_MASS_LUMPED || desc->kind == WF_OP_MASS_DENSE,
              "wf_op_create: unknown operator kind");
-  WF_REQUIRE(desc->ncells >= 0 && desc->ndofs >= 0, "wf_op_create: negative size");
-  WF_REQUIRE(desc->h_dofmap || desc->ncells == 0, "wf_op_create: dofmap missing");
+  if ((rc = check_hex_arrays(desc, "wf_op_create")) != WF_OK) return rc;
   const int n = P + 1, nd = n * n * n;
   const size_t ncells = (size_t)desc->ncells;
   const bool have_mesh = desc->h_xverts && desc->h_geom_dofmap;
-
-  // host-side validation of every index the kernels will dereference
-  int rc;
-  if ((rc = check_index_range(desc->h_dofmap, ncells * nd, desc->ndofs, "wf_op_create: dofmap entry out of range")) != WF_OK) return rc;
-  if (desc->h_perm) {
-    std::vector<char> seen(nd, 0);
-    for (int k = 0; k < nd; ++k) {
-      WF_REQUIRE(desc->h_perm[k] >= 0 && desc->h_perm[k] < nd && !seen[desc->h_perm[k]],
-                 "wf_op_create: perm is not a permutation");
-      seen[desc->h_perm[k]] = 1;
-    }
-  }
-  if (have_mesh
-      && (rc = check_index_range(desc->h_geom_dofmap, ncells * 8, desc->nverts, "wf_op_create: vertex index out of range")) != WF_OK)
-    return rc;
-
-  if ((rc = check_cell_coeff(desc->h_cell_coeff, ncells, "wf_op_create")) != WF_OK) return rc;
 
   const CallerFrame fr(desc, n);
   OpPtr op = new_op(desc->kind, P, nd, nd, desc->ncells, desc->ndofs, desc->c0, desc->tuning);

@@ -149,40 +149,13 @@ int upload_box_cell_geometry(wf_op* op, const std::vector<double>& h_Gc)
   return op->d_Gcell.upload(blk);
 }
 
-// WF_FLAG_ORDERED on a box: the box's lexicographic dofmap (dof (I, J, K) -> I + NX (J + NY K), tensor order) and vertex
-// map (vertex (a, b, c) -> a + (nx+1)(b + (ny+1) c)) built on the host, then the dofmap operator of wf_op_create -- a box
-// operator with the flag IS that dofmap operator, bit for bit.
+// WF_FLAG_ORDERED on a box: the box written out as a dofmap mesh (BoxDesc, box_mesh.h), then the dofmap operator of
+// wf_op_create -- a box operator with the flag IS that dofmap operator, bit for bit.
 int create_box_ordered(int kind, int P, int nx, int ny, int nz, const double* h_xverts, double c0, const double* h_cell_coeff,
                        int flags, const wf_tuning* tuning, wf_op** out)
 {
-  const int n = P + 1, nd = n * n * n;
-  const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
-  const size_t ncells = (size_t)nx * ny * nz;
-  std::vector<int32_t> dm(ncells * nd), gd(ncells * 8);
-  for (int cz = 0; cz < nz; ++cz)
-    for (int cy = 0; cy < ny; ++cy)
-      for (int cx = 0; cx < nx; ++cx) {
-        const size_t c = (size_t)cx + (size_t)nx * (cy + (size_t)ny * cz);
-        const size_t base = (size_t)P * cx + NX * ((size_t)P * cy + NY * ((size_t)P * cz));
-        for (int k = 0; k < n; ++k)
-          for (int j = 0; j < n; ++j)
-            for (int i = 0; i < n; ++i) dm[c * nd + i + n * (j + n * k)] = (int32_t)(base + i + NX * (j + NY * k));
-        for (int v = 0; v < 8; ++v) gd[c * 8 + v] = (int32_t)box_vertex(nx, ny, c, v);
-      }
-  wf_op_desc d{};
-  d.kind = kind;
-  d.degree = P;
-  d.ncells = (int)ncells;
-  d.ndofs = (int)(NX * NY * NZ);
-  d.h_dofmap = dm.data();
-  d.nverts = (nx + 1) * (ny + 1) * (nz + 1);
-  d.h_xverts = h_xverts;
-  d.h_geom_dofmap = gd.data();
-  d.c0 = c0;
-  d.flags = flags;
-  d.tuning = tuning;
-  d.h_cell_coeff = h_cell_coeff;   // the dofmap's rows are the box's cells in lexicographic order
-  int rc = wf_op_create(&d, out);
+  const BoxDesc box(kind, P, nx, ny, nz, h_xverts, c0, h_cell_coeff, flags, tuning);
+  int rc = wf_op_create(&box.desc, out);
   if (rc != WF_OK) return rc;
   (*out)->structured = 1;
   (*out)->nx = nx;
@@ -380,16 +353,14 @@ int wf_op_create_box_coeff(int kind, int degree, int nx, int ny, int nz, const d
   WF_REQUIRE(out != nullptr, "wf_op_create_box: null output");
   *out = nullptr;
   const int P = degree;
-  if (P < 1 || P > kMaxDegree) {
-    set_error("wf_op_create_box: degree must be 1..7 (hexahedron)");
-    return WF_ERR_UNSUPPORTED;
-  }
+  int rc;
+  // the degree is reported ahead of the kind and the tuning, the mesh behind them
+  if ((rc = check_hex_degree(P, "wf_op_create_box")) != WF_OK) return rc;
   WF_REQUIRE(kind == WF_OP_STIFFNESS || kind == WF_OP_MASS_LUMPED, "wf_op_create_box: kind must be stiffness or lumped mass");
   WF_REQUIRE(!tuning || tuning->kernel != WF_KERNEL_FORCE_MASS_MARCH,
              "wf_op_create_box: WF_KERNEL_FORCE_MASS_MARCH applies to the dense mass only");
-  WF_REQUIRE(nx > 0 && ny > 0 && nz > 0 && h_xverts, "wf_op_create_box: bad mesh");
+  if ((rc = check_box_args("wf_op_create_box", P, nx, ny, nz, h_xverts)) != WF_OK) return rc;
   const size_t NX = (size_t)P * nx + 1, NY = (size_t)P * ny + 1, NZ = (size_t)P * nz + 1;
-  WF_REQUIRE(NX * NY * NZ < ((size_t)1 << 31), "wf_op_create_box: dof lattice exceeds int32");
   const int n = P + 1, nd = n * n * n;
   const size_t ncells = (size_t)nx * ny * nz;
   if (int bad = check_cell_coeff(h_cell_coeff, ncells, "wf_op_create_box")) return bad;
@@ -406,15 +377,13 @@ int wf_op_create_box_coeff(int kind, int degree, int nx, int ny, int nz, const d
   op->kernel = OpKernel::diagonal;   // lumped mass: the pre-assembled diagonal
   std::vector<double> h_Gc;          // per-cell geometry, [ncells][6]
   default_box_block(P, op->tun, &op->box.bx, &op->box.by, &op->box.bz);
-  int rc;
   if (kind == WF_OP_STIFFNESS
       && (rc = choose_box_stiffness(P, nx, ny, nz, h_xverts, flags, op->tun, &op->kernel, &op->box, &op->geom, h_Gc)) != WF_OK)
     return rc;
   // The cell coefficient enters behind every choice: the affine-cell test, the axes test and the z segmentation have
   // seen the geometry without it.  Per-cell geometry takes it here, in the caller's cell order; the device-built arrays
   // take it in the geometry kernel.
-  if (h_cell_coeff && kind == WF_OP_STIFFNESS && op->geom != MarchGeom::point)
-    for (size_t e = 0; e < h_Gc.size(); ++e) h_Gc[e] *= h_cell_coeff[e / 6];
+  if (kind == WF_OP_STIFFNESS && op->geom != MarchGeom::point) scale_cell_geometry(h_Gc, h_cell_coeff);
 
   if ((rc = upload_derivative_tables(op.get(), true)) != WF_OK) return rc;
   DevArray<double> d_x, d_pts, d_wts, d_coeff;

@@ -1,5 +1,6 @@
-// Set-up steps shared by the operator creation paths (op.h): tables, geometry staging, batch-unique lists, the
-// caller's tensor frame; the batch plan of the dense simplex operators.
+// Set-up steps shared by the operator creation paths and the cell forms (op.h): the checks of a hexahedral descriptor
+// and the per-cell refusals, tables, geometry staging, batch-unique lists, the caller's tensor frame; the batch plan
+// of the dense simplex operators.
 #include <cmath>
 #include <cstring>
 
@@ -21,6 +22,59 @@ OpPtr new_op(int kind, int P, int nd, int nq, int ncells, int ndofs, double c0, 
   op->coeff = -1.0 * c0 * c0;   // operators.hpp:115
   op->tun = tuning ? *tuning : wf_tuning{};
   return op;
+}
+
+int check_hex_arrays(const wf_op_desc* desc, const char* who)
+{
+  const std::string w = std::string(who) + ": ";
+  WF_REQUIRE(desc->ncells >= 0 && desc->ndofs >= 0, w + "negative size");
+  WF_REQUIRE(desc->h_dofmap || desc->ncells == 0, w + "dofmap missing");
+  const int n = desc->degree + 1, nd = n * n * n;
+  const size_t ncells = (size_t)desc->ncells;
+  int rc;
+  if ((rc = check_index_range(desc->h_dofmap, ncells * nd, desc->ndofs, w + "dofmap entry out of range")) != WF_OK) return rc;
+  if (desc->h_perm) {
+    std::vector<char> seen(nd, 0);
+    for (int k = 0; k < nd; ++k) {
+      WF_REQUIRE(desc->h_perm[k] >= 0 && desc->h_perm[k] < nd && !seen[desc->h_perm[k]], w + "perm is not a permutation");
+      seen[desc->h_perm[k]] = 1;
+    }
+  }
+  if (desc->h_xverts && desc->h_geom_dofmap
+      && (rc = check_index_range(desc->h_geom_dofmap, ncells * 8, desc->nverts, w + "vertex index out of range")) != WF_OK)
+    return rc;
+  return check_cell_coeff(desc->h_cell_coeff, ncells, who);
+}
+
+int per_cell_refusal(const char* who, int64_t bad, int reason)
+{
+  static const char* kWhy[4] = {"", "is not affine (its edge vectors along a reference axis differ)",
+                                "is degenerate (det J zero or not finite)",
+                                "has geometry on which the -1/0/1 clamp takes effect (WF_FLAG_NO_CLAMP turns it off)"};
+  set_error(std::string(who) + ": WF_GEOMETRY_PER_CELL: cell " + std::to_string(bad) + " " + kWhy[reason]);
+  return WF_ERR_INVALID;
+}
+
+int per_cell_refuses_G(const char* who)
+{
+  set_error(std::string(who) + ": WF_GEOMETRY_PER_CELL: per-cell geometry is derived from the mesh; h_G must be NULL");
+  return WF_ERR_UNSUPPORTED;
+}
+
+int tensor_dofmap(const wf_op_desc* desc, const CallerFrame& fr, int nd, std::vector<int32_t>& store, const int32_t** tdm)
+{
+  *tdm = desc->h_dofmap;
+  if (!fr.perm() || desc->ncells == 0) return WF_OK;
+  store.resize((size_t)desc->ncells * nd);
+  int rc = wf_reorder_dofmap(desc->ncells, nd, fr.perm(), desc->h_dofmap, store.data());
+  *tdm = store.data();
+  return rc;
+}
+
+void scale_cell_geometry(std::vector<double>& h_Gc, const double* h_cell_coeff)
+{
+  if (h_cell_coeff)
+    for (size_t e = 0; e < h_Gc.size(); ++e) h_Gc[e] *= h_cell_coeff[e / 6];
 }
 
 int upload_tables(int P, DevArray<double>& d_pts, DevArray<double>& d_wts)

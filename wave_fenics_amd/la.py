@@ -2,7 +2,7 @@
 (common/cuda/la.hpp:31-138, common/LinearGLL.hpp:15-35)."""
 from __future__ import annotations
 
-from ._lib import check, lib
+from ._lib import Handle, check, lib
 from .operators import _ptr, _stream
 
 
@@ -90,10 +90,11 @@ def leapfrog_step(b, m, u, u_prev, u_next, dt: float, v=None, bc=None, s1: float
     check(lib().wf_leapfrog_step(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_next), vp, _stream(b)))
 
 
-class BoundaryPlan:
+class BoundaryPlan(Handle):
     """wf_boundary_create: the two boundary dof sets of the form L (LinearGLL.hpp:113-115, forms.ufl:19-24) as a
     bitmap + coefficient arrays, so that the fused RK4 stage can leave the next right-hand side's boundary
     term in b instead of zeroing it (rk4_stage(..., bc=plan, s1_next=, s2=))."""
+    _destroy = "wf_boundary_destroy"
 
     def __init__(self, n: int, idx1, m1, idx2, m2):
         import ctypes
@@ -113,17 +114,6 @@ class BoundaryPlan:
     def apply(self, s1: float, s2: float, v, b):
         """b[idx1] += s1 m1; b[idx2] += s2 m2 v[idx2] (the plain launch)."""
         check(lib().wf_boundary_apply_plan(self._h, float(s1), float(s2), _ptr(v), _ptr(b), _stream(b)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().wf_boundary_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def cg(x, b, A, kmax: int = 50, rtol: float = 1e-8, updater=None, comm=None):

@@ -194,30 +194,73 @@ KERNEL_NAMES = {0: "none", 1: "march_box", 2: "march_idx", 3: "batch_unique", 4:
                 10: "dense_simplex_mass"}
 
 
-class _Operator:
-    _kind = None
+GEOMETRY_NAMES = {1: "per_point", 2: "per_cell"}    # wf_op_info_t.geometry, wf_cell_form_info_t.geometry
+
+
+def _structured_default(V, *arrays) -> bool:
+    """structured=None: the box entry point when V says its dofmap is the lexicographic box numbering and the caller
+    hands over no array (G, detJ, perm) that only the dofmap entry point takes."""
+    return bool(getattr(V, "structured", False)) and all(a is None for a in arrays)
+
+
+def _hex_desc(V: FunctionSpace, kind: int, degree: int, perm=None, c0: float = 0.0, flags: int = 0, G=None, detJ=None,
+              cell_coeff=None, tuning=None):
+    """The wf_op_desc of the dofmap entry points (wf_op_create, wf_cell_form_create) and the arrays it points into,
+    which the caller holds until the call has returned: (desc, keep).  The geometry is G [ncells][nq][3][3] or detJ
+    where given, else V's mesh."""
+    d = OpDesc()
+    d.kind, d.degree, d.ncells, d.ndofs = kind, degree, V.mesh.ncells, V.ndofs
+    d.c0, d.flags = c0, flags
+    dm = np.ascontiguousarray(V.dofmap, dtype=np.int32)
+    if dm.shape != (V.mesh.ncells, (degree + 1) ** 3):
+        raise _lib.WavehipError("dofmap shape does not match ncells x (degree+1)^3")
+    pm = None if perm is None else np.ascontiguousarray(perm, dtype=np.int32)
+    d.h_dofmap, d.h_perm = _ip(dm), _ip(pm)
+    keep = [dm, pm]
+    if G is not None:
+        Gc = np.ascontiguousarray(G, dtype=np.float64)
+        if Gc.size != V.mesh.ncells * (degree + 1) ** 3 * 9:
+            raise _lib.WavehipError("G must be [ncells][nq][3][3]")
+        keep.append(Gc)
+        d.h_G = _dp(Gc)
+    elif detJ is not None:
+        keep.append(np.ascontiguousarray(detJ, dtype=np.float64))
+        d.h_detJ = _dp(keep[-1])
+    else:
+        x = np.ascontiguousarray(V.mesh.x, dtype=np.float64)
+        gd = np.ascontiguousarray(V.mesh.geom_dofmap, dtype=np.int32)
+        keep += [x, gd]
+        d.nverts, d.h_xverts, d.h_geom_dofmap = x.shape[0], _dp(x), _ip(gd)
+    a, t = _cell_coeff(cell_coeff, d.ncells), make_tuning(tuning)
+    keep += [a, t]
+    d.h_cell_coeff = _dp(a)
+    if t is not None:
+        d.tuning = ctypes.pointer(t)
+    return d, keep
+
+
+def _create_on_box(create, handle, kind: int, p: int, mesh, c0: float, flags: int, tuning, cell_coeff):
+    """wf_op_create_box_coeff or wf_cell_form_create_box (one argument list) on the box `mesh`"""
+    nx, ny, nz = mesh.n
+    x = np.ascontiguousarray(mesh.x, dtype=np.float64)
+    a = _cell_coeff(cell_coeff, nx * ny * nz)
+    t = make_tuning(tuning)
+    check(create(kind, p, nx, ny, nz, _dp(x), float(c0), _dp(a), flags, ctypes.byref(t) if t is not None else None,
+                 ctypes.byref(handle)))
+
+
+class _Operator(_lib.Handle):
+    _destroy = "wf_op_destroy"
 
     def __init__(self):
         self._h = c_void_p()
 
-    def _create(self, desc: OpDesc, keep=(), tuning=None, cell_coeff=None):
-        a = _cell_coeff(cell_coeff, desc.ncells)
-        self._keep = (keep, a)
-        desc.h_cell_coeff = _dp(a)
-        t = make_tuning(tuning)
-        if t is not None:
-            desc.tuning = ctypes.pointer(t)
-        check(lib().wf_op_create(ctypes.byref(desc), ctypes.byref(self._h)))
-        self._keep = ()
+    def _create(self, desc: OpDesc, keep):
+        check(lib().wf_op_create(ctypes.byref(desc), ctypes.byref(self._h)))   # keep: the arrays desc points into
         self._info()
 
     def _create_box(self, kind: int, p: int, mesh, c0: float, flags: int, tuning=None, cell_coeff=None):
-        nx, ny, nz = mesh.n
-        x = np.ascontiguousarray(mesh.x, dtype=np.float64)
-        a = _cell_coeff(cell_coeff, nx * ny * nz)
-        t = make_tuning(tuning)
-        check(lib().wf_op_create_box_coeff(kind, p, nx, ny, nz, _dp(x), float(c0), _dp(a), flags,
-                                           ctypes.byref(t) if t is not None else None, ctypes.byref(self._h)))
+        _create_on_box(lib().wf_op_create_box_coeff, self._h, kind, p, mesh, c0, flags, tuning, cell_coeff)
         self._info()
 
     @property
@@ -233,7 +276,7 @@ class _Operator:
     @property
     def geometry(self) -> str:
         """How the stiffness geometry is stored (wf_op_info_t.geometry): "per_point", "per_cell" or "none"."""
-        return {1: "per_point", 2: "per_cell"}.get(self.info.geometry, "none")
+        return GEOMETRY_NAMES.get(self.info.geometry, "none")
 
     @property
     def metric(self) -> str:
@@ -329,45 +372,6 @@ class _Operator:
         s = _stream(x) if stream is None else stream
         check(lib().wf_op_apply_part(self._h, _ptr(x), _ptr(y), part, s))
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().wf_op_destroy(self._h)
-            self._h = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _base_desc(V: FunctionSpace, kind: int, degree: int, perm=None):
-    d = OpDesc()
-    d.kind = kind
-    d.degree = degree
-    d.ncells = V.mesh.ncells
-    d.ndofs = V.ndofs
-    keep = []
-    dm = np.ascontiguousarray(V.dofmap, dtype=np.int32)
-    if dm.shape != (V.mesh.ncells, (degree + 1) ** 3):
-        raise _lib.WavehipError("dofmap shape does not match ncells x (degree+1)^3")
-    keep.append(dm)
-    d.h_dofmap = _ip(dm)
-    if perm is not None:
-        pm = np.ascontiguousarray(perm, dtype=np.int32)
-        keep.append(pm)
-        d.h_perm = _ip(pm)
-    return d, keep
-
-
-def _attach_mesh(d: OpDesc, V: FunctionSpace, keep: list):
-    x = np.ascontiguousarray(V.mesh.x, dtype=np.float64)
-    gd = np.ascontiguousarray(V.mesh.geom_dofmap, dtype=np.int32)
-    keep += [x, gd]
-    d.nverts = x.shape[0]
-    d.h_xverts = _dp(x)
-    d.h_geom_dofmap = _ip(gd)
-
 
 class StiffnessOperator(_Operator):
     """StiffnessOperator(V, bdegree, params) -- common/operators.hpp:137-201.
@@ -393,25 +397,12 @@ class StiffnessOperator(_Operator):
         super().__init__()
         c0 = 1500.0 if not params else float(params.get("c0", 1500.0))
         self.c0 = c0
-        if structured is None:
-            structured = bool(getattr(V, "structured", False)) and G is None and perm is None
-        if structured:
+        if _structured_default(V, G, perm) if structured is None else structured:
             if bdegree != V.degree:
                 raise _lib.WavehipError("structured operator: bdegree must equal the space's degree")
             self._create_box(_lib.WF_OP_STIFFNESS, bdegree, V.mesh, c0, flags, tuning, cell_coeff)
             return
-        d, keep = _base_desc(V, _lib.WF_OP_STIFFNESS, bdegree, perm)
-        d.c0 = c0
-        d.flags = flags
-        if G is not None:
-            Gc = np.ascontiguousarray(G, dtype=np.float64)
-            if Gc.size != V.mesh.ncells * (bdegree + 1) ** 3 * 9:
-                raise _lib.WavehipError("G must be [ncells][nq][3][3]")
-            keep.append(Gc)
-            d.h_G = _dp(Gc)
-        else:
-            _attach_mesh(d, V, keep)
-        self._create(d, keep, tuning, cell_coeff)
+        self._create(*_hex_desc(V, _lib.WF_OP_STIFFNESS, bdegree, perm, c0, flags, G=G, cell_coeff=cell_coeff, tuning=tuning))
 
 
 class MassOperatorLumped(_Operator):
@@ -421,24 +412,15 @@ class MassOperatorLumped(_Operator):
     def __init__(self, V: FunctionSpace, bdegree: int, detJ=None, perm=None, structured: bool | None = None,
                  flags: int = 0, tuning=None, cell_coeff=None):
         super().__init__()
-        if structured is None:
-            structured = bool(getattr(V, "structured", False)) and detJ is None and perm is None
-        if structured:
+        if _structured_default(V, detJ, perm) if structured is None else structured:
             self._create_box(_lib.WF_OP_MASS_LUMPED, bdegree, V.mesh, 0.0, flags, tuning if flags & _lib.WF_FLAG_ORDERED else None,
                              cell_coeff)
             return
-        d, keep = _base_desc(V, _lib.WF_OP_MASS_LUMPED, bdegree, perm)
-        d.flags = flags
-        if detJ is not None:
-            Dc = np.ascontiguousarray(detJ, dtype=np.float64)
-            keep.append(Dc)
-            d.h_detJ = _dp(Dc)
-        else:
-            _attach_mesh(d, V, keep)
-        self._create(d, keep, tuning, cell_coeff)
+        self._create(*_hex_desc(V, _lib.WF_OP_MASS_LUMPED, bdegree, perm, 0.0, flags, detJ=detJ, cell_coeff=cell_coeff,
+                                tuning=tuning))
 
 
-class CellForm:
+class CellForm(_lib.Handle):
     """Cell form of an operator: e_c(lambda, u) = (P_c lambda)^T A_c (P_c u), one number per cell (wf_cell_form,
     include/wavehip.h).  A_c is the cell matrix the operator of the same arguments stores: for kind="stiffness" with
     -c0^2, the clamp and cell_coeff, for kind="mass_lumped" cell_coeff det J w.  Without cell_coeff e_c is the
@@ -450,6 +432,7 @@ class CellForm:
     is in the mesh's cell order, bitwise reproducible, and independent of where a cell sits in that order."""
 
     KINDS = {"stiffness": _lib.WF_OP_STIFFNESS, "mass_lumped": _lib.WF_OP_MASS_LUMPED, "mass_dense": _lib.WF_OP_MASS_DENSE}
+    _destroy = "wf_cell_form_destroy"
 
     def __init__(self, V: FunctionSpace, degree: int, kind: str = "stiffness", params: dict | None = None, G=None,
                  detJ=None, perm=None, structured: bool | None = None, cell_coeff=None, tuning=None, flags: int = 0):
@@ -459,36 +442,14 @@ class CellForm:
         k = self.KINDS[kind]
         self.kind = kind
         self.c0 = 1500.0 if not params else float(params.get("c0", 1500.0))
-        t = make_tuning(tuning)
-        a = _cell_coeff(cell_coeff, V.mesh.ncells)
-        if structured is None:
-            structured = bool(getattr(V, "structured", False)) and G is None and detJ is None and perm is None
-        if structured:
+        if _structured_default(V, G, detJ, perm) if structured is None else structured:
             if degree != V.degree:
                 raise _lib.WavehipError("structured cell form: degree must equal the space's degree")
-            nx, ny, nz = V.mesh.n
-            x = np.ascontiguousarray(V.mesh.x, dtype=np.float64)
-            check(lib().wf_cell_form_create_box(k, degree, nx, ny, nz, _dp(x), self.c0, _dp(a), flags,
-                                                ctypes.byref(t) if t is not None else None, ctypes.byref(self._h)))
+            _create_on_box(lib().wf_cell_form_create_box, self._h, k, degree, V.mesh, self.c0, flags, tuning, cell_coeff)
         else:
-            d, keep = _base_desc(V, k, degree, perm)
-            d.c0 = self.c0
-            d.flags = flags
-            if k == _lib.WF_OP_STIFFNESS and G is not None:
-                Gc = np.ascontiguousarray(G, dtype=np.float64)
-                if Gc.size != V.mesh.ncells * (degree + 1) ** 3 * 9:
-                    raise _lib.WavehipError("G must be [ncells][nq][3][3]")
-                keep.append(Gc)
-                d.h_G = _dp(Gc)
-            elif k != _lib.WF_OP_STIFFNESS and detJ is not None:
-                Dc = np.ascontiguousarray(detJ, dtype=np.float64)
-                keep.append(Dc)
-                d.h_detJ = _dp(Dc)
-            else:
-                _attach_mesh(d, V, keep)
-            d.h_cell_coeff = _dp(a)
-            if t is not None:
-                d.tuning = ctypes.pointer(t)
+            stiffness = k == _lib.WF_OP_STIFFNESS
+            d, keep = _hex_desc(V, k, degree, perm, self.c0, flags, G=G if stiffness else None,
+                                detJ=None if stiffness else detJ, cell_coeff=cell_coeff, tuning=tuning)
             check(lib().wf_cell_form_create(ctypes.byref(d), ctypes.byref(self._h)))
         info = _lib.CellFormInfo()
         check(lib().wf_cell_form_info(self._h, ctypes.byref(info)))
@@ -497,7 +458,7 @@ class CellForm:
     @property
     def geometry(self) -> str:
         """How the stiffness form stores its geometry: "per_point", "per_cell", or "none" (lumped mass)."""
-        return {1: "per_point", 2: "per_cell"}.get(self.info.geometry, "none")
+        return GEOMETRY_NAMES.get(self.info.geometry, "none")
 
     def eval(self, lam, u, out=None, alpha: float = 1.0, accumulate: bool = False, stream: int | None = None):
         """out[c] = (out[c] if accumulate else 0) + alpha e_c(lam, u); returns out (a new device vector when None).
@@ -515,17 +476,6 @@ class CellForm:
         return out
 
     __call__ = eval
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().wf_cell_form_destroy(self._h)
-            self._h = c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class SpectralMassOperator(MassOperatorLumped):
@@ -555,8 +505,6 @@ class MassOperator(_Operator):
                  perm=None, variant: str = "gll_warped", quad: str = "gll", qdegree: int | None = None, tuning=None,
                  flags: int = 0, cell_coeff=None):
         super().__init__()
-        d, keep = _base_desc(V, _lib.WF_OP_MASS_DENSE, degree, perm)
-        d.flags = flags
         if phi1 is None:
             if qdegree is None:
                 qdegree = degree + 1 if degree > 1 else degree      # gpu_operator_monolithic/main.cpp:95
@@ -566,24 +514,20 @@ class MassOperator(_Operator):
         p1 = np.ascontiguousarray(phi1, dtype=np.float64)
         if p1.ndim != 2 or p1.shape[1] != degree + 1:
             raise _lib.WavehipError("phi1 must be [nq1][degree+1]")
+        if detJ is not None and np.size(detJ) != V.mesh.ncells * p1.shape[0] ** 3:
+            raise _lib.WavehipError("detJ must be [ncells][nq1^3]")
+        if detJ is None and not hasattr(self, "points1"):
+            raise _lib.WavehipError("MassOperator: explicit phi1 needs detJ")
+        d, keep = _hex_desc(V, _lib.WF_OP_MASS_DENSE, degree, perm, 0.0, flags, detJ=detJ, cell_coeff=cell_coeff, tuning=tuning)
         keep.append(p1)
         d.nq1 = p1.shape[0]
         d.h_phi1 = _dp(p1)
-        if detJ is not None:
-            Dc = np.ascontiguousarray(detJ, dtype=np.float64)
-            if Dc.size != V.mesh.ncells * p1.shape[0] ** 3:
-                raise _lib.WavehipError("detJ must be [ncells][nq1^3]")
-            keep.append(Dc)
-            d.h_detJ = _dp(Dc)
-        else:
-            if not hasattr(self, "points1"):
-                raise _lib.WavehipError("MassOperator: explicit phi1 needs detJ")
-            _attach_mesh(d, V, keep)
+        if detJ is None:
             d.flags |= _lib.WF_FLAG_NO_FABS   # mass.hpp:35-39: det J * w keeps its sign (compute_jacobian_determinant)
             qp, qw = np.ascontiguousarray(self.points1), np.ascontiguousarray(self.weights1)
             keep += [qp, qw]
             d.h_qpts1, d.h_qwts1 = _dp(qp), _dp(qw)
-        self._create(d, keep, tuning, cell_coeff)
+        self._create(d, keep)
 
 
 # ---------------------------------------------------------------------------

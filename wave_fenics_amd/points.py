@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import _dp, _ip, check, lib
+from ._lib import Handle, _dp, _ip, check, lib
 from .operators import _check_vec, _ptr, _stream
 
 #: tolerance of locate(): a cell accepts a point whose reference coordinates lie in [-TOL/2, 1 + TOL/2]
@@ -99,10 +99,11 @@ def wavelet_value(wavelet: dict, t: float) -> float:
     return wavelet["amplitude"] * ((1.0 - th) * float(v[k]) + th * float(v[k + 1]))
 
 
-class _Points:
+class _Points(Handle):
     """wf_points: located points with their dofmap rows and weights on the device.  located = (cell [n], ref [n][3]), a
     public keyword of Receivers and Sources: the points are given by their cell and reference coordinates in [0, 1]^3 and
     xyz is not looked at -- for a caller who has located them already, or wants a point exactly on a node."""
+    _destroy = "wf_points_destroy"
 
     def __init__(self, V, xyz, what: str, located=None):
         self.V = V
@@ -127,17 +128,6 @@ class _Points:
 
     def __len__(self):
         return int(self.cell.size)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().wf_points_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Receivers(_Points):
