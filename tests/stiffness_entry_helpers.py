@@ -304,10 +304,12 @@ def box_mesh(kind: str, n, p: int):
 
 
 @functools.lru_cache(maxsize=None)
-def batch_mesh(p: int):
-    """the first 2 B + 1 cells of the perturbed box BATCH_BOX[p] with the box's dof numbers, B = 256 // (P+1)^2"""
+def batch_mesh(p: int, ncells: int | None = None):
+    """the first 2 B + 1 cells of the perturbed box BATCH_BOX[p] with the box's dof numbers, B = 256 // (P+1)^2 (or the
+    first ncells: the mass kernels with another batch size)"""
     import wave_fenics_amd as w
-    ncells = 2 * cells_per_batch(p) + 1
+    if ncells is None:
+        ncells = 2 * cells_per_batch(p) + 1
     box = w.create_box(BATCH_BOX[p], perturb=0.2)
     Vb = w.create_functionspace(box, p)
     assert ncells <= box.ncells
