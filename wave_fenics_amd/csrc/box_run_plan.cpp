@@ -145,4 +145,41 @@ BoxRunPlan box_run_plan(int ncols, int nz, int resident, int nxcd, double prolog
   return plan;
 }
 
+std::vector<int32_t> aligned_runs(int ncols, int nz, int nseg)
+{
+  const size_t n = (size_t)ncols * nseg, q = n / kXcds, r = n % kXcds;
+  std::vector<int32_t> table(3 * n);
+  size_t xcd = 0, i = 0;   // run i of XCD xcd is entry kXcds * i + xcd
+  for (int s = 0; s < nseg; ++s)
+    for (int col = 0; col < ncols; ++col) {
+      int32_t* e = &table[3 * (kXcds * i + xcd)];
+      e[0] = col, e[1] = (int32_t)((long)nz * s / nseg), e[2] = (int32_t)((long)nz * (s + 1) / nseg);
+      if (++i == q + (xcd < r ? 1 : 0)) i = 0, ++xcd;
+    }
+  return table;
+}
+
+int longest_run(const std::vector<int32_t>& table)
+{
+  int longest = 0;
+  for (size_t r = 0; r + 2 < table.size(); r += 3) longest = std::max(longest, table[r + 2] - table[r + 1]);
+  return longest;
+}
+
+RunTableFault check_run_table(const int32_t* runs, int32_t nruns, int ncols, int nz)
+{
+  std::vector<char> seen((size_t)ncols * nz, 0);
+  size_t covered = 0;
+  for (int32_t r = 0; r < nruns; ++r) {
+    const int32_t col = runs[3 * r], z0 = runs[3 * r + 1], z1 = runs[3 * r + 2];
+    if (!(col >= 0 && col < ncols && z0 >= 0 && z0 < z1 && z1 <= nz)) return RunTableFault::outside_or_empty;
+    for (int z = z0; z < z1; ++z) {
+      if (seen[(size_t)col * nz + z]) return RunTableFault::covered_twice;
+      seen[(size_t)col * nz + z] = 1;
+    }
+    covered += (size_t)(z1 - z0);
+  }
+  return nruns == 0 || covered == seen.size() ? RunTableFault::none : RunTableFault::not_covered;
+}
+
 }  // namespace wf

@@ -38,4 +38,16 @@ double box_runs_makespan(const std::vector<BoxRun>& runs, int xcd, int nxcd, int
 // uniform plan, as does a uniform plan of one round whose columns are cut (or have fewer than 6 layers to cut).
 BoxRunPlan box_run_plan(int ncols, int nz, int resident, int nxcd, double prologue, int lz_tuning);
 
+// ---- run tables as the kernel takes them: [runs][3] = (column, z0, z1), entry e the run of workgroup e ----
+// Aligned cut: every column cut at the same nseg places (lengths differ by at most one layer), the runs in segment-major
+// order and dealt to the XCDs in contiguous chunks, as the uniform order deals its items: neighbouring columns march
+// through the same layers at the same time, and what one reads as halo the other has just brought into the XCD's L2.
+std::vector<int32_t> aligned_runs(int ncols, int nz, int nseg);
+// layers of the longest run of a table (0 for the empty table)
+int longest_run(const std::vector<int32_t>& table);
+// The kernel trusts its table: every run non-empty and inside its column, every (column, layer) exactly once.  The
+// empty table (nruns = 0: the uniform plan runs) is valid.  The first fault found, runs in table order:
+enum class RunTableFault : int { none = 0, outside_or_empty, covered_twice, not_covered };
+RunTableFault check_run_table(const int32_t* runs, int32_t nruns, int ncols, int nz);
+
 }  // namespace wf

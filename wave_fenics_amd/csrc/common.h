@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "box_items.h"
 #include "march_plan.h"
 #include "wavehip.h"
 
@@ -218,19 +219,7 @@ int launch_stiffness_march_owner(int P, int variant, int nx, int ny, int nz, int
                                  const double* d_D, const DMat& am, double coeff, const double* d_x, double* d_y,
                                  const int32_t* d_items, int nitems, hipStream_t s);
 int march_owner_resident(int P, int variant);   // workgroups resident on the device (occupancy query)
-// Work items of the box marching kernels: item = column + columns * z segment.  Columns of the atomic forms are pieces of bx x by cells; the owner form cuts the lattice lines 0 .. P nx
-// into pieces of P*bx x P*by from (0, 0).  Segment 0 has lz0 layers, every later one lz (the last one what is left):
-// box_segment (march_column.h), for host and kernels alike.
-struct BoxColumns {
-  int nbx, nby;
-  int count() const { return nbx * nby; }
-};
-inline BoxColumns box_columns(int nx, int ny, int bx, int by) { return {(nx + bx - 1) / bx, (ny + by - 1) / by}; }
-inline BoxColumns box_owner_columns(int P, int nx, int ny, int bx, int by)
-{
-  return box_columns(P * nx + 1, P * ny + 1, P * bx, P * by);
-}
-inline int box_segments(int nz, int lz, int lz0) { return 1 + (std::max(nz - lz0, 0) + lz - 1) / lz; }
+// work items of the box marching kernels (columns x z segments), for host and kernels alike: box_items.h
 // indexed marching kernels for arbitrary dofmaps (stiffness_march_idx.hip, stiffness_march_ks.hip): the plan is
 // MarchPlan of march_plan.h, this is the view of its device arrays the launchers take
 struct MarchPlanDev {

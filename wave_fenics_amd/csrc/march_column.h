@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 
+#include "box_items.h"
 #include "common.h"
 
 namespace wf {
@@ -57,17 +58,7 @@ __device__ __forceinline__ int tile_or_dump(int m, int pos, int base, int dump, 
   return (256 * (m + 1) <= LIMIT || pos < LIMIT) ? base + pos : dump + t;
 }
 
-// Layers [z0, z1) of z segment seg of a box: segment 0 has lz0 layers, every later one lz, the last one what is left
-// of nz (lz0 = lz unless the operator is split for the ghost exchange: a short first segment keeps the work that reads
-// the z ghost plane small).  box_segments (common.h) counts them.
-struct BoxSegment {
-  int z0, z1;
-};
-__host__ __device__ inline BoxSegment box_segment(int seg, int nz, int lz, int lz0)
-{
-  const int z0 = seg == 0 ? 0 : lz0 + (seg - 1) * lz, z1 = min(nz, seg == 0 ? lz0 : z0 + lz);
-  return {z0, z1};
-}
+// The layers of a z segment of a box: box_segment (box_items.h).
 
 // ---- LDS of one workgroup, as the host plans with it (lz is chosen from these values; the kernel files assert, for
 // every compiled cross-section, that they cover what the kernel's layout needs) -----------------------------------------

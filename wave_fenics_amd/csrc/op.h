@@ -2,6 +2,8 @@
 //   op_setup.hip       the shared steps          op_create.hip   wf_op_create and its three paths
 //   op_create_box.hip  the box creation path     op_apply.hip    launch, interior / interface splits, info, destroy
 //   box_mesh.h         the box as a dofmap mesh (box_space.cpp)
+// The index lists the kernels trust are computed in files without HIP that take no wf_op: box_items.h (work items and
+// their split), box_run_plan.h (run tables), unique_lists.h (batch-unique lists), march_plan.h (lattice columns).
 #pragma once
 #include <functional>
 #include <memory>
@@ -149,7 +151,8 @@ struct HexMesh {
 
 // the GLL points and weights of degree P on the device
 int upload_tables(int P, DevArray<double>& d_pts, DevArray<double>& d_wts);
-int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB);
+// batch-unique gather/scatter lists of h_dofmap (what d_dofmap holds), batches of CB cells: built on the host, uploaded
+int upload_unique_lists(wf_op* op, const int32_t* h_dofmap, size_t ncells, int nd, int CB);
 // h_cell_coeff (may be null): the cell coefficient per cell of `mesh`, folded into every array written
 int mesh_geometry_rule(int n1, const double* h_pts, const double* h_wts, const HexMesh& mesh, int use_fabs, int clamp,
                        const double* h_cell_coeff, double* d_G9, double* d_G6blk, double* d_detJ);

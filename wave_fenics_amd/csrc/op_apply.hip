@@ -1,6 +1,6 @@
-// What is done with an operator handle once it exists: the launch switch, the interior / interface splits of the
-// marching operators, wf_op_info and wf_op_destroy -- and the two dense simplex creators, whose set-up lives with their
-// kernels (stiffness_dense.hip, mass_dense_simplex.hip).
+// What is done with an operator handle once it exists: the launch switch, the entry points of the interior / interface
+// splits of the marching operators (the split itself: box_items.cpp, march_plan.cpp), wf_op_info and wf_op_destroy --
+// and the two dense simplex creators, whose set-up lives with their kernels (stiffness_dense.hip, mass_dense_simplex.hip).
 #include "dense_simplex.h"
 #include "march_column.h"
 #include "op.h"
@@ -27,17 +27,19 @@ size_t wf::op_device_bytes(const wf_op* op)
 
 namespace {
 
-// the three box marching kernels: work items = columns x z segments (common.h), which split into interior / interface
+// the three box marching kernels: work items = columns x z segments (box_items.h), which split into interior / interface
 bool is_box_march(OpKernel k)
 {
   return k == OpKernel::box_march || k == OpKernel::box_ksplit || k == OpKernel::box_owner;
 }
 
-// columns of a box marching operator: cells in pieces of bx x by, or the owner form's pieces of lattice lines
-BoxColumns op_columns(const wf_op* op)
+// what the split (box_items.h) takes of a box marching operator: its columns are cells in pieces of bx x by, or the
+// owner form's pieces of P*obx x P*oby lattice lines
+BoxItemShape item_shape(const wf_op* op)
 {
-  return op->kernel == OpKernel::box_owner ? box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby)
-                                           : box_columns(op->nx, op->ny, op->box.bx, op->box.by);
+  const bool owner = op->kernel == OpKernel::box_owner;
+  return {op->P, op->nx, op->ny, op->nz, owner, owner ? op->box.obx : op->box.bx, owner ? op->box.oby : op->box.by,
+          op->box.lz, op->tun.lz0};
 }
 
 // the public (geometry, metric, update) of wf_op_info_t for the geometry form of a marching stiffness kernel
@@ -48,14 +50,9 @@ void geom_info(MarchGeom geom, int* geometry, int* metric, int* update)
   *update = geom == MarchGeom::cell_axes ? WF_UPDATE_ATOMIC : WF_UPDATE_NONE;
 }
 
-// uploads the interior / interface work-item lists (and the two interior halves)
-int set_item_lists(wf_op* op, std::vector<int32_t> (&items)[4])
+// uploads the interior / interface work-item lists and the two interior halves
+int set_item_lists(wf_op* op, const std::vector<int32_t> (&items)[4])
 {
-  // the interior halves let a caller hide BOTH halo directions: forward update under
-  // half A, reverse update under half B (alternate items so both halves span the mesh)
-  items[2].clear();
-  items[3].clear();
-  for (size_t q = 0; q < items[0].size(); ++q) items[2 + (q & 1)].push_back(items[0][q]);
   for (int k = 0; k < 4; ++k) {
     op->nitems[k] = (int)items[k].size();
     int rc = op->d_items[k].upload(items[k]);   // replaces the list of an earlier split
@@ -65,25 +62,10 @@ int set_item_lists(wf_op* op, std::vector<int32_t> (&items)[4])
   return WF_OK;
 }
 
-// Splits the work items of a box marching operator (item = column + columns * z segment): interface(Bx, By, seg, z0, z1)
-// says whether the item of column (Bx, By) and layers [z0, z1) reads a ghost value of x or adds into one of y.
-// With a ghost plane below, the first z segment is kept short (wf_tuning.lz0, default 3 layers):
-// only its first layer reads the ghost plane, but the whole segment has to wait for the halo, and
-// the less interface work there is the earlier the reverse exchange can start under the interior.
-template <class Interface>
-int split_box_items(wf_op* op, bool ghost_below, Interface&& interface)
+int set_box_item_lists(wf_op* op, const BoxItemLists& split)
 {
-  const int lz = op->box.lz;
-  op->lz0_split = ghost_below ? std::max(1, std::min(op->tun.lz0 > 0 ? op->tun.lz0 : 3, lz)) : lz;
-  const BoxColumns cols = op_columns(op);
-  const int ncols = cols.count(), nseg = box_segments(op->nz, lz, op->lz0_split);
-  std::vector<int32_t> items[4];
-  for (int seg = 0; seg < nseg; ++seg) {
-    const BoxSegment zs = box_segment(seg, op->nz, lz, op->lz0_split);
-    for (int col = 0; col < ncols; ++col)
-      items[interface(col % cols.nbx, col / cols.nbx, seg, zs.z0, zs.z1) ? 1 : 0].push_back(col + ncols * seg);
-  }
-  return set_item_lists(op, items);
+  op->lz0_split = split.lz0_split;
+  return set_item_lists(op, split.items);
 }
 
 }  // namespace
@@ -237,15 +219,7 @@ int wf_op_set_ghost_faces(wf_op* op, int ghost_x0, int ghost_y0, int ghost_z0)
               "splits any marching operator)");
     return WF_ERR_UNSUPPORTED;
   }
-  // A work item is "interface" when it reads a ghost plane of x / adds into a ghost plane of y.  The owner form's columns
-  // are lattice lines in pieces of P*obx x P*oby and it reads P lattice lines / planes below what it owns:
-  // [I0 - P, ..] x [J0 - P, ..] x [P z0 - P, ..]
-  const bool owner = op->kernel == OpKernel::box_owner;
-  const int P = op->P, obx = op->box.obx, oby = op->box.oby;
-  return split_box_items(op, ghost_z0 != 0, [&](int Bx, int By, int seg, int z0, int) {
-    return owner ? (ghost_x0 && P * obx * Bx <= P) || (ghost_y0 && P * oby * By <= P) || (ghost_z0 && z0 <= 1)
-                 : (ghost_x0 && Bx == 0) || (ghost_y0 && By == 0) || (ghost_z0 && seg == 0);
-  });
+  return set_box_item_lists(op, split_box_items_by_faces(item_shape(op), ghost_x0 != 0, ghost_y0 != 0, ghost_z0 != 0));
 }
 
 int wf_op_set_ghost_dofs(wf_op* op, const int32_t* h_ghost_positions, int32_t nghosts)
@@ -262,32 +236,7 @@ int wf_op_set_ghost_dofs(wf_op* op, const int32_t* h_ghost_positions, int32_t ng
     WF_REQUIRE(h_ghost_positions[g] >= 0 && h_ghost_positions[g] < op->ndofs, "wf_op_set_ghost_dofs: ghost position out of range");
     ghost[h_ghost_positions[g]] = 1;
   }
-  const int P = op->P;
-  if (box) {
-    const int NX = P * op->nx + 1, NY = P * op->ny + 1;
-    const size_t plane = (size_t)NX * NY;
-    // a z ghost plane below: every position of plane K = 0 is a ghost, which is what ghost_z0 of wf_op_set_ghost_faces
-    // says.  (A ghost anywhere in the plane is not enough: an x or y ghost plane alone holds the plane's edge, and the
-    // same planes then gave another segmentation through this call than through wf_op_set_ghost_faces.)
-    bool gz = true;
-    for (size_t g = 0; g < plane && gz; ++g) gz = ghost[g] != 0;
-    // the owner form's columns are pieces of P*obx x P*oby lattice lines; its footprint reaches P lines / planes below
-    // what it owns: [I0 - P, I0 + P obx] x [J0 - P, J0 + P oby] x [P z0 - P, P z1]
-    const bool owner = op->kernel == OpKernel::box_owner;
-    const int cbx = owner ? op->box.obx : op->box.bx, cby = owner ? op->box.oby : op->box.by;   // cells per column
-    const int halo = owner ? P : 0;
-    return split_box_items(op, gz, [&](int Bx, int By, int, int z0, int z1) {
-      const int I0 = std::max(0, P * Bx * cbx - halo), J0 = std::max(0, P * By * cby - halo);
-      const int I1 = std::min(NX - 1, P * Bx * cbx + P * cbx), J1 = std::min(NY - 1, P * By * cby + P * cby);
-      for (int K = std::max(0, P * z0 - halo); K <= P * z1; ++K)
-        for (int J = J0; J <= J1; ++J) {
-          const char* row = &ghost[(size_t)I0 + (size_t)NX * J + plane * K];
-          for (int I = 0; I <= I1 - I0; ++I)
-            if (row[I]) return true;
-        }
-      return false;
-    });
-  }
+  if (box) return set_box_item_lists(op, split_box_items_by_ghosts(item_shape(op), ghost));
   // the plan's item arrays are read back from the handle's device copies: the handle keeps no host copy
   std::vector<int32_t> items[4], base, pat, pat_off;
   int rc;
@@ -295,6 +244,7 @@ int wf_op_set_ghost_dofs(wf_op* op, const int32_t* h_ghost_positions, int32_t ng
   if ((rc = op->d_item_pattern.download(pat)) != WF_OK) return rc;
   if ((rc = op->d_pat_off.download(pat_off)) != WF_OK) return rc;
   split_items_by_ghost(base, pat, pat_off, op->plan.tile_size, ghost, items[0], items[1]);
+  alternate_interior(items);
   return set_item_lists(op, items);
 }
 

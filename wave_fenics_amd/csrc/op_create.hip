@@ -320,6 +320,8 @@ struct BatchInputs {
   bool have_mesh = false;
   HexMesh mesh{};
   const double* h_detJ = nullptr;
+  std::vector<int32_t> p_dofmap;
+  const int32_t* dofmap = nullptr;   // the tensor-ordered dofmap in the internal cell order: what d_dofmap holds
 };
 
 // Order-fixed accumulation: the plan of the order contract (wf_ordered_slots on the CALLER's dofmap, so neither the
@@ -347,7 +349,7 @@ int batch_stiffness(const wf_op_desc* desc, const CallerFrame& fr, const BatchIn
   int rc;
   // batch-unique dof lists (WF_KERNEL_FORCE_ELEMENTWISE keeps the element-wise scatter for comparison)
   const bool unique = !no_unique && ncells > 0 && !op->ordered;
-  if (unique && (rc = build_unique_lists(op, ncells, nd, CB)) != WF_OK) return rc;
+  if (unique && (rc = upload_unique_lists(op, in.dofmap, ncells, nd, CB)) != WF_OK) return rc;
   op->kernel = op->ordered ? OpKernel::ordered_stiffness : unique ? OpKernel::generic_unique : OpKernel::generic_elementwise;
   const size_t g6 = nbatch * CB * nd * 6;
   if ((rc = op->d_G6blk.alloc(g6)) != WF_OK) return rc;
@@ -403,7 +405,7 @@ int batch_mass(const wf_op_desc* desc, const BatchInputs& in, bool no_unique, wf
   const bool elementwise = !dense && (desc->flags & WF_FLAG_MASS_ELEMENTWISE);
   const bool want = elementwise || (dense && (P <= 3 || square));
   const bool unique = want && !no_unique && ncells > 0 && !op->ordered;
-  if (unique && (rc = build_unique_lists(op, ncells, nd, CBm)) != WF_OK) return rc;
+  if (unique && (rc = upload_unique_lists(op, in.dofmap, ncells, nd, CBm)) != WF_OK) return rc;
 
   if (desc->h_detJ) {
     if ((rc = op->d_detJ.upload(in.h_detJ, ncells * op->nq)) != WF_OK) return rc;
@@ -494,17 +496,14 @@ int create_batch(const wf_op_desc* desc, const CallerFrame& fr, const int32_t* t
     }
     in.h_detJ = in.p_detJ.data();
   }
-  int rc;
-  {
-    std::vector<int32_t> sorted;
-    const int32_t* src = tdm;
-    if (!in.identity_cells) {
-      sorted.resize(ncells * nd);
-      for (size_t c = 0; c < ncells; ++c) std::memcpy(&sorted[c * nd], tdm + (size_t)in.cperm[c] * nd, nd * sizeof(int32_t));
-      src = sorted.data();
-    }
-    if ((rc = op->d_dofmap.upload(src, ncells * nd)) != WF_OK) return rc;
+  in.dofmap = tdm;
+  if (!in.identity_cells) {
+    in.p_dofmap.resize(ncells * nd);
+    for (size_t c = 0; c < ncells; ++c) std::memcpy(&in.p_dofmap[c * nd], tdm + (size_t)in.cperm[c] * nd, nd * sizeof(int32_t));
+    in.dofmap = in.p_dofmap.data();
   }
+  int rc;
+  if ((rc = op->d_dofmap.upload(in.dofmap, ncells * nd)) != WF_OK) return rc;
   if ((rc = upload_derivative_tables(op, false)) != WF_OK) return rc;
   if (op->ordered && (rc = build_ordered_plan(desc, fr, in.cperm, op)) != WF_OK) return rc;
   rc = desc->kind == WF_OP_STIFFNESS ? batch_stiffness(desc, fr, in, no_unique, op) : batch_mass(desc, in, no_unique, op);

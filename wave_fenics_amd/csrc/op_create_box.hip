@@ -179,29 +179,11 @@ int wf::plan_owner_runs(wf_op* op, int resident)
 
 namespace {
 
-// Aligned cut: every column cut at the same nseg places (lengths differ by at most one layer), the runs in segment-major
-// order and dealt to the XCDs in contiguous chunks, as the uniform order deals its items: neighbouring columns march
-// through the same layers at the same time, and what one reads as halo the other has just brought into the XCD's L2.
-std::vector<int32_t> aligned_runs(int ncols, int nz, int nseg)
-{
-  const size_t n = (size_t)ncols * nseg, q = n / kXcds, r = n % kXcds;
-  std::vector<int32_t> table(3 * n);
-  size_t xcd = 0, i = 0;   // run i of XCD xcd is entry kXcds * i + xcd
-  for (int s = 0; s < nseg; ++s)
-    for (int col = 0; col < ncols; ++col) {
-      int32_t* e = &table[3 * (kXcds * i + xcd)];
-      e[0] = col, e[1] = (int32_t)((long)nz * s / nseg), e[2] = (int32_t)((long)nz * (s + 1) / nseg);
-      if (++i == q + (xcd < r ? 1 : 0)) i = 0, ++xcd;
-    }
-  return table;
-}
-
+// a run table (box_run_plan.h) on the handle and the device; the empty table: the uniform z segments of box.lz run
 int install_runs(wf_op* op, std::vector<int32_t> table)
 {
   op->h_runs = std::move(table);
-  int longest = 0;
-  for (size_t r = 0; r < op->h_runs.size(); r += 3) longest = std::max(longest, op->h_runs[r + 2] - op->h_runs[r + 1]);
-  op->runs_longest = op->h_runs.empty() ? op->box.lz : longest;
+  op->runs_longest = op->h_runs.empty() ? op->box.lz : longest_run(op->h_runs);
   return op->d_runs.upload(op->h_runs);   // no runs: no array
 }
 
@@ -237,9 +219,7 @@ struct EventPair {
 // plan needs more than one round of the resident workgroups: every other operator stays what it was.
 int wf::tune_owner_runs(wf_op* op)
 {
-  op->h_runs.clear();
-  op->runs_longest = op->box.lz;
-  int rc = op->d_runs.upload(op->h_runs);
+  int rc = install_runs(op, {});
   const int ncols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby).count(), nz = op->nz;
   long resident = march_owner_resident(op->P, op->box.variant);
   if (resident <= 0) resident = 512;
@@ -303,26 +283,14 @@ int wf_op_set_runs(wf_op* op, const int32_t* h_runs, int32_t nruns)
     set_error("wf_op_set_runs: only the owner form of the box stiffness operator runs by a run table");
     return WF_ERR_UNSUPPORTED;
   }
-  // the kernel trusts the table: every (column, layer) exactly once, every run inside its column
-  const int ncols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby).count(), nz = op->nz;
-  std::vector<char> seen((size_t)ncols * nz, 0);
-  size_t covered = 0;
-  int longest = 0;
-  for (int32_t r = 0; r < nruns; ++r) {
-    const int32_t col = h_runs[3 * r], z0 = h_runs[3 * r + 1], z1 = h_runs[3 * r + 2];
-    WF_REQUIRE(col >= 0 && col < ncols && z0 >= 0 && z0 < z1 && z1 <= nz, "wf_op_set_runs: run outside the mesh or empty");
-    for (int z = z0; z < z1; ++z) {
-      WF_REQUIRE(!seen[(size_t)col * nz + z], "wf_op_set_runs: a layer of a column is covered twice");
-      seen[(size_t)col * nz + z] = 1;
-    }
-    covered += (size_t)(z1 - z0);
-    longest = std::max(longest, z1 - z0);
-  }
-  WF_REQUIRE(nruns == 0 || covered == seen.size(), "wf_op_set_runs: the runs do not cover every layer of every column");
+  static const char* kFault[4] = {nullptr, "wf_op_set_runs: run outside the mesh or empty",
+                                 "wf_op_set_runs: a layer of a column is covered twice",
+                                 "wf_op_set_runs: the runs do not cover every layer of every column"};
+  const int ncols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby).count();
+  const RunTableFault fault = check_run_table(h_runs, nruns, ncols, op->nz);
+  WF_REQUIRE(fault == RunTableFault::none, kFault[(int)fault]);
   WF_HIP_CHECK(hipDeviceSynchronize());   // an apply in flight may still read the table this replaces
-  op->h_runs.assign(h_runs, h_runs + 3 * (size_t)nruns);
-  op->runs_longest = nruns ? longest : op->box.lz;
-  return op->d_runs.upload(op->h_runs);
+  return install_runs(op, std::vector<int32_t>(h_runs, h_runs + 3 * (size_t)nruns));
 }
 
 int wf_op_get_runs(const wf_op* op, int32_t* h_runs, int32_t capacity, int32_t* nruns)

@@ -1,11 +1,12 @@
 // Set-up steps shared by the operator creation paths and the cell forms (op.h): the checks of a hexahedral descriptor
-// and the per-cell refusals, tables, geometry staging, batch-unique lists, the caller's tensor frame; the batch plan
-// of the dense simplex operators.
+// and the per-cell refusals, tables, geometry staging, the upload of the batch-unique lists (unique_lists.cpp builds
+// them, also for the batch plan of the dense simplex operators), the caller's tensor frame.
 #include <cmath>
 #include <cstring>
 
 #include "dense_simplex.h"
 #include "op.h"
+#include "unique_lists.h"
 
 namespace wf {
 
@@ -87,78 +88,39 @@ int upload_tables(int P, DevArray<double>& d_pts, DevArray<double>& d_wts)
   return d_wts.upload(wts);
 }
 
-// Batch-unique gather/scatter lists: for every batch of CB consecutive cells the
-// sorted list of its distinct dofs (uniq, offsets uoff) and the position of each
-// element-local dof in that list (loc).  Kernels read x once per unique dof, sum
-// the batch in LDS and issue one global atomic per unique dof.
-int build_unique_lists(wf_op* op, size_t ncells, int nd, int CB)
+// The batch-unique lists (unique_lists.h) of the batch kernels, for batches of CB cells of h_dofmap: the dofmap that
+// d_dofmap holds, tensor order and internal cell order.
+int upload_unique_lists(wf_op* op, const int32_t* h_dofmap, size_t ncells, int nd, int CB)
 {
   if (ncells == 0) return WF_OK;
-  if ((size_t)CB * nd > 65535) {
+  UniqueLists lists;
+  if ((size_t)CB * nd > 65535 || !build_unique_lists(h_dofmap, ncells, nd, CB, &lists)) {
     set_error("build_unique_lists: batch too large for 16-bit local indices");
     return WF_ERR_UNSUPPORTED;
   }
-  const size_t nbatch = (ncells + CB - 1) / CB;
-  std::vector<int32_t> tdm(ncells * nd);
-  WF_HIP_CHECK(hipMemcpy(tdm.data(), op->d_dofmap.data(), tdm.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-  std::vector<int32_t> uoff(nbatch + 1, 0), uniq, tmp;
-  std::vector<uint16_t> loc(ncells * nd);
-  uniq.reserve(ncells * nd / 2);
-  for (size_t b = 0; b < nbatch; ++b) {
-    const size_t c0 = b * CB, nc = std::min<size_t>(CB, ncells - c0);
-    tmp.assign(tdm.begin() + c0 * nd, tdm.begin() + (c0 + nc) * nd);
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    for (size_t e = c0 * nd; e < (c0 + nc) * nd; ++e)
-      loc[e] = (uint16_t)(std::lower_bound(tmp.begin(), tmp.end(), tdm[e]) - tmp.begin());
-    uniq.insert(uniq.end(), tmp.begin(), tmp.end());
-    uoff[b + 1] = (int32_t)uniq.size();
-  }
   int rc;
-  if ((rc = op->d_uoff.upload(uoff)) != WF_OK) return rc;
-  if ((rc = op->d_uniq.upload(uniq)) != WF_OK) return rc;
-  if ((rc = op->d_loc.upload(loc)) != WF_OK) return rc;
+  if ((rc = op->d_uoff.upload(lists.uoff)) != WF_OK) return rc;
+  if ((rc = op->d_uniq.upload(lists.uniq)) != WF_OK) return rc;
+  if ((rc = op->d_loc.upload(lists.loc)) != WF_OK) return rc;
   op->unique_cb = CB;
   return WF_OK;
 }
 
 // The same for the 64-cell batches of the dense simplex kernels (dense_simplex.h), with the local indices packed two to
-// a word in the kernels' operand order: locP[b][ks / 2][lg][cell] holds the local index of dof 4 ks + lg in bits
-// 16 (ks & 1) .. 16 (ks & 1) + 15.
+// a word in the kernels' operand order (pack_dense_loc).
 int DenseBatchPlanDev::build(int nd, int KT, int ncells, const int32_t* dofmap)
 {
-  constexpr int NCB = kDenseBatchCells;
-  const int KT2 = (KT + 1) / 2;   // DenseBatchShape::KT2 of a run-time KT
-  nbatch = (ncells + NCB - 1) / NCB;
-  std::vector<uint32_t> h_locP((size_t)nbatch * KT2 * 4 * NCB, 0);
-  std::vector<int32_t> h_uoff(nbatch + 1, 0), h_uniq, tmp;
-  h_uniq.reserve((size_t)ncells * nd / 2);
-  numax = 1;
-  for (int b = 0; b < nbatch; ++b) {
-    const int c0 = b * NCB, nc = std::min(NCB, ncells - c0);
-    tmp.assign(dofmap + (size_t)c0 * nd, dofmap + (size_t)(c0 + nc) * nd);
-    std::sort(tmp.begin(), tmp.end());
-    tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-    const int nu = (int)tmp.size();
-    if (nu > 65535) {
-      set_error("dense_setup: more than 65535 unique dofs in a batch");
-      return WF_ERR_UNSUPPORTED;
-    }
-    numax = std::max(numax, nu);
-    for (int c = 0; c < nc; ++c)
-      for (int k = 0; k < nd; ++k) {
-        const int32_t g = dofmap[(size_t)(c0 + c) * nd + k];
-        const int u = (int)(std::lower_bound(tmp.begin(), tmp.end(), g) - tmp.begin());
-        const int ks = k / 4, lg = k % 4;
-        h_locP[(((size_t)b * KT2 + ks / 2) * 4 + lg) * NCB + c] |= (uint32_t)u << (16 * (ks & 1));
-      }
-    h_uniq.insert(h_uniq.end(), tmp.begin(), tmp.end());
-    h_uoff[b + 1] = (int32_t)h_uniq.size();
+  UniqueLists lists;
+  if (!build_unique_lists(dofmap, (size_t)ncells, nd, kDenseBatchCells, &lists)) {
+    set_error("dense_setup: more than 65535 unique dofs in a batch");
+    return WF_ERR_UNSUPPORTED;
   }
+  nbatch = (int)lists.uoff.size() - 1;
+  numax = std::max(1, lists.largest());
   int rc;
-  if ((rc = locP.upload(h_locP)) != WF_OK) return rc;
-  if ((rc = uoff.upload(h_uoff)) != WF_OK) return rc;
-  return uniq.upload(h_uniq);
+  if ((rc = locP.upload(pack_dense_loc(lists.loc, (size_t)ncells, nd, KT, kDenseBatchCells))) != WF_OK) return rc;
+  if ((rc = uoff.upload(lists.uoff)) != WF_OK) return rc;
+  return uniq.upload(lists.uniq);
 }
 
 // Geometry of every cell at the n1^3 points of a 1-D rule, computed from the mesh into whichever of the device arrays
