@@ -879,6 +879,19 @@ int wf_sources_destroy(wf_sources* src);
 int wf_sources_info(const wf_sources* src, int* nsources, int* nunique, int* nentries);
 int wf_sources_add(const wf_sources* src, double t, double* d_b, void* stream);
 
+/* ---- the passes of the discrete adjoint of the leapfrog loop (csrc/adjoint.hip) ----
+ * wf_leapfrog_correlate: p[i] = p[i] + lam[i] * ((up[i] - 2.0*u[i]) + um[i]) for i < n, evaluated as written (no fused
+ *   multiply-add), so every compiled form gives the same bits: the multiplier of a step times the second difference of
+ *   the state, accumulated over the steps.  d_p must not overlap an input (WF_ERR_INVALID, nothing written); the inputs
+ *   may overlap each other.  n <= 0 is a no-op.  48 B/dof of HBM traffic.
+ * wf_sources_add_values: the wavelets are not looked at; d_values [nsources] on the device takes their place:
+ *   acc = sum over the entries e of dof d, in the CSR order of wf_sources_merge, of weight[e] * d_values[source[e]];
+ *   d_b[d] += scale * acc.  One thread and one update per unique dof, no atomics: with sources on the points of a
+ *   wf_points plan it is the transpose of wf_points_sample.  d_values may point anywhere inside a larger buffer. */
+int wf_leapfrog_correlate(int64_t n, const double* d_lam, const double* d_up, const double* d_u, const double* d_um, double* d_p,
+                          void* stream);
+int wf_sources_add_values(const wf_sources* src, const double* d_values, double scale, double* d_b, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

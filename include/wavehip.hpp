@@ -556,6 +556,14 @@ void scale(Scalar alpha, Vector& x, void* stream = nullptr)
 }
 }  // namespace linalg
 
+/// p += lam * ((up - 2 u) + um) over n entries, evaluated as written (wf_leapfrog_correlate): the per-step term of the
+/// lumped-mass sensitivity of the leapfrog loop's discrete adjoint.  p must not overlap an input.
+inline void leapfrog_correlate(std::int64_t n, const double* d_lam, const double* d_up, const double* d_u, const double* d_um,
+                               double* d_p, void* stream = nullptr)
+{
+  check(wf_leapfrog_correlate(n, d_lam, d_up, d_u, d_um, d_p, stream));
+}
+
 // ---- point sources and receivers (wf_points_*, wf_sources_*; not in the reference) ----
 /// Physical points located in the mesh of a Space (wf_points_locate, reference coordinates in [0, 1]^3) with their
 /// dofmap rows and interpolation weights on the device.  Throws naming the first point that lies in no cell.
@@ -610,6 +618,12 @@ public:
   Sources& operator=(const Sources&) = delete;
   ~Sources() { wf_sources_destroy(_s); }
   void add(double t, double* d_b, void* stream = nullptr) const { check(wf_sources_add(_s, t, d_b, stream)); }
+  /// b[d] += scale * sum_i d_values[i] phi_d(x_i): device values in the place of the wavelets (wf_sources_add_values),
+  /// the transpose of Receivers::sample on the same points
+  void add_values(const double* d_values, double* d_b, double scale = 1.0, void* stream = nullptr) const
+  {
+    check(wf_sources_add_values(_s, d_values, scale, d_b, stream));
+  }
   const wf_sources* handle() const { return _s; }
 
 private:

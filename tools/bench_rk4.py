@@ -11,7 +11,12 @@ Prints one JSON line: ms per RK4 time step and dof-stages/s over all ranks.
 window includes the scheme's start-up and finish, two extra stiffness applies).
 --receivers N / --sources S (one rank): the same loop with N point receivers recorded every step and S Ricker point
 sources, against the loop without them -- two models in one process, timed alternately --rounds times after one warm-up
-each; prints medians and ranges of both and the difference per step."""
+each; prints medians and ranges of both and the difference per step.
+--scheme leapfrog --gradient (one rank): LinearGLLOpt.misfit_gradient against LinearGLLOpt.leapfrog on one model with
+--receivers (default 1000) receivers and --sources (default 1) source, --steps (default 200) steps each, timed alternately
+--rounds times with device events after a warm-up of both; prints ms per step of both, their ratio and the time per
+backward step (the difference).  The split of a backward step by kernel comes from a run of its own under
+`rocprofv3 --kernel-trace --stats -- python tools/bench_rk4.py --scheme leapfrog --gradient --rounds 1`."""
 import argparse
 import json
 import os
@@ -24,7 +29,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100; 200 with --gradient)")
     ap.add_argument("--warmup", type=int, default=150, help="untimed steps; long enough to pass the power ramp after idle (profiles/r03_power_ramp.md)")
     ap.add_argument("--size", type=int, default=54)
     ap.add_argument("--degree", type=int, default=4)
@@ -33,9 +38,17 @@ def main():
                     help="leapfrog: LinearGLLOpt.leapfrog at the same step (one stiffness apply per step; ms_per_rk4_step is then ms per leapfrog step)")
     ap.add_argument("--receivers", type=int, default=0, help="point receivers recorded every step (A/B against the plain loop)")
     ap.add_argument("--sources", type=int, default=0, help="Ricker point sources (A/B against the plain loop)")
+    ap.add_argument("--gradient", action="store_true", help="with --scheme leapfrog: time misfit_gradient against leapfrog")
+    ap.add_argument("--checkpoint-every", type=int, default=None, help="--gradient: steps between checkpoints (default ceil(sqrt(steps)))")
     ap.add_argument("--rounds", type=int, default=5, help="alternating timed runs per variant of the A/B")
     ap.add_argument("--periodic", default="", help="axes identified with their opposite face (one rank: RCCL exchange with itself)")
     args = ap.parse_args()
+    if args.gradient and args.scheme != "leapfrog":
+        sys.exit("--gradient needs --scheme leapfrog")
+    if args.steps is None:
+        args.steps = 200 if args.gradient else 100
+    if args.gradient:
+        args.receivers, args.sources = args.receivers or 1000, args.sources or 1
     import torch
     import torch.distributed as dist
     import wave_fenics_amd as w
@@ -85,6 +98,9 @@ def main():
                              [points.ricker(0.5e6, 3.0e-6, 1.0e9)] * args.sources) if args.sources else None
         with_points = LinearGLLOpt(V, p, 1500.0, 0.5e6, 6e4, tags=boundary_tags(part), device=dev, sources=src, receivers=rec)
         with_points.init()
+        if args.gradient:
+            gradient_ab(args, with_points, rec, dt, part.size_global)
+            return
         models = {"plain": eqn, "points": with_points}
         name = "leapfrog" if args.scheme == "leapfrog" else "rk4" if args.unfused else "rk4_fused"
         times = {k: [] for k in models}
@@ -130,6 +146,46 @@ def main():
                           "exchange": updater.transport if updater is not None else None, "finite": ok, "scaling": "weak"}), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def gradient_ab(args, eqn, rec, dt, global_dofs):
+    """misfit_gradient against leapfrog on one model, alternately, each run timed by a pair of device events"""
+    import statistics
+
+    import torch
+    steps = args.steps
+
+    def timed(fn):
+        rec.reset()
+        eqn.init()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / steps, out
+
+    forward = lambda: eqn.leapfrog(0.0, 1.0e9, dt, max_steps=steps)    # noqa: E731
+    eqn.leapfrog(0.0, 1.0e9, dt, max_steps=args.warmup)
+    timed(forward)
+    observed = 0.9 * rec.traces.clone()                                # a misfit that is not zero
+    gradient = lambda: eqn.misfit_gradient(0.0, 1.0e9, dt, observed, checkpoint_every=args.checkpoint_every, max_steps=steps)    # noqa: E731
+    timed(gradient)
+    times = {"leapfrog": [], "gradient": []}
+    for _ in range(args.rounds):
+        times["leapfrog"].append(timed(forward)[0])
+        ms, (J, gK, gM, info) = timed(gradient)
+        times["gradient"].append(ms)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    stat = lambda v, m: {"median": m, "min": min(v), "max": max(v)}    # noqa: E731
+    print(json.dumps({"metric": "misfit_gradient against leapfrog, ms per step (device events)", "steps": steps, "rounds": args.rounds,
+                      "receivers": args.receivers, "sources": args.sources, "global_dofs": global_dofs,
+                      "leapfrog_ms": stat(times["leapfrog"], med["leapfrog"]), "gradient_ms": stat(times["gradient"], med["gradient"]),
+                      "gradient_over_leapfrog": med["gradient"] / med["leapfrog"],
+                      "backward_step_ms": med["gradient"] - med["leapfrog"],
+                      "S": info["S"], "vectors": info["vectors"], "bytes": info["bytes"], "launches": info["launches"], "J": J,
+                      "finite": bool(torch.isfinite(gK).all() and torch.isfinite(gM).all())}), flush=True)
 
 
 if __name__ == "__main__":

@@ -251,6 +251,8 @@ SIGNATURES = {
     "wf_sources_destroy": (c_int, [c_void_p]),
     "wf_sources_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "wf_sources_add": (c_int, [c_void_p, c_double, c_void_p, c_void_p]),
+    "wf_leapfrog_correlate": (c_int, [c_int64] + [c_void_p] * 6),
+    "wf_sources_add_values": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "wf_cell_form_create": (c_int, [POINTER(OpDesc), POINTER(c_void_p)]),
     "wf_cell_form_create_box": (c_int, [c_int, c_int, c_int, c_int, c_int, _DP, c_double, _DP, c_int, POINTER(Tuning),
                                         POINTER(c_void_p)]),

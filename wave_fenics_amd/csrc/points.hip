@@ -13,26 +13,8 @@
 //   own entries at time t in fp64, sums w s(t) in CSR order and does one b[d] += acc: one writer per dof.
 #include "common.h"
 #include "device_array.h"
+#include "points_handles.h"
 #include "points_plan.h"
-
-struct wf_points {
-  int P = 0, nd = 0, npoints = 0;
-  int64_t ndofs = 0;
-  std::vector<int32_t> h_dofs;   // [npoints][nd], kept for wf_sources_create
-  std::vector<double> h_w;       // [npoints][3][P+1]
-  wf::DevArray<int32_t> d_dofs;
-  wf::DevArray<double> d_w;
-};
-
-struct wf_sources {
-  int nsrc = 0, nunique = 0, nentries = 0;
-  int64_t ndofs = 0;
-  wf::DevArray<int32_t> d_dof, d_off, d_src;
-  wf::DevArray<double> d_weight;
-  // wavelets: kind, (amplitude, frequency, delay, t_start, dt) and the table [soff[s], soff[s+1]) per source
-  wf::DevArray<int32_t> d_kind, d_soff;
-  wf::DevArray<double> d_par, d_samples;
-};
 
 namespace wf {
 

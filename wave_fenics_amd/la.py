@@ -90,6 +90,11 @@ def leapfrog_step(b, m, u, u_prev, u_next, dt: float, v=None, bc=None, s1: float
     check(lib().wf_leapfrog_step(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_next), vp, _stream(b)))
 
 
+def leapfrog_correlate(lam, up, u, um, p):
+    """p += lam * ((up - 2 u) + um), evaluated as written (wf_leapfrog_correlate); p must not overlap an input."""
+    check(lib().wf_leapfrog_correlate(p.numel(), _ptr(lam), _ptr(up), _ptr(u), _ptr(um), _ptr(p), _stream(p)))
+
+
 class BoundaryPlan(Handle):
     """wf_boundary_create: the two boundary dof sets of the form L (LinearGLL.hpp:113-115, forms.ufl:19-24) as a
     bitmap + coefficient arrays, so that the fused RK4 stage can leave the next right-hand side's boundary

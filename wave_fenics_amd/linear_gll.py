@@ -64,6 +64,7 @@ class LinearGLLOpt:
     #: the boundary term a launch of its own after each stage kernel, for comparison (tools/ab_rk4_boundary.py).
     fold_boundary = True
     _bc = None   # la.BoundaryPlan of the fused loops (_boundary_plan)
+    _rec_T = None   # (receivers, their transpose as Sources) of misfit_gradient
 
     def __init__(self, V, degreeOfBasis: int, speedOfSound: float, sourceFrequency: float,
                  pressureAmplitude: float, boundary=None, updater=None, device=None, structured=None,
@@ -381,6 +382,12 @@ class LinearGLLOpt:
 
         The step is constant: steps are counted by `while t < finalTime` and the last step is NOT shortened to land on
         finalTime (a shortened step would break the two-level recurrence).  Returns (t, steps)."""
+        return self._leapfrog(startTime, finalTime, timeStep, max_steps)
+
+    def _leapfrog(self, startTime, finalTime, timeStep, max_steps, keep=None):
+        """leapfrog(); keep(n, t, u_prev, u, a0) (misfit_gradient) is called before step n = 0, 1, ... with the time and the
+        two states the step reads (a0: the vector holding the start-up acceleration, valid at n = 0 only).  It may copy
+        them; the loop's own launches and their order do not depend on it."""
         t, tf, dt = startTime, finalTime, timeStep
         step = 0
         b, m = self.b, self.m
@@ -402,6 +409,8 @@ class LinearGLLOpt:
         la.axpy(w, 0.5 * dt * dt, scratch, w)
         la.fill(b, 0.0)
         while t < tf:
+            if keep is not None:
+                keep(step, t, w, u, scratch)
             rhs(u, b)                              # b is zero on entry
             if src is not None:
                 src.add(t, b)
@@ -423,6 +432,138 @@ class LinearGLLOpt:
             self.updater.scatter_fwd(self.u_n)
             self.updater.scatter_fwd(self.v_n)
         return t, step
+
+    def misfit_gradient(self, t0: float, tf: float, dt: float, observed, checkpoint_every: int | None = None,
+                        max_steps: int | None = None):
+        """The L2 trace misfit of a leapfrog run and its gradient with respect to the cell coefficients of the model's two
+        operators: returns (J, g_stiff, g_mass, info).
+
+        The forward run is leapfrog(t0, tf, dt, max_steps) from the current (u_n, v_n): the same launches in the same
+        order, recording u at `receivers` (rows n = 0 .. N, N the number of steps), and leaving u_n, v_n and
+        receivers.traces as leapfrog would.  observed is [N + 1, R] (numpy or device) and
+
+            J = 1/2 dt sum_n sum_r (traces[n, r] - observed[n, r])^2.
+
+        g_stiff[c] = dJ/da^K_c and g_mass[c] = dJ/da^M_c are device vectors in the mesh's cell order; a^K, a^M are the cell
+        coefficients of stiff_op and mass_op -- medium.stiff_coeff and medium.mass_coeff, or an implicit 1 per cell
+        without a medium.  Held fixed: the facet masses mG1, mG2 (the admittance they carry included), s1(t), the sources,
+        u^0 and v^0.  The chain rule to (c, rho) is the caller's, and exact only for cells without a tagged face.
+
+        It is the gradient of the loop as it runs (the discrete adjoint), start-up included; the finishing step does not
+        enter J.  With A+- = m +- h (h = hdt c2 on the boundary sets) step n is
+            A+ u^{n+1} = dt^2 (K u^n + f^n) + 2 m u^n - A- u^{n-1},
+        and the multipliers mu_N = mu_{N+1} = 0,
+            A+ mu_{k-1} = dt^2 (K mu_k + R^T r^k / dt) + 2 m mu_k - A- mu_{k+1},        r^k = traces[k] - observed[k],
+        march backwards through the same wf_leapfrog_step_bc (s1 = 0, the load by wf_sources_add_values on the transposed
+        receivers): K is symmetric and m, h diagonal, so the adjoint absorbs with the same sign.  Then
+            a^K_c g_stiff[c] = dt^2 (sum_n e^K_c(mu_n, u^n) + e^K_c(-1/2 (A-/m) mu_0, u^0)),
+            a^M_c g_mass[c]  = e^M_c(1, q - p),   p = sum_n mu_n (u^{n+1} - 2 u^n + u^{n-1}),  q = dt^2/2 (A-/m) mu_0 a^0,
+        with the forms of cell_forms() and p accumulated per step by wf_leapfrog_correlate (the lumped mass is diagonal).
+
+        Memory: the forward run keeps the pair (u^{jS-1}, u^{jS}) every S = checkpoint_every steps (default
+        ceil(sqrt(N))); the backward pass re-runs one segment at a time from its pair into S further vectors and marches
+        mu back through it.  info: "N", "S", "vectors" (2 ceil(N/S) + min(S, N) + 5 vectors of ndofs doubles beyond the
+        model's own: the pairs, the segment, mu twice, p, a^0, h), "bytes", "launches" (library calls that launch
+        kernels), "t" and "steps" of the forward run.
+
+        Re-running a segment repeats the launches of the forward run.  Where the stiffness apply is bitwise repeatable (the
+        structured box's owner kernel, WF_FLAG_ORDERED) the replayed states, and so J and both gradients, are
+        bit-identical for every S and from call to call; where the apply adds by atomics they agree to rounding only.
+
+        Raises before the first launch: with updater=, without receivers, dt <= 0, observed of another shape, S < 1."""
+        if self.updater is not None:
+            raise NotImplementedError("LinearGLLOpt.misfit_gradient on a partitioned mesh (updater=) is not implemented")
+        rec, src = self.receivers, self.sources
+        if rec is None:
+            raise ValueError("LinearGLLOpt.misfit_gradient needs receivers=")
+        if not dt > 0.0:
+            raise ValueError("LinearGLLOpt.misfit_gradient: the time step must be positive")
+        N, t = 0, t0                                # the steps leapfrog will take
+        while t < tf:
+            t += dt
+            N += 1
+            if max_steps is not None and N >= max_steps:
+                break
+        R = len(rec)
+        if tuple(observed.shape) != (N + 1, R):
+            raise ValueError(f"LinearGLLOpt.misfit_gradient: observed is {tuple(observed.shape)}, the run records {(N + 1, R)}")
+        S = max(1, math.isqrt(max(N - 1, 0)) + 1) if checkpoint_every is None else int(checkpoint_every)
+        if S < 1:
+            raise ValueError("LinearGLLOpt.misfit_gradient: checkpoint_every must be at least 1")
+        if isinstance(observed, np.ndarray):
+            observed = torch.from_numpy(np.array(observed, dtype=np.float64))   # a copy: the caller's array may be read-only
+        observed = observed.to(self.device, dtype=torch.float64)
+        ncp, Sb = -(-N // S), min(S, N)
+        b, m = self.b, self.m
+        new = lambda: torch.empty_like(self.u_n)   # noqa: E731
+        pairs, times, a0 = [], [], new()
+
+        def keep(n, tn, u_prev, u, scratch):
+            times.append(tn)
+            if n == 0:
+                la.copy(scratch, a0)
+            if n % S == 0:
+                pair = (new(), new())
+                la.copy(u_prev, pair[0])
+                la.copy(u, pair[1])
+                pairs.append(pair)
+
+        row0 = rec._rows
+        t, steps = self._leapfrog(t0, tf, dt, max_steps, keep)
+        assert steps == N and len(pairs) == ncp
+        resid = rec.traces[row0:row0 + N + 1] - observed
+        J = 0.5 * dt * float((resid * resid).sum().item())
+        ncells = self.V.mesh.ncells
+        g_stiff = torch.zeros(ncells, dtype=torch.float64, device=self.device)
+        ns = 0 if src is None else 1
+        info = {"N": N, "S": S, "vectors": 2 * ncp + Sb + 5, "t": t, "steps": steps,
+                "launches": (8 + ns + (N > 0)) + N * (3 + ns) + (3 + ns) + 2 * ncp + N * (2 + ns) + 5 * N + 2 * (N > 0)}
+        info["bytes"] = info["vectors"] * self.u_n.numel() * 8
+        if N == 0:
+            return J, g_stiff, torch.zeros_like(g_stiff), info
+        kform, mform = self.cell_forms()
+        if self._rec_T is None or self._rec_T[0] is not rec:
+            self._rec_T = (rec, rec.transpose())
+        RT = self._rec_T[1]
+        bc, s1, s2, rhs = self._boundary_plan(), self._s1, self._s2, self._rhs
+        mu, mu_next, p = torch.zeros_like(self.u_n), torch.zeros_like(self.u_n), torch.zeros_like(self.u_n)
+        bufs = [new() for _ in range(Sb)]
+        for j in reversed(range(ncp)):
+            n0, n1 = j * S, min((j + 1) * S, N)
+            st = [pairs[j][0], pairs[j][1]] + bufs[:n1 - n0]          # st[i] = u^{n0 - 1 + i}
+            for i, n in enumerate(range(n0, n1)):                     # the forward steps of the segment again
+                rhs(st[i + 1], b)
+                if src is not None:
+                    src.add(times[n], b)
+                la.leapfrog_step(b, m, st[i + 1], st[i], st[i + 2], dt, bc=bc, s1=s1(times[n]), s2=s2)
+            for n in reversed(range(n0, n1)):                         # mu_n from mu = mu_{n+1}, mu_next = mu_{n+2}
+                i = n - n0
+                rhs(mu, b)
+                RT.add_values(resid[n + 1], b, scale=1.0 / dt)
+                la.leapfrog_step(b, m, mu, mu_next, mu_next, dt, bc=bc, s1=0.0, s2=s2)
+                mu, mu_next = mu_next, mu
+                kform.eval(mu, st[i + 1], out=g_stiff, accumulate=True)
+                la.leapfrog_correlate(mu, st[i + 2], st[i + 1], st[i], p)
+            if j > 0:
+                pairs[j] = None
+        # start-up: u^{-1} = u^0 - dt v^0 + dt^2/2 a^0 depends on K and m; mu_next = (A-/m) mu_0
+        u0 = pairs[0][1]
+        h = torch.zeros_like(self.u_n)
+        if self.idx2.numel():
+            h.index_add_(0, self.idx2.long(), self.mG2)
+        h.mul_((-s2) * (0.5 * dt))
+        torch.sub(m, h, out=mu_next)
+        mu_next.div_(m).mul_(mu)
+        kform.eval(mu_next, u0, out=g_stiff, alpha=-0.5, accumulate=True)
+        mu_next.mul_(a0)
+        p.mul_(-1.0).add_(mu_next, alpha=0.5 * dt * dt)               # q - p
+        mu.fill_(1.0)
+        g_mass = mform.eval(mu, p)
+        g_stiff.mul_(dt * dt)
+        if self.medium is not None:
+            g_stiff.div_(torch.from_numpy(np.ascontiguousarray(self.medium.stiff_coeff)).to(self.device))
+            g_mass.div_(torch.from_numpy(np.ascontiguousarray(self.medium.mass_coeff)).to(self.device))
+        return J, g_stiff, g_mass, info
 
     def max_eigenvalue(self, iters: int = 100):
         """Largest eigenvalue of -M^{-1} K (lumped mass, the model's stiffness operator) by `iters` power iterations; the

@@ -184,6 +184,11 @@ class Receivers(_Points):
         self._rows = 0
         self.times = []
 
+    def transpose(self):
+        """Sources on the same located points (the same cells and reference coordinates, so the same weights) with
+        zero-amplitude wavelets: its add_values(r, b) is b += R^T r where sample(x) is R x."""
+        return Sources(self.V, None, [ricker(1.0, 0.0, 0.0)] * len(self), located=(self.cell, self.ref))
+
 
 class Sources(_Points):
     """Sources(V, xyz, wavelets): point sources f = s_i(t) delta(x - x_i), wavelets a list of ricker(...) / sampled(...)
@@ -226,6 +231,13 @@ class Sources(_Points):
         """b[d] += sum_i s_i(t) phi_d(x_i)"""
         _check_vec(b, self.V.ndofs, "Sources.add b")
         check(lib().wf_sources_add(self._s, float(t), _ptr(b), _stream(b)))
+
+    def add_values(self, values, b, scale: float = 1.0):
+        """b[d] += scale * sum_i values[i] phi_d(x_i): the wavelets are not looked at, values (a contiguous float64 device
+        vector of len(self) entries, which may be a row of a larger buffer) takes their place (wf_sources_add_values)."""
+        _check_vec(values, len(self), "Sources.add_values values")
+        _check_vec(b, self.V.ndofs, "Sources.add_values b")
+        check(lib().wf_sources_add_values(self._s, _ptr(values), float(scale), _ptr(b), _stream(b)))
 
     def close(self):
         if getattr(self, "_s", None) is not None and self._s.value:
