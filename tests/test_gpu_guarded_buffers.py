@@ -50,7 +50,9 @@ BY + 1, 5) cells at lz = 2.
 
 Covered before: the tetrahedral mass runs inside padded buffers (test_gpu_tet_mass.py); wf_tsmm and the tetrahedral
 stiffness at 8-byte aligned addresses (test_gpu_parity.py, test_gpu_tet_dense_paths.py).  No
-stiffness or hexahedral mass kernel did."""
+stiffness or hexahedral mass kernel did.  wf_tsmm's padded buffers in test_gpu_parity.py reach the kernel's tail only;
+test_gpu_tsmm_paths.py runs every path of its launch plan, the main loop included, inside padded buffers at both
+alignments."""
 import functools
 
 import numpy as np

@@ -847,8 +847,12 @@ def test_generic_ops_random_cell_order(gpu, oracle):
 def test_tsmm_vs_numpy(gpu, ncells, K, N):
     """wf_tsmm in both array layouts (demo/gpu_operator cell-major, demo/gpu_tsmm
     column-major with lda = ncells) against a float64 numpy product: k-ordered
-    fma chains, tolerance 1e-13 of the row magnitude.  K > 128 (the P5..P7 tables of
-    demo/gpu_operator: 216, 343, 512) runs as row ranges accumulating onto out."""
+    fma chains, tolerance 1e-13 of the largest row magnitude.  K > 128 (the P5..P7 tables of
+    demo/gpu_operator: 216, 343, 512) runs as row ranges accumulating onto out.  out is zeroed
+    beforehand and nothing around it is watched.  The twelve small shapes run in the column-split
+    tail (or, for N <= 16, the main loop at one accumulator tile per wave); only the six large ones
+    enter the main loop with several tiles per wave.  tests/test_gpu_tsmm_paths.py holds every
+    path of the launch plan to entry-wise bounds in padded buffers."""
     import torch
     import wave_fenics_amd as w
     rng = np.random.default_rng(ncells + K)
@@ -908,14 +912,19 @@ def tsmm_check(gpu, ncells, K, N, layout, shift):
                                         (1, 27, 27), (1, 129, 216), (50, 35, 1), (33, 343, 1), (1, 1, 1)])  # one cell, one column
 def test_tsmm_overwrites_out(gpu, ncells, K, N, layout):
     """`out = in . phi` with out full of NaN on entry: K <= 128 is one row range, K > 128 several that accumulate onto
-    the first, which must overwrite; 1e-13 of the row magnitude as test_tsmm_vs_numpy"""
+    the first, which must overwrite; 1e-13 of the row magnitude as test_tsmm_vs_numpy.  These shapes have at most 256
+    cell tiles, so with N > 16 every launch runs in the kernel's tail (tail_ct = 1, no main-loop tile); only N = 1
+    (one accumulator tile per wave) runs the main loop.  The main loop's overwrite and accumulate at two to eight tiles
+    per wave are in tests/test_gpu_tsmm_paths.py."""
     tsmm_check(gpu, ncells, K, N, layout, 0)
 
 
 @pytest.mark.parametrize("layout", [0, 1])
 @pytest.mark.parametrize("ncells,K,N", [(77, 27, 27), (100, 129, 125), (1, 27, 27), (50, 35, 1), (4099, 125, 125)])
 def test_tsmm_8_byte_aligned_operands(gpu, ncells, K, N, layout):
-    """in, phi and out one entry off 16-byte alignment inside padded buffers"""
+    """in, phi and out one entry off 16-byte alignment inside padded buffers.  Every shape with N > 16 runs in the
+    kernel's tail ((4099, 125, 125) at tail_ct = 2, the others at 1); the main loop at this alignment is in
+    tests/test_gpu_tsmm_paths.py."""
     tsmm_check(gpu, ncells, K, N, layout, 1)
 
 

@@ -19,19 +19,11 @@
 #include <type_traits>
 
 #include "common.h"
+#include "tsmm_plan.h"   // kTsmmChunk, kTsmmWaves and the launch plan (no HIP; walked on the host by tests/cxx/tsmm_plan_walk.cpp)
 
 namespace wf {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
-
-// k-steps per chunk: the A operands of a chunk are loaded two chunks ahead (three rotating
-// register sets), the B operands (LDS) one k-step ahead, so that no MFMA waits on the load
-// issued just before it.  The LDS table is zero-padded to a whole number of chunks.
-constexpr int kTsmmChunk = 8;
-#ifndef WF_TSMM_WAVES
-#define WF_TSMM_WAVES 8
-#endif
-constexpr int kTsmmWaves = WF_TSMM_WAVES;   // waves per workgroup (one workgroup per CU)
 
 // Diagnostic (tools/tsmm_trace.hip defines WF_TSMM_TRACE and includes this file): per-wave
 // timestamps of the prologue and of each cell tile, 100 MHz constant clock.
@@ -373,27 +365,15 @@ template <int NT>
 static int launch_tsmm_t(int layout, int64_t ncells, int Kfull, int N, int n0, int k0, int K, const double* in,
                          const double* phi, double* out, hipStream_t s)
 {
-
-  const int KT = (K + 3) / 4, rows = 4 * kTsmmChunk * ((KT + kTsmmChunk - 1) / kTsmmChunk);
-  const int NW = 16 * NT, NP = NW + ((NW & 31) == 16 ? 0 : 16);
-  const size_t lds = (size_t)(rows + 4) * NP * sizeof(double);
-  if (lds > 160 * 1024) {
+  const TsmmLaunchPlan plan = tsmm_launch_plan(NT, ncells, K);   // tsmm_plan.h
+  const size_t lds = plan.lds;
+  if (lds > kTsmmLdsLimit) {
     set_error("wf_tsmm: row range too large for the LDS-staged table");
     return WF_ERR_UNSUPPORTED;
   }
-  const int64_t ntiles = (ncells + 15) / 16;
-  const unsigned nb = (unsigned)std::min<int64_t>(ntiles, 256);   // one workgroup per CU; small problems spread over CUs first
-  // partial last round: split its tiles along the columns when every wave then gets at most one unit
-  const int64_t nwaves = (int64_t)nb * kTsmmWaves, rem = ntiles % nwaves;
-  int64_t main_tiles = ntiles;
-  int tail_ct = 0;
-  if (rem > 0 && KT <= 4 * kTsmmChunk)
-    for (int ct : {1, 2, 4})
-      if (ct < NT && rem * ((NT + ct - 1) / ct) <= nwaves) {
-        tail_ct = ct;
-        main_tiles = ntiles - rem;
-        break;
-      }
+  const unsigned nb = plan.nb;
+  const int64_t main_tiles = plan.main_tiles;
+  const int tail_ct = plan.tail_ct;
   // (the attribute is set on every launch that needs more than 64 KB: a per-process cache of "already set" is wrong for a
   // second device in the process and racy between host threads, and the call costs well under a microsecond)
   auto go = [&](auto kern) -> int {
@@ -421,30 +401,16 @@ extern "C" int wf_tsmm(int layout, int64_t ncells, int K, int N, const double* d
   WF_REQUIRE(ncells < (int64_t(1) << 27), "wf_tsmm: at most 2^27 cells per call (32-bit lane offsets)");
   if (ncells == 0) return WF_OK;
   hipStream_t s = (hipStream_t)stream;
-  // Columns in passes of at most 128 (8 accumulator tiles of 16 per wave), the tiles spread evenly
-  // over the passes (N = 216: 7 + 7 tiles rather than 8 + 6 with two idle); table rows in ranges
-  // of at most 128 (the LDS-resident block is 128 x 144 doubles = 147 KB), whole 32-row chunks
-  // first, later ranges accumulating onto out.  The P5..P7 tables of demo/gpu_operator
-  // (216^2, 343^2, 512^2) take 4 / 9 / 16 launches.
-  const int tiles = (N + 15) / 16, npass = (tiles + 7) / 8, tpp = (tiles + npass - 1) / npass;
-  const int nk = (K + 127) / 128, kc = 32 * (((K + nk - 1) / nk + 31) / 32);
-  for (int n0 = 0; n0 < N; n0 += 16 * tpp) {
-    const int nt = std::min(tpp, (N - n0 + 15) / 16);
-    for (int k0 = 0; k0 < K; k0 += kc) {
-      const int kk = std::min(kc, K - k0);
-      int rc;
-      switch (nt) {
-      case 1: rc = launch_tsmm_t<1>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      case 2: rc = launch_tsmm_t<2>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      case 3:
-      case 4: rc = launch_tsmm_t<4>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      case 5: rc = launch_tsmm_t<5>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      case 6: rc = launch_tsmm_t<6>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      case 7: rc = launch_tsmm_t<7>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      default: rc = launch_tsmm_t<8>(layout, ncells, K, N, n0, k0, kk, d_in, d_phi, d_out, s); break;
-      }
-      if (rc != WF_OK) return rc;
+  // column passes and row ranges (tsmm_plan.h), later ranges accumulating onto out
+  return tsmm_for_each_launch(K, N, [&](const TsmmLaunch& l) -> int {
+    switch (l.NT) {
+    case 1: return launch_tsmm_t<1>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
+    case 2: return launch_tsmm_t<2>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
+    case 4: return launch_tsmm_t<4>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
+    case 5: return launch_tsmm_t<5>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
+    case 6: return launch_tsmm_t<6>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
+    case 7: return launch_tsmm_t<7>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
+    default: return launch_tsmm_t<8>(layout, ncells, K, N, l.n0, l.k0, l.K, d_in, d_phi, d_out, s);
     }
-  }
-  return WF_OK;
+  });
 }
