@@ -16,7 +16,9 @@
  *     scatter.cu:43; the caller zeroes y, LinearGLL.hpp:173).
  *   - stream is a hipStream_t passed as void* (NULL = default stream); all
  *     device work is stream-ordered and asynchronous, nothing synchronises
- *     except wf_sync and the setup calls that read host memory.
+ *     except wf_sync, the two calls that hand results to the host (wf_comm_barrier,
+ *     wf_cg: both synchronise `stream`) and the setup calls that read host memory
+ *     (the create calls allocate and copy synchronously: keep them out of a step loop).
  *   - element-local tensor ordering l = i + n*(j + n*k), n = P+1, i along x (x FASTEST).
  *     This is the order of every per-dof / per-point array handed over: the tensor side
  *     of h_perm, h_dofmap when h_perm is NULL, the point index q of h_G [c][q][3][3] and
@@ -705,7 +707,9 @@ int wf_op_apply_overlapped(wf_op* op, wf_updater* u, double* d_x, double* d_y, v
  * accumulated to the owners after every matvec, and the reductions run over owned
  * entries with one scalar all-reduce each (the MPI_Allreduce of cg.hpp:15-24).
  * The textbook algorithm is implemented, not the reference loop's arithmetic
- * (update_rev(p), nrm2 used as a squared norm, axpy(1,p,r): cg.hpp:84,59,117). */
+ * (update_rev(p), nrm2 used as a squared norm, axpy(1,p,r): cg.hpp:84,59,117).
+ * Synchronises `stream`: the stopping test reads the residual on the host every
+ * iteration, and iterations / rel_residual are host values on return. */
 typedef int (*wf_matvec_fn)(void* user, const double* d_v, double* d_y, void* stream);
 typedef struct {
   int64_t n;              /* local vector length (owned + ghost)                  */

@@ -63,7 +63,6 @@ class LinearGLLOpt:
     #: rk4_fused: the stage kernel leaves the next right-hand side's boundary term in b (wf_rk4_stage_bc).  False keeps
     #: the boundary term a launch of its own after each stage kernel, for comparison (tools/ab_rk4_boundary.py).
     fold_boundary = True
-    _bc = None   # la.BoundaryPlan of the fused loops (_boundary_plan)
     _rec_T = None   # (receivers, their transpose as Sources) of misfit_gradient
 
     def __init__(self, V, degreeOfBasis: int, speedOfSound: float, sourceFrequency: float,
@@ -136,6 +135,9 @@ class LinearGLLOpt:
                 i1, m1 = owned_boundary_set(self.updater, V, i1, m1, self.device)
                 i2, m2 = owned_boundary_set(self.updater, V, i2, m2, self.device)
         td = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(self.device, dtype=dt)
+        # the same sets as the fused passes read them.  Built here and not on a loop's first call: wf_boundary_create
+        # allocates and copies synchronously, and the first loop queued behind other work would wait for that work
+        self._bc = la.BoundaryPlan(N, i1, m1, i2, m2)
         self.idx1, self.mG1 = td(i1, torch.int32), td(m1, torch.float64)
         self.idx2, self.mG2 = td(i2, torch.int32), td(m2, torch.float64)
         # LinearGLL.hpp:120-127; tuning: the stiffness operator's make_tuning dict, e.g. {"geometry": "per_cell"}
@@ -215,10 +217,7 @@ class LinearGLLOpt:
             self.updater.scatter_rev(b)
 
     def _boundary_plan(self):
-        """The boundary sets as the fused passes read them (la.BoundaryPlan), built on first use."""
-        if self._bc is None:
-            self._bc = la.BoundaryPlan(self.b.numel(), self.idx1.cpu().numpy(), self.mG1.cpu().numpy(), self.idx2.cpu().numpy(),
-                                       self.mG2.cpu().numpy())
+        """The boundary sets as the fused passes read them (la.BoundaryPlan), built by the constructor."""
         return self._bc
 
     def f0(self, t, u, v, result):
