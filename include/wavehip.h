@@ -896,6 +896,80 @@ int wf_leapfrog_correlate(int64_t n, const double* d_lam, const double* d_up, co
                           void* stream);
 int wf_sources_add_values(const wf_sources* src, const double* d_values, double scale, double* d_b, void* stream);
 
+/* ---- the time loops of the wave model (csrc/wave_source.h, csrc/wave_loops.cpp; host code over the entries above) ----
+ * The one copy of rk4_fused and leapfrog: LinearGLLOpt of wave_fenics_amd/linear_gll.py and of wavehip_linear_gll.hpp
+ * both call these.
+ *
+ * wf_wave_source: the plane source on Gamma_1 (LinearGLL.hpp:153-162).  c0_squared is the caller's own c0^2: the Python
+ *   model forms c0 ** 2 (libm pow) and the C++ model c0 * c0, which differ in the last bit for about one speed in a
+ *   thousand, and each keeps its bits.  With `medium` the facet masses carry the admittance and c0 is not read.
+ *   wf_wave_window: the start-up ramp, 0.5 (1 - cos(freq0 pi t / alpha)) while t < period alpha, then 1.
+ *   wf_wave_g: g(t) = window p0 w0 / c0 cos(w0 t), the Neumann datum without a medium.
+ *   wf_wave_s1, wf_wave_s1_left_to_right: the coefficient of the Gamma_1 term in its two associations (wave_source.h);
+ *   wf_wave_s2: the coefficient of the Gamma_2 term, -c0, or -1 with a medium.
+ *
+ * wf_wave_desc: what a loop works on.  The right-hand side b += K x is `rhs` when given (accumulate semantics, every
+ *   launch on the stream it is handed), else the operator: wf_op_apply_overlapped(op, updater) when `overlapped`, else
+ *   wf_updater_fwd(x) (with an updater), wf_op_apply, wf_updater_rev(b).  d_work points to wf_wave_work_vectors(scheme)
+ *   device vectors of n doubles of the caller's, seven for WF_WAVE_RK4_FUSED and three for WF_WAVE_LEAPFROG, distinct
+ *   from each other and from every other vector of the call.  Their contents on entry do not matter.
+ *   With receivers, row k of d_traces [trace_rows][npoints] receives u after step k (row 0: at t0) by wf_points_sample;
+ *   h_times[k] (host, optional, with or without receivers) receives the time of that row.
+ *
+ * wf_wave_rk4_fused: RK4 (LinearGLL.hpp:198-287) from t0 while t < tf, the last step shortened to end at tf, with the
+ *   vector algebra between two applies in one pass: per stage rhs, wf_rk4_stage_bc (fold_boundary; else wf_rk4_stage
+ *   and wf_boundary_apply_plan), wf_sources_add.  s1 is wf_wave_s1_left_to_right at t + c_i dt.
+ * wf_wave_leapfrog: central differences with a constant step (the last one is not shortened): a start-up apply for
+ *   u^{-1}, per step rhs, wf_sources_add, wf_leapfrog_step_bc, and one finishing apply for the central velocity.  s1 is
+ *   wf_wave_s1.  before_step (optional) is called before step k = 0, 1, ... with the time and the two states the step
+ *   reads; d_a0 holds the start-up acceleration b / m at k = 0 only.  The loop's launches do not depend on it.
+ * Both read the state d_u, d_v on entry and leave the result there; the forward ghost update of the result is the
+ *   caller's.  max_steps < 0: no limit; otherwise the loop ends after the step that makes steps >= max_steps.  t_end and
+ *   steps (host, optional) receive the time reached and the steps taken.  All launches go to `stream`; nothing is
+ *   allocated, freed or synchronised.  Refused before the first launch (WF_ERR_INVALID): a null descriptor, state, work,
+ *   m, b or plan, n < 0, neither op nor rhs, overlapped without an updater, receivers without d_traces, receivers or
+ *   h_times with trace_rows < steps + 1, dt <= 0.
+ * wf_wave_step_count: the steps a loop will take, by the loop's own t += dt accumulation (host only). */
+typedef struct {
+  double c0, c0_squared, p0, w0, freq0, alpha, period;
+  int medium;
+} wf_wave_source;
+double wf_wave_window(const wf_wave_source* p, double t);
+double wf_wave_g(const wf_wave_source* p, double t);
+double wf_wave_s1(const wf_wave_source* p, double t);
+double wf_wave_s1_left_to_right(const wf_wave_source* p, double t);
+double wf_wave_s2(const wf_wave_source* p);
+
+enum { WF_WAVE_RK4_FUSED = 0, WF_WAVE_LEAPFROG = 1 };
+typedef int (*wf_wave_rhs_fn)(void* user, double* d_x, double* d_b, void* stream);
+typedef int (*wf_wave_step_fn)(void* user, int64_t step, double t, const double* d_u_prev, const double* d_u, const double* d_a0,
+                               void* stream);
+typedef struct {
+  int64_t n;                     /* local vector length (owned + ghost)                                  */
+  const double* d_m;             /* the lumped mass                                                      */
+  double* d_b;                   /* the right-hand side vector                                           */
+  const wf_boundary* bc;
+  wf_wave_source source;
+  int fold_boundary;             /* rk4_fused: the stage kernel leaves the next boundary term in b       */
+  wf_op* op;                     /* K; used when rhs is NULL                                             */
+  wf_updater* updater;           /* NULL on one rank                                                     */
+  int overlapped;                /* wf_op_apply_overlapped (the operator is split)                       */
+  wf_wave_rhs_fn rhs;            /* or a callback, b += K x with its ghost exchange                      */
+  void* rhs_user;
+  const wf_sources* sources;     /* optional                                                             */
+  const wf_points* receivers;    /* optional                                                             */
+  double* d_traces;
+  double* h_times;               /* optional, host: the time of every row, [trace_rows]                  */
+  int64_t trace_rows;
+  double* const* d_work;         /* [wf_wave_work_vectors(scheme)] vectors of n doubles                  */
+} wf_wave_desc;
+int wf_wave_work_vectors(int scheme);
+int64_t wf_wave_step_count(int scheme, double t0, double tf, double dt, int64_t max_steps);
+int wf_wave_rk4_fused(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
+                      double* t_end, int64_t* steps, void* stream);
+int wf_wave_leapfrog(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
+                     wf_wave_step_fn before_step, void* before_step_user, double* t_end, int64_t* steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

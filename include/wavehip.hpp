@@ -636,19 +636,35 @@ class Receivers {
 public:
   Receivers(const Space& V, const std::vector<std::array<double, 3>>& xyz) : _pts(V, xyz) {}
   int size() const { return _pts.size(); }
+  const wf_points* points() const { return _pts.handle(); }
   void sample(const double* d_x, double* d_out, void* stream = nullptr) const { check(wf_points_sample(_pts.handle(), d_x, d_out, stream)); }
-  void record(const double* d_x, double t)
+  /// Room for `rows` more rows and the device pointer of the next one, for a writer that fills them itself (the time
+  /// loops of the library; advance() then counts them).  Without receivers there is no buffer: nullptr.
+  double* reserve(std::size_t rows)
   {
     const std::size_t R = (std::size_t)size();
-    if (R && (!_buf || (_rows + 1) * R > _buf->size())) {   // 64 rows at first, then twice as many
-      auto grown = std::make_unique<array<double>>(_buf ? 2 * _buf->size() : 64 * R);
+    if (!R) return nullptr;
+    std::size_t need = _buf ? _buf->size() : 64 * R;   // 64 rows at first, then twice as many
+    while (need < (_rows + rows) * R) need *= 2;
+    if (!_buf || need > _buf->size()) {
+      auto grown = std::make_unique<array<double>>(need);
       if (_buf && _rows) check(wf_copy((std::int64_t)(_rows * R), _buf->data(), grown->data(), nullptr));
       check(wf_sync(nullptr));
       _buf = std::move(grown);
     }
-    if (R) sample(d_x, _buf->data() + _rows * R);   // without receivers only the times are kept
-    ++_rows;
-    _times.push_back(t);
+    return _buf->data() + _rows * R;
+  }
+  /// count `n` rows written behind reserve(), with their times
+  void advance(const double* times, std::size_t n)
+  {
+    _rows += n;
+    _times.insert(_times.end(), times, times + n);
+  }
+  void record(const double* d_x, double t)
+  {
+    double* row = reserve(1);
+    if (row) sample(d_x, row);   // without receivers only the times are kept
+    advance(&t, 1);
   }
   std::size_t rows() const { return _rows; }
   const std::vector<double>& times() const { return _times; }

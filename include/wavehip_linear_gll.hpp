@@ -44,14 +44,13 @@ protected:
   double w0_;     // angular frequency (rad/s)
   double T_;      // period (s)
   double alpha_;
-  double window_ = 0.0;
 
   std::int64_t N_;  // vector length (owned + ghost), size_local on one rank
   std::unique_ptr<array<double>> m, b;
   std::unique_ptr<array<std::int32_t>> idx1, idx2;
   std::unique_ptr<array<double>> mG1, mG2;
   std::unique_ptr<detail::OpBase> stiff_op;
-  wf_boundary* bc_ = nullptr;                  // boundary plan of the fused loop (created on first use)
+  wf_boundary* bc_ = nullptr;                  // the boundary sets as the fused passes read them (setup)
   VectorUpdater<double>* updater_ = nullptr;   // nullptr on one rank
   bool split_ = false;                         // interior / interface overlap available
   const Sources* sources_ = nullptr;           // point sources added to every right-hand side (set_sources)
@@ -65,32 +64,29 @@ protected:
     if (receivers_) receivers_->record(u.data(), t);
   }
 
-  double source(double t)
+  /// the plane source as the library evaluates it (csrc/wave_source.h); c0 * c0 is this front end's own c0^2
+  wf_wave_source wave() const { return wf_wave_source{c0_, c0_ * c0_, p0_, w0_, freq0_, alpha_, T_, 0}; }
+  /// g(t) of LinearGLL.hpp:153-162
+  double source(double t) const
   {
-    // LinearGLL.hpp:153-162
-    if (t < T_ * alpha_)
-      window_ = 0.5 * (1.0 - std::cos(freq0_ * M_PI * t / alpha_));
-    else
-      window_ = 1.0;
-    return window_ * p0_ * w0_ / c0_ * std::cos(w0_ * t);
+    const wf_wave_source w = wave();
+    return wf_wave_g(&w, t);
   }
   /// the two scalars of the boundary term b[idx1] += s1 mG1, b[idx2] += s2 mG2 v (LinearGLL.hpp:175) at time t
-  double s1(double t) { return c0_ * c0_ * source(t); }
-  double s2() const { return -c0_; }
+  double s1(double t) const
+  {
+    const wf_wave_source w = wave();
+    return wf_wave_s1(&w, t);
+  }
+  double s2() const
+  {
+    const wf_wave_source w = wave();
+    return wf_wave_s2(&w);
+  }
   void boundary(double t, const double* v)
   {
     check(wf_boundary_apply((std::int32_t)idx1->size(), idx1->data(), mG1->data(), s1(t), (std::int32_t)idx2->size(), idx2->data(),
                             mG2->data(), s2(), v, b->data(), nullptr));
-  }
-  /// the boundary sets as the fused passes read them, created on first use
-  wf_boundary* plan()
-  {
-    if (!bc_) {
-      const auto i1 = idx1->copy_to_host(), i2 = idx2->copy_to_host();
-      const auto a1 = mG1->copy_to_host(), a2 = mG2->copy_to_host();
-      check(wf_boundary_create(N_, (std::int32_t)i1.size(), i1.data(), a1.data(), (std::int32_t)i2.size(), i2.data(), a2.data(), &bc_));
-    }
-    return bc_;
   }
   /// b += K u (+ ghost exchange on a partitioned mesh); b is zero on entry
   void stiffness(double* u)
@@ -123,7 +119,8 @@ protected:
   }
   /// What both constructors end with, stiff_op in place: the vectors, m = M 1 with scatter_rev(add) (LinearGLL.hpp:102-110;
   /// the forward update keeps the ghost entries of m consistent: b / m runs over the whole array), the boundary sets on
-  /// the device and the first stiffness apply (LinearGLL.hpp:120-127).
+  /// the device with their plan for the fused passes (built here from the host sets, not on a loop's first call:
+  /// wf_boundary_create allocates and copies synchronously) and the first stiffness apply (LinearGLL.hpp:120-127).
   void setup(detail::OpBase&& mass, const BoundarySet& gamma1, const BoundarySet& gamma2)
   {
     auto filled = [&](double value) {
@@ -146,6 +143,8 @@ protected:
     mG1 = upload(gamma1.second);
     idx2 = upload(gamma2.first);
     mG2 = upload(gamma2.second);
+    check(wf_boundary_create(N_, (std::int32_t)gamma1.first.size(), gamma1.first.data(), gamma1.second.data(),
+                             (std::int32_t)gamma2.first.size(), gamma2.first.data(), gamma2.second.data(), &bc_));
     stiffness(u_n->data());
   }
 
@@ -257,7 +256,8 @@ public:
   }
 
   /// Runge-Kutta 4th order solver (LinearGLL.hpp:198-287), the reference's sequence of
-  /// vector operations; returns the number of steps taken
+  /// vector operations; returns the number of steps taken.  rk4, f0 and f1 are the line-by-line transcription of
+  /// common/LinearGLL.hpp:141-287 and stay readable as such; the loops the product runs are the library's (below).
   int rk4(double& startTime, double& finalTime, double& timeStep)
   {
     double t = startTime, tf = finalTime, dt = timeStep;
@@ -303,56 +303,12 @@ public:
   /// into ONE pass (wf_rk4_stage: divide, f0, both solution updates, the next stage's
   /// un / vn and the zeroing of b) and the stage-0 copies removed by pointer rotation.
   /// Same arithmetic expressions as rk4(); 72-96 B/dof of vector traffic per stage
-  /// instead of 208.
-  int rk4_fused(double& startTime, double& finalTime, double& timeStep)
+  /// instead of 208.  The boundary term of each right-hand side is left in b by the stage kernel in front of it
+  /// (wf_rk4_stage_bc), the first one by a plain launch: a stage is two launches, stiffness + vector algebra.
+  /// The loop is wf_wave_rk4_fused, the one the Python model runs.  max_steps < 0: no limit.
+  int rk4_fused(double& startTime, double& finalTime, double& timeStep, std::int64_t max_steps = -1)
   {
-    double t = startTime, tf = finalTime, dt = timeStep;
-    int step = 0;
-    auto mk = [&]() { return std::make_unique<array<double>>((std::size_t)N_); };
-    auto u0 = mk(), v0 = mk(), u_ = mk(), v_ = mk(), un = mk(), vn_a = mk(), vn_b = mk();
-    kernels::copy(*u_n, *u0);
-    kernels::copy(*v_n, *v0);
-    const double a_runge[4] = {0.0, 0.5, 0.5, 1.0};
-    const double b_runge[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
-    const double c_runge[4] = {0.0, 0.5, 0.5, 1.0};
-    // The boundary term of each right-hand side is left in b by the stage kernel in front of it
-    // (wf_rk4_stage_bc), the first one by a plain launch: a stage is two launches, stiffness + vector algebra.
-    check(wf_fill(N_, 0.0, b->data(), nullptr));
-    check(wf_boundary_apply_plan(plan(), s1(t), s2(), v0->data(), b->data(), nullptr));
-    add_sources(t);
-    record(*u0, t);
-    while (t < tf) {
-      dt = std::min(dt, tf - t);
-      double* x_u = u0->data();           // stage 0 reads u0 / v0 directly (a_0 = 0)
-      double* x_v = v0->data();
-      double* vn_next = vn_a->data();
-      for (int i = 0; i < 4; ++i) {
-        stiffness(x_u);
-        const double* ur = i == 0 ? u0->data() : u_->data();
-        const double* vr = i == 0 ? v0->data() : v_->data();
-        const int has_next = i < 3;
-        // time of the next right-hand side: the next stage, or stage 0 of the next step
-        const double s1_next = s1(has_next ? t + c_runge[i + 1] * dt : t + dt);
-        check(wf_rk4_stage_bc(N_, dt * b_runge[i], has_next ? dt * a_runge[i + 1] : 0.0, has_next, b->data(), m->data(), x_v,
-                              ur, vr, u_->data(), v_->data(), u0->data(), v0->data(), un->data(), vn_next, plan(), s1_next,
-                              s2(), nullptr));
-        add_sources(has_next ? t + c_runge[i + 1] * dt : t + dt);
-        if (has_next) {
-          x_u = un->data();
-          x_v = vn_next;
-          vn_next = vn_next == vn_a->data() ? vn_b->data() : vn_a->data();
-        }
-      }
-      std::swap(u0, u_);   // the new solution is the next step's u0
-      std::swap(v0, v_);
-      t += dt;
-      step += 1;
-      record(*u0, t);
-    }
-    kernels::copy(*u0, *u_n);
-    kernels::copy(*v0, *v_n);
-    finish();
-    return step;
+    return run(WF_WAVE_RK4_FUSED, startTime, finalTime, timeStep, max_steps);
   }
 
   /// Second-order central-difference (leapfrog, explicit Newmark beta = 0, gamma = 1/2) integration from the state
@@ -362,42 +318,52 @@ public:
   /// a^0 = (K u^0 + boundary term) / m; finish: one more apply and update into a scratch vector for the central
   /// velocity v_n at the final time, u not advanced, so that a split run equals a continuous one.  The step is constant:
   /// steps are counted while t < finalTime and the last one is not shortened.  Returns the number of steps taken.
-  int leapfrog(double& startTime, double& finalTime, double& timeStep)
+  /// The loop is wf_wave_leapfrog, the one the Python model runs.
+  int leapfrog(double& startTime, double& finalTime, double& timeStep, std::int64_t max_steps = -1)
   {
-    double t = startTime;
-    const double tf = finalTime, dt = timeStep;
-    int step = 0;
-    auto mk = [&]() { return std::make_unique<array<double>>((std::size_t)N_); };
-    auto u = mk(), w = mk(), scratch = mk();   // u^n, u^{n-1} (overwritten by u^{n+1}), a^0 / the finishing update
-    kernels::copy(*u_n, *u);
-    check(wf_fill(N_, 0.0, b->data(), nullptr));
-    stiffness(u->data());
-    check(wf_boundary_apply_plan(plan(), s1(t), s2(), v_n->data(), b->data(), nullptr));
-    add_sources(t);
-    record(*u, t);
-    check(wf_pointwise_div(N_, b->data(), m->data(), scratch->data(), nullptr));
-    kernels::axpy(*w, -dt, *v_n, *u, N_);
-    kernels::axpy(*w, 0.5 * dt * dt, *scratch, *w, N_);
-    check(wf_fill(N_, 0.0, b->data(), nullptr));
-    while (t < tf) {
-      stiffness(u->data());
-      add_sources(t);
-      check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), w->data(), nullptr, plan(), s1(t), s2(), nullptr));
-      std::swap(u, w);
-      t += dt;
-      step += 1;
-      record(*u, t);
-    }
-    stiffness(u->data());
-    add_sources(t);
-    check(wf_leapfrog_step_bc(N_, dt, b->data(), m->data(), u->data(), w->data(), scratch->data(), v_n->data(), plan(), s1(t),
-                              s2(), nullptr));
-    kernels::copy(*u, *u_n);
-    finish();
-    return step;
+    return run(WF_WAVE_LEAPFROG, startTime, finalTime, timeStep, max_steps);
   }
 
 protected:
+  /// one call of a loop of the library on (u_n, v_n): the descriptor, the work vectors and the trace rows
+  int run(int scheme, double t0, double tf, double dt, std::int64_t max_steps)
+  {
+    wf_wave_desc d{};
+    d.n = N_;
+    d.d_m = m->data();
+    d.d_b = b->data();
+    d.bc = bc_;
+    d.source = wave();
+    d.fold_boundary = 1;
+    d.op = stiff_op->handle();
+    d.updater = updater_ ? updater_->handle() : nullptr;
+    d.overlapped = split_;
+    d.sources = sources_ ? sources_->handle() : nullptr;
+    std::vector<double> times;
+    if (receivers_) {
+      times.resize((std::size_t)wf_wave_step_count(scheme, t0, tf, dt, max_steps) + 1);
+      d.h_times = times.data();
+      d.trace_rows = (std::int64_t)times.size();
+      d.d_traces = receivers_->reserve(times.size());
+      if (d.d_traces) d.receivers = receivers_->points();
+    }
+    std::vector<std::unique_ptr<array<double>>> work;
+    std::vector<double*> work_ptr;
+    for (int k = 0; k < wf_wave_work_vectors(scheme); ++k) {
+      work.push_back(std::make_unique<array<double>>((std::size_t)N_));
+      work_ptr.push_back(work.back()->data());
+    }
+    d.d_work = work_ptr.data();
+    std::int64_t steps = 0;
+    if (scheme == WF_WAVE_LEAPFROG)
+      check(wf_wave_leapfrog(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, nullptr, nullptr, &steps, nullptr));
+    else
+      check(wf_wave_rk4_fused(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, &steps, nullptr));
+    if (receivers_) receivers_->advance(times.data(), (std::size_t)steps + 1);
+    finish();   // synchronises: the work vectors go out of scope behind it
+    return (int)steps;
+  }
+
   void finish()
   {
     if (updater_) {   // LinearGLL.hpp:284-285

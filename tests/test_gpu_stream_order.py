@@ -68,7 +68,10 @@ TOL_FORM = 1e-13      # of max|y|: tests/test_gpu_owner_update.py
 # so the second column's third segment is an interior item.
 PARTITION = dict(n=(9, 2, 5), periodic=(True, False, True))
 REFERENCED = {"wf_tsmm": "tests/test_gpu_tsmm_paths.py (every plan path behind queued work on a side stream)",
-              "wf_cg": "tests/test_gpu_cg_iteration.py::test_cg_on_side_stream; the row `cg-synchronises` here"}
+              "wf_cg": "tests/test_gpu_cg_iteration.py::test_cg_on_side_stream; the row `cg-synchronises` here",
+              "wf_wave_rk4_fused": "tests/test_gpu_stream_models.py (rk4_fused behind queued work, one rank and a z-periodic partition)",
+              "wf_wave_leapfrog": "tests/test_gpu_stream_models.py (leapfrog and misfit_gradient behind queued work, one rank and a "
+                                  "z-periodic partition)"}
 ROWS = []             # (id, entries, builder(gpu, s, rng, request) -> case)
 
 

@@ -115,6 +115,27 @@ class CGDesc(ctypes.Structure):
     ]
 
 
+class WaveSource(ctypes.Structure):
+    """wf_wave_source"""
+    _fields_ = [("c0", c_double), ("c0_squared", c_double), ("p0", c_double), ("w0", c_double), ("freq0", c_double),
+                ("alpha", c_double), ("period", c_double), ("medium", c_int)]
+
+
+WAVE_RHS_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, c_void_p)
+WAVE_STEP_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p)
+
+
+class WaveDesc(ctypes.Structure):
+    """wf_wave_desc"""
+    _fields_ = [
+        ("n", c_int64), ("d_m", c_void_p), ("d_b", c_void_p), ("bc", c_void_p), ("source", WaveSource),
+        ("fold_boundary", c_int), ("op", c_void_p), ("updater", c_void_p), ("overlapped", c_int),
+        ("rhs", WAVE_RHS_FN), ("rhs_user", c_void_p), ("sources", c_void_p), ("receivers", c_void_p),
+        ("d_traces", c_void_p), ("h_times", POINTER(c_double)), ("trace_rows", c_int64), ("d_work", POINTER(c_void_p)),
+    ]
+
+
+WF_WAVE_RK4_FUSED, WF_WAVE_LEAPFROG = 0, 1
 WF_QUAD_GLL, WF_QUAD_GAUSS_JACOBI = 0, 1
 WF_VARIANT_GLL_WARPED, WF_VARIANT_EQUISPACED = 0, 1
 WF_MAX_QUAD_POINTS = 16
@@ -259,6 +280,17 @@ SIGNATURES = {
     "wf_cell_form_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p]),
     "wf_cell_form_info": (c_int, [c_void_p, POINTER(CellFormInfo)]),
     "wf_cell_form_destroy": (c_int, [c_void_p]),
+    "wf_wave_window": (c_double, [POINTER(WaveSource), c_double]),
+    "wf_wave_g": (c_double, [POINTER(WaveSource), c_double]),
+    "wf_wave_s1": (c_double, [POINTER(WaveSource), c_double]),
+    "wf_wave_s1_left_to_right": (c_double, [POINTER(WaveSource), c_double]),
+    "wf_wave_s2": (c_double, [POINTER(WaveSource)]),
+    "wf_wave_work_vectors": (c_int, [c_int]),
+    "wf_wave_step_count": (c_int64, [c_int, c_double, c_double, c_double, c_int64]),
+    "wf_wave_rk4_fused": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p,
+                                  POINTER(c_double), POINTER(c_int64), c_void_p]),
+    "wf_wave_leapfrog": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p, WAVE_STEP_FN,
+                                 c_void_p, POINTER(c_double), POINTER(c_int64), c_void_p]),
 }
 
 _LIB = None

@@ -31,11 +31,11 @@ import numpy as np
 import torch
 
 from . import la
-from ._lib import _dp, _ip, check, lib
+from ._lib import WAVE_RHS_FN, WAVE_STEP_FN, WF_WAVE_LEAPFROG, WF_WAVE_RK4_FUSED, WaveDesc, WaveSource, _dp, _ip, check, lib
 from .box import _int3
 from .distributed import overlapped_apply
 from .mesh_io import cfl_time_step  # noqa: F401  (demo/cpu_planar3d/main.cpp:48-66: one function for box and file meshes)
-from .operators import CellForm, MassOperatorLumped, StiffnessOperator
+from .operators import CellForm, MassOperatorLumped, StiffnessOperator, _ptr, _stream
 
 
 def facet_lumped_mass(V, tag_of_face, tag: int, cell_weight=None):
@@ -92,6 +92,9 @@ class LinearGLLOpt:
         self.w0_ = 2.0 * math.pi * self.freq0_
         self.T_ = 1.0 / self.freq0_
         self.alpha_ = 4.0
+        # the plane source as the library evaluates it (csrc/wave_source.h); c0 ** 2 is this front end's own c0^2
+        c0 = 0.0 if medium is not None else float(self.c0_)
+        self._wave = WaveSource(c0, c0 ** 2, self.p0_, self.w0_, self.freq0_, self.alpha_, self.T_, int(medium is not None))
         self.updater = updater
         self._structured = structured
         self._cell_forms = None   # (stiffness form, lumped-mass form), built on first use (cell_forms)
@@ -169,40 +172,32 @@ class LinearGLLOpt:
         """The time of every row of receivers.traces"""
         return [] if self.receivers is None else self.receivers.times
 
-    # ---- the pieces every time loop shares ----
+    # ---- the pieces every time loop shares: the plane source is the library's (csrc/wave_source.h) ----
     def _window(self, t: float) -> float:
         """The source's start-up ramp over alpha_ periods (LinearGLL.hpp:153-159)."""
-        if t < self.T_ * self.alpha_:
-            return 0.5 * (1.0 - math.cos(self.freq0_ * math.pi * t / self.alpha_))
-        return 1.0
+        return lib().wf_wave_window(ctypes.byref(self._wave), t)
 
-    def _g(self, window: float, t: float) -> float:
+    def _g(self, t: float) -> float:
         """g(t) of LinearGLL.hpp:153-162 (no medium: with one g = s1 / c differs from cell to cell and only s1 exists)."""
-        return window * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
+        return lib().wf_wave_g(ctypes.byref(self._wave), t)
 
     @property
     def _s2(self) -> float:
         """Coefficient of the Gamma_2 term: -c0 (LinearGLL.hpp:175); -1 with a medium (admittance-weighted facet masses)."""
-        return -self.c0_ if self.medium is None else -1.0
+        return lib().wf_wave_s2(ctypes.byref(self._wave))
 
-    def _boundary_scalars(self, window: float, t: float):
+    def _boundary_scalars(self, t: float):
         """(s1, s2) of the boundary term b[idx1] += s1 mG1, b[idx2] += s2 mG2 v at time t: c0^2 g(t) and -c0
         (LinearGLL.hpp:153-162,175); with a medium window p0 w0 cos(w0 t) and -1 on admittance-weighted facet masses."""
-        if self.medium is None:
-            return self.c0_ ** 2 * self._g(window, t), self._s2
-        return window * self.p0_ * self.w0_ * math.cos(self.w0_ * t), self._s2
+        return self._s1(t), self._s2
 
     def _s1(self, t: float) -> float:
         """Coefficient of the Gamma_1 term at time t."""
-        return self._boundary_scalars(self._window(t), t)[0]
+        return lib().wf_wave_s1(ctypes.byref(self._wave), t)
 
     def _s1_fused(self, t: float) -> float:
-        """_s1(t) as rk4_fused rounds it.  Without a medium that loop has always taken the product from left to right,
-        ((c0^2 window) p0 w0 / c0) cos(w0 t), where _boundary_scalars forms c0^2 (window p0 w0 / c0 cos(w0 t)): equal up to
-        the last bit only.  Both spellings stay, so that neither loop's results change."""
-        if self.medium is not None:
-            return self._s1(t)
-        return self.c0_ ** 2 * self._window(t) * self.p0_ * self.w0_ / self.c0_ * math.cos(self.w0_ * t)
+        """_s1(t) as rk4_fused rounds it: the product taken from left to right (wave_source.h says why both stay)."""
+        return lib().wf_wave_s1_left_to_right(ctypes.byref(self._wave), t)
 
     def _rhs(self, x, b):
         """b += K x with the ghost exchange of a partitioned mesh around it: forward halo of x, reverse halo of b."""
@@ -216,18 +211,14 @@ class LinearGLLOpt:
         if self.updater is not None:
             self.updater.scatter_rev(b)
 
-    def _boundary_plan(self):
-        """The boundary sets as the fused passes read them (la.BoundaryPlan), built by the constructor."""
-        return self._bc
-
     def f0(self, t, u, v, result):
         la.copy(v, result)                                   # LinearGLL.hpp:141-144
 
     def f1(self, t, u, v, result):
         # LinearGLL.hpp:151-192
         self.window_ = self._window(t)
-        self.g_ = self._g(self.window_, t) if self.medium is None else None
-        s1, s2 = self._boundary_scalars(self.window_, t)
+        self.g_ = self._g(t) if self.medium is None else None
+        s1, s2 = self._boundary_scalars(t)
         if self._split:
             # same operations as below, reordered so that the cells that read no ghost
             # value run while the halo of u is in flight (update_fwd_begin/_end,
@@ -256,7 +247,8 @@ class LinearGLLOpt:
         la.pointwise_div(self.b, self.m, result)
 
     def rk4(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
-        # LinearGLL.hpp:198-287
+        # LinearGLL.hpp:198-287.  rk4, f0 and f1 are the line-by-line transcription of common/LinearGLL.hpp:141-287 and stay
+        # readable as such, here and in wavehip_linear_gll.hpp; the loops the product runs are the library's (_run)
         t, tf, dt = startTime, finalTime, timeStep
         step = 0
         nl = self.size_local
@@ -307,65 +299,8 @@ class LinearGLLOpt:
         of the NEXT right-hand side is left in b by the stage kernel (instead of zeros), so a
         stage is two launches: stiffness apply, fused vector algebra.  Same arithmetic
         expressions as the unfused loop (b receives the boundary term before the stiffness
-        contributions instead of after them)."""
-        t, tf, dt = startTime, finalTime, timeStep
-        step = 0
-        new = lambda: torch.zeros_like(self.u_n)
-        u0, v0 = self.u_n.clone(), self.v_n.clone()      # solution at the start of the step
-        u_, v_ = new(), new()                              # running solution of the step
-        un, vn_a, vn_b = new(), new(), new()
-        b, m = self.b, self.m
-        a_runge = [0.0, 0.5, 0.5, 1.0]
-        b_runge = [1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0]
-        c_runge = [0.0, 0.5, 0.5, 1.0]
-        bc, s1, s2, rhs, fold = self._boundary_plan(), self._s1_fused, self._s2, self._rhs, self.fold_boundary
-        la.fill(b, 0.0)
-        bc.apply(s1(t), s2, v0, b)           # boundary term of the first right-hand side; the stage kernels leave the others
-        src, rec = self.sources, self.receivers
-        if src is not None:
-            src.add(t, b)                    # likewise the point sources: a launch after each stage kernel leaves the others
-        if rec is not None:
-            rec.record(u0, t)
-        while t < tf:
-            dt = min(dt, tf - t)
-            # stage 0: un = u0, vn = v0 (a_0 = 0), read straight from u0 / v0
-            x_u, x_v = u0, v0
-            vn_next = vn_a
-            for i in range(4):
-                rhs(x_u, b)                  # b holds the boundary term of this right-hand side on entry
-                last = i == 3
-                ur, vr = (u0, v0) if i == 0 else (u_, v_)
-                if not last:
-                    la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], dt * a_runge[i + 1], u0, v0, un, vn_next,
-                                 bc=bc if fold else None, s1_next=s1(t + c_runge[i + 1] * dt), s2=s2)
-                    if not fold:
-                        bc.apply(s1(t + c_runge[i + 1] * dt), s2, vn_next, b)
-                    if src is not None:
-                        src.add(t + c_runge[i + 1] * dt, b)
-                    x_u, x_v = un, vn_next
-                    vn_next = vn_b if vn_next is vn_a else vn_a
-                else:
-                    # the next right-hand side is stage 0 of the next step: v = the updated solution, time t + dt
-                    # (after the last step b is left holding a boundary term nobody reads; f1 / rk4 zero b themselves)
-                    la.rk4_stage(b, m, x_v, ur, vr, u_, v_, dt * b_runge[i], bc=bc if fold else None, s1_next=s1(t + dt), s2=s2)
-                    if not fold:
-                        bc.apply(s1(t + dt), s2, v_, b)
-                    if src is not None:
-                        src.add(t + dt, b)
-            u0, u_ = u_, u0          # the new solution becomes the next step's u0
-            v0, v_ = v_, v0
-            t += dt
-            step += 1
-            if rec is not None:
-                rec.record(u0, t)
-            if max_steps is not None and step >= max_steps:
-                break
-        la.copy(u0, self.u_n)
-        la.copy(v0, self.v_n)
-        if self.updater is not None:
-            self.updater.scatter_fwd(self.u_n)
-            self.updater.scatter_fwd(self.v_n)
-        return t, step
+        contributions instead of after them).  The loop itself is wf_wave_rk4_fused (csrc/wave_loops.cpp)."""
+        return self._run(WF_WAVE_RK4_FUSED, startTime, finalTime, timeStep, max_steps)
 
     def leapfrog(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
         """Second-order central-difference (leapfrog, explicit Newmark beta = 0, gamma = 1/2) integration of
@@ -380,57 +315,81 @@ class LinearGLLOpt:
         time, without advancing u -- so a run split in two equals the continuous run up to rounding.
 
         The step is constant: steps are counted by `while t < finalTime` and the last step is NOT shortened to land on
-        finalTime (a shortened step would break the two-level recurrence).  Returns (t, steps)."""
-        return self._leapfrog(startTime, finalTime, timeStep, max_steps)
+        finalTime (a shortened step would break the two-level recurrence).  Returns (t, steps).  The loop itself is
+        wf_wave_leapfrog (csrc/wave_loops.cpp)."""
+        return self._run(WF_WAVE_LEAPFROG, startTime, finalTime, timeStep, max_steps)
 
-    def _leapfrog(self, startTime, finalTime, timeStep, max_steps, keep=None):
-        """leapfrog(); keep(n, t, u_prev, u, a0) (misfit_gradient) is called before step n = 0, 1, ... with the time and the
-        two states the step reads (a0: the vector holding the start-up acceleration, valid at n = 0 only).  It may copy
-        them; the loop's own launches and their order do not depend on it."""
-        t, tf, dt = startTime, finalTime, timeStep
-        step = 0
-        b, m = self.b, self.m
-        u = self.u_n.clone()                       # u^n
-        w = torch.zeros_like(u)                    # u^{n-1}, overwritten in place by u^{n+1}
-        scratch = torch.zeros_like(u)
-        bc, s1, s2, rhs = self._boundary_plan(), self._s1, self._s2, self._rhs
-        # start-up: scratch = a^0, w = u^{-1}
-        la.fill(b, 0.0)
-        rhs(u, b)
-        bc.apply(s1(t), s2, self.v_n, b)
-        src, rec = self.sources, self.receivers
-        if src is not None:
-            src.add(t, b)
+    def _guarded(self, errors, body):
+        """body(*args) as a callback of the library (la.cg's trampoline): it runs under the stream the library hands over
+        and lets no exception cross the C boundary -- the exception waits in `errors` for _run to raise it."""
+        dev = self.device
+
+        def call(stream, *args):
+            try:
+                # torch.cuda.ExternalStream(0) is NOT the null stream on ROCm (it wraps a bogus handle)
+                st = torch.cuda.ExternalStream(stream, device=dev) if stream else torch.cuda.default_stream(dev)
+                with torch.cuda.stream(st):
+                    body(*args)
+                return 0
+            except Exception as e:   # noqa: BLE001
+                errors.append(e)
+                return -1
+        return call
+
+    def _run(self, scheme: int, t0: float, tf: float, dt: float, max_steps, keep=None, rhs=None, work=None):
+        """One call of wf_wave_rk4_fused / wf_wave_leapfrog on (u_n, v_n): the descriptor, the work vectors and the trace
+        rows are set up here, every launch is the library's.  keep(n, t, u_prev, u, a0) (leapfrog; misfit_gradient) is
+        called before step n = 0, 1, ... with the time and the two states the step reads (a0: the vector holding the
+        start-up acceleration, valid at n = 0 only).  It may copy them; the loop's own launches and their order do not
+        depend on it.  For tests: rhs(x, b), a right-hand side b += K x in place of the model's, and work, the work vectors
+        (wf_wave_work_vectors of them) in place of fresh ones."""
+        L, n, errors = lib(), self.u_n.numel(), []
+        vec = lambda p: la._tensor_from_ptr(p, n, self.device)   # noqa: E731
+        d = WaveDesc()
+        d.n, d.d_m, d.d_b, d.bc = n, _ptr(self.m), _ptr(self.b), self._bc._h
+        d.source, d.fold_boundary = self._wave, int(self.fold_boundary)
+        if rhs is None and (self.updater is None or self.updater.transport == "native"):
+            # the sequence of _rhs, in the library
+            d.op, d.overlapped = self.stiff_op._h, int(self._split)
+            if self.updater is not None and (self._split or self.updater.active):
+                d.updater = self.updater._h
+        else:   # the torch transport exchanges ghosts in Python: _rhs itself, as a callback
+            body = self._rhs if rhs is None else rhs
+            call = self._guarded(errors, lambda px, pb: body(vec(px), vec(pb)))
+            d.rhs = WAVE_RHS_FN(lambda user, px, pb, stream: call(stream, px, pb))
+        if self.sources is not None:
+            d.sources = self.sources._s
+        max_steps = -1 if max_steps is None else int(max_steps)
+        rec = self.receivers
         if rec is not None:
-            rec.record(u, t)
-        la.pointwise_div(b, m, scratch)
-        la.axpy(w, -dt, self.v_n, u)
-        la.axpy(w, 0.5 * dt * dt, scratch, w)
-        la.fill(b, 0.0)
-        while t < tf:
+            rows = L.wf_wave_step_count(scheme, t0, tf, dt, max_steps) + 1
+            times = (ctypes.c_double * rows)()
+            d.h_times, d.trace_rows = times, rows
+            if len(rec):
+                d.receivers, d.d_traces = rec._h, rec.reserve(rows, self.device)
+        if work is None:
+            work = [torch.empty_like(self.u_n) for _ in range(L.wf_wave_work_vectors(scheme))]
+        d.d_work = (ctypes.c_void_p * len(work))(*[_ptr(x) for x in work])
+        t_end, steps = ctypes.c_double(t0), ctypes.c_int64(0)
+        args = (ctypes.byref(d), t0, tf, dt, max_steps, _ptr(self.u_n), _ptr(self.v_n))
+        out = (ctypes.byref(t_end), ctypes.byref(steps), _stream(self.u_n))
+        if scheme == WF_WAVE_LEAPFROG:
+            step_fn = WAVE_STEP_FN()
             if keep is not None:
-                keep(step, t, w, u, scratch)
-            rhs(u, b)                              # b is zero on entry
-            if src is not None:
-                src.add(t, b)
-            la.leapfrog_step(b, m, u, w, w, dt, bc=bc, s1=s1(t), s2=s2)
-            u, w = w, u
-            t += dt
-            step += 1
-            if rec is not None:
-                rec.record(u, t)
-            if max_steps is not None and step >= max_steps:
-                break
-        # finish: the step after the last one, into scratch, for the central velocity at t
-        rhs(u, b)
-        if src is not None:
-            src.add(t, b)
-        la.leapfrog_step(b, m, u, w, scratch, dt, v=self.v_n, bc=bc, s1=s1(t), s2=s2)
-        la.copy(u, self.u_n)
+                call_keep = self._guarded(errors, lambda k, t, pw, pu, pa: keep(k, t, vec(pw), vec(pu), vec(pa)))
+                step_fn = WAVE_STEP_FN(lambda user, k, t, pw, pu, pa, stream: call_keep(stream, k, t, pw, pu, pa))
+            rc = L.wf_wave_leapfrog(*args, step_fn, None, *out)
+        else:
+            rc = L.wf_wave_rk4_fused(*args, *out)
+        if errors:
+            raise errors[0]
+        check(rc)
+        if rec is not None:
+            rec.advance(list(times)[:steps.value + 1])
         if self.updater is not None:
             self.updater.scatter_fwd(self.u_n)
             self.updater.scatter_fwd(self.v_n)
-        return t, step
+        return t_end.value, int(steps.value)
 
     def misfit_gradient(self, t0: float, tf: float, dt: float, observed, checkpoint_every: int | None = None,
                         max_steps: int | None = None):
@@ -477,12 +436,7 @@ class LinearGLLOpt:
             raise ValueError("LinearGLLOpt.misfit_gradient needs receivers=")
         if not dt > 0.0:
             raise ValueError("LinearGLLOpt.misfit_gradient: the time step must be positive")
-        N, t = 0, t0                                # the steps leapfrog will take
-        while t < tf:
-            t += dt
-            N += 1
-            if max_steps is not None and N >= max_steps:
-                break
+        N = lib().wf_wave_step_count(WF_WAVE_LEAPFROG, t0, tf, dt, -1 if max_steps is None else int(max_steps))   # the steps leapfrog will take
         R = len(rec)
         if tuple(observed.shape) != (N + 1, R):
             raise ValueError(f"LinearGLLOpt.misfit_gradient: observed is {tuple(observed.shape)}, the run records {(N + 1, R)}")
@@ -508,7 +462,7 @@ class LinearGLLOpt:
                 pairs.append(pair)
 
         row0 = rec._rows
-        t, steps = self._leapfrog(t0, tf, dt, max_steps, keep)
+        t, steps = self._run(WF_WAVE_LEAPFROG, t0, tf, dt, max_steps, keep)
         assert steps == N and len(pairs) == ncp
         resid = rec.traces[row0:row0 + N + 1] - observed
         J = 0.5 * dt * float((resid * resid).sum().item())
@@ -524,7 +478,7 @@ class LinearGLLOpt:
         if self._rec_T is None or self._rec_T[0] is not rec:
             self._rec_T = (rec, rec.transpose())
         RT = self._rec_T[1]
-        bc, s1, s2, rhs = self._boundary_plan(), self._s1, self._s2, self._rhs
+        bc, s1, s2, rhs = self._bc, self._s1, self._s2, self._rhs
         mu, mu_next, p = torch.zeros_like(self.u_n), torch.zeros_like(self.u_n), torch.zeros_like(self.u_n)
         bufs = [new() for _ in range(Sb)]
         for j in reversed(range(ncp)):

@@ -156,20 +156,34 @@ class Receivers(_Points):
         check(lib().wf_points_sample(self._h, _ptr(x), _ptr(out), _stream(x)))
         return out
 
-    def record(self, x, t: float | None = None):
-        """Append x at the receivers as one row of traces (time t, if given, to times)."""
+    def reserve(self, rows: int, device) -> int:
+        """Room for `rows` more rows -- the buffer doubles until they fit -- and the device pointer of the next row, for a
+        writer that fills them itself (the time loops of the library); advance() then counts them."""
         import torch
         R = len(self)
         if self._buf is None:
-            self._buf = torch.zeros(self._capacity * R, dtype=torch.float64, device=x.device)
-        elif self._rows * R >= self._buf.numel() and R:
-            grown = torch.zeros(2 * self._buf.numel(), dtype=torch.float64, device=x.device)
+            self._buf = torch.zeros(self._capacity * R, dtype=torch.float64, device=device)
+        size = self._buf.numel()
+        while size < (self._rows + rows) * R:
+            size *= 2
+        if size > self._buf.numel():
+            grown = torch.zeros(size, dtype=torch.float64, device=device)
             grown[:self._buf.numel()].copy_(self._buf)
             self._buf = grown
+        return self._buf.data_ptr() + self._rows * R * 8
+
+    def advance(self, times):
+        """Count the rows a writer filled behind reserve(), one per entry of times."""
+        self._rows += len(times)
+        self.times.extend(times)
+
+    def record(self, x, t: float | None = None):
+        """Append x at the receivers as one row of traces (time t, if given, to times)."""
+        R = len(self)
+        self.reserve(1, x.device)
         if R:
             self.sample(x, self._buf[self._rows * R:(self._rows + 1) * R])
-        self._rows += 1
-        self.times.append(t)
+        self.advance([t])
 
     @property
     def traces(self):
