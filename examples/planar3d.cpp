@@ -7,9 +7,9 @@
 // Gamma_1 = face x = 0 and Gamma_2 = every other face.
 //
 //   planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]]
-//            [--size N] [--degree P] [--cfl C] [--steps S] [--length L] [--dump FILE]
+//            [--size N] [--degree P] [--cfl C] [--steps S] [--length L] [--dump FILE] [--dump-mass FILE]
 //            [--periodic xyz] [--reference-order] [--markers] [--geometry auto|per_point|per_cell]
-//            [--scheme rk4|leapfrog] [--amplitude P0] [--source x,y,z,f] [--receiver x,y,z]... [--traces FILE]
+//            [--scheme rk4|leapfrog|leapfrog4] [--amplitude P0] [--source x,y,z,f] [--receiver x,y,z]... [--traces FILE]
 //
 // One process per GPU: with WORLD_SIZE > 1 in the environment (RANK, LOCAL_RANK,
 // MASTER_PORT as torchrun exports them) --size is the number of cells per edge PER
@@ -20,8 +20,10 @@
 // its own RCCL neighbour).  --reference-order runs LinearGLLOpt::rk4, the
 // reference's unfused sequence of vector operations, instead of rk4_fused.
 // --scheme leapfrog runs LinearGLLOpt::leapfrog, the second-order central-difference scheme (one stiffness apply per
-// step, constant step) instead of RK4; rk4 is the default.
-// --dump writes u_n then v_n of this rank (float64, local lattice order).
+// step, constant step) instead of RK4; --scheme leapfrog4 runs LinearGLLOpt::leapfrog4, the fourth-order modified-equation
+// scheme (two applies per step, constant step, stable to sqrt(3) times leapfrog's step); rk4 is the default.
+// --dump writes u_n then v_n of this rank (float64, local lattice order); --dump-mass the model's lumped mass (generated
+// box, one rank), for a comparison of two models bit for bit: the mass is assembled by atomics.
 // --amplitude sets the pressure amplitude of the plane source on Gamma_1 (60000 Pa; 0 silences it).
 // --source adds a point source s(t) delta(x - (x,y,z)), a Ricker wavelet of frequency f, unit amplitude and delay 1.5/f;
 // --receiver (repeatable) records u at a point at the start time and after every step; --traces writes the record as
@@ -41,10 +43,10 @@ int main(int argc, char* argv[])
 {
   int size = 18, degreeOfBasis = 4, nsteps_override = -1;
   double CFL = 0.5, domainLength = 0.1;
-  const char* dump = nullptr;
+  const char *dump = nullptr, *dump_mass = nullptr;
   const char *mesh_file = nullptr, *grid_name = "planar3d", *tags_name = "planar3d_boundaries";
   std::array<bool, 3> periodic{false, false, false};
-  bool reference_order = false, markers = false, leapfrog = false;
+  bool reference_order = false, markers = false, leapfrog = false, leapfrog4 = false;
   int geometry = WF_GEOMETRY_AUTO;
   double amplitude = 60000;
   const char* traces = nullptr;
@@ -68,6 +70,7 @@ int main(int argc, char* argv[])
     else if (is("--steps")) nsteps_override = std::atoi(argv[++i]);
     else if (is("--length")) domainLength = std::atof(argv[++i]);
     else if (is("--dump")) dump = argv[++i];
+    else if (is("--dump-mass")) dump_mass = argv[++i];
     else if (is("--mesh")) mesh_file = argv[++i];
     else if (is("--amplitude")) amplitude = std::atof(argv[++i]);
     else if (is("--traces")) traces = argv[++i];
@@ -93,16 +96,17 @@ int main(int argc, char* argv[])
     else if (is("--geometry") && std::strcmp(argv[i + 1], "auto") == 0) ++i, geometry = WF_GEOMETRY_AUTO;
     else if (is("--geometry") && std::strcmp(argv[i + 1], "per_point") == 0) ++i, geometry = WF_GEOMETRY_PER_POINT;
     else if (is("--geometry") && std::strcmp(argv[i + 1], "per_cell") == 0) ++i, geometry = WF_GEOMETRY_PER_CELL;
-    else if (is("--scheme") && std::strcmp(argv[i + 1], "rk4") == 0) ++i, leapfrog = false;
-    else if (is("--scheme") && std::strcmp(argv[i + 1], "leapfrog") == 0) ++i, leapfrog = true;
+    else if (is("--scheme") && std::strcmp(argv[i + 1], "rk4") == 0) ++i, leapfrog = leapfrog4 = false;
+    else if (is("--scheme") && std::strcmp(argv[i + 1], "leapfrog") == 0) ++i, leapfrog = true, leapfrog4 = false;
+    else if (is("--scheme") && std::strcmp(argv[i + 1], "leapfrog4") == 0) ++i, leapfrog4 = true, leapfrog = false;
     else if (is("--periodic")) {
       for (const char* c = argv[++i]; *c; ++c)
         if (*c >= 'x' && *c <= 'z') periodic[*c - 'x'] = true;
     } else if (std::strcmp(argv[i], "--reference-order") == 0) reference_order = true;
     else {
       std::cerr << "usage: planar3d [--mesh FILE.xdmf [--grid NAME] [--tags NAME]] [--size N] [--degree P] [--cfl C]"
-                   " [--steps S] [--length L] [--dump FILE] [--periodic xyz] [--reference-order] [--markers]"
-                   " [--geometry auto|per_point|per_cell] [--scheme rk4|leapfrog] [--amplitude P0] [--source x,y,z,f]"
+                   " [--steps S] [--length L] [--dump FILE] [--dump-mass FILE] [--periodic xyz] [--reference-order] [--markers]"
+                   " [--geometry auto|per_point|per_cell] [--scheme rk4|leapfrog|leapfrog4] [--amplitude P0] [--source x,y,z,f]"
                    " [--receiver x,y,z]... [--traces FILE]\n";
       return 2;
     }
@@ -175,7 +179,8 @@ int main(int argc, char* argv[])
       attach_points(eqn, V.space());
       eqn.init();
       auto t0 = std::chrono::steady_clock::now();
-      int steps = leapfrog          ? eqn.leapfrog(startTime, finalTime, timeStepSize)
+      int steps = leapfrog4         ? eqn.leapfrog4(startTime, finalTime, timeStepSize)
+                  : leapfrog        ? eqn.leapfrog(startTime, finalTime, timeStepSize)
                     : reference_order ? eqn.rk4(startTime, finalTime, timeStepSize)
                                       : eqn.rk4_fused(startTime, finalTime, timeStepSize);
       wavehip::check(wf_sync(nullptr));
@@ -233,7 +238,8 @@ int main(int argc, char* argv[])
     eqn.init();
     if (comm) comm->barrier();
     auto t0 = std::chrono::steady_clock::now();
-    int steps = leapfrog          ? eqn.leapfrog(startTime, finalTime, timeStepSize)
+    int steps = leapfrog4         ? eqn.leapfrog4(startTime, finalTime, timeStepSize)
+                : leapfrog        ? eqn.leapfrog(startTime, finalTime, timeStepSize)
                   : reference_order ? eqn.rk4(startTime, finalTime, timeStepSize)
                                     : eqn.rk4_fused(startTime, finalTime, timeStepSize);
     if (comm) comm->barrier();
@@ -243,6 +249,14 @@ int main(int argc, char* argv[])
       std::cout << "Solve time: " << secs << std::endl;
     }
 
+    if (dump_mass) {
+      if (world > 1) throw std::runtime_error("--dump-mass runs on one rank");
+      auto m = eqn.lumped_mass().copy_to_host();
+      FILE* f = std::fopen(dump_mass, "wb");
+      if (!f) throw std::runtime_error("cannot open mass dump file");
+      std::fwrite(m.data(), sizeof(double), m.size(), f);
+      std::fclose(f);
+    }
     if (dump) {
       auto u = eqn.u_n->copy_to_host();
       auto v = eqn.v_n->copy_to_host();

@@ -20,6 +20,7 @@
 #include <memory>
 
 #include "wavehip_box.hpp"
+#include "wavehip_leapfrog4.h"
 
 namespace wavehip {
 
@@ -151,6 +152,8 @@ protected:
 public:
   const BoxSpace* V = nullptr;   // the box constructor's space (nullptr for the general-Space constructor)
   std::unique_ptr<array<double>> u_n, v_n;
+  /// the lumped mass the loops divide by (assembled by atomics at creation: two models' may differ in the last bit)
+  const array<double>& lumped_mass() const { return *m; }
 
   /// The mesh-file path (demo/cpu_planar3d/main.cpp:39-45, common/LinearGLL.hpp:53-128): any conforming
   /// hexahedral space plus the dof sets of Gamma_1 (source) and Gamma_2 (absorbing) with their collocated
@@ -324,10 +327,22 @@ public:
     return run(WF_WAVE_LEAPFROG, startTime, finalTime, timeStep, max_steps);
   }
 
+  /// Fourth-order leapfrog (the modified-equation scheme) from the state (u_n, v_n) to the state (u_n, v_n):
+  /// (u+ - 2u + u-)/dt^2 = A u + (dt^2/12) A^2 u, A = M^-1 K: TWO stiffness applies and two streaming passes
+  /// (wf_leapfrog4_predict, wf_leapfrog4_correct) per step, fourth order in time, stable for dt <= sqrt(12/lambda_max),
+  /// sqrt(3) times leapfrog's limit.  The centred absorbing term stays second order.  Constant step, counted as
+  /// leapfrog() counts; a split run equals a continuous one to truncation order, not to rounding.
+  /// The loop is wf_wave_leapfrog4 (wavehip_leapfrog4.h), the one the Python model runs.
+  int leapfrog4(double& startTime, double& finalTime, double& timeStep, std::int64_t max_steps = -1)
+  {
+    return run(WF_WAVE_LEAPFROG4, startTime, finalTime, timeStep, max_steps);
+  }
+
 protected:
   /// one call of a loop of the library on (u_n, v_n): the descriptor, the work vectors and the trace rows
   int run(int scheme, double t0, double tf, double dt, std::int64_t max_steps)
   {
+    const bool fourth = scheme == WF_WAVE_LEAPFROG4;   // its own count of work vectors (wavehip_leapfrog4.h)
     wf_wave_desc d{};
     d.n = N_;
     d.d_m = m->data();
@@ -349,13 +364,15 @@ protected:
     }
     std::vector<std::unique_ptr<array<double>>> work;
     std::vector<double*> work_ptr;
-    for (int k = 0; k < wf_wave_work_vectors(scheme); ++k) {
+    for (int k = 0; k < (fourth ? wf_wave_leapfrog4_work_vectors() : wf_wave_work_vectors(scheme)); ++k) {
       work.push_back(std::make_unique<array<double>>((std::size_t)N_));
       work_ptr.push_back(work.back()->data());
     }
     d.d_work = work_ptr.data();
     std::int64_t steps = 0;
-    if (scheme == WF_WAVE_LEAPFROG)
+    if (fourth)
+      check(wf_wave_leapfrog4(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, &steps, nullptr));
+    else if (scheme == WF_WAVE_LEAPFROG)
       check(wf_wave_leapfrog(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, nullptr, nullptr, &steps, nullptr));
     else
       check(wf_wave_rk4_fused(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, &steps, nullptr));

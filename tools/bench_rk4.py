@@ -9,6 +9,11 @@ ghost exchange, LinearGLLOpt.rk4_fused -- launched like bench.py:
 Prints one JSON line: ms per RK4 time step and dof-stages/s over all ranks.
 --scheme leapfrog times LinearGLLOpt.leapfrog at the same step instead (the same keys, per leapfrog step; the timed
 window includes the scheme's start-up and finish, two extra stiffness applies).
+--scheme leapfrog4 times LinearGLLOpt.leapfrog4 likewise (two applies per step; start-up and finish are six more).
+--compare (one rank): leapfrog, leapfrog4 and rk4_fused on one model, timed alternately --rounds times with device events
+after a warm-up of each, at each scheme's own step -- stable_time_step(0.9) of leapfrog, sqrt(3) times it for leapfrog4,
+sqrt(2) times it for RK4 (its limit on the imaginary axis is sqrt(8) / sqrt(lambda_max)) -- and at the common CFL step;
+prints ms per step and ms per microsecond of simulated time for each.
 --receivers N / --sources S (one rank): the same loop with N point receivers recorded every step and S Ricker point
 sources, against the loop without them -- two models in one process, timed alternately --rounds times after one warm-up
 each; prints medians and ranges of both and the difference per step.
@@ -34,8 +39,10 @@ def main():
     ap.add_argument("--size", type=int, default=54)
     ap.add_argument("--degree", type=int, default=4)
     ap.add_argument("--unfused", action="store_true")
-    ap.add_argument("--scheme", choices=["rk4", "leapfrog"], default="rk4",
-                    help="leapfrog: LinearGLLOpt.leapfrog at the same step (one stiffness apply per step; ms_per_rk4_step is then ms per leapfrog step)")
+    ap.add_argument("--scheme", choices=["rk4", "leapfrog", "leapfrog4"], default="rk4",
+                    help="leapfrog / leapfrog4: LinearGLLOpt.leapfrog / leapfrog4 at the same step (one / two stiffness applies per step; "
+                         "ms_per_rk4_step is then ms per step of that scheme)")
+    ap.add_argument("--compare", action="store_true", help="leapfrog, leapfrog4 and rk4_fused alternately, at their own steps and a common one")
     ap.add_argument("--receivers", type=int, default=0, help="point receivers recorded every step (A/B against the plain loop)")
     ap.add_argument("--sources", type=int, default=0, help="Ricker point sources (A/B against the plain loop)")
     ap.add_argument("--gradient", action="store_true", help="with --scheme leapfrog: time misfit_gradient against leapfrog")
@@ -76,14 +83,19 @@ def main():
     eqn = LinearGLLOpt(part.V, p, 1500.0, 0.5e6, 6e4, updater=updater, tags=boundary_tags(part), device=dev)
     dt, _ = cfl_time_step(part.mesh, p, 1500.0, 0.5e6, CFL=0.25)
     eqn.init()
-    run = eqn.leapfrog if args.scheme == "leapfrog" else eqn.rk4 if args.unfused else eqn.rk4_fused
-    applies = 1.0 if args.scheme == "leapfrog" else 4.0
+    run = {"leapfrog": eqn.leapfrog, "leapfrog4": eqn.leapfrog4}.get(args.scheme, eqn.rk4 if args.unfused else eqn.rk4_fused)
+    applies = {"leapfrog": 1.0, "leapfrog4": 2.0}.get(args.scheme, 4.0)
 
     def sync():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
+    if args.compare:
+        if updater is not None:
+            sys.exit("--compare runs on one rank without --periodic")
+        compare(args, eqn, dt, part.size_global)
+        return
     if args.receivers or args.sources:
         if updater is not None:
             sys.exit("--receivers / --sources run on one rank without --periodic")
@@ -102,7 +114,7 @@ def main():
             gradient_ab(args, with_points, rec, dt, part.size_global)
             return
         models = {"plain": eqn, "points": with_points}
-        name = "leapfrog" if args.scheme == "leapfrog" else "rk4" if args.unfused else "rk4_fused"
+        name = args.scheme if args.scheme != "rk4" else "rk4" if args.unfused else "rk4_fused"
         times = {k: [] for k in models}
         t_at = {k: 0.0 for k in models}
         for rnd in range(args.rounds + 1):            # round 0 is the warm-up of both
@@ -146,6 +158,45 @@ def main():
                           "exchange": updater.transport if updater is not None else None, "finite": ok, "scaling": "weak"}), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def compare(args, eqn, dt_cfl, global_dofs):
+    """the three loops on one model, alternately, each run timed by a pair of device events; the timed window includes
+    each scheme's start-up and finish (leapfrog two applies, leapfrog4 six)"""
+    import math
+    import statistics
+
+    import torch
+    steps = args.steps
+    dt_lf = eqn.stable_time_step(0.9)
+    own = {"leapfrog": dt_lf, "leapfrog4": eqn.stable_time_step(0.9, scheme="leapfrog4"), "rk4_fused": dt_lf * math.sqrt(2.0)}
+    out = {"metric": "leapfrog, leapfrog4 and rk4_fused, ms per step (device events)", "steps": steps, "rounds": args.rounds,
+           "global_dofs": global_dofs, "dt_common": dt_cfl, "dt_own": own}
+
+    def timed(name, dt, n):
+        eqn.init()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        getattr(eqn, name)(0.0, 1.0e9, dt, max_steps=n)
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / n
+
+    for label, dts in (("own", own), ("common", {k: dt_cfl for k in own})):
+        for name in own:
+            timed(name, dts[name], args.warmup)
+        times = {k: [] for k in own}
+        for _ in range(args.rounds):
+            for name in own:
+                times[name].append(timed(name, dts[name], steps))
+        finite = {}
+        for name in own:                                       # after a timed run of each: did it stay bounded at this step
+            timed(name, dts[name], steps)
+            finite[name] = bool(torch.isfinite(eqn.u_n).all())
+        out[label] = {k: {"ms_per_step": statistics.median(v), "min": min(v), "max": max(v),
+                          "ms_per_simulated_us": statistics.median(v) / (dts[k] * 1e6), "finite": finite[k]} for k, v in times.items()}
+    print(json.dumps(out), flush=True)
 
 
 def gradient_ab(args, eqn, rec, dt, global_dofs):

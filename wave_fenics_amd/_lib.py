@@ -136,6 +136,7 @@ class WaveDesc(ctypes.Structure):
 
 
 WF_WAVE_RK4_FUSED, WF_WAVE_LEAPFROG = 0, 1
+WF_WAVE_LEAPFROG4 = 2   # include/wavehip_leapfrog4.h
 WF_QUAD_GLL, WF_QUAD_GAUSS_JACOBI = 0, 1
 WF_VARIANT_GLL_WARPED, WF_VARIANT_EQUISPACED = 0, 1
 WF_MAX_QUAD_POINTS = 16
@@ -293,6 +294,17 @@ SIGNATURES = {
                                  c_void_p, POINTER(c_double), POINTER(c_int64), c_void_p]),
 }
 
+# every symbol include/wavehip_leapfrog4.h declares (the fourth-order leapfrog): a table of its own beside SIGNATURES,
+# which mirrors include/wavehip.h alone
+SIGNATURES_LEAPFROG4 = {
+    "wf_leapfrog4_predict": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
+    "wf_leapfrog4_correct": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
+    "wf_sources_add_stencil": (c_int, [c_void_p, c_int, _DP, _DP, c_void_p, c_void_p]),
+    "wf_wave_leapfrog4_work_vectors": (c_int, []),
+    "wf_wave_leapfrog4": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p,
+                                  POINTER(c_double), POINTER(c_int64), c_void_p]),
+}
+
 _LIB = None
 
 
@@ -313,7 +325,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_LEAPFROG4}.items():
             fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -15,6 +15,7 @@
 #include "device_array.h"
 #include "points_handles.h"
 #include "points_plan.h"
+#include "wavehip_leapfrog4.h"
 
 namespace wf {
 
@@ -76,6 +77,39 @@ __global__ __launch_bounds__(256) void k_sources_add(int nunique, const int32_t*
   for (int e = off[u]; e < off[u + 1]; ++e) {
     const int s = src[e];
     acc += weight[e] * wavelet_value(kind[s], par + (size_t)s * kWaveletPars, samples + soff[s], soff[s + 1] - soff[s], t);
+  }
+  b[dof[u]] += acc;
+}
+
+// k_sources_add with the wavelet of every entry replaced by ((a0 s(t0)) + a1 s(t1)) + a2 s(t2), the first nt terms, formed
+// as written; times and weights travel with the launch.
+struct SourceStencil {
+  int nt;
+  double t[3], a[3];
+};
+
+__device__ inline double stencil_sum(const SourceStencil& st, int kind, const double* __restrict__ par, const double* __restrict__ tab,
+                                     int ns)
+{
+#pragma clang fp contract(off)
+  double sum = st.a[0] * wavelet_value(kind, par, tab, ns, st.t[0]);
+  if (st.nt > 1) sum = sum + st.a[1] * wavelet_value(kind, par, tab, ns, st.t[1]);
+  if (st.nt > 2) sum = sum + st.a[2] * wavelet_value(kind, par, tab, ns, st.t[2]);
+  return sum;
+}
+
+__global__ __launch_bounds__(256) void k_sources_add_stencil(int nunique, const int32_t* __restrict__ dof, const int32_t* __restrict__ off,
+                                                              const int32_t* __restrict__ src, const double* __restrict__ weight,
+                                                              const int32_t* __restrict__ kind, const int32_t* __restrict__ soff,
+                                                              const double* __restrict__ par, const double* __restrict__ samples,
+                                                              SourceStencil st, double* __restrict__ b)
+{
+  const int u = blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= nunique) return;
+  double acc = 0.0;
+  for (int e = off[u]; e < off[u + 1]; ++e) {
+    const int s = src[e];
+    acc += weight[e] * stencil_sum(st, kind[s], par + (size_t)s * kWaveletPars, samples + soff[s], soff[s + 1] - soff[s]);
   }
   b[dof[u]] += acc;
 }
@@ -210,6 +244,25 @@ int wf_sources_add(const wf_sources* src, double t, double* d_b, void* stream)
   hipLaunchKernelGGL(wf::k_sources_add, dim3(wf::grid_for((size_t)src->nunique, 256)), dim3(256), 0, (hipStream_t)stream, src->nunique,
                      src->d_dof.data(), src->d_off.data(), src->d_src.data(), src->d_weight.data(), src->d_kind.data(),
                      src->d_soff.data(), src->d_par.data(), src->d_samples.data(), t, d_b);
+  WF_LAUNCH_CHECK();
+  return WF_OK;
+}
+
+int wf_sources_add_stencil(const wf_sources* src, int nt, const double* h_t, const double* h_a, double* d_b, void* stream)
+{
+  WF_REQUIRE(src != nullptr, "wf_sources_add_stencil: null handle");
+  WF_REQUIRE(nt >= 1 && nt <= 3, "wf_sources_add_stencil: nt must be 1, 2 or 3");
+  WF_REQUIRE(h_t && h_a, "wf_sources_add_stencil: null times or weights");
+  wf::SourceStencil st{nt, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+  for (int k = 0; k < nt; ++k) {
+    WF_REQUIRE(std::isfinite(h_t[k]) && std::isfinite(h_a[k]), "wf_sources_add_stencil: time or weight not finite");
+    st.t[k] = h_t[k], st.a[k] = h_a[k];
+  }
+  if (src->nunique == 0) return WF_OK;
+  WF_REQUIRE(d_b != nullptr, "wf_sources_add_stencil: null vector");
+  hipLaunchKernelGGL(wf::k_sources_add_stencil, dim3(wf::grid_for((size_t)src->nunique, 256)), dim3(256), 0, (hipStream_t)stream,
+                     src->nunique, src->d_dof.data(), src->d_off.data(), src->d_src.data(), src->d_weight.data(), src->d_kind.data(),
+                     src->d_soff.data(), src->d_par.data(), src->d_samples.data(), st, d_b);
   WF_LAUNCH_CHECK();
   return WF_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "device_array.h"
 #include "sweep.h"
+#include "wavehip_leapfrog4.h"
 
 namespace wf {
 
@@ -230,6 +231,130 @@ __global__ void __launch_bounds__(256) k_leapfrog_step(int64_t nvec, int ntail, 
   sweep<VEC, NT>(nvec, ntail, WF_SWEEP_THREAD, [&](auto io, int64_t g) { leapfrog_entry<BC, HAS_V>(a, io, g); });
 }
 
+// The two passes of one fourth-order (modified-equation) leapfrog step, (u+ - 2u + u-)/dt^2 = A u + (dt^2/12) A^2 u with
+// A = M^-1 K: the predictor after the apply that left K u in b, the corrector after the apply that left K w in b.
+//   predictor:  u* = the leapfrog update above (leapfrog_plain / leapfrog_boundary: the same bits)
+//               w = c12 (b / m), on the union set c12 ((b + s1 c1[r]) / m) ; b = +0.0
+//   corrector:  u_next = u* + dt2 (b / m), on the union set h = hdt c2[r] ; u_next = u* + (dt2 (b + s1c c1[r])) / (m + h)
+//               v = (u_next - u_prev) / (2 dt)  (HAS_V) ; b = +0.0
+// c12 = dt2 / 12 from the host, s1c the second difference of s1 over 12.  u* may alias u_prev and u_next may alias u*
+// (every thread reads its entry before it writes it).  HBM traffic per dof: predictor b, m, u, u_prev read, u*, w, b
+// written = 56 B; corrector b, m, u* read, u_next, b written = 40 B (56 B with u_prev and v).
+// Plain accesses for what the next apply touches (w and b; u_next and b) and for u, which the last apply just read;
+// everything else bypasses the caches as in k_leapfrog_step.
+struct Leapfrog4PredictArgs {
+  double dt2, hdt, c12;
+  double* b;
+  const double* m;
+  const double* u;
+  const double* up;
+  double* us;
+  double* w;
+  BoundaryPlanDev bc;   // s1 = the coefficient of the Gamma_1 term at the current time; s2 is folded into hdt
+};
+
+__device__ __forceinline__ double leapfrog4_w_plain(double b, double m, double c12)
+{
+#pragma clang fp contract(off)
+  return c12 * (b / m);
+}
+__device__ __forceinline__ double leapfrog4_w_boundary(double b, double m, double c12, double s1, double c1)
+{
+#pragma clang fp contract(off)
+  return c12 * ((b + s1 * c1) / m);
+}
+
+template <bool BC, int VEC, bool NT>
+__device__ __forceinline__ void leapfrog4_predict_entry(const Leapfrog4PredictArgs& a, Lanes<VEC, NT> io, int64_t g)
+{
+  using L = Lanes<VEC, NT>;
+  using V = typename L::V;
+  const double dt2 = a.dt2, c12 = a.c12;
+  const V bb = io.ldnt(a.b, g), mm = io.ldnt(a.m, g), uu = io.ld(a.u, g), pp = io.ldnt(a.up, g);
+  V ss, ww, zero;
+  for (int l = 0; l < VEC; ++l) {
+    L::at(ss, l) = leapfrog_plain(L::at(bb, l), L::at(mm, l), L::at(uu, l), L::at(pp, l), dt2);
+    L::at(ww, l) = leapfrog4_w_plain(L::at(bb, l), L::at(mm, l), c12);
+    L::at(zero, l) = 0.0;
+  }
+  if constexpr (BC) {
+    const BoundaryPlanDev& bc = a.bc;
+    for_boundary_dofs<VEC>(bc, io.off + (int64_t)VEC * g, [&](int lane, int64_t r) {
+      const double c1 = bc.c1[r];
+      L::at(ss, lane) = leapfrog_boundary(L::at(bb, lane), L::at(mm, lane), L::at(uu, lane), L::at(pp, lane), dt2, a.hdt, bc.s1, c1,
+                                          bc.c2[r]);
+      L::at(ww, lane) = leapfrog4_w_boundary(L::at(bb, lane), L::at(mm, lane), c12, bc.s1, c1);
+    });
+  }
+  io.stnt(a.us, g, ss);
+  io.st(a.w, g, ww);
+  io.st(a.b, g, zero);
+}
+
+template <int VEC, bool NT, bool BC>
+__global__ void __launch_bounds__(256) k_leapfrog4_predict(int64_t nvec, int ntail, Leapfrog4PredictArgs a)
+{
+  sweep<VEC, NT>(nvec, ntail, WF_SWEEP_THREAD, [&](auto io, int64_t g) { leapfrog4_predict_entry<BC>(a, io, g); });
+}
+
+struct Leapfrog4CorrectArgs {
+  double dt2, hdt, tdt;
+  double* b;
+  const double* m;
+  const double* us;
+  const double* up;
+  double* un;
+  double* v;
+  BoundaryPlanDev bc;   // s1 = s1c, the second difference of the Gamma_1 coefficient over 12; s2 is folded into hdt
+};
+
+__device__ __forceinline__ double leapfrog4_correct_plain(double b, double m, double us, double dt2)
+{
+#pragma clang fp contract(off)
+  return us + dt2 * (b / m);
+}
+__device__ __forceinline__ double leapfrog4_correct_boundary(double b, double m, double us, double dt2, double hdt, double s1c, double c1,
+                                                             double c2)
+{
+#pragma clang fp contract(off)
+  const double h = hdt * c2;
+  return us + (dt2 * (b + s1c * c1)) / (m + h);
+}
+
+template <bool BC, bool HAS_V, int VEC, bool NT>
+__device__ __forceinline__ void leapfrog4_correct_entry(const Leapfrog4CorrectArgs& a, Lanes<VEC, NT> io, int64_t g)
+{
+  using L = Lanes<VEC, NT>;
+  using V = typename L::V;
+  const double dt2 = a.dt2;
+  const V bb = io.ldnt(a.b, g), mm = io.ldnt(a.m, g), ss = io.ldnt(a.us, g);
+  V nn, zero;
+  for (int l = 0; l < VEC; ++l) {
+    L::at(nn, l) = leapfrog4_correct_plain(L::at(bb, l), L::at(mm, l), L::at(ss, l), dt2);
+    L::at(zero, l) = 0.0;
+  }
+  if constexpr (BC) {
+    const BoundaryPlanDev& bc = a.bc;
+    for_boundary_dofs<VEC>(bc, io.off + (int64_t)VEC * g, [&](int lane, int64_t r) {
+      L::at(nn, lane) = leapfrog4_correct_boundary(L::at(bb, lane), L::at(mm, lane), L::at(ss, lane), dt2, a.hdt, bc.s1, bc.c1[r], bc.c2[r]);
+    });
+  }
+  if constexpr (HAS_V) {
+    const V pp = io.ldnt(a.up, g);
+    V w;
+    for (int l = 0; l < VEC; ++l) L::at(w, l) = (L::at(nn, l) - L::at(pp, l)) / a.tdt;
+    io.stnt(a.v, g, w);
+  }
+  io.st(a.un, g, nn);
+  io.st(a.b, g, zero);
+}
+
+template <int VEC, bool NT, bool BC, bool HAS_V>
+__global__ void __launch_bounds__(256) k_leapfrog4_correct(int64_t nvec, int ntail, Leapfrog4CorrectArgs a)
+{
+  sweep<VEC, NT>(nvec, ntail, WF_SWEEP_THREAD, [&](auto io, int64_t g) { leapfrog4_correct_entry<BC, HAS_V>(a, io, g); });
+}
+
 }  // namespace wf
 
 struct wf_boundary {
@@ -325,9 +450,72 @@ int leapfrog_step_impl(int64_t n, double dt, double* d_b, const double* d_m, con
   return WF_OK;
 }
 
+// two vectors of n entries that share memory
+bool vectors_overlap(int64_t n, const double* p, const double* q)
+{
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), c = reinterpret_cast<uintptr_t>(q), len = (uintptr_t)n * sizeof(double);
+  return a < c + len && c < a + len;
+}
+
 }  // namespace
 
 extern "C" {
+
+int wf_leapfrog4_predict(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                         double* d_u_star, double* d_w, const wf_boundary* bcp, double s1, double s2, void* stream)
+{
+  if (n <= 0) return WF_OK;
+  WF_REQUIRE(d_b && d_m && d_u && d_u_prev && d_u_star && d_w, "wf_leapfrog4_predict: null vector");
+  WF_REQUIRE(dt > 0.0, "wf_leapfrog4_predict: the time step must be positive");
+  WF_REQUIRE(!(s2 > 0.0), "wf_leapfrog4_predict: s2 > 0 is a negative absorbing coefficient");
+  auto overlap = [n](const double* p, const double* q) { return vectors_overlap(n, p, q); };
+  WF_REQUIRE(!overlap(d_u_star, d_u) && !overlap(d_u_star, d_b) && !overlap(d_u_star, d_m),
+             "wf_leapfrog4_predict: u_star must not alias u, b or m");
+  WF_REQUIRE(d_u_star == d_u_prev || !overlap(d_u_star, d_u_prev), "wf_leapfrog4_predict: u_star overlaps u_prev without being u_prev");
+  WF_REQUIRE(!overlap(d_w, d_b) && !overlap(d_w, d_m) && !overlap(d_w, d_u) && !overlap(d_w, d_u_prev) && !overlap(d_w, d_u_star),
+             "wf_leapfrog4_predict: w must not alias another vector of the call");
+  WF_REQUIRE(!bcp || bcp->n == n, "wf_leapfrog4_predict: the boundary plan was built for another vector length");
+  wf::MarkerScope mk("wf_leapfrog4_predict");
+  const double dt2 = dt * dt;
+  const wf::Leapfrog4PredictArgs a{dt2, (-s2) * (0.5 * dt), dt2 / 12.0, d_b, d_m, d_u, d_u_prev, d_u_star, d_w, plan_dev(bcp, s1, 0.0)};
+  const wf::SweepShape s = wf::sweep_shape(n, d_b, d_m, d_u, d_u_prev, d_u_star, d_w);
+  with_bools(s.vec, a.bc.mask != nullptr, false, [&](auto vec, auto bc, auto) {
+    hipLaunchKernelGGL((wf::k_leapfrog4_predict<vec() ? 2 : 1, vec(), bc()>), dim3(s.grid), dim3(256), 0, (hipStream_t)stream, s.nvec,
+                       s.ntail, a);
+  });
+  WF_LAUNCH_CHECK();
+  return WF_OK;
+}
+
+int wf_leapfrog4_correct(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u_star, const double* d_u_prev,
+                         double* d_u_next, double* d_v, const wf_boundary* bcp, double s1c, double s2, void* stream)
+{
+  if (n <= 0) return WF_OK;
+  WF_REQUIRE(d_b && d_m && d_u_star && d_u_next, "wf_leapfrog4_correct: null vector");
+  WF_REQUIRE(!d_v || d_u_prev, "wf_leapfrog4_correct: v needs u_prev");
+  WF_REQUIRE(dt > 0.0, "wf_leapfrog4_correct: the time step must be positive");
+  WF_REQUIRE(!(s2 > 0.0), "wf_leapfrog4_correct: s2 > 0 is a negative absorbing coefficient");
+  auto overlap = [n](const double* p, const double* q) { return vectors_overlap(n, p, q); };
+  WF_REQUIRE(!overlap(d_u_next, d_b) && !overlap(d_u_next, d_m), "wf_leapfrog4_correct: u_next must not alias b or m");
+  WF_REQUIRE(d_u_next == d_u_star || !overlap(d_u_next, d_u_star), "wf_leapfrog4_correct: u_next overlaps u_star without being u_star");
+  WF_REQUIRE(!overlap(d_u_star, d_b) && !overlap(d_u_star, d_m), "wf_leapfrog4_correct: u_star must not alias b or m");
+  WF_REQUIRE(!d_v || (!overlap(d_u_prev, d_u_next) && !overlap(d_u_prev, d_b) && !overlap(d_u_prev, d_u_star)),
+             "wf_leapfrog4_correct: u_prev must not alias u_next, u_star or b");
+  WF_REQUIRE(!d_v || (!overlap(d_v, d_b) && !overlap(d_v, d_m) && !overlap(d_v, d_u_star) && !overlap(d_v, d_u_prev)
+                      && !overlap(d_v, d_u_next)),
+             "wf_leapfrog4_correct: v must not alias another vector of the call");
+  WF_REQUIRE(!bcp || bcp->n == n, "wf_leapfrog4_correct: the boundary plan was built for another vector length");
+  wf::MarkerScope mk("wf_leapfrog4_correct");
+  const double* const up = d_v ? d_u_prev : nullptr;          // not read without v, so not asked to be aligned either
+  const wf::Leapfrog4CorrectArgs a{dt * dt, (-s2) * (0.5 * dt), 2.0 * dt, d_b, d_m, d_u_star, up, d_u_next, d_v, plan_dev(bcp, s1c, 0.0)};
+  const wf::SweepShape s = wf::sweep_shape(n, d_b, d_m, d_u_star, up, d_u_next, d_v);
+  with_bools(s.vec, a.bc.mask != nullptr, d_v != nullptr, [&](auto vec, auto bc, auto has_v) {
+    hipLaunchKernelGGL((wf::k_leapfrog4_correct<vec() ? 2 : 1, vec(), bc(), has_v()>), dim3(s.grid), dim3(256), 0, (hipStream_t)stream,
+                       s.nvec, s.ntail, a);
+  });
+  WF_LAUNCH_CHECK();
+  return WF_OK;
+}
 
 int wf_leapfrog_step(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
                      double* d_u_next, double* d_v, void* stream)

@@ -1,4 +1,4 @@
-// The two time loops of the wave model, rk4_fused and leapfrog, once: host code over the library's own entries (no HIP
+// The time loops of the wave model, rk4_fused, leapfrog and leapfrog4, once: host code over the library's own entries (no HIP
 // in here; wave_source.h holds the plane source).  The Python and the C++ LinearGLLOpt both call these.  Every launch
 // goes to the caller's stream; nothing is allocated, freed or synchronised.
 #include <algorithm>
@@ -7,6 +7,7 @@
 
 #include "wave_source.h"
 #include "wavehip.h"
+#include "wavehip_leapfrog4.h"
 
 namespace wf {
 void set_error(const std::string& msg);                     // tables.cpp
@@ -15,6 +16,7 @@ void set_error(const std::string& msg);                     // tables.cpp
 namespace {
 
 constexpr int kWorkVectors[2] = {7, 3};                     // WF_WAVE_RK4_FUSED, WF_WAVE_LEAPFROG
+constexpr int kWorkVectorsLeapfrog4 = 4;                    // wf_wave_leapfrog4: u^n, u^{n-1}, the corrector's operand, a scratch
 constexpr double a_runge[4] = {0.0, 0.5, 0.5, 1.0};
 constexpr double b_runge[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
 constexpr double c_runge[4] = {0.0, 0.5, 0.5, 1.0};
@@ -43,13 +45,13 @@ double stage_time(double t, double c, double dt)
   } while (0)
 
 int check_call(const std::string& who, int scheme, const wf_wave_desc* d, double t0, double tf, double dt, int64_t max_steps,
-               const double* d_u, const double* d_v)
+               const double* d_u, const double* d_v, int nwork = -1)
 {
   WF_REFUSE_UNLESS(d, who + ": null descriptor");
   WF_REFUSE_UNLESS(d->n >= 0, who + ": n < 0");
   WF_REFUSE_UNLESS(d_u && d_v, who + ": null state");
   WF_REFUSE_UNLESS(d->d_work, who + ": null work");
-  for (int k = 0; k < kWorkVectors[scheme]; ++k) WF_REFUSE_UNLESS(d->d_work[k], who + ": null work");
+  for (int k = 0; k < (nwork < 0 ? kWorkVectors[scheme] : nwork); ++k) WF_REFUSE_UNLESS(d->d_work[k], who + ": null work");
   WF_REFUSE_UNLESS(d->d_m && d->d_b && d->bc, who + ": null m, b or boundary plan");
   WF_REFUSE_UNLESS(d->rhs || d->op, who + ": needs an operator handle or a right-hand-side callback");
   WF_REFUSE_UNLESS(d->rhs || !d->overlapped || d->updater, who + ": overlapped needs an updater");
@@ -88,6 +90,11 @@ struct Loop {
     return d.updater ? wf_updater_rev(d.updater, d.d_b, s) : WF_OK;
   }
   int add_sources(double t) const { return d.sources ? wf_sources_add(d.sources, t, d.d_b, s) : WF_OK; }
+  // b += the point sources' sum over nt times with weights (a difference quotient of the load)
+  int add_stencil(int nt, const double* times, const double* weights) const
+  {
+    return d.sources ? wf_sources_add_stencil(d.sources, nt, times, weights, d.d_b, s) : WF_OK;
+  }
   // row `row` of the traces: u at the receivers, at time t
   int record(const double* u, int64_t row, double t) const
   {
@@ -232,6 +239,98 @@ int wf_wave_leapfrog(const wf_wave_desc* desc, double t0, double tf, double dt, 
   WF_TRY(L.rhs(u));
   WF_TRY(L.add_sources(t));
   WF_TRY(wf_leapfrog_step_bc(n, dt, b, m, u, w, scratch, d_v, d.bc, s1(t), s2, stream));
+  WF_TRY(wf_copy(n, u, d_u, stream));
+  if (t_end) *t_end = t;
+  if (steps) *steps = step;
+  return WF_OK;
+}
+
+int wf_wave_leapfrog4_work_vectors(void) { return kWorkVectorsLeapfrog4; }
+
+int wf_wave_leapfrog4(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
+                      double* t_end, int64_t* steps, void* stream)
+{
+  WF_TRY(check_call("wf_wave_leapfrog4", WF_WAVE_LEAPFROG, desc, t0, tf, dt, max_steps, d_u, d_v, kWorkVectorsLeapfrog4));
+  const wf_wave_desc& d = *desc;
+  Loop L{d, stream};
+  WF_TRY(L.init());
+  const int64_t n = d.n;
+  double* const b = d.d_b;
+  const double* const m = d.d_m;
+  double *u = d.d_work[0], *p = d.d_work[1];                  // u^n; u^{n-1}, overwritten in place by u* and then u^{n+1}
+  double *const w = d.d_work[2], *const scratch = d.d_work[3];
+  const double s2 = wf::wave_s2(d.source);
+  const double dt2 = dt * dt;
+  auto s1 = [&](double t) { return wf::wave_s1(d.source, t); };
+  // central differences of the plane source's coefficient over t +- dt: first and second derivative, and the second
+  // difference over 12 of the corrector
+  auto s1_d1 = [&](double t) { return (s1(t + dt) - s1(t - dt)) / (2.0 * dt); };
+  auto s1_dd = [&](double t) { return (s1(t + dt) - 2.0 * s1(t)) + s1(t - dt); };
+  // the same differences of the point sources, onto b
+  auto sources_d1 = [&](double t) {
+    const double ts[2] = {t - dt, t + dt}, as[2] = {-1.0 / (2.0 * dt), 1.0 / (2.0 * dt)};
+    return L.add_stencil(2, ts, as);
+  };
+  auto sources_dd = [&](double t, double scale) {
+    const double ts[3] = {t - dt, t, t + dt}, as[3] = {scale, -2.0 * scale, scale};
+    return L.add_stencil(3, ts, as);
+  };
+  // one step from (u, prev) at time t: u* and then u^{n+1} into `star` (prev itself, or another vector), v if asked for
+  auto advance = [&](double t, const double* prev, double* star, double* v) {
+    WF_TRY(L.rhs(u));                                         // b is zero on entry
+    WF_TRY(L.add_sources(t));
+    WF_TRY(wf_leapfrog4_predict(n, dt, b, m, u, prev, star, w, d.bc, s1(t), s2, stream));
+    WF_TRY(L.rhs(w));
+    WF_TRY(sources_dd(t, 1.0 / 12.0));
+    return wf_leapfrog4_correct(n, dt, b, m, star, prev, star, v, d.bc, s1_dd(t) / 12.0, s2, stream);
+  };
+  double t = t0;
+  int64_t step = 0;
+  WF_TRY(wf_copy(n, d_u, u, stream));
+  WF_TRY(L.record(u, 0, t));
+  // start-up: a^0 in w, j^0 in scratch, q^0 in w; p = u^{-1} by its Taylor series to dt^4
+  // (the boundary term goes onto the zeroed b in front of the apply, as in wf_wave_rk4_fused: wf_boundary_apply adds by
+  // atomics, and a dof of both sets takes its two terms in either order -- onto zero that order cannot show)
+  WF_TRY(wf_fill(n, 0.0, b, stream));
+  WF_TRY(wf_boundary_apply_plan(d.bc, s1(t), s2, d_v, b, stream));
+  WF_TRY(L.add_sources(t));
+  WF_TRY(L.rhs(u));
+  WF_TRY(wf_pointwise_div(n, b, m, w, stream));
+  WF_TRY(wf_axpy(n, -dt, d_v, u, p, stream));
+  WF_TRY(wf_axpy(n, 0.5 * dt2, w, p, p, stream));
+  WF_TRY(wf_fill(n, 0.0, b, stream));
+  WF_TRY(wf_boundary_apply_plan(d.bc, s1_d1(t), s2, w, b, stream));
+  WF_TRY(sources_d1(t));
+  WF_TRY(L.rhs(d_v));
+  WF_TRY(wf_pointwise_div(n, b, m, scratch, stream));
+  WF_TRY(wf_axpy(n, -(dt2 * dt) / 6.0, scratch, p, p, stream));
+  WF_TRY(wf_fill(n, 0.0, b, stream));
+  WF_TRY(wf_boundary_apply_plan(d.bc, s1_dd(t) / dt2, s2, scratch, b, stream));
+  WF_TRY(sources_dd(t, 1.0 / dt2));
+  WF_TRY(L.rhs(w));                                           // K a^0 accumulates onto the loads; a^0 is then free
+  WF_TRY(wf_pointwise_div(n, b, m, w, stream));
+  WF_TRY(wf_axpy(n, (dt2 * dt2) / 24.0, w, p, p, stream));
+  WF_TRY(wf_fill(n, 0.0, b, stream));
+  while (t < tf) {
+    WF_TRY(advance(t, p, p, nullptr));
+    std::swap(u, p);
+    t += dt;
+    step += 1;
+    WF_TRY(L.record(u, step, t));
+    if (limit_reached(step, max_steps)) break;
+  }
+  // finish: the step after the last one out of place, u^{n+1} in scratch and the central velocity in d_v; then the
+  // central acceleration in scratch, j = (K v + L'(t) - d a) / m in w and v -= dt^2/6 j
+  WF_TRY(advance(t, p, scratch, d_v));
+  WF_TRY(wf_axpy(n, -2.0, u, scratch, scratch, stream));
+  WF_TRY(wf_axpy(n, 1.0, p, scratch, scratch, stream));
+  WF_TRY(wf_scale(n, 1.0 / dt2, scratch, stream));
+  WF_TRY(wf_boundary_apply_plan(d.bc, s1_d1(t), s2, scratch, b, stream));   // the corrector left b zero
+  WF_TRY(sources_d1(t));
+  WF_TRY(L.rhs(d_v));
+  WF_TRY(wf_pointwise_div(n, b, m, w, stream));
+  WF_TRY(wf_axpy(n, -dt2 / 6.0, w, d_v, d_v, stream));
+  WF_TRY(wf_fill(n, 0.0, b, stream));
   WF_TRY(wf_copy(n, u, d_u, stream));
   if (t_end) *t_end = t;
   if (steps) *steps = step;

@@ -90,6 +90,23 @@ def leapfrog_step(b, m, u, u_prev, u_next, dt: float, v=None, bc=None, s1: float
     check(lib().wf_leapfrog_step(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_next), vp, _stream(b)))
 
 
+def leapfrog4_predict(b, m, u, u_prev, u_star, w, dt: float, bc=None, s1: float = 0.0, s2: float = 0.0):
+    """The first pass of a fourth-order leapfrog step (wf_leapfrog4_predict, include/wavehip_leapfrog4.h): b holds K u on
+    entry and +0.0 on return, u_star = what leapfrog_step stores in u_next, w = (dt^2/12) b/m (with bc the dofs of its
+    sets take s1 c1 into b first).  u_star may be u_prev."""
+    check(lib().wf_leapfrog4_predict(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_star), _ptr(w),
+                                     bc._h if bc is not None else None, float(s1), float(s2), _stream(b)))
+
+
+def leapfrog4_correct(b, m, u_star, u_next, dt: float, u_prev=None, v=None, bc=None, s1c: float = 0.0, s2: float = 0.0):
+    """The second pass (wf_leapfrog4_correct): b holds K w on entry and +0.0 on return, u_next = u_star + dt^2 b/m, on the
+    sets of bc u_star + dt^2 (b + s1c c1) / (m + h).  u_next may be u_star; v (optional, needs u_prev) receives
+    (u_next - u_prev) / (2 dt)."""
+    check(lib().wf_leapfrog4_correct(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u_star), _ptr(u_prev) if u_prev is not None else 0,
+                                     _ptr(u_next), _ptr(v) if v is not None else 0, bc._h if bc is not None else None,
+                                     float(s1c), float(s2), _stream(b)))
+
+
 def leapfrog_correlate(lam, up, u, um, p):
     """p += lam * ((up - 2 u) + um), evaluated as written (wf_leapfrog_correlate); p must not overlap an input."""
     check(lib().wf_leapfrog_correlate(p.numel(), _ptr(lam), _ptr(up), _ptr(u), _ptr(um), _ptr(p), _stream(p)))

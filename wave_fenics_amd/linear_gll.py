@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import la
-from ._lib import WAVE_RHS_FN, WAVE_STEP_FN, WF_WAVE_LEAPFROG, WF_WAVE_RK4_FUSED, WaveDesc, WaveSource, _dp, _ip, check, lib
+from ._lib import WAVE_RHS_FN, WAVE_STEP_FN, WF_WAVE_LEAPFROG, WF_WAVE_LEAPFROG4, WF_WAVE_RK4_FUSED, WaveDesc, WaveSource, _dp, _ip, check, lib
 from .box import _int3
 from .distributed import overlapped_apply
 from .mesh_io import cfl_time_step  # noqa: F401  (demo/cpu_planar3d/main.cpp:48-66: one function for box and file meshes)
@@ -319,6 +319,31 @@ class LinearGLLOpt:
         wf_wave_leapfrog (csrc/wave_loops.cpp)."""
         return self._run(WF_WAVE_LEAPFROG, startTime, finalTime, timeStep, max_steps)
 
+    def leapfrog4(self, startTime: float, finalTime: float, timeStep: float, max_steps: int | None = None):
+        """Fourth-order leapfrog (the modified-equation scheme, Lax-Wendroff on the two-level recurrence) of the same
+        equation as leapfrog(), from (u_n, v_n) to (u_n, v_n):
+            (u+ - 2u + u-) / dt^2 = A u + (dt^2/12) A^2 u,   A = M^-1 K,
+        with the loads L and (dt^2/12)(A L + L'') beside it.  TWO stiffness applies and two streaming passes per step
+        (wf_leapfrog4_predict 56 B/dof, wf_leapfrog4_correct 40 B/dof) against the four applies of RK4, at RK4's order.
+        With x = dt^2 lambda_max the symbol x - x^2/12 stays in [0, 3] for 0 <= x <= 12: dt <= sqrt(12) / sqrt(lambda_max),
+        sqrt(3) times leapfrog's limit (stable_time_step(scheme="leapfrog4")), with and without absorbing sets.
+
+        The limit of the scheme: the centred absorbing term d u' stays SECOND order.  The result is fourth order on
+        closed, reflecting and periodic domains and in the phase error that accumulates in the interior, second order in
+        what the absorbing faces and their reflections contribute.  The order claim holds for Ricker wavelets and smooth
+        loads; a sampled wavelet is piecewise linear and its second difference is not smooth.
+
+        L' and L'' are central differences of the loads at t +- dt.  Start-up: a0, j0, q0 = the second to fourth time
+        derivatives at t0 from three applies, u^{-1} = u0 - dt v0 + dt^2/2 a0 - dt^3/6 j0 + dt^4/24 q0.  Finish: one more
+        full step into a scratch vector gives the central velocity vt and acceleration at; one more apply gives
+        j = (K vt + L' - d at) / m and v_n = vt - dt^2/6 j (the plain central velocity is second order only); u is not
+        advanced.  A run split in two equals the continuous run to TRUNCATION order, not to rounding: the start-up is a
+        Taylor series, not the inverse of the finish.
+
+        The step is constant and the last step is not shortened, as in leapfrog().  Returns (t, steps).  The loop itself is
+        wf_wave_leapfrog4 (csrc/wave_loops.cpp, include/wavehip_leapfrog4.h)."""
+        return self._run(WF_WAVE_LEAPFROG4, startTime, finalTime, timeStep, max_steps)
+
     def _guarded(self, errors, body):
         """body(*args) as a callback of the library (la.cg's trampoline): it runs under the stream the library hands over
         and lets no exception cross the C boundary -- the exception waits in `errors` for _run to raise it."""
@@ -337,13 +362,17 @@ class LinearGLLOpt:
         return call
 
     def _run(self, scheme: int, t0: float, tf: float, dt: float, max_steps, keep=None, rhs=None, work=None):
-        """One call of wf_wave_rk4_fused / wf_wave_leapfrog on (u_n, v_n): the descriptor, the work vectors and the trace
-        rows are set up here, every launch is the library's.  keep(n, t, u_prev, u, a0) (leapfrog; misfit_gradient) is
-        called before step n = 0, 1, ... with the time and the two states the step reads (a0: the vector holding the
-        start-up acceleration, valid at n = 0 only).  It may copy them; the loop's own launches and their order do not
+        """One call of wf_wave_rk4_fused / wf_wave_leapfrog / wf_wave_leapfrog4 on (u_n, v_n), by scheme: the
+        descriptor, the work vectors and the trace rows are set up here, every launch is the library's.
+        keep(n, t, u_prev, u, a0) (leapfrog alone, refused with another scheme; misfit_gradient) is called before step
+        n = 0, 1, ... with the time and the two states the step reads (a0: the vector holding the start-up acceleration,
+        valid at n = 0 only).  It may copy them; the loop's own launches and their order do not
         depend on it.  For tests: rhs(x, b), a right-hand side b += K x in place of the model's, and work, the work vectors
         (wf_wave_work_vectors of them) in place of fresh ones."""
         L, n, errors = lib(), self.u_n.numel(), []
+        fourth = scheme == WF_WAVE_LEAPFROG4
+        if keep is not None and scheme != WF_WAVE_LEAPFROG:
+            raise ValueError("LinearGLLOpt._run: keep= is the per-step callback of wf_wave_leapfrog alone")
         vec = lambda p: la._tensor_from_ptr(p, n, self.device)   # noqa: E731
         d = WaveDesc()
         d.n, d.d_m, d.d_b, d.bc = n, _ptr(self.m), _ptr(self.b), self._bc._h
@@ -368,12 +397,15 @@ class LinearGLLOpt:
             if len(rec):
                 d.receivers, d.d_traces = rec._h, rec.reserve(rows, self.device)
         if work is None:
-            work = [torch.empty_like(self.u_n) for _ in range(L.wf_wave_work_vectors(scheme))]
+            nwork = L.wf_wave_leapfrog4_work_vectors() if fourth else L.wf_wave_work_vectors(scheme)
+            work = [torch.empty_like(self.u_n) for _ in range(nwork)]
         d.d_work = (ctypes.c_void_p * len(work))(*[_ptr(x) for x in work])
         t_end, steps = ctypes.c_double(t0), ctypes.c_int64(0)
         args = (ctypes.byref(d), t0, tf, dt, max_steps, _ptr(self.u_n), _ptr(self.v_n))
         out = (ctypes.byref(t_end), ctypes.byref(steps), _stream(self.u_n))
-        if scheme == WF_WAVE_LEAPFROG:
+        if fourth:
+            rc = L.wf_wave_leapfrog4(*args, *out)
+        elif scheme == WF_WAVE_LEAPFROG:
             step_fn = WAVE_STEP_FN()
             if keep is not None:
                 call_keep = self._guarded(errors, lambda k, t, pw, pu, pa: keep(k, t, vec(pw), vec(pu), vec(pa)))
@@ -545,11 +577,15 @@ class LinearGLLOpt:
             x, mx = mx, x
         return lam
 
-    def stable_time_step(self, safety: float = 0.9, iters: int = 100):
+    def stable_time_step(self, safety: float = 0.9, iters: int = 100, scheme: str = "leapfrog"):
         """safety * 2 / sqrt(lambda_max(-M^{-1} K)): a stable step of leapfrog() (its limit is 2 / sqrt(lambda_max), with or
         without the absorbing term).  max_eigenvalue approaches lambda_max from below, so the limit is overestimated by
-        up to ~0.04 % after 100 iterations; safety covers it.  One rank."""
-        return safety * 2.0 / math.sqrt(self.max_eigenvalue(iters))
+        up to ~0.04 % after 100 iterations; safety covers it.  scheme="leapfrog4": sqrt(3) times that, a stable step of
+        leapfrog4() (limit sqrt(12) / sqrt(lambda_max)).  One rank."""
+        if scheme not in ("leapfrog", "leapfrog4"):
+            raise ValueError(f"stable_time_step: scheme must be 'leapfrog' or 'leapfrog4', got {scheme!r}")
+        dt = safety * 2.0 / math.sqrt(self.max_eigenvalue(iters))
+        return dt * math.sqrt(3.0) if scheme == "leapfrog4" else dt
 
     def cell_forms(self):
         """(stiffness form, lumped-mass form) of the model's operators: operators.CellForm with the model's c0, or with

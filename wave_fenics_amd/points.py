@@ -246,6 +246,16 @@ class Sources(_Points):
         _check_vec(b, self.V.ndofs, "Sources.add b")
         check(lib().wf_sources_add(self._s, float(t), _ptr(b), _stream(b)))
 
+    def add_stencil(self, times, weights, b):
+        """b[d] += sum_i S_i phi_d(x_i), S_i = ((a_0 s_i(t_0)) + a_1 s_i(t_1)) + a_2 s_i(t_2) over the one to three (times,
+        weights) given: a difference quotient of the load in one launch (wf_sources_add_stencil)."""
+        t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+        a = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if t.size != a.size:
+            raise ValueError(f"Sources.add_stencil: {t.size} times but {a.size} weights")
+        _check_vec(b, self.V.ndofs, "Sources.add_stencil b")
+        check(lib().wf_sources_add_stencil(self._s, int(t.size), _dp(t), _dp(a), _ptr(b), _stream(b)))
+
     def add_values(self, values, b, scale: float = 1.0):
         """b[d] += scale * sum_i values[i] phi_d(x_i): the wavelets are not looked at, values (a contiguous float64 device
         vector of len(self) entries, which may be a row of a larger buffer) takes their place (wf_sources_add_values)."""
