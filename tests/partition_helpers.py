@@ -11,10 +11,20 @@ Two scenarios on the global box [0, 0.01]^3, c0 = 1500, f = 0.5 MHz:
   of a source face cut by a rank interface in the run.
 
 The references are the single-domain oracle on the global mesh (oracle.make_periodic first in the periodic case):
-leapfrog_helpers.leapfrog for leapfrog, oracle.LinearGLLOpt.rk4 for RK4.  Local vectors are the global ones taken
-through dist_helpers.local_to_global, ghosts included."""
+leapfrog_helpers.leapfrog for leapfrog, leapfrog4_helpers.leapfrog4 for the fourth-order leapfrog (at the leapfrog
+runs' step, inside its own limit, which is sqrt(3) times leapfrog's), oracle.LinearGLLOpt.rk4 for RK4.  Local vectors are
+the global ones taken through dist_helpers.local_to_global, ghosts included.
+
+Mutants of the leapfrog4 reference, for the host test (mutant= of reference()): each wraps the stepper's K and counts its
+calls -- three applies in the start-up (K u0, K v0, K a0), two per step (K u, K w), three in the finish (K u, K w, K vt):
+
+* "second_apply": the operand of every step's second apply (the finish's included) is zeroed on the interface planes
+  -- the forward halo of w not made;
+* "startup_v": the operand of the second start-up apply, v0, is zeroed there -- the forward halo of v not made;
+* "rounding": no mutant, the yardstick of the bound: every apply's result times (1 + 2^-52)."""
 import numpy as np
 
+import leapfrog4_helpers as l4
 import leapfrog_helpers as lh
 from support import relerr  # noqa: F401
 
@@ -33,6 +43,7 @@ CASES = {
     "w8_p4": dict(world=8, procs=(2, 2, 2), p=4, n=(2, 2, 2), periodic=(False, False, False), cfl_lf=0.5, cfl_rk=0.25),
     "w2_p2_periodic": dict(world=2, procs=(2, 1, 1), p=2, n=(3, 4, 4), periodic=(True, True, False), cfl_lf=0.5, cfl_rk=0.25),
 }
+MUTANTS = ("second_apply", "startup_v", "rounding")
 _MESH, _REF = {}, {}
 
 
@@ -62,7 +73,7 @@ def global_mesh(oracle, case):
 
 def time_step(oracle, case, scheme):
     c = CASES[case]
-    return oracle.cfl_time_step(global_mesh(oracle, case), c["p"], C0, FREQ, CFL=c["cfl_lf" if scheme == "leapfrog" else "cfl_rk"])[0]
+    return oracle.cfl_time_step(global_mesh(oracle, case), c["p"], C0, FREQ, CFL=c["cfl_lf" if scheme in ("leapfrog", "leapfrog4") else "cfl_rk"])[0]
 
 
 def initial_state(ndofs, dt, scenario):
@@ -91,11 +102,49 @@ def interface_planes(case):
     return planes
 
 
-def reference(oracle, case, scheme, scenario, steps=STEPS, halve_mG2=None):
-    """(dt, u_n, v_n) of the single-domain oracle after `steps` steps, computed once per key.  halve_mG2: a mask of global
-    dofs whose absorbing facet mass is halved (the mutant of the host test: masses not assembled across ranks)."""
+def mutated(K, mutant, steps, planes):
+    """K of the stepper under a mutant of the module docstring (steps: the steps of the ONE call of leapfrog4 that
+    follows; planes: a mask of dofs).  Returns (the wrapper, a list holding the number of calls made)."""
+    assert mutant in MUTANTS, mutant
+    calls = [0]
+    second = {3 + 2 * k + 1 for k in range(steps + 1)}
+
+    def wrapped(u):
+        i = calls[0]
+        calls[0] += 1
+        if (mutant == "second_apply" and i in second) or (mutant == "startup_v" and i == 1):
+            u = np.where(planes, 0.0, u)
+        y = K(u)
+        return y * (1.0 + 2.0 ** -52) if mutant == "rounding" else y
+    return wrapped, calls
+
+
+def run_stepper(ref, scheme, dt, segments, mutant=None, planes=None):
+    """the numpy stepper of `scheme` ("leapfrog", "leapfrog4") on the oracle model ref from its (u_n, v_n): one call per
+    entry of segments (numbers of steps), each from the (t, u_n, v_n) the one before left.  Returns t."""
+    K, s1, s2 = lh.oracle_parts(ref)
+    calls = None
+    if mutant is not None:
+        assert scheme == "leapfrog4" and len(segments) == 1
+        K, calls = mutated(K, mutant, segments[0], planes)
+    step = l4.leapfrog4 if scheme == "leapfrog4" else lh.leapfrog
+    t = 0.0
+    for k, n in enumerate(segments):
+        # the first call as the models' tests make it, the later ones as a restart does: from t, max_steps alone
+        t, took = step(ref, K, s1, s2, t, n * dt - 1e-13, dt) if k == 0 else step(ref, K, s1, s2, t, 1.0, dt, max_steps=n)
+        assert took == n
+    assert calls is None or calls[0] == 3 + 2 * segments[0] + 3, calls
+    return t
+
+
+def reference(oracle, case, scheme, scenario, steps=STEPS, halve_mG2=None, mutant=None):
+    """(dt, u_n, v_n) of the single-domain oracle after `steps` steps, computed once per key.  steps: a number, or a tuple
+    (steps_a, steps_b, ...) -- the split reference of a restarted run, one call of the stepper per entry (leapfrog and
+    leapfrog4).  halve_mG2: a mask of global dofs whose absorbing facet mass is halved (the mutant of the host test:
+    masses not assembled across ranks).  mutant: one of MUTANTS, on the interface planes of the case (leapfrog4)."""
     key = (case, scheme, scenario, steps)
-    if halve_mG2 is None and key in _REF:
+    plain = halve_mG2 is None and mutant is None
+    if plain and key in _REF:
         return _REF[key]
     c = CASES[case]
     om = global_mesh(oracle, case)
@@ -108,15 +157,17 @@ def reference(oracle, case, scheme, scenario, steps=STEPS, halve_mG2=None):
     ref.init()
     ref.u_n[:] = u0
     ref.v_n[:] = v0
-    if scheme == "leapfrog":
-        t, n = lh.leapfrog(ref, *lh.oracle_parts(ref), 0.0, steps * dt - 1e-13, dt)
+    if scheme in ("leapfrog", "leapfrog4"):
+        planes = np.logical_or.reduce(list(interface_planes(case).values())) if mutant is not None else None
+        run_stepper(ref, scheme, dt, steps if isinstance(steps, tuple) else (steps,), mutant, planes)
     else:
+        assert mutant is None and not isinstance(steps, tuple)
         t, n = ref.rk4(0.0, steps * dt - 1e-13, dt)
-    assert n == steps
+        assert n == steps
     out = (dt, ref.u_n.copy(), ref.v_n.copy())
     for a in out[1:]:
         a.setflags(write=False)
-    if halve_mG2 is None:
+    if plain:
         _REF[key] = out
     return out
 

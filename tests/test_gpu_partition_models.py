@@ -1,4 +1,4 @@
-"""LinearGLLOpt.leapfrog / rk4 / rk4_fused on real partitions of 2 and 4 ranks and a periodic pair, from a state in which every plane where
+"""LinearGLLOpt.leapfrog / leapfrog4 / rk4 / rk4_fused on real partitions of 2 and 4 ranks and a periodic pair, from a state in which every plane where
 ranks meet is live from the first step (partition_helpers; test_partition_scenario_host.py shows on the oracle that the
 scenario can see an error made there), and the C++ model's leapfrog on a partition.
 
@@ -11,7 +11,21 @@ test_gpu_leapfrog_model.py, the RK4 bound of test_distributed_on_one_gpu); 5 + 5
 (test_restart); one apply to 1e-12.  Exact: every ghost entry of u_n and v_n carries its owner's bits, and the owned
 entries of all ranks cover every global dof once.  Leapfrog with the interior / interface overlap and without it sum the
 cells of a dof in different orders, so nothing in the code says they agree bit for bit: the number of differing entries is
-printed and each run is held to the reference."""
+printed and each run is held to the reference.
+
+Leapfrog4 (the same four variants as leapfrog, both scenarios, at the leapfrog step): two applies per step, the second on
+the predictor's w, whose ghosts only its forward halo makes right; v_n is an operand of an apply in the start-up and in
+the finish, which no other loop exchanges; the finish corrects v_n at ghost entries too, and the closing forward halo
+restores the owner's bits.  Here ranks meet over gloo, so every halo is the model's _rhs as the loop's callback
+(test_gpu_leapfrog4_partition.py drives the library's own exchange).  Rows of the parent:
+  {scenario}/l4_*    u_n, v_n to 1e-9 against leapfrog4_helpers.leapfrog4 on the oracle; ghosts bit for bit their owner's
+  restart/l4_parts   5 + 5 steps to 1e-9 against the stepper SPLIT 5 + 5 (a split run differs from the continuous one by
+                     truncation, 5e-4 to 9e-2 here: the start-up is a Taylor series, not the inverse of the finish)
+  stale/l4_*         v_n's ghost entries overwritten with -7 / (STEPS dt) before the run (u_n's stay consistent): to 1e-9
+                     against the same reference, box and dofmap path; the entries that differ in bits from the run with
+                     consistent ghosts are counted and printed
+test_partition_scenario_host.py shows that the random state sees a halo of w or of v that is not made, and that from rest
+the start-up's apply on v multiplies zeros."""
 import os
 import queue
 import subprocess
@@ -30,6 +44,8 @@ TOL, TOL_RESTART, TOL_APPLY = 1e-9, 1e-11, 1e-12
 CPUS = 16                                   # what a run is given; nothing here is sized by the machine's count
 LEAPFROG = {"lf_box_split": (True, True), "lf_box_unsplit": (True, False), "lf_map_split": (False, True),
             "lf_map_unsplit": (False, False)}          # name: (structured, split)
+LEAPFROG4 = {name.replace("lf_", "l4_"): variant for name, variant in LEAPFROG.items()}      # the same four, eqn.leapfrog4
+STALE = {"l4_box": True, "l4_map": False}              # stale ghosts of v_n: name: structured (both split)
 APPLY_SEED = 5
 
 
@@ -85,6 +101,11 @@ def _worker(rank, world, port, case, dts, q):
                 t, steps = eqn.leapfrog(0.0, ph.STEPS * dt - 1e-13, dt)
                 assert steps == ph.STEPS
                 out[f"{scenario}/{name}"] = state(eqn)
+            for name, (structured, split) in LEAPFROG4.items():
+                eqn = model(structured, split, scenario, dt)
+                t, steps = eqn.leapfrog4(0.0, ph.STEPS * dt - 1e-13, dt)
+                assert steps == ph.STEPS
+                out[f"{scenario}/{name}"] = state(eqn)
             dt = dts["rk4"]
             for name in ("rk4", "rk4_fused"):
                 eqn = model(True, True, scenario, dt)
@@ -99,6 +120,20 @@ def _worker(rank, world, port, case, dts, q):
         t, n2 = parts.leapfrog(t, 1.0, dt, max_steps=5)
         assert (n1, n2) == (5, 5)
         out["restart/whole"], out["restart/parts"] = state(whole), state(parts)
+        # leapfrog4: 5 + 5 steps, the second call from the first's t (the parent holds it to the stepper split likewise)
+        parts = model(True, True, "random", dt)
+        t, n1 = parts.leapfrog4(0.0, 5 * dt - 1e-13, dt)
+        t, n2 = parts.leapfrog4(t, 1.0, dt, max_steps=5)
+        assert (n1, n2) == (5, 5)
+        out["restart/l4_parts"] = state(parts)
+        # leapfrog4 from a v_n whose ghost entries are wrong (finite, of the size of v0); u_n's stay consistent
+        ghost = torch.from_numpy(~owned).to(dev)      # (the lowest rank owns all it shares: the parent asserts that some rank has ghosts)
+        for name, structured in STALE.items():
+            eqn = model(structured, True, "random", dt)
+            eqn.v_n[ghost] = -7.0 / (ph.STEPS * dt)
+            t, steps = eqn.leapfrog4(0.0, ph.STEPS * dt - 1e-13, dt)
+            assert steps == ph.STEPS
+            out[f"stale/{name}"] = state(eqn)
         if c["procs"][2] > 1:
             # one apply across a z interface between different ranks, both paths
             xg = np.random.default_rng(APPLY_SEED).uniform(-1, 1, nd)
@@ -174,7 +209,8 @@ GPU_CASES = [name for name, c in ph.CASES.items() if c["world"] < 8]
 def test_models_on_partitions(gpu, oracle, case):
     c = ph.CASES[case]
     om = ph.global_mesh(oracle, case)
-    dts = {s: ph.time_step(oracle, case, s) for s in ("leapfrog", "rk4")}
+    dts = {s: ph.time_step(oracle, case, s) for s in ("leapfrog", "rk4", "leapfrog4")}
+    assert dts["leapfrog4"] == dts["leapfrog"], "the workers run both at the leapfrog step"
     t0 = time.monotonic()
     ranks = run_workers(case, dts)
     wall = time.monotonic() - t0
@@ -203,8 +239,8 @@ def test_models_on_partitions(gpu, oracle, case):
 
     results = {}
     for scenario in ph.SCENARIOS:
-        for variant in (*LEAPFROG, "rk4", "rk4_fused"):
-            scheme = "leapfrog" if variant in LEAPFROG else "rk4"
+        for variant in (*LEAPFROG, *LEAPFROG4, "rk4", "rk4_fused"):
+            scheme = "leapfrog" if variant in LEAPFROG else "leapfrog4" if variant in LEAPFROG4 else "rk4"
             dt, uref, vref = ph.reference(oracle, case, scheme, scenario)
             assert dt == dts[scheme]
             if scenario == "rest" and not any(c["periodic"]):
@@ -215,7 +251,8 @@ def test_models_on_partitions(gpu, oracle, case):
             print(f"{case} {key}: u {eu:.3e} v {ev:.3e}")
             if not (eu <= TOL and ev <= TOL):
                 failures.append(f"{key}: u {eu:.3e} v {ev:.3e} against the oracle, bound {TOL:.0e}")
-        for a, b in (("lf_box_split", "lf_box_unsplit"), ("lf_map_split", "lf_map_unsplit")):
+        for a, b in (("lf_box_split", "lf_box_unsplit"), ("lf_map_split", "lf_map_unsplit"),
+                     ("l4_box_split", "l4_box_unsplit"), ("l4_map_split", "l4_map_unsplit")):
             du, dv = (ph.differing_entries(x, y) for x, y in zip(results[f"{scenario}/{a}"], results[f"{scenario}/{b}"]))
             print(f"{case} {scenario}: {a} against {b}: {du} of {om.ndofs} entries of u_n and {dv} of v_n differ in their bits")
     (uw, vw), (up, vp) = glob("restart/whole"), glob("restart/parts")
@@ -223,6 +260,27 @@ def test_models_on_partitions(gpu, oracle, case):
     print(f"{case} restart 5 + 5 against 10: u {du:.3e} v {dv:.3e}")
     if not (du <= TOL_RESTART and dv <= TOL_RESTART):
         failures.append(f"restart: u {du:.3e} v {dv:.3e}, bound {TOL_RESTART:.0e}")
+    # leapfrog4, 5 + 5: against the numpy stepper split the same way, to TOL -- not to TOL_RESTART against a 10-step run: its
+    # start-up is a Taylor series, not the inverse of its finish, so a split run differs from the continuous one by
+    # truncation (5e-4 to 9e-2 here on the oracle), which no bound on rounding can hold
+    _, uref, vref = ph.reference(oracle, case, "leapfrog4", "random", steps=(5, 5))
+    up, vp = glob("restart/l4_parts")
+    du, dv = ph.relerr(up, uref), ph.relerr(vp, vref)
+    print(f"{case} leapfrog4 restart 5 + 5 against the stepper split 5 + 5: u {du:.3e} v {dv:.3e}")
+    if not (du <= TOL and dv <= TOL):
+        failures.append(f"restart/l4_parts: u {du:.3e} v {dv:.3e} against the split stepper, bound {TOL:.0e}")
+    # leapfrog4 from stale ghosts of v_n: the loop exchanges v before its start-up apply reads a ghost of it, so the run
+    # is held to the same reference as the run from consistent ghosts
+    _, uref, vref = ph.reference(oracle, case, "leapfrog4", "random")
+    for name, structured in STALE.items():
+        us, vs = glob(f"stale/{name}")
+        du, dv = ph.relerr(us, uref), ph.relerr(vs, vref)
+        uc, vc = results[f"random/{name}_split"]
+        print(f"{case} leapfrog4 from stale ghosts of v_n, {name}: u {du:.3e} v {dv:.3e}; {ph.differing_entries(us, uc)} of {om.ndofs} "
+              f"entries of u_n and {ph.differing_entries(vs, vc)} of v_n differ in their bits from the run with consistent ghosts")
+        if not (du <= TOL and dv <= TOL):
+            failures.append(f"stale/{name}: u {du:.3e} v {dv:.3e} against the oracle, bound {TOL:.0e}: a ghost of v_n is read "
+                            "before it is exchanged")
     if c["procs"][2] > 1:
         xg = np.random.default_rng(APPLY_SEED).uniform(-1, 1, om.ndofs)
         yref = np.zeros(om.ndofs)

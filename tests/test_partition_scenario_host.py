@@ -20,13 +20,20 @@ not tolerances -- they keep the GPU test from being blind):
   (measured with seed 11: 0.51 to 1.0 for leapfrog);
 * a mutant is visible: the same run with the absorbing facet mass mG2 halved on the interface planes -- masses not
   assembled across ranks -- moves u_n by >= 1e-3 of its maximum (measured: 0.09 to 0.18 for leapfrog), eight orders
-  of magnitude above the GPU test's bound of 1e-9."""
+  of magnitude above the GPU test's bound of 1e-9.
+
+The fourth-order leapfrog is held to both conditions as well (measured: 0.67 to 1.0; 0.07 to 0.19), and has halos of its
+own -- of w, the operand of each step's second apply, and of v, an operand of its start-up and finish
+(test_leapfrog4_halo_mutants_are_visible).  Measured on the four cases, as the larger of the moves of u_n and v_n: the
+second apply's operand zeroed on the interface planes 0.11 to 1.2; the start-up's K v0 operand zeroed there 2.3e-3 to
+8.2e-3 (and exactly nothing from rest); every apply perturbed by one rounding 2.0e-15 to 5.1e-15."""
 import numpy as np
 import pytest
 
 import partition_helpers as ph
 
 LIVE, VISIBLE = 0.25, 1e-3
+MUTANT_VISIBLE, ROUNDING = 1e-4, 1e-11     # leapfrog4: 1e5 times the GPU bound of 1e-9, and a hundredth of it
 
 
 def plane_ratios(case, u):
@@ -34,7 +41,7 @@ def plane_ratios(case, u):
     return {name: float(np.abs(u[mask]).max() / top) for name, mask in ph.interface_planes(case).items()}
 
 
-@pytest.mark.parametrize("scheme", ["leapfrog", "rk4"])
+@pytest.mark.parametrize("scheme", ["leapfrog", "rk4", "leapfrog4"])
 @pytest.mark.parametrize("case", list(ph.CASES))
 def test_interfaces_are_live_and_a_mutant_is_visible(oracle, case, scheme):
     dt, u, v = ph.reference(oracle, case, scheme, "random")
@@ -47,6 +54,39 @@ def test_interfaces_are_live_and_a_mutant_is_visible(oracle, case, scheme):
           + ", ".join(f"{k}: {r:.3f}" for k, r in ratios.items()) + f"; mutant moves u_n by {moved:.3e}")
     assert min(ratios.values()) >= LIVE, ratios
     assert moved >= VISIBLE
+
+
+@pytest.mark.parametrize("case", list(ph.CASES))
+def test_leapfrog4_halo_mutants_are_visible(oracle, case):
+    """The fourth-order leapfrog exchanges more than the other loops: the operand w of every step's second apply, and v,
+    an operand of the start-up's K v0 and the finish's K vt.  From the random state each of three mutants -- the
+    absorbing facet mass halved on the interface planes, the operand of every second apply zeroed there, the operand
+    of the start-up's K v0 zeroed there (partition_helpers) -- moves u_n or v_n by at least MUTANT_VISIBLE of its maximum,
+    1e5 times the GPU test's bound of 1e-9; and the unmutated stepper with every apply's result perturbed by one rounding
+    moves them by at most ROUNDING, a hundredth of that bound (measured: 1.8e-15), so the bound has the headroom.
+
+    From REST the start-up's K v0 multiplies zeros: zeroing its operand on the interface planes changes the result by
+    exactly nothing, bit for bit (asserted on the non-periodic cases, the ones with a source).  A run from rest cannot
+    see a forward halo of v that is not made: the reason the GPU runs of leapfrog4 use the random state."""
+    dt, u, v = ph.reference(oracle, case, "leapfrog4", "random")
+    assert np.isfinite(u).all() and np.isfinite(v).all()
+    on_planes = np.logical_or.reduce(list(ph.interface_planes(case).values()))
+    moved = {}
+    for name, kw in (("halve_mG2", dict(halve_mG2=on_planes)), ("second_apply", dict(mutant="second_apply")),
+                     ("startup_v", dict(mutant="startup_v")), ("rounding", dict(mutant="rounding"))):
+        dtm, um, vm = ph.reference(oracle, case, "leapfrog4", "random", **kw)
+        assert dtm == dt
+        moved[name] = (ph.relerr(um, u), ph.relerr(vm, v))
+    print(f"{case} leapfrog4, random state: max |u| {np.abs(u).max():.3f}; moved (u, v): "
+          + ", ".join(f"{k}: {a:.3e} {b:.3e}" for k, (a, b) in moved.items()))
+    for name in ("halve_mG2", "second_apply", "startup_v"):
+        assert max(moved[name]) >= MUTANT_VISIBLE, (name, moved[name])
+    assert max(moved["rounding"]) <= ROUNDING, moved["rounding"]
+    if not any(ph.CASES[case]["periodic"]):
+        _, u, v = ph.reference(oracle, case, "leapfrog4", "rest")
+        _, um, vm = ph.reference(oracle, case, "leapfrog4", "rest", mutant="startup_v")
+        assert np.abs(u).max() > 0.0 and np.abs(v).max() > 0.0
+        assert ph.differing_entries(um, u) == 0 and ph.differing_entries(vm, v) == 0
 
 
 @pytest.mark.parametrize("case", ["w2_p2", "w4_p4"])

@@ -39,6 +39,9 @@ def call(wlib, entry, d, u=FAKE + 0x7000, v=FAKE + 0x8000, t0=0.0, tf=4.5, dt=1.
     args = (None if d is None else ctypes.byref(d), t0, tf, dt, max_steps, u, v)
     if entry == "wf_wave_leapfrog":
         rc = L.wf_wave_leapfrog(*args, wlib.WAVE_STEP_FN(), None, ctypes.byref(t_end), ctypes.byref(steps), None)
+    elif entry == "wf_wave_leapfrog4":
+        assert entry in wlib.SIGNATURES_LEAPFROG4 and entry not in wlib.SIGNATURES      # the second table of _lib.py
+        rc = L.wf_wave_leapfrog4(*args, ctypes.byref(t_end), ctypes.byref(steps), None)
     else:
         rc = L.wf_wave_rk4_fused(*args, ctypes.byref(t_end), ctypes.byref(steps), None)
     assert t_end.value == -1.0 and steps.value == -1       # a refused call writes nothing
@@ -65,13 +68,23 @@ DESC_DEFECTS = {
 }
 
 
-@pytest.mark.parametrize("entry", ["wf_wave_rk4_fused", "wf_wave_leapfrog"])
+# the work vectors each entry asks for: a null one among them is refused, whichever it is, and one beyond them is not read
+WORK_VECTORS = {"wf_wave_rk4_fused": 7, "wf_wave_leapfrog": 3, "wf_wave_leapfrog4": 4}
+
+
+@pytest.mark.parametrize("entry", ["wf_wave_rk4_fused", "wf_wave_leapfrog", "wf_wave_leapfrog4"])
 def test_refusals_before_any_launch(wlib, entry):
     for name, (defect, text) in DESC_DEFECTS.items():
         d = descriptor(wlib)
         defect(d)
         rc, msg = call(wlib, entry, d)
         assert rc == INVALID and msg == f"{entry}: {text}", (name, rc, msg)
+    # each work vector alone null, the others not -- for wf_wave_leapfrog4 the fourth, which wf_wave_leapfrog never reads
+    for k in range(WORK_VECTORS[entry]):
+        d = descriptor(wlib)
+        d.d_work = (ctypes.c_void_p * 7)(*[None if j == k else FAKE + 0x10000 * (j + 1) for j in range(7)])
+        rc, msg = call(wlib, entry, d)
+        assert rc == INVALID and msg == f"{entry}: null work", (k, rc, msg)
     rc, msg = call(wlib, entry, None)
     assert rc == INVALID and msg == f"{entry}: null descriptor", (rc, msg)
     for state in ({"u": None}, {"v": None}):
@@ -125,6 +138,8 @@ def test_step_count(wlib):
     assert {0, 1, 3, 5, 1000, 1001} <= seen, sorted(seen)
     assert L.wf_wave_work_vectors(wlib.WF_WAVE_RK4_FUSED) == 7 and L.wf_wave_work_vectors(wlib.WF_WAVE_LEAPFROG) == 3
     assert L.wf_wave_work_vectors(2) == -1 and L.wf_wave_work_vectors(-1) == -1
+    # the fourth-order leapfrog has its own count (include/wavehip_leapfrog4.h); scheme 2 stays unknown to the first
+    assert wlib.WF_WAVE_LEAPFROG4 == 2 and L.wf_wave_leapfrog4_work_vectors() == WORK_VECTORS["wf_wave_leapfrog4"] == 4
 
 
 def test_descriptor_layout(wlib, tmp_path):
