@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "wavehip.h"
+#include "wavehip_adjoint4.h"
 
 namespace wavehip {
 
@@ -562,6 +563,15 @@ inline void leapfrog_correlate(std::int64_t n, const double* d_lam, const double
                                double* d_p, void* stream = nullptr)
 {
   check(wf_leapfrog_correlate(n, d_lam, d_up, d_u, d_um, d_p, stream));
+}
+
+/// p = (p + lam * ((up - 2 u) + um)) + 12 (om * w) and, with d_z, z = u + w over n entries, evaluated as written
+/// (wf_leapfrog4_correlate, wavehip_adjoint4.h): the per-step terms of the fourth-order leapfrog loop's discrete adjoint.
+/// p and z must not overlap an input or each other.
+inline void leapfrog4_correlate(std::int64_t n, const double* d_lam, const double* d_om, const double* d_up, const double* d_u,
+                                const double* d_um, const double* d_w, double* d_p, double* d_z = nullptr, void* stream = nullptr)
+{
+  check(wf_leapfrog4_correlate(n, d_lam, d_om, d_up, d_u, d_um, d_w, d_p, d_z, stream));
 }
 
 // ---- point sources and receivers (wf_points_*, wf_sources_*; not in the reference) ----

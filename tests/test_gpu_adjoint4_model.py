@@ -1,0 +1,209 @@
+"""LinearGLLOpt.misfit_gradient(scheme="leapfrog4") on the device against the numpy adjoint of tests/adjoint4_helpers.py,
+on the scenario of tests/test_adjoint4_host.py: P2 and P4 on the structured box (owner-computes stiffness kernel: bitwise
+repeatable), P4 on a perturbed box through the dofmap path (structured=False: atomic accumulation, repeatable to rounding
+only) and P2 without a medium.
+
+Bounds.  Gradient and J: 8 x D64_4 (adjoint4_helpers: what float64 rounding does to the numpy gradient, 1e-14 of max|g|),
+the rule of tests/test_gpu_adjoint_model.py.  Directional derivative: 8 x what the float64 numpy stepper reaches with
+the same step DIR_H and the same direction on the same configuration (truncation).  Without a medium the model has no
+coefficient array to move, so that configuration has no directional test."""
+import numpy as np
+import pytest
+
+import adjoint4_helpers as a4
+import adjoint_helpers as ah
+from support import bits, gpu  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+#           degree, perturb, medium, structured
+CONFIGS = {"P2": (2, 0.0, True, True), "P4": (4, 0.0, True, True), "P4-perturbed-dofmap": (4, 0.2, True, False),
+           "P2-no-medium": (2, 0.0, False, True)}
+N = a4.STEPS
+_made = {}
+
+
+def made(name, gpu):
+    """(scenario, numpy float64 adjoint, model, the first misfit_gradient with the default S) of a configuration, once"""
+    import torch
+    if name not in _made:
+        p, perturb, medium, structured = CONFIGS[name]
+        sc, g64, _, _ = a4.reference(p, (2, 2, 2), perturb, medium)
+        eqn = ah.device_model(sc, gpu, structured)
+        if structured:
+            assert eqn.stiff_op.update == "owner"
+        J, gK, gM, info = eqn.misfit_gradient(0.0, a4.tf(sc), sc.dt, sc.observed, scheme="leapfrog4")
+        torch.cuda.synchronize()
+        first = (J, gK.cpu().numpy(), gM.cpu().numpy(), info, eqn.receivers.traces.cpu().numpy().copy(),
+                 eqn.u_n.cpu().numpy(), eqn.v_n.cpu().numpy())
+        _made[name] = (sc, g64, eqn, first)
+    return _made[name]
+
+
+def same(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def launches(N, S, s=1):
+    """info["launches"] as the docstring of LinearGLLOpt._misfit_gradient4 states it"""
+    ncp = -(-N // S)
+    return 36 + 6 * s + N * (5 + 2 * s) + 2 * ncp + (N * (4 + 2 * s) + 5 * N + 3 * (N - 1) + 8 if N > 0 else 0)
+
+
+@pytest.mark.parametrize("name", sorted(CONFIGS))
+def test_forward_run_is_leapfrog4(gpu, name):
+    import torch
+    sc, _, eqn, first = made(name, gpu)
+    ah.reset(eqn, sc, gpu)
+    t, steps = eqn.leapfrog4(0.0, a4.tf(sc), sc.dt)
+    torch.cuda.synchronize()
+    assert steps == N == first[3]["N"] == first[3]["steps"] and t == first[3]["t"]
+    traces, u, v = eqn.receivers.traces.cpu().numpy(), eqn.u_n.cpu().numpy(), eqn.v_n.cpu().numpy()
+    assert traces.shape == (N + 1, 4) and len(eqn.trace_times) == N + 1
+    if CONFIGS[name][3]:
+        assert same(traces, first[4]) and same(u, first[5]) and same(v, first[6])
+    else:
+        for a, b in ((traces, first[4]), (u, first[5]), (v, first[6])):
+            assert np.abs(a - b).max() <= 1e-12 * np.abs(b).max()
+
+
+@pytest.mark.parametrize("name", sorted(CONFIGS))
+def test_gradient_and_misfit_against_numpy(gpu, name):
+    sc, g64, _, first = made(name, gpu)
+    J, gK, gM = first[:3]
+    assert gK.shape == gM.shape == (sc.nc,)
+    tol = 8.0 * a4.D64_4
+    eJ = abs(J - float(g64[0])) / float(g64[0])
+    e = [float(np.abs(g - r).max() / np.abs(r).max()) for g, r in ((gK, g64[1]), (gM, g64[2]))]
+    print(f"ADJOINT4 model {name}: |g - numpy| / max|g| = {e[0]:.2e} (stiffness) {e[1]:.2e} (mass), J {eJ:.2e}; allowed {tol:.1e}")
+    assert max(e) <= tol and eJ <= tol
+
+
+@pytest.mark.parametrize("name", [k for k in sorted(CONFIGS) if CONFIGS[k][2]])
+def test_directional_derivative(gpu, name):
+    import torch
+    sc, g64, _, first = made(name, gpu)
+    structured = CONFIGS[name][3]
+    reach, dK, dM = ah.directional(sc, ah.DIR_H, lambda a, b: float(a4.misfit(sc, a, b, np.float64)))
+    size = float(np.abs(g64[1]) @ np.abs(dK) + np.abs(g64[2]) @ np.abs(dM))
+    reached = abs(reach - float(g64[1] @ dK + g64[2] @ dM))
+
+    def run(aK, aM):
+        eqn = ah.device_model(sc, gpu, structured, coefficients=(aK, aM))
+        J = eqn.misfit_gradient(0.0, a4.tf(sc), sc.dt, sc.observed, scheme="leapfrog4")[0]
+        torch.cuda.synchronize()
+        return J
+
+    fd, _, _ = ah.directional(sc, ah.DIR_H, run)
+    gd = float(first[1] @ dK + first[2] @ dM)
+    print(f"ADJOINT4 model {name}: directional FD {fd:.12e}, g.delta {gd:.12e}: {abs(fd - gd) / size:.2e} of sum |g||delta a|, "
+          f"numpy reaches {reached / size:.2e}")
+    assert abs(fd - gd) <= 8.0 * reached
+
+
+@pytest.mark.parametrize("name", sorted(CONFIGS))
+def test_checkpointing_repeats_and_info(gpu, name):
+    import torch
+    sc, g64, eqn, first = made(name, gpu)
+    structured = CONFIGS[name][3]
+    assert first[3]["S"] == 5 and first[3]["vectors"] == 2 * 5 + 2 * 5 + 10        # ceil(sqrt(23)) = 5, 5 segments
+    for S in (None, 1, 3, 5, 23, 100):
+        ah.reset(eqn, sc, gpu)
+        J, gK, gM, info = eqn.misfit_gradient(0.0, a4.tf(sc), sc.dt, torch.from_numpy(sc.observed.copy()).to(gpu), checkpoint_every=S,
+                                              scheme="leapfrog4")
+        torch.cuda.synchronize()
+        gK, gM = gK.cpu().numpy(), gM.cpu().numpy()
+        Su = 5 if S is None else S
+        assert info["N"] == N == info["steps"] and info["S"] == Su and info["t"] == first[3]["t"]
+        assert info["vectors"] == 2 * -(-N // Su) + 2 * min(Su, N) + 10 and info["bytes"] == info["vectors"] * sc.ndofs * 8
+        assert info["launches"] == launches(N, Su)
+        if structured:
+            assert J == first[0] and same(gK, first[1]) and same(gM, first[2]), f"S = {S}"
+            assert same(eqn.receivers.traces.cpu().numpy(), first[4]) and same(eqn.u_n.cpu().numpy(), first[5])
+            assert same(eqn.v_n.cpu().numpy(), first[6])
+        else:
+            tol = 8.0 * a4.D64_4
+            assert abs(J - float(g64[0])) <= tol * float(g64[0])
+            assert np.abs(gK - g64[1]).max() <= tol * np.abs(g64[1]).max() and np.abs(gM - g64[2]).max() <= tol * np.abs(g64[2]).max()
+
+
+def test_no_steps_and_max_steps(gpu):
+    """N = 0: J of row 0 alone and zero gradients; max_steps cuts the run as in leapfrog4, rows are appended"""
+    import torch
+    sc, _, eqn, first = made("P2", gpu)
+    ah.reset(eqn, sc, gpu)
+    J, gK, gM, info = eqn.misfit_gradient(0.0, 0.0, sc.dt, sc.observed[:1], scheme="leapfrog4")
+    torch.cuda.synchronize()
+    r0 = first[4][0] - sc.observed[0]
+    assert info["N"] == 0 == info["steps"] and info["vectors"] == 10 and info["launches"] == launches(0, 1)
+    assert abs(J - 0.5 * sc.dt * float((r0 * r0).sum())) <= 4 * 2.0 ** -52 * J          # four squares summed in either order
+    assert not gK.cpu().numpy().any() and not gM.cpu().numpy().any() and gK.shape == gM.shape == (sc.nc,)
+    assert same(eqn.receivers.traces.cpu().numpy(), first[4][:1])
+    ah.reset(eqn, sc, gpu)
+    eqn.receivers.record(eqn.u_n, -1.0)
+    J, gK, gM, info = eqn.misfit_gradient(0.0, 1.0, sc.dt, sc.observed[:8], max_steps=7, scheme="leapfrog4")
+    torch.cuda.synchronize()
+    assert info["N"] == 7 and info["S"] == 3 and eqn.receivers.traces.shape == (9, 4)
+    assert same(eqn.receivers.traces.cpu().numpy()[1:], first[4][:8])
+    assert J > 0 and np.abs(gK.cpu().numpy()).min() > 0 and np.abs(gM.cpu().numpy()).min() > 0
+
+
+def test_default_scheme_is_leapfrog_unchanged(gpu):
+    """misfit_gradient() without scheme: the bits and the info of scheme="leapfrog", the numbers of the second-order
+    adjoint (adjoint_helpers) and its count of vectors"""
+    import torch
+    sc, g64, _, _ = ah.reference(2)
+    eqn = ah.device_model(sc, gpu)
+    out = []
+    for kw in ({}, {"scheme": "leapfrog"}):
+        ah.reset(eqn, sc, gpu)
+        J, gK, gM, info = eqn.misfit_gradient(0.0, ah.tf(sc), sc.dt, sc.observed, **kw)
+        torch.cuda.synchronize()
+        out.append((J, gK.cpu().numpy(), gM.cpu().numpy(), info, eqn.receivers.traces.cpu().numpy().copy(), eqn.u_n.cpu().numpy()))
+    a, b = out
+    assert a[0] == b[0] and same(a[1], b[1]) and same(a[2], b[2]) and a[3] == b[3] and same(a[4], b[4]) and same(a[5], b[5])
+    assert a[3]["vectors"] == 2 * 5 + 5 + 5 and a[3]["S"] == 5 and a[3]["N"] == ah.STEPS
+    assert a[3]["launches"] == (8 + 1 + 1) + N * 4 + 4 + 2 * 5 + N * 3 + 5 * N + 2          # the parent's count, with a source
+    tol = 8.0 * ah.D64
+    assert abs(a[0] - float(g64[0])) <= tol * float(g64[0])
+    assert np.abs(a[1] - g64[1]).max() <= tol * np.abs(g64[1]).max() and np.abs(a[2] - g64[2]).max() <= tol * np.abs(g64[2]).max()
+
+
+def test_refusals_come_before_the_first_launch(gpu):
+    import torch
+    sc, _, eqn, _ = made("P2", gpu)
+    ah.reset(eqn, sc, gpu)
+    torch.cuda.synchronize()
+    before = eqn.u_n.cpu().numpy()
+
+    def untouched():
+        torch.cuda.synchronize()
+        assert eqn.receivers._rows == 0 and same(eqn.u_n.cpu().numpy(), before)
+
+    args = (0.0, a4.tf(sc), sc.dt)
+    for scheme in ("rk4", "leapfrog6", None):
+        with pytest.raises(ValueError):
+            eqn.misfit_gradient(*args, sc.observed, scheme=scheme)
+        untouched()
+    for bad in (sc.observed[:-1], sc.observed[:, :3], np.zeros((N + 2, 4)), sc.observed.T):
+        with pytest.raises(ValueError):
+            eqn.misfit_gradient(*args, bad, scheme="leapfrog4")
+        untouched()
+    with pytest.raises(ValueError):
+        eqn.misfit_gradient(*args, sc.observed, checkpoint_every=0, scheme="leapfrog4")
+    with pytest.raises(ValueError):
+        eqn.misfit_gradient(0.0, a4.tf(sc), -sc.dt, sc.observed, scheme="leapfrog4")
+    eqn.updater = object()
+    with pytest.raises(NotImplementedError):
+        eqn.misfit_gradient(*args, sc.observed, scheme="leapfrog4")
+    eqn.updater = None
+    untouched()
+    rec, eqn.receivers = eqn.receivers, None
+    with pytest.raises(ValueError):
+        eqn.misfit_gradient(*args, sc.observed, scheme="leapfrog4")
+    eqn.receivers = rec
+    untouched()
+    from wave_fenics_amd._lib import WF_WAVE_LEAPFROG4
+    with pytest.raises(ValueError):                       # the public route of the loop still refuses a callback
+        eqn._run(WF_WAVE_LEAPFROG4, *args, None, keep=lambda *a: None)
+    untouched()

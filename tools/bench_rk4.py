@@ -21,7 +21,10 @@ each; prints medians and ranges of both and the difference per step.
 --receivers (default 1000) receivers and --sources (default 1) source, --steps (default 200) steps each, timed alternately
 --rounds times with device events after a warm-up of both; prints ms per step of both, their ratio and the time per
 backward step (the difference).  The split of a backward step by kernel comes from a run of its own under
-`rocprofv3 --kernel-trace --stats -- python tools/bench_rk4.py --scheme leapfrog --gradient --rounds 1`."""
+`rocprofv3 --kernel-trace --stats -- python tools/bench_rk4.py --scheme leapfrog --gradient --rounds 1`.
+--scheme leapfrog4 --gradient (one rank): misfit_gradient(scheme="leapfrog4") against leapfrog4 and against the leapfrog
+gradient of the line above, the three alternately in one process, each scheme at its own stable_time_step(0.9); prints ms
+per step of the three, ms per microsecond of simulated time of the two gradients and their ratio."""
 import argparse
 import json
 import os
@@ -45,13 +48,13 @@ def main():
     ap.add_argument("--compare", action="store_true", help="leapfrog, leapfrog4 and rk4_fused alternately, at their own steps and a common one")
     ap.add_argument("--receivers", type=int, default=0, help="point receivers recorded every step (A/B against the plain loop)")
     ap.add_argument("--sources", type=int, default=0, help="Ricker point sources (A/B against the plain loop)")
-    ap.add_argument("--gradient", action="store_true", help="with --scheme leapfrog: time misfit_gradient against leapfrog")
+    ap.add_argument("--gradient", action="store_true", help="with --scheme leapfrog / leapfrog4: time misfit_gradient against the loop")
     ap.add_argument("--checkpoint-every", type=int, default=None, help="--gradient: steps between checkpoints (default ceil(sqrt(steps)))")
     ap.add_argument("--rounds", type=int, default=5, help="alternating timed runs per variant of the A/B")
     ap.add_argument("--periodic", default="", help="axes identified with their opposite face (one rank: RCCL exchange with itself)")
     args = ap.parse_args()
-    if args.gradient and args.scheme != "leapfrog":
-        sys.exit("--gradient needs --scheme leapfrog")
+    if args.gradient and args.scheme not in ("leapfrog", "leapfrog4"):
+        sys.exit("--gradient needs --scheme leapfrog or leapfrog4")
     if args.steps is None:
         args.steps = 200 if args.gradient else 100
     if args.gradient:
@@ -111,7 +114,7 @@ def main():
         with_points = LinearGLLOpt(V, p, 1500.0, 0.5e6, 6e4, tags=boundary_tags(part), device=dev, sources=src, receivers=rec)
         with_points.init()
         if args.gradient:
-            gradient_ab(args, with_points, rec, dt, part.size_global)
+            (gradient4_ab if args.scheme == "leapfrog4" else gradient_ab)(args, with_points, rec, dt, part.size_global)
             return
         models = {"plain": eqn, "points": with_points}
         name = args.scheme if args.scheme != "rk4" else "rk4" if args.unfused else "rk4_fused"
@@ -237,6 +240,58 @@ def gradient_ab(args, eqn, rec, dt, global_dofs):
                       "backward_step_ms": med["gradient"] - med["leapfrog"],
                       "S": info["S"], "vectors": info["vectors"], "bytes": info["bytes"], "launches": info["launches"], "J": J,
                       "finite": bool(torch.isfinite(gK).all() and torch.isfinite(gM).all())}), flush=True)
+
+
+def gradient4_ab(args, eqn, rec, dt, global_dofs):
+    """misfit_gradient(scheme="leapfrog4") against leapfrog4 and against the leapfrog gradient on one model, alternately,
+    each scheme at its own stable step, each run timed by a pair of device events"""
+    import statistics
+
+    import torch
+    steps = args.steps
+    dts = {"leapfrog": eqn.stable_time_step(0.9), "leapfrog4": eqn.stable_time_step(0.9, scheme="leapfrog4")}
+
+    def timed(fn):
+        rec.reset()
+        eqn.init()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / steps, out
+
+    eqn.leapfrog4(0.0, 1.0e9, dts["leapfrog4"], max_steps=args.warmup)
+    observed = {}
+    for scheme, loop in (("leapfrog", eqn.leapfrog), ("leapfrog4", eqn.leapfrog4)):
+        timed(lambda: loop(0.0, 1.0e9, dts[scheme], max_steps=steps))
+        observed[scheme] = 0.9 * rec.traces.clone()                    # a misfit that is not zero
+    runs = {"leapfrog4": lambda: eqn.leapfrog4(0.0, 1.0e9, dts["leapfrog4"], max_steps=steps)}
+    for scheme in ("leapfrog4", "leapfrog"):
+        runs["gradient_" + scheme] = lambda scheme=scheme: eqn.misfit_gradient(
+            0.0, 1.0e9, dts[scheme], observed[scheme], checkpoint_every=args.checkpoint_every, max_steps=steps, scheme=scheme)
+    times, last = {k: [] for k in runs}, {}
+    for rnd in range(args.rounds + 1):                                 # round 0 is the warm-up of all three
+        for k, fn in runs.items():
+            ms, last[k] = timed(fn)
+            if rnd:
+                times[k].append(ms)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    stat = lambda k: {"median": med[k], "min": min(times[k]), "max": max(times[k])}    # noqa: E731
+    per_us = {k: med["gradient_" + k] / (dts[k] * 1e6) for k in dts}
+    J, gK, gM, info = last["gradient_leapfrog4"]
+    print(json.dumps({"metric": "misfit_gradient(leapfrog4) against leapfrog4 and misfit_gradient(leapfrog), ms per step (device events)",
+                      "steps": steps, "rounds": args.rounds, "receivers": args.receivers, "sources": args.sources,
+                      "global_dofs": global_dofs, "dt": dts, "leapfrog4_ms": stat("leapfrog4"),
+                      "gradient_leapfrog4_ms": stat("gradient_leapfrog4"), "gradient_leapfrog_ms": stat("gradient_leapfrog"),
+                      "gradient_over_leapfrog4": med["gradient_leapfrog4"] / med["leapfrog4"],
+                      "backward_step_ms": med["gradient_leapfrog4"] - med["leapfrog4"],
+                      "gradient_ms_per_simulated_us": per_us,
+                      "leapfrog4_over_leapfrog_per_simulated_time": per_us["leapfrog4"] / per_us["leapfrog"],
+                      "S": info["S"], "vectors": info["vectors"], "bytes": info["bytes"], "launches": info["launches"], "J": J,
+                      "finite": bool(torch.isfinite(gK).all() and torch.isfinite(gM).all()
+                                     and torch.isfinite(last["gradient_leapfrog"][1]).all())}), flush=True)
 
 
 if __name__ == "__main__":

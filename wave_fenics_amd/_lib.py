@@ -305,6 +305,13 @@ SIGNATURES_LEAPFROG4 = {
                                   POINTER(c_double), POINTER(c_int64), c_void_p]),
 }
 
+# every symbol include/wavehip_adjoint4.h declares (the discrete adjoint of the fourth-order leapfrog loop), likewise
+SIGNATURES_ADJOINT4 = {
+    "wf_leapfrog4_correlate": (c_int, [c_int64] + [c_void_p] * 9),
+    "wf_wave_leapfrog4_steps": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p, WAVE_STEP_FN,
+                                        c_void_p, POINTER(c_void_p), POINTER(c_double), POINTER(c_int64), c_void_p]),
+}
+
 _LIB = None
 
 
@@ -325,7 +332,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **SIGNATURES_LEAPFROG4}.items():
+        for name, (res, args) in {**SIGNATURES, **SIGNATURES_LEAPFROG4, **SIGNATURES_ADJOINT4}.items():
             fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

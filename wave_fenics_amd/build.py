@@ -13,13 +13,13 @@ LIB = os.path.join(HERE, "libwavehip.so")
 SOURCES = [
     "tables.cpp", "mesh_io.cpp", "march_plan.cpp", "box_run_plan.cpp", "box_items.cpp", "unique_lists.cpp", "function_space.cpp", "box_space.cpp", "markers.cpp", "point_locate.cpp", "wave_loops.cpp",
     "hex_geometry.hip", "stiffness_batch.hip", "mass_batch.hip", "stiffness_march.hip", "stiffness_march_owner.hip", "stiffness_march_idx.hip", "stiffness_march_ks.hip",
-    "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "mass_dense_simplex.hip", "tsmm.hip", "vector_kernels.hip", "time_step.hip", "comm.hip", "updater.hip", "cg.hip", "points.hip", "adjoint.hip", "cell_form.hip", "api.hip",
+    "mass_march.hip", "ordered.hip", "stiffness_dense.hip", "mass_dense_simplex.hip", "tsmm.hip", "vector_kernels.hip", "time_step.hip", "comm.hip", "updater.hip", "cg.hip", "points.hip", "adjoint.hip", "adjoint4.hip", "cell_form.hip", "api.hip",
     "hex_cell_geometry.cpp", "op_setup.hip", "op_create.hip", "op_create_box.hip", "op_apply.hip",
 ]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_array.h"), os.path.join(CSRC, "op.h"), os.path.join(CSRC, "box_mesh.h"),
            os.path.join(CSRC, "stiffness_core.h"), os.path.join(CSRC, "cell_batch.h"), os.path.join(CSRC, "stiffness_elementwise.h"),
            os.path.join(CSRC, "march_column.h"), os.path.join(CSRC, "box_run_plan.h"), os.path.join(CSRC, "box_items.h"), os.path.join(CSRC, "unique_lists.h"), os.path.join(CSRC, "march_plan.h"), os.path.join(CSRC, "dense_simplex.h"), os.path.join(CSRC, "owner_pieces.h"), os.path.join(CSRC, "points_plan.h"), os.path.join(CSRC, "points_handles.h"), os.path.join(CSRC, "sweep.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "tsmm_plan.h"), os.path.join(CSRC, "wave_source.h"),
-           os.path.join(ROOT, "include", "wavehip.h"), os.path.join(ROOT, "include", "wavehip_leapfrog4.h")]
+           os.path.join(ROOT, "include", "wavehip.h"), os.path.join(ROOT, "include", "wavehip_leapfrog4.h"), os.path.join(ROOT, "include", "wavehip_adjoint4.h")]
 
 
 def hipcc() -> str:

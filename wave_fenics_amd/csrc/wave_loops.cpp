@@ -7,6 +7,7 @@
 
 #include "wave_source.h"
 #include "wavehip.h"
+#include "wavehip_adjoint4.h"
 #include "wavehip_leapfrog4.h"
 
 namespace wf {
@@ -250,7 +251,17 @@ int wf_wave_leapfrog4_work_vectors(void) { return kWorkVectorsLeapfrog4; }
 int wf_wave_leapfrog4(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
                       double* t_end, int64_t* steps, void* stream)
 {
+  return wf_wave_leapfrog4_steps(desc, t0, tf, dt, max_steps, d_u, d_v, nullptr, nullptr, nullptr, t_end, steps, stream);
+}
+
+int wf_wave_leapfrog4_steps(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
+                            wf_wave_step_fn before_step, void* before_step_user, double* const* d_startup, double* t_end,
+                            int64_t* steps, void* stream)
+{
   WF_TRY(check_call("wf_wave_leapfrog4", WF_WAVE_LEAPFROG, desc, t0, tf, dt, max_steps, d_u, d_v, kWorkVectorsLeapfrog4));
+  for (int k = 0; d_startup && k < 3; ++k) WF_REFUSE_UNLESS(d_startup[k], "wf_wave_leapfrog4_steps: null start-up vector");
+  // the start-up derivative just formed in `from`, for the caller (the discrete adjoint reads a0, j0, q0)
+  auto keep_startup = [&](int k, const double* from) { return d_startup ? wf_copy(desc->n, from, d_startup[k], stream) : WF_OK; };
   const wf_wave_desc& d = *desc;
   Loop L{d, stream};
   WF_TRY(L.init());
@@ -296,6 +307,7 @@ int wf_wave_leapfrog4(const wf_wave_desc* desc, double t0, double tf, double dt,
   WF_TRY(L.add_sources(t));
   WF_TRY(L.rhs(u));
   WF_TRY(wf_pointwise_div(n, b, m, w, stream));
+  WF_TRY(keep_startup(0, w));
   WF_TRY(wf_axpy(n, -dt, d_v, u, p, stream));
   WF_TRY(wf_axpy(n, 0.5 * dt2, w, p, p, stream));
   WF_TRY(wf_fill(n, 0.0, b, stream));
@@ -303,15 +315,21 @@ int wf_wave_leapfrog4(const wf_wave_desc* desc, double t0, double tf, double dt,
   WF_TRY(sources_d1(t));
   WF_TRY(L.rhs(d_v));
   WF_TRY(wf_pointwise_div(n, b, m, scratch, stream));
+  WF_TRY(keep_startup(1, scratch));
   WF_TRY(wf_axpy(n, -(dt2 * dt) / 6.0, scratch, p, p, stream));
   WF_TRY(wf_fill(n, 0.0, b, stream));
   WF_TRY(wf_boundary_apply_plan(d.bc, s1_dd(t) / dt2, s2, scratch, b, stream));
   WF_TRY(sources_dd(t, 1.0 / dt2));
   WF_TRY(L.rhs(w));                                           // K a^0 accumulates onto the loads; a^0 is then free
   WF_TRY(wf_pointwise_div(n, b, m, w, stream));
+  WF_TRY(keep_startup(2, w));
   WF_TRY(wf_axpy(n, (dt2 * dt2) / 24.0, w, p, p, stream));
   WF_TRY(wf_fill(n, 0.0, b, stream));
   while (t < tf) {
+    if (before_step && before_step(before_step_user, step, t, p, u, d_startup ? d_startup[0] : nullptr, stream) != WF_OK) {
+      wf::set_error("wf_wave_leapfrog4_steps: per-step callback failed");
+      return WF_ERR_INVALID;
+    }
     WF_TRY(advance(t, p, p, nullptr));
     std::swap(u, p);
     t += dt;

@@ -112,6 +112,13 @@ def leapfrog_correlate(lam, up, u, um, p):
     check(lib().wf_leapfrog_correlate(p.numel(), _ptr(lam), _ptr(up), _ptr(u), _ptr(um), _ptr(p), _stream(p)))
 
 
+def leapfrog4_correlate(lam, om, up, u, um, w, p, z=None):
+    """p = (p + lam * ((up - 2 u) + um)) + 12 (om * w) and, with z, z = u + w, evaluated as written
+    (wf_leapfrog4_correlate, include/wavehip_adjoint4.h); p and z must not overlap an input or each other."""
+    check(lib().wf_leapfrog4_correlate(p.numel(), _ptr(lam), _ptr(om), _ptr(up), _ptr(u), _ptr(um), _ptr(w), _ptr(p),
+                                       _ptr(z) if z is not None else 0, _stream(p)))
+
+
 class BoundaryPlan(Handle):
     """wf_boundary_create: the two boundary dof sets of the form L (LinearGLL.hpp:113-115, forms.ufl:19-24) as a
     bitmap + coefficient arrays, so that the fused RK4 stage can leave the next right-hand side's boundary

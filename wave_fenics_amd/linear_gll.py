@@ -369,11 +369,17 @@ class LinearGLLOpt:
         valid at n = 0 only).  It may copy them; the loop's own launches and their order do not
         depend on it.  For tests: rhs(x, b), a right-hand side b += K x in place of the model's, and work, the work vectors
         (wf_wave_work_vectors of them) in place of fresh ones."""
-        L, n, errors = lib(), self.u_n.numel(), []
-        fourth = scheme == WF_WAVE_LEAPFROG4
         if keep is not None and scheme != WF_WAVE_LEAPFROG:
             raise ValueError("LinearGLLOpt._run: keep= is the per-step callback of wf_wave_leapfrog alone")
-        vec = lambda p: la._tensor_from_ptr(p, n, self.device)   # noqa: E731
+        return self._loop(scheme, t0, tf, dt, max_steps, keep, rhs, work)
+
+    def _loop(self, scheme: int, t0: float, tf: float, dt: float, max_steps, keep=None, rhs=None, work=None, startup=None):
+        """The call behind _run.  With WF_WAVE_LEAPFROG4 and keep or startup (three vectors that receive a0, j0, q0) the loop
+        is wf_wave_leapfrog4_steps (include/wavehip_adjoint4.h), whose keep is called as leapfrog's (its last argument is
+        startup[0] or None); without either it is wf_wave_leapfrog4."""
+        L, n, errors = lib(), self.u_n.numel(), []
+        fourth = scheme == WF_WAVE_LEAPFROG4
+        vec = lambda p: la._tensor_from_ptr(p, n, self.device) if p else None   # noqa: E731
         d = WaveDesc()
         d.n, d.d_m, d.d_b, d.bc = n, _ptr(self.m), _ptr(self.b), self._bc._h
         d.source, d.fold_boundary = self._wave, int(self.fold_boundary)
@@ -403,13 +409,16 @@ class LinearGLLOpt:
         t_end, steps = ctypes.c_double(t0), ctypes.c_int64(0)
         args = (ctypes.byref(d), t0, tf, dt, max_steps, _ptr(self.u_n), _ptr(self.v_n))
         out = (ctypes.byref(t_end), ctypes.byref(steps), _stream(self.u_n))
-        if fourth:
+        step_fn = WAVE_STEP_FN()
+        if keep is not None:
+            call_keep = self._guarded(errors, lambda k, t, pw, pu, pa: keep(k, t, vec(pw), vec(pu), vec(pa)))
+            step_fn = WAVE_STEP_FN(lambda user, k, t, pw, pu, pa, stream: call_keep(stream, k, t, pw, pu, pa))
+        if fourth and (keep is not None or startup is not None):
+            kept = None if startup is None else (ctypes.c_void_p * 3)(*[_ptr(x) for x in startup])
+            rc = L.wf_wave_leapfrog4_steps(*args, step_fn, None, kept, *out)
+        elif fourth:
             rc = L.wf_wave_leapfrog4(*args, *out)
         elif scheme == WF_WAVE_LEAPFROG:
-            step_fn = WAVE_STEP_FN()
-            if keep is not None:
-                call_keep = self._guarded(errors, lambda k, t, pw, pu, pa: keep(k, t, vec(pw), vec(pu), vec(pa)))
-                step_fn = WAVE_STEP_FN(lambda user, k, t, pw, pu, pa, stream: call_keep(stream, k, t, pw, pu, pa))
             rc = L.wf_wave_leapfrog(*args, step_fn, None, *out)
         else:
             rc = L.wf_wave_rk4_fused(*args, *out)
@@ -424,7 +433,7 @@ class LinearGLLOpt:
         return t_end.value, int(steps.value)
 
     def misfit_gradient(self, t0: float, tf: float, dt: float, observed, checkpoint_every: int | None = None,
-                        max_steps: int | None = None):
+                        max_steps: int | None = None, scheme: str = "leapfrog"):
         """The L2 trace misfit of a leapfrog run and its gradient with respect to the cell coefficients of the model's two
         operators: returns (J, g_stiff, g_mass, info).
 
@@ -460,7 +469,13 @@ class LinearGLLOpt:
         structured box's owner kernel, WF_FLAG_ORDERED) the replayed states, and so J and both gradients, are
         bit-identical for every S and from call to call; where the apply adds by atomics they agree to rounding only.
 
-        Raises before the first launch: with updater=, without receivers, dt <= 0, observed of another shape, S < 1."""
+        scheme="leapfrog4": the same for the fourth-order loop, the forward run being leapfrog4(t0, tf, dt, max_steps) --
+        _misfit_gradient4 says what differs.
+
+        Raises before the first launch: an unknown scheme, with updater=, without receivers, dt <= 0, observed of another
+        shape, S < 1."""
+        if scheme not in ("leapfrog", "leapfrog4"):
+            raise ValueError(f"LinearGLLOpt.misfit_gradient: scheme must be 'leapfrog' or 'leapfrog4', got {scheme!r}")
         if self.updater is not None:
             raise NotImplementedError("LinearGLLOpt.misfit_gradient on a partitioned mesh (updater=) is not implemented")
         rec, src = self.receivers, self.sources
@@ -479,6 +494,8 @@ class LinearGLLOpt:
             observed = torch.from_numpy(np.array(observed, dtype=np.float64))   # a copy: the caller's array may be read-only
         observed = observed.to(self.device, dtype=torch.float64)
         ncp, Sb = -(-N // S), min(S, N)
+        if scheme == "leapfrog4":
+            return self._misfit_gradient4(t0, tf, dt, observed, N, S, max_steps)
         b, m = self.b, self.m
         new = lambda: torch.empty_like(self.u_n)   # noqa: E731
         pairs, times, a0 = [], [], new()
@@ -545,6 +562,137 @@ class LinearGLLOpt:
         mu.fill_(1.0)
         g_mass = mform.eval(mu, p)
         g_stiff.mul_(dt * dt)
+        if self.medium is not None:
+            g_stiff.div_(torch.from_numpy(np.ascontiguousarray(self.medium.stiff_coeff)).to(self.device))
+            g_mass.div_(torch.from_numpy(np.ascontiguousarray(self.medium.mass_coeff)).to(self.device))
+        return J, g_stiff, g_mass, info
+
+    def _misfit_gradient4(self, t0: float, tf: float, dt: float, observed, N: int, S: int, max_steps):
+        """misfit_gradient(scheme="leapfrog4") behind its checks: the discrete adjoint of the leapfrog4 loop
+        (include/wavehip_adjoint4.h has the derivation in the loop's notation).  Step n is
+            b1 = K u^n + F1^n,  u* = the leapfrog update,  w^n = c12 b1/m,  A+ u^{n+1} = A+ u* + dt^2 (K w^n + F2^n),
+        that is A+ u^{n+1} = dt^2 K' u^n + 2 m u^n - A- u^{n-1} + loads with K' = K + c12 K m^-1 K symmetric, and
+            mu_N = mu_{N+1} = 0,   A+ mu_{k-1} = dt^2 (K mu_k + K om_k + R^T r^k / dt) + 2 m mu_k - A- mu_{k+1},   om_k = c12 (K mu_k)/m
+        is the forward step again: la.leapfrog4_predict on b = K mu_k with s1 = 0 leaves om_k in its w, the residual load
+        goes onto b = K om_k AFTER it (before, it would flow into om), la.leapfrog4_correct with s1c = 0.  Per step n < N
+            a^K_c g_stiff[c] += dt^2 (e^K_c(mu_n, u^n + w^n) + e^K_c(om_n, u^n)),
+            p += mu_n (u^{n+1} - 2 u^n + u^{n-1}) + 12 om_n w^n          (la.leapfrog4_correlate, which also writes u^n + w^n),
+        and the start-up, with nu = -A- mu_0 and d = -s2 c2:
+            qh = (dt^4/24 nu)/m,  jh = (-dt^3/6 nu - d qh)/m,  ah = (dt^2/2 nu + K qh - d jh)/m,
+            a^K_c g_stiff[c] += e^K_c(qh, a0) + e^K_c(jh, v0) + e^K_c(ah, u0),   p += qh q0 + jh j0 + ah a0,
+        and a^M_c g_mass[c] = e^M_c(1, -p).  The backward pass takes two applies a step: om_n comes out of the predictor half
+        of the iteration that forms mu_{n-1}, so each iteration is predictor half, the step's terms, (the replay of the
+        segment before, where n opens one,) corrector half.
+
+        Memory: the pairs (u^{jS-1}, u^{jS}) as for leapfrog, and u^n AND w^n of one segment.  info["vectors"] =
+        2 ceil(N/S) + 2 min(S, N) + 10: the pairs, the segment, and mu twice, om, p, u + w, a0, j0, q0, v0, h.
+        info["launches"] = 36 + 6 s + N (5 + 2 s) + 2 ceil(N/S), the forward run with its copies, and with N > 0 a further
+        N (4 + 2 s) + 5 N + 3 (N - 1) + 8: the replays, the predictor halves with the step's terms, the corrector halves,
+        and mu_{N-1} with the start-up terms (s = 1 with sources)."""
+        rec, src = self.receivers, self.sources
+        ncp, Sb = -(-N // S), min(S, N)
+        b, m = self.b, self.m
+        new = lambda: torch.empty_like(self.u_n)   # noqa: E731
+        pairs, times = [], []
+        a0, j0, q0, v0 = new(), new(), new(), new()
+
+        def keep(n, tn, u_prev, u, _):
+            times.append(tn)
+            if n % S == 0:
+                pair = (new(), new())
+                la.copy(u_prev, pair[0])
+                la.copy(u, pair[1])
+                pairs.append(pair)
+
+        row0 = rec._rows
+        la.copy(self.v_n, v0)
+        t, steps = self._loop(WF_WAVE_LEAPFROG4, t0, tf, dt, max_steps, keep, startup=(a0, j0, q0))
+        assert steps == N and len(pairs) == ncp
+        resid = rec.traces[row0:row0 + N + 1] - observed
+        J = 0.5 * dt * float((resid * resid).sum().item())
+        ncells = self.V.mesh.ncells
+        g_stiff = torch.zeros(ncells, dtype=torch.float64, device=self.device)
+        ns = 0 if src is None else 1
+        info = {"N": N, "S": S, "vectors": 2 * ncp + 2 * Sb + 10, "t": t, "steps": steps,
+                "launches": 36 + 6 * ns + N * (5 + 2 * ns) + 2 * ncp + (N * (4 + 2 * ns) + 5 * N + 3 * (N - 1) + 8 if N > 0 else 0)}
+        info["bytes"] = info["vectors"] * self.u_n.numel() * 8
+        if N == 0:
+            return J, g_stiff, torch.zeros_like(g_stiff), info
+        kform, mform = self.cell_forms()
+        if self._rec_T is None or self._rec_T[0] is not rec:
+            self._rec_T = (rec, rec.transpose())
+        RT = self._rec_T[1]
+        bc, s1, s2, rhs = self._bc, self._s1, self._s2, self._rhs
+        dt2 = dt * dt
+        mu, mu_next, om = torch.zeros_like(self.u_n), torch.zeros_like(self.u_n), new()
+        p, z = torch.zeros_like(self.u_n), new()
+        ubuf, wbuf = [new() for _ in range(Sb)], [new() for _ in range(Sb)]
+
+        def states(j):
+            """st[i] = u^{jS - 1 + i} of segment j"""
+            return [pairs[j][0], pairs[j][1]] + ubuf[:min((j + 1) * S, N) - j * S]
+
+        def replay(j):
+            """the forward steps of segment j again, from its pair: the launches of wf_wave_leapfrog4's step"""
+            st = states(j)
+            for i, n in enumerate(range(j * S, min((j + 1) * S, N))):
+                tn = times[n]
+                rhs(st[i + 1], b)
+                if src is not None:
+                    src.add(tn, b)
+                la.leapfrog4_predict(b, m, st[i + 1], st[i], st[i + 2], wbuf[i], dt, bc=bc, s1=s1(tn), s2=s2)
+                rhs(wbuf[i], b)
+                if src is not None:
+                    src.add_stencil((tn - dt, tn, tn + dt), (1.0 / 12.0, -2.0 * (1.0 / 12.0), 1.0 / 12.0), b)
+                s1c = ((s1(tn + dt) - 2.0 * s1(tn)) + s1(tn - dt)) / 12.0
+                la.leapfrog4_correct(b, m, st[i + 2], st[i + 2], dt, bc=bc, s1c=s1c, s2=s2)
+
+        # mu_{N-1} from mu_N = mu_{N+1} = 0: the predictor half of zeros is zeros, b holds the residual load alone
+        RT.add_values(resid[N], b, scale=1.0 / dt)
+        la.leapfrog4_correct(b, m, mu_next, mu, dt, bc=bc, s1c=0.0, s2=s2)
+        replay(ncp - 1)
+        st = states(ncp - 1)
+        for n in reversed(range(N)):                                  # mu = mu_n, mu_next = mu_{n+1}
+            j, i = divmod(n, S)
+            rhs(mu, b)
+            la.leapfrog4_predict(b, m, mu, mu_next, mu_next, om, dt, bc=bc, s1=0.0, s2=s2)     # om = om_n, mu_next = mu*
+            la.leapfrog4_correlate(mu, om, st[i + 2], st[i + 1], st[i], wbuf[i], p, z)
+            kform.eval(mu, z, out=g_stiff, accumulate=True)
+            kform.eval(om, st[i + 1], out=g_stiff, accumulate=True)
+            if i == 0 and j > 0:
+                pairs[j] = None
+                replay(j - 1)
+                st = states(j - 1)
+            if n > 0:
+                rhs(om, b)
+                RT.add_values(resid[n], b, scale=1.0 / dt)
+                la.leapfrog4_correct(b, m, mu_next, mu_next, dt, bc=bc, s1c=0.0, s2=s2)
+                mu, mu_next = mu_next, mu
+        g_stiff.mul_(dt2)
+        # start-up: u^{-1} = u0 - dt v0 + dt^2/2 a0 - dt^3/6 j0 + dt^4/24 q0 depends on K and m through a0, j0, q0.
+        # mu holds mu_0; nu goes into mu_next, qh into om, jh into mu, ah into mu_next; z holds d
+        u0 = pairs[0][1]
+        h = torch.zeros_like(self.u_n)
+        if self.idx2.numel():
+            h.index_add_(0, self.idx2.long(), self.mG2)
+        torch.mul(h, -s2, out=z)                                      # d = -s2 c2
+        h.mul_((-s2) * (0.5 * dt))
+        torch.sub(h, m, out=mu_next)
+        mu_next.mul_(mu)                                              # nu = -A- mu_0
+        torch.mul(mu_next, (dt2 * dt2) / 24.0, out=om)
+        om.div_(m)                                                    # qh
+        torch.mul(mu_next, -(dt2 * dt) / 6.0, out=mu)
+        mu.addcmul_(z, om, value=-1.0).div_(m)                        # jh
+        rhs(om, b)                                                    # b = K qh (the corrector left it zero)
+        mu_next.mul_(0.5 * dt2).add_(b).addcmul_(z, mu, value=-1.0).div_(m)   # ah
+        la.fill(b, 0.0)
+        kform.eval(om, a0, out=g_stiff, accumulate=True)
+        kform.eval(mu, v0, out=g_stiff, accumulate=True)
+        kform.eval(mu_next, u0, out=g_stiff, accumulate=True)
+        p.addcmul_(om, q0).addcmul_(mu, j0).addcmul_(mu_next, a0)
+        p.mul_(-1.0)
+        z.fill_(1.0)
+        g_mass = mform.eval(z, p)
         if self.medium is not None:
             g_stiff.div_(torch.from_numpy(np.ascontiguousarray(self.medium.stiff_coeff)).to(self.device))
             g_mass.div_(torch.from_numpy(np.ascontiguousarray(self.medium.mass_coeff)).to(self.device))
