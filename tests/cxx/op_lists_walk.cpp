@@ -1,6 +1,7 @@
 // The index lists that operator set-up computes on the host and the kernels dereference unchecked, walked without a GPU:
 //   work items   the interior / interface split of the box marching operators (wave_fenics_amd/csrc/box_items.{h,cpp});
-//   run tables   the owner kernel's (column, z0, z1) tables (csrc/box_run_plan.{h,cpp}: aligned_runs, check_run_table);
+//   run tables   the owner kernel's (column, z0, z1) tables (csrc/box_run_plan.{h,cpp}: aligned_runs, check_run_table),
+//                and which of them creation times (owner_cut_is_timed, owner_cut_candidates);
 //   unique lists the batch-unique gather/scatter lists and their packed dense form (csrc/unique_lists.{h,cpp}).
 // Every expectation is written out here from the contract (include/wavehip.h, DESIGN "Interior / interface split"), not
 // taken from the code under test: the columns, the z segments, the footprint of an item, the first-segment rule.
@@ -289,6 +290,68 @@ void expect_fault(const char* what, std::vector<int32_t> t, int ncols, int nz, w
   std::printf("runs mutant '%s': %s\n", what, fault_name(got));
 }
 
+// What creation decides before it times the owner apply (owner_cut_candidates, owner_cut_is_timed): the lists written
+// out, every table a candidate stands for, and the predicate at its edges.
+void walk_timed_cuts()
+{
+  const struct {
+    int nz;
+    std::vector<int> nsegs;
+  } lists[] = {{7, {}},
+               {8, {2}},
+               {13, {2, 3}},
+               {27, {3, 4, 5, 6}},
+               {54, {5, 6, 7, 8, 9, 10, 11, 12, 13}},
+               {200, {17, 20, 23, 26, 29, 32, 35, 38, 41, 44, 47, 50}}};
+  long before = failures;
+  for (const auto& l : lists) {
+    const std::vector<int> got = wf::owner_cut_candidates(l.nz);
+    CHECK(got == l.nsegs, "owner_cut_candidates(%d): %zu candidates from %d to %d, expected %zu from %d to %d", l.nz, got.size(),
+          got.empty() ? 0 : got.front(), got.empty() ? 0 : got.back(), l.nsegs.size(), l.nsegs.empty() ? 0 : l.nsegs.front(),
+          l.nsegs.empty() ? 0 : l.nsegs.back());
+  }
+  for (int nz = 0; nz < 8; ++nz) CHECK(wf::owner_cut_candidates(nz).empty(), "owner_cut_candidates(%d) is not empty", nz);
+  std::printf("runs timed cuts, candidate lists of nz 0..8, 13, 27, 54, 200: %ld failures\n", failures - before);
+
+  // every candidate of nz = 8 .. 256: an exact cover (walk_aligned) by runs of 4 to 12 layers, the list ascending, of
+  // at most 17 entries and never empty; 33 columns leave the XCDs unequal shares at every nseg that 8 does not divide
+  before = failures;
+  int tables = 0;
+  for (int nz = 8; nz <= 256; ++nz) {
+    const std::vector<int> nsegs = wf::owner_cut_candidates(nz);
+    CHECK(!nsegs.empty() && nsegs.size() <= 17, "owner_cut_candidates(%d): %zu candidates", nz, nsegs.size());
+    for (size_t c = 0; c < nsegs.size(); ++c, ++tables) {
+      const int ncols = 33, nseg = nsegs[c];
+      CHECK(nseg >= 2 && (c == 0 || nseg > nsegs[c - 1]), "owner_cut_candidates(%d): entry %zu is %d", nz, c, nseg);
+      if (nseg < 1 || nseg > nz) continue;
+      walk_aligned(ncols, nz, nseg);
+      const std::vector<int32_t> t = wf::aligned_runs(ncols, nz, nseg);
+      for (size_t r = 0; 3 * r + 2 < t.size(); ++r) {
+        const int len = t[3 * r + 2] - t[3 * r + 1];
+        CHECK(len >= 4 && len <= 12, "aligned_runs(%d, %d, %d): run %zu of %d layers", ncols, nz, nseg, r, len);
+      }
+    }
+  }
+  std::printf("runs timed cuts, nz 8..256: %d tables of 4 to 12 layers a run, %ld failures\n", tables, failures - before);
+
+  // the tuner runs: P4 only, without wf_tuning.lz, and with more items than resident workgroups.  33 columns of 27
+  // layers in segments of 7: 4 segments, 132 items.
+  before = failures;
+  const int ncols = 33, nz = 27, lz = 7, items = 132;
+  CHECK(ncols * wf::box_segments(nz, lz, lz) == items, "%d items", ncols * wf::box_segments(nz, lz, lz));
+  CHECK(wf::owner_cut_is_timed(4, 0, ncols, nz, lz, items - 1), "one item above one round: not timed");
+  CHECK(!wf::owner_cut_is_timed(4, 0, ncols, nz, lz, items), "items == resident: timed");
+  CHECK(!wf::owner_cut_is_timed(4, 0, ncols, nz, lz, items + 1), "fewer items than resident workgroups: timed");
+  CHECK(!wf::owner_cut_is_timed(4, 0, ncols, nz, lz, 768), "one round of 768: timed");
+  for (int P : {1, 2, 3, 5, 6, 7}) CHECK(!wf::owner_cut_is_timed(P, 0, ncols, nz, lz, 1), "P%d: timed", P);
+  for (int tuning_lz : {1, 7, 27}) CHECK(!wf::owner_cut_is_timed(4, tuning_lz, ncols, nz, lz, 1), "wf_tuning.lz = %d: timed", tuning_lz);
+  // whole columns (lz = nz) are one segment each: 33 items; the count does not wrap where int would (2^16 columns of
+  // 2^16 single layers against 2^31 resident)
+  CHECK(wf::owner_cut_is_timed(4, 0, ncols, nz, nz, 32) && !wf::owner_cut_is_timed(4, 0, ncols, nz, nz, 33), "whole columns");
+  CHECK(wf::owner_cut_is_timed(4, 0, 1 << 16, 1 << 16, 1, 1L << 31), "2^32 items against 2^31 resident: not timed");
+  std::printf("runs timed cuts, predicate: %ld failures\n", failures - before);
+}
+
 void walk_runs()
 {
   for (int ncols : {1, 7, 8, 9, 63}) {
@@ -443,6 +506,7 @@ int main()
 {
   walk_items();
   walk_runs();
+  walk_timed_cuts();
   walk_lists();
   std::printf("%ld failures\n", failures);
   return failures ? 1 : 0;

@@ -64,6 +64,27 @@ def reference(oracle, om, p, x, y0):
     return y
 
 
+def owner_cut_candidates(nz):
+    """The nseg of the tables that creation times against the uniform plan of a P4 owner operator (owner_cut_candidates,
+    csrc/box_run_plan.cpp): runs of 4 to 12 layers, at most 17 candidates."""
+    lo, hi = max(2, (nz + 11) // 12), nz // 4
+    return list(range(lo, hi + 1, max(1, (hi - lo + 16) // 16)))
+
+
+def aligned_runs(ncols, nz, nseg, nxcd=8):
+    """aligned_runs of csrc/box_run_plan.cpp, restated: every column cut at layers nz s // nseg, the runs in segment-major
+    order dealt to the XCDs in contiguous shares (the first n % 8 one run longer); run i of XCD xcd is entry 8 i + xcd.
+    [runs][3] = (column, z0, z1), int32."""
+    n = ncols * nseg
+    start = np.concatenate([[0], np.cumsum(n // nxcd + (np.arange(nxcd) < n % nxcd))])
+    t = np.arange(n)
+    xcd = np.searchsorted(start, t, side="right") - 1
+    s, col = t // ncols, t % ncols
+    table = np.full((n, 3), -1, dtype=np.int32)
+    table[nxcd * (t - start[xcd]) + xcd] = np.stack([col, nz * s // nseg, nz * (s + 1) // nseg], axis=1)
+    return table
+
+
 _boxes = {}
 
 

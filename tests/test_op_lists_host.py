@@ -33,6 +33,7 @@ def test_op_lists_sanitized(tmp_path):
     lines = out.stdout.splitlines()
     assert out.returncode == 0 and lines and lines[-1] == "0 failures", out.stdout[-4000:] + out.stderr[-4000:]
     # every family of cases ran: 8 cross-sections x 3 boxes x 3 segmentations and 12 exhaustive walks, 5 column counts
-    # and 8 mutants of a run table, 9 hexahedral and 10 dense dofmaps and the refusals
+    # and 8 mutants of a run table, the tuner's candidate lists, their tables and its predicate, 9 hexahedral and 10 dense
+    # dofmaps and the refusals
     count = lambda prefix: sum(line.startswith(prefix) for line in lines)
-    assert (count("items "), count("runs "), count("lists ")) == (84, 13, 20), out.stdout[-4000:]
+    assert (count("items "), count("runs "), count("runs timed cuts"), count("lists ")) == (84, 16, 3, 20), out.stdout[-4000:]

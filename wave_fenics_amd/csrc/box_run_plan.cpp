@@ -5,6 +5,8 @@
 #include <functional>
 #include <queue>
 
+#include "box_items.h"
+
 namespace wf {
 
 int box_uniform_lz(int ncols, int nz, long resident, double prologue, double* cost, long* items)
@@ -157,6 +159,19 @@ std::vector<int32_t> aligned_runs(int ncols, int nz, int nseg)
       if (++i == q + (xcd < r ? 1 : 0)) i = 0, ++xcd;
     }
   return table;
+}
+
+bool owner_cut_is_timed(int P, int tuning_lz, int ncols, int nz, int lz, long resident)
+{
+  return P == 4 && tuning_lz <= 0 && (long)ncols * box_segments(nz, lz, lz) > resident;
+}
+
+std::vector<int> owner_cut_candidates(int nz)
+{
+  const int lo = std::max(2, (nz + 11) / 12), hi = nz / 4, step = std::max(1, (hi - lo + 16) / 16);
+  std::vector<int> nsegs;
+  for (int nseg = lo; nseg <= hi; nseg += step) nsegs.push_back(nseg);
+  return nsegs;
 }
 
 int longest_run(const std::vector<int32_t>& table)

@@ -43,6 +43,14 @@ BoxRunPlan box_run_plan(int ncols, int nz, int resident, int nxcd, double prolog
 // order and dealt to the XCDs in contiguous chunks, as the uniform order deals its items: neighbouring columns march
 // through the same layers at the same time, and what one reads as halo the other has just brought into the XCD's L2.
 std::vector<int32_t> aligned_runs(int ncols, int nz, int nseg);
+// What creation decides before it times anything (tune_owner_runs, op_create_box.hip; DESIGN §4.2 "r19"):
+// whether the cut of the owner apply is chosen by timing at all: only at P4, where the bits of y do not depend on the
+// cut, without wf_tuning.lz, and where the uniform plan (ncols columns in segments of lz layers) needs more than one
+// round of the resident workgroups;
+bool owner_cut_is_timed(int P, int tuning_lz, int ncols, int nz, int lz, long resident);
+// and the nseg of the aligned_runs tables timed against the uniform plan: cuts of 4 to 12 layers per run, at most 17 of
+// them, ascending (none where nz < 8).
+std::vector<int> owner_cut_candidates(int nz);
 // layers of the longest run of a table (0 for the empty table)
 int longest_run(const std::vector<int32_t>& table);
 // The kernel trusts its table: every run non-empty and inside its column, every (column, layer) exactly once.  The

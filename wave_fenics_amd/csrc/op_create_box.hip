@@ -223,8 +223,7 @@ int wf::tune_owner_runs(wf_op* op)
   const int ncols = box_owner_columns(op->P, op->nx, op->ny, op->box.obx, op->box.oby).count(), nz = op->nz;
   long resident = march_owner_resident(op->P, op->box.variant);
   if (resident <= 0) resident = 512;
-  if (rc != WF_OK || op->P != 4 || op->tun.lz > 0 || (long)ncols * box_segments(nz, op->box.lz, op->box.lz) <= resident) return rc;
-  const int lo = std::max(2, (nz + 11) / 12), hi = nz / 4, step = std::max(1, (hi - lo + 16) / 16);
+  if (rc != WF_OK || !owner_cut_is_timed(op->P, op->tun.lz, ncols, nz, op->box.lz, resident)) return rc;
   DevArray<double> vectors;   // x | y of the timing; no room for them: the uniform plan stays
   if (vectors.alloc(2 * (size_t)op->ndofs) != WF_OK) return (void)hipGetLastError(), WF_OK;
   const double* d_x = vectors.data();
@@ -234,7 +233,7 @@ int wf::tune_owner_runs(wf_op* op)
   WF_HIP_CHECK(hipEventCreate(&ev.e0));
   WF_HIP_CHECK(hipEventCreate(&ev.e1));
   std::vector<int> nsegs = {0};   // 0: the uniform plan
-  for (int nseg = lo; nseg <= hi; nseg += step) nsegs.push_back(nseg);
+  for (int nseg : owner_cut_candidates(nz)) nsegs.push_back(nseg);
   std::vector<float> us(nsegs.size(), 1e30f);
   for (int pass = 0; pass < 3; ++pass)   // interleaved, so that a clock ramp after idle does not favour a candidate
     for (size_t c = 0; c < nsegs.size(); ++c) {
