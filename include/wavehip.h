@@ -623,6 +623,40 @@ int wf_leapfrog_step(int64_t n, double dt, double* d_b, const double* d_m, const
 int wf_leapfrog_step_bc(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
                         double* d_u_next, double* d_v, const wf_boundary* bc, double s1, double s2, void* stream);
 
+/* The fourth-order leapfrog (modified-equation, "ME4") step: the two fused passes.  With A = M^-1 K (lumped mass m, sign
+ * convention of f1: u'' = b / m) one step is
+ *       (u+ - 2u + u-) / dt^2 = A u + (dt^2/12) A^2 u   (+ loads and their second difference),
+ * fourth order in time, two stiffness applies and two passes per step, stable for dt <= sqrt(12) / sqrt(lambda_max(-A)):
+ * sqrt(3) times the limit of wf_leapfrog_step.  The diagonal absorbing term d u', d = -s2 c2, is taken centred exactly
+ * as wf_leapfrog_step_bc takes it and stays second order.
+ *
+ * One step, b = +0.0 on entry, dt2 = dt*dt, hdt = (-s2)*(0.5*dt), tdt = 2*dt, c12 = dt2/12 computed by the host:
+ *   1. b += K u (the apply); wf_sources_add(t)
+ *   2. wf_leapfrog4_predict, with s1 = s1(t):
+ *        u_star = what wf_leapfrog_step_bc stores in u_next (the same expressions, the same bits)
+ *        outside the plan's union set (and every dof without a plan):   w = c12*(b/m)
+ *        dof r of the union set:                                         w = c12*((b + s1*c1[r])/m)
+ *        b = +0.0
+ *      d_u_star may be d_u_prev (in place); it must not overlap d_u, d_b, d_m or d_w; d_w overlaps no other vector.
+ *      56 B/dof of HBM traffic.
+ *   3. b += K w (the apply, ghost exchange as in 1)
+ *   4. wf_sources_add_stencil at t - dt, t, t + dt with the weights 1/12, -2/12, 1/12 (the Numerov weighting of the load)
+ *   5. wf_leapfrog4_correct, with s1c = (s1(t+dt) - 2*s1(t) + s1(t-dt))/12 from the host:
+ *        outside the union set:   u_next = u_star + dt2*(b/m)
+ *        dof r of the union set:  h = hdt*c2[r];  u_next = u_star + (dt2*(b + s1c*c1[r]))/(m + h)
+ *        d_v non-null:            v = (u_next - u_prev)/tdt   (d_u_prev must then still hold u^{n-1}: step 2 out of place)
+ *        b = +0.0
+ *      d_u_next may be d_u_star (in place); it must not overlap d_b or d_m, nor d_u_prev when d_v is given; d_v overlaps
+ *      no other vector.  d_u_prev is not read without d_v and may then be NULL.  40 B/dof, 56 with d_v.
+ * The expressions are evaluated as written (no fused multiply-add), so every compiled form -- 16-byte and scalar sweep,
+ * with and without a plan, with and without v -- gives the same bits.  bc may be NULL: no boundary sets (s1, s2 are then
+ * not used, s2 is still checked).  Refused (WF_ERR_INVALID, nothing written): a forbidden overlap, s2 > 0, dt <= 0 or
+ * NaN, a plan built for another n, a null vector.  n <= 0 is a no-op. */
+int wf_leapfrog4_predict(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u, const double* d_u_prev,
+                         double* d_u_star, double* d_w, const wf_boundary* bc, double s1, double s2, void* stream);
+int wf_leapfrog4_correct(int64_t n, double dt, double* d_b, const double* d_m, const double* d_u_star, const double* d_u_prev,
+                         double* d_u_next, double* d_v, const wf_boundary* bc, double s1c, double s2, void* stream);
+
 /* ---- a14: ghost exchange over RCCL ----------------------------------------
  * demo/gpu_scatter_mpi/VectorUpdater.hpp:21-230 (GPU pack + CUDA-aware MPI per
  * IndexMap neighbour) and la::Vector::scatter_fwd / scatter_rev(add) of
@@ -857,7 +891,12 @@ int wf_box_partition(const int* n, int degree, int nproc, int rank, const int* p
  *     WF_WAVELET_SAMPLED: s(t) = amplitude times the linear interpolation of h_samples [nsamples] on t_start + k dt,
  *                         zero outside the table; nsamples >= 2, dt > 0
  * wf_sources_add: d_b[d] += sum over the sources at dof d, in source order, of weight * s(t): one thread and one
- *   update per unique dof, no atomics; the wavelets are evaluated on the device in fp64. */
+ *   update per unique dof, no atomics; the wavelets are evaluated on the device in fp64.
+ * wf_sources_add_stencil: d_b[d] += sum over the sources at dof d, in source order, of weight * S,
+ *   S = ((h_a[0] s(h_t[0])) + h_a[1] s(h_t[1])) + h_a[2] s(h_t[2])  (the first nt terms, 1 <= nt <= 3), one thread and one
+ *   writer per dof like wf_sources_add; nt = 1 with h_a[0] = 1 gives the bits of wf_sources_add.  h_t and h_a are host
+ *   arrays of nt doubles read during the call (they travel by value with the launch).  Refused: a null handle, nt outside
+ *   1..3, a null array or vector, a time or weight that is not finite. */
 typedef struct wf_points wf_points;
 typedef struct wf_sources wf_sources;
 enum { WF_WAVELET_RICKER = 0, WF_WAVELET_SAMPLED = 1 };
@@ -882,6 +921,7 @@ int wf_sources_create(const wf_points* plan, int nsrc, const int32_t* h_point_of
 int wf_sources_destroy(wf_sources* src);
 int wf_sources_info(const wf_sources* src, int* nsources, int* nunique, int* nentries);
 int wf_sources_add(const wf_sources* src, double t, double* d_b, void* stream);
+int wf_sources_add_stencil(const wf_sources* src, int nt, const double* h_t, const double* h_a, double* d_b, void* stream);
 
 /* ---- the passes of the discrete adjoint of the leapfrog loop (csrc/adjoint.hip) ----
  * wf_leapfrog_correlate: p[i] = p[i] + lam[i] * ((up[i] - 2.0*u[i]) + um[i]) for i < n, evaluated as written (no fused
@@ -891,13 +931,32 @@ int wf_sources_add(const wf_sources* src, double t, double* d_b, void* stream);
  * wf_sources_add_values: the wavelets are not looked at; d_values [nsources] on the device takes their place:
  *   acc = sum over the entries e of dof d, in the CSR order of wf_sources_merge, of weight[e] * d_values[source[e]];
  *   d_b[d] += scale * acc.  One thread and one update per unique dof, no atomics: with sources on the points of a
- *   wf_points plan it is the transpose of wf_points_sample.  d_values may point anywhere inside a larger buffer. */
+ *   wf_points plan it is the transpose of wf_points_sample.  d_values may point anywhere inside a larger buffer.
+ *
+ * The adjoint of the fourth-order loop (csrc/adjoint4.hip; notation of wf_leapfrog4_predict).  Step n of wf_wave_leapfrog4
+ * is A+ u^{n+1} = dt2 K' u^n + 2 m u^n - A- u^{n-1} + loads with A+- = m +- h and K' = K + c12 K m^-1 K symmetric, so the
+ * multipliers march backwards through the step itself:
+ *       mu_N = mu_{N+1} = 0,   A+ mu_{k-1} = dt2 (K mu_k + K om_k + R^T r^k / dt) + 2 m mu_k - A- mu_{k+1},   om_k = c12 (K mu_k)/m,
+ * wf_leapfrog4_predict on b = K mu_k with s1 = 0 (it leaves om_k in its w), the residual load onto b = K om_k AFTER the
+ * predictor (before it, it would flow into om), wf_leapfrog4_correct with s1c = 0.  Per step n < N the sensitivities are
+ *       stiffness cells:  dt2 (e_c(mu_n, u^n + w^n) + e_c(om_n, u^n))
+ *       pointwise:        p += mu_n (u^{n+1} - 2 u^n + u^{n-1}) + 12 om_n w^n       (the second term: through the 1/m inside w)
+ * with w^n the predictor's w of the forward step, and the mass sensitivity is the lumped-mass form of -p at the end.
+ * wf_leapfrog4_correlate: for i < n
+ *       p[i] = (p[i] + lam[i] * ((up[i] - 2.0*u[i]) + um[i])) + 12.0 * (om[i] * w[i])
+ *       z[i] = u[i] + w[i]                                        (d_z may be NULL: no store)
+ *   evaluated as written (no fused multiply-add), so the 16-byte and the scalar form of the sweep give the same bits.
+ *   z is the right operand of the step's first cell form.  64 B/dof of HBM traffic, 72 with z.  Refused (WF_ERR_INVALID,
+ *   nothing written): a null vector other than d_z; p or z overlapping an input or each other.  The inputs may overlap
+ *   each other.  n <= 0 is a no-op. */
 int wf_leapfrog_correlate(int64_t n, const double* d_lam, const double* d_up, const double* d_u, const double* d_um, double* d_p,
                           void* stream);
+int wf_leapfrog4_correlate(int64_t n, const double* d_lam, const double* d_om, const double* d_up, const double* d_u,
+                           const double* d_um, const double* d_w, double* d_p, double* d_z, void* stream);
 int wf_sources_add_values(const wf_sources* src, const double* d_values, double scale, double* d_b, void* stream);
 
 /* ---- the time loops of the wave model (csrc/wave_source.h, csrc/wave_loops.cpp; host code over the entries above) ----
- * The one copy of rk4_fused and leapfrog: LinearGLLOpt of wave_fenics_amd/linear_gll.py and of wavehip_linear_gll.hpp
+ * The one copy of rk4_fused, leapfrog and leapfrog4: LinearGLLOpt of wave_fenics_amd/linear_gll.py and of wavehip_linear_gll.hpp
  * both call these.
  *
  * wf_wave_source: the plane source on Gamma_1 (LinearGLL.hpp:153-162).  c0_squared is the caller's own c0^2: the Python
@@ -911,8 +970,8 @@ int wf_sources_add_values(const wf_sources* src, const double* d_values, double 
  * wf_wave_desc: what a loop works on.  The right-hand side b += K x is `rhs` when given (accumulate semantics, every
  *   launch on the stream it is handed), else the operator: wf_op_apply_overlapped(op, updater) when `overlapped`, else
  *   wf_updater_fwd(x) (with an updater), wf_op_apply, wf_updater_rev(b).  d_work points to wf_wave_work_vectors(scheme)
- *   device vectors of n doubles of the caller's, seven for WF_WAVE_RK4_FUSED and three for WF_WAVE_LEAPFROG, distinct
- *   from each other and from every other vector of the call.  Their contents on entry do not matter.
+ *   device vectors of n doubles of the caller's, seven for WF_WAVE_RK4_FUSED, three for WF_WAVE_LEAPFROG and four for
+ *   WF_WAVE_LEAPFROG4 (-1: an unknown scheme), distinct from each other and from every other vector of the call.  Their contents on entry do not matter.
  *   With receivers, row k of d_traces [trace_rows][npoints] receives u after step k (row 0: at t0) by wf_points_sample;
  *   h_times[k] (host, optional, with or without receivers) receives the time of that row.
  *
@@ -923,7 +982,24 @@ int wf_sources_add_values(const wf_sources* src, const double* d_values, double 
  *   u^{-1}, per step rhs, wf_sources_add, wf_leapfrog_step_bc, and one finishing apply for the central velocity.  s1 is
  *   wf_wave_s1.  before_step (optional) is called before step k = 0, 1, ... with the time and the two states the step
  *   reads; d_a0 holds the start-up acceleration b / m at k = 0 only.  The loop's launches do not depend on it.
- * Both read the state d_u, d_v on entry and leave the result there; the forward ghost update of the result is the
+ * wf_wave_leapfrog4: the fourth-order loop (wf_leapfrog4_predict has the step), state (u, v) in and out as
+ *   wf_wave_leapfrog, constant step, the last step not shortened, steps counted as wf_wave_step_count counts
+ *   WF_WAVE_LEAPFROG; receivers record u at t0 and after every step.  Derivatives of the loads are central differences at
+ *   t +- dt: the plane source through wf_boundary_apply_plan with the differenced s1 (wf_wave_s1), the point sources
+ *   through wf_sources_add_stencil.
+ *   Start-up (three applies): a0 = (K u0 + L(t0) - d v0)/m, j0 = (K v0 + L'(t0) - d a0)/m, q0 = (K a0 + L''(t0) - d j0)/m,
+ *     u^{-1} = u0 - dt v0 + dt^2/2 a0 - dt^3/6 j0 + dt^4/24 q0.
+ *   Finish (three applies): one more full step out of place gives vt = (u^{n+1} - u^{n-1})/(2 dt) and
+ *     at = (u^{n+1} - 2 u^n + u^{n-1})/dt^2; then j = (K vt + L'(t) - d at)/m and v = vt - dt^2/6 j.  u is not advanced.
+ *   A run split in two equals the continuous run to truncation order (the start-up is a Taylor series, not the inverse
+ *   of the finish), not to rounding.
+ *   before_step(user, n, t, u^{n-1}, u^n, d_startup ? d_startup[0] : NULL, stream) (optional) is called before step
+ *   n = 0, 1, ... as wf_wave_leapfrog calls its own (not before the finishing step); it may copy the vectors, a non-zero
+ *   return ends the loop with WF_ERR_INVALID.  d_startup, if not NULL, holds three vectors of n doubles that receive a0,
+ *   j0 and q0 of the start-up (a copy after each is formed: the loop overwrites a0 with q0).  The loop's other launches
+ *   and their order depend on neither.  Refused before the first launch: what wf_wave_leapfrog refuses, and a null entry
+ *   of d_startup.
+ * All three read the state d_u, d_v on entry and leave the result there; the forward ghost update of the result is the
  *   caller's.  max_steps < 0: no limit; otherwise the loop ends after the step that makes steps >= max_steps.  t_end and
  *   steps (host, optional) receive the time reached and the steps taken.  All launches go to `stream`; nothing is
  *   allocated, freed or synchronised.  Refused before the first launch (WF_ERR_INVALID): a null descriptor, state, work,
@@ -940,7 +1016,7 @@ double wf_wave_s1(const wf_wave_source* p, double t);
 double wf_wave_s1_left_to_right(const wf_wave_source* p, double t);
 double wf_wave_s2(const wf_wave_source* p);
 
-enum { WF_WAVE_RK4_FUSED = 0, WF_WAVE_LEAPFROG = 1 };
+enum { WF_WAVE_RK4_FUSED = 0, WF_WAVE_LEAPFROG = 1, WF_WAVE_LEAPFROG4 = 2 };
 typedef int (*wf_wave_rhs_fn)(void* user, double* d_x, double* d_b, void* stream);
 typedef int (*wf_wave_step_fn)(void* user, int64_t step, double t, const double* d_u_prev, const double* d_u, const double* d_a0,
                                void* stream);
@@ -969,6 +1045,9 @@ int wf_wave_rk4_fused(const wf_wave_desc* desc, double t0, double tf, double dt,
                       double* t_end, int64_t* steps, void* stream);
 int wf_wave_leapfrog(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
                      wf_wave_step_fn before_step, void* before_step_user, double* t_end, int64_t* steps, void* stream);
+int wf_wave_leapfrog4(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
+                      wf_wave_step_fn before_step, void* before_step_user, double* const* d_startup, double* t_end,
+                      int64_t* steps, void* stream);
 
 #ifdef __cplusplus
 }

@@ -26,7 +26,6 @@
 #include <vector>
 
 #include "wavehip.h"
-#include "wavehip_adjoint4.h"
 
 namespace wavehip {
 
@@ -566,7 +565,7 @@ inline void leapfrog_correlate(std::int64_t n, const double* d_lam, const double
 }
 
 /// p = (p + lam * ((up - 2 u) + um)) + 12 (om * w) and, with d_z, z = u + w over n entries, evaluated as written
-/// (wf_leapfrog4_correlate, wavehip_adjoint4.h): the per-step terms of the fourth-order leapfrog loop's discrete adjoint.
+/// (wf_leapfrog4_correlate): the per-step terms of the fourth-order leapfrog loop's discrete adjoint.
 /// p and z must not overlap an input or each other.
 inline void leapfrog4_correlate(std::int64_t n, const double* d_lam, const double* d_om, const double* d_up, const double* d_u,
                                 const double* d_um, const double* d_w, double* d_p, double* d_z = nullptr, void* stream = nullptr)

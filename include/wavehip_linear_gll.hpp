@@ -20,7 +20,6 @@
 #include <memory>
 
 #include "wavehip_box.hpp"
-#include "wavehip_leapfrog4.h"
 
 namespace wavehip {
 
@@ -332,7 +331,7 @@ public:
   /// (wf_leapfrog4_predict, wf_leapfrog4_correct) per step, fourth order in time, stable for dt <= sqrt(12/lambda_max),
   /// sqrt(3) times leapfrog's limit.  The centred absorbing term stays second order.  Constant step, counted as
   /// leapfrog() counts; a split run equals a continuous one to truncation order, not to rounding.
-  /// The loop is wf_wave_leapfrog4 (wavehip_leapfrog4.h), the one the Python model runs.
+  /// The loop is wf_wave_leapfrog4, the one the Python model runs.
   int leapfrog4(double& startTime, double& finalTime, double& timeStep, std::int64_t max_steps = -1)
   {
     return run(WF_WAVE_LEAPFROG4, startTime, finalTime, timeStep, max_steps);
@@ -342,7 +341,6 @@ protected:
   /// one call of a loop of the library on (u_n, v_n): the descriptor, the work vectors and the trace rows
   int run(int scheme, double t0, double tf, double dt, std::int64_t max_steps)
   {
-    const bool fourth = scheme == WF_WAVE_LEAPFROG4;   // its own count of work vectors (wavehip_leapfrog4.h)
     wf_wave_desc d{};
     d.n = N_;
     d.d_m = m->data();
@@ -364,14 +362,14 @@ protected:
     }
     std::vector<std::unique_ptr<array<double>>> work;
     std::vector<double*> work_ptr;
-    for (int k = 0; k < (fourth ? wf_wave_leapfrog4_work_vectors() : wf_wave_work_vectors(scheme)); ++k) {
+    for (int k = 0; k < wf_wave_work_vectors(scheme); ++k) {
       work.push_back(std::make_unique<array<double>>((std::size_t)N_));
       work_ptr.push_back(work.back()->data());
     }
     d.d_work = work_ptr.data();
     std::int64_t steps = 0;
-    if (fourth)
-      check(wf_wave_leapfrog4(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, &steps, nullptr));
+    if (scheme == WF_WAVE_LEAPFROG4)
+      check(wf_wave_leapfrog4(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, nullptr, nullptr, nullptr, &steps, nullptr));
     else if (scheme == WF_WAVE_LEAPFROG)
       check(wf_wave_leapfrog(&d, t0, tf, dt, max_steps, u_n->data(), v_n->data(), nullptr, nullptr, nullptr, &steps, nullptr));
     else

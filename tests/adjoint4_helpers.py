@@ -7,7 +7,7 @@ limit sqrt(12 / lambda_max(-M^-1 K)) so that the dt^4 terms weigh, and `observed
 under THIS loop.  The loop is leapfrog4_helpers.leapfrog4 restated so that it keeps what the adjoint reads (u^n, w^n,
 a0, j0, q0, the traces); `forward` equals that stepper bit for bit in float64 (asserted by the host test).
 
-Notation (include/wavehip_leapfrog4.h): A+- = m +- h, h = hdt c2, d = -s2 c2, c12 = dt2/12.  Step n:
+Notation (wf_leapfrog4_predict in include/wavehip.h): A+- = m +- h, h = hdt c2, d = -s2 c2, c12 = dt2/12.  Step n:
     b1 = K u^n + F1^n,  u* = the leapfrog update,  w^n = c12 b1/m,  u^{n+1} = u* + dt2 (K w^n + F2^n)/A+
 The adjoint, r^k = traces[k] - observed[k], J = 1/2 dt sum_{n <= N} |r^n|^2:
     mu_N = mu_{N+1} = 0,   om_k = c12 (K mu_k)/m,

@@ -2,7 +2,7 @@
 wf_leapfrog4_predict / wf_leapfrog4_correct in long double with their derived bounds, and a numpy stepper of
 LinearGLLOpt.leapfrog4 (start-up, steps, finish) over the parts of leapfrog_helpers.
 
-The expressions (include/wavehip_leapfrog4.h), with dt2 = dt*dt, hdt = (-s2)*(0.5*dt), tdt = 2*dt and c12 = dt2/12 rounded
+The expressions (include/wavehip.h), with dt2 = dt*dt, hdt = (-s2)*(0.5*dt), tdt = 2*dt and c12 = dt2/12 rounded
 once each in float64 by the host (the references take the host's float64 values as exact inputs):
 
   predictor   u_star:        the two expressions of leapfrog_helpers (plain_update, boundary_update)

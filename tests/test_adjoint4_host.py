@@ -129,7 +129,7 @@ def test_refusals_that_need_no_device(wpackage):
 
 
 def test_loop_with_a_hook_refuses_before_any_launch(wpackage):
-    """wf_wave_leapfrog4_steps on the made-up descriptors of test_wave_loops_host.py: the refusals of wf_wave_leapfrog4
+    """wf_wave_leapfrog4 with a hook on the made-up descriptors of test_wave_loops_host.py: its refusals without one,
     under its name, and a null entry of d_startup; a refused call writes nothing and calls no hook"""
     import ctypes
 
@@ -142,8 +142,8 @@ def test_loop_with_a_hook_refuses_before_any_launch(wpackage):
     def call(d, startup, u=wl.FAKE + 0x7000, dt=1.0):
         t_end, steps = ctypes.c_double(-1.0), ctypes.c_int64(-1)
         kept = None if startup is None else (ctypes.c_void_p * 3)(*startup)
-        rc = L.wf_wave_leapfrog4_steps(None if d is None else ctypes.byref(d), 0.0, 4.5, dt, -1, u, wl.FAKE + 0x8000, hook, None, kept,
-                                       ctypes.byref(t_end), ctypes.byref(steps), None)
+        rc = L.wf_wave_leapfrog4(None if d is None else ctypes.byref(d), 0.0, 4.5, dt, -1, u, wl.FAKE + 0x8000, hook, None, kept,
+                                 ctypes.byref(t_end), ctypes.byref(steps), None)
         assert t_end.value == -1.0 and steps.value == -1 and not called
         return rc, L.wf_last_error().decode()
 
@@ -158,6 +158,5 @@ def test_loop_with_a_hook_refuses_before_any_launch(wpackage):
     assert call(wl.descriptor(_lib), good, dt=0.0) == (wl.INVALID, "wf_wave_leapfrog4: the time step must be positive")
     for k in range(3):
         startup = [None if j == k else good[j] for j in range(3)]
-        assert call(wl.descriptor(_lib), startup) == (wl.INVALID, "wf_wave_leapfrog4_steps: null start-up vector"), k
-    assert set(_lib.SIGNATURES_ADJOINT4) == {"wf_leapfrog4_correlate", "wf_wave_leapfrog4_steps"}
-    assert not set(_lib.SIGNATURES_ADJOINT4) & (set(_lib.SIGNATURES) | set(_lib.SIGNATURES_LEAPFROG4))
+        assert call(wl.descriptor(_lib), startup) == (wl.INVALID, "wf_wave_leapfrog4: null start-up vector"), k
+    assert {"wf_leapfrog4_correlate", "wf_wave_leapfrog4"} <= set(_lib.SIGNATURES)

@@ -1,4 +1,4 @@
-"""wf_leapfrog4_correlate (csrc/adjoint4.hip, include/wavehip_adjoint4.h) entry by entry against long double, in
+"""wf_leapfrog4_correlate (csrc/adjoint4.hip, include/wavehip.h) entry by entry against long double, in
 sentinel-guarded buffers (guard_helpers), and the C++ wrapper's program against Python bit for bit.
 
 The bound is derived, not measured; eps = 2^-52, one rounding = eps / 2, the library evaluates as written:

@@ -45,7 +45,7 @@ def same(a, b):
 
 
 def launches(N, S, s=1):
-    """info["launches"] as the docstring of LinearGLLOpt._misfit_gradient4 states it"""
+    """info["launches"] as the docstring of LinearGLLOpt._backward_leapfrog4 states it"""
     ncp = -(-N // S)
     return 36 + 6 * s + N * (5 + 2 * s) + 2 * ncp + (N * (4 + 2 * s) + 5 * N + 3 * (N - 1) + 8 if N > 0 else 0)
 
@@ -203,7 +203,10 @@ def test_refusals_come_before_the_first_launch(gpu):
         eqn.misfit_gradient(*args, sc.observed, scheme="leapfrog4")
     eqn.receivers = rec
     untouched()
-    from wave_fenics_amd._lib import WF_WAVE_LEAPFROG4
-    with pytest.raises(ValueError):                       # the public route of the loop still refuses a callback
-        eqn._run(WF_WAVE_LEAPFROG4, *args, None, keep=lambda *a: None)
+    from wave_fenics_amd._lib import WF_WAVE_LEAPFROG, WF_WAVE_RK4_FUSED
+    with pytest.raises(ValueError):                       # what the library does not have: a hook in rk4_fused ...
+        eqn._run(WF_WAVE_RK4_FUSED, *args, None, keep=lambda *a: None)
+    untouched()
+    with pytest.raises(ValueError):                       # ... and start-up derivatives of another loop than leapfrog4
+        eqn._run(WF_WAVE_LEAPFROG, *args, None, startup=(eqn.u, eqn.v, eqn.b))
     untouched()

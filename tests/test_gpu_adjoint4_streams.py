@@ -1,20 +1,17 @@
-"""The stream-taking entries of include/wavehip_adjoint4.h behind work on a side stream, built with stream_helpers.py as
-tests/test_gpu_leapfrog4_streams.py builds its rows (tests/test_stream_table.py parses include/wavehip.h alone, so these
-rows stand here).
+"""The stream-taking entries that the adjoint of the fourth-order leapfrog loop uses (include/wavehip.h) behind work on a
+side stream, built with stream_helpers.py as tests/test_gpu_leapfrog4_streams.py builds its rows; REFERENCED of
+tests/test_gpu_stream_order.py points here.
 
 Rows: wf_leapfrog4_correlate with and without z, each 16-byte aligned and shifted by 8 bytes (n = 513: two full
 workgroups of pairs and the odd last dof).  Every input and in/out vector is NaN until the side stream, behind the load,
 copies the values in; the call follows at once and must return while the load is still running; the outputs are compared
 bit for bit with the same call on the default stream afterwards.
 
-The loop: five steps of wf_wave_leapfrog4_steps with a hook that keeps every pair, and the start-up derivatives, on
+The loop: five steps of wf_wave_leapfrog4 with a hook that keeps every pair, and the start-up derivatives, on
 adjoint_helpers.device_model (P2, two-layer medium, a point source, four receivers, all faces absorbing, the owner
 stiffness kernel) at leapfrog4's step: u_n, v_n, the traces, a0, j0, q0 and the kept states bit for bit against a twin
 model on the default stream.  Then one misfit_gradient(scheme="leapfrog4") the same way; it returns J as a host number,
 so it waits for its own stream and is not held to returning early (as test_gpu_stream_models.py holds leapfrog's)."""
-import os
-import re
-
 import numpy as np
 import pytest
 
@@ -23,6 +20,7 @@ import adjoint_helpers as ah
 import stream_helpers as sh
 import test_gpu_stream_models as sm
 import test_gpu_stream_order as so
+import test_stream_table
 from support import bits, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +28,7 @@ pytestmark = pytest.mark.gpu
 N = so.N
 FIRST = 300           # the factor of row k is stream_helpers.factor(FIRST + k): no case of another module shares it
 ROWS = []             # (id, entries, builder(gpu, s, rng, request) -> case)
-STREAM_ENTRIES = {"wf_leapfrog4_correlate", "wf_wave_leapfrog4_steps"}
+STREAM_ENTRIES = {"wf_leapfrog4_correlate", "wf_wave_leapfrog4"}
 INPUTS = ("lam", "om", "up", "u", "um", "w")
 
 
@@ -52,18 +50,13 @@ for _z in (True, False):
 
 
 def test_every_stream_entry_of_the_header_is_covered():
-    """the parser of tests/test_stream_table.py on include/wavehip_adjoint4.h: every prototype with a `void* stream` has
-    a row here or is the loop test_loop_with_a_hook_behind_queued_work runs"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "include", "wavehip_adjoint4.h")) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    names = [m.group(1) for m in re.finditer(r"\bint\s+(wf_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
-             if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2))]
-    assert set(names) == STREAM_ENTRIES and len(names) == 2
-    assert {e for _, entries, _ in ROWS for e in entries} | {"wf_wave_leapfrog4_steps"} == STREAM_ENTRIES
+    """STREAM_ENTRIES are declared with a `void* stream` in include/wavehip.h (the parser of tests/test_stream_table.py),
+    and each has a row here or is the loop test_loop_with_a_hook_behind_queued_work runs"""
+    assert STREAM_ENTRIES <= set(test_stream_table.stream_entries())
+    assert {e for _, entries, _ in ROWS for e in entries} | {"wf_wave_leapfrog4"} == STREAM_ENTRIES
     assert len({r[0] for r in ROWS}) == len(ROWS)
     from wave_fenics_amd import _lib
-    assert set(_lib.SIGNATURES_ADJOINT4) == STREAM_ENTRIES and not set(_lib.SIGNATURES_ADJOINT4) & set(_lib.SIGNATURES)
+    assert STREAM_ENTRIES <= set(_lib.SIGNATURES)
 
 
 @pytest.mark.parametrize("k", range(len(ROWS)), ids=[r[0] for r in ROWS])
@@ -110,7 +103,7 @@ def _twin_run(gpu, sc, s, run, names, what, pending):
 
 
 def test_loop_with_a_hook_behind_queued_work(gpu, oracle):
-    """five steps of wf_wave_leapfrog4_steps: the hook copies u^{n-1} and u^n of every step on the stream it is handed"""
+    """five steps of wf_wave_leapfrog4: the hook copies u^{n-1} and u^n of every step on the stream it is handed"""
     import torch
     from wave_fenics_amd import la
     from wave_fenics_amd._lib import WF_WAVE_LEAPFROG4
@@ -129,13 +122,13 @@ def test_loop_with_a_hook_behind_queued_work(gpu, oracle):
             la.copy(u, pair[1])
             kept.extend(pair)
 
-        t, steps = eqn._loop(WF_WAVE_LEAPFROG4, 0.0, tf, sc.dt, None, hook, startup=startup)
+        t, steps = eqn._run(WF_WAVE_LEAPFROG4, 0.0, tf, sc.dt, None, keep=hook, startup=startup)
         assert steps == sm.STEPS and [k for k, _ in seen] == list(range(sm.STEPS)) and seen[0][1] == 0.0
         assert [tt for _, tt in seen] + [t] == list(eqn.trace_times)[-(sm.STEPS + 1):]
         return startup + kept
 
     names = ["u_n", "v_n", "traces", "a0", "j0", "q0"] + [f"kept{i}" for i in range(2 * sm.STEPS)]
-    _twin_run(gpu, sc, sh.factor(FIRST + len(ROWS)), run, names, "wf_wave_leapfrog4_steps", pending=True)
+    _twin_run(gpu, sc, sh.factor(FIRST + len(ROWS)), run, names, "wf_wave_leapfrog4 with a hook", pending=True)
 
 
 def test_misfit_gradient_behind_queued_work(gpu, oracle):

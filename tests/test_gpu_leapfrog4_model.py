@@ -264,7 +264,7 @@ def test_stable_beyond_leapfrog(gpu, oracle):
 def test_energy_on_the_device(gpu, oracle):
     """the module docstring's energy test; also the rhs= callback path of the loop (the torch transport's)"""
     import torch
-    from wave_fenics_amd._lib import WF_WAVE_LEAPFROG4
+    from wave_fenics_amd._lib import WF_WAVE_LEAPFROG, WF_WAVE_LEAPFROG4, WF_WAVE_RK4_FUSED
     from wave_fenics_amd.linear_gll import LinearGLLOpt
     p, N = 2, 200
     n, hi = BOXES[p]
@@ -289,8 +289,10 @@ def test_energy_on_the_device(gpu, oracle):
     assert steps == N and len(seen) == 3 + 2 * N + 3
     hist = [seen[3 + 2 * k].cpu().numpy() for k in range(N + 1)]
     assert np.array_equal(bits(hist[0]), bits(u0)) and np.array_equal(bits(hist[N]), bits(eqn.u_n.cpu().numpy()))
-    with pytest.raises(ValueError):
-        eqn._run(WF_WAVE_LEAPFROG4, 0.0, 1.0, dt, 1, keep=lambda *a: None)
+    with pytest.raises(ValueError):                       # what the library does not have: a hook in rk4_fused ...
+        eqn._run(WF_WAVE_RK4_FUSED, 0.0, 1.0, dt, 1, keep=lambda *a: None)
+    with pytest.raises(ValueError):                       # ... and start-up derivatives of another loop than leapfrog4
+        eqn._run(WF_WAVE_LEAPFROG, 0.0, 1.0, dt, 1, startup=(eqn.u, eqn.v, eqn.b))
 
     class Closed:
         m, mG1, mG2 = ref.m, np.zeros_like(ref.m), np.zeros_like(ref.m)

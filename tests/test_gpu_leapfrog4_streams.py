@@ -1,6 +1,5 @@
-"""The stream-taking entries of include/wavehip_leapfrog4.h behind work on a side stream, built with stream_helpers.py
-exactly as tests/test_gpu_stream_order.py builds its rows (tests/test_stream_table.py parses include/wavehip.h alone, so
-these rows stand here), and five steps of LinearGLLOpt.leapfrog4 behind the load as tests/test_gpu_stream_models.py runs
+"""The stream-taking entries of the fourth-order leapfrog (include/wavehip.h) behind work on a side stream, built with
+stream_helpers.py exactly as tests/test_gpu_stream_order.py builds its rows (its REFERENCED points here), and five steps of LinearGLLOpt.leapfrog4 behind the load as tests/test_gpu_stream_models.py runs
 the other loops.
 
 Rows: wf_leapfrog4_predict with and without a plan, wf_leapfrog4_correct with and without a plan and v, each 16-byte
@@ -18,6 +17,7 @@ import adjoint_helpers as ah
 import stream_helpers as sh
 import test_gpu_stream_models as sm
 import test_gpu_stream_order as so
+import test_stream_table
 from support import bits, gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -86,16 +86,10 @@ ROWS.append(("sources_add_stencil", ("wf_sources_add_stencil",), stencil_row))
 
 
 def test_every_stream_entry_of_the_header_is_covered():
-    """the parser of tests/test_stream_table.py on include/wavehip_leapfrog4.h: every prototype with a `void* stream` has
-    a row here or is the loop test_model_behind_queued_work runs"""
-    import os
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "include", "wavehip_leapfrog4.h")) as f:
-        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
-    names = [m.group(1) for m in re.finditer(r"\bint\s+(wf_\w+)\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
-             if re.search(r"\bvoid\s*\*\s*stream\b", m.group(2))]
-    assert set(names) == STREAM_ENTRIES
+    """STREAM_ENTRIES are declared with a `void* stream` in include/wavehip.h (the parser of tests/test_stream_table.py),
+    and each has a row here or is the loop test_model_behind_queued_work runs"""
+    from wave_fenics_amd import _lib
+    assert STREAM_ENTRIES <= set(test_stream_table.stream_entries()) and STREAM_ENTRIES <= set(_lib.SIGNATURES)
     assert {e for _, entries, _ in ROWS for e in entries} | {"wf_wave_leapfrog4"} == STREAM_ENTRIES
     assert len({r[0] for r in ROWS}) == len(ROWS)
 

@@ -71,7 +71,13 @@ REFERENCED = {"wf_tsmm": "tests/test_gpu_tsmm_paths.py (every plan path behind q
               "wf_cg": "tests/test_gpu_cg_iteration.py::test_cg_on_side_stream; the row `cg-synchronises` here",
               "wf_wave_rk4_fused": "tests/test_gpu_stream_models.py (rk4_fused behind queued work, one rank and a z-periodic partition)",
               "wf_wave_leapfrog": "tests/test_gpu_stream_models.py (leapfrog and misfit_gradient behind queued work, one rank and a "
-                                  "z-periodic partition)"}
+                                  "z-periodic partition)",
+              "wf_leapfrog4_predict": "tests/test_gpu_leapfrog4_streams.py::test_stream_order (rows leapfrog4_predict*)",
+              "wf_leapfrog4_correct": "tests/test_gpu_leapfrog4_streams.py::test_stream_order (rows leapfrog4_correct*)",
+              "wf_sources_add_stencil": "tests/test_gpu_leapfrog4_streams.py::test_stream_order (row sources_add_stencil)",
+              "wf_leapfrog4_correlate": "tests/test_gpu_adjoint4_streams.py::test_stream_order (rows leapfrog4_correlate*)",
+              "wf_wave_leapfrog4": "tests/test_gpu_leapfrog4_streams.py::test_model_behind_queued_work (leapfrog4, no hook) and "
+                                   "tests/test_gpu_adjoint4_streams.py::test_loop_with_a_hook_behind_queued_work (hook and start-up)"}
 ROWS = []             # (id, entries, builder(gpu, s, rng, request) -> case)
 
 

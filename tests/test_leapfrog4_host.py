@@ -338,13 +338,13 @@ def test_refusals_before_any_device_call():
         assert Lb.wf_leapfrog4_correct(nn, dt, None, None, None, None, None, None, None, 0.0, 0.0, None) == 0
     two = (ctypes.c_double * 3)(0.0, 1.0, 2.0)
     assert Lb.wf_sources_add_stencil(None, 1, two, two, p["b"], None) == -1 and b"handle" in Lb.wf_last_error()
-    assert Lb.wf_wave_leapfrog4_work_vectors() == 4 and Lb.wf_wave_work_vectors(2) == -1
+    assert Lb.wf_wave_work_vectors(2) == 4
     desc = _lib.WaveDesc()
     st = (ctypes.c_double(0.0), ctypes.c_int64(0))
-    assert Lb.wf_wave_leapfrog4(None, 0.0, 1.0, 0.1, -1, p["u"], p["v"], ctypes.byref(st[0]), ctypes.byref(st[1]), None) == -1
-    assert Lb.wf_wave_leapfrog4(ctypes.byref(desc), 0.0, 1.0, 0.1, -1, None, p["v"], None, None, None) == -1
+    assert Lb.wf_wave_leapfrog4(None, 0.0, 1.0, 0.1, -1, p["u"], p["v"], _lib.WAVE_STEP_FN(), None, None, ctypes.byref(st[0]), ctypes.byref(st[1]), None) == -1
+    assert Lb.wf_wave_leapfrog4(ctypes.byref(desc), 0.0, 1.0, 0.1, -1, None, p["v"], _lib.WAVE_STEP_FN(), None, None, None, None, None) == -1
     assert b"wf_wave_leapfrog4" in Lb.wf_last_error()
     work = (ctypes.c_void_p * 4)(p["u"], p["up"], p["us"], None)         # the fourth work vector is asked for
     desc.n, desc.d_work = n, work
-    assert Lb.wf_wave_leapfrog4(ctypes.byref(desc), 0.0, 1.0, 0.1, -1, p["u"], p["v"], None, None, None) == -1
+    assert Lb.wf_wave_leapfrog4(ctypes.byref(desc), 0.0, 1.0, 0.1, -1, p["u"], p["v"], _lib.WAVE_STEP_FN(), None, None, None, None, None) == -1
     assert b"null work" in Lb.wf_last_error()

@@ -24,9 +24,10 @@ def stream_entries():
 def test_header_is_parsed():
     """the count of today, so that a change of the header's style that hides prototypes from the parser shows"""
     names = stream_entries()
-    assert len(names) == len(set(names)) >= 38
+    assert len(names) == len(set(names)) >= 45
     for known in ("wf_memset", "wf_sync", "wf_op_apply", "wf_tsmm", "wf_rk4_stage_bc", "wf_leapfrog_step_bc", "wf_updater_rev_end",
-                  "wf_op_apply_overlapped", "wf_cg", "wf_cell_form_eval", "wf_sources_add_values", "wf_leapfrog_correlate"):
+                  "wf_op_apply_overlapped", "wf_cg", "wf_cell_form_eval", "wf_sources_add_values", "wf_leapfrog_correlate",
+                  "wf_leapfrog4_predict", "wf_leapfrog4_correct", "wf_sources_add_stencil", "wf_leapfrog4_correlate", "wf_wave_leapfrog4"):
         assert known in names, known
     assert "wf_matvec_fn" not in names          # a callback type, not an entry
 

@@ -40,8 +40,7 @@ def call(wlib, entry, d, u=FAKE + 0x7000, v=FAKE + 0x8000, t0=0.0, tf=4.5, dt=1.
     if entry == "wf_wave_leapfrog":
         rc = L.wf_wave_leapfrog(*args, wlib.WAVE_STEP_FN(), None, ctypes.byref(t_end), ctypes.byref(steps), None)
     elif entry == "wf_wave_leapfrog4":
-        assert entry in wlib.SIGNATURES_LEAPFROG4 and entry not in wlib.SIGNATURES      # the second table of _lib.py
-        rc = L.wf_wave_leapfrog4(*args, ctypes.byref(t_end), ctypes.byref(steps), None)
+        rc = L.wf_wave_leapfrog4(*args, wlib.WAVE_STEP_FN(), None, None, ctypes.byref(t_end), ctypes.byref(steps), None)
     else:
         rc = L.wf_wave_rk4_fused(*args, ctypes.byref(t_end), ctypes.byref(steps), None)
     assert t_end.value == -1.0 and steps.value == -1       # a refused call writes nothing
@@ -120,7 +119,7 @@ def parent_steps(scheme, t0, tf, dt, max_steps):
 
 def test_step_count(wlib):
     L = wlib.lib()
-    schemes = {"rk4_fused": wlib.WF_WAVE_RK4_FUSED, "leapfrog": wlib.WF_WAVE_LEAPFROG}
+    schemes = {"rk4_fused": wlib.WF_WAVE_RK4_FUSED, "leapfrog": wlib.WF_WAVE_LEAPFROG, "leapfrog4": wlib.WF_WAVE_LEAPFROG4}
     dt = 1.2345e-8
     runs = [(0.0, 5 * dt - 1e-13, dt), (0.0, 5 * dt, dt), (0.0, 5 * dt + 1e-13, dt), (2 * dt, 5 * dt - 1e-13, dt), (0.0, 0.3, 0.1),
             (0.0, 0.1 + 0.1 + 0.1, 0.1), (0.0, 1.0, 0.1), (1.0, 1.0, 0.1), (2.0, 1.0, 0.1), (0.0, 1.0e9, dt), (0.0, 0.25 * dt, dt),
@@ -137,9 +136,8 @@ def test_step_count(wlib):
                 seen.add(want)
     assert {0, 1, 3, 5, 1000, 1001} <= seen, sorted(seen)
     assert L.wf_wave_work_vectors(wlib.WF_WAVE_RK4_FUSED) == 7 and L.wf_wave_work_vectors(wlib.WF_WAVE_LEAPFROG) == 3
-    assert L.wf_wave_work_vectors(2) == -1 and L.wf_wave_work_vectors(-1) == -1
-    # the fourth-order leapfrog has its own count (include/wavehip_leapfrog4.h); scheme 2 stays unknown to the first
-    assert wlib.WF_WAVE_LEAPFROG4 == 2 and L.wf_wave_leapfrog4_work_vectors() == WORK_VECTORS["wf_wave_leapfrog4"] == 4
+    assert wlib.WF_WAVE_LEAPFROG4 == 2 and L.wf_wave_work_vectors(wlib.WF_WAVE_LEAPFROG4) == WORK_VECTORS["wf_wave_leapfrog4"] == 4
+    assert L.wf_wave_work_vectors(3) == -1 and L.wf_wave_work_vectors(-1) == -1
 
 
 def test_descriptor_layout(wlib, tmp_path):

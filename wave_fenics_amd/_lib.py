@@ -135,8 +135,7 @@ class WaveDesc(ctypes.Structure):
     ]
 
 
-WF_WAVE_RK4_FUSED, WF_WAVE_LEAPFROG = 0, 1
-WF_WAVE_LEAPFROG4 = 2   # include/wavehip_leapfrog4.h
+WF_WAVE_RK4_FUSED, WF_WAVE_LEAPFROG, WF_WAVE_LEAPFROG4 = 0, 1, 2
 WF_QUAD_GLL, WF_QUAD_GAUSS_JACOBI = 0, 1
 WF_VARIANT_GLL_WARPED, WF_VARIANT_EQUISPACED = 0, 1
 WF_MAX_QUAD_POINTS = 16
@@ -218,6 +217,8 @@ SIGNATURES = {
     "wf_rk4_stage_bc": (c_int, [c_int64, c_double, c_double, c_int] + [c_void_p] * 11 + [c_void_p, c_double, c_double, c_void_p]),
     "wf_leapfrog_step": (c_int, [c_int64, c_double] + [c_void_p] * 7),
     "wf_leapfrog_step_bc": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
+    "wf_leapfrog4_predict": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
+    "wf_leapfrog4_correct": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
     "wf_comm_unique_id": (c_int, [c_char_p]),
     "wf_comm_create": (c_int, [c_char_p, c_int, c_int, POINTER(c_void_p)]),
     "wf_comm_rendezvous_file": (c_int, [c_char_p, c_int, c_double, c_char_p]),
@@ -273,7 +274,9 @@ SIGNATURES = {
     "wf_sources_destroy": (c_int, [c_void_p]),
     "wf_sources_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "wf_sources_add": (c_int, [c_void_p, c_double, c_void_p, c_void_p]),
+    "wf_sources_add_stencil": (c_int, [c_void_p, c_int, _DP, _DP, c_void_p, c_void_p]),
     "wf_leapfrog_correlate": (c_int, [c_int64] + [c_void_p] * 6),
+    "wf_leapfrog4_correlate": (c_int, [c_int64] + [c_void_p] * 9),
     "wf_sources_add_values": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
     "wf_cell_form_create": (c_int, [POINTER(OpDesc), POINTER(c_void_p)]),
     "wf_cell_form_create_box": (c_int, [c_int, c_int, c_int, c_int, c_int, _DP, c_double, _DP, c_int, POINTER(Tuning),
@@ -292,24 +295,8 @@ SIGNATURES = {
                                   POINTER(c_double), POINTER(c_int64), c_void_p]),
     "wf_wave_leapfrog": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p, WAVE_STEP_FN,
                                  c_void_p, POINTER(c_double), POINTER(c_int64), c_void_p]),
-}
-
-# every symbol include/wavehip_leapfrog4.h declares (the fourth-order leapfrog): a table of its own beside SIGNATURES,
-# which mirrors include/wavehip.h alone
-SIGNATURES_LEAPFROG4 = {
-    "wf_leapfrog4_predict": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
-    "wf_leapfrog4_correct": (c_int, [c_int64, c_double] + [c_void_p] * 6 + [c_void_p, c_double, c_double, c_void_p]),
-    "wf_sources_add_stencil": (c_int, [c_void_p, c_int, _DP, _DP, c_void_p, c_void_p]),
-    "wf_wave_leapfrog4_work_vectors": (c_int, []),
-    "wf_wave_leapfrog4": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p,
-                                  POINTER(c_double), POINTER(c_int64), c_void_p]),
-}
-
-# every symbol include/wavehip_adjoint4.h declares (the discrete adjoint of the fourth-order leapfrog loop), likewise
-SIGNATURES_ADJOINT4 = {
-    "wf_leapfrog4_correlate": (c_int, [c_int64] + [c_void_p] * 9),
-    "wf_wave_leapfrog4_steps": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p, WAVE_STEP_FN,
-                                        c_void_p, POINTER(c_void_p), POINTER(c_double), POINTER(c_int64), c_void_p]),
+    "wf_wave_leapfrog4": (c_int, [POINTER(WaveDesc), c_double, c_double, c_double, c_int64, c_void_p, c_void_p, WAVE_STEP_FN,
+                                  c_void_p, POINTER(c_void_p), POINTER(c_double), POINTER(c_int64), c_void_p]),
 }
 
 _LIB = None
@@ -332,7 +319,7 @@ def lib():
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **SIGNATURES_LEAPFROG4, **SIGNATURES_ADJOINT4}.items():
+        for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)          # AttributeError if the library lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

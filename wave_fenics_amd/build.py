@@ -19,7 +19,7 @@ SOURCES = [
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "device_array.h"), os.path.join(CSRC, "op.h"), os.path.join(CSRC, "box_mesh.h"),
            os.path.join(CSRC, "stiffness_core.h"), os.path.join(CSRC, "cell_batch.h"), os.path.join(CSRC, "stiffness_elementwise.h"),
            os.path.join(CSRC, "march_column.h"), os.path.join(CSRC, "box_run_plan.h"), os.path.join(CSRC, "box_items.h"), os.path.join(CSRC, "unique_lists.h"), os.path.join(CSRC, "march_plan.h"), os.path.join(CSRC, "dense_simplex.h"), os.path.join(CSRC, "owner_pieces.h"), os.path.join(CSRC, "points_plan.h"), os.path.join(CSRC, "points_handles.h"), os.path.join(CSRC, "sweep.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "tsmm_plan.h"), os.path.join(CSRC, "wave_source.h"),
-           os.path.join(ROOT, "include", "wavehip.h"), os.path.join(ROOT, "include", "wavehip_leapfrog4.h"), os.path.join(ROOT, "include", "wavehip_adjoint4.h")]
+           os.path.join(ROOT, "include", "wavehip.h")]
 
 
 def hipcc() -> str:

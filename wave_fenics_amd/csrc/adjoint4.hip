@@ -1,5 +1,5 @@
 // The pass the discrete adjoint of the fourth-order leapfrog loop adds (LinearGLLOpt.misfit_gradient(scheme="leapfrog4"),
-// include/wavehip_adjoint4.h), in a translation unit of its own: neighbours in a unit change code generation.
+// wf_leapfrog4_correlate of include/wavehip.h), in a translation unit of its own: neighbours in a unit change code generation.
 //
 // k_leapfrog4_correlate: p[i] = (p[i] + lam[i] * ((up[i] - 2 u[i]) + um[i])) + 12 (om[i] * w[i]) and, if asked for,
 //   z[i] = u[i] + w[i].  The first product is that of k_leapfrog_correlate (adjoint.hip); the second is the derivative
@@ -10,7 +10,7 @@
 //   follow, lam by the corrector half of the adjoint step.
 #include "common.h"
 #include "sweep.h"
-#include "wavehip_adjoint4.h"
+#include "wavehip.h"
 
 namespace wf {
 

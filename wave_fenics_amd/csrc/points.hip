@@ -15,7 +15,7 @@
 #include "device_array.h"
 #include "points_handles.h"
 #include "points_plan.h"
-#include "wavehip_leapfrog4.h"
+#include "wavehip.h"
 
 namespace wf {
 

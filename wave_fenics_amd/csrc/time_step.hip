@@ -8,7 +8,7 @@
 
 #include "device_array.h"
 #include "sweep.h"
-#include "wavehip_leapfrog4.h"
+#include "wavehip.h"
 
 namespace wf {
 

@@ -7,8 +7,6 @@
 
 #include "wave_source.h"
 #include "wavehip.h"
-#include "wavehip_adjoint4.h"
-#include "wavehip_leapfrog4.h"
 
 namespace wf {
 void set_error(const std::string& msg);                     // tables.cpp
@@ -16,8 +14,8 @@ void set_error(const std::string& msg);                     // tables.cpp
 
 namespace {
 
-constexpr int kWorkVectors[2] = {7, 3};                     // WF_WAVE_RK4_FUSED, WF_WAVE_LEAPFROG
-constexpr int kWorkVectorsLeapfrog4 = 4;                    // wf_wave_leapfrog4: u^n, u^{n-1}, the corrector's operand, a scratch
+// by scheme; WF_WAVE_LEAPFROG4: u^n, u^{n-1}, the corrector's operand, a scratch
+constexpr int kWorkVectors[3] = {7, 3, 4};
 constexpr double a_runge[4] = {0.0, 0.5, 0.5, 1.0};
 constexpr double b_runge[4] = {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0};
 constexpr double c_runge[4] = {0.0, 0.5, 0.5, 1.0};
@@ -46,13 +44,13 @@ double stage_time(double t, double c, double dt)
   } while (0)
 
 int check_call(const std::string& who, int scheme, const wf_wave_desc* d, double t0, double tf, double dt, int64_t max_steps,
-               const double* d_u, const double* d_v, int nwork = -1)
+               const double* d_u, const double* d_v)
 {
   WF_REFUSE_UNLESS(d, who + ": null descriptor");
   WF_REFUSE_UNLESS(d->n >= 0, who + ": n < 0");
   WF_REFUSE_UNLESS(d_u && d_v, who + ": null state");
   WF_REFUSE_UNLESS(d->d_work, who + ": null work");
-  for (int k = 0; k < (nwork < 0 ? kWorkVectors[scheme] : nwork); ++k) WF_REFUSE_UNLESS(d->d_work[k], who + ": null work");
+  for (int k = 0; k < kWorkVectors[scheme]; ++k) WF_REFUSE_UNLESS(d->d_work[k], who + ": null work");
   WF_REFUSE_UNLESS(d->d_m && d->d_b && d->bc, who + ": null m, b or boundary plan");
   WF_REFUSE_UNLESS(d->rhs || d->op, who + ": needs an operator handle or a right-hand-side callback");
   WF_REFUSE_UNLESS(d->rhs || !d->overlapped || d->updater, who + ": overlapped needs an updater");
@@ -114,7 +112,7 @@ double wf_wave_s1(const wf_wave_source* p, double t) { return wf::wave_s1(*p, t)
 double wf_wave_s1_left_to_right(const wf_wave_source* p, double t) { return wf::wave_s1_left_to_right(*p, t); }
 double wf_wave_s2(const wf_wave_source* p) { return wf::wave_s2(*p); }
 
-int wf_wave_work_vectors(int scheme) { return scheme == WF_WAVE_RK4_FUSED || scheme == WF_WAVE_LEAPFROG ? kWorkVectors[scheme] : -1; }
+int wf_wave_work_vectors(int scheme) { return scheme >= WF_WAVE_RK4_FUSED && scheme <= WF_WAVE_LEAPFROG4 ? kWorkVectors[scheme] : -1; }
 
 int64_t wf_wave_step_count(int scheme, double t0, double tf, double dt, int64_t max_steps)
 {
@@ -246,20 +244,12 @@ int wf_wave_leapfrog(const wf_wave_desc* desc, double t0, double tf, double dt, 
   return WF_OK;
 }
 
-int wf_wave_leapfrog4_work_vectors(void) { return kWorkVectorsLeapfrog4; }
-
 int wf_wave_leapfrog4(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
-                      double* t_end, int64_t* steps, void* stream)
+                      wf_wave_step_fn before_step, void* before_step_user, double* const* d_startup, double* t_end,
+                      int64_t* steps, void* stream)
 {
-  return wf_wave_leapfrog4_steps(desc, t0, tf, dt, max_steps, d_u, d_v, nullptr, nullptr, nullptr, t_end, steps, stream);
-}
-
-int wf_wave_leapfrog4_steps(const wf_wave_desc* desc, double t0, double tf, double dt, int64_t max_steps, double* d_u, double* d_v,
-                            wf_wave_step_fn before_step, void* before_step_user, double* const* d_startup, double* t_end,
-                            int64_t* steps, void* stream)
-{
-  WF_TRY(check_call("wf_wave_leapfrog4", WF_WAVE_LEAPFROG, desc, t0, tf, dt, max_steps, d_u, d_v, kWorkVectorsLeapfrog4));
-  for (int k = 0; d_startup && k < 3; ++k) WF_REFUSE_UNLESS(d_startup[k], "wf_wave_leapfrog4_steps: null start-up vector");
+  WF_TRY(check_call("wf_wave_leapfrog4", WF_WAVE_LEAPFROG4, desc, t0, tf, dt, max_steps, d_u, d_v));
+  for (int k = 0; d_startup && k < 3; ++k) WF_REFUSE_UNLESS(d_startup[k], "wf_wave_leapfrog4: null start-up vector");
   // the start-up derivative just formed in `from`, for the caller (the discrete adjoint reads a0, j0, q0)
   auto keep_startup = [&](int k, const double* from) { return d_startup ? wf_copy(desc->n, from, d_startup[k], stream) : WF_OK; };
   const wf_wave_desc& d = *desc;
@@ -327,7 +317,7 @@ int wf_wave_leapfrog4_steps(const wf_wave_desc* desc, double t0, double tf, doub
   WF_TRY(wf_fill(n, 0.0, b, stream));
   while (t < tf) {
     if (before_step && before_step(before_step_user, step, t, p, u, d_startup ? d_startup[0] : nullptr, stream) != WF_OK) {
-      wf::set_error("wf_wave_leapfrog4_steps: per-step callback failed");
+      wf::set_error("wf_wave_leapfrog4: per-step callback failed");
       return WF_ERR_INVALID;
     }
     WF_TRY(advance(t, p, p, nullptr));

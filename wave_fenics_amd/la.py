@@ -91,7 +91,7 @@ def leapfrog_step(b, m, u, u_prev, u_next, dt: float, v=None, bc=None, s1: float
 
 
 def leapfrog4_predict(b, m, u, u_prev, u_star, w, dt: float, bc=None, s1: float = 0.0, s2: float = 0.0):
-    """The first pass of a fourth-order leapfrog step (wf_leapfrog4_predict, include/wavehip_leapfrog4.h): b holds K u on
+    """The first pass of a fourth-order leapfrog step (wf_leapfrog4_predict, include/wavehip.h): b holds K u on
     entry and +0.0 on return, u_star = what leapfrog_step stores in u_next, w = (dt^2/12) b/m (with bc the dofs of its
     sets take s1 c1 into b first).  u_star may be u_prev."""
     check(lib().wf_leapfrog4_predict(b.numel(), float(dt), _ptr(b), _ptr(m), _ptr(u), _ptr(u_prev), _ptr(u_star), _ptr(w),
@@ -114,7 +114,7 @@ def leapfrog_correlate(lam, up, u, um, p):
 
 def leapfrog4_correlate(lam, om, up, u, um, w, p, z=None):
     """p = (p + lam * ((up - 2 u) + um)) + 12 (om * w) and, with z, z = u + w, evaluated as written
-    (wf_leapfrog4_correlate, include/wavehip_adjoint4.h); p and z must not overlap an input or each other."""
+    (wf_leapfrog4_correlate, include/wavehip.h); p and z must not overlap an input or each other."""
     check(lib().wf_leapfrog4_correlate(p.numel(), _ptr(lam), _ptr(om), _ptr(up), _ptr(u), _ptr(um), _ptr(w), _ptr(p),
                                        _ptr(z) if z is not None else 0, _stream(p)))
 

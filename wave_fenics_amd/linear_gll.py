@@ -341,7 +341,7 @@ class LinearGLLOpt:
         Taylor series, not the inverse of the finish.
 
         The step is constant and the last step is not shortened, as in leapfrog().  Returns (t, steps).  The loop itself is
-        wf_wave_leapfrog4 (csrc/wave_loops.cpp, include/wavehip_leapfrog4.h)."""
+        wf_wave_leapfrog4 (csrc/wave_loops.cpp)."""
         return self._run(WF_WAVE_LEAPFROG4, startTime, finalTime, timeStep, max_steps)
 
     def _guarded(self, errors, body):
@@ -361,24 +361,21 @@ class LinearGLLOpt:
                 return -1
         return call
 
-    def _run(self, scheme: int, t0: float, tf: float, dt: float, max_steps, keep=None, rhs=None, work=None):
+    def _run(self, scheme: int, t0: float, tf: float, dt: float, max_steps, keep=None, rhs=None, work=None, startup=None):
         """One call of wf_wave_rk4_fused / wf_wave_leapfrog / wf_wave_leapfrog4 on (u_n, v_n), by scheme: the
         descriptor, the work vectors and the trace rows are set up here, every launch is the library's.
-        keep(n, t, u_prev, u, a0) (leapfrog alone, refused with another scheme; misfit_gradient) is called before step
-        n = 0, 1, ... with the time and the two states the step reads (a0: the vector holding the start-up acceleration,
-        valid at n = 0 only).  It may copy them; the loop's own launches and their order do not
-        depend on it.  For tests: rhs(x, b), a right-hand side b += K x in place of the model's, and work, the work vectors
-        (wf_wave_work_vectors of them) in place of fresh ones."""
-        if keep is not None and scheme != WF_WAVE_LEAPFROG:
-            raise ValueError("LinearGLLOpt._run: keep= is the per-step callback of wf_wave_leapfrog alone")
-        return self._loop(scheme, t0, tf, dt, max_steps, keep, rhs, work)
-
-    def _loop(self, scheme: int, t0: float, tf: float, dt: float, max_steps, keep=None, rhs=None, work=None, startup=None):
-        """The call behind _run.  With WF_WAVE_LEAPFROG4 and keep or startup (three vectors that receive a0, j0, q0) the loop
-        is wf_wave_leapfrog4_steps (include/wavehip_adjoint4.h), whose keep is called as leapfrog's (its last argument is
-        startup[0] or None); without either it is wf_wave_leapfrog4."""
+        keep(n, t, u_prev, u, a0) (the two leapfrog loops; misfit_gradient) is called before step n = 0, 1, ... with the
+        time and the two states the step reads; a0 is the vector holding the start-up acceleration, valid at n = 0 only
+        (leapfrog), or startup[0] or None (leapfrog4).  It may copy them; the loop's own launches and their order do not
+        depend on it.  startup (leapfrog4 alone): three vectors that receive a0, j0, q0 of the start-up.  For tests:
+        rhs(x, b), a right-hand side b += K x in place of the model's, and work, the work vectors (wf_wave_work_vectors of
+        them) in place of fresh ones.  Raises ValueError before any launch for what the library does not have: keep= with
+        WF_WAVE_RK4_FUSED, startup= with another scheme than WF_WAVE_LEAPFROG4."""
+        if keep is not None and scheme == WF_WAVE_RK4_FUSED:
+            raise ValueError("LinearGLLOpt._run: keep= is the per-step callback of the leapfrog loops; wf_wave_rk4_fused has none")
+        if startup is not None and scheme != WF_WAVE_LEAPFROG4:
+            raise ValueError("LinearGLLOpt._run: startup= are the start-up derivatives of wf_wave_leapfrog4 alone")
         L, n, errors = lib(), self.u_n.numel(), []
-        fourth = scheme == WF_WAVE_LEAPFROG4
         vec = lambda p: la._tensor_from_ptr(p, n, self.device) if p else None   # noqa: E731
         d = WaveDesc()
         d.n, d.d_m, d.d_b, d.bc = n, _ptr(self.m), _ptr(self.b), self._bc._h
@@ -403,8 +400,7 @@ class LinearGLLOpt:
             if len(rec):
                 d.receivers, d.d_traces = rec._h, rec.reserve(rows, self.device)
         if work is None:
-            nwork = L.wf_wave_leapfrog4_work_vectors() if fourth else L.wf_wave_work_vectors(scheme)
-            work = [torch.empty_like(self.u_n) for _ in range(nwork)]
+            work = [torch.empty_like(self.u_n) for _ in range(L.wf_wave_work_vectors(scheme))]
         d.d_work = (ctypes.c_void_p * len(work))(*[_ptr(x) for x in work])
         t_end, steps = ctypes.c_double(t0), ctypes.c_int64(0)
         args = (ctypes.byref(d), t0, tf, dt, max_steps, _ptr(self.u_n), _ptr(self.v_n))
@@ -413,11 +409,9 @@ class LinearGLLOpt:
         if keep is not None:
             call_keep = self._guarded(errors, lambda k, t, pw, pu, pa: keep(k, t, vec(pw), vec(pu), vec(pa)))
             step_fn = WAVE_STEP_FN(lambda user, k, t, pw, pu, pa, stream: call_keep(stream, k, t, pw, pu, pa))
-        if fourth and (keep is not None or startup is not None):
+        if scheme == WF_WAVE_LEAPFROG4:
             kept = None if startup is None else (ctypes.c_void_p * 3)(*[_ptr(x) for x in startup])
-            rc = L.wf_wave_leapfrog4_steps(*args, step_fn, None, kept, *out)
-        elif fourth:
-            rc = L.wf_wave_leapfrog4(*args, *out)
+            rc = L.wf_wave_leapfrog4(*args, step_fn, None, kept, *out)
         elif scheme == WF_WAVE_LEAPFROG:
             rc = L.wf_wave_leapfrog(*args, step_fn, None, *out)
         else:
@@ -470,7 +464,7 @@ class LinearGLLOpt:
         bit-identical for every S and from call to call; where the apply adds by atomics they agree to rounding only.
 
         scheme="leapfrog4": the same for the fourth-order loop, the forward run being leapfrog4(t0, tf, dt, max_steps) --
-        _misfit_gradient4 says what differs.
+        _backward_leapfrog4 says what differs.
 
         Raises before the first launch: an unknown scheme, with updater=, without receivers, dt <= 0, observed of another
         shape, S < 1."""
@@ -493,17 +487,16 @@ class LinearGLLOpt:
         if isinstance(observed, np.ndarray):
             observed = torch.from_numpy(np.array(observed, dtype=np.float64))   # a copy: the caller's array may be read-only
         observed = observed.to(self.device, dtype=torch.float64)
+        fourth = scheme == "leapfrog4"
         ncp, Sb = -(-N // S), min(S, N)
-        if scheme == "leapfrog4":
-            return self._misfit_gradient4(t0, tf, dt, observed, N, S, max_steps)
-        b, m = self.b, self.m
         new = lambda: torch.empty_like(self.u_n)   # noqa: E731
-        pairs, times, a0 = [], [], new()
+        pairs, times = [], []
+        kept = [new() for _ in range(4 if fourth else 1)]   # a0; with leapfrog4 also j0, q0 (the loop hands all three out) and v0
 
         def keep(n, tn, u_prev, u, scratch):
             times.append(tn)
-            if n == 0:
-                la.copy(scratch, a0)
+            if n == 0 and not fourth:
+                la.copy(scratch, kept[0])
             if n % S == 0:
                 pair = (new(), new())
                 la.copy(u_prev, pair[0])
@@ -511,25 +504,56 @@ class LinearGLLOpt:
                 pairs.append(pair)
 
         row0 = rec._rows
-        t, steps = self._run(WF_WAVE_LEAPFROG, t0, tf, dt, max_steps, keep)
+        if fourth:
+            la.copy(self.v_n, kept[3])
+            t, steps = self._run(WF_WAVE_LEAPFROG4, t0, tf, dt, max_steps, keep, startup=kept[:3])
+        else:
+            t, steps = self._run(WF_WAVE_LEAPFROG, t0, tf, dt, max_steps, keep)
         assert steps == N and len(pairs) == ncp
         resid = rec.traces[row0:row0 + N + 1] - observed
         J = 0.5 * dt * float((resid * resid).sum().item())
-        ncells = self.V.mesh.ncells
-        g_stiff = torch.zeros(ncells, dtype=torch.float64, device=self.device)
+        g_stiff = torch.zeros(self.V.mesh.ncells, dtype=torch.float64, device=self.device)
         ns = 0 if src is None else 1
-        info = {"N": N, "S": S, "vectors": 2 * ncp + Sb + 5, "t": t, "steps": steps,
-                "launches": (8 + ns + (N > 0)) + N * (3 + ns) + (3 + ns) + 2 * ncp + N * (2 + ns) + 5 * N + 2 * (N > 0)}
+        if fourth:
+            vectors = 2 * ncp + 2 * Sb + 10
+            launches = 36 + 6 * ns + N * (5 + 2 * ns) + 2 * ncp + (N * (4 + 2 * ns) + 5 * N + 3 * (N - 1) + 8 if N > 0 else 0)
+        else:
+            vectors = 2 * ncp + Sb + 5
+            launches = (8 + ns + (N > 0)) + N * (3 + ns) + (3 + ns) + 2 * ncp + N * (2 + ns) + 5 * N + 2 * (N > 0)
+        info = {"N": N, "S": S, "vectors": vectors, "t": t, "steps": steps, "launches": launches}
         info["bytes"] = info["vectors"] * self.u_n.numel() * 8
         if N == 0:
             return J, g_stiff, torch.zeros_like(g_stiff), info
+        backward = self._backward_leapfrog4 if fourth else self._backward_leapfrog
+        g_mass = backward(dt, N, S, pairs, times, resid, kept, g_stiff)
+        if self.medium is not None:
+            g_stiff.div_(torch.from_numpy(np.ascontiguousarray(self.medium.stiff_coeff)).to(self.device))
+            g_mass.div_(torch.from_numpy(np.ascontiguousarray(self.medium.mass_coeff)).to(self.device))
+        return J, g_stiff, g_mass, info
+
+    def _receivers_transposed(self):
+        """the receivers as sources (their transpose), built once per Receivers object"""
+        if self._rec_T is None or self._rec_T[0] is not self.receivers:
+            self._rec_T = (self.receivers, self.receivers.transpose())
+        return self._rec_T[1]
+
+    def _absorbing_masses(self):
+        """c2: the facet masses mG2 scattered to the dofs, zero elsewhere"""
+        c2 = torch.zeros_like(self.u_n)
+        if self.idx2.numel():
+            c2.index_add_(0, self.idx2.long(), self.mG2)
+        return c2
+
+    def _backward_leapfrog(self, dt, N, S, pairs, times, resid, kept, g_stiff):
+        """The backward pass of misfit_gradient(scheme="leapfrog") behind the forward run (N > 0): accumulates
+        a^K_c g_stiff[c] into g_stiff and returns a^M_c g_mass[c].  kept = [a0]."""
+        src, b, m = self.sources, self.b, self.m
+        ncp, Sb = len(pairs), min(S, N)
         kform, mform = self.cell_forms()
-        if self._rec_T is None or self._rec_T[0] is not rec:
-            self._rec_T = (rec, rec.transpose())
-        RT = self._rec_T[1]
+        RT = self._receivers_transposed()
         bc, s1, s2, rhs = self._bc, self._s1, self._s2, self._rhs
         mu, mu_next, p = torch.zeros_like(self.u_n), torch.zeros_like(self.u_n), torch.zeros_like(self.u_n)
-        bufs = [new() for _ in range(Sb)]
+        bufs = [torch.empty_like(self.u_n) for _ in range(Sb)]
         for j in reversed(range(ncp)):
             n0, n1 = j * S, min((j + 1) * S, N)
             st = [pairs[j][0], pairs[j][1]] + bufs[:n1 - n0]          # st[i] = u^{n0 - 1 + i}
@@ -549,10 +573,8 @@ class LinearGLLOpt:
             if j > 0:
                 pairs[j] = None
         # start-up: u^{-1} = u^0 - dt v^0 + dt^2/2 a^0 depends on K and m; mu_next = (A-/m) mu_0
-        u0 = pairs[0][1]
-        h = torch.zeros_like(self.u_n)
-        if self.idx2.numel():
-            h.index_add_(0, self.idx2.long(), self.mG2)
+        u0, a0 = pairs[0][1], kept[0]
+        h = self._absorbing_masses()
         h.mul_((-s2) * (0.5 * dt))
         torch.sub(m, h, out=mu_next)
         mu_next.div_(m).mul_(mu)
@@ -562,14 +584,11 @@ class LinearGLLOpt:
         mu.fill_(1.0)
         g_mass = mform.eval(mu, p)
         g_stiff.mul_(dt * dt)
-        if self.medium is not None:
-            g_stiff.div_(torch.from_numpy(np.ascontiguousarray(self.medium.stiff_coeff)).to(self.device))
-            g_mass.div_(torch.from_numpy(np.ascontiguousarray(self.medium.mass_coeff)).to(self.device))
-        return J, g_stiff, g_mass, info
+        return g_mass
 
-    def _misfit_gradient4(self, t0: float, tf: float, dt: float, observed, N: int, S: int, max_steps):
-        """misfit_gradient(scheme="leapfrog4") behind its checks: the discrete adjoint of the leapfrog4 loop
-        (include/wavehip_adjoint4.h has the derivation in the loop's notation).  Step n is
+    def _backward_leapfrog4(self, dt, N, S, pairs, times, resid, kept, g_stiff):
+        """_backward_leapfrog for scheme="leapfrog4", kept = [a0, j0, q0, v0]: the discrete adjoint of the leapfrog4 loop
+        (wf_leapfrog4_correlate in include/wavehip.h has the derivation in the loop's notation).  Step n is
             b1 = K u^n + F1^n,  u* = the leapfrog update,  w^n = c12 b1/m,  A+ u^{n+1} = A+ u* + dt^2 (K w^n + F2^n),
         that is A+ u^{n+1} = dt^2 K' u^n + 2 m u^n - A- u^{n-1} + loads with K' = K + c12 K m^-1 K symmetric, and
             mu_N = mu_{N+1} = 0,   A+ mu_{k-1} = dt^2 (K mu_k + K om_k + R^T r^k / dt) + 2 m mu_k - A- mu_{k+1},   om_k = c12 (K mu_k)/m
@@ -589,39 +608,12 @@ class LinearGLLOpt:
         info["launches"] = 36 + 6 s + N (5 + 2 s) + 2 ceil(N/S), the forward run with its copies, and with N > 0 a further
         N (4 + 2 s) + 5 N + 3 (N - 1) + 8: the replays, the predictor halves with the step's terms, the corrector halves,
         and mu_{N-1} with the start-up terms (s = 1 with sources)."""
-        rec, src = self.receivers, self.sources
-        ncp, Sb = -(-N // S), min(S, N)
-        b, m = self.b, self.m
+        src, b, m = self.sources, self.b, self.m
+        ncp, Sb = len(pairs), min(S, N)
+        a0, j0, q0, v0 = kept
         new = lambda: torch.empty_like(self.u_n)   # noqa: E731
-        pairs, times = [], []
-        a0, j0, q0, v0 = new(), new(), new(), new()
-
-        def keep(n, tn, u_prev, u, _):
-            times.append(tn)
-            if n % S == 0:
-                pair = (new(), new())
-                la.copy(u_prev, pair[0])
-                la.copy(u, pair[1])
-                pairs.append(pair)
-
-        row0 = rec._rows
-        la.copy(self.v_n, v0)
-        t, steps = self._loop(WF_WAVE_LEAPFROG4, t0, tf, dt, max_steps, keep, startup=(a0, j0, q0))
-        assert steps == N and len(pairs) == ncp
-        resid = rec.traces[row0:row0 + N + 1] - observed
-        J = 0.5 * dt * float((resid * resid).sum().item())
-        ncells = self.V.mesh.ncells
-        g_stiff = torch.zeros(ncells, dtype=torch.float64, device=self.device)
-        ns = 0 if src is None else 1
-        info = {"N": N, "S": S, "vectors": 2 * ncp + 2 * Sb + 10, "t": t, "steps": steps,
-                "launches": 36 + 6 * ns + N * (5 + 2 * ns) + 2 * ncp + (N * (4 + 2 * ns) + 5 * N + 3 * (N - 1) + 8 if N > 0 else 0)}
-        info["bytes"] = info["vectors"] * self.u_n.numel() * 8
-        if N == 0:
-            return J, g_stiff, torch.zeros_like(g_stiff), info
         kform, mform = self.cell_forms()
-        if self._rec_T is None or self._rec_T[0] is not rec:
-            self._rec_T = (rec, rec.transpose())
-        RT = self._rec_T[1]
+        RT = self._receivers_transposed()
         bc, s1, s2, rhs = self._bc, self._s1, self._s2, self._rhs
         dt2 = dt * dt
         mu, mu_next, om = torch.zeros_like(self.u_n), torch.zeros_like(self.u_n), new()
@@ -672,9 +664,7 @@ class LinearGLLOpt:
         # start-up: u^{-1} = u0 - dt v0 + dt^2/2 a0 - dt^3/6 j0 + dt^4/24 q0 depends on K and m through a0, j0, q0.
         # mu holds mu_0; nu goes into mu_next, qh into om, jh into mu, ah into mu_next; z holds d
         u0 = pairs[0][1]
-        h = torch.zeros_like(self.u_n)
-        if self.idx2.numel():
-            h.index_add_(0, self.idx2.long(), self.mG2)
+        h = self._absorbing_masses()
         torch.mul(h, -s2, out=z)                                      # d = -s2 c2
         h.mul_((-s2) * (0.5 * dt))
         torch.sub(h, m, out=mu_next)
@@ -692,11 +682,7 @@ class LinearGLLOpt:
         p.addcmul_(om, q0).addcmul_(mu, j0).addcmul_(mu_next, a0)
         p.mul_(-1.0)
         z.fill_(1.0)
-        g_mass = mform.eval(z, p)
-        if self.medium is not None:
-            g_stiff.div_(torch.from_numpy(np.ascontiguousarray(self.medium.stiff_coeff)).to(self.device))
-            g_mass.div_(torch.from_numpy(np.ascontiguousarray(self.medium.mass_coeff)).to(self.device))
-        return J, g_stiff, g_mass, info
+        return mform.eval(z, p)
 
     def max_eigenvalue(self, iters: int = 100):
         """Largest eigenvalue of -M^{-1} K (lumped mass, the model's stiffness operator) by `iters` power iterations; the
